@@ -8,13 +8,18 @@ A "step" is one pass of the hot path over one synthetic batch that is already re
 Workload at N = 1: BASELINE.json configs[1] (simple_cnn, 36 logits = background + 35 Speech Commands v2 words,
 batch 4096, HIP featurizer + fwd/bwd + Adam).  Weak scaling: every rank keeps B = 4096.
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with
+Output: ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps, writes the
+outputs of the last timed step if --dump-outputs DIR is given, and prints the line: metric, value (clips/s), ms_per_step, config.final_loss (the loss of the last timed step).
+The figures below take runs of their own and are measured only with --full (null / empty otherwise):
   roofline      the step's dominant kernel, timed live with HIP events on its launch stream (kws_prof_*)
   cpu_baseline  the same step on the host cores: torch-CPU operators (stand-in for TF-Keras CPU, which this image lacks) behind
                 the C featurizer oracle, plus the rows SURVEY.md 8(d) lists (reference-plumbing numpy featurizer, bs 512 / 5 classes)
   extra         the other SURVEY.md 8(d) workloads measured in the same run (N = 1 only): featurize + simple_cnn inference forward
                 (the north star's HBM-roofline target), simple_gru train step, simple_cnn_lite fp16 hipGraph forward, the train
                 step with exact-fp32 MFMA products, and the dense head's matrix-core figures.
+--dump-outputs DIR writes, on rank 0, what the last timed step left to its caller as float32 .npy files (dump_outputs).  That step
+starts from the run's seeded starting point (see `start` in main), and its inputs (waveforms, labels, weights, dropout seed) are
+fixed by the arguments, so two runs or two builds can be compared output for output.
 """
 import argparse
 import json
@@ -104,6 +109,31 @@ def synthetic_batch(B, rank, n_classes):
         wav[b, :lead[b]] = 0.0
     labels = rng.integers(0, n_classes, B).astype(np.int32)
     return wav, labels
+
+
+DUMP_FEATURE_ROWS = 16384      # features.npy holds at most this many clips (39 MB); the other arrays are ~3 MB together
+
+
+def dump_outputs(out_dir, dm, feat):
+    """--dump-outputs: what the last timed step computed, as the caller of the step receives it, one float32 .npy per array:
+      params, state         weights after the step's Adam update / BatchNormalization moving statistics (Keras order, flat)
+      grads                 the step's gradient buffer (after the all-reduce when N > 1)
+      adam_m, adam_v        Adam's moment estimates after the update
+      stats                 [sum of the per-clip losses, top-1 hits] of the step's batch
+      features              the featurizer's output for the step's batch (B, 30, 20); above DUMP_FEATURE_ROWS clips a fixed
+                            seeded sample of rows, whose indices go to features_rows.npy"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"params": dm.params, "state": dm.state, "grads": dm.grads, "adam_m": dm.adam_m, "adam_v": dm.adam_v, "stats": dm.stats}
+    if feat.shape[0] > DUMP_FEATURE_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(feat.shape[0], DUMP_FEATURE_ROWS, replace=False))
+        feat = feat[torch.from_numpy(rows).to(feat.device)]
+        arrays["features_rows"] = torch.from_numpy(rows.astype(np.float64))
+    arrays["features"] = feat
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    log("outputs of the last timed step written to %s (%s)" % (out_dir, ", ".join(sorted(arrays))))
 
 
 def kernel_models(B, C):
@@ -530,10 +560,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=4096, help="per-GPU batch (weak scaling)")
-    ap.add_argument("--cpu-budget", type=float, default=16.0, help="seconds of CPU work for the cpu_baseline rows")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other SURVEY 8(d) workloads (extra.*)")
-    ap.add_argument("--profile-steps", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel times and roofline, the side workloads (extra.*), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--cpu-budget", type=float, default=16.0, help="(--full) seconds of CPU work for the cpu_baseline rows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the cpu_baseline rows")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the other SURVEY 8(d) workloads (extra.*)")
+    ap.add_argument("--profile-steps", type=int, default=10, help="(--full) steps of each per-kernel timing pass")
     ap.add_argument("--extra-only", nargs="?", const="all", default=None, choices=("all", "fit", "infer", "gru", "lite"),
                     help="(internal) run the SURVEY 8(d) side workloads (or one of them) and print their JSON")
     ap.add_argument("--force-comm", action="store_true",
@@ -611,21 +645,37 @@ def main():
     elif args.force_comm:
         comm = KwsComm.from_torch_group() if dist is not None else KwsComm.single()      # a one-rank world runs the same code
     step_no = [0]
+    last_feat = [None]                           # the feature buffer the most recent step read (--dump-outputs)
     overlap_ev = torch.cuda.Event()
+    # The run's seeded starting point (weights, BatchNorm moving statistics, zero Adam moments).  The step adds its reductions
+    # with atomics whose order varies from run to run, and training amplifies those last-bit differences: after a few tens of
+    # steps two runs' weights differ far beyond rounding.  The last timed step therefore starts from this point again, so that
+    # what it computes is the same in every run with the same arguments (four copies, 1.6 MB in all, once per run).
+    start = [t.clone() for t in (dm.params, dm.state, dm.adam_m, dm.adam_v)]
+
+    def restart():
+        for dst, src in zip((dm.params, dm.state, dm.adam_m, dm.adam_v), start):
+            dst.copy_(src)
+        dm.step_count = 0
+        dm.invalidate_prepared()
 
     def submit_next():
         pipe.submit(wav, after=overlap_ev)
 
-    def run_steps(n):
+    def run_steps(n, restart_last=False):
         # n complete train steps = n featurizations + n (fwd + bwd + all-reduce + Adam), all enqueued inside this call.
         # The features of batch k+1 are computed on a side stream while batch k trains (kws_amd/pipeline.py); the first
-        # batch of every call is not overlapped with anything.
+        # batch of every call is not overlapped with anything.  restart_last: the last step starts from `start` (stream order:
+        # behind the previous step's Adam, which waits for all of that step's gradients).
         if n <= 0:
             return
         pipe.submit(wav)
         for i in range(n):
+            if restart_last and i == n - 1:
+                restart()
             step_no[0] += 1
             feat, mom = pipe.take()
+            last_feat[0] = feat
             # next batch's features on the side stream, started at the step's overlap point (behind conv3's forward kernel, include/kws.h): the library
             # records overlap_ev there and calls back, so the featurizer launch also sits at that point in HOST order
             # data parallel: the step exchanges its gradients itself (kws_train_args.comm): the early bucket (conv4 + dense + head,
@@ -647,7 +697,7 @@ def main():
     fence()
     log("timed region: %d steps" % args.steps)
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    run_steps(args.steps, restart_last=True)
     fence()
     elapsed = time.perf_counter() - t0
     if dist is not None:
@@ -656,11 +706,13 @@ def main():
         elapsed = float(t.item())
     loss = float(dm.stats[0].item()) / B
     log("timed region done: %.4f ms/step" % (elapsed / args.steps * 1e3))
+    if args.dump_outputs and rank == 0 and last_feat[0] is not None:
+        dump_outputs(args.dump_outputs, dm, last_feat[0])       # before anything else runs a step
 
     # per-kernel timing on the launch stream (HIP events inside the library), separate from the timed region
     # (every rank runs these steps -- they contain the all-reduce -- but only rank 0 records and reports)
     roofline, breakdown, breakdown_serial, allreduce_us = None, {}, {}, None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         if rank == 0:
             L.prof_enable(True)
         run_steps(args.profile_steps)          # the same pipelined execution as the timed region
@@ -690,7 +742,7 @@ def main():
             for k, v in sorted(rep_serial.items(), key=lambda kv: -kv[1]["total_ms"]):
                 breakdown_serial[k] = round(v["total_ms"] / args.profile_steps, 4)
     dense_head = None
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and args.full and args.profile_steps > 0:
         models = kernel_models(B, N_CLASSES)
         tot = sum(v["total_ms"] for v in rep.values())
         name = max(rep, key=lambda k: rep[k]["total_ms"])
@@ -739,7 +791,7 @@ def main():
                       "mfma_busy_pmc": pmc}
 
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         # the headline step with exact-fp32 MFMA products everywhere (KWS_MATRIX_FP32), same pipeline
         log("extra: fp32 MFMA step")
         dm.set_precision(matrix=L.MATRIX_FP32)
@@ -770,11 +822,11 @@ def main():
         extra["fp32_mfma_step"] = {"workload": "the headline train step with every matrix product on v_mfma_f32_16x16x4_f32 (bit-exact fp32 fma chains)",
                                    "ms_per_step": round(ms32, 4), "clips_per_s": round(B / ms32 * 1e3, 1)}
         extra["dense_head_mfma"] = dense_head
-    elif rank == 0:
+    elif rank == 0 and args.full:
         extra = {"dense_head_mfma": dense_head}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_budget)
 
     if rank == 0:
@@ -782,7 +834,7 @@ def main():
         value = world * B * args.steps / elapsed
         out = {"metric": METRIC, "value": round(value, 1), "unit": "clips/s", "n_gpus": world, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
                "config": {"workload": "configs[1]: simple_cnn train step = featurize(f32 1 s @16 kHz) + fwd + bwd + Adam, "
                                       "36 logits (background + 35 words), batch %d per GPU" % B,
                           "global_batch": B * world, "parallelism": "dp%d" % world, "final_loss": round(loss, 4),

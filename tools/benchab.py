@@ -1,4 +1,5 @@
-"""Run bench.py against another build of the library: python tools/benchab.py <lib | -> [bench args]"""
+"""Run bench.py against another build of the library: python tools/benchab.py <lib | -> [bench args]
+(the per-kernel rows it prints are measured only with --full among the bench args)"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
