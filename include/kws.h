@@ -129,6 +129,69 @@ int kws_featurizer_set_cu_share(kws_featurizer *f, int blocks_per_cu);
 int kws_featurizer_occupancy(const kws_featurizer *f, int *blocks_per_cu, size_t *lds_bytes);
 
 /* ------------------------------------------------------------------------
+ * Background-noise augmentation of raw audio: the mix of tools/audio_process/add_noise.py:19-35, drawn afresh for every clip of every
+ * train step on the device instead of written once as *_noised.wav copies.  Per clip (voice v of valid length Lv, clipped to max_samples
+ * as the featurizer does):
+ *   noised:   L = min(Lv, seg_len[k]); p_v = mean(v[0:L]^2), p_n = mean(n_k[o:o+L]^2);
+ *             g = sqrt(p_v / 10^(s/10) / (p_n + FLT_EPSILON)); m[t] = v[t] + g n_k[o+t], t < L
+ *   otherwise m = v[0:Lv], L = Lv
+ *   time shift (no counterpart in the reference): m'[t] = m[t - d] where 0 <= t - d < L, else 0; length L
+ * m' is then featurized with the keep-head / left-pad rule on length L.  Divergences from the offline tool: no int16 quantisation or
+ * clipping of the mixed clip, the voice power is taken over the head the featurizer keeps, draws are fresh every step.
+ * ---------------------------------------------------------------------- */
+typedef struct kws_noise_bank kws_noise_bank;
+
+/* K recordings (add_noise.py: noise_files), concatenated on the HOST: samples[sum(seg_len)] of wav_dtype (int16 is scaled by 1/32768 as
+ * the featurizer does), seg_len[K] >= 1 each.  Uploads them with an fp64 prefix sum of squares (the power of any window in O(1)). */
+int kws_noise_bank_create(const void *samples, int wav_dtype, const int32_t *seg_len, int K, kws_noise_bank **out);
+void kws_noise_bank_destroy(kws_noise_bank *bank);
+/* host: number of segments, total samples, and (seg_len may be NULL) the K segment lengths */
+int kws_noise_bank_info(const kws_noise_bank *bank, int *K, int64_t *total, int32_t *seg_len);
+
+#define KWS_AUG_MAX_SNR 16
+typedef struct kws_augment_params {
+    float noised_rate;                 /* add_noise.py --noised_rate: fraction of clips noised, [0, 1] */
+    int32_t n_snr;                     /* 1..KWS_AUG_MAX_SNR */
+    float snr_db[KWS_AUG_MAX_SNR];     /* add_noise.py --snr: choice(snr_list) */
+    int32_t max_shift;                 /* time shift d uniform in [-max_shift, max_shift] samples; 0 = off */
+    int32_t max_samples;               /* the head the featurizer keeps (kws_geometry.max_samples) */
+    uint64_t seed;
+} kws_augment_params;
+
+/* one clip's augmentation (32 bytes, device memory) */
+typedef struct kws_aug_clip {
+    int32_t apply;        /* 1: noised */
+    int32_t segment;      /* k: choice(noise_files) */
+    int32_t offset;       /* o: start of the noise window in segment k */
+    int32_t shift;        /* d */
+    int32_t length;       /* L (filled by kws_augment_plan) */
+    float snr_db;         /* s: choice(snr_list) */
+    float gain;           /* g (filled by kws_augment_plan; 0 when not noised) */
+    int32_t voice_length; /* Lv (filled by kws_augment_plan) */
+} kws_aug_clip;
+
+/* Plan B clips, one wave per clip, no host synchronisation.  Clip b is row index[b] (device int32; NULL: row b) of wav (rows x stride)
+ * with valid_len[row] samples (device int32; NULL: stride).  Draws are counter-based, keyed by (params->seed, step) and indexed by the
+ * clip's global position position_base + b (a data-parallel shard plans with position_base = its first position): apply = u <
+ * noised_rate, k, s, o uniform in [0, seg_len[k] - L], d uniform in [-max_shift, max_shift].  explicit_plan (HOST, B records, or NULL):
+ * take apply / segment / offset / shift / snr_db from the caller instead (an offset past seg_len[k] - L is clamped to it); L, gain and
+ * voice_length are computed either way.  plan: B device records. */
+int kws_augment_plan(const kws_noise_bank *bank, const kws_augment_params *params, const void *wav, int wav_dtype, const int32_t *index,
+                     int B, int64_t stride, const int32_t *valid_len, int64_t position_base, int64_t step, kws_aug_clip *plan,
+                     const kws_aug_clip *explicit_plan, void *stream);
+
+/* Materialise the planned clips m' (what the model trains on): out (B x out_stride float32, out_stride >= max_samples) holds m'[0:L]
+ * head-aligned, zeros after; lengths (device int32 B, may be NULL) = L.  featurize(out, valid_len = lengths) equals
+ * kws_featurize_gather_augmented bit for bit. */
+int kws_augment_apply(const kws_noise_bank *bank, const kws_aug_clip *plan, const void *wav, int wav_dtype, const int32_t *index, int B,
+                      int64_t stride, int max_samples, float *out, int64_t out_stride, int32_t *lengths, void *stream);
+
+/* kws_featurize_gather of the planned clips m' (lengths from the plan; the plan must have been made with this featurizer's
+ * max_samples).  The default geometry mixes in the tuned kernel's sample loads; other geometries run apply + featurize. */
+int kws_featurize_gather_augmented(kws_featurizer *f, const void *wav, int wav_dtype, const int32_t *index, int B, int64_t stride,
+                                   const kws_noise_bank *bank, const kws_aug_clip *plan, float *feat, void *stream);
+
+/* ------------------------------------------------------------------------
  * Model: replaces the tf.keras objects built by classifier/model.py:14-46
  * get_model() (backbones classifier/models/cnn.py, rnn.py) and the work
  * Keras does inside model.fit / model.predict (train.py:75-92).

@@ -2,6 +2,8 @@
 
 Layout and cache format are the reference's: <dataset>/sounds/<class>/*.wav is featurized once into
 <dataset>/features/<class>/<uuid>.npy (float32, shape (n_features, feature_size, 1)); later runs load the cache.
+get_audio_dataset() loads the same clips as waveforms instead, for training on raw audio (featurized per step on the GPU, optionally
+with background noise mixed in: kws_amd.augment).
 The featurization itself is batched on the GPU (PCM16 wav decode with the stdlib, one kws_featurize launch per
 `batch` files) instead of the reference's serial per-file loop (:39-44)."""
 import glob
@@ -95,3 +97,48 @@ def get_dataset(dataset_path, class_names, val_split=None):
     if val_split:
         return split_data(x, y, val_split)
     return np.asarray(x), np.asarray(y), None, None
+
+
+def load_audio_samples(audio_path, class_names):
+    """-> x (N, max_samples) float32 head-aligned (the first max_samples of every clip, zeros after), lengths (N,) int32, labels (N,)
+    class names, in the order of get_sample_list: the layout extract_features hands the featurizer"""
+    sample_list = get_sample_list(audio_path, class_names)
+    x = np.zeros((len(sample_list), pr.max_samples), np.float32)
+    lengths = np.zeros((len(sample_list),), np.int32)
+    for j, s in enumerate(sample_list):
+        a = load_wav(s['file'])[:pr.max_samples]              # keep the head (common/data_utils.py:77)
+        x[j, :len(a)] = a
+        lengths[j] = len(a)
+    return x, lengths, [s['word'] for s in sample_list]
+
+
+def get_audio_dataset(dataset_path, class_names, val_split=None):
+    """Raw-audio counterpart of get_dataset: -> x_train, len_train, y_train, x_val, len_val, y_val with x (N, max_samples) float32
+    head-aligned waveforms and len (N,) int32 their valid lengths (KWSModel.fit(x, y, sample_lengths=len)); labels and the split rule
+    are get_dataset's (class index of the folder, shuffled val_split share).  Without val_split the val entries are None."""
+    x, lengths, words = load_audio_samples(os.path.join(dataset_path, 'sounds'), class_names)
+    y = np.array([class_names.index(w.lower()) for w in words], dtype=np.int64)
+    if val_split:
+        n_val = int(math_ceil(len(x) * val_split))
+        perm = np.random.permutation(len(x))
+        val, train = perm[:n_val], perm[n_val:]
+        return x[train], lengths[train], y[train], x[val], lengths[val], y[val]
+    return x, lengths, y, None, None, None
+
+
+def load_noise_bank(path):
+    """every *.wav under `path` (a folder, searched recursively, or one file) through load_wav -> list of float32 arrays, sorted by path:
+    the noise_files of tools/audio_process/add_noise.py; kws_amd.augment.NoiseBank uploads them"""
+    if os.path.isfile(path):
+        files = [path]
+    else:
+        files = sorted(glob.glob(os.path.join(path, '**', '*.wav'), recursive=True))
+    if not files:
+        raise ValueError('no .wav files found under ' + str(path))
+    out = []
+    for f in files:
+        a = load_wav(f)
+        if len(a) == 0:
+            raise ValueError('noise file %s is empty' % f)
+        out.append(a)
+    return out

@@ -272,7 +272,12 @@ class KWSModel(object):
         (kws_featurize_gather), features are gathered -- together with its labels and, for simple_cnn, the second moments of its features
         (kws_train_args.feat_moments); the side stream starts at the step's overlap point (overlap_event / overlap_callback).  Nothing
         on the host waits for the device inside an epoch.  `pipeline=False` runs the same arithmetic step by step on one stream
-        (bit-identical results in the deterministic gradient mode: tests/test_host_api_gpu.py)."""
+        (bit-identical results in the deterministic gradient mode: tests/test_host_api_gpu.py).
+
+        Raw audio only: `sample_lengths` (N,) is the valid length of every row (a shorter clip keeps its head and is left-padded with zeros
+        by the featurizer, as extract_features does); `augment` (kws_amd.augment.WaveAugment) mixes background noise into every training
+        clip, drawn afresh for every step (tools/audio_process/add_noise.py of the reference, done offline there).  Validation and
+        evaluate are never augmented."""
         import torch
         from kws_amd.parallel import DataParallel
         from kws_amd.pipeline import FeaturePipeline
@@ -280,6 +285,8 @@ class KWSModel(object):
         cw, ig = self._loss_args()
         dp = kwargs.pop("data_parallel", None) or DataParallel.for_device()    # injectable for tests (a forced one-rank world)
         pipelined = bool(kwargs.pop("pipeline", True))
+        augment = kwargs.pop("augment", None)
+        sample_lengths = kwargs.pop("sample_lengths", None)
         if dp.active:
             dp.broadcast_(dm.params)
             dp.broadcast_(dm.state)
@@ -289,6 +296,15 @@ class KWSModel(object):
         xd, is_audio = self._to_device_inputs(x)
         n = xd.shape[0]
         yd = self._labels(y, n)
+        if (augment is not None or sample_lengths is not None) and not is_audio:
+            raise ValueError("augment / sample_lengths need raw audio (N, samples) input, got features")
+        lens_d = None
+        if sample_lengths is not None:
+            lens_d = (sample_lengths if isinstance(sample_lengths, torch.Tensor) else torch.from_numpy(np.asarray(sample_lengths)))
+            lens_d = lens_d.reshape(-1).to(torch.int32).to(xd.device).contiguous()
+            if lens_d.numel() != n:
+                raise ValueError("%d sample lengths for %d clips" % (lens_d.numel(), n))
+        in_place = augment is not None or lens_d is not None        # stepwise too: featurize the batch's rows in place (lengths / augmentation)
         callbacks = list(callbacks or [])
         for cb in callbacks:
             cb.set_model(self)
@@ -326,18 +342,22 @@ class KWSModel(object):
             perm = perm.to(torch.int32)
             stats_all.zero_()
             seen = 0
+            step0 = self._global_step              # batch i of this epoch is step step0 + i + 1 (the augmentation's draw key)
 
             def shard_of(i):
                 idx = perm[i * batch_size:(i + 1) * batch_size]
                 if dp.active:
                     lo, hi, weight = dp.shard_plan(idx.numel())     # an empty shard (weight 0) still joins the collectives
-                    return idx[lo:hi], weight
-                return idx, None
+                    return idx[lo:hi], weight, lo
+                return idx, None, 0
 
             def submit(i, after=None):
-                idx, _ = shard_of(i)
+                idx, _, lo = shard_of(i)
                 if idx.numel() > 0:
-                    if is_audio:
+                    if is_audio and in_place:
+                        pipe.submit(wav=xd, valid_len=lens_d, index=idx, labels=yd, after=after, augment=augment, step=step0 + i + 1,
+                                    position_base=lo)
+                    elif is_audio:
                         pipe.submit(wav=xd, index=idx, labels=yd, after=after)
                     else:
                         pipe.submit(features=xd, index=idx, labels=yd, after=after)
@@ -345,7 +365,7 @@ class KWSModel(object):
             if pipe is not None:
                 submit(0)
             for i in range(steps):
-                idx, weight = shard_of(i)
+                idx, weight, lo = shard_of(i)
                 nloc = idx.numel()
                 self._global_step += 1
                 seed = (self._dropout_base << 20) + self._global_step * 64 + dp.rank
@@ -356,6 +376,9 @@ class KWSModel(object):
                         got = pipe.take()
                         feat, yb = got[0], got[-1]
                         mom = got[1] if len(got) == 3 else None
+                    elif in_place:
+                        feat = self._get_featurizer()(xd, valid_len=lens_d, index=idx, augment=augment, step=step0 + i + 1, position_base=lo)
+                        yb = yd.index_select(0, idx)
                     else:
                         xb = xd.index_select(0, idx)
                         feat, yb = self._features_of(xb, is_audio), yd.index_select(0, idx)

@@ -23,6 +23,7 @@
 
 #include "kws_common.h"
 #include "kws_device.h"
+#include "kws_augment.h"
 
 #ifndef KWS_FEAT_ABLATE
 #define KWS_FEAT_ABLATE 0
@@ -624,13 +625,14 @@ static size_t v3_smem_bytes(int chp, int waves)
     return (size_t)waves * 4 * (kV3Tile + TB * 64 + 64 + 4) + 4 * (size_t)(kTunedBands * kTunedCoefs + 64 * chp) + 8 * (size_t)(7 * 64 + 7 * 8 + 4 * 64) +
            4 * (size_t)round4(kTunedBands + 1);
 }
-template <typename WavT, int CHP, int WAVES>
-static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name, int bpc)
+template <typename WavT, int CHP, int WAVES, bool AUG = false>
+static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name, int bpc,
+                     const AugDev &aug = {})
 {
     const int cus = device_cus();
     const size_t smem = v3_smem_bytes(CHP, WAVES);
     if ((size_t)WAVES * 4 * kV3Tile > 65536) return fail(KWS_ERR_UNSUPPORTED, "wave tiles must sit in the first 64 KiB of LDS (M0 holds 16 address bits)");
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES>), (int)smem)) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, AUG>), (int)smem)) return rc;
     FeatDev dd = d;
     const long waves = (long)bpc * cus * WAVES;
     {
@@ -646,8 +648,12 @@ static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, c
     }
     const long jobs = (long)B * dd.jpc;
     const unsigned grid = (unsigned)std::min<long>((long)bpc * cus, (jobs + WAVES - 1) / WAVES);
-    KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES>), dim3(grid), dim3(WAVES * 64), smem, s, wav, stride,
-               valid_len, B, dd, feat);
+    if constexpr (AUG)
+        KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, true>), dim3(grid), dim3(WAVES * 64), smem, s, wav, stride,
+                   valid_len, B, dd, feat, aug);
+    else
+        KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES>), dim3(grid), dim3(WAVES * 64), smem, s, wav, stride,
+                   valid_len, B, dd, feat);
     KWS_LAUNCH_CHECK("featurize_fft1024_v3_kernel");
     return KWS_OK;
 }
@@ -657,23 +663,25 @@ static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, c
 #ifndef KWS_V3_ALONE_BLOCKS
 #define KWS_V3_ALONE_BLOCKS 2
 #endif
-template <typename WavT, int WAVES>
-static int launch_v3_chp(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name, int bpc)
+template <typename WavT, int WAVES, bool AUG = false>
+static int launch_v3_chp(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name, int bpc,
+                         const AugDev &aug = {})
 {
     switch (d.chp3) {
-    case 12: return launch_v3<WavT, 12, WAVES>(d, wav, B, stride, valid_len, feat, s, name, bpc);
-    case 16: return launch_v3<WavT, 16, WAVES>(d, wav, B, stride, valid_len, feat, s, name, bpc);
-    default: return launch_v3<WavT, 20, WAVES>(d, wav, B, stride, valid_len, feat, s, name, bpc);
+    case 12: return launch_v3<WavT, 12, WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
+    case 16: return launch_v3<WavT, 16, WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
+    default: return launch_v3<WavT, 20, WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
     }
 }
 // The kernel holds its per-lane twiddles in registers (110 registers: 4 waves per SIMD = 16 per CU).  With the chip to itself: two blocks of 8
 // waves per CU; beside a train step (kws_featurizer_set_cu_share(f, 1)): ONE block of 12 waves per CU, which leaves a quarter of the wave
 // slots and half of the LDS to the step's kernels.
-template <typename WavT>
-static int launch_v3_any(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name)
+template <typename WavT, bool AUG = false>
+static int launch_v3_any(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name,
+                         const AugDev &aug = {})
 {
-    if (d.blocks_per_cu == 1) return launch_v3_chp<WavT, kV3Waves>(d, wav, B, stride, valid_len, feat, s, name, 1);
-    return launch_v3_chp<WavT, KWS_V3_ALONE_WAVES>(d, wav, B, stride, valid_len, feat, s, name, KWS_V3_ALONE_BLOCKS);
+    if (d.blocks_per_cu == 1) return launch_v3_chp<WavT, kV3Waves, AUG>(d, wav, B, stride, valid_len, feat, s, name, 1, aug);
+    return launch_v3_chp<WavT, KWS_V3_ALONE_WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, KWS_V3_ALONE_BLOCKS, aug);
 }
 
 extern "C" {
@@ -1051,6 +1059,42 @@ int kws_featurize_gather(kws_featurizer *f, const void *wav, int wav_dtype, cons
     d.blocks_per_cu = f->blocks_per_cu;
     d.index = index;
     return launch_featurize(d, wav, wav_dtype, B, stride, valid_len, feat, stream);
+}
+
+int kws_featurize_gather_augmented(kws_featurizer *f, const void *wav, int wav_dtype, const int32_t *index, int B, int64_t stride,
+                                   const kws_noise_bank *bank, const kws_aug_clip *plan, float *feat, void *stream)
+{
+    if (!f || !feat || !bank || (B > 0 && (!wav || !plan))) return fail(KWS_ERR_INVALID, "null argument");
+    if (B < 0 || stride < 0) return fail(KWS_ERR_INVALID, "negative batch or stride");
+    if (bank->K < 1) return fail(KWS_ERR_INVALID, "empty noise bank");
+    if (wav_dtype != KWS_WAV_F32 && wav_dtype != KWS_WAV_I16) return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
+    if (B == 0) return KWS_OK;
+    FeatDev d = f->dev;
+    d.blocks_per_cu = f->blocks_per_cu;
+    d.index = index;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (d.n_fft == 1024) {
+        feat_job_shape(d);
+        if (v3_applies(d)) {       // the default geometry: the mix happens in the tuned kernel's sample loads
+            const AugDev aug{plan, bank->samples, bank->d_start};
+            if (wav_dtype == KWS_WAV_F32)
+                return launch_v3_any<float, true>(d, static_cast<const float *>(wav), B, stride, nullptr, feat, s, "featurize_fft1024_aug_f32", aug);
+            return launch_v3_any<short, true>(d, static_cast<const short *>(wav), B, stride, nullptr, feat, s, "featurize_fft1024_aug_i16", aug);
+        }
+    }
+    // other geometries: materialise the clips (stream-ordered scratch), then the plain featurizer on them with valid_len = L
+    const int ms = f->dev.max_samples;
+    float *tmp = nullptr;
+    KWS_HIP_CHECK(hipMallocAsync(reinterpret_cast<void **>(&tmp), sizeof(float) * (size_t)B * ms + sizeof(int32_t) * (size_t)B, s));
+    int32_t *lens = reinterpret_cast<int32_t *>(tmp + (size_t)B * ms);
+    int rc = augment_apply_launch(bank, plan, wav, wav_dtype, index, B, stride, ms, tmp, ms, lens, s);
+    if (rc == KWS_OK) {
+        d = f->dev;
+        d.blocks_per_cu = f->blocks_per_cu;
+        rc = launch_featurize(d, tmp, KWS_WAV_F32, B, ms, lens, feat, stream);
+    }
+    KWS_HIP_CHECK(hipFreeAsync(tmp, s));
+    return rc;
 }
 
 int kws_featurize(kws_featurizer *f, const void *wav, int wav_dtype, int B, int64_t stride, const int32_t *valid_len,

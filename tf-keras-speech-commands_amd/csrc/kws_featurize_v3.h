@@ -222,13 +222,27 @@ __device__ __forceinline__ void v3_store_power(const float (&pk)[4], const float
                  :: "v"(pk[0]), "v"(pk[1]), "v"(pk[2]), "v"(pk[3]), "v"(p256), "v"(pm[0]), "v"(pm[1]), "v"(pm[2]), "v"(pm[3]), "s"(m0) : "memory");
 }
 
+// Background-noise augmentation (AUG = true, kws_featurize_gather_augmented): the samples of clip b are those of the planned clip m'
+// (kws_augment.h: aug_sample, the function the apply kernel materialises them with), built in the sample loads; the clip's length is the
+// plan's L.  The AUG = false instantiation is the plain kernel, unchanged.
+template <typename WavT, int J0>
+__device__ __forceinline__ void aug_load_half(float2 (&v)[4], const WavT *__restrict__ src, const float *__restrict__ nz, int L, int d, float g,
+                                              bool noised, int base, int pad, int lane)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = base + 2 * (lane + 64 * (J0 + j)) - pad;
+        v[j] = make_float2(aug_sample(src, nz, L, d, g, noised, t), aug_sample(src, nz, L, d, g, noised, t + 1));
+    }
+}
+
 // WAVES: waves per block.  The per-lane twiddles (7 + 7 + 4 complex values that never change for a lane) live in 36 registers instead of
 // being re-read from LDS for every frame (18 ds_read_b64 = 39 LDS cycles per frame, in a kernel bound by the LDS pipe): 110 registers,
 // 4 waves per SIMD.
-template <typename WavT, int CHP, int NF, int NO, int WAVES = kV3Waves>
+template <typename WavT, int CHP, int NF, int NO, int WAVES = kV3Waves, bool AUG = false>
 __global__ __launch_bounds__(WAVES * 64, 4) void featurize_fft1024_v3_kernel(const WavT *__restrict__ wav, int64_t stride,
                                                                                   const int32_t *__restrict__ valid_len, int B,
-                                                                                  FeatDev c, float *__restrict__ feat)
+                                                                                  FeatDev c, float *__restrict__ feat, AugDev aug = {})
 {
     static_assert(NF % 4 == 0 && NF <= 32 && NO <= NF && CHP % 4 == 0, "band / coefficient counts of the tuned kernel");
     constexpr int TB = 64 / NF;                       // frames per tail batch (lanes = frame x band)
@@ -285,10 +299,24 @@ __global__ __launch_bounds__(WAVES * 64, 4) void featurize_fft1024_v3_kernel(con
     // clip geometry: keep the head, left-pad zeros (data_utils.py:77-80)
     const int bc = b;
     const int row = c.index ? c.index[bc] : bc;                            // kws_featurize_gather: clip bc is a row of the caller's dataset
-    int len = valid_len ? valid_len[row] : (stride > c.max_samples ? c.max_samples : (int)stride);
-    len = len < 0 ? 0 : len;
-    if ((int64_t)len > stride) len = (int)stride;
-    if (len > c.max_samples) len = c.max_samples;
+    int len;
+    const float *nz = nullptr;
+    int a_shift = 0;
+    float a_gain = 0.f;
+    bool a_noised = false;
+    if constexpr (AUG) {
+        const kws_aug_clip r = aug.plan[bc];                              // L, shift, gain, noise window of the planned clip
+        len = r.length;
+        a_shift = r.shift;
+        a_gain = r.gain;
+        a_noised = r.apply != 0;
+        nz = aug.bank + (a_noised ? aug.seg_start[r.segment] + r.offset : 0);
+    } else {
+        len = valid_len ? valid_len[row] : (stride > c.max_samples ? c.max_samples : (int)stride);
+        len = len < 0 ? 0 : len;
+        if ((int64_t)len > stride) len = (int)stride;
+        if (len > c.max_samples) len = c.max_samples;
+    }
     const int pad = c.max_samples - len;
     const WavT *src = wav + (int64_t)row * stride;
     const bool vec_ok = ((pad & 1) == 0) && ((reinterpret_cast<uintptr_t>(src) & (2 * sizeof(WavT) - 1)) == 0);
@@ -300,8 +328,13 @@ __global__ __launch_bounds__(WAVES * 64, 4) void featurize_fft1024_v3_kernel(con
 
     float2 xl[4], xh[4];                // lower / upper half of the next frame to transform
     if (f_beg < f_end) {
-        load_half<WavT, 0>(xl, src, f_beg * 512, pad, 1024, vec_ok, n2);
-        load_half<WavT, 4>(xh, src, f_beg * 512, pad, 1024, vec_ok, n2);
+        if constexpr (AUG) {
+            aug_load_half<WavT, 0>(xl, src, nz, len, a_shift, a_gain, a_noised, f_beg * 512, pad, n2);
+            aug_load_half<WavT, 4>(xh, src, nz, len, a_shift, a_gain, a_noised, f_beg * 512, pad, n2);
+        } else {
+            load_half<WavT, 0>(xl, src, f_beg * 512, pad, 1024, vec_ok, n2);
+            load_half<WavT, 4>(xh, src, f_beg * 512, pad, 1024, vec_ok, n2);
+        }
     }
     int qi = 0;                          // frames waiting in this wave's tail batch
     for (int f = f_beg; f < f_end; ++f) {
@@ -311,7 +344,8 @@ __global__ __launch_bounds__(WAVES * 64, 4) void featurize_fft1024_v3_kernel(con
         if (f + 1 < f_end) {             // next frame: its lower half is this frame's upper half; the new half loads under the FFT
 #pragma unroll
             for (int j = 0; j < 4; ++j) xl[j] = xh[j];
-            load_half<WavT, 4>(xh, src, (f + 1) * 512, pad, 1024, vec_ok, n2);
+            if constexpr (AUG) aug_load_half<WavT, 4>(xh, src, nz, len, a_shift, a_gain, a_noised, (f + 1) * 512, pad, n2);
+            else load_half<WavT, 4>(xh, src, (f + 1) * 512, pad, 1024, vec_ok, n2);
         }
         // pass 1: DFT-8 over a (n = n2 + 64 a), twiddle W_512^(n2 A)
         dft8x(v);

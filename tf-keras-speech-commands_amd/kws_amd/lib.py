@@ -47,6 +47,19 @@ class KwsTrainArgs(ctypes.Structure):
                 ("comm_state_weight", ctypes.c_float), ("feat_moments", ctypes.c_void_p)]
 
 
+AUG_MAX_SNR = 16
+
+
+class KwsAugmentParams(ctypes.Structure):
+    _fields_ = [("noised_rate", ctypes.c_float), ("n_snr", ctypes.c_int32), ("snr_db", ctypes.c_float * AUG_MAX_SNR),
+                ("max_shift", ctypes.c_int32), ("max_samples", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
+class KwsAugClip(ctypes.Structure):
+    _fields_ = [("apply", ctypes.c_int32), ("segment", ctypes.c_int32), ("offset", ctypes.c_int32), ("shift", ctypes.c_int32),
+                ("length", ctypes.c_int32), ("snr_db", ctypes.c_float), ("gain", ctypes.c_float), ("voice_length", ctypes.c_int32)]
+
+
 MODEL_KINDS = {"simple_cnn": 0, "simple_cnn_lite": 1, "simple_gru": 2, "simple_lstm": 3}
 BANK_MEL, BANK_BARK = 0, 1
 WAV_F32, WAV_I16 = 0, 1
@@ -147,6 +160,13 @@ def get_lib():
     L.kws_prof_enable.argtypes = [i32]
     L.kws_prof_report.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     L.kws_prof_report.restype = i64
+    L.kws_noise_bank_create.argtypes = [vp, i32, vp, i32, ctypes.POINTER(vp)]
+    L.kws_noise_bank_destroy.argtypes = [vp]
+    L.kws_noise_bank_destroy.restype = None
+    L.kws_noise_bank_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64), vp]
+    L.kws_augment_plan.argtypes = [vp, ctypes.POINTER(KwsAugmentParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, vp]
+    L.kws_augment_apply.argtypes = [vp, vp, vp, i32, vp, i32, i64, i32, vp, i64, vp, vp]
+    L.kws_featurize_gather_augmented.argtypes = [vp, vp, i32, vp, i32, i64, vp, vp, fp, vp]
     _lib = L
     return L
 

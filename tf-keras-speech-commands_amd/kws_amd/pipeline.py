@@ -41,15 +41,18 @@ class FeaturePipeline(object):
         # labels=True: submit(labels=..., index=...) also gathers the batch's labels; take() then returns them as the last element
         self.lab_bufs = [torch.empty((batch,), dtype=torch.int32, device=device) for _ in range(2)] if labels else None
 
-    def submit(self, wav=None, valid_len=None, after=None, index=None, features=None, labels=None):
+    def submit(self, wav=None, valid_len=None, after=None, index=None, features=None, labels=None, augment=None, step=0, position_base=0):
         """Enqueue the preparation of one batch on the side stream (returns at once).  Source: `wav` (rows, samples) raw audio,
         featurized here, or `features` (rows, n_features, feature_size); `index` (CUDA int32) picks the batch's rows from either
         (default: every row); `labels` (rows,) int32 are gathered with the same index.  `after`: an event on the main stream to
         start behind -- best the running step's overlap_event (DeviceModel.train_fwd_bwd(overlap_event=...), recorded at the point
         of the step that a sweep found best for this -- for simple_cnn behind conv3's forward kernel (round 3's sweep),
         include/kws.h); call submit from train_fwd_bwd's overlap_callback so that the launch also sits there in host order;
-        default: everything enqueued so far."""
+        default: everything enqueued so far.  augment / step / position_base: background-noise augmentation of raw audio
+        (Featurizer.__call__)."""
         torch = _torch()
+        if augment is not None and features is not None:
+            raise ValueError("augment needs raw audio (wav=...), not features")
         i = self.n_submitted % 2
         if after is not None:
             self.side.wait_event(after)
@@ -63,7 +66,9 @@ class FeaturePipeline(object):
             raise ValueError("batch of %d clips in a pipeline built for %d" % (n, self.batch))
         out = self.bufs[i] if n == self.batch else self.bufs[i][:n]
         with torch.cuda.stream(self.side):
-            if features is None:
+            if features is None and augment is not None:
+                self.featurizer(wav, valid_len=valid_len, out=out, index=index, augment=augment, step=step, position_base=position_base)
+            elif features is None:
                 self.featurizer(wav, valid_len=valid_len, out=out, index=index)
             elif index is not None:
                 torch.index_select(features.reshape(features.shape[0], out.shape[1], out.shape[2]), 0, index, out=out)

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Train a keyword-spotting model on your own dataset (mirror of the reference's train.py:22-137 for the native runtime).
+
+Same flags, callbacks and flow as the reference: features from get_dataset, Adam / RMSprop / SGD with the optional decay schedule,
+(weighted) sparse cross entropy, checkpoints on the best val_accuracy.  Checkpoints are .npz files (KWSModel.save: Keras-ordered arrays;
+HDF5 needs h5py) and the TensorBoard scalars become one JSON line per epoch (logs/000/train_log.jsonl).
+
+Beyond the reference: --raw_audio trains on the waveforms (get_audio_dataset; every batch is featurized on the GPU inside the step
+pipeline), and --noise_path mixes background noise into every training clip afresh in every epoch, with the knobs of the reference's
+offline tool tools/audio_process/add_noise.py (--snr, --noised_rate) and an optional random time shift (--time_shift_ms)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.append(os.path.dirname(os.path.realpath(__file__)))
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from classifier.data import get_audio_dataset, get_dataset
+    from classifier.loss import SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy
+    from classifier.model import get_model
+    from classifier.params import inject_params
+    from common.callbacks import (CheckpointCleanCallBack, EarlyStopping, JsonlLogger, ModelCheckpoint, ReduceLROnPlateau,
+                                  TerminateOnNaN)
+    from common.model_utils import get_optimizer
+    from common.utils import get_classes
+
+    log_dir = args.log_dir
+    os.makedirs(log_dir, exist_ok=True)
+    class_names = get_classes(args.classes_path)
+    assert class_names[0] == 'background', '1st class should be background.'
+    num_classes = len(class_names)
+    if args.noise_path and not args.raw_audio:
+        raise SystemExit('--noise_path needs --raw_audio (the noise is mixed into the waveforms before featurization)')
+
+    # callbacks for training process
+    logging = JsonlLogger(os.path.join(log_dir, 'train_log.jsonl'))
+    checkpoint = ModelCheckpoint(os.path.join(log_dir, 'ep{epoch:03d}-loss{loss:.3f}-accuracy{accuracy:.3f}-val_loss{val_loss:.3f}-val_accuracy{val_accuracy:.3f}.npz'),
+                                 monitor='val_accuracy', mode='max', verbose=1, save_weights_only=False, save_best_only=True, period=1)
+    reduce_lr = ReduceLROnPlateau(monitor='val_accuracy', factor=0.5, mode='max', patience=10, verbose=1, cooldown=0, min_lr=1e-10)
+    early_stopping = EarlyStopping(monitor='val_accuracy', min_delta=0, patience=50, verbose=1, mode='max')
+    checkpoint_clean = CheckpointCleanCallBack(log_dir, max_keep=5)
+    terminate_on_nan = TerminateOnNaN()
+    callbacks = [logging, checkpoint, reduce_lr, early_stopping, terminate_on_nan, checkpoint_clean]
+
+    # load & update audio params
+    if args.params_path:
+        inject_params(args.params_path)
+
+    # get train & val dataset
+    len_train = len_val = None
+    if args.raw_audio:
+        if args.val_data_path:
+            x_train, len_train, y_train, _, _, _ = get_audio_dataset(args.train_data_path, class_names)
+            x_val, len_val, y_val, _, _, _ = get_audio_dataset(args.val_data_path, class_names)
+        else:
+            assert args.val_split > 0, 'no val data split.'
+            x_train, len_train, y_train, x_val, len_val, y_val = get_audio_dataset(args.train_data_path, class_names, args.val_split)
+    elif args.val_data_path:
+        x_train, y_train, _, _ = get_dataset(args.train_data_path, class_names)
+        x_val, y_val, _, _ = get_dataset(args.val_data_path, class_names)
+    else:
+        assert args.val_split > 0, 'no val data split.'
+        x_train, y_train, x_val, y_val = get_dataset(args.train_data_path, class_names, args.val_split)
+
+    augment = None
+    if args.noise_path:
+        from kws_amd.augment import NoiseBank, WaveAugment
+        augment = WaveAugment(NoiseBank(args.noise_path), snr=args.snr, noised_rate=args.noised_rate, time_shift_ms=args.time_shift_ms)
+    elif args.time_shift_ms:
+        raise SystemExit('--time_shift_ms is part of the noise augmentation: give --noise_path too')
+
+    # prepare optimizer
+    if args.decay_type:
+        callbacks.remove(reduce_lr)
+    steps_per_epoch = max(1, len(x_train) // args.batch_size)
+    decay_steps = steps_per_epoch * args.epochs
+    optimizer = get_optimizer(args.optimizer, args.learning_rate, average_type=None, decay_type=args.decay_type, decay_steps=decay_steps)
+
+    # prepare loss according to loss type
+    if args.background_bias:
+        assert args.background_bias > 0 and args.background_bias < 1, 'background bias should between 0 and 1'
+        weights = [args.background_bias] + [(1.0 - args.background_bias) / (num_classes - 1)] * (num_classes - 1)
+        losses = WeightedSparseCategoricalCrossEntropy(np.array(weights))
+    else:
+        losses = SparseCategoricalCrossEntropy()
+
+    # get train model
+    model = get_model(args.model_type, num_classes, weights_path=args.weights_path)
+    model.compile(optimizer=optimizer, loss=losses, metrics=['accuracy'])
+    model.summary()
+
+    if args.raw_audio:
+        # the validation clips are featurized once (never augmented), with their lengths
+        from common.data_utils import get_featurizer
+        import torch
+        x_val = get_featurizer()(torch.from_numpy(x_val).cuda(), torch.from_numpy(len_val).cuda()).cpu().numpy()
+    print('Train on {} samples, val on {} samples, with batch size {}.'.format(len(x_train), len(x_val), args.batch_size))
+    fit_kw = dict(sample_lengths=len_train, augment=augment) if args.raw_audio else {}
+    history = model.fit(x_train, y_train, batch_size=args.batch_size, epochs=args.epochs, validation_data=(x_val, y_val),
+                        validation_freq=1, callbacks=callbacks, shuffle=True, verbose=1, **fit_kw)
+
+    # Finally store model
+    model.save(os.path.join(log_dir, 'trained_final.npz'))
+    return history
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description='train a keyword-spotting model on the GPU')
+    # Model definition options
+    parser.add_argument('--model_type', type=str, required=False, default='simple_cnn',
+                        help='classifier model type: simple_cnn/simple_cnn_lite/simple_gru/simple_lstm, default=%(default)s')
+    parser.add_argument('--weights_path', type=str, required=False, default=None,
+                        help="Pretrained model/weights file for fine tune")
+
+    # Data options
+    parser.add_argument('--train_data_path', type=str, required=True,
+                        help='path to train dataset')
+    parser.add_argument('--val_data_path', type=str, required=False, default=None,
+                        help='path to val dataset')
+    parser.add_argument('--val_split', type=float, required=False, default=0.15,
+                        help="validation data persentage in dataset if no val dataset provide, default=%(default)s")
+    parser.add_argument('--classes_path', type=str, required=True,
+                        help='path to class definitions')
+    parser.add_argument('--params_path', type=str, required=False, default=None,
+                        help='path to params json file')
+
+    # Training options
+    parser.add_argument('--background_bias', type=float, required=False, default=None,
+                        help="background loss bias (0~1) when training. lower values may cause more false positives if set, default=%(default)s")
+    parser.add_argument('--batch_size', type=int, required=False, default=512,
+                        help="Batch size for train, default=%(default)s")
+    parser.add_argument('--optimizer', type=str, required=False, default='adam', choices=['adam', 'rmsprop', 'sgd'],
+                        help="optimizer for training (adam/rmsprop/sgd), default=%(default)s")
+    parser.add_argument('--learning_rate', type=float, required=False, default=1e-3,
+                        help="Initial learning rate, default=%(default)s")
+    parser.add_argument('--decay_type', type=str, required=False, default=None, choices=[None, 'cosine', 'exponential', 'polynomial', 'piecewise_constant'],
+                        help="Learning rate decay type, default=%(default)s")
+    parser.add_argument('--epochs', type=int, required=False, default=100,
+                        help="Total training epochs, default=%(default)s")
+    parser.add_argument('--log_dir', type=str, required=False, default=os.path.join('logs', '000'),
+                        help="directory of the checkpoints, the epoch log and the final weights, default=%(default)s")
+
+    # Raw-audio training and background-noise augmentation (tools/audio_process/add_noise.py, drawn per clip and per step)
+    parser.add_argument('--raw_audio', action='store_true',
+                        help="train on the waveforms of <train_data_path>/sounds (featurized on the GPU every step) instead of cached features")
+    parser.add_argument('--noise_path', type=str, required=False, default=None,
+                        help="background noise .wav file or directory: mix it into every training clip (needs --raw_audio)")
+    parser.add_argument('--snr', type=str, required=False, default='50',
+                        help="Sound Noise Ratio (SNR) choice in dB, separate with comma if more than one. default=%(default)s")
+    parser.add_argument('--noised_rate', type=float, required=False, default=1.0,
+                        help="random percentage rate of adding noise to voice audio (0.0~1.0). default=%(default)s")
+    parser.add_argument('--time_shift_ms', type=float, required=False, default=0.0,
+                        help="random time shift of every training clip by up to +-this many ms (0: off). default=%(default)s")
+    return parser.parse_args(argv)
+
+
+if __name__ == '__main__':
+    main()
