@@ -192,6 +192,48 @@ int kws_featurize_gather_augmented(kws_featurizer *f, const void *wav, int wav_d
                                    const kws_noise_bank *bank, const kws_aug_clip *plan, float *feat, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Room-reverberation augmentation of raw audio: the convolution of tools/audio_process/audio_reverberation.py (pyroomacoustics) and
+ * gpuRIR_reverberation.py of the reference with a room impulse response (RIR), drawn afresh for every clip of every train step on the
+ * device instead of written once as *_reverb.wav copies.  Clip b sits at global batch position p = position_base + b; its dry signal v
+ * is row index[b] of wav (int16 scaled by 1/32768), Lv = min(valid_len[row] or stride, max_samples).  Draws: h_f = aug_hash(seed, step,
+ * 2 p + f) (kws_augment.h; kws_amd passes seed_r = WaveAugment seed ^ 0x9E3779B97F4A7C15, so the noise draws are unchanged):
+ *   f = 0: wet = ((h_0 >> 8) * 2^-24) < reverb_rate;  f = 1: k = aug_uniform(h_1, K)
+ *   wet:  L' = min(Lv + Lh_k - 1, max_samples) (0 when Lv = 0); y[t] = sum_{j <= min(t, Lh_k - 1)} h_k[j] v[t - j], t < L' (v[u] = 0 for
+ *         u >= Lv): causal, starting at the direct path; the tail lengthens a short clip up to max_samples.  rescale: y *= sqrt(E_v /
+ *         (E_y + Lv FLT_EPSILON)), E = sum of squares over t < Lv (the clip keeps its level, so a later SNR draw means what it says)
+ *   dry:  L' = Lv, y = v (bit for bit after the f32 conversion)
+ * Reverb runs first; the noise stage (kws_augment_plan and the fused featurizer, time shift included) then runs unchanged on (out,
+ * lengths) with index = NULL and the same position_base.  Divergences from the reference: the noise is mixed after the reverberation
+ * (the reference places it as a second source in the same room); a single omni microphone (the reference records a 3-mic array that
+ * librosa.load(mono=True) averages); no int16 quantisation of the result; fresh draws every step.
+ * ---------------------------------------------------------------------- */
+typedef struct kws_rir_bank kws_rir_bank;
+
+/* K RIRs concatenated on the HOST: taps[sum(rir_len)] float32, rir_len[K] >= 1 each, finite.  Taps at index >= max_samples can never
+ * reach an output sample and are clipped away (Lh = min(rir_len, max_samples)).  Every clipped RIR is transformed once (fp64 on the
+ * host) into the spectrum the kernel multiplies by.  max_samples in [1, 16384] (KWS_ERR_UNSUPPORTED above: one 32768-point transform). */
+int kws_rir_bank_create(const float *taps, const int32_t *rir_len, int K, int max_samples, kws_rir_bank **out);
+void kws_rir_bank_destroy(kws_rir_bank *bank);
+/* host: number of RIRs, the bank's max_samples and the real transform size (32768) */
+int kws_rir_bank_info(const kws_rir_bank *bank, int *K, int *max_samples, int *fft_size);
+
+typedef struct kws_reverb_params {
+    float reverb_rate;     /* fraction of clips reverberated, [0, 1] */
+    int32_t rescale;       /* 1: keep the dry clip's energy over t < Lv */
+    int32_t max_samples;   /* the head the featurizer keeps, [1, 16384] */
+    int32_t reserved;      /* 0 */
+    uint64_t seed;         /* seed_r */
+} kws_reverb_params;
+
+/* Reverberate B clips, no host synchronisation (explicit_rir is copied from the host first).  out: B x out_stride float32
+ * (out_stride >= max_samples), row b = y[0:L'] then zeros; lengths (device int32 B, required) = L'; rir_used (device int32 B, may be
+ * NULL) = k, or -1 for a dry clip.  explicit_rir (HOST int32 B, values -1..K-1, or NULL): take k (-1 = dry) from the caller instead of
+ * the draws.  Fixed reduction order and no atomics: two calls give the same bits. */
+int kws_reverb_apply(const kws_rir_bank *bank, const kws_reverb_params *params, const void *wav, int wav_dtype, const int32_t *index,
+                     int B, int64_t stride, const int32_t *valid_len, int64_t position_base, int64_t step, const int32_t *explicit_rir,
+                     float *out, int64_t out_stride, int32_t *lengths, int32_t *rir_used, void *stream);
+
+/* ------------------------------------------------------------------------
  * Model: replaces the tf.keras objects built by classifier/model.py:14-46
  * get_model() (backbones classifier/models/cnn.py, rnn.py) and the work
  * Keras does inside model.fit / model.predict (train.py:75-92).

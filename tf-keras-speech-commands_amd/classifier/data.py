@@ -126,9 +126,9 @@ def get_audio_dataset(dataset_path, class_names, val_split=None):
     return x, lengths, y, None, None, None
 
 
-def load_noise_bank(path):
+def load_noise_bank(path, what='noise'):
     """every *.wav under `path` (a folder, searched recursively, or one file) through load_wav -> list of float32 arrays, sorted by path:
-    the noise_files of tools/audio_process/add_noise.py; kws_amd.augment.NoiseBank uploads them"""
+    the noise_files of tools/audio_process/add_noise.py; kws_amd.augment.NoiseBank uploads them (and RirBank, with what='RIR')"""
     if os.path.isfile(path):
         files = [path]
     else:
@@ -139,6 +139,6 @@ def load_noise_bank(path):
     for f in files:
         a = load_wav(f)
         if len(a) == 0:
-            raise ValueError('noise file %s is empty' % f)
+            raise ValueError('%s file %s is empty' % (what, f))
         out.append(a)
     return out

@@ -1,4 +1,5 @@
-"""Background-noise augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*, kws_augment_*).
+"""Background-noise and room-reverberation augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*, kws_augment_*,
+kws_rir_bank_*, kws_reverb_apply).
 
 The reference makes training data robust offline: tools/audio_process/add_noise.py mixes a randomly chosen background recording into a
 `noised_rate` fraction of the clips at an SNR drawn from a list and writes one fixed *_noised.wav copy per clip.  Here the same mix is
@@ -8,7 +9,14 @@ drawn afresh for every clip of every train step, inside the featurizer's sample 
     aug = WaveAugment(noise, snr=(5, 10, 20), noised_rate=0.8, time_shift_ms=100, seed=1)
     model.fit(x_audio, y, augment=aug, sample_lengths=lengths)
 
-Argument checks run on the host; the device copy of the bank is made on first use."""
+The reference's other augmentation tool, tools/audio_process/audio_reverberation.py (or gpuRIR_reverberation.py), convolves every clip
+with the impulse response of a random room and writes one *_reverb.wav copy.  Here a bank of room impulse responses (RIRs) is built once
+-- from wav files, or simulated by simulate_rirs() with the reference's room draws -- and every clip of every step is convolved with a
+RIR drawn afresh, before the noise is mixed in:
+
+    aug = WaveAugment(noise, rirs=simulate_rirs(64, seed=0), reverb_rate=1.0, seed=1)     # noise may be None
+
+Argument checks run on the host; the device copy of a bank is made on first use."""
 import ctypes
 import math
 import os
@@ -103,13 +111,167 @@ def parse_snr(snr):
     return [float(s) for s in snr]
 
 
+# the reverb draws use seed ^ REVERB_SEED_MIX, so that they are independent of the noise draws of the same seed (include/kws.h)
+REVERB_SEED_MIX = 0x9E3779B97F4A7C15
+SPEED_OF_SOUND = 343.0            # m/s
+SINC_HALF_WIDTH = 16              # samples: the Hann-windowed sinc of a fractional delay spans [-16, 16] around it, shifted to be causal
+
+
+class RirBank(object):
+    """Room impulse responses: a folder (searched recursively) or file of *.wav read with common.data_utils.load_wav (resampled to
+    pr.sample_rate), or a list of 1-D float arrays.  Every RIR is trimmed to start at its peak argmax|h| (the propagation and
+    fractional-delay lead-in goes, so labels keep their timing) and divided by it (the direct path is +1); taps at index >= max_samples
+    (default pr.max_samples) can never reach an output sample and are clipped away."""
+
+    def __init__(self, rirs, max_samples=None):
+        from classifier.params import pr
+        if isinstance(rirs, (str, os.PathLike)):
+            from classifier.data import load_noise_bank
+            rirs = load_noise_bank(rirs, what='RIR')
+        if isinstance(rirs, np.ndarray) and rirs.ndim == 1:
+            rirs = [rirs]
+        ms = int(pr.max_samples if max_samples is None else max_samples)
+        if not 1 <= ms <= _l.REVERB_MAX_SAMPLES:
+            raise ValueError("max_samples must be in [1, %d], got %d" % (_l.REVERB_MAX_SAMPLES, ms))
+        taps = []
+        for i, h in enumerate(list(rirs)):
+            h = np.asarray(h)
+            if h.ndim != 1 or h.size == 0:
+                raise ValueError("RIR %d must be a non-empty 1-D array, got shape %s" % (i, h.shape))
+            if h.dtype not in (np.float32, np.float64):
+                raise TypeError("RIR %d: float32 or float64 taps expected, got %s" % (i, h.dtype))
+            if not np.all(np.isfinite(h)):
+                raise ValueError("RIR %d has non-finite taps" % i)
+            h = h.astype(np.float64)
+            peak = int(np.argmax(np.abs(h)))
+            if h[peak] == 0:
+                raise ValueError("RIR %d is all zeros" % i)
+            taps.append((h[peak:peak + ms] / h[peak]).astype(np.float32))
+        if not taps:
+            raise ValueError("a RIR bank needs at least one RIR")
+        self.taps, self.max_samples = taps, ms
+        self.rir_len = np.array([t.size for t in taps], np.int32)
+        self._h = None
+
+    def __len__(self):
+        return len(self.taps)
+
+    def handle(self):
+        if self._h is None:
+            _torch()
+            L = _l.get_lib()
+            h = ctypes.c_void_p()
+            flat = np.ascontiguousarray(np.concatenate(self.taps), np.float32)
+            _l.check(L.kws_rir_bank_create(flat.ctypes.data, self.rir_len.ctypes.data, len(self.taps), self.max_samples, ctypes.byref(h)))
+            self._h, self._L = h, L
+        return self._h
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            self._L.kws_rir_bank_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _windowed_sinc_add(h, delay, amp):
+    """h[n] += amp * sinc(n - c) * hann(n - c) for |n - c| < SINC_HALF_WIDTH, c = delay + SINC_HALF_WIDTH (vectorised over images)"""
+    c = np.asarray(delay, np.float64) + SINC_HALF_WIDTH
+    base = np.floor(c).astype(np.int64)
+    offs = np.arange(-SINC_HALF_WIDTH + 1, SINC_HALF_WIDTH + 1)
+    n = base[:, None] + offs[None, :]
+    x = n - c[:, None]
+    w = np.where(np.abs(x) < SINC_HALF_WIDTH, 0.5 * (1.0 + np.cos(np.pi * x / SINC_HALF_WIDTH)), 0.0)
+    np.add.at(h, n.ravel(), (np.asarray(amp, np.float64)[:, None] * np.sinc(x) * w).ravel())
+
+
+def shoebox_rir(room, source, mic, rt60, sample_rate=None, rng=None):
+    """The impulse response (float64, not aligned) from `source` to one omni microphone `mic` in a shoebox `room` (metres) with
+    reverberation time rt60 (s), from the textbook models:
+      - Sabine: every wall reflects with beta = sqrt(1 - alpha), alpha = min(0.161 V / (S rt60), 1 - 1e-6);
+      - image sources (Allen & Berkley) up to the time the Sabine decay reaches 15 dB: beta^reflections / (4 pi d) at delay
+        d / c * fs (c = 343 m/s), through a Hann-windowed sinc fractional delay of half-width SINC_HALF_WIDTH (shifted to be causal);
+      - from there to the 60 dB point a Gaussian tail with amplitude envelope exp(-6.9078 t / rt60), its level matched to the image
+        sources' energy over the 5 ms before the hand-over."""
+    from classifier.params import pr
+    fs = float(sample_rate or pr.sample_rate)
+    rng = np.random.default_rng() if rng is None else rng
+    room, src, mic = (np.asarray(a, np.float64) for a in (room, source, mic))
+    rt60 = float(rt60)
+    V = float(np.prod(room))
+    S = 2.0 * (room[0] * room[1] + room[0] * room[2] + room[1] * room[2])
+    alpha = min(0.161 * V / (S * rt60), 1.0 - 1e-6)
+    beta = math.sqrt(1.0 - alpha)
+    t_diff, t_max = rt60 * 15.0 / 60.0, rt60            # Sabine decay: 15 dB and 60 dB
+    n_diff = int(round(t_diff * fs)) + SINC_HALF_WIDTH
+    n_len = int(round(t_max * fs)) + 2 * SINC_HALF_WIDTH + 1
+    h = np.zeros(n_len + SINC_HALF_WIDTH + 1)
+    d_max = t_diff * SPEED_OF_SOUND
+    nmax = np.ceil(d_max / (2.0 * room)).astype(int) + 1
+    grids = np.meshgrid(*[np.arange(-m, m + 1) for m in nmax], indexing="ij")
+    cells = np.stack([g.ravel() for g in grids], 1)               # (n_cells, 3) image cell indices
+    for parity in np.ndindex(2, 2, 2):
+        u = np.array(parity)
+        pos = (1 - 2 * u)[None, :] * src[None, :] + 2.0 * cells * room[None, :]
+        refl = np.abs(2 * cells - u[None, :]).sum(1)
+        d = np.sqrt(((pos - mic[None, :]) ** 2).sum(1))
+        keep = d <= d_max
+        d, refl = np.maximum(d[keep], 1e-3), refl[keep]
+        _windowed_sinc_add(h, d / SPEED_OF_SOUND * fs, beta ** refl / (4.0 * np.pi * d))
+    h = h[:n_len]
+    if n_len > n_diff:
+        w = max(int(0.005 * fs), 1)
+        e_ism = float(np.mean(h[max(n_diff - w, 0):n_diff] ** 2))
+        t = (np.arange(n_diff, n_len) - SINC_HALF_WIDTH) / fs
+        env = np.exp(-6.9078 * t / rt60)
+        g = math.sqrt(e_ism) / env[0]
+        h[n_diff:] = g * env * rng.standard_normal(n_len - n_diff)
+    return h
+
+
+def simulate_rirs(count, seed=None, rt60=(0.3, 0.7), sample_rate=None, with_geometry=False):
+    """`count` RIRs (float32, not aligned: RirBank aligns them) of random shoebox rooms, drawn as tools/audio_process/gpuRIR_reverberation.py
+    of the reference draws them: rt60 uniform in the range, room uniform in [4, 3, 2.6]..[6, 4.8, 2.8] m, source uniform in
+    [0.5, 0.5, 1.6]..[Lx - 0.5, Ly - 0.5, 1.9], one omni microphone (the centre of the reference's array) uniform in
+    [0.5, 0.5]..[Lx - 0.5, Ly - 0.5] at 0.1 m.  Deterministic for a given seed.  with_geometry: also return a list of dicts
+    (room, source, mic, rt60)."""
+    count = int(count)
+    if count < 1:
+        raise ValueError("count must be >= 1, got %d" % count)
+    lo, hi = (float(r) for r in rt60)
+    if not 0.0 < lo <= hi:
+        raise ValueError("rt60 range must satisfy 0 < low <= high, got %r" % (rt60,))
+    rng = np.random.default_rng(seed)
+    out, geo = [], []
+    for _ in range(count):
+        t60 = rng.uniform(lo, hi)
+        room = rng.uniform([4.0, 3.0, 2.6], [6.0, 4.8, 2.8])
+        src = rng.uniform([0.5, 0.5, 1.6], [room[0] - 0.5, room[1] - 0.5, 1.9])
+        mic = np.r_[rng.uniform([0.5, 0.5], [room[0] - 0.5, room[1] - 0.5]), 0.1]
+        out.append(shoebox_rir(room, src, mic, t60, sample_rate, rng).astype(np.float32))
+        geo.append({"room": room, "source": src, "mic": mic, "rt60": t60})
+    return (out, geo) if with_geometry else out
+
+
 class WaveAugment(object):
     """Per-clip background noise (add_noise.py:19-35) at an SNR drawn from `snr` for a `noised_rate` fraction of the clips, and an
-    optional time shift of up to +-time_shift_ms (off by default; the reference has none).  Draws are counter-based, keyed by
-    (seed, step) and indexed by the clip's position in the global batch."""
+    optional time shift of up to +-time_shift_ms (off by default; the reference has none).  With `rirs` (a RirBank, or anything RirBank
+    accepts) a `reverb_rate` fraction of the clips is first convolved with a RIR drawn from the bank (audio_reverberation.py), with the
+    clip's energy kept when `rescale` is on; `noise` may then be None.  Draws are counter-based, keyed by (seed, step) and indexed by the
+    clip's position in the global batch."""
 
-    def __init__(self, noise, snr=(50,), noised_rate=1.0, time_shift_ms=0, seed=None, sample_rate=None):
+    def __init__(self, noise, snr=(50,), noised_rate=1.0, time_shift_ms=0, seed=None, sample_rate=None, rirs=None, reverb_rate=1.0,
+                 rescale=True):
         from classifier.params import pr
+        if noise is None and rirs is None:
+            raise ValueError("WaveAugment needs a noise bank, a RIR bank or both")
+        rrate = float(reverb_rate)
+        if not 0.0 <= rrate <= 1.0:
+            raise ValueError("reverb_rate must be in [0, 1], got %r" % reverb_rate)
         rate = float(noised_rate)
         if not 0.0 <= rate <= 1.0:
             raise ValueError("noised_rate must be in [0, 1], got %r" % noised_rate)
@@ -120,11 +282,68 @@ class WaveAugment(object):
             raise ValueError("SNR values must be finite: %r" % (snr,))
         if not float(time_shift_ms) >= 0:
             raise ValueError("time_shift_ms must be >= 0, got %r" % time_shift_ms)
-        self.noise = noise if isinstance(noise, NoiseBank) else NoiseBank(noise)
+        self.noise = None if noise is None else noise if isinstance(noise, NoiseBank) else NoiseBank(noise)
+        self.rirs = None if rirs is None else rirs if isinstance(rirs, RirBank) else RirBank(rirs)
+        self.reverb_rate, self.rescale = rrate, bool(rescale)
         self.snr, self.noised_rate, self.time_shift_ms = snr, rate, float(time_shift_ms)
         sr = int(sample_rate or pr.sample_rate)
         self.max_shift = int(round(self.time_shift_ms * sr / 1000.0))
         self.seed = int(np.random.randint(0, 2 ** 62) if seed is None else seed) & (2 ** 64 - 1)
+
+    @property
+    def reverb_seed(self):
+        return self.seed ^ REVERB_SEED_MIX
+
+    def reverb_params(self, max_samples):
+        p = _l.KwsReverbParams()
+        p.reverb_rate, p.rescale, p.max_samples, p.reserved, p.seed = self.reverb_rate, int(self.rescale), int(max_samples), 0, self.reverb_seed
+        return p
+
+    def reverberate(self, wav, valid_len=None, index=None, step=0, position_base=0, explicit=None, max_samples=None, out=None, lengths=None,
+                    rir_used=None):
+        """-> (out (B, max_samples) float32, lengths (B,) int32, rir_used (B,) int32): the B clips wav[index] (default: every row),
+        each convolved with the RIR drawn for (seed, step) at global position position_base + b (rir_used = its index) or left dry
+        (rir_used = -1), head-aligned, zeros after.  explicit: B ints in [-1, len(rirs)) instead of the draws.  out / lengths / rir_used:
+        optional preallocated CUDA buffers (out may be wider than max_samples; rir_used=False skips it)."""
+        from classifier.params import pr
+        torch = _torch()
+        if self.rirs is None:
+            raise ValueError("this WaveAugment has no RIR bank")
+        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
+            raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
+        rows, stride = wav.shape
+        B, ix = rows, 0
+        if index is not None:
+            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
+                raise ValueError("index must be a contiguous CUDA int32 vector")
+            B, ix = index.numel(), index.data_ptr()
+        vl = 0
+        if valid_len is not None:
+            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
+                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
+            vl = valid_len.data_ptr()
+        ms = int(pr.max_samples if max_samples is None else max_samples)
+        ex = None
+        if explicit is not None:
+            ex = np.ascontiguousarray(np.asarray(explicit).reshape(-1), np.int32)
+            if ex.shape != (B,):
+                raise ValueError("explicit RIR choice has %s entries for %d clips" % (ex.shape, B))
+        if out is None:
+            out = torch.empty((B, ms), dtype=torch.float32, device=wav.device)
+        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] < ms or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError("out must be a contiguous float32 CUDA tensor of at least (%d, %d)" % (B, ms))
+        if lengths is None:
+            lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
+        if rir_used is None:
+            rir_used = torch.empty((B,), dtype=torch.int32, device=wav.device)
+        _l.check(_l.get_lib().kws_reverb_apply(self.rirs.handle(), ctypes.byref(self.reverb_params(ms)), wav.data_ptr(), _wav_code(wav), ix, B,
+                                               stride, vl, int(position_base), int(step), None if ex is None else ex.ctypes.data,
+                                               out.data_ptr(), out.shape[1], lengths.data_ptr(),
+                                               rir_used.data_ptr() if rir_used is not False else None,
+                                               torch.cuda.current_stream().cuda_stream))
+        if ex is not None:
+            torch.cuda.current_stream().synchronize()       # the host choices are copied from pageable memory
+        return out, lengths, (rir_used if rir_used is not False else None)
 
     def params(self, max_samples):
         p = _l.KwsAugmentParams()
@@ -140,6 +359,8 @@ class WaveAugment(object):
         explicit: a CLIP_DTYPE array (apply / segment / offset / shift / snr_db taken from it) instead of the draws."""
         from classifier.params import pr
         torch = _torch()
+        if self.noise is None:
+            raise ValueError("this WaveAugment has no noise bank")
         if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
         rows, stride = wav.shape

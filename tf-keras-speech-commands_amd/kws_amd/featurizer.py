@@ -85,7 +85,9 @@ class Featurizer(object):
         """wav: CUDA tensor (rows, stride) float32|int16; valid_len: optional CUDA int32 (rows,).  index: optional CUDA int32 (B,): featurize
         the B rows wav[index[b]] in place of all rows (kws_featurize_gather: a shuffled minibatch of a device-resident dataset, no copy).
         augment: optional kws_amd.augment.WaveAugment: featurize the clips with background noise mixed in, drawn for (its seed, `step`)
-        at global batch positions position_base + b (kws_augment_plan + kws_featurize_gather_augmented)."""
+        at global batch positions position_base + b (kws_augment_plan + kws_featurize_gather_augmented).  With a RIR bank the clips are
+        reverberated first (kws_reverb_apply into a scratch buffer of this featurizer), then noised (if it has a noise bank) and featurized
+        from there."""
         torch = _torch()
         if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous CUDA tensor of shape (B, stride)")
@@ -106,6 +108,15 @@ class Featurizer(object):
             if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
                 raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
             vl = valid_len.data_ptr()
+        if augment is not None and augment.rirs is not None:
+            # reverberation first, into this featurizer's scratch on the call's stream; then noise (or nothing) on the wet clips
+            ms = g["max_samples"]
+            wet, lens, _ = augment.reverberate(wav, valid_len=valid_len, index=index, step=step, position_base=position_base,
+                                               max_samples=ms, out=self._reverb_scratch(B, ms, wav.device), lengths=self._reverb_lengths(B, wav.device),
+                                               rir_used=False)
+            wav, index, valid_len, stride, ix, vl = wet, None, lens, ms, 0, lens.data_ptr()
+            if augment.noise is None:
+                augment = None
         if augment is not None:
             plan = augment.plan(wav, valid_len=valid_len, index=index, step=step, position_base=position_base, max_samples=g["max_samples"])
             _l.check(self._L.kws_featurize_gather_augmented(self._h, wav.data_ptr(), self._dtype_code(wav), ix, B, stride,
@@ -115,6 +126,19 @@ class Featurizer(object):
         _l.check(self._L.kws_featurize_gather(self._h, wav.data_ptr(), self._dtype_code(wav), ix, B, stride, vl, out.data_ptr(),
                                               torch.cuda.current_stream().cuda_stream))
         return out
+
+    def _reverb_scratch(self, B, ms, device):
+        """(B, ms) float32 rows the reverberated clips go to, one buffer per stream (grown on demand)"""
+        torch = _torch()
+        key = torch.cuda.current_stream().cuda_stream
+        bufs = self.__dict__.setdefault("_rv_bufs", {})
+        buf = bufs.get(key)
+        if buf is None or buf[0].shape[0] < B or buf[0].shape[1] != ms or buf[0].device != device:
+            buf = bufs[key] = (torch.empty((B, ms), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.int32, device=device))
+        return buf[0][:B]
+
+    def _reverb_lengths(self, B, device):
+        return self._rv_bufs[_torch().cuda.current_stream().cuda_stream][1][:B]
 
     def raw(self, wav, n_samples=None):
         """vectorize_raw semantics: (B, n) -> (B, n_frames, n_mfcc), no padding / clipping / deltas."""

@@ -60,6 +60,14 @@ class KwsAugClip(ctypes.Structure):
                 ("length", ctypes.c_int32), ("snr_db", ctypes.c_float), ("gain", ctypes.c_float), ("voice_length", ctypes.c_int32)]
 
 
+class KwsReverbParams(ctypes.Structure):
+    _fields_ = [("reverb_rate", ctypes.c_float), ("rescale", ctypes.c_int32), ("max_samples", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
+REVERB_MAX_SAMPLES = 16384
+
+
 MODEL_KINDS = {"simple_cnn": 0, "simple_cnn_lite": 1, "simple_gru": 2, "simple_lstm": 3}
 BANK_MEL, BANK_BARK = 0, 1
 WAV_F32, WAV_I16 = 0, 1
@@ -167,6 +175,11 @@ def get_lib():
     L.kws_augment_plan.argtypes = [vp, ctypes.POINTER(KwsAugmentParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, vp]
     L.kws_augment_apply.argtypes = [vp, vp, vp, i32, vp, i32, i64, i32, vp, i64, vp, vp]
     L.kws_featurize_gather_augmented.argtypes = [vp, vp, i32, vp, i32, i64, vp, vp, fp, vp]
+    L.kws_rir_bank_create.argtypes = [vp, vp, i32, i32, ctypes.POINTER(vp)]
+    L.kws_rir_bank_destroy.argtypes = [vp]
+    L.kws_rir_bank_destroy.restype = None
+    L.kws_rir_bank_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.kws_reverb_apply.argtypes = [vp, ctypes.POINTER(KwsReverbParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp]
     _lib = L
     return L
 

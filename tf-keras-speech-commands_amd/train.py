@@ -7,7 +7,9 @@ HDF5 needs h5py) and the TensorBoard scalars become one JSON line per epoch (log
 
 Beyond the reference: --raw_audio trains on the waveforms (get_audio_dataset; every batch is featurized on the GPU inside the step
 pipeline), and --noise_path mixes background noise into every training clip afresh in every epoch, with the knobs of the reference's
-offline tool tools/audio_process/add_noise.py (--snr, --noised_rate) and an optional random time shift (--time_shift_ms)."""
+offline tool tools/audio_process/add_noise.py (--snr, --noised_rate) and an optional random time shift (--time_shift_ms).  --rir_path
+(a folder of room impulse responses) or --simulate_rirs N (N simulated rooms) reverberates a --reverb_rate share of the training clips
+before the noise, as tools/audio_process/audio_reverberation.py does offline; either works without --noise_path."""
 import argparse
 import os
 import sys
@@ -35,6 +37,15 @@ def main(argv=None):
     num_classes = len(class_names)
     if args.noise_path and not args.raw_audio:
         raise SystemExit('--noise_path needs --raw_audio (the noise is mixed into the waveforms before featurization)')
+    has_rirs = bool(args.rir_path) or bool(args.simulate_rirs)
+    if args.rir_path and args.simulate_rirs:
+        raise SystemExit('give one RIR source: --rir_path or --simulate_rirs')
+    if args.reverb_rate is not None and not has_rirs:
+        raise SystemExit('--reverb_rate needs a RIR source: --rir_path or --simulate_rirs')
+    if has_rirs and not args.raw_audio:
+        raise SystemExit('--rir_path / --simulate_rirs need --raw_audio (the waveforms are reverberated before featurization)')
+    if args.simulate_rirs is not None and args.simulate_rirs < 1:
+        raise SystemExit('--simulate_rirs needs a positive number of rooms')
 
     # callbacks for training process
     logging = JsonlLogger(os.path.join(log_dir, 'train_log.jsonl'))
@@ -67,11 +78,20 @@ def main(argv=None):
         x_train, y_train, x_val, y_val = get_dataset(args.train_data_path, class_names, args.val_split)
 
     augment = None
+    rirs = None
+    if has_rirs:
+        from kws_amd.augment import RirBank, simulate_rirs
+        rirs = RirBank(args.rir_path if args.rir_path else simulate_rirs(args.simulate_rirs))
+    reverb_rate = 1.0 if args.reverb_rate is None else args.reverb_rate
     if args.noise_path:
         from kws_amd.augment import NoiseBank, WaveAugment
-        augment = WaveAugment(NoiseBank(args.noise_path), snr=args.snr, noised_rate=args.noised_rate, time_shift_ms=args.time_shift_ms)
+        augment = WaveAugment(NoiseBank(args.noise_path), snr=args.snr, noised_rate=args.noised_rate, time_shift_ms=args.time_shift_ms,
+                              rirs=rirs, reverb_rate=reverb_rate)
     elif args.time_shift_ms:
         raise SystemExit('--time_shift_ms is part of the noise augmentation: give --noise_path too')
+    elif rirs is not None:
+        from kws_amd.augment import WaveAugment
+        augment = WaveAugment(None, rirs=rirs, reverb_rate=reverb_rate)
 
     # prepare optimizer
     if args.decay_type:
@@ -155,6 +175,13 @@ def parse_args(argv=None):
                         help="random percentage rate of adding noise to voice audio (0.0~1.0). default=%(default)s")
     parser.add_argument('--time_shift_ms', type=float, required=False, default=0.0,
                         help="random time shift of every training clip by up to +-this many ms (0: off). default=%(default)s")
+    # Room reverberation (tools/audio_process/audio_reverberation.py, drawn per clip and per step)
+    parser.add_argument('--rir_path', type=str, required=False, default=None,
+                        help="room impulse response .wav file or directory: reverberate the training clips (needs --raw_audio)")
+    parser.add_argument('--simulate_rirs', type=int, required=False, default=None,
+                        help="simulate this many random rooms (the reference's gpuRIR draws) as the RIR bank (needs --raw_audio)")
+    parser.add_argument('--reverb_rate', type=float, required=False, default=None,
+                        help="random percentage rate of reverberating the training clips (0.0~1.0). default=1.0")
     return parser.parse_args(argv)
 
 
