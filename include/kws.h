@@ -234,6 +234,57 @@ int kws_reverb_apply(const kws_rir_bank *bank, const kws_reverb_params *params, 
                      float *out, int64_t out_stride, int32_t *lengths, int32_t *rir_used, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Butterworth filter augmentation of raw audio: tools/audio_process/wav_filter.py of the reference (scipy.signal.butter(order, Wn, type),
+ * Wn = 2 f / sample_rate, applied with zero phase by scipy.signal.filtfilt(b, a, x)), drawn afresh for every clip of every train step on
+ * the device instead of written once as filtered copies.  Clip b sits at global batch position p = position_base + b; its dry signal v
+ * is row index[b] of wav (int16 scaled by 1/32768), Lv = min(valid_len[row] or stride, max_samples).  Draws: h_f = aug_hash(seed, step,
+ * 2 p + f) (kws_augment.h; kws_amd passes seed_f = WaveAugment seed ^ 0xD1B54A32D192ED03, so the noise and reverb draws are unchanged):
+ *   f = 0: filtered = ((h_0 >> 8) * 2^-24) < filter_rate;  f = 1: k = aug_uniform(h_1, K)
+ *   filtered, Lv > padlen_k: y[0:Lv] = filtfilt of v[0:Lv] with scipy's defaults: the odd extension ext of padlen_k samples on each side
+ *         (ext[i] = 2 v[0] - v[padlen - i], ext[padlen + Lv + j] = 2 v[Lv-1] - v[Lv-2-j]); the forward pass runs the cascade from
+ *         zi_k * ext[0], the backward pass over the reversed forward output from zi_k * y_fwd[last]; cropped back to Lv, zeros after.
+ *         rescale: y *= sqrt(E_v / (E_y + Lv FLT_EPSILON)), E = sum of squares over t < Lv (a later SNR draw means what it says)
+ *   dry (not drawn, or Lv <= padlen_k, where scipy raises): y = v (bit for bit after the f32 conversion), filter_used = -1
+ *   lengths = Lv either way.
+ * Order of stages: reverb (kws_reverb_apply), then this filter on its (out, lengths) with index = NULL, then the noise stage (time shift
+ * included), all with the same position_base.  Divergences from the reference: only the featurizer's head (max_samples) is filtered, not
+ * the whole file; no int16 quantisation of the result; the noise is not filtered; fresh draws every step; short clips stay dry instead
+ * of raising.
+ * ---------------------------------------------------------------------- */
+#define KWS_FILTER_MAX_SECTIONS 4      /* lowpass / highpass up to order 8, bandpass / bandstop up to order 4 */
+#define KWS_FILTER_MAX_PADLEN 32       /* filtfilt's default 3 (n + 1) is at most 27 within the section limit */
+#define KWS_FILTER_MAX_SAMPLES 16320   /* max_samples + 2 padlen fits the kernel's 64 chunks of 256 samples */
+typedef struct kws_filter_bank kws_filter_bank;
+
+/* K filters as second-order sections on the HOST, float64: sos[K][n_sections][6] = (b0, b1, b2, a0, a1, a2) per section (scipy's
+ * output='sos'; a filter of fewer sections is padded with (1, 0, 0, 1, 0, 0)), n_sections in [1, KWS_FILTER_MAX_SECTIONS]
+ * (KWS_ERR_UNSUPPORTED above), padlen[K] in [1, KWS_FILTER_MAX_PADLEN] (filtfilt's 3 max(len(a), len(b))).  Every section must be finite,
+ * a0 != 0 and stable (both poles inside the unit circle).  The steady-state initial conditions zi (scipy's sosfilt_zi) and the powers
+ * A^(2^e) of the cascade's state matrix the kernel's chunk scan needs are computed here in float64, and the device filters in float64
+ * (samples stay float32 in memory). */
+int kws_filter_bank_create(const double *sos, int n_sections, const int32_t *padlen, int K, kws_filter_bank **out);
+void kws_filter_bank_destroy(kws_filter_bank *bank);
+/* host: number of filters, sections per filter, and padlen[K] (may be NULL) */
+int kws_filter_bank_info(const kws_filter_bank *bank, int *K, int *n_sections, int32_t *padlen);
+
+typedef struct kws_filter_params {
+    float filter_rate;     /* fraction of clips filtered, [0, 1] */
+    int32_t rescale;       /* 1: keep the dry clip's energy over t < Lv */
+    int32_t max_samples;   /* the head the featurizer keeps, [1, KWS_FILTER_MAX_SAMPLES] */
+    int32_t reserved;      /* 0 */
+    uint64_t seed;         /* seed_f */
+} kws_filter_params;
+
+/* Filter B clips, no host synchronisation (explicit_filter is copied from the host first).  out: B x out_stride float32 (out_stride >=
+ * max_samples), row b = y[0:Lv] then zeros; lengths (device int32 B, required; may be valid_len itself when index is NULL) = Lv;
+ * filter_used (device int32 B, may be NULL unless explicit_filter is given) = k, or -1 for a dry clip.  explicit_filter (HOST int32 B,
+ * values -1..K-1, or NULL): take k (-1 = dry) from the caller instead of the draws.  In place (out == wav) needs float32 input, index
+ * NULL and out_stride == stride.  Fixed reduction order and no atomics: two calls give the same bits. */
+int kws_filter_apply(const kws_filter_bank *bank, const kws_filter_params *params, const void *wav, int wav_dtype, const int32_t *index,
+                     int B, int64_t stride, const int32_t *valid_len, int64_t position_base, int64_t step, const int32_t *explicit_filter,
+                     float *out, int64_t out_stride, int32_t *lengths, int32_t *filter_used, void *stream);
+
+/* ------------------------------------------------------------------------
  * Model: replaces the tf.keras objects built by classifier/model.py:14-46
  * get_model() (backbones classifier/models/cnn.py, rnn.py) and the work
  * Keras does inside model.fit / model.predict (train.py:75-92).

@@ -1,5 +1,5 @@
-"""Background-noise and room-reverberation augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*, kws_augment_*,
-kws_rir_bank_*, kws_reverb_apply).
+"""Background-noise, room-reverberation and filter augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*, kws_augment_*,
+kws_rir_bank_*, kws_reverb_apply, kws_filter_bank_*, kws_filter_apply).
 
 The reference makes training data robust offline: tools/audio_process/add_noise.py mixes a randomly chosen background recording into a
 `noised_rate` fraction of the clips at an SNR drawn from a list and writes one fixed *_noised.wav copy per clip.  Here the same mix is
@@ -15,6 +15,12 @@ with the impulse response of a random room and writes one *_reverb.wav copy.  He
 RIR drawn afresh, before the noise is mixed in:
 
     aug = WaveAugment(noise, rirs=simulate_rirs(64, seed=0), reverb_rate=1.0, seed=1)     # noise may be None
+
+The third tool, tools/audio_process/wav_filter.py, filters a clip with a Butterworth design (scipy.signal.butter) at zero phase
+(scipy.signal.filtfilt).  Here a bank of designs (butter_sos, in float64 numpy) is built once, and a `filter_rate` share of the clips of
+every step is filtered with one drawn afresh, after the reverberation and before the noise:
+
+    aug = WaveAugment(noise, filters=random_filters(64, seed=0), filter_rate=0.5, seed=1)   # noise may be None
 
 Argument checks run on the host; the device copy of a bank is made on first use."""
 import ctypes
@@ -257,18 +263,237 @@ def simulate_rirs(count, seed=None, rt60=(0.3, 0.7), sample_rate=None, with_geom
     return (out, geo) if with_geometry else out
 
 
+# the filter draws use seed ^ FILTER_SEED_MIX, independent of the noise and reverb draws of the same seed (include/kws.h)
+FILTER_SEED_MIX = 0xD1B54A32D192ED03
+FILTER_TYPES = ("lowpass", "highpass", "bandpass", "bandstop")
+
+
+def _zpk_poly(r):
+    return np.real(np.poly(r)) if len(r) else np.ones(1)
+
+
+def _zpk2sos(z, p, k):
+    """second-order sections (b0, b1, b2, 1, a1, a2) of a real zpk system with as many zeros as poles: conjugate pole pairs (and real
+    poles two by two) make the sections, each pole pair takes its nearest zeros, the poles closest to the unit circle come last and the
+    gain goes to the first section (the layout of scipy's zpk2sos)"""
+    tol = 1e-10
+
+    def split(r):
+        r = np.asarray(r, complex)
+        return list(r[r.imag > tol]), sorted(np.real(r[np.abs(r.imag) <= tol]))
+
+    pc, preal = split(p)
+    zc, zreal = split(z)
+    groups = [[q, np.conj(q)] for q in pc]
+    preal = sorted(preal, key=abs)
+    while len(preal) >= 2:
+        groups.append([preal.pop(), preal.pop()])
+    if preal:
+        groups.append([preal.pop()])
+    groups.sort(key=lambda g: max(abs(q) for q in g))             # closest to the unit circle last
+    zeros = [None] * len(groups)
+    for i in reversed(range(len(groups))):                         # pair the poles nearest the circle first
+        g = groups[i]
+        ref = g[0]
+        if len(g) == 2 and zc:
+            j = int(np.argmin([abs(q - ref) for q in zc]))
+            q = zc.pop(j)
+            zeros[i] = [q, np.conj(q)]
+        else:
+            want = len(g)
+            if len(zreal) < want:
+                raise ValueError("zpk system with unpaired complex zeros")
+            sel = []
+            for _ in range(want):
+                j = int(np.argmin([abs(q - ref) for q in zreal]))
+                sel.append(zreal.pop(j))
+            zeros[i] = sel
+    sos = np.zeros((len(groups), 6))
+    for i, (g, zz) in enumerate(zip(groups, zeros)):
+        b, a = _zpk_poly(zz), _zpk_poly(g)
+        sos[i, :3] = np.r_[b, np.zeros(3 - len(b))]
+        sos[i, 3:] = np.r_[a, np.zeros(3 - len(a))]
+    sos[0, :3] *= k
+    return sos
+
+
+def butter_sos(order, wn, btype="lowpass"):
+    """A digital Butterworth filter as second-order sections, float64 (scipy.signal.butter(order, wn, btype, output='sos')): wn in (0, 1)
+    as a fraction of the Nyquist frequency, a pair (low, high) for 'bandpass' / 'bandstop'.  The analog prototype's poles, pre-warping,
+    the lowpass / highpass / bandpass / bandstop transform and the bilinear transform are the textbook zpk steps."""
+    if btype not in FILTER_TYPES:
+        raise ValueError("filter type must be one of %s, got %r" % (", ".join(FILTER_TYPES), btype))
+    N = int(order)
+    if N != order or N < 1:
+        raise ValueError("filter order must be a positive integer, got %r" % (order,))
+    band = btype in ("bandpass", "bandstop")
+    wn = np.atleast_1d(np.asarray(wn, np.float64))
+    if wn.shape != ((2,) if band else (1,)):
+        raise ValueError("%s needs %s critical frequency, got %r" % (btype, "a (low, high)" if band else "one", wn.tolist()))
+    if not np.all((wn > 0) & (wn < 1)):
+        raise ValueError("critical frequencies must be in (0, 1) of Nyquist, got %r" % wn.tolist())
+    if band and not wn[0] < wn[1]:
+        raise ValueError("band edges need low < high, got %r" % wn.tolist())
+    p = -np.exp(1j * np.pi * np.arange(-N + 1, N, 2) / (2 * N))     # analog prototype, cutoff 1 rad/s
+    z = np.zeros(0, complex)
+    k = 1.0
+    fs = 2.0
+    warped = 2 * fs * np.tan(np.pi * wn / fs)
+    deg = len(p) - len(z)
+    if btype == "lowpass":
+        wo = warped[0]
+        z, p, k = z * wo, p * wo, k * wo ** deg
+    elif btype == "highpass":
+        wo = warped[0]
+        k = k * np.real(np.prod(-z) / np.prod(-p))
+        z, p = np.r_[wo / z, np.zeros(deg)], wo / p
+    else:
+        wo, bw = np.sqrt(warped[0] * warped[1]), warped[1] - warped[0]
+        if btype == "bandpass":
+            zl, pl = z * bw / 2, p * bw / 2
+            z = np.r_[zl + np.sqrt(zl ** 2 - wo ** 2), zl - np.sqrt(zl ** 2 - wo ** 2), np.zeros(deg)]
+            p = np.r_[pl + np.sqrt(pl ** 2 - wo ** 2), pl - np.sqrt(pl ** 2 - wo ** 2)]
+            k = k * bw ** deg
+        else:
+            k = k * np.real(np.prod(-z) / np.prod(-p))
+            zh, ph = (bw / 2) / z, (bw / 2) / p
+            z = np.r_[zh + np.sqrt(zh ** 2 - wo ** 2), zh - np.sqrt(zh ** 2 - wo ** 2), np.full(deg, 1j * wo), np.full(deg, -1j * wo)]
+            p = np.r_[ph + np.sqrt(ph ** 2 - wo ** 2), ph - np.sqrt(ph ** 2 - wo ** 2)]
+    fs2 = 2.0 * fs                                                    # bilinear transform
+    deg = len(p) - len(z)
+    k = k * np.real(np.prod(fs2 - z) / np.prod(fs2 - p))
+    z = np.r_[(fs2 + z) / (fs2 - z), -np.ones(deg)]
+    p = (fs2 + p) / (fs2 - p)
+    return _zpk2sos(z, p, k)
+
+
+def filter_padlen(order, btype):
+    """filtfilt's default padlen 3 max(len(a), len(b)) = 3 (n + 1), n the transfer function's order (2 order for a band filter)"""
+    n = int(order) * (2 if btype in ("bandpass", "bandstop") else 1)
+    return 3 * (n + 1)
+
+
+class FilterBank(object):
+    """Butterworth designs (tools/audio_process/wav_filter.py): specs (btype, order, freq) for 'lowpass' / 'highpass' or (btype, order,
+    (low, high)) for 'bandpass' / 'bandstop', frequencies in Hz below the Nyquist frequency of sample_rate (default pr.sample_rate).
+    Every design is butter_sos(order, 2 f / sample_rate, btype); at most FILTER_MAX_SECTIONS sections (order 8 for lowpass / highpass,
+    4 for bandpass / bandstop)."""
+
+    def __init__(self, specs, sample_rate=None):
+        from classifier.params import pr
+        sr = float(sample_rate or pr.sample_rate)
+        if isinstance(specs, tuple) and specs and isinstance(specs[0], str):
+            specs = [specs]
+        specs = list(specs)
+        if not specs:
+            raise ValueError("a filter bank needs at least one filter")
+        sos, pad, norm = [], [], []
+        for i, spec in enumerate(specs):
+            if len(spec) != 3:
+                raise ValueError("filter %d: a spec is (btype, order, freq), got %r" % (i, spec))
+            btype, order, freq = spec
+            if btype not in FILTER_TYPES:
+                raise ValueError("filter %d: type must be one of %s, got %r" % (i, ", ".join(FILTER_TYPES), btype))
+            if isinstance(order, bool) or int(order) != order or order < 1:
+                raise ValueError("filter %d: order must be a positive integer, got %r" % (i, order))
+            band = btype in ("bandpass", "bandstop")
+            sections = int(order) if band else (int(order) + 1) // 2
+            if sections > _l.FILTER_MAX_SECTIONS:
+                raise ValueError("filter %d: %s of order %d needs %d sections, more than %d (order <= %d)"
+                                 % (i, btype, order, sections, _l.FILTER_MAX_SECTIONS, _l.FILTER_MAX_SECTIONS if band else 2 * _l.FILTER_MAX_SECTIONS))
+            f = np.atleast_1d(np.asarray(freq, np.float64))
+            if f.shape != ((2,) if band else (1,)):
+                raise ValueError("filter %d: %s needs %s, got %r" % (i, btype, "(low, high) in Hz" if band else "one frequency in Hz", freq))
+            if not np.all(np.isfinite(f)) or not np.all((f > 0) & (f < sr / 2)):
+                raise ValueError("filter %d: frequencies must be in (0, %g) Hz (Nyquist), got %r" % (i, sr / 2, f.tolist()))
+            if band and not f[0] < f[1]:
+                raise ValueError("filter %d: band edges need low < high, got %r" % (i, f.tolist()))
+            sos.append(butter_sos(int(order), 2.0 * f / sr if band else 2.0 * f[0] / sr, btype))
+            pad.append(filter_padlen(order, btype))
+            norm.append((btype, int(order), tuple(float(x) for x in f) if band else float(f[0])))
+        self.specs, self.sos, self.sample_rate = norm, sos, sr
+        self.padlen = np.array(pad, np.int32)
+        self.n_sections = max(s.shape[0] for s in sos)
+        table = np.tile(np.array([1.0, 0, 0, 1.0, 0, 0]), (len(sos), self.n_sections, 1))
+        for i, s in enumerate(sos):
+            table[i, :s.shape[0]] = s
+        self.table = np.ascontiguousarray(table, np.float64)          # (K, n_sections, 6), identity sections pad the lower orders
+        self._h = None
+
+    def __len__(self):
+        return len(self.sos)
+
+    def handle(self):
+        if self._h is None:
+            _torch()
+            L = _l.get_lib()
+            h = ctypes.c_void_p()
+            _l.check(L.kws_filter_bank_create(self.table.ctypes.data, self.n_sections, self.padlen.ctypes.data, len(self.sos), ctypes.byref(h)))
+            self._h, self._L = h, L
+        return self._h
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            self._L.kws_filter_bank_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _log_uniform(rng, lo, hi):
+    return float(np.exp(rng.uniform(np.log(lo), np.log(hi))))
+
+
+def random_filters(count, types=("lowpass", "highpass", "bandpass"), order=4, seed=None, lowpass=(2000.0, 7000.0), highpass=(50.0, 500.0),
+                   notch=(300.0, 4000.0)):
+    """`count` random Butterworth specs for FilterBank, deterministic for a given seed: the type uniform over `types`, then
+    log-uniform draws: a lowpass cutoff in `lowpass` Hz, a highpass cutoff in `highpass` Hz, a bandpass as one of each (low from
+    `highpass`, high from `lowpass`), a bandstop as a third-octave notch [fc 2^(-1/6), fc 2^(1/6)] centred in `notch` Hz."""
+    count = int(count)
+    if count < 1:
+        raise ValueError("count must be >= 1, got %d" % count)
+    if isinstance(types, str):
+        types = [t for t in types.split(",") if t.strip()]
+    types = [t.strip() for t in types]
+    if not types or any(t not in FILTER_TYPES for t in types):
+        raise ValueError("filter types must be among %s, got %r" % (", ".join(FILTER_TYPES), types))
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(count):
+        t = types[int(rng.integers(len(types)))]
+        if t == "lowpass":
+            out.append((t, order, _log_uniform(rng, *lowpass)))
+        elif t == "highpass":
+            out.append((t, order, _log_uniform(rng, *highpass)))
+        elif t == "bandpass":
+            lo = _log_uniform(rng, *highpass)
+            out.append((t, order, (lo, _log_uniform(rng, *lowpass))))
+        else:
+            fc = _log_uniform(rng, *notch)
+            out.append((t, order, (fc * 2.0 ** (-1.0 / 6.0), fc * 2.0 ** (1.0 / 6.0))))
+    return out
+
+
 class WaveAugment(object):
     """Per-clip background noise (add_noise.py:19-35) at an SNR drawn from `snr` for a `noised_rate` fraction of the clips, and an
     optional time shift of up to +-time_shift_ms (off by default; the reference has none).  With `rirs` (a RirBank, or anything RirBank
     accepts) a `reverb_rate` fraction of the clips is first convolved with a RIR drawn from the bank (audio_reverberation.py), with the
-    clip's energy kept when `rescale` is on; `noise` may then be None.  Draws are counter-based, keyed by (seed, step) and indexed by the
-    clip's position in the global batch."""
+    clip's energy kept when `rescale` is on; `noise` may then be None.  With `filters` (a FilterBank, or specs FilterBank accepts) a
+    `filter_rate` fraction of the clips is then filtered at zero phase with a design drawn from the bank (wav_filter.py), energy kept
+    likewise.  Draws are counter-based, keyed by (seed, step) and indexed by the clip's position in the global batch."""
 
     def __init__(self, noise, snr=(50,), noised_rate=1.0, time_shift_ms=0, seed=None, sample_rate=None, rirs=None, reverb_rate=1.0,
-                 rescale=True):
+                 rescale=True, filters=None, filter_rate=1.0):
         from classifier.params import pr
-        if noise is None and rirs is None:
+        if noise is None and rirs is None and filters is None:
             raise ValueError("WaveAugment needs a noise bank, a RIR bank or both")
+        frate = float(filter_rate)
+        if not 0.0 <= frate <= 1.0:
+            raise ValueError("filter_rate must be in [0, 1], got %r" % filter_rate)
         rrate = float(reverb_rate)
         if not 0.0 <= rrate <= 1.0:
             raise ValueError("reverb_rate must be in [0, 1], got %r" % reverb_rate)
@@ -284,7 +509,8 @@ class WaveAugment(object):
             raise ValueError("time_shift_ms must be >= 0, got %r" % time_shift_ms)
         self.noise = None if noise is None else noise if isinstance(noise, NoiseBank) else NoiseBank(noise)
         self.rirs = None if rirs is None else rirs if isinstance(rirs, RirBank) else RirBank(rirs)
-        self.reverb_rate, self.rescale = rrate, bool(rescale)
+        self.filters = None if filters is None else filters if isinstance(filters, FilterBank) else FilterBank(filters, sample_rate)
+        self.reverb_rate, self.rescale, self.filter_rate = rrate, bool(rescale), frate
         self.snr, self.noised_rate, self.time_shift_ms = snr, rate, float(time_shift_ms)
         sr = int(sample_rate or pr.sample_rate)
         self.max_shift = int(round(self.time_shift_ms * sr / 1000.0))
@@ -344,6 +570,64 @@ class WaveAugment(object):
         if ex is not None:
             torch.cuda.current_stream().synchronize()       # the host choices are copied from pageable memory
         return out, lengths, (rir_used if rir_used is not False else None)
+
+    @property
+    def filter_seed(self):
+        return self.seed ^ FILTER_SEED_MIX
+
+    def filter_params(self, max_samples):
+        p = _l.KwsFilterParams()
+        p.filter_rate, p.rescale, p.max_samples, p.reserved, p.seed = self.filter_rate, int(self.rescale), int(max_samples), 0, self.filter_seed
+        return p
+
+    def filter(self, wav, valid_len=None, index=None, step=0, position_base=0, explicit=None, max_samples=None, out=None, lengths=None,
+               filter_used=None):
+        """-> (out (B, max_samples) float32, lengths (B,) int32, filter_used (B,) int32): the B clips wav[index] (default: every row),
+        each filtered at zero phase with the design drawn for (seed, step) at global position position_base + b (filter_used = its
+        index) or left dry (filter_used = -1; also every clip of Lv <= padlen), head-aligned, zeros after.  explicit: B ints in
+        [-1, len(filters)) instead of the draws.  out / lengths / filter_used: optional preallocated CUDA buffers (out may be wider than
+        max_samples, and may be wav itself for a float32 wav without index; lengths may be valid_len then; filter_used=False skips it)."""
+        from classifier.params import pr
+        torch = _torch()
+        if self.filters is None:
+            raise ValueError("this WaveAugment has no filter bank")
+        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
+            raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
+        rows, stride = wav.shape
+        B, ix = rows, 0
+        if index is not None:
+            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
+                raise ValueError("index must be a contiguous CUDA int32 vector")
+            B, ix = index.numel(), index.data_ptr()
+        vl = 0
+        if valid_len is not None:
+            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
+                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
+            vl = valid_len.data_ptr()
+        ms = int(pr.max_samples if max_samples is None else max_samples)
+        ex = None
+        if explicit is not None:
+            ex = np.ascontiguousarray(np.asarray(explicit).reshape(-1), np.int32)
+            if ex.shape != (B,):
+                raise ValueError("explicit filter choice has %s entries for %d clips" % (ex.shape, B))
+            if filter_used is False:
+                filter_used = None                          # the explicit choices are staged there
+        if out is None:
+            out = torch.empty((B, ms), dtype=torch.float32, device=wav.device)
+        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] < ms or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError("out must be a contiguous float32 CUDA tensor of at least (%d, %d)" % (B, ms))
+        if lengths is None:
+            lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
+        if filter_used is None:
+            filter_used = torch.empty((B,), dtype=torch.int32, device=wav.device)
+        _l.check(_l.get_lib().kws_filter_apply(self.filters.handle(), ctypes.byref(self.filter_params(ms)), wav.data_ptr(), _wav_code(wav), ix,
+                                               B, stride, vl, int(position_base), int(step), None if ex is None else ex.ctypes.data,
+                                               out.data_ptr(), out.shape[1], lengths.data_ptr(),
+                                               filter_used.data_ptr() if filter_used is not False else None,
+                                               torch.cuda.current_stream().cuda_stream))
+        if ex is not None:
+            torch.cuda.current_stream().synchronize()       # the host choices are copied from pageable memory
+        return out, lengths, (filter_used if filter_used is not False else None)
 
     def params(self, max_samples):
         p = _l.KwsAugmentParams()

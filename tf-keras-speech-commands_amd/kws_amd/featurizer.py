@@ -86,8 +86,8 @@ class Featurizer(object):
         the B rows wav[index[b]] in place of all rows (kws_featurize_gather: a shuffled minibatch of a device-resident dataset, no copy).
         augment: optional kws_amd.augment.WaveAugment: featurize the clips with background noise mixed in, drawn for (its seed, `step`)
         at global batch positions position_base + b (kws_augment_plan + kws_featurize_gather_augmented).  With a RIR bank the clips are
-        reverberated first (kws_reverb_apply into a scratch buffer of this featurizer), then noised (if it has a noise bank) and featurized
-        from there."""
+        reverberated first (kws_reverb_apply into a scratch buffer of this featurizer); with a filter bank they are filtered next
+        (kws_filter_apply, in place in that scratch); then noised (if it has a noise bank) and featurized from there."""
         torch = _torch()
         if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous CUDA tensor of shape (B, stride)")
@@ -108,12 +108,17 @@ class Featurizer(object):
             if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
                 raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
             vl = valid_len.data_ptr()
-        if augment is not None and augment.rirs is not None:
-            # reverberation first, into this featurizer's scratch on the call's stream; then noise (or nothing) on the wet clips
+        if augment is not None and (augment.rirs is not None or augment.filters is not None):
+            # reverberation, then the filter (in place), into this featurizer's scratch on the call's stream; then noise (or nothing)
             ms = g["max_samples"]
-            wet, lens, _ = augment.reverberate(wav, valid_len=valid_len, index=index, step=step, position_base=position_base,
-                                               max_samples=ms, out=self._reverb_scratch(B, ms, wav.device), lengths=self._reverb_lengths(B, wav.device),
-                                               rir_used=False)
+            wet, lens = self._reverb_scratch(B, ms, wav.device), self._reverb_lengths(B, wav.device)
+            if augment.rirs is not None:
+                augment.reverberate(wav, valid_len=valid_len, index=index, step=step, position_base=position_base, max_samples=ms, out=wet,
+                                    lengths=lens, rir_used=False)
+                wav, index, valid_len = wet, None, lens
+            if augment.filters is not None:
+                augment.filter(wav, valid_len=valid_len, index=index, step=step, position_base=position_base, max_samples=ms, out=wet,
+                               lengths=lens, filter_used=False)
             wav, index, valid_len, stride, ix, vl = wet, None, lens, ms, 0, lens.data_ptr()
             if augment.noise is None:
                 augment = None

@@ -68,6 +68,16 @@ class KwsReverbParams(ctypes.Structure):
 REVERB_MAX_SAMPLES = 16384
 
 
+class KwsFilterParams(ctypes.Structure):
+    _fields_ = [("filter_rate", ctypes.c_float), ("rescale", ctypes.c_int32), ("max_samples", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
+FILTER_MAX_SECTIONS = 4
+FILTER_MAX_PADLEN = 32
+FILTER_MAX_SAMPLES = 16320
+
+
 MODEL_KINDS = {"simple_cnn": 0, "simple_cnn_lite": 1, "simple_gru": 2, "simple_lstm": 3}
 BANK_MEL, BANK_BARK = 0, 1
 WAV_F32, WAV_I16 = 0, 1
@@ -180,6 +190,11 @@ def get_lib():
     L.kws_rir_bank_destroy.restype = None
     L.kws_rir_bank_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.kws_reverb_apply.argtypes = [vp, ctypes.POINTER(KwsReverbParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp]
+    L.kws_filter_bank_create.argtypes = [vp, i32, vp, i32, ctypes.POINTER(vp)]
+    L.kws_filter_bank_destroy.argtypes = [vp]
+    L.kws_filter_bank_destroy.restype = None
+    L.kws_filter_bank_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
+    L.kws_filter_apply.argtypes = [vp, ctypes.POINTER(KwsFilterParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp]
     _lib = L
     return L
 

@@ -9,7 +9,9 @@ Beyond the reference: --raw_audio trains on the waveforms (get_audio_dataset; ev
 pipeline), and --noise_path mixes background noise into every training clip afresh in every epoch, with the knobs of the reference's
 offline tool tools/audio_process/add_noise.py (--snr, --noised_rate) and an optional random time shift (--time_shift_ms).  --rir_path
 (a folder of room impulse responses) or --simulate_rirs N (N simulated rooms) reverberates a --reverb_rate share of the training clips
-before the noise, as tools/audio_process/audio_reverberation.py does offline; either works without --noise_path."""
+before the noise, as tools/audio_process/audio_reverberation.py does offline; either works without --noise_path.  --filter_rate filters
+that share of the training clips at zero phase with a Butterworth design drawn from a bank of --num_filters random ones
+(--filter_types, --filter_order), after the room and before the noise, as tools/audio_process/wav_filter.py does offline."""
 import argparse
 import os
 import sys
@@ -46,6 +48,10 @@ def main(argv=None):
         raise SystemExit('--rir_path / --simulate_rirs need --raw_audio (the waveforms are reverberated before featurization)')
     if args.simulate_rirs is not None and args.simulate_rirs < 1:
         raise SystemExit('--simulate_rirs needs a positive number of rooms')
+    if args.filter_rate is not None and not args.raw_audio:
+        raise SystemExit('--filter_rate needs --raw_audio (the waveforms are filtered before featurization)')
+    if args.num_filters < 1:
+        raise SystemExit('--num_filters needs a positive bank size')
 
     # callbacks for training process
     logging = JsonlLogger(os.path.join(log_dir, 'train_log.jsonl'))
@@ -83,15 +89,23 @@ def main(argv=None):
         from kws_amd.augment import RirBank, simulate_rirs
         rirs = RirBank(args.rir_path if args.rir_path else simulate_rirs(args.simulate_rirs))
     reverb_rate = 1.0 if args.reverb_rate is None else args.reverb_rate
+    filters = None
+    filter_rate = 1.0 if args.filter_rate is None else args.filter_rate
+    if args.filter_rate is not None:
+        from kws_amd.augment import FilterBank, random_filters
+        try:
+            filters = FilterBank(random_filters(args.num_filters, types=args.filter_types, order=args.filter_order))
+        except ValueError as e:
+            raise SystemExit('--filter_types / --filter_order: %s' % e)
     if args.noise_path:
         from kws_amd.augment import NoiseBank, WaveAugment
         augment = WaveAugment(NoiseBank(args.noise_path), snr=args.snr, noised_rate=args.noised_rate, time_shift_ms=args.time_shift_ms,
-                              rirs=rirs, reverb_rate=reverb_rate)
+                              rirs=rirs, reverb_rate=reverb_rate, filters=filters, filter_rate=filter_rate)
     elif args.time_shift_ms:
         raise SystemExit('--time_shift_ms is part of the noise augmentation: give --noise_path too')
-    elif rirs is not None:
+    elif rirs is not None or filters is not None:
         from kws_amd.augment import WaveAugment
-        augment = WaveAugment(None, rirs=rirs, reverb_rate=reverb_rate)
+        augment = WaveAugment(None, rirs=rirs, reverb_rate=reverb_rate, filters=filters, filter_rate=filter_rate)
 
     # prepare optimizer
     if args.decay_type:
@@ -182,6 +196,15 @@ def parse_args(argv=None):
                         help="simulate this many random rooms (the reference's gpuRIR draws) as the RIR bank (needs --raw_audio)")
     parser.add_argument('--reverb_rate', type=float, required=False, default=None,
                         help="random percentage rate of reverberating the training clips (0.0~1.0). default=1.0")
+    # Butterworth filtering (tools/audio_process/wav_filter.py, drawn per clip and per step)
+    parser.add_argument('--filter_rate', type=float, required=False, default=None,
+                        help="random percentage rate of filtering the training clips (0.0~1.0; needs --raw_audio). default: off")
+    parser.add_argument('--filter_types', type=str, required=False, default='lowpass,highpass,bandpass',
+                        help="comma list of the filter types drawn for the bank (lowpass, highpass, bandpass, bandstop). default=%(default)s")
+    parser.add_argument('--filter_order', type=int, required=False, default=4,
+                        help="order of the Butterworth filters. default=%(default)s")
+    parser.add_argument('--num_filters', type=int, required=False, default=64,
+                        help="number of random filters in the bank. default=%(default)s")
     return parser.parse_args(argv)
 
 
