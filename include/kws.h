@@ -452,6 +452,82 @@ int kws_model_set_overlap_point(kws_model *m, int point);
 int64_t kws_model_grad_split(const kws_model *m);
 
 /* ------------------------------------------------------------------------
+ * int8 post-training quantization of simple_cnn: what a user of the reference does with the MNN quantizer
+ * (inference/MNN/configs/quantizeConfig.json, weight_quantize_method MAX_ABS) or tools/model_converter/custom_tflite_convert.py
+ * (--post_training_quantize) before shipping the model, and then measures with eval.py.  A quantized model is a frozen snapshot: it
+ * does not follow later changes of the float weights.  Scope: KWS_SIMPLE_CNN at the default geometry (30 x 20 features; pooled maps
+ * 15 x 10 -> 7 x 5 -> 4 x 3 -> 2 x 1) and C <= KWS_QUANT_MAX_CLASSES; everything else is KWS_ERR_UNSUPPORTED.
+ *
+ * Contract.  Symmetric, zero-point 0 everywhere: "same" padding pads with code 0 and every accumulator is an exact int32.
+ *   Quantized tensors t0 = the features x, t1 = a1 (after pool 1), t2 = a2 (after pool 2), t3 = a3 (conv3 -> BN -> ReLU6),
+ *   t4 = a4 (after pool 4), t5 = d (Dense -> ReLU6).
+ *   Activation scales s_t = A_t / 127 in double.  A_0 = calibrated max|x|; for t >= 1 A_t = min(calibrated max, 6), a calibrated 0
+ *   (dead layer) becoming 6; KWS_QUANT_RELU6 uses A_t = 6 for t >= 1.  A non-finite or negative A_t, or A_0 == 0, is KWS_ERR_INVALID.
+ *   Weights, per output channel c, MAX_ABS in double: r_c = max|W[..., c]|, s_wc = r_c / 127 (1 when r_c == 0),
+ *   q = clamp(rint(W / s_wc), -127, 127), rint rounding half to even; all four conv kernels (HWIO), Dense (256, 128), head (128, C).
+ *   BatchNorm fold in double: g = gamma / sqrt(moving_var + eps), h = beta - moving_mean * g, eps = the library's float 1e-3 widened.
+ *   Per-channel constants, each computed in double in the order written and rounded ONCE to fp32:
+ *     conv l = 1..4: M[c] = ((s_in * s_wc) * g_c) / s_out,  Bq[c] = h_c / s_out
+ *     Dense:         M[c] = (s_4 * s_wc) / s_5,             Bq[c] = bias_c / s_5
+ *     head:          Mh[c] = s_5 * s_wc;   input: inv_s0 = 1 / s_0
+ *   Device arithmetic (fp32, every multiply and add rounded separately -- no contraction -- and rint half to even):
+ *     input:           code = clamp(rint(x * inv_s0), -127, 127)
+ *     conv1-3, Dense:  code = clamp(rint((float)acc * M[c] + Bq[c]), 0, 127)          (the clamp is ReLU6)
+ *     conv4:           acc = max(acc, 0) first (Conv2D(activation='relu') -> BN -> ReLU6), then as conv1-3
+ *     max pooling (2 x 2, stride 2, valid) on the codes AFTER the epilogue (a negative gamma makes the epilogue decreasing)
+ *     head:            logit = (float)acc * Mh[c] + bias[c], then the fp32 softmax of the float head (first maximum wins the arg-max)
+ *   |acc| < 2^24 everywhere (conv4: 576 * 127^2 ~ 9.3 M), so (float)acc is exact.
+ * Divergences from MNN / TFLite: symmetric int8 instead of TFLite's asymmetric uint8; per-channel weight scales; max calibration
+ * instead of MNN's KL; fp32 epilogue multipliers instead of fixed-point ones; fp32 softmax.
+ * ---------------------------------------------------------------------- */
+#define KWS_QUANT_TENSORS 6
+#define KWS_QUANT_MAX_CLASSES 48
+enum { KWS_QUANT_MAX = 0, KWS_QUANT_RELU6 = 1 };
+
+/* Calibration: runs the fp32 inference forward (BN moving statistics, no dropout) of B clips and max-reduces into amax (6 DEVICE floats):
+ * amax[0] = max |x|, amax[1..5] = max of t1..t5 (all >= 0).  The caller zeroes amax once; every call folds its batch into the running
+ * maxima, so calls over the halves of a set give the call over the whole set.  One block per clip, exact fp32; does not use or touch
+ * the tuned forward's kernels.  ws may be NULL (no scratch needed); B = 0 is a no-op. */
+int kws_model_calibrate(kws_model *m, const float *feat, int B, const float *params, const float *state, void *ws, size_t ws_bytes,
+                        float *amax, void *stream);
+
+/* The quantized network on the HOST (every array in Keras order, filled by kws_quantize_simple_cnn) */
+typedef struct kws_qsimple_cnn {
+    int32_t num_classes;                /* C, 2..KWS_QUANT_MAX_CLASSES */
+    int32_t method;                     /* KWS_QUANT_MAX / KWS_QUANT_RELU6 */
+    float inv_s0;                       /* 1 / s_0 */
+    int32_t reserved;
+    double amax[KWS_QUANT_TENSORS];     /* A_0..A_5 after the rules above */
+    double scale[KWS_QUANT_TENSORS];    /* s_0..s_5 (reporting) */
+    int8_t conv_w1[3 * 3 * 1 * 16];     /* HWIO */
+    int8_t conv_w2[3 * 3 * 16 * 32];
+    int8_t conv_w3[3 * 3 * 32 * 64];
+    int8_t conv_w4[3 * 3 * 64 * 128];
+    int8_t dense_w[256 * 128];          /* (in, out) */
+    int8_t head_w[128 * KWS_QUANT_MAX_CLASSES];   /* (128, C): the first 128 C entries, row stride C */
+    float M1[16], B1[16], M2[32], B2[32], M3[64], B3[64], M4[128], B4[128];
+    float Md[128], Bd[128];
+    float Mh[KWS_QUANT_MAX_CLASSES], head_bias[KWS_QUANT_MAX_CLASSES];
+} kws_qsimple_cnn;
+
+/* Host only (no GPU): params_host / state_host are the model's flat buffers (kws_model_param_count / state_count floats, the layout of
+ * kws_model_tensor_info), amax_host the 6 calibrated maxima.  Fills *out by the contract above. */
+int kws_quantize_simple_cnn(const kws_model *m, const float *params_host, const float *state_host, const float *amax_host, int method,
+                            kws_qsimple_cnn *out);
+
+/* A quantized model on the CURRENT device: uploads q's arrays and packs the weights into the fragment-major layout the kernel reads.
+ * The only way to build one (a saved quantized checkpoint is loaded through it too).  m gives the model kind and geometry. */
+typedef struct kws_qmodel kws_qmodel;
+int kws_qmodel_create(const kws_model *m, const kws_qsimple_cnn *q, kws_qmodel **out);
+void kws_qmodel_destroy(kws_qmodel *q);
+/* bytes of device scratch kws_qmodel_forward needs for batch B (the single-kernel forward needs none: 0) */
+int64_t kws_qmodel_workspace_bytes(const kws_qmodel *q, int B);
+/* feat (B, 30, 20) float32 -> logits (B, C) float32, probs (B, C) float32, argmax (B) int32; each may be NULL.  B = 0 is a no-op, B
+ * need not be a multiple of anything.  One kernel on `stream`, no host synchronisation: capturable into a hipGraph. */
+int kws_qmodel_forward(const kws_qmodel *q, const float *feat, int B, void *ws, size_t ws_bytes, float *logits, float *probs,
+                       int32_t *argmax, void *stream);
+
+/* ------------------------------------------------------------------------
  * Data-parallel exchange (RCCL over xGMI).  New: the reference trains in one
  * process (train.py:81-92, model.fit(..., workers=1) at :90-91); this is the
  * collective SURVEY.md section 5 / 8(e) specify around that loop.  One process

@@ -465,6 +465,74 @@ class KWSModel(object):
     def test_on_batch(self, x, y):
         return self.evaluate(x, y, batch_size=len(x))
 
+    def quantize(self, x_calib, method='max', batch_size=None):
+        """int8 post-training quantization of a simple_cnn (what the reference's users do with the MNN quantizer or
+        custom_tflite_convert.py --post_training_quantize before deploying): calibrates the six quantized tensors on x_calib (features
+        or raw audio, as predict takes) with the fp32 forward on the GPU, quantizes the CURRENT weights (kws_amd.quant, include/kws.h)
+        with method 'max' or 'relu6' and returns a QuantizedKWSModel (predict / evaluate / save).  A snapshot: it does not follow
+        later training."""
+        import torch
+        from kws_amd.quant import QuantizedCNN, calibrate
+        dm = self._device()
+        xd, is_audio = self._to_device_inputs(x_calib)
+        if xd.shape[0] == 0:
+            raise ValueError("quantize needs at least one calibration sample")
+        batch_size = int(batch_size or 4096)
+        amax = torch.zeros((_l.QUANT_TENSORS,), dtype=torch.float32, device=xd.device)
+        for i in range(0, xd.shape[0], batch_size):
+            calibrate(dm, self._features_of(xd[i:i + batch_size], is_audio).contiguous(), amax=amax)
+        return QuantizedKWSModel(self, QuantizedCNN.from_model(dm, amax.cpu().numpy(), method))
+
+
+class QuantizedKWSModel(object):
+    """The int8 model KWSModel.quantize returns: predict / evaluate as KWSModel's (features or raw audio in), computed by the int8
+    forward (one kernel per batch).  `quantized` is the kws_amd.quant.QuantizedCNN (arrays, save)."""
+
+    def __init__(self, model, quantized):
+        self.model, self.quantized = model, quantized
+        self.num_classes = model.num_classes
+
+    def save(self, filepath):
+        self.quantized.save(filepath)
+
+    def _batches(self, x, batch_size):
+        xd, is_audio = self.model._to_device_inputs(x)
+        batch_size = int(batch_size or 4096)
+        for i in range(0, xd.shape[0], batch_size):
+            yield i, self.quantized.forward(self.model._features_of(xd[i:i + batch_size], is_audio).contiguous())
+
+    def predict(self, x, batch_size=None, verbose=0, **kwargs):
+        """-> (N, num_classes) softmax scores of the int8 network (numpy)"""
+        import torch
+        out = [probs for _, (probs, _) in self._batches(x, batch_size)]
+        if not out:
+            return np.zeros((0, self.num_classes), np.float32)
+        return torch.cat(out).cpu().numpy()
+
+    __call__ = predict
+
+    def predict_classes(self, x, batch_size=None):
+        """-> (N,) int32 arg-max of the int8 network (numpy)"""
+        import torch
+        out = [am for _, (_, am) in self._batches(x, batch_size)]
+        return torch.cat(out).cpu().numpy() if out else np.zeros((0,), np.int32)
+
+    def evaluate(self, x, y, batch_size=None, verbose=0, **kwargs):
+        """-> [loss, accuracy] of the int8 network; the loss is the compiled one of the float model (plain sparse cross-entropy when it
+        was never compiled)"""
+        import torch
+        from classifier.loss import SparseCategoricalCrossEntropy
+        loss = self.model.loss or SparseCategoricalCrossEntropy()
+        n = len(x)
+        yd = self.model._labels(y, n)
+        loss_sum = torch.zeros((), dtype=torch.float64, device=yd.device)
+        hits = torch.zeros((), dtype=torch.float64, device=yd.device)
+        for i, (probs, am) in self._batches(x, batch_size):
+            yb = yd[i:i + probs.shape[0]]
+            loss_sum += loss(yb, probs).double().sum()
+            hits += (am == yb).double().sum()
+        return [float(loss_sum.item()) / max(n, 1), float(hits.item()) / max(n, 1)]
+
 
 def get_model(model_type, num_classes, batch_size=None, weights_path=None):
     """simple_cnn / simple_cnn_lite (4-D input) or simple_gru / simple_lstm (3-D input) + Dense softmax 'score_predict'"""

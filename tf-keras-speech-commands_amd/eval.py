@@ -37,6 +37,33 @@ def evaluate_accuracy(model, x, y, class_names, batch_size=4096):
     return (float(np.trace(cm)) / total if total else 0.0), cm
 
 
+def evaluate_int8(model, x, y, class_names, x_calib, calib_samples=1000, method='max', batch_size=4096, seed=0):
+    """int8 post-training quantization (KWSModel.quantize) calibrated on `calib_samples` clips of x_calib drawn without replacement
+    (seeded), then scored on (x, y) -> (quantized model, int8 accuracy, fp32 / int8 arg-max agreement, int8 confusion matrix)"""
+    import torch
+    n_cal = min(int(calib_samples), len(x_calib))
+    idx = np.sort(np.random.default_rng(seed).choice(len(x_calib), n_cal, replace=False))
+    qmodel = model.quantize(np.asarray(x_calib)[idx], method=method, batch_size=batch_size)
+    dm = model._device()
+    xd, is_audio = model._to_device_inputs(x)
+    yd = model._labels(y, xd.shape[0])
+    C = len(class_names)
+    counts = torch.zeros((C, C), dtype=torch.int32, device=xd.device)
+    agree = torch.zeros((), dtype=torch.int64, device=xd.device)
+    L = _l.get_lib()
+    for i in range(0, xd.shape[0], batch_size):
+        f = model._features_of(xd[i:i + batch_size], is_audio).contiguous()
+        _, am32 = dm.forward(f, False, True)
+        _, am8 = qmodel.quantized.forward(f)
+        agree += (am32 == am8).sum()
+        yb = yd[i:i + batch_size].contiguous()
+        _l.check(L.kws_confusion_counts(yb.data_ptr(), am8.data_ptr(), yb.numel(), C, counts.data_ptr(),
+                                        torch.cuda.current_stream().cuda_stream))
+    cm = counts.cpu().numpy().astype(np.int64)
+    total = int(cm.sum())
+    return qmodel, (float(np.trace(cm)) / total if total else 0.0), (float(agree.item()) / total if total else 0.0), cm
+
+
 def print_confusion_matrix(cm, class_names):
     w = max(8, max(len(c) for c in class_names) + 1)
     print(' ' * w + ''.join('%*s' % (w, c[:w - 1]) for c in class_names))
@@ -52,6 +79,12 @@ def main():
     parser.add_argument('--classes_path', type=str, required=True)
     parser.add_argument('--params_path', type=str, default=None)
     parser.add_argument('--batch_size', type=int, default=4096)
+    parser.add_argument('--int8', default=False, action='store_true',
+                        help='also quantize the model to int8 (post-training, simple_cnn) and report its accuracy and agreement')
+    parser.add_argument('--calib_path', type=str, default=None, help='dataset to calibrate the int8 ranges on (default: the evaluated set)')
+    parser.add_argument('--calib_samples', type=int, default=1000, help='calibration clips, drawn with a fixed seed')
+    parser.add_argument('--quant_method', type=str, default='max', choices=['max', 'relu6'])
+    parser.add_argument('--save_quantized', type=str, default=None, help='write the int8 model to this .npz')
     args = parser.parse_args()
     class_names = get_classes(args.classes_path)
     assert class_names[0] == 'background', '1st class should be background.'
@@ -62,6 +95,16 @@ def main():
     acc, cm = evaluate_accuracy(model, x, y, class_names, args.batch_size)
     print('%d correct out of %d samples, accuracy %.4f' % (int(np.trace(cm)), int(cm.sum()), acc))
     print_confusion_matrix(cm, class_names)
+    if args.int8:
+        x_calib = x if not args.calib_path else get_dataset(args.calib_path, class_names)[0]
+        qmodel, acc8, agree, cm8 = evaluate_int8(model, x, y, class_names, x_calib, args.calib_samples, args.quant_method, args.batch_size)
+        print('int8 (%s calibration, %d clips): %d correct out of %d samples, accuracy %.4f'
+              % (args.quant_method, min(args.calib_samples, len(x_calib)), int(np.trace(cm8)), int(cm8.sum()), acc8))
+        print('fp32 / int8 argmax agreement %.4f' % agree)
+        print_confusion_matrix(cm8, class_names)
+        if args.save_quantized:
+            qmodel.save(args.save_quantized)
+            print('Saved int8 model {}.'.format(args.save_quantized))
 
 
 if __name__ == '__main__':

@@ -77,6 +77,24 @@ FILTER_MAX_SECTIONS = 4
 FILTER_MAX_PADLEN = 32
 FILTER_MAX_SAMPLES = 16320
 
+QUANT_TENSORS = 6
+QUANT_MAX_CLASSES = 48
+QUANT_MAX, QUANT_RELU6 = 0, 1
+QUANT_METHODS = {"max": QUANT_MAX, "relu6": QUANT_RELU6}
+
+
+class KwsQSimpleCnn(ctypes.Structure):
+    """kws_qsimple_cnn: the int8 simple_cnn on the host (include/kws.h)"""
+    _fields_ = [("num_classes", ctypes.c_int32), ("method", ctypes.c_int32), ("inv_s0", ctypes.c_float), ("reserved", ctypes.c_int32),
+                ("amax", ctypes.c_double * QUANT_TENSORS), ("scale", ctypes.c_double * QUANT_TENSORS),
+                ("conv_w1", ctypes.c_int8 * (9 * 16)), ("conv_w2", ctypes.c_int8 * (9 * 16 * 32)),
+                ("conv_w3", ctypes.c_int8 * (9 * 32 * 64)), ("conv_w4", ctypes.c_int8 * (9 * 64 * 128)),
+                ("dense_w", ctypes.c_int8 * (256 * 128)), ("head_w", ctypes.c_int8 * (128 * QUANT_MAX_CLASSES)),
+                ("M1", ctypes.c_float * 16), ("B1", ctypes.c_float * 16), ("M2", ctypes.c_float * 32), ("B2", ctypes.c_float * 32),
+                ("M3", ctypes.c_float * 64), ("B3", ctypes.c_float * 64), ("M4", ctypes.c_float * 128), ("B4", ctypes.c_float * 128),
+                ("Md", ctypes.c_float * 128), ("Bd", ctypes.c_float * 128),
+                ("Mh", ctypes.c_float * QUANT_MAX_CLASSES), ("head_bias", ctypes.c_float * QUANT_MAX_CLASSES)]
+
 
 MODEL_KINDS = {"simple_cnn": 0, "simple_cnn_lite": 1, "simple_gru": 2, "simple_lstm": 3}
 BANK_MEL, BANK_BARK = 0, 1
@@ -195,6 +213,14 @@ def get_lib():
     L.kws_filter_bank_destroy.restype = None
     L.kws_filter_bank_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.kws_filter_apply.argtypes = [vp, ctypes.POINTER(KwsFilterParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp]
+    L.kws_model_calibrate.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp]
+    L.kws_quantize_simple_cnn.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(KwsQSimpleCnn)]
+    L.kws_qmodel_create.argtypes = [vp, ctypes.POINTER(KwsQSimpleCnn), ctypes.POINTER(vp)]
+    L.kws_qmodel_destroy.argtypes = [vp]
+    L.kws_qmodel_destroy.restype = None
+    L.kws_qmodel_workspace_bytes.argtypes = [vp, i32]
+    L.kws_qmodel_workspace_bytes.restype = i64
+    L.kws_qmodel_forward.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp, vp]
     _lib = L
     return L
 

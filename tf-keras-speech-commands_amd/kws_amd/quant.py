@@ -1,0 +1,189 @@
+"""int8 post-training quantization of simple_cnn (include/kws.h: kws_model_calibrate, kws_quantize_simple_cnn, kws_qmodel_*).
+
+The reference quantizes a trained model outside Python (the MNN quantizer with inference/MNN/configs/quantizeConfig.json, or
+tools/model_converter/custom_tflite_convert.py --post_training_quantize) and measures it with eval.py.  Here:
+
+    amax = calibrate(dm, feature_batches)                 # fp32 forward on the GPU, running maxima of the six quantized tensors
+    q = QuantizedCNN.from_model(dm, amax, method="max")   # host quantizer (the contract of include/kws.h), uploaded to the device
+    probs, argmax = q.forward(features)                   # ONE int8 kernel from features to probabilities
+    q.save("model_int8.npz"); q = QuantizedCNN.load("model_int8.npz")
+
+A QuantizedCNN is a frozen snapshot of the weights it was made from."""
+import ctypes
+
+import numpy as np
+
+from . import lib as _l
+
+_SHAPES = {"conv_w1": (3, 3, 1, 16), "conv_w2": (3, 3, 16, 32), "conv_w3": (3, 3, 32, 64), "conv_w4": (3, 3, 64, 128),
+           "dense_w": (256, 128)}
+_EPILOGUE = ("M1", "B1", "M2", "B2", "M3", "B3", "M4", "B4", "Md", "Bd")
+_FORMAT = "kws_int8_simple_cnn/1"
+
+
+def _torch():
+    import torch
+    if not torch.cuda.is_available():
+        raise _l.KwsError(-3, "no HIP device visible to torch: int8 inference has no CPU fallback")
+    return torch
+
+
+def _as_feature_tensor(x, spec):
+    torch = _torch()
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32)))
+    n = spec.n_features * spec.feature_size
+    if t.numel() % n:
+        raise ValueError("features must have shape (B, %d, %d[, 1])" % (spec.n_features, spec.feature_size))
+    return t.reshape(t.numel() // n, spec.n_features, spec.feature_size).to(torch.float32).cuda().contiguous()
+
+
+def calibrate(dm, feature_batches, amax=None):
+    """Running maxima (numpy float32 (6,)) of t0..t5 -- max|x|, a1, a2, a3, a4, d -- of the fp32 inference forward of a simple_cnn
+    DeviceModel over `feature_batches` (one (B, n_features, feature_size[, 1]) array / tensor, or an iterable of them).  `amax`: a
+    CUDA float32 (6,) tensor to fold the batches into (the running maxima of earlier calls); a fresh zero one by default."""
+    torch = _torch()
+    L = _l.get_lib()
+    if amax is None:
+        amax = torch.zeros((_l.QUANT_TENSORS,), dtype=torch.float32, device=dm.device)
+    elif amax.dtype != torch.float32 or not amax.is_cuda or amax.numel() != _l.QUANT_TENSORS:
+        raise ValueError("amax must be a CUDA float32 tensor of %d values" % _l.QUANT_TENSORS)
+    if isinstance(feature_batches, (np.ndarray, torch.Tensor)):
+        feature_batches = [feature_batches]
+    for fb in feature_batches:
+        f = _as_feature_tensor(fb, dm.spec)
+        _l.check(L.kws_model_calibrate(dm.spec.handle, f.data_ptr(), f.shape[0], dm.params.data_ptr(), dm.state.data_ptr(), None, 0,
+                                       amax.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return amax.cpu().numpy()
+
+
+class QuantizedCNN(object):
+    """An int8 simple_cnn on the current HIP device (kws_qmodel).  Build it with from_model or load."""
+
+    def __init__(self, spec, qstruct):
+        self.spec = spec
+        self._q = qstruct
+        self._L = _l.get_lib()
+        self._h = ctypes.c_void_p()
+        self.device = None
+
+    def _handle(self):
+        """the device copy (kws_qmodel_create on the current device at the first forward: quantizing, arrays and save / load are
+        host-only)"""
+        if not self._h.value:
+            torch = _torch()
+            _l.check(self._L.kws_qmodel_create(self.spec.handle, ctypes.byref(self._q), ctypes.byref(self._h)))
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        return self._h
+
+    @classmethod
+    def from_weights(cls, spec, params, state, amax, method="max"):
+        """Host only: quantize the flat float32 params / state buffers of a simple_cnn ModelSpec (the layout of spec.tensors) with the
+        calibrated maxima `amax` (6 values); method "max" (the calibrated activation ranges, capped at 6) or "relu6" (every activation
+        range 6)."""
+        if method not in _l.QUANT_METHODS:
+            raise ValueError("method must be one of %s" % sorted(_l.QUANT_METHODS))
+        p = np.ascontiguousarray(np.asarray(params, np.float32).reshape(-1))
+        s = np.ascontiguousarray(np.asarray(state, np.float32).reshape(-1))
+        a = np.ascontiguousarray(np.asarray(amax, np.float32).reshape(-1))
+        if p.size < spec.param_count or s.size < spec.state_count:
+            raise ValueError("params / state are shorter than the model's %d / %d floats" % (spec.param_count, spec.state_count))
+        if a.size != _l.QUANT_TENSORS:
+            raise ValueError("amax must hold %d values" % _l.QUANT_TENSORS)
+        q = _l.KwsQSimpleCnn()
+        _l.check(_l.get_lib().kws_quantize_simple_cnn(spec.handle, p.ctypes.data, s.ctypes.data, a.ctypes.data, _l.QUANT_METHODS[method],
+                                                      ctypes.byref(q)))
+        return cls(spec, q)
+
+    @classmethod
+    def from_model(cls, dm, amax, method="max"):
+        """Quantize the CURRENT weights of a simple_cnn DeviceModel (see from_weights)"""
+        return cls.from_weights(dm.spec, dm.params.cpu().numpy(), dm.state.cpu().numpy(), amax, method)
+
+    @property
+    def num_classes(self):
+        return self.spec.num_classes
+
+    @property
+    def method(self):
+        return {v: k for k, v in _l.QUANT_METHODS.items()}[self._q.method]
+
+    @property
+    def arrays(self):
+        """numpy views of the quantized model: int8 weights in Keras shapes, the fp32 epilogue constants, inv_s0, the scales s_0..s_5
+        and the ranges A_0..A_5 (views into the host copy; the device copy is made at the first forward)."""
+        q, C = self._q, self.spec.num_classes
+        out = {}
+        for n, shp in _SHAPES.items():
+            out[n] = np.ctypeslib.as_array(getattr(q, n)).reshape(shp)
+        out["head_w"] = np.ctypeslib.as_array(q.head_w)[:128 * C].reshape(128, C)
+        for n in _EPILOGUE:
+            out[n] = np.ctypeslib.as_array(getattr(q, n))
+        out["Mh"] = np.ctypeslib.as_array(q.Mh)[:C]
+        out["head_bias"] = np.ctypeslib.as_array(q.head_bias)[:C]
+        out["inv_s0"] = np.float32(q.inv_s0)
+        out["scale"] = np.ctypeslib.as_array(q.scale)
+        out["amax"] = np.ctypeslib.as_array(q.amax)
+        return out
+
+    def _launch(self, feat, B, logits, probs, argmax):
+        torch = _torch()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _l.check(self._L.kws_qmodel_forward(self._handle(), feat.data_ptr(), int(B), None, 0, ptr(logits), ptr(probs), ptr(argmax),
+                                            torch.cuda.current_stream().cuda_stream))
+
+    def forward(self, features, logits=False):
+        """features (B, n_features, feature_size[, 1]) -> (probs, argmax) CUDA tensors, or (logits, probs, argmax) with logits=True"""
+        torch = _torch()
+        f = _as_feature_tensor(features, self.spec)
+        B, C = f.shape[0], self.spec.num_classes
+        lg = torch.empty((B, C), dtype=torch.float32, device=f.device) if logits else None
+        probs = torch.empty((B, C), dtype=torch.float32, device=f.device)
+        am = torch.empty((B,), dtype=torch.int32, device=f.device)
+        self._launch(f, B, lg, probs, am)
+        return (lg, probs, am) if logits else (probs, am)
+
+    __call__ = forward
+
+    def save(self, path):
+        """.npz (the project's checkpoint format): the arrays above plus the model's geometry; load() rebuilds the model from them"""
+        arrays = {k: np.asarray(v) for k, v in self.arrays.items()}
+        arrays["__meta__"] = np.array([_FORMAT, self.spec.model_type, str(self.spec.num_classes), str(self.spec.n_features),
+                                       str(self.spec.feature_size), self.method])
+        np.savez(path, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        """a QuantizedCNN from a file save() wrote (bit-identical arrays; the device copy is made by kws_qmodel_create, as for a
+        freshly quantized model)"""
+        from .model import ModelSpec
+        z = np.load(path, allow_pickle=False)
+        meta = [str(v) for v in z["__meta__"]]
+        if meta[0] != _FORMAT:
+            raise ValueError("%s is not a quantized simple_cnn checkpoint" % path)
+        spec = ModelSpec(meta[1], int(meta[2]), int(meta[3]), int(meta[4]))
+        C = spec.num_classes
+        q = _l.KwsQSimpleCnn()
+        q.num_classes = C
+        q.method = _l.QUANT_METHODS[meta[5]]
+        q.inv_s0 = float(z["inv_s0"])
+        for n in _SHAPES:
+            np.ctypeslib.as_array(getattr(q, n))[:] = z[n].reshape(-1)
+        np.ctypeslib.as_array(q.head_w)[:128 * C] = z["head_w"].reshape(-1)
+        for n in _EPILOGUE:
+            np.ctypeslib.as_array(getattr(q, n))[:] = z[n]
+        np.ctypeslib.as_array(q.Mh)[:C] = z["Mh"]
+        np.ctypeslib.as_array(q.head_bias)[:C] = z["head_bias"]
+        np.ctypeslib.as_array(q.scale)[:] = z["scale"]
+        np.ctypeslib.as_array(q.amax)[:] = z["amax"]
+        return cls(spec, q)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.kws_qmodel_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,110 @@
+"""Cost of the int8 simple_cnn (kws_amd.quant) at B = 4096 against the fp32-level forward it replaces: the forward alone (features in,
+probabilities out; fp32 = kws_model_forward with its weight tables prepared, int8 = kws_qmodel_forward) and the graph-captured
+featurize + forward of kws_amd.inference.InferenceSession for each.  Variants alternate within each round (several rounds, medians).
+Next to every time stand the algorithmic bytes and int8 ops and the HBM, matrix and VALU floors.  Kernel-only times for DESIGN.md come
+from a separate `rocprofv3 --kernel-trace --stats` run of `--kernel-only`.  Prints one JSON line; --out also writes it to a file.
+
+    python tools/quantbench.py [--rounds 7] [--out quantbench.json] [--kernel-only]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tf-keras-speech-commands_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+HBM_GBS = 6300.0          # MI355X HBM3E, measured copy bandwidth
+I8_TOPS = 5000.0          # dense int8 matrix peak (v_mfma_i32_16x16x64_i8)
+VALU_TOPS = 78.6          # 32-bit vector ops per second (256 CUs x 128 lanes x 2.4 GHz), one op per lane and cycle
+
+# int8 multiply-adds per clip of the forward: conv1 on the vector ALU, the rest on the matrix cores
+MACS_VALU = 600 * 16 * 9
+MACS_MATRIX = 150 * 32 * 144 + 12 * 64 * 288 + 12 * 128 * 576 + 256 * 128 + 128 * 36
+
+
+def time_ms(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def floors(B, C):
+    """bytes (features in, probabilities and arg-max out), int8 ops and the three floors (ms) of one int8 forward"""
+    nbytes = B * (600 * 4 + C * 4 + 4)
+    ops_m, ops_v = 2 * B * MACS_MATRIX, 2 * B * MACS_VALU
+    return {"bytes": int(nbytes), "int8_matrix_ops": int(ops_m), "int8_valu_ops": int(ops_v),
+            "hbm_floor_ms": round(nbytes / (HBM_GBS * 1e6), 5), "matrix_floor_ms": round(ops_m / (I8_TOPS * 1e9), 5),
+            "valu_floor_ms": round(B * MACS_VALU / 4 / (VALU_TOPS * 1e9), 5)}      # v_dot4: four multiply-adds per op
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--kernel-only", action="store_true", help="only launch the two forwards (for a rocprofv3 --kernel-trace run)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    from classifier.params import pr
+    from kws_amd.featurizer import Featurizer
+    from kws_amd.inference import InferenceSession
+    from kws_amd.init import init_weights
+    from kws_amd.model import DeviceModel, ModelSpec
+    from kws_amd.quant import QuantizedCNN, calibrate
+    torch.manual_seed(0)
+    B, C = 4096, 36
+    spec = ModelSpec("simple_cnn", C, pr.n_features, pr.feature_size)
+    dm = DeviceModel(spec)
+    dm.set_weights(init_weights(spec, seed=0))
+    feat = (3.0 * torch.randn((B, pr.n_features, pr.feature_size), device="cuda")).contiguous()
+    q = QuantizedCNN.from_model(dm, calibrate(dm, feat), "max")
+    ws = dm.new_workspace(B)
+    dm.prepare_inference(B, workspace=ws)
+    probs = torch.empty((B, C), device="cuda")
+    am = torch.empty((B,), dtype=torch.int32, device="cuda")
+    fwd = {"fp32": lambda: dm.forward(feat, workspace=ws), "int8": lambda: q._launch(feat, B, None, probs, am)}
+    if args.kernel_only:
+        for _ in range(args.iters):
+            for f in fwd.values():
+                f()
+        torch.cuda.synchronize()
+        print(json.dumps({"kernel_only": True, "launches": len(fwd) * args.iters}))
+        return
+
+    fz = Featurizer(pr)
+    sess = {"fp32": InferenceSession(dm, fz, B, wav_dtype=torch.int16), "int8": InferenceSession(dm, fz, B, wav_dtype=torch.int16, quantized=q)}
+    pcm = torch.randint(-3000, 3000, (B, pr.max_samples), dtype=torch.int16, device="cuda")
+    for s in sess.values():
+        s.wav.copy_(pcm)
+    res = {"B": B, "C": C, "int8_floors": floors(B, C), "forward": {}, "featurize_forward_graph": {}}
+    ft = {n: [] for n in fwd}
+    gt = {n: [] for n in sess}
+    for _ in range(args.rounds):
+        for n, f in fwd.items():
+            ft[n].append(time_ms(f, args.iters))
+        for n, s in sess.items():
+            gt[n].append(time_ms(s.run, args.iters))
+    for n in fwd:
+        res["forward"][n] = {"median_ms": round(float(np.median(ft[n])), 4), "rounds": [round(x, 4) for x in ft[n]]}
+        res["featurize_forward_graph"][n] = {"median_ms": round(float(np.median(gt[n])), 4), "rounds": [round(x, 4) for x in gt[n]]}
+    agree = float((sess["fp32"].argmax == sess["int8"].argmax).float().mean().item())
+    res["fp32_int8_argmax_agreement_random_weights"] = round(agree, 4)
+    res["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
