@@ -528,6 +528,72 @@ int kws_qmodel_forward(const kws_qmodel *q, const float *feat, int B, void *ws, 
                        int32_t *argmax, void *stream);
 
 /* ------------------------------------------------------------------------
+ * int8 post-training quantization of simple_cnn_lite (classifier/models/cnn.py:77-141, four SeparableConv2D stages): the on-device
+ * model, the one a user of the reference ships through the same MNN / TFLite quantizers.  Scope: KWS_SIMPLE_CNN_LITE at the default
+ * geometry (30 x 20; pooled maps 15 x 10 -> 7 x 5 -> 4 x 3 -> 2 x 1) and C <= KWS_QUANT_MAX_CLASSES; everything else is
+ * KWS_ERR_UNSUPPORTED.  The rules of the simple_cnn section above hold unless stated otherwise (symmetric, zero-point 0, "same"
+ * padding = code 0, exact int32 accumulators with |acc| < 2^24, rint half to even, constants in double rounded once to fp32, no
+ * contraction on the device).
+ *
+ * Contract.
+ *   Quantized tensors, in the order of amax[0..9]: t0 = x, t1 = u1, t2 = a1 (after pool 1), t3 = u2, t4 = a2 (after pool 2), t5 = u3,
+ *   t6 = a3, t7 = u4, t8 = a4 (after pool 4), t9 = d (Dense -> ReLU6).  u_l is the depthwise output of stage l: signed and quantized
+ *   as a tensor of its own, as TFLite does when it splits a SeparableConv2D into DEPTHWISE_CONV_2D + CONV_2D.
+ *   Ranges A_t, scales s_t = A_t / 127: x: A = calibrated max|x| (0 is KWS_ERR_INVALID); u_l: A = calibrated max|u_l|, no cap, a
+ *   calibrated 0 becoming 1 (the tensor is identically zero); a1..a4, d: A = min(calibrated max, 6), a calibrated 0 becoming 6.
+ *   KWS_QUANT_RELU6 uses 6 for a1..a4 and d and the calibrated values for x and u_l.  Non-finite or negative: KWS_ERR_INVALID.
+ *   Weights, per-channel MAX_ABS as for simple_cnn: depthwise kernels (3, 3, C, 1) per channel c over its 9 taps; pointwise kernels
+ *   (1, 1, CI, CO) per output channel; Dense and head as for simple_cnn.
+ *   Stage l (s_in = s_{2l-2}, s_u = s_{2l-1}, s_out = s_{2l}; s_dwc, s_pwc the weight scales; g, h the BatchNorm fold of simple_cnn):
+ *     Mu[c] = (s_in * s_dwc) / s_u
+ *     bq[c] = rint(bias_c / (s_u * s_pwc)) clamped to +-2^23 (int32)
+ *     M[c]  = ((s_u * s_pwc) * g_c) / s_out,   Bq[c] = h_c / s_out
+ *   Dense: Md[c] = (s_8 * s_wc) / s_9, Bd[c] = bias_c / s_9;  head: Mh[c] = s_9 * s_wc;  input: inv_s0 = 1 / s_0.
+ *   Device arithmetic:
+ *     input:      code = clamp(rint(x * inv_s0), -127, 127)
+ *     depthwise:  dacc = sum over the 9 taps of code_in * qdw[tap][c];  u = clamp(rint((float)dacc * Mu[c]), -127, 127)
+ *                 (stage 3: stride 2, padding 1 before and 1 after on both axes, as simple_cnn's conv3)
+ *     pointwise:  acc = sum over ci of u[ci] * qpw[ci][c] + bq[c]  (|acc| <= 64 * 127^2 + 2^23 < 2^24);  stages 3 and 4 then
+ *                 acc = max(acc, 0) (their activation='relu');  code = clamp(rint((float)acc * M[c] + Bq[c]), 0, 127)
+ *     max pooling on the codes after the epilogue (stages 1, 2, 4); Dense, head, softmax, arg-max as in the simple_cnn contract.
+ * Divergences from MNN / TFLite: symmetric int8; per-channel depthwise and pointwise scales; max calibration; fp32 epilogue
+ * multipliers; the pointwise bias clamped to +-2^23 (TFLite keeps the full int32 bias).
+ * ---------------------------------------------------------------------- */
+#define KWS_QLITE_TENSORS 10
+
+/* Calibration of simple_cnn_lite: as kws_model_calibrate, into 10 DEVICE floats amax[0..9] = max|x|, max|u1|, max a1, max|u2|, max a2,
+ * max|u3|, max a3, max|u4|, max a4, max d (the u_l over the whole depthwise map).  Exact fp32 forward, one block per clip, in a
+ * kernel of its own (not the tuned lite kernels).  Other model kinds: KWS_ERR_UNSUPPORTED. */
+int kws_model_calibrate_lite(kws_model *m, const float *feat, int B, const float *params, const float *state, void *ws, size_t ws_bytes,
+                             float *amax, void *stream);
+
+/* The quantized simple_cnn_lite on the HOST (Keras order, filled by kws_quantize_simple_cnn_lite) */
+typedef struct kws_qsimple_cnn_lite {
+    int32_t num_classes;                /* C, 2..KWS_QUANT_MAX_CLASSES */
+    int32_t method;                     /* KWS_QUANT_MAX / KWS_QUANT_RELU6 */
+    float inv_s0;                       /* 1 / s_0 */
+    int32_t reserved;
+    double amax[KWS_QLITE_TENSORS];     /* A_0..A_9 after the rules above */
+    double scale[KWS_QLITE_TENSORS];    /* s_0..s_9 (reporting) */
+    int8_t dw_w1[3 * 3 * 1], dw_w2[3 * 3 * 16], dw_w3[3 * 3 * 32], dw_w4[3 * 3 * 64];     /* (3, 3, C, 1) */
+    int8_t pw_w1[1 * 16], pw_w2[16 * 32], pw_w3[32 * 64], pw_w4[64 * 128];              /* (1, 1, CI, CO) */
+    int8_t dense_w[256 * 128];          /* (in, out) */
+    int8_t head_w[128 * KWS_QUANT_MAX_CLASSES];   /* (128, C): the first 128 C entries, row stride C */
+    int32_t bq1[16], bq2[32], bq3[64], bq4[128];
+    float Mu1[1], Mu2[16], Mu3[32], Mu4[64];
+    float M1[16], B1[16], M2[32], B2[32], M3[64], B3[64], M4[128], B4[128];
+    float Md[128], Bd[128];
+    float Mh[KWS_QUANT_MAX_CLASSES], head_bias[KWS_QUANT_MAX_CLASSES];
+} kws_qsimple_cnn_lite;
+
+/* Host only: as kws_quantize_simple_cnn, with the 10 calibrated maxima of kws_model_calibrate_lite */
+int kws_quantize_simple_cnn_lite(const kws_model *m, const float *params_host, const float *state_host, const float *amax_host, int method,
+                                 kws_qsimple_cnn_lite *out);
+/* A quantized simple_cnn_lite on the CURRENT device.  kws_qmodel_forward (ONE kernel, features to probabilities, capturable),
+ * kws_qmodel_workspace_bytes (0) and kws_qmodel_destroy serve it as they serve a quantized simple_cnn. */
+int kws_qmodel_create_lite(const kws_model *m, const kws_qsimple_cnn_lite *q, kws_qmodel **out);
+
+/* ------------------------------------------------------------------------
  * Data-parallel exchange (RCCL over xGMI).  New: the reference trains in one
  * process (train.py:81-92, model.fit(..., workers=1) at :90-91); this is the
  * collective SURVEY.md section 5 / 8(e) specify around that loop.  One process

@@ -466,27 +466,28 @@ class KWSModel(object):
         return self.evaluate(x, y, batch_size=len(x))
 
     def quantize(self, x_calib, method='max', batch_size=None):
-        """int8 post-training quantization of a simple_cnn (what the reference's users do with the MNN quantizer or
-        custom_tflite_convert.py --post_training_quantize before deploying): calibrates the six quantized tensors on x_calib (features
-        or raw audio, as predict takes) with the fp32 forward on the GPU, quantizes the CURRENT weights (kws_amd.quant, include/kws.h)
-        with method 'max' or 'relu6' and returns a QuantizedKWSModel (predict / evaluate / save).  A snapshot: it does not follow
-        later training."""
+        """int8 post-training quantization of a simple_cnn or simple_cnn_lite (what the reference's users do with the MNN quantizer or
+        custom_tflite_convert.py --post_training_quantize before deploying): calibrates the quantized tensors (six for simple_cnn,
+        ten for simple_cnn_lite) on x_calib (features or raw audio, as predict takes) with the fp32 forward on the GPU, quantizes the
+        CURRENT weights (kws_amd.quant, include/kws.h) with method 'max' or 'relu6' and returns a QuantizedKWSModel (predict /
+        evaluate / save).  A snapshot: it does not follow later training."""
         import torch
-        from kws_amd.quant import QuantizedCNN, calibrate
+        from kws_amd.quant import QuantizedCNN, QuantizedCNNLite, calibrate
+        cls, n = (QuantizedCNNLite, _l.QLITE_TENSORS) if self.model_type == 'simple_cnn_lite' else (QuantizedCNN, _l.QUANT_TENSORS)
         dm = self._device()
         xd, is_audio = self._to_device_inputs(x_calib)
         if xd.shape[0] == 0:
             raise ValueError("quantize needs at least one calibration sample")
         batch_size = int(batch_size or 4096)
-        amax = torch.zeros((_l.QUANT_TENSORS,), dtype=torch.float32, device=xd.device)
+        amax = torch.zeros((n,), dtype=torch.float32, device=xd.device)
         for i in range(0, xd.shape[0], batch_size):
             calibrate(dm, self._features_of(xd[i:i + batch_size], is_audio).contiguous(), amax=amax)
-        return QuantizedKWSModel(self, QuantizedCNN.from_model(dm, amax.cpu().numpy(), method))
+        return QuantizedKWSModel(self, cls.from_model(dm, amax.cpu().numpy(), method))
 
 
 class QuantizedKWSModel(object):
     """The int8 model KWSModel.quantize returns: predict / evaluate as KWSModel's (features or raw audio in), computed by the int8
-    forward (one kernel per batch).  `quantized` is the kws_amd.quant.QuantizedCNN (arrays, save)."""
+    forward (one kernel per batch).  `quantized` is the kws_amd.quant.QuantizedCNN / QuantizedCNNLite (arrays, save)."""
 
     def __init__(self, model, quantized):
         self.model, self.quantized = model, quantized

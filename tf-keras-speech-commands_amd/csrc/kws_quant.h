@@ -1,8 +1,11 @@
-// csrc/kws_quant.h -- int8 simple_cnn (include/kws.h: kws_model_calibrate, kws_quantize_simple_cnn, kws_qmodel_*): the geometry the
-// quantized forward is built for, the fragment-major weight layout its kernel reads and the device-side model.
+// csrc/kws_quant.h -- int8 simple_cnn and simple_cnn_lite (include/kws.h: kws_model_calibrate[_lite], kws_quantize_simple_cnn[_lite],
+// kws_qmodel_*): the geometry the quantized forwards are built for, the fragment-major weight layout their kernels read, the helpers
+// both share and the device-side model.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "kws.h"
 
@@ -28,15 +31,58 @@ constexpr int kSh = 2, kNh = 3;     // K = 128, C <= 48
 // epilogue constants, one fp32 array: M1 B1 M2 B2 M3 B3 M4 B4 Md Bd Mh head_bias (the order of kws_qsimple_cnn)
 constexpr int kEpM1 = 0, kEpB1 = 16, kEpM2 = 32, kEpB2 = 64, kEpM3 = 96, kEpB3 = 160, kEpM4 = 224, kEpB4 = 352;
 constexpr int kEpMd = 480, kEpBd = 608, kEpMh = 736, kEpHb = 784, kEpCount = 832;
+
+__device__ __forceinline__ i32x4 mfma_i8(i32x4 a, i32x4 b, i32x4 c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
+
+// (float)acc * M + B with the multiply and the add rounded separately: HIP compiles with fp-contract=fast and __fmul_rn / __fadd_rn are
+// plain operators, so without the pragma the pair becomes one v_fma_f32 (one rounding) and the logits move by an ulp
+__device__ __forceinline__ float affine(int acc, float M, float B)
+{
+#pragma clang fp contract(off)
+    return (float)acc * M + B;
+}
+// code = clamp(rint((float)acc * M + Bq), 0, 127)
+__device__ __forceinline__ int requant(int acc, float M, float Bq)
+{
+    const float r = rintf(affine(acc, M, Bq));
+    return (int)fminf(fmaxf(r, 0.f), 127.f);
+}
+
+__device__ __forceinline__ int pack4(int a, int b, int c, int d) { return (a & 255) | (b & 255) << 8 | (c & 255) << 16 | (int)((unsigned)d << 24); }
+
+// host helpers (kws_quant.hip): per-output-channel MAX_ABS of a K x N row-major matrix; the fragment-major image of an int8 K x N matrix
+void quantize_weight(const float *W, int K, int N, int8_t *q, std::vector<double> &sw);
+void pack_frags(const int8_t *W, int K, int N, int S, int NCT, std::vector<int8_t> &out);
+
+// simple_cnn_lite (kws_quant_lite.hip).  Stages: depthwise 3 x 3 (vector ALU) -> u_l codes; pointwise as one k-step of
+// v_mfma_i32_16x16x64_i8 (K = 16 and 32 zero-padded to 64; pointwise 1, K = 1, on the vector ALU).  Epilogue constants, one fp32 array
+// in the order of kws_qsimple_cnn_lite: Mu1..Mu4, M1 B1 .. M4 B4, Md Bd Mh head_bias; the int32 pointwise biases bq1..bq4 in another.
+constexpr int kLEpMu1 = 0, kLEpMu2 = 1, kLEpMu3 = 17, kLEpMu4 = 49, kLEpM1 = 113, kLEpB1 = 129, kLEpM2 = 145, kLEpB2 = 177;
+constexpr int kLEpM3 = 209, kLEpB3 = 273, kLEpM4 = 337, kLEpB4 = 465, kLEpMd = 593, kLEpBd = 721, kLEpMh = 849, kLEpHb = 897;
+constexpr int kLEpCount = 945;
+constexpr int kLBq1 = 0, kLBq2 = 16, kLBq3 = 48, kLBq4 = 112, kLBqCount = 240;
 }  // namespace q8
 }  // namespace kws
 
 struct kws_qmodel {
+    int kind = KWS_SIMPLE_CNN;            // KWS_SIMPLE_CNN or KWS_SIMPLE_CNN_LITE: which forward kws_qmodel_forward runs
     int C = 0;
     int device = -1;
     float inv_s0 = 0.f;
     void *blob = nullptr;                 // one device allocation holding everything below
     const int32_t *w1 = nullptr;          // conv1: [16][3] int32 = the 9 taps of a channel packed 4 per word (tap 8 alone in the third)
     const kws::q8::i32x4 *f2 = nullptr, *f3 = nullptr, *f4 = nullptr, *fd = nullptr, *fh = nullptr;
-    const float *ep = nullptr;            // kEpCount floats
+    const float *ep = nullptr;            // kEpCount floats (simple_cnn) / kLEpCount (simple_cnn_lite)
+    // simple_cnn_lite: depthwise taps [stage][channel word][tap] as int32 words of 4 channels (stage 1: the 9 taps of its one channel
+    // packed 4 per word, as conv1 above), pointwise 1 [16] int8 in one array, fragments of pointwise 2..4, the int32 biases
+    const int32_t *dw[4] = {nullptr, nullptr, nullptr, nullptr};
+    const int8_t *pw1 = nullptr;
+    const kws::q8::i32x4 *fp[4] = {nullptr, nullptr, nullptr, nullptr};
+    const int32_t *bq = nullptr;          // kLBqCount
 };
+
+namespace kws {
+namespace q8 {
+int lite_qforward(const kws_qmodel *q, const float *feat, int B, float *logits, float *probs, int32_t *argmax, hipStream_t s);
+}  // namespace q8
+}  // namespace kws

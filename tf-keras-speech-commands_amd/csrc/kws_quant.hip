@@ -42,24 +42,6 @@ constexpr int kLds = kOffA2 + kG * kA2Clip;
 static_assert(kG * kA3Clip <= kOffX && kOffMS + 8 * kG <= kLds && kOffX + kG * kXClip <= kLds, "LDS regions");
 static_assert(kA1Clip % 16 == 0 && kA2Clip % 16 == 0 && kA3Clip % 16 == 0 && kOffX % 16 == 0, "16-byte fragment reads");
 
-__device__ __forceinline__ i32x4 mfma_i8(i32x4 a, i32x4 b, i32x4 c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
-
-// (float)acc * M + B with the multiply and the add rounded separately: HIP compiles with fp-contract=fast and __fmul_rn / __fadd_rn are
-// plain operators, so without the pragma the pair becomes one v_fma_f32 (one rounding) and the logits move by an ulp
-__device__ __forceinline__ float affine(int acc, float M, float B)
-{
-#pragma clang fp contract(off)
-    return (float)acc * M + B;
-}
-// code = clamp(rint((float)acc * M + Bq), 0, 127)
-__device__ __forceinline__ int requant(int acc, float M, float Bq)
-{
-    const float r = rintf(affine(acc, M, Bq));
-    return (int)fminf(fmaxf(r, 0.f), 127.f);
-}
-
-__device__ __forceinline__ int pack4(int a, int b, int c, int d) { return (a & 255) | (b & 255) << 8 | (c & 255) << 16 | (int)((unsigned)d << 24); }
-
 struct QFwdArgs {
     const float *feat;
     int B, C;
@@ -581,6 +563,7 @@ int kws_qmodel_create(const kws_model *m, const kws_qsimple_cnn *q, kws_qmodel *
                  o4 = put(f4.data(), f4.size()), od = put(fd.data(), fd.size()), oh = put(fh.data(), fh.size()),
                  oe = put(ep, sizeof(float) * kEpCount);
     auto *qm = new kws_qmodel();
+    qm->kind = KWS_SIMPLE_CNN;
     qm->C = m->C;
     qm->inv_s0 = q->inv_s0;
     if (hipGetDevice(&qm->device) != hipSuccess || hipMalloc(&qm->blob, img.size()) != hipSuccess) {
@@ -632,6 +615,7 @@ int kws_qmodel_forward(const kws_qmodel *q, const float *feat, int B, void *ws, 
     if (B < 0) return fail(KWS_ERR_INVALID, "batch must be >= 0");
     if (B == 0) return KWS_OK;
     if (!feat) return fail(KWS_ERR_INVALID, "null features");
+    if (q->kind == KWS_SIMPLE_CNN_LITE) return lite_qforward(q, feat, B, logits, probs, argmax, static_cast<hipStream_t>(stream));
     int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(qforward_kernel), kLds);
     if (rc) return rc;
     QFwdArgs a{feat, B, q->C, q->inv_s0, q->w1, q->f2, q->f3, q->f4, q->fd, q->fh, q->ep, logits, probs, argmax};

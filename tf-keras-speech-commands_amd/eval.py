@@ -80,7 +80,7 @@ def main():
     parser.add_argument('--params_path', type=str, default=None)
     parser.add_argument('--batch_size', type=int, default=4096)
     parser.add_argument('--int8', default=False, action='store_true',
-                        help='also quantize the model to int8 (post-training, simple_cnn) and report its accuracy and agreement')
+                        help='also quantize the model to int8 (post-training, simple_cnn / simple_cnn_lite) and report its accuracy and agreement')
     parser.add_argument('--calib_path', type=str, default=None, help='dataset to calibrate the int8 ranges on (default: the evaluated set)')
     parser.add_argument('--calib_samples', type=int, default=1000, help='calibration clips, drawn with a fixed seed')
     parser.add_argument('--quant_method', type=str, default='max', choices=['max', 'relu6'])

@@ -96,6 +96,26 @@ class KwsQSimpleCnn(ctypes.Structure):
                 ("Mh", ctypes.c_float * QUANT_MAX_CLASSES), ("head_bias", ctypes.c_float * QUANT_MAX_CLASSES)]
 
 
+QLITE_TENSORS = 10
+
+
+class KwsQSimpleCnnLite(ctypes.Structure):
+    """kws_qsimple_cnn_lite: the int8 simple_cnn_lite on the host (include/kws.h)"""
+    _fields_ = [("num_classes", ctypes.c_int32), ("method", ctypes.c_int32), ("inv_s0", ctypes.c_float), ("reserved", ctypes.c_int32),
+                ("amax", ctypes.c_double * QLITE_TENSORS), ("scale", ctypes.c_double * QLITE_TENSORS),
+                ("dw_w1", ctypes.c_int8 * 9), ("dw_w2", ctypes.c_int8 * (9 * 16)), ("dw_w3", ctypes.c_int8 * (9 * 32)),
+                ("dw_w4", ctypes.c_int8 * (9 * 64)),
+                ("pw_w1", ctypes.c_int8 * 16), ("pw_w2", ctypes.c_int8 * (16 * 32)), ("pw_w3", ctypes.c_int8 * (32 * 64)),
+                ("pw_w4", ctypes.c_int8 * (64 * 128)),
+                ("dense_w", ctypes.c_int8 * (256 * 128)), ("head_w", ctypes.c_int8 * (128 * QUANT_MAX_CLASSES)),
+                ("bq1", ctypes.c_int32 * 16), ("bq2", ctypes.c_int32 * 32), ("bq3", ctypes.c_int32 * 64), ("bq4", ctypes.c_int32 * 128),
+                ("Mu1", ctypes.c_float * 1), ("Mu2", ctypes.c_float * 16), ("Mu3", ctypes.c_float * 32), ("Mu4", ctypes.c_float * 64),
+                ("M1", ctypes.c_float * 16), ("B1", ctypes.c_float * 16), ("M2", ctypes.c_float * 32), ("B2", ctypes.c_float * 32),
+                ("M3", ctypes.c_float * 64), ("B3", ctypes.c_float * 64), ("M4", ctypes.c_float * 128), ("B4", ctypes.c_float * 128),
+                ("Md", ctypes.c_float * 128), ("Bd", ctypes.c_float * 128),
+                ("Mh", ctypes.c_float * QUANT_MAX_CLASSES), ("head_bias", ctypes.c_float * QUANT_MAX_CLASSES)]
+
+
 MODEL_KINDS = {"simple_cnn": 0, "simple_cnn_lite": 1, "simple_gru": 2, "simple_lstm": 3}
 BANK_MEL, BANK_BARK = 0, 1
 WAV_F32, WAV_I16 = 0, 1
@@ -221,6 +241,9 @@ def get_lib():
     L.kws_qmodel_workspace_bytes.argtypes = [vp, i32]
     L.kws_qmodel_workspace_bytes.restype = i64
     L.kws_qmodel_forward.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp, vp]
+    L.kws_model_calibrate_lite.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp]
+    L.kws_quantize_simple_cnn_lite.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(KwsQSimpleCnnLite)]
+    L.kws_qmodel_create_lite.argtypes = [vp, ctypes.POINTER(KwsQSimpleCnnLite), ctypes.POINTER(vp)]
     _lib = L
     return L
 

@@ -1,4 +1,5 @@
-"""int8 post-training quantization of simple_cnn (include/kws.h: kws_model_calibrate, kws_quantize_simple_cnn, kws_qmodel_*).
+"""int8 post-training quantization of simple_cnn and simple_cnn_lite (include/kws.h: kws_model_calibrate[_lite],
+kws_quantize_simple_cnn[_lite], kws_qmodel_*).
 
 The reference quantizes a trained model outside Python (the MNN quantizer with inference/MNN/configs/quantizeConfig.json, or
 tools/model_converter/custom_tflite_convert.py --post_training_quantize) and measures it with eval.py.  Here:
@@ -6,9 +7,10 @@ tools/model_converter/custom_tflite_convert.py --post_training_quantize) and mea
     amax = calibrate(dm, feature_batches)                 # fp32 forward on the GPU, running maxima of the six quantized tensors
     q = QuantizedCNN.from_model(dm, amax, method="max")   # host quantizer (the contract of include/kws.h), uploaded to the device
     probs, argmax = q.forward(features)                   # ONE int8 kernel from features to probabilities
-    q.save("model_int8.npz"); q = QuantizedCNN.load("model_int8.npz")
+    q.save("model_int8.npz"); q = load("model_int8.npz")
 
-A QuantizedCNN is a frozen snapshot of the weights it was made from."""
+simple_cnn_lite: calibrate() returns its ten maxima (x and the depthwise outputs u1..u4 beside the activations) and QuantizedCNNLite
+takes the place of QuantizedCNN, with the same interface.  A quantized model is a frozen snapshot of the weights it was made from."""
 import ctypes
 
 import numpy as np
@@ -19,6 +21,11 @@ _SHAPES = {"conv_w1": (3, 3, 1, 16), "conv_w2": (3, 3, 16, 32), "conv_w3": (3, 3
            "dense_w": (256, 128)}
 _EPILOGUE = ("M1", "B1", "M2", "B2", "M3", "B3", "M4", "B4", "Md", "Bd")
 _FORMAT = "kws_int8_simple_cnn/1"
+_LITE_CH = ((1, 16), (16, 32), (32, 64), (64, 128))
+_LITE_SHAPES = dict([("dw_w%d" % (l + 1), (3, 3, ci, 1)) for l, (ci, co) in enumerate(_LITE_CH)] +
+                    [("pw_w%d" % (l + 1), (1, 1, ci, co)) for l, (ci, co) in enumerate(_LITE_CH)] + [("dense_w", (256, 128))])
+_LITE_EPILOGUE = ("bq1", "bq2", "bq3", "bq4", "Mu1", "Mu2", "Mu3", "Mu4") + _EPILOGUE
+_LITE_FORMAT = "kws_int8_simple_cnn_lite/1"
 
 
 def _torch():
@@ -40,24 +47,33 @@ def _as_feature_tensor(x, spec):
 def calibrate(dm, feature_batches, amax=None):
     """Running maxima (numpy float32 (6,)) of t0..t5 -- max|x|, a1, a2, a3, a4, d -- of the fp32 inference forward of a simple_cnn
     DeviceModel over `feature_batches` (one (B, n_features, feature_size[, 1]) array / tensor, or an iterable of them).  `amax`: a
-    CUDA float32 (6,) tensor to fold the batches into (the running maxima of earlier calls); a fresh zero one by default."""
+    CUDA float32 (6,) tensor to fold the batches into (the running maxima of earlier calls); a fresh zero one by default.
+    A simple_cnn_lite DeviceModel gives ten maxima: max|x|, max|u1|, a1, max|u2|, a2, max|u3|, a3, max|u4|, a4, d (u_l = the depthwise
+    output of stage l)."""
     torch = _torch()
     L = _l.get_lib()
+    lite = dm.spec.model_type == "simple_cnn_lite"
+    n = _l.QLITE_TENSORS if lite else _l.QUANT_TENSORS
+    fn = L.kws_model_calibrate_lite if lite else L.kws_model_calibrate
     if amax is None:
-        amax = torch.zeros((_l.QUANT_TENSORS,), dtype=torch.float32, device=dm.device)
-    elif amax.dtype != torch.float32 or not amax.is_cuda or amax.numel() != _l.QUANT_TENSORS:
-        raise ValueError("amax must be a CUDA float32 tensor of %d values" % _l.QUANT_TENSORS)
+        amax = torch.zeros((n,), dtype=torch.float32, device=dm.device)
+    elif amax.dtype != torch.float32 or not amax.is_cuda or amax.numel() != n:
+        raise ValueError("amax must be a CUDA float32 tensor of %d values" % n)
     if isinstance(feature_batches, (np.ndarray, torch.Tensor)):
         feature_batches = [feature_batches]
     for fb in feature_batches:
         f = _as_feature_tensor(fb, dm.spec)
-        _l.check(L.kws_model_calibrate(dm.spec.handle, f.data_ptr(), f.shape[0], dm.params.data_ptr(), dm.state.data_ptr(), None, 0,
+        _l.check(fn(dm.spec.handle, f.data_ptr(), f.shape[0], dm.params.data_ptr(), dm.state.data_ptr(), None, 0,
                                        amax.data_ptr(), torch.cuda.current_stream().cuda_stream))
     return amax.cpu().numpy()
 
 
 class QuantizedCNN(object):
     """An int8 simple_cnn on the current HIP device (kws_qmodel).  Build it with from_model or load."""
+    _STRUCT = _l.KwsQSimpleCnn
+    _QUANTIZE, _CREATE = "kws_quantize_simple_cnn", "kws_qmodel_create"
+    _NT = _l.QUANT_TENSORS
+    _SHAPES, _EPILOGUE, _FORMAT = _SHAPES, _EPILOGUE, _FORMAT
 
     def __init__(self, spec, qstruct):
         self.spec = spec
@@ -71,7 +87,7 @@ class QuantizedCNN(object):
         host-only)"""
         if not self._h.value:
             torch = _torch()
-            _l.check(self._L.kws_qmodel_create(self.spec.handle, ctypes.byref(self._q), ctypes.byref(self._h)))
+            _l.check(getattr(self._L, self._CREATE)(self.spec.handle, ctypes.byref(self._q), ctypes.byref(self._h)))
             self.device = torch.device("cuda", torch.cuda.current_device())
         return self._h
 
@@ -87,10 +103,10 @@ class QuantizedCNN(object):
         a = np.ascontiguousarray(np.asarray(amax, np.float32).reshape(-1))
         if p.size < spec.param_count or s.size < spec.state_count:
             raise ValueError("params / state are shorter than the model's %d / %d floats" % (spec.param_count, spec.state_count))
-        if a.size != _l.QUANT_TENSORS:
-            raise ValueError("amax must hold %d values" % _l.QUANT_TENSORS)
-        q = _l.KwsQSimpleCnn()
-        _l.check(_l.get_lib().kws_quantize_simple_cnn(spec.handle, p.ctypes.data, s.ctypes.data, a.ctypes.data, _l.QUANT_METHODS[method],
+        if a.size != cls._NT:
+            raise ValueError("amax must hold %d values" % cls._NT)
+        q = cls._STRUCT()
+        _l.check(getattr(_l.get_lib(), cls._QUANTIZE)(spec.handle, p.ctypes.data, s.ctypes.data, a.ctypes.data, _l.QUANT_METHODS[method],
                                                       ctypes.byref(q)))
         return cls(spec, q)
 
@@ -113,10 +129,10 @@ class QuantizedCNN(object):
         and the ranges A_0..A_5 (views into the host copy; the device copy is made at the first forward)."""
         q, C = self._q, self.spec.num_classes
         out = {}
-        for n, shp in _SHAPES.items():
+        for n, shp in self._SHAPES.items():
             out[n] = np.ctypeslib.as_array(getattr(q, n)).reshape(shp)
         out["head_w"] = np.ctypeslib.as_array(q.head_w)[:128 * C].reshape(128, C)
-        for n in _EPILOGUE:
+        for n in self._EPILOGUE:
             out[n] = np.ctypeslib.as_array(getattr(q, n))
         out["Mh"] = np.ctypeslib.as_array(q.Mh)[:C]
         out["head_bias"] = np.ctypeslib.as_array(q.head_bias)[:C]
@@ -147,7 +163,7 @@ class QuantizedCNN(object):
     def save(self, path):
         """.npz (the project's checkpoint format): the arrays above plus the model's geometry; load() rebuilds the model from them"""
         arrays = {k: np.asarray(v) for k, v in self.arrays.items()}
-        arrays["__meta__"] = np.array([_FORMAT, self.spec.model_type, str(self.spec.num_classes), str(self.spec.n_features),
+        arrays["__meta__"] = np.array([self._FORMAT, self.spec.model_type, str(self.spec.num_classes), str(self.spec.n_features),
                                        str(self.spec.feature_size), self.method])
         np.savez(path, **arrays)
 
@@ -158,18 +174,18 @@ class QuantizedCNN(object):
         from .model import ModelSpec
         z = np.load(path, allow_pickle=False)
         meta = [str(v) for v in z["__meta__"]]
-        if meta[0] != _FORMAT:
-            raise ValueError("%s is not a quantized simple_cnn checkpoint" % path)
+        if meta[0] != cls._FORMAT:
+            raise ValueError("%s is not a quantized %s checkpoint" % (path, cls._FORMAT.split("/")[0][9:]))
         spec = ModelSpec(meta[1], int(meta[2]), int(meta[3]), int(meta[4]))
         C = spec.num_classes
-        q = _l.KwsQSimpleCnn()
+        q = cls._STRUCT()
         q.num_classes = C
         q.method = _l.QUANT_METHODS[meta[5]]
         q.inv_s0 = float(z["inv_s0"])
-        for n in _SHAPES:
+        for n in cls._SHAPES:
             np.ctypeslib.as_array(getattr(q, n))[:] = z[n].reshape(-1)
         np.ctypeslib.as_array(q.head_w)[:128 * C] = z["head_w"].reshape(-1)
-        for n in _EPILOGUE:
+        for n in cls._EPILOGUE:
             np.ctypeslib.as_array(getattr(q, n))[:] = z[n]
         np.ctypeslib.as_array(q.Mh)[:C] = z["Mh"]
         np.ctypeslib.as_array(q.head_bias)[:C] = z["head_bias"]
@@ -187,3 +203,33 @@ class QuantizedCNN(object):
             self.close()
         except Exception:
             pass
+
+
+class QuantizedCNNLite(QuantizedCNN):
+    """An int8 simple_cnn_lite on the current HIP device (kws_qmodel_create_lite; kws_qmodel_forward runs its one-kernel forward).
+    The interface of QuantizedCNN; from_weights takes the ten maxima calibrate() returns for a simple_cnn_lite model, arrays adds the
+    depthwise / pointwise codes (dw_w*, pw_w*), the int32 pointwise biases bq* and the depthwise multipliers Mu*."""
+    _STRUCT = _l.KwsQSimpleCnnLite
+    _QUANTIZE, _CREATE = "kws_quantize_simple_cnn_lite", "kws_qmodel_create_lite"
+    _NT = _l.QLITE_TENSORS
+    _SHAPES, _EPILOGUE, _FORMAT = _LITE_SHAPES, _LITE_EPILOGUE, _LITE_FORMAT
+
+
+_CLASSES = {"simple_cnn": QuantizedCNN, "simple_cnn_lite": QuantizedCNNLite}
+
+
+def quantized_class(model_type):
+    """the quantized class of a model type (ValueError for the types int8 does not cover)"""
+    if model_type not in _CLASSES:
+        raise ValueError("int8 quantization covers %s, not %s" % (" and ".join(sorted(_CLASSES)), model_type))
+    return _CLASSES[model_type]
+
+
+def load(path):
+    """a QuantizedCNN or QuantizedCNNLite from a file save() wrote, chosen by the file's format"""
+    with np.load(path, allow_pickle=False) as z:
+        fmt = str(z["__meta__"][0])
+    for cls in _CLASSES.values():
+        if fmt == cls._FORMAT:
+            return cls.load(path)
+    raise ValueError("%s is not a quantized model checkpoint (format %r)" % (path, fmt))

@@ -127,17 +127,19 @@ class StreamBatch(object):
 
     push(chunks) takes one chunk of int16 PCM per stream -- (S, n) int16 array / CUDA tensor, or a list of S `bytes`
     objects as PyAudio / wave.readframes deliver them -- and returns (index, score, fired) as CUDA tensors of length S.
+    With `quantized` (a kws_amd.quant.QuantizedCNN / QuantizedCNNLite) the probabilities come from its int8 forward instead of
+    device_model's.
     """
 
     def __init__(self, pr, device_model, n_streams, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
-                 decoder=None, featurizer=None, background_index=0):
+                 decoder=None, featurizer=None, background_index=0, quantized=None):
         torch = _torch()
         if pr.use_delta:
             # listen.py:111-112 re-applies add_deltas to the whole matrix on every chunk, which doubles its width and
             # makes the next np.concatenate raise; streaming with deltas never worked in the reference
             raise ValueError("streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered")
         self._L = _l.get_lib()
-        self.pr, self.model = pr, device_model
+        self.pr, self.model, self.quantized = pr, device_model, quantized
         self.S, self.chunk_size = int(n_streams), int(chunk_size)
         self.sensitivity, self.trigger_level = float(sensitivity), int(trigger_level)
         self.background_index = int(background_index)
@@ -198,7 +200,10 @@ class StreamBatch(object):
     def push(self, chunks):
         """One step of the loop listen.py:350-375 for every stream."""
         feats = self.update_vectors(chunks)
-        self.probs, _ = self.model.forward(feats, want_probs=True, want_argmax=False)
+        if self.quantized is not None:
+            self.probs, _ = self.quantized.forward(feats)
+        else:
+            self.probs, _ = self.model.forward(feats, want_probs=True, want_argmax=False)
         _l.check(self._L.kws_stream_postprocess(self.decoder.handle, self.probs.data_ptr(), self.S, self.probs.shape[1],
                                                 self.background_index, self.sensitivity, self.trigger_level, self.chunk_size,
                                                 self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),

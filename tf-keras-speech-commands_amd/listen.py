@@ -22,6 +22,7 @@ from kws_amd.stream import StreamBatch, ThresholdDecoder, TriggerDetector  # noq
 
 default_config = {                                     # listen.py:31-40
     "model_path": '',
+    "quantized_path": None,
     "model_type": 'simple_cnn',
     "classes_path": os.path.join('configs', 'direction_classes.txt'),
     "params_path": None,
@@ -48,6 +49,15 @@ class Listener(object):
         self.pr = inject_params(self.params_path) if self.params_path else pr
         self.class_names = get_classes(self.classes_path)
         assert self.class_names[0] == 'background', '1st class should be background.'
+        self.quantized = None
+        if getattr(self, "quantized_path", None):
+            # an int8 model saved by eval.py --save_quantized: it computes the probabilities; the float model only carries the device
+            from kws_amd.quant import load as load_quantized
+            self.quantized = load_quantized(self.quantized_path)
+            if self.quantized.num_classes != len(self.class_names):
+                raise ValueError("%s has %d classes, %s lists %d" % (self.quantized_path, self.quantized.num_classes, self.classes_path,
+                                                                    len(self.class_names)))
+            self.model_type = self.quantized.spec.model_type
         self.model = kwargs.get("model") or get_model(self.model_type, len(self.class_names), weights_path=self.model_path or None)
         self.threshold_decoder = ThresholdDecoder(self.pr.threshold_config, self.pr.threshold_center)
         self._sb = self.batch(1)
@@ -57,7 +67,8 @@ class Listener(object):
     def batch(self, n_streams):
         """A StreamBatch of n lock-stepped streams sharing this listener's model, decoder and settings."""
         return StreamBatch(self.pr, self.model._device(), n_streams, chunk_size=self.chunk_size, class_names=self.class_names,
-                           sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder)
+                           sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
+                           quantized=self.quantized)
 
     def update_vectors(self, chunk):
         """listen.py:96-114: bytes of int16 PCM in, the (n_features, n_mfcc, 1) feature matrix out."""
@@ -65,6 +76,9 @@ class Listener(object):
         return np.expand_dims(feats[0].cpu().numpy(), axis=-1)
 
     def predict(self, data):
+        if self.quantized is not None:
+            probs, _ = self.quantized.forward(np.asarray(data, dtype=np.float32))
+            return probs.cpu().numpy()
         return self.model.predict(np.asarray(data, dtype=np.float32))
 
     def step(self, chunk):
@@ -117,7 +131,9 @@ class Listener(object):
 
 def main():
     parser = argparse.ArgumentParser(description='keyword detection on a wav file (MI355X path)')
-    parser.add_argument('--model_path', type=str, required=True, help='.npz weights written by classifier.model')
+    parser.add_argument('--model_path', type=str, default=None, help='.npz weights written by classifier.model')
+    parser.add_argument('--quantized_path', type=str, default=None,
+                        help='stream with an int8 model written by eval.py --save_quantized (instead of, or beside, --model_path)')
     parser.add_argument('--model_type', type=str, default=default_config['model_type'])
     parser.add_argument('--classes_path', type=str, default=default_config['classes_path'])
     parser.add_argument('--params_path', type=str, default=None)
@@ -126,6 +142,8 @@ def main():
     parser.add_argument('--trigger_level', type=int, default=3)
     parser.add_argument('--input_wav', type=str, required=True)
     args = parser.parse_args()
+    if not args.model_path and not args.quantized_path:
+        parser.error('one of --model_path and --quantized_path is required')
     Listener(**vars(args)).run()
 
 

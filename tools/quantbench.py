@@ -4,7 +4,11 @@ featurize + forward of kws_amd.inference.InferenceSession for each.  Variants al
 Next to every time stand the algorithmic bytes and int8 ops and the HBM, matrix and VALU floors.  Kernel-only times for DESIGN.md come
 from a separate `rocprofv3 --kernel-trace --stats` run of `--kernel-only`.  Prints one JSON line; --out also writes it to a file.
 
-    python tools/quantbench.py [--rounds 7] [--out quantbench.json] [--kernel-only]"""
+    python tools/quantbench.py [--rounds 7] [--out quantbench.json] [--kernel-only]
+
+--model simple_cnn_lite: the int8 simple_cnn_lite forward against the fp32 and the fp16 lite forwards (kws_model_forward at
+KWS_INFER_FP32 / KWS_INFER_FP16, weight tables prepared) and the three graph-captured featurize + forward sessions, at B = 4096 and
+16 384 (--batches)."""
 import argparse
 import json
 import os
@@ -23,6 +27,10 @@ VALU_TOPS = 78.6          # 32-bit vector ops per second (256 CUs x 128 lanes x 
 # int8 multiply-adds per clip of the forward: conv1 on the vector ALU, the rest on the matrix cores
 MACS_VALU = 600 * 16 * 9
 MACS_MATRIX = 150 * 32 * 144 + 12 * 64 * 288 + 12 * 128 * 576 + 256 * 128 + 128 * 36
+# simple_cnn_lite, as the kernel computes it (only the pixels pooling keeps): depthwise 1..4 and pointwise 1 on the vector ALU,
+# pointwise 2..4, Dense and head on the matrix cores
+LITE_MACS_VALU = 600 * 9 + 600 * 16 + 140 * 16 * 9 + 12 * 32 * 9 + 8 * 64 * 9
+LITE_MACS_MATRIX = 140 * 16 * 32 + 12 * 32 * 64 + 8 * 64 * 128 + 256 * 128 + 128 * 36
 
 
 def time_ms(fn, n):
@@ -37,13 +45,75 @@ def time_ms(fn, n):
     return e0.elapsed_time(e1) / n
 
 
-def floors(B, C):
+def floors(B, C, macs_matrix=MACS_MATRIX, macs_valu=MACS_VALU, macs_per_valu_op=4):
     """bytes (features in, probabilities and arg-max out), int8 ops and the three floors (ms) of one int8 forward"""
     nbytes = B * (600 * 4 + C * 4 + 4)
-    ops_m, ops_v = 2 * B * MACS_MATRIX, 2 * B * MACS_VALU
+    ops_m, ops_v = 2 * B * macs_matrix, 2 * B * macs_valu
     return {"bytes": int(nbytes), "int8_matrix_ops": int(ops_m), "int8_valu_ops": int(ops_v),
             "hbm_floor_ms": round(nbytes / (HBM_GBS * 1e6), 5), "matrix_floor_ms": round(ops_m / (I8_TOPS * 1e9), 5),
-            "valu_floor_ms": round(B * MACS_VALU / 4 / (VALU_TOPS * 1e9), 5)}      # v_dot4: four multiply-adds per op
+            "valu_floor_ms": round(B * macs_valu / macs_per_valu_op / (VALU_TOPS * 1e9), 5)}   # simple_cnn: v_dot4, four per op
+
+
+def lite_main(args):
+    """--model simple_cnn_lite: fp32 / fp16 / int8 forwards and graph-captured sessions, alternating within each round"""
+    from classifier.params import pr
+    from kws_amd import lib as _l
+    from kws_amd.featurizer import Featurizer
+    from kws_amd.inference import InferenceSession
+    from kws_amd.init import init_weights
+    from kws_amd.model import DeviceModel, ModelSpec
+    from kws_amd.quant import QuantizedCNNLite, calibrate
+    torch.manual_seed(0)
+    C = 36
+    spec = ModelSpec("simple_cnn_lite", C, pr.n_features, pr.feature_size)
+    w = init_weights(spec, seed=0)
+    # one ModelSpec each: the precision attribute belongs to the library's model handle, which a ModelSpec owns
+    dm = {n: DeviceModel(ModelSpec("simple_cnn_lite", C, pr.n_features, pr.feature_size)) for n in ("fp32", "fp16")}
+    for m in dm.values():
+        m.set_weights(w)
+    dm["fp32"].set_precision(infer=_l.INFER_FP32)
+    dm["fp16"].set_precision(infer=_l.INFER_FP16)
+    fz = Featurizer(pr)
+    out = {"model": "simple_cnn_lite", "C": C, "runs": []}
+    for B in args.batches:
+        feat = (3.0 * torch.randn((B, pr.n_features, pr.feature_size), device="cuda")).contiguous()
+        q = QuantizedCNNLite.from_model(dm["fp32"], calibrate(dm["fp32"], feat[:4096]), "max")
+        ws = {n: m.new_workspace(B) for n, m in dm.items()}
+        for n, m in dm.items():
+            m.prepare_inference(B, workspace=ws[n])
+        probs = torch.empty((B, C), device="cuda")
+        am = torch.empty((B,), dtype=torch.int32, device="cuda")
+        fwd = {"fp32": lambda: dm["fp32"].forward(feat, workspace=ws["fp32"]), "fp16": lambda: dm["fp16"].forward(feat, workspace=ws["fp16"]),
+               "int8": lambda: q._launch(feat, B, None, probs, am)}
+        if args.kernel_only:
+            for _ in range(args.iters):
+                for f in fwd.values():
+                    f()
+            torch.cuda.synchronize()
+            out["runs"].append({"B": B, "kernel_only": True, "launches": len(fwd) * args.iters})
+            continue
+        sess = {"fp32": InferenceSession(dm["fp32"], fz, B, wav_dtype=torch.int16),
+                "fp16": InferenceSession(dm["fp32"], fz, B, wav_dtype=torch.int16, fp16=True),
+                "int8": InferenceSession(dm["fp32"], fz, B, wav_dtype=torch.int16, quantized=q)}
+        pcm = torch.randint(-3000, 3000, (B, pr.max_samples), dtype=torch.int16, device="cuda")
+        for s in sess.values():
+            s.wav.copy_(pcm)
+        res = {"B": B, "int8_floors": floors(B, C, LITE_MACS_MATRIX, LITE_MACS_VALU, 1), "forward": {}, "featurize_forward_graph": {}}
+        ft = {n: [] for n in fwd}
+        gt = {n: [] for n in sess}
+        for _ in range(args.rounds):
+            for n, f in fwd.items():
+                ft[n].append(time_ms(f, args.iters))
+            for n, s in sess.items():
+                gt[n].append(time_ms(s.run, args.iters))
+        for n in fwd:
+            res["forward"][n] = {"median_ms": round(float(np.median(ft[n])), 4), "rounds": [round(x, 4) for x in ft[n]]}
+            res["featurize_forward_graph"][n] = {"median_ms": round(float(np.median(gt[n])), 4), "rounds": [round(x, 4) for x in gt[n]]}
+        res["fp32_int8_argmax_agreement_random_weights"] = round(float((sess["fp32"].argmax == sess["int8"].argmax).float().mean().item()), 4)
+        out["runs"].append(res)
+        del sess, ws
+    out["device"] = torch.cuda.get_device_name(0)
+    return out
 
 
 def main():
@@ -52,7 +122,18 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--kernel-only", action="store_true", help="only launch the two forwards (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--model", default="simple_cnn", choices=["simple_cnn", "simple_cnn_lite"])
+    ap.add_argument("--batches", type=int, nargs="+", default=[4096, 16384], help="simple_cnn_lite: the batch sizes")
     args = ap.parse_args()
+    if args.model == "simple_cnn_lite":
+        res = lite_main(args)
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     from classifier.params import pr
     from kws_amd.featurizer import Featurizer
     from kws_amd.inference import InferenceSession
