@@ -477,12 +477,14 @@ int64_t kws_model_grad_split(const kws_model *m);
  *     max pooling (2 x 2, stride 2, valid) on the codes AFTER the epilogue (a negative gamma makes the epilogue decreasing)
  *     head:            logit = (float)acc * Mh[c] + bias[c], then the fp32 softmax of the float head (first maximum wins the arg-max)
  *   |acc| < 2^24 everywhere (conv4: 576 * 127^2 ~ 9.3 M), so (float)acc is exact.
- * Divergences from MNN / TFLite: symmetric int8 instead of TFLite's asymmetric uint8; per-channel weight scales; max calibration
- * instead of MNN's KL; fp32 epilogue multipliers instead of fixed-point ones; fp32 softmax.
+ *   KWS_QUANT_KL (section "entropy calibration" below) applies the rules of KWS_QUANT_MAX to KL ranges passed in place of the maxima.
+ * Divergences from MNN / TFLite: symmetric int8 instead of TFLite's asymmetric uint8; per-channel weight scales; the entropy (KL)
+ * calibration is modelled on MNN's "KL" feature_quantize_method (TensorRT's 8-bit recipe), its details fixed by the contract below
+ * rather than by MNN's source; fp32 epilogue multipliers instead of fixed-point ones; fp32 softmax.
  * ---------------------------------------------------------------------- */
 #define KWS_QUANT_TENSORS 6
 #define KWS_QUANT_MAX_CLASSES 48
-enum { KWS_QUANT_MAX = 0, KWS_QUANT_RELU6 = 1 };
+enum { KWS_QUANT_MAX = 0, KWS_QUANT_RELU6 = 1, KWS_QUANT_KL = 2 };
 
 /* Calibration: runs the fp32 inference forward (BN moving statistics, no dropout) of B clips and max-reduces into amax (6 DEVICE floats):
  * amax[0] = max |x|, amax[1..5] = max of t1..t5 (all >= 0).  The caller zeroes amax once; every call folds its batch into the running
@@ -494,7 +496,7 @@ int kws_model_calibrate(kws_model *m, const float *feat, int B, const float *par
 /* The quantized network on the HOST (every array in Keras order, filled by kws_quantize_simple_cnn) */
 typedef struct kws_qsimple_cnn {
     int32_t num_classes;                /* C, 2..KWS_QUANT_MAX_CLASSES */
-    int32_t method;                     /* KWS_QUANT_MAX / KWS_QUANT_RELU6 */
+    int32_t method;                     /* KWS_QUANT_MAX / KWS_QUANT_RELU6 / KWS_QUANT_KL */
     float inv_s0;                       /* 1 / s_0 */
     int32_t reserved;
     double amax[KWS_QUANT_TENSORS];     /* A_0..A_5 after the rules above */
@@ -556,8 +558,10 @@ int kws_qmodel_forward(const kws_qmodel *q, const float *feat, int B, void *ws, 
  *     pointwise:  acc = sum over ci of u[ci] * qpw[ci][c] + bq[c]  (|acc| <= 64 * 127^2 + 2^23 < 2^24);  stages 3 and 4 then
  *                 acc = max(acc, 0) (their activation='relu');  code = clamp(rint((float)acc * M[c] + Bq[c]), 0, 127)
  *     max pooling on the codes after the epilogue (stages 1, 2, 4); Dense, head, softmax, arg-max as in the simple_cnn contract.
- * Divergences from MNN / TFLite: symmetric int8; per-channel depthwise and pointwise scales; max calibration; fp32 epilogue
- * multipliers; the pointwise bias clamped to +-2^23 (TFLite keeps the full int32 bias).
+ *   KWS_QUANT_KL applies the rules of KWS_QUANT_MAX to KL ranges passed in place of the maxima (section "entropy calibration" below).
+ * Divergences from MNN / TFLite: symmetric int8; per-channel depthwise and pointwise scales; the entropy (KL) calibration modelled on
+ * MNN's "KL" method (TensorRT's 8-bit recipe) by the contract below, not by MNN's source; fp32 epilogue multipliers; the pointwise
+ * bias clamped to +-2^23 (TFLite keeps the full int32 bias).
  * ---------------------------------------------------------------------- */
 #define KWS_QLITE_TENSORS 10
 
@@ -570,7 +574,7 @@ int kws_model_calibrate_lite(kws_model *m, const float *feat, int B, const float
 /* The quantized simple_cnn_lite on the HOST (Keras order, filled by kws_quantize_simple_cnn_lite) */
 typedef struct kws_qsimple_cnn_lite {
     int32_t num_classes;                /* C, 2..KWS_QUANT_MAX_CLASSES */
-    int32_t method;                     /* KWS_QUANT_MAX / KWS_QUANT_RELU6 */
+    int32_t method;                     /* KWS_QUANT_MAX / KWS_QUANT_RELU6 / KWS_QUANT_KL */
     float inv_s0;                       /* 1 / s_0 */
     int32_t reserved;
     double amax[KWS_QLITE_TENSORS];     /* A_0..A_9 after the rules above */
@@ -592,6 +596,40 @@ int kws_quantize_simple_cnn_lite(const kws_model *m, const float *params_host, c
 /* A quantized simple_cnn_lite on the CURRENT device.  kws_qmodel_forward (ONE kernel, features to probabilities, capturable),
  * kws_qmodel_workspace_bytes (0) and kws_qmodel_destroy serve it as they serve a quantized simple_cnn. */
 int kws_qmodel_create_lite(const kws_model *m, const kws_qsimple_cnn_lite *q, kws_qmodel **out);
+
+/* ------------------------------------------------------------------------
+ * Entropy (KL) calibration of the int8 models: what the reference's deployment recipe asks for
+ * (inference/MNN/configs/quantizeConfig.json, "feature_quantize_method": "KL").  Modelled on MNN's KL method, itself TensorRT's 8-bit
+ * entropy calibration; MNN's source being outside this project, the details below are this contract's own: zeros are not counted,
+ * the 128 groups split [0, i) with integer arithmetic, the candidates run up to i = 2048 inclusive and the range is i* amax / 2048.
+ *
+ *   1. A max pass (kws_model_calibrate / kws_model_calibrate_lite) gives the T maxima amax_t (T = 6 / 10, their order).
+ *   2. A histogram pass (kws_model_calibrate_hist) over the same set, with amax copied to the host: for every tensor t with
+ *      amax_t > 0, k_t = (float)(2048.0 / (double)amax_t) on the host, and for every element v the max pass reduces for t (the same
+ *      fp32 values: both passes run one per-clip forward), v != 0: bin = min((int)(|v| * k_t), 2047) (one fp32 multiply, no
+ *      contraction), hist[t][bin] += 1.  Zeros are not counted (after a ReLU6 they would swamp bin 0); amax_t == 0 gives no counts.
+ *   3. kws_quant_kl_ranges (host) turns the counts into ranges A_t; kws_quantize_simple_cnn[_lite](..., A, KWS_QUANT_KL, ...) applies
+ *      the rules of KWS_QUANT_MAX to them (post-ReLU6 ranges capped at 6; a range of 0 becoming 6, or 1 for u_l; A_0 = 0 invalid)
+ *      and records method = KWS_QUANT_KL.
+ *   KL search, per tensor, h its 2048 counts, N = sum h, all in double with sums in ascending index order: for i = 128 .. 2048,
+ *     P[j] = h[j] for j < i, then P[i-1] += sum_{j >= i} h[j];
+ *     groups g = 0..127 of [0, i): [floor(g i / 128), floor((g + 1) i / 128)), S_g = sum of h, n_g = number of nonzero h over the group;
+ *     Q[j] = S_g / n_g where h[j] != 0, else 0;  p = P / sum P, q = Q / sum Q;  KL_i = sum_{p_j > 0} p_j ln(p_j / q_j),
+ *     +inf if sum Q = 0 or some p_j > 0 has q_j = 0 (i = 2048 clips nothing: some KL_i is finite).
+ *   i* = the SMALLEST i of least KL_i; A_t = i* amax_t / 2048 in double, rounded once to float.  N = 0 gives A_t = 0.
+ * ---------------------------------------------------------------------- */
+#define KWS_QUANT_HIST_BINS 2048
+
+/* Histogram pass: dispatches on the model kind (simple_cnn: T = 6, simple_cnn_lite: T = 10; other kinds KWS_ERR_UNSUPPORTED).
+ * amax_host: the T maxima of a finished max pass (HOST floats, copied into the kernel arguments: the call is capturable).  hist: a
+ * DEVICE T x KWS_QUANT_HIST_BINS uint64 array of running counts; the caller zeroes it once and every call adds its batch (calls over
+ * the halves of a set give the call over the whole set, exactly).  A persistent kernel: each block counts in LDS and adds its nonzero
+ * bins once at its end.  ws may be NULL; B = 0 is a no-op. */
+int kws_model_calibrate_hist(kws_model *m, const float *feat, int B, const float *params, const float *state, void *ws, size_t ws_bytes,
+                             const float *amax_host, uint64_t *hist, void *stream);
+/* Host only: the KL search above over T histograms (hist_host T x KWS_QUANT_HIST_BINS, amax_host T floats) -> ranges_out[T] and, when
+ * bins_out is not NULL, i* per tensor (0 for an empty histogram). */
+int kws_quant_kl_ranges(const uint64_t *hist_host, const float *amax_host, int T, float *ranges_out, int32_t *bins_out);
 
 /* ------------------------------------------------------------------------
  * Data-parallel exchange (RCCL over xGMI).  New: the reference trains in one

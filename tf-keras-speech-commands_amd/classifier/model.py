@@ -469,10 +469,13 @@ class KWSModel(object):
         """int8 post-training quantization of a simple_cnn or simple_cnn_lite (what the reference's users do with the MNN quantizer or
         custom_tflite_convert.py --post_training_quantize before deploying): calibrates the quantized tensors (six for simple_cnn,
         ten for simple_cnn_lite) on x_calib (features or raw audio, as predict takes) with the fp32 forward on the GPU, quantizes the
-        CURRENT weights (kws_amd.quant, include/kws.h) with method 'max' or 'relu6' and returns a QuantizedKWSModel (predict /
-        evaluate / save).  A snapshot: it does not follow later training."""
+        CURRENT weights (kws_amd.quant, include/kws.h) with method 'max', 'relu6' or 'kl' and returns a QuantizedKWSModel (predict /
+        evaluate / save).  'kl' (the reference's MNN recipe) makes a second pass over x_calib that histograms the tensors against the
+        maxima of the first and takes the ranges of least KL divergence.  A snapshot: it does not follow later training."""
         import torch
-        from kws_amd.quant import QuantizedCNN, QuantizedCNNLite, calibrate
+        from kws_amd.quant import QuantizedCNN, QuantizedCNNLite, calibrate, histograms
+        if method not in _l.QUANT_SNAPSHOT_METHODS:
+            raise ValueError("method must be one of %s" % sorted(_l.QUANT_SNAPSHOT_METHODS))
         cls, n = (QuantizedCNNLite, _l.QLITE_TENSORS) if self.model_type == 'simple_cnn_lite' else (QuantizedCNN, _l.QUANT_TENSORS)
         dm = self._device()
         xd, is_audio = self._to_device_inputs(x_calib)
@@ -482,7 +485,13 @@ class KWSModel(object):
         amax = torch.zeros((n,), dtype=torch.float32, device=xd.device)
         for i in range(0, xd.shape[0], batch_size):
             calibrate(dm, self._features_of(xd[i:i + batch_size], is_audio).contiguous(), amax=amax)
-        return QuantizedKWSModel(self, cls.from_model(dm, amax.cpu().numpy(), method))
+        amax = amax.cpu().numpy()
+        if method != 'kl':
+            return QuantizedKWSModel(self, cls.from_model(dm, amax, method))
+        hist = None
+        for i in range(0, xd.shape[0], batch_size):
+            hist = histograms(dm, self._features_of(xd[i:i + batch_size], is_audio).contiguous(), amax, hist=hist)
+        return QuantizedKWSModel(self, cls.from_model_histograms(dm, amax, hist))
 
 
 class QuantizedKWSModel(object):

@@ -50,6 +50,30 @@ __device__ __forceinline__ int requant(int acc, float M, float Bq)
 
 __device__ __forceinline__ int pack4(int a, int b, int c, int d) { return (a & 255) | (b & 255) << 8 | (c & 255) << 16 | (int)((unsigned)d << 24); }
 
+// Observers of the calibration forwards (kws_quant.hip cal_forward, kws_quant_lite.hip lite_cal_forward): obs(t, v) gets every value v
+// >= 0 of quantized tensor t (|v| for a signed tensor), t a compile-time constant once inlined.  CalMax keeps the thread's running
+// maxima; CalHist counts v != 0 into the block's LDS histograms [T][KWS_QUANT_HIST_BINS]: bin = min((int)(v * k_t), 2047), k_t = 2048
+// / amax_t (0: tensor t is not counted) -- one fp32 multiply, nothing to contract.
+template <int T>
+struct CalMax {
+    float mx[T];
+    __device__ __forceinline__ CalMax()
+    {
+#pragma unroll
+        for (int t = 0; t < T; ++t) mx[t] = 0.f;
+    }
+    __device__ __forceinline__ void operator()(int t, float v) { mx[t] = fmaxf(mx[t], v); }
+};
+template <int T>
+struct CalHist {
+    unsigned *cnt;
+    float k[T];
+    __device__ __forceinline__ void operator()(int t, float v)
+    {
+        if (v != 0.f && k[t] > 0.f) atomicAdd(cnt + t * KWS_QUANT_HIST_BINS + min((int)__fmul_rn(v, k[t]), KWS_QUANT_HIST_BINS - 1), 1u);
+    }
+};
+
 // host helpers (kws_quant.hip): per-output-channel MAX_ABS of a K x N row-major matrix; the fragment-major image of an int8 K x N matrix
 void quantize_weight(const float *W, int K, int N, int8_t *q, std::vector<double> &sw);
 void pack_frags(const int8_t *W, int K, int N, int S, int NCT, std::vector<int8_t> &out);
@@ -84,5 +108,12 @@ struct kws_qmodel {
 namespace kws {
 namespace q8 {
 int lite_qforward(const kws_qmodel *q, const float *feat, int B, float *logits, float *probs, int32_t *argmax, hipStream_t s);
+// kws_model_calibrate_hist for simple_cnn_lite (kws_quant_lite.hip)
+int lite_calibrate_hist(const kws_model *m, const float *feat, int B, const float *params, const float *state, const float *amax_host,
+                        uint64_t *hist, hipStream_t s);
+// kws_quant.hip: the grid of a persistent calibration-histogram kernel, min(B, resident blocks of the device); the bin factors k_t =
+// (float)(2048.0 / amax_t), 0 where amax_t == 0 (KWS_ERR_INVALID for a non-finite or negative maximum)
+int hist_grid(const void *kernel, int B);
+int hist_factors(const float *amax_host, int T, float *k);
 }  // namespace q8
 }  // namespace kws

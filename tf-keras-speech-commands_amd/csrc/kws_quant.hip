@@ -18,6 +18,7 @@
 // resident, 140 KB in all); the epilogue constants likewise.
 #include <cmath>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "kws_common.h"
@@ -296,12 +297,18 @@ __global__ __launch_bounds__(kThreads) void qforward_kernel(QFwdArgs g)
         }
 }
 
-// ---- calibration: the fp32 inference forward, one block per clip, max-reduced into amax --------------------------------------------
+// ---- calibration: the fp32 inference forward of one clip (plain loops), every value of a quantized tensor handed to an observer ------
+// Two observers: CalMax (qcalibrate_kernel, one block per clip, max-reduced into amax) and CalHist (qhist_kernel, persistent, counted
+// into LDS histograms).  Both passes run this one function, so the histogram pass sees exactly the values the max pass reduced.
 struct CalArgs {
     const float *feat;
     const float *k[4], *gamma[4], *beta[4], *mm[4], *mv[4];
     const float *dk, *db;
     float *amax;
+};
+
+struct CalSmem {
+    float x0[kH0 * kW0], a1[15 * 10 * kC1], a2[7 * 5 * kC2], a3[4 * 3 * kC3], a4[kFlat];
 };
 
 __device__ __forceinline__ float bn_relu6(float y, const CalArgs &a, int l, int c)
@@ -311,17 +318,16 @@ __device__ __forceinline__ float bn_relu6(float y, const CalArgs &a, int l, int 
     return fminf(fmaxf(v, 0.f), 6.f);
 }
 
-__global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
+// obs(t, v): v >= 0 is |x| for t0, the activation itself for t1..t5.  Ends without a barrier after the Dense stage (it reads a4 only).
+template <class Obs>
+__device__ __forceinline__ void cal_forward(const CalArgs &a, const float *f, CalSmem &sm, Obs &obs)
 {
-    __shared__ float x0[kH0 * kW0], a1[15 * 10 * kC1], a2[7 * 5 * kC2], a3[4 * 3 * kC3], a4[kFlat];
-    __shared__ int red[KWS_QUANT_TENSORS];
     const int tid = threadIdx.x;
-    float mx[KWS_QUANT_TENSORS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (tid < KWS_QUANT_TENSORS) red[tid] = 0;
-    const float *f = a.feat + (long)blockIdx.x * (kH0 * kW0);
+    float *x0 = sm.x0, *a1 = sm.a1, *a2 = sm.a2, *a3 = sm.a3, *a4 = sm.a4;
     for (int i = tid; i < kH0 * kW0; i += 256) {
-        x0[i] = f[i];
-        mx[0] = fmaxf(mx[0], fabsf(f[i]));
+        const float v = f[i];
+        x0[i] = v;
+        obs(0, fabsf(v));
     }
     __syncthreads();
     // conv1 + pool: 15 x 10 x 16 (pad 1 on every side)
@@ -340,7 +346,7 @@ __global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
             best = fmaxf(best, bn_relu6(s, a, 0, co));
         }
         a1[o] = best;
-        mx[1] = fmaxf(mx[1], best);
+        obs(1, best);
     }
     __syncthreads();
     // conv2 + pool: 7 x 5 x 32 of the 15 x 10 map (pad 1)
@@ -361,7 +367,7 @@ __global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
             best = fmaxf(best, bn_relu6(s, a, 1, co));
         }
         a2[o] = best;
-        mx[2] = fmaxf(mx[2], best);
+        obs(2, best);
     }
     __syncthreads();
     // conv3: stride 2, 'same' (pad 1 before): 4 x 3 x 64
@@ -377,7 +383,7 @@ __global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
         }
         const float v = bn_relu6(s, a, 2, co);
         a3[o] = v;
-        mx[3] = fmaxf(mx[3], v);
+        obs(3, v);
     }
     __syncthreads();
     // conv4 (relu) + BN + ReLU6 + pool: 2 x 1 x 128 of the 4 x 3 map
@@ -398,7 +404,7 @@ __global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
             best = fmaxf(best, bn_relu6(fmaxf(s, 0.f), a, 3, co));
         }
         a4[o] = best;
-        mx[4] = fmaxf(mx[4], best);
+        obs(4, best);
     }
     __syncthreads();
     // Dense(128) + ReLU6
@@ -406,13 +412,52 @@ __global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
         float s = a.db[o];
 #pragma unroll 4
         for (int k = 0; k < kFlat; ++k) s += a4[k] * a.dk[k * kD + o];
-        mx[5] = fmaxf(mx[5], fminf(fmaxf(s, 0.f), 6.f));
+        obs(5, fminf(fmaxf(s, 0.f), 6.f));
     }
+}
+
+__global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
+{
+    __shared__ CalSmem sm;
+    __shared__ int red[KWS_QUANT_TENSORS];
+    const int tid = threadIdx.x;
+    CalMax<KWS_QUANT_TENSORS> obs;
+    if (tid < KWS_QUANT_TENSORS) red[tid] = 0;
+    cal_forward(a, a.feat + (long)blockIdx.x * (kH0 * kW0), sm, obs);
     // non-negative floats order like their bit patterns as int (a NaN's pattern would win: the host rejects it)
 #pragma unroll
-    for (int t = 0; t < KWS_QUANT_TENSORS; ++t) atomicMax(&red[t], __float_as_int(mx[t]));
+    for (int t = 0; t < KWS_QUANT_TENSORS; ++t) atomicMax(&red[t], __float_as_int(obs.mx[t]));
     __syncthreads();
     if (tid < KWS_QUANT_TENSORS) atomicMax(reinterpret_cast<int *>(a.amax) + tid, red[tid]);
+}
+
+struct HistArgs {
+    CalArgs c;
+    int B;
+    float k[KWS_QUANT_TENSORS];       // 2048 / amax_t, 0 for a tensor that gets no counts
+    unsigned long long *hist;
+};
+
+// persistent: block b counts clips b, b + grid, ... into its LDS histograms (48 KB beside the forward's 20.6 KB: two blocks per CU)
+// and adds its nonzero bins to hist once at its end
+__global__ __launch_bounds__(256) void qhist_kernel(HistArgs g)
+{
+    __shared__ CalSmem sm;
+    __shared__ unsigned cnt[KWS_QUANT_TENSORS * KWS_QUANT_HIST_BINS];
+    for (int i = threadIdx.x; i < KWS_QUANT_TENSORS * KWS_QUANT_HIST_BINS; i += 256) cnt[i] = 0u;
+    CalHist<KWS_QUANT_TENSORS> obs;
+    obs.cnt = cnt;
+#pragma unroll
+    for (int t = 0; t < KWS_QUANT_TENSORS; ++t) obs.k[t] = g.k[t];
+    for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
+        __syncthreads();      // the previous clip's Dense stage has read a4; the counters are cleared
+        cal_forward(g.c, g.c.feat + (long)b * (kH0 * kW0), sm, obs);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < KWS_QUANT_TENSORS * KWS_QUANT_HIST_BINS; i += 256) {
+        const unsigned c = cnt[i];
+        if (c) atomicAdd(g.hist + i, (unsigned long long)c);
+    }
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
@@ -454,6 +499,65 @@ void pack_frags(const int8_t *W, int K, int N, int S, int NCT, std::vector<int8_
                 }
 }
 
+int hist_grid(const void *kernel, int B)
+{
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
+    return std::min(B, nb * device_cus());
+}
+
+// 2048 / amax_t per tensor (0 for amax_t == 0: no counts); KWS_ERR_INVALID for a non-finite or negative maximum
+int hist_factors(const float *amax_host, int T, float *k)
+{
+    for (int t = 0; t < T; ++t) {
+        const double v = amax_host[t];
+        if (!std::isfinite(v) || v < 0.0) return fail(KWS_ERR_INVALID, "calibrated maximum of t%d is %g (must be finite and >= 0)", t, v);
+        k[t] = v > 0.0 ? (float)(2048.0 / v) : 0.f;
+    }
+    return KWS_OK;
+}
+
+// the KL search of include/kws.h over one histogram -> i* (0 for an empty one)
+int kl_best_bin(const uint64_t *h)
+{
+    constexpr int kBins = KWS_QUANT_HIST_BINS, kGroups = 128;
+    // prefix sums of the counts and of the nonzero bins: every partial sum is an integer, exact in uint64 (and in double below 2^53)
+    std::vector<uint64_t> pre(kBins + 1, 0), nz(kBins + 1, 0);
+    for (int j = 0; j < kBins; ++j) {
+        pre[j + 1] = pre[j] + h[j];
+        nz[j + 1] = nz[j] + (h[j] != 0);
+    }
+    if (pre[kBins] == 0) return 0;
+    std::vector<double> Q(kBins);
+    double best = INFINITY;
+    int best_i = kBins;
+    for (int i = kGroups; i <= kBins; ++i) {
+        const double tail = (double)(pre[kBins] - pre[i]);
+        if (tail > 0.0 && h[i - 1] == 0) continue;             // p_{i-1} > 0, q_{i-1} = 0: KL_i = +inf
+        double sumQ = 0.0;
+        for (int g = 0; g < kGroups; ++g) {
+            const int j0 = g * i / kGroups, j1 = (g + 1) * i / kGroups;
+            const uint64_t n = nz[j1] - nz[j0];
+            const double v = n ? (double)(pre[j1] - pre[j0]) / (double)n : 0.0;
+            for (int j = j0; j < j1; ++j) {
+                Q[j] = h[j] ? v : 0.0;
+                sumQ += Q[j];
+            }
+        }
+        if (sumQ == 0.0) continue;
+        const double sumP = (double)pre[kBins];                 // sum P = N
+        double kl = 0.0;
+        for (int j = 0; j < i; ++j) {
+            const double P = (double)h[j] + (j == i - 1 ? tail : 0.0);
+            if (P == 0.0) continue;
+            const double p = P / sumP, q = Q[j] / sumQ;
+            kl += p * std::log(p / q);
+        }
+        if (kl < best) { best = kl; best_i = i; }
+    }
+    return best_i;
+}
+
 }  // namespace q8
 }  // namespace kws
 
@@ -483,13 +587,70 @@ int kws_model_calibrate(kws_model *m, const float *feat, int B, const float *par
     return KWS_OK;
 }
 
+int kws_model_calibrate_hist(kws_model *m, const float *feat, int B, const float *params, const float *state, void *ws, size_t ws_bytes,
+                             const float *amax_host, uint64_t *hist, void *stream)
+{
+    (void)ws; (void)ws_bytes;
+    if (m && m->kind == KWS_SIMPLE_CNN_LITE)
+        return lite_calibrate_hist(m, feat, B, params, state, amax_host, hist, static_cast<hipStream_t>(stream));
+    int rc = check_model(m);
+    if (rc) return rc;
+    if (B < 0) return fail(KWS_ERR_INVALID, "batch must be >= 0");
+    if (B == 0) return KWS_OK;
+    if (!feat || !params || !state || !amax_host || !hist) return fail(KWS_ERR_INVALID, "null argument");
+    float k[KWS_QUANT_TENSORS];
+    rc = hist_factors(amax_host, KWS_QUANT_TENSORS, k);
+    if (rc) return rc;
+    HistArgs g{};
+    g.c.feat = feat;
+    for (int l = 0; l < 4; ++l) {
+        g.c.k[l] = params + m->o_k[l]; g.c.gamma[l] = params + m->o_g[l]; g.c.beta[l] = params + m->o_b[l];
+        g.c.mm[l] = state + m->o_mm[l]; g.c.mv[l] = state + m->o_mv[l];
+    }
+    g.c.dk = params + m->o_dk; g.c.db = params + m->o_db;
+    g.B = B;
+    for (int t = 0; t < KWS_QUANT_TENSORS; ++t) g.k[t] = k[t];
+    g.hist = reinterpret_cast<unsigned long long *>(hist);
+    KWS_LAUNCH("qhist_kernel", qhist_kernel, dim3(hist_grid(reinterpret_cast<const void *>(qhist_kernel), B)), dim3(256), 0,
+               static_cast<hipStream_t>(stream), g);
+    KWS_LAUNCH_CHECK("calibration histograms");
+    return KWS_OK;
+}
+
+int kws_quant_kl_ranges(const uint64_t *hist_host, const float *amax_host, int T, float *ranges_out, int32_t *bins_out)
+{
+    if (T < 0) return fail(KWS_ERR_INVALID, "tensor count must be >= 0");
+    if (T > 0 && (!hist_host || !amax_host || !ranges_out)) return fail(KWS_ERR_INVALID, "null argument");
+    for (int t = 0; t < T; ++t)
+        if (!std::isfinite(amax_host[t]) || amax_host[t] < 0.f)
+            return fail(KWS_ERR_INVALID, "calibrated maximum of t%d is %g (must be finite and >= 0)", t, (double)amax_host[t]);
+    // one host thread per tensor (about 2 M log terms each; the searches are independent)
+    std::vector<int> best(T, 0);
+    std::vector<std::thread> pool;
+    for (int t = 1; t < T; ++t) {
+        try {
+            pool.emplace_back([&best, hist_host, t] { best[t] = kl_best_bin(hist_host + (size_t)t * KWS_QUANT_HIST_BINS); });
+        } catch (...) {       // no thread to be had: search here
+            best[t] = kl_best_bin(hist_host + (size_t)t * KWS_QUANT_HIST_BINS);
+        }
+    }
+    if (T > 0) best[0] = kl_best_bin(hist_host);
+    for (auto &th : pool) th.join();
+    for (int t = 0; t < T; ++t) {
+        ranges_out[t] = (float)((double)best[t] * (double)amax_host[t] / (double)KWS_QUANT_HIST_BINS);
+        if (bins_out) bins_out[t] = best[t];
+    }
+    return KWS_OK;
+}
+
 int kws_quantize_simple_cnn(const kws_model *m, const float *params_host, const float *state_host, const float *amax_host, int method,
                             kws_qsimple_cnn *out)
 {
     int rc = check_model(m);
     if (rc) return rc;
     if (!params_host || !state_host || !amax_host || !out) return fail(KWS_ERR_INVALID, "null argument");
-    if (method != KWS_QUANT_MAX && method != KWS_QUANT_RELU6) return fail(KWS_ERR_INVALID, "unknown quantization method %d", method);
+    if (method != KWS_QUANT_MAX && method != KWS_QUANT_RELU6 && method != KWS_QUANT_KL)
+        return fail(KWS_ERR_INVALID, "unknown quantization method %d", method);
     double A[KWS_QUANT_TENSORS];
     for (int t = 0; t < KWS_QUANT_TENSORS; ++t) {
         const double v = amax_host[t];

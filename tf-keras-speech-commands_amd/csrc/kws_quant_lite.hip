@@ -340,7 +340,8 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
         }
 }
 
-// ---- calibration: the fp32 inference forward, one block per clip, max-reduced into amax (plain loops) ------------------------------
+// ---- calibration: the fp32 inference forward of one clip (plain loops) for the max pass (one block per clip, max-reduced into amax)
+// and the histogram pass (persistent, LDS counts): one function, two observers (kws_quant.h) ------------------------------------------
 struct LCalArgs {
     const float *feat;
     const float *dwk[4], *pwk[4], *pwb[4], *gamma[4], *beta[4], *mm[4], *mv[4];
@@ -376,25 +377,26 @@ __device__ float lpw(const float *u, int CI, const float *k, const float *b, int
     return relu ? fmaxf(s, 0.f) : s;
 }
 
-__global__ __launch_bounds__(256) void lite_qcalibrate_kernel(LCalArgs a)
+struct LCalSmem {
+    float x0[kH0 * kW0], u1[kH0 * kW0], a1[150 * kL1], u2[150 * kL1], a2[35 * kL2], u3[12 * kL2], a3[12 * kL3], u4[12 * kL3], a4[kFlat];
+};
+
+// the fp32 forward of one clip; obs(t, v) as in kws_quant.h (|u_l| for the signed depthwise outputs).  Ends without a barrier after
+// the Dense stage (it reads a4 only).
+template <class Obs>
+__device__ __forceinline__ void lite_cal_forward(const LCalArgs &a, const float *f, LCalSmem &sm, Obs &obs)
 {
-    __shared__ float x0[kH0 * kW0], u1[kH0 * kW0], a1[150 * kL1], u2[150 * kL1], a2[35 * kL2], u3[12 * kL2], a3[12 * kL3], u4[12 * kL3],
-        a4[kFlat];
-    __shared__ int red[KWS_QLITE_TENSORS];
     const int tid = threadIdx.x;
-    float mx[KWS_QLITE_TENSORS];
-#pragma unroll
-    for (int t = 0; t < KWS_QLITE_TENSORS; ++t) mx[t] = 0.f;
-    if (tid < KWS_QLITE_TENSORS) red[tid] = 0;
-    const float *f = a.feat + (long)blockIdx.x * (kH0 * kW0);
+    float *x0 = sm.x0, *u1 = sm.u1, *a1 = sm.a1, *u2 = sm.u2, *a2 = sm.a2, *u3 = sm.u3, *a3 = sm.a3, *u4 = sm.u4, *a4 = sm.a4;
     for (int i = tid; i < kH0 * kW0; i += 256) {
-        x0[i] = f[i];
-        mx[0] = fmaxf(mx[0], fabsf(f[i]));
+        const float v = f[i];
+        x0[i] = v;
+        obs(0, fabsf(v));
     }
     __syncthreads();
     for (int o = tid; o < kH0 * kW0; o += 256) {
         u1[o] = ldw(x0, kH0, kW0, 1, a.dwk[0], o / kW0, o % kW0, 0, 1);
-        mx[1] = fmaxf(mx[1], fabsf(u1[o]));
+        obs(1, fabsf(u1[o]));
     }
     __syncthreads();
     for (int o = tid; o < 150 * kL1; o += 256) {      // pointwise 1 + BN + ReLU6 + pool: 15 x 10 x 16
@@ -405,12 +407,12 @@ __global__ __launch_bounds__(256) void lite_qcalibrate_kernel(LCalArgs a)
             best = fmaxf(best, lbn_relu6(lpw(u1 + y * kW0 + x, 1, a.pwk[0], a.pwb[0], kL1, co, false), a, 0, co));
         }
         a1[o] = best;
-        mx[2] = fmaxf(mx[2], best);
+        obs(2, best);
     }
     __syncthreads();
     for (int o = tid; o < 150 * kL1; o += 256) {
         u2[o] = ldw(a1, 15, 10, kL1, a.dwk[1], (o / kL1) / 10, (o / kL1) % 10, o % kL1, 1);
-        mx[3] = fmaxf(mx[3], fabsf(u2[o]));
+        obs(3, fabsf(u2[o]));
     }
     __syncthreads();
     for (int o = tid; o < 35 * kL2; o += 256) {       // pointwise 2 + BN + ReLU6 + pool: 7 x 5 x 32
@@ -421,23 +423,23 @@ __global__ __launch_bounds__(256) void lite_qcalibrate_kernel(LCalArgs a)
             best = fmaxf(best, lbn_relu6(lpw(u2 + (y * 10 + x) * kL1, kL1, a.pwk[1], a.pwb[1], kL2, co, false), a, 1, co));
         }
         a2[o] = best;
-        mx[4] = fmaxf(mx[4], best);
+        obs(4, best);
     }
     __syncthreads();
     for (int o = tid; o < 12 * kL2; o += 256) {       // depthwise 3, stride 2: 4 x 3 x 32
         u3[o] = ldw(a2, 7, 5, kL2, a.dwk[2], (o / kL2) / 3, (o / kL2) % 3, o % kL2, 2);
-        mx[5] = fmaxf(mx[5], fabsf(u3[o]));
+        obs(5, fabsf(u3[o]));
     }
     __syncthreads();
     for (int o = tid; o < 12 * kL3; o += 256) {
         const float v = lbn_relu6(lpw(u3 + (o / kL3) * kL2, kL2, a.pwk[2], a.pwb[2], kL3, o % kL3, true), a, 2, o % kL3);
         a3[o] = v;
-        mx[6] = fmaxf(mx[6], v);
+        obs(6, v);
     }
     __syncthreads();
     for (int o = tid; o < 12 * kL3; o += 256) {
         u4[o] = ldw(a3, 4, 3, kL3, a.dwk[3], (o / kL3) / 3, (o / kL3) % 3, o % kL3, 1);
-        mx[7] = fmaxf(mx[7], fabsf(u4[o]));
+        obs(7, fabsf(u4[o]));
     }
     __syncthreads();
     for (int o = tid; o < kFlat; o += 256) {          // pointwise 4 + relu + BN + ReLU6 + pool: 2 x 1 x 128
@@ -448,20 +450,58 @@ __global__ __launch_bounds__(256) void lite_qcalibrate_kernel(LCalArgs a)
             best = fmaxf(best, lbn_relu6(lpw(u4 + (y * 3 + x) * kL3, kL3, a.pwk[3], a.pwb[3], kL4, co, true), a, 3, co));
         }
         a4[o] = best;
-        mx[8] = fmaxf(mx[8], best);
+        obs(8, best);
     }
     __syncthreads();
     for (int o = tid; o < kD; o += 256) {             // Dense(128) + ReLU6
         float s = a.db[o];
 #pragma unroll 4
         for (int k = 0; k < kFlat; ++k) s += a4[k] * a.dk[k * kD + o];
-        mx[9] = fmaxf(mx[9], fminf(fmaxf(s, 0.f), 6.f));
+        obs(9, fminf(fmaxf(s, 0.f), 6.f));
     }
+}
+
+__global__ __launch_bounds__(256) void lite_qcalibrate_kernel(LCalArgs a)
+{
+    __shared__ LCalSmem sm;
+    __shared__ int red[KWS_QLITE_TENSORS];
+    const int tid = threadIdx.x;
+    CalMax<KWS_QLITE_TENSORS> obs;
+    if (tid < KWS_QLITE_TENSORS) red[tid] = 0;
+    lite_cal_forward(a, a.feat + (long)blockIdx.x * (kH0 * kW0), sm, obs);
     // non-negative floats order like their bit patterns as int (a NaN's pattern would win: the host rejects it)
 #pragma unroll
-    for (int t = 0; t < KWS_QLITE_TENSORS; ++t) atomicMax(&red[t], __float_as_int(mx[t]));
+    for (int t = 0; t < KWS_QLITE_TENSORS; ++t) atomicMax(&red[t], __float_as_int(obs.mx[t]));
     __syncthreads();
     if (tid < KWS_QLITE_TENSORS) atomicMax(reinterpret_cast<int *>(a.amax) + tid, red[tid]);
+}
+
+struct LHistArgs {
+    LCalArgs c;
+    int B;
+    float k[KWS_QLITE_TENSORS];
+    unsigned long long *hist;
+};
+
+// persistent, as qhist_kernel (kws_quant.hip): 80 KB of LDS counts beside the forward's 37.2 KB, one block per CU
+__global__ __launch_bounds__(256) void lite_qhist_kernel(LHistArgs g)
+{
+    __shared__ LCalSmem sm;
+    __shared__ unsigned cnt[KWS_QLITE_TENSORS * KWS_QUANT_HIST_BINS];
+    for (int i = threadIdx.x; i < KWS_QLITE_TENSORS * KWS_QUANT_HIST_BINS; i += 256) cnt[i] = 0u;
+    CalHist<KWS_QLITE_TENSORS> obs;
+    obs.cnt = cnt;
+#pragma unroll
+    for (int t = 0; t < KWS_QLITE_TENSORS; ++t) obs.k[t] = g.k[t];
+    for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
+        __syncthreads();      // the previous clip's Dense stage has read a4; the counters are cleared
+        lite_cal_forward(g.c, g.c.feat + (long)b * (kH0 * kW0), sm, obs);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < KWS_QLITE_TENSORS * KWS_QUANT_HIST_BINS; i += 256) {
+        const unsigned c = cnt[i];
+        if (c) atomicAdd(g.hist + i, (unsigned long long)c);
+    }
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
@@ -495,6 +535,32 @@ int lite_qforward(const kws_qmodel *q, const float *feat, int B, float *logits, 
                 q->fp[1], q->fp[2], q->fp[3], q->fd, q->fh, q->ep, q->bq, logits, probs, argmax};
     KWS_LAUNCH("lite_qforward_kernel", lite_qforward_kernel, dim3(blocks_for(B, kG)), dim3(kThreads), kLLds, s, a);
     KWS_LAUNCH_CHECK("int8 lite forward");
+    return KWS_OK;
+}
+
+int lite_calibrate_hist(const kws_model *m, const float *feat, int B, const float *params, const float *state, const float *amax_host,
+                        uint64_t *hist, hipStream_t s)
+{
+    int rc = check_lite(m);
+    if (rc) return rc;
+    if (B < 0) return fail(KWS_ERR_INVALID, "batch must be >= 0");
+    if (B == 0) return KWS_OK;
+    if (!feat || !params || !state || !amax_host || !hist) return fail(KWS_ERR_INVALID, "null argument");
+    LHistArgs g{};
+    rc = hist_factors(amax_host, KWS_QLITE_TENSORS, g.k);
+    if (rc) return rc;
+    g.c.feat = feat;
+    for (int l = 0; l < 4; ++l) {
+        g.c.dwk[l] = params + m->o_dwk[l]; g.c.pwk[l] = params + m->o_pwk[l]; g.c.pwb[l] = params + m->o_pwb[l];
+        g.c.gamma[l] = params + m->o_g[l]; g.c.beta[l] = params + m->o_b[l];
+        g.c.mm[l] = state + m->o_mm[l]; g.c.mv[l] = state + m->o_mv[l];
+    }
+    g.c.dk = params + m->o_dk; g.c.db = params + m->o_db;
+    g.B = B;
+    g.hist = reinterpret_cast<unsigned long long *>(hist);
+    KWS_LAUNCH("lite_qhist_kernel", lite_qhist_kernel, dim3(hist_grid(reinterpret_cast<const void *>(lite_qhist_kernel), B)), dim3(256), 0, s,
+               g);
+    KWS_LAUNCH_CHECK("lite calibration histograms");
     return KWS_OK;
 }
 
@@ -534,7 +600,8 @@ int kws_quantize_simple_cnn_lite(const kws_model *m, const float *params_host, c
     int rc = check_lite(m);
     if (rc) return rc;
     if (!params_host || !state_host || !amax_host || !out) return fail(KWS_ERR_INVALID, "null argument");
-    if (method != KWS_QUANT_MAX && method != KWS_QUANT_RELU6) return fail(KWS_ERR_INVALID, "unknown quantization method %d", method);
+    if (method != KWS_QUANT_MAX && method != KWS_QUANT_RELU6 && method != KWS_QUANT_KL)
+        return fail(KWS_ERR_INVALID, "unknown quantization method %d", method);
     double A[KWS_QLITE_TENSORS];
     for (int t = 0; t < KWS_QLITE_TENSORS; ++t) {
         const double v = amax_host[t];

@@ -83,7 +83,9 @@ def main():
                         help='also quantize the model to int8 (post-training, simple_cnn / simple_cnn_lite) and report its accuracy and agreement')
     parser.add_argument('--calib_path', type=str, default=None, help='dataset to calibrate the int8 ranges on (default: the evaluated set)')
     parser.add_argument('--calib_samples', type=int, default=1000, help='calibration clips, drawn with a fixed seed')
-    parser.add_argument('--quant_method', type=str, default='max', choices=['max', 'relu6'])
+    parser.add_argument('--quant_method', type=str, default='max', choices=['max', 'relu6', 'kl'],
+                        help="activation ranges: calibrated maxima ('max'), 6 for every ReLU6 tensor ('relu6'), or the ranges of least KL "
+                             "divergence of a second, histogram pass ('kl', the reference's MNN recipe)")
     parser.add_argument('--save_quantized', type=str, default=None, help='write the int8 model to this .npz')
     args = parser.parse_args()
     class_names = get_classes(args.classes_path)

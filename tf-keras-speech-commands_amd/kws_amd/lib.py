@@ -79,8 +79,12 @@ FILTER_MAX_SAMPLES = 16320
 
 QUANT_TENSORS = 6
 QUANT_MAX_CLASSES = 48
-QUANT_MAX, QUANT_RELU6 = 0, 1
+QUANT_MAX, QUANT_RELU6, QUANT_KL = 0, 1, 2
+# the methods that turn bare calibrated maxima into ranges; "kl" needs histograms (kws_amd.quant.calibrate_kl / from_histograms)
 QUANT_METHODS = {"max": QUANT_MAX, "relu6": QUANT_RELU6}
+# every method a quantized snapshot may record (its `method` field, the .npz __meta__)
+QUANT_SNAPSHOT_METHODS = {"max": QUANT_MAX, "relu6": QUANT_RELU6, "kl": QUANT_KL}
+QUANT_HIST_BINS = 2048
 
 
 class KwsQSimpleCnn(ctypes.Structure):
@@ -244,6 +248,8 @@ def get_lib():
     L.kws_model_calibrate_lite.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp]
     L.kws_quantize_simple_cnn_lite.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(KwsQSimpleCnnLite)]
     L.kws_qmodel_create_lite.argtypes = [vp, ctypes.POINTER(KwsQSimpleCnnLite), ctypes.POINTER(vp)]
+    L.kws_model_calibrate_hist.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]
+    L.kws_quant_kl_ranges.argtypes = [vp, vp, i32, vp, vp]
     _lib = L
     return L
 

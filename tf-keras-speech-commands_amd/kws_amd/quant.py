@@ -9,6 +9,12 @@ tools/model_converter/custom_tflite_convert.py --post_training_quantize) and mea
     probs, argmax = q.forward(features)                   # ONE int8 kernel from features to probabilities
     q.save("model_int8.npz"); q = load("model_int8.npz")
 
+Entropy (KL) calibration, the reference's deployment recipe ("feature_quantize_method": "KL"): a max pass, then a histogram pass over
+the same clips, then the KL search on the host:
+
+    amax, hist = calibrate_kl(dm, feature_batches)        # = calibrate(...), then histograms(dm, feature_batches, amax)
+    q = QuantizedCNN.from_model_histograms(dm, amax, hist)    # ranges kl_ranges(hist, amax); q.method == "kl"
+
 simple_cnn_lite: calibrate() returns its ten maxima (x and the depthwise outputs u1..u4 beside the activations) and QuantizedCNNLite
 takes the place of QuantizedCNN, with the same interface.  A quantized model is a frozen snapshot of the weights it was made from."""
 import ctypes
@@ -68,6 +74,59 @@ def calibrate(dm, feature_batches, amax=None):
     return amax.cpu().numpy()
 
 
+def _n_tensors(dm):
+    return _l.QLITE_TENSORS if dm.spec.model_type == "simple_cnn_lite" else _l.QUANT_TENSORS
+
+
+def histograms(dm, feature_batches, amax, hist=None):
+    """Running counts (CUDA int64 (T, 2048), T = 6 / 10) of the quantized tensors of the fp32 inference forward over `feature_batches`
+    (as calibrate takes them), binned by the finished maxima `amax` of calibrate() over the same set (include/kws.h,
+    kws_model_calibrate_hist: |v| * (2048 / amax_t) for every nonzero value).  `hist`: a tensor of earlier counts to add to (every
+    call adds its batches exactly: halves fold to the whole); a fresh zero one by default."""
+    torch = _torch()
+    L = _l.get_lib()
+    n = _n_tensors(dm)
+    a = np.ascontiguousarray(np.asarray(amax, np.float32).reshape(-1))
+    if a.size != n:
+        raise ValueError("amax must hold %d values" % n)
+    if hist is None:
+        hist = torch.zeros((n, _l.QUANT_HIST_BINS), dtype=torch.int64, device=dm.device)
+    elif hist.dtype != torch.int64 or not hist.is_cuda or tuple(hist.shape) != (n, _l.QUANT_HIST_BINS) or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous CUDA int64 tensor of shape (%d, %d)" % (n, _l.QUANT_HIST_BINS))
+    if isinstance(feature_batches, (np.ndarray, torch.Tensor)):
+        feature_batches = [feature_batches]
+    for fb in feature_batches:
+        f = _as_feature_tensor(fb, dm.spec)
+        _l.check(L.kws_model_calibrate_hist(dm.spec.handle, f.data_ptr(), f.shape[0], dm.params.data_ptr(), dm.state.data_ptr(), None, 0,
+                                            a.ctypes.data, hist.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return hist
+
+
+def kl_ranges(hist, amax):
+    """Host only: the KL ranges A_t (numpy float32 (T,)) of the counts `hist` ((T, 2048), a CUDA tensor or an array) binned by `amax`
+    (kws_quant_kl_ranges: the smallest of the least-divergent clip points i*, A_t = i* amax_t / 2048)."""
+    h = hist.cpu().numpy() if hasattr(hist, "cpu") else np.asarray(hist)
+    h = np.ascontiguousarray(h.astype(np.uint64).reshape(-1, _l.QUANT_HIST_BINS))
+    a = np.ascontiguousarray(np.asarray(amax, np.float32).reshape(-1))
+    if a.size != h.shape[0]:
+        raise ValueError("amax holds %d values for %d histograms" % (a.size, h.shape[0]))
+    out = np.zeros(a.size, np.float32)
+    _l.check(_l.get_lib().kws_quant_kl_ranges(h.ctypes.data, a.ctypes.data, a.size, out.ctypes.data, None))
+    return out
+
+
+def calibrate_kl(dm, feature_batches):
+    """The two calibration passes of the KL method over `feature_batches` -> (amax, hist): calibrate(), then histograms() with its
+    maxima.  The input is read twice, so it must be re-iterable: one array / tensor, or a list or tuple of them (TypeError for a
+    one-shot iterator)."""
+    import torch
+    if not isinstance(feature_batches, (np.ndarray, torch.Tensor, list, tuple)):
+        raise TypeError("calibrate_kl reads its input twice: pass an array, a tensor, or a list or tuple of them, not %s"
+                        % type(feature_batches).__name__)
+    amax = calibrate(dm, feature_batches)
+    return amax, histograms(dm, feature_batches, amax)
+
+
 class QuantizedCNN(object):
     """An int8 simple_cnn on the current HIP device (kws_qmodel).  Build it with from_model or load."""
     _STRUCT = _l.KwsQSimpleCnn
@@ -97,7 +156,23 @@ class QuantizedCNN(object):
         calibrated maxima `amax` (6 values); method "max" (the calibrated activation ranges, capped at 6) or "relu6" (every activation
         range 6)."""
         if method not in _l.QUANT_METHODS:
-            raise ValueError("method must be one of %s" % sorted(_l.QUANT_METHODS))
+            raise ValueError("method must be one of %s%s" % (sorted(_l.QUANT_METHODS), "; the kl method needs histograms of the calibration"
+                             " set: calibrate_kl, then from_histograms / from_model_histograms" if method == "kl" else ""))
+        return cls._quantize(spec, params, state, amax, _l.QUANT_METHODS[method])
+
+    @classmethod
+    def from_histograms(cls, spec, params, state, amax, hist):
+        """Host only: quantize as from_weights with the KL ranges of the calibration histograms `hist` (histograms() / calibrate_kl)
+        binned by the maxima `amax`; the rules of "max" apply to those ranges and the snapshot records method "kl"."""
+        return cls._quantize(spec, params, state, kl_ranges(hist, amax), _l.QUANT_KL)
+
+    @classmethod
+    def from_model_histograms(cls, dm, amax, hist):
+        """Quantize the CURRENT weights of a DeviceModel with KL ranges (see from_histograms)"""
+        return cls.from_histograms(dm.spec, dm.params.cpu().numpy(), dm.state.cpu().numpy(), amax, hist)
+
+    @classmethod
+    def _quantize(cls, spec, params, state, amax, code):
         p = np.ascontiguousarray(np.asarray(params, np.float32).reshape(-1))
         s = np.ascontiguousarray(np.asarray(state, np.float32).reshape(-1))
         a = np.ascontiguousarray(np.asarray(amax, np.float32).reshape(-1))
@@ -106,8 +181,7 @@ class QuantizedCNN(object):
         if a.size != cls._NT:
             raise ValueError("amax must hold %d values" % cls._NT)
         q = cls._STRUCT()
-        _l.check(getattr(_l.get_lib(), cls._QUANTIZE)(spec.handle, p.ctypes.data, s.ctypes.data, a.ctypes.data, _l.QUANT_METHODS[method],
-                                                      ctypes.byref(q)))
+        _l.check(getattr(_l.get_lib(), cls._QUANTIZE)(spec.handle, p.ctypes.data, s.ctypes.data, a.ctypes.data, code, ctypes.byref(q)))
         return cls(spec, q)
 
     @classmethod
@@ -121,7 +195,7 @@ class QuantizedCNN(object):
 
     @property
     def method(self):
-        return {v: k for k, v in _l.QUANT_METHODS.items()}[self._q.method]
+        return {v: k for k, v in _l.QUANT_SNAPSHOT_METHODS.items()}[self._q.method]
 
     @property
     def arrays(self):
@@ -180,7 +254,7 @@ class QuantizedCNN(object):
         C = spec.num_classes
         q = cls._STRUCT()
         q.num_classes = C
-        q.method = _l.QUANT_METHODS[meta[5]]
+        q.method = _l.QUANT_SNAPSHOT_METHODS[meta[5]]
         q.inv_s0 = float(z["inv_s0"])
         for n in cls._SHAPES:
             np.ctypeslib.as_array(getattr(q, n))[:] = z[n].reshape(-1)

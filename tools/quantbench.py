@@ -8,7 +8,11 @@ from a separate `rocprofv3 --kernel-trace --stats` run of `--kernel-only`.  Prin
 
 --model simple_cnn_lite: the int8 simple_cnn_lite forward against the fp32 and the fp16 lite forwards (kws_model_forward at
 KWS_INFER_FP32 / KWS_INFER_FP16, weight tables prepared) and the three graph-captured featurize + forward sessions, at B = 4096 and
-16 384 (--batches)."""
+16 384 (--batches).
+
+--calib kl: the calibration passes of the KL method for both models at B = 4096 (--calib-batch): the max pass (kws_model_calibrate[_lite])
+and the histogram pass (kws_model_calibrate_hist) alternating within each round, then the KL search on the host (kws_quant_kl_ranges)
+over the histograms of that set.  With --kernel-only it only launches the two passes of both models."""
 import argparse
 import json
 import os
@@ -116,6 +120,62 @@ def lite_main(args):
     return out
 
 
+def calib_main(args):
+    """--calib kl: max pass, histogram pass and host KL search for simple_cnn and simple_cnn_lite"""
+    import time
+    from classifier.params import pr
+    from kws_amd import lib as _l
+    from kws_amd.init import init_weights
+    from kws_amd.model import DeviceModel, ModelSpec
+    from kws_amd.quant import calibrate, histograms
+    torch.manual_seed(0)
+    B, C = args.calib_batch, 36
+    feat = (3.0 * torch.randn((B, pr.n_features, pr.feature_size), device="cuda")).contiguous()
+    L = _l.get_lib()
+    out = {"calib": "kl", "B": B, "C": C, "models": {}}
+    for model in ("simple_cnn", "simple_cnn_lite"):
+        spec = ModelSpec(model, C, pr.n_features, pr.feature_size)
+        dm = DeviceModel(spec)
+        dm.set_weights(init_weights(spec, seed=0))
+        amax = calibrate(dm, feat)
+        T = amax.size
+        amax_d = torch.zeros((T,), dtype=torch.float32, device="cuda")
+        hist = torch.zeros((T, _l.QUANT_HIST_BINS), dtype=torch.int64, device="cuda")
+        passes = {"max": lambda: calibrate(dm, feat, amax=amax_d), "hist": lambda: histograms(dm, feat, amax, hist=hist)}
+        if args.kernel_only:
+            for _ in range(args.iters):
+                for f in passes.values():
+                    f()
+            torch.cuda.synchronize()
+            out["models"][model] = {"kernel_only": True, "launches": len(passes) * args.iters}
+            continue
+        # calibrate() copies its maxima to the host after the launch; time the launches alone
+        fmax = lambda: _l.check(getattr(L, "kws_model_calibrate_lite" if model == "simple_cnn_lite" else "kws_model_calibrate")(
+            spec.handle, feat.data_ptr(), B, dm.params.data_ptr(), dm.state.data_ptr(), None, 0, amax_d.data_ptr(),
+            torch.cuda.current_stream().cuda_stream))
+        passes["max"] = fmax
+        t = {n: [] for n in passes}
+        for _ in range(args.rounds):
+            for n, f in passes.items():
+                t[n].append(time_ms(f, args.iters))
+        hist.zero_()
+        histograms(dm, feat, amax, hist=hist)
+        h = np.ascontiguousarray(hist.cpu().numpy().astype(np.uint64))
+        ranges, bins = np.zeros(T, np.float32), np.zeros(T, np.int32)
+        ks = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            _l.check(L.kws_quant_kl_ranges(h.ctypes.data, amax.ctypes.data, T, ranges.ctypes.data, bins.ctypes.data))
+            ks.append(time.perf_counter() - t0)
+        res = {"T": T, "pass_ms": {n: {"median_ms": round(float(np.median(v)), 4), "rounds": [round(x, 4) for x in v]} for n, v in t.items()},
+               "kl_search_host_s": round(float(np.median(ks)), 4), "amax": [round(float(v), 4) for v in amax],
+               "kl_ranges": [round(float(v), 4) for v in ranges], "kl_bins": bins.tolist()}
+        res["hist_over_max"] = round(res["pass_ms"]["hist"]["median_ms"] / res["pass_ms"]["max"]["median_ms"], 3)
+        out["models"][model] = res
+    out["device"] = torch.cuda.get_device_name(0)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -124,9 +184,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--model", default="simple_cnn", choices=["simple_cnn", "simple_cnn_lite"])
     ap.add_argument("--batches", type=int, nargs="+", default=[4096, 16384], help="simple_cnn_lite: the batch sizes")
+    ap.add_argument("--calib", default=None, choices=["kl"], help="time the calibration passes of the KL method instead of the forwards")
+    ap.add_argument("--calib-batch", type=int, default=4096)
     args = ap.parse_args()
-    if args.model == "simple_cnn_lite":
-        res = lite_main(args)
+    if args.calib or args.model == "simple_cnn_lite":
+        res = calib_main(args) if args.calib else lite_main(args)
         line = json.dumps(res)
         print(line)
         if args.out:
