@@ -7,7 +7,7 @@ import numpy as np
 
 from oracle import model_oracle as mo
 
-from int8_ref import BN_EPS, _weight_q, _matmul, _pool, requant
+from int8_ref import BN_EPS, _weight_q, _matmul, _pool, head, requant
 
 CIN, COUT = (1, 16, 32, 64), (16, 32, 64, 128)
 BQ_MAX = 2.0 ** 23
@@ -81,6 +81,11 @@ def _stage(arr, l, c, stride=1, relu=False):
 
 def forward(arr, feat):
     """arr: QuantizedCNNLite.arrays (or quantize()'s dict); feat (B, 30, 20) float32 -> (logits float32, probs float32, argmax int32)"""
+    return head(arr, trunk(arr, feat))
+
+
+def trunk(arr, feat):
+    """the network up to the Dense layer's codes (B, 128), int64"""
     x = np.asarray(feat, np.float32).reshape(-1, 30, 20, 1)
     c = np.clip(np.rint(x * np.float32(arr["inv_s0"])), -127, 127).astype(np.int64)
     c = _pool(_stage(arr, 1, c))
@@ -88,10 +93,4 @@ def forward(arr, feat):
     c = _stage(arr, 3, c, stride=2, relu=True)
     c = _pool(_stage(arr, 4, c, relu=True))
     c = c.reshape(c.shape[0], -1)
-    d = requant(_matmul(c, arr["dense_w"]), arr["Md"], arr["Bd"])
-    acc = _matmul(d, arr["head_w"])
-    logits = acc.astype(np.float32) * np.asarray(arr["Mh"], np.float32) + np.asarray(arr["head_bias"], np.float32)
-    m = logits.max(1, keepdims=True)
-    e = np.exp(logits - m)
-    probs = e * (np.float32(1.0) / e.sum(1, keepdims=True, dtype=np.float32))
-    return logits.astype(np.float32), probs.astype(np.float32), logits.argmax(1).astype(np.int32)
+    return requant(_matmul(c, arr["dense_w"]), arr["Md"], arr["Bd"])

@@ -80,6 +80,11 @@ def _pool(x):
 
 def forward(arr, feat):
     """arr: QuantizedCNN.arrays (or quantize()'s dict); feat (B, 30, 20) float32 -> (logits float32, probs float32, argmax int32)"""
+    return head(arr, trunk(arr, feat))
+
+
+def trunk(arr, feat):
+    """the network up to the Dense layer's codes (B, 128), int64"""
     x = np.asarray(feat, np.float32).reshape(-1, 30, 20, 1)
     c = np.clip(np.rint(x * np.float32(arr["inv_s0"])), -127, 127).astype(np.int64)
     c = _pool(requant(_conv(c, arr["conv_w1"]), arr["M1"], arr["B1"]))
@@ -87,7 +92,11 @@ def forward(arr, feat):
     c = requant(_conv(c, arr["conv_w3"], 2), arr["M3"], arr["B3"])
     c = _pool(requant(np.maximum(_conv(c, arr["conv_w4"]), 0), arr["M4"], arr["B4"]))
     c = c.reshape(c.shape[0], -1)
-    d = requant(_matmul(c, arr["dense_w"]), arr["Md"], arr["Bd"])
+    return requant(_matmul(c, arr["dense_w"]), arr["Md"], arr["Bd"])
+
+
+def head(arr, d):
+    """the head on the Dense layer's codes d (B, 128) -> (logits, probs, argmax) as forward() returns them"""
     acc = _matmul(d, arr["head_w"])
     logits = acc.astype(np.float32) * np.asarray(arr["Mh"], np.float32) + np.asarray(arr["head_bias"], np.float32)
     m = logits.max(1, keepdims=True)

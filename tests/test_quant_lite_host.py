@@ -74,8 +74,18 @@ def test_weight_order_is_the_keras_one():
 
 @pytest.mark.parametrize("method", ["max", "relu6"])
 def test_quantizer_matches_the_float64_restatement_bit_for_bit(method):
+    _check_bit_for_bit(method, C)
+
+
+@pytest.mark.parametrize("method", ["max", "relu6"])
+def test_quantizer_matches_the_float64_restatement_at_48_classes(method):
+    """the largest head the int8 kernel takes (three full 16-column tiles)"""
+    _check_bit_for_bit(method, 48)
+
+
+def _check_bit_for_bit(method, classes):
     from kws_amd.quant import QuantizedCNNLite
-    spec = _spec()
+    spec = _spec(classes=classes)
     ws = _weights(spec)
     p, s = _flat(spec, ws)
     got = QuantizedCNNLite.from_weights(spec, p, s, AMAX, method).arrays
