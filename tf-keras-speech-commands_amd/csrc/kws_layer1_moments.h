@@ -135,22 +135,18 @@ __device__ __forceinline__ void l1_bn_from_moments(const double *__restrict__ q,
 // split the conv3 / conv4 / dense weights into bf16 planes and clear the gradient buffer (they used to ride with the statistics
 // pass this kernel replaces).
 struct L1PrepArgs { SplitDescs all; float *zero_buf; long zero_n; int nsplit, nzero; };
-template <bool PREP>
-__global__ __launch_bounds__(256) void l1m_act_pool_moments_kernel(const float *__restrict__ feat, const float *__restrict__ wk,
-                                                                    const double *__restrict__ q, const float *__restrict__ gamma,
-                                                                    const float *__restrict__ beta, float *__restrict__ moving_mean,
-                                                                    float *__restrict__ moving_var, BnCoef k, float *__restrict__ a1, int B, int H,
-                                                                    int W, int clips_per_wave, int nclip_blocks, L1PrepArgs prep)
+// PREP block e: one slice of a weight split, or one share of the gradient clear (kws_l1_conv2.h's kernel carries the same blocks)
+__device__ __forceinline__ void l1_prep_block(const L1PrepArgs &prep, int e)
 {
-    if (PREP && (int)blockIdx.x >= nclip_blocks) {
-        const int e = blockIdx.x - nclip_blocks;
-        if (e < 3 * prep.nsplit) { weight_split_slice(prep.all.d[e / prep.nsplit], e % prep.nsplit, prep.nsplit); return; }
-        if (prep.zero_buf)
-            for (long i = (long)(e - 3 * prep.nsplit) * 256 + threadIdx.x; i < prep.zero_n; i += (long)prep.nzero * 256) prep.zero_buf[i] = 0.f;
-        return;
-    }
-    extern __shared__ float l1smem[];
-    __shared__ float s_sc[16], s_sh[16];
+    if (e < 3 * prep.nsplit) { weight_split_slice(prep.all.d[e / prep.nsplit], e % prep.nsplit, prep.nsplit); return; }
+    if (prep.zero_buf)
+        for (long i = (long)(e - 3 * prep.nsplit) * 256 + threadIdx.x; i < prep.zero_n; i += (long)prep.nzero * 256) prep.zero_buf[i] = 0.f;
+}
+// threads 0..15: scale / shift of channel threadIdx.x into s_sc / s_sh; block 0 also writes the coefficients and the moving statistics
+__device__ __forceinline__ void l1_bn_prologue(const double *__restrict__ q, const float *__restrict__ wk, const float *__restrict__ gamma,
+                                               const float *__restrict__ beta, float *__restrict__ moving_mean, float *__restrict__ moving_var,
+                                               BnCoef k, float *s_sc, float *s_sh)
+{
     if (threadIdx.x < 16) {
         const int c = threadIdx.x;
         double mean, var, inv, sc, sh;
@@ -164,6 +160,18 @@ __global__ __launch_bounds__(256) void l1m_act_pool_moments_kernel(const float *
             moving_var[c] = (float)((double)moving_var[c] * kBnMomentum + unbiased * (1.0 - kBnMomentum));
         }
     }
+}
+template <bool PREP>
+__global__ __launch_bounds__(256) void l1m_act_pool_moments_kernel(const float *__restrict__ feat, const float *__restrict__ wk,
+                                                                    const double *__restrict__ q, const float *__restrict__ gamma,
+                                                                    const float *__restrict__ beta, float *__restrict__ moving_mean,
+                                                                    float *__restrict__ moving_var, BnCoef k, float *__restrict__ a1, int B, int H,
+                                                                    int W, int clips_per_wave, int nclip_blocks, L1PrepArgs prep)
+{
+    if (PREP && (int)blockIdx.x >= nclip_blocks) { l1_prep_block(prep, blockIdx.x - nclip_blocks); return; }
+    extern __shared__ float l1smem[];
+    __shared__ float s_sc[16], s_sh[16];
+    l1_bn_prologue(q, wk, gamma, beta, moving_mean, moving_var, k, s_sc, s_sh);
     const int lane = threadIdx.x & 63, li = lane & 15, lq = lane >> 4;
     if (H == 30 && W == 20) {                     // the default map: compile-time form (kws_layer1.h: l1f_forward_clips)
         __syncthreads();

@@ -15,6 +15,7 @@
 #include "kws_layer1.h"
 #include "kws_layer1_moments.h"
 #include "kws_layer1_fast.h"
+#include "kws_l1_conv2.h"
 #include "kws_lite.h"
 #include "kws_lite_f16.h"
 #include "kws_infer_fused.h"
@@ -543,6 +544,22 @@ int cnn_forward(const kws_model *m, const float *feat, int B, const float *param
     }
     if (!training && !prepared)
         if (int rc = infer_coefs(m, params, state, w, s)) return rc;
+    const bool routed_bwd2 = cnn_compact_g2(m, bf16);
+    const bool fuse_pool2 = group_fwd && routed_bwd2 && d.H1 == kGrH1 && d.W1 == kGrW1;
+    // finalize-free batch statistics (kws_device.h: acc_add), non-deterministic training at the default geometry: conv2 .. conv4 add their
+    // sums to accumulator sets and the next kernel of the chain derives scale / shift in its prologue -- three launches less
+    const bool acc_fwd = fuse_pool2 && !m->deterministic && kCh[4] <= 128 && !stream_capturing(s);
+    unsigned fpar[4] = {0, 0, 0, 0};
+    if (acc_fwd) {
+        if (!R) R = const_cast<kws_model *>(m)->dev_res();
+        if (!R) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
+        for (int l = 1; l < 4; ++l) fpar[l] = R->acc_uses[0][l]++;
+        KWS_TRY(acc_make_clean(R, s));
+        R->acc_dirty = true;               // until every kernel of this pass is enqueued
+    }
+    // layer 1 and conv2's forward as ONE clip-resident kernel (kws_l1_conv2.h): split-precision training at the default map with the
+    // PREP blocks in the layer-1 grid and conv2's sums in the accumulator form; every other case keeps the two kernels
+    const bool l1_conv2 = prep_in_stats && acc_fwd && d.H0 == 30 && d.W0 == 20;
     // layer 1: conv1 is recomputed from the feature map wherever z1 is needed (kws_layer1.h)
     {
         const int cpb = std::max(1, (B + kMaxStatBlocks - 1) / kMaxStatBlocks), nb = (B + cpb - 1) / cpb;
@@ -569,6 +586,15 @@ int cnn_forward(const kws_model *m, const float *feat, int B, const float *param
             if (prep_in_stats) {
                 pa.all = split_descs(m, params, w, group_fwd, dense_fused); pa.zero_buf = zero_grads; pa.zero_n = (long)m->P;
                 pa.nsplit = kPrepSplitBlocks; pa.nzero = kPrepZeroBlocks;
+            }
+            if (l1_conv2) {
+                // conv2's grid (one block per clip up to kMaxStatBlocks, then clips b + k * nblk) plus the PREP blocks
+                const int nblk = std::min(B, kMaxStatBlocks);
+                const size_t sml = L1Conv2Lds<30, 20>::BYTES;
+                KWS_LAUNCH("l1_conv2_fwd_bf16<30,20>", (l1_conv2_fwd_bf16_kernel<30, 20>), dim3(nblk + kPrepBlocks), dim3(256), sml, s, feat, kern1,
+                           q, params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], params + m->o_k[1], w.z[1],
+                           acc_set(R, 0, 1, fpar[1]), B, nblk, pa);
+            } else if (prep_in_stats) {
                 KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_moments_kernel<true>, dim3(nbm + kPrepBlocks), dim3(256), smemm, s, feat, kern1, q,
                            params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], B, d.H0, d.W0, cpw, nbm, pa);
             } else {
@@ -589,19 +615,6 @@ int cnn_forward(const kws_model *m, const float *feat, int B, const float *param
     if (hook) KWS_TRY(hook->fire(8, s));                 // behind layer 1: the featurizer then shares the chip with the forward convolutions
     bool bound6 = false;
     const bool a3_on_load = cnn_a3_on_load(m, bf16, training);
-    const bool routed_bwd2 = cnn_compact_g2(m, bf16);
-    const bool fuse_pool2 = group_fwd && routed_bwd2 && d.H1 == kGrH1 && d.W1 == kGrW1;
-    // finalize-free batch statistics (kws_device.h: acc_add), non-deterministic training at the default geometry: conv2 .. conv4 add their
-    // sums to accumulator sets and the next kernel of the chain derives scale / shift in its prologue -- three launches less
-    const bool acc_fwd = fuse_pool2 && !m->deterministic && kCh[4] <= 128 && !stream_capturing(s);
-    unsigned fpar[4] = {0, 0, 0, 0};
-    if (acc_fwd) {
-        if (!R) R = const_cast<kws_model *>(m)->dev_res();
-        if (!R) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
-        for (int l = 1; l < 4; ++l) fpar[l] = R->acc_uses[0][l]++;
-        KWS_TRY(acc_make_clean(R, s));
-        R->acc_dirty = true;               // until every kernel of this pass is enqueued
-    }
     auto acc_in = [&](int l) {             // the consumer's view of layer l's statistics
         return BnAccFwd{acc_set(R, 0, l, fpar[l]), acc_set(R, 0, l, fpar[l] + 1), (long)B * Hz[l] * Wz[l], params + m->o_g[l], params + m->o_b[l],
                         state + m->o_mm[l], state + m->o_mv[l], coef_of(w.coef[l], kCh[l + 1])};
@@ -617,7 +630,9 @@ int cnn_forward(const kws_model *m, const float *feat, int B, const float *param
             const unsigned nblk = (unsigned)std::min(B, kMaxStatBlocks);
             const size_t sm = std::max(sizeof(float) * (size_t)(Hs[1] + 2) * (Ws[1] + 2) * 20, sizeof(double) * 4 * 2 * 32);
             const size_t smb = std::max((size_t)6 * 16 * (((Hs[1] + 2) * (Ws[1] + 2) + 15) & ~15), sizeof(double) * 4 * 2 * 16);
-            if (training && bf16) {
+            if (l1_conv2) {
+                fused_stat_blocks = (int)nblk;     // ran inside the layer-1 launch above
+            } else if (training && bf16) {
                 KWS_LAUNCH("conv_fwd_clip_bf16<16,32>", (conv_fwd_clip_bf16_kernel<true>), dim3(nblk), dim3(256), smb, s, in, kern, w.z[1], B, Hs[1],
                            Ws[1], w.partial, kStatStride, nullptr, nullptr, acc_fwd ? acc_set(R, 0, 1, fpar[1]) : nullptr);
                 fused_stat_blocks = (int)nblk;
