@@ -598,6 +598,66 @@ int kws_quantize_simple_cnn_lite(const kws_model *m, const float *params_host, c
 int kws_qmodel_create_lite(const kws_model *m, const kws_qsimple_cnn_lite *q, kws_qmodel **out);
 
 /* ------------------------------------------------------------------------
+ * int8 dynamic-range ("hybrid") quantization of simple_gru and simple_lstm: what the reference's
+ * tools/model_converter/custom_tflite_convert.py --post_training_quantize gives a recurrent model (Optimize.DEFAULT, no
+ * representative dataset, FLOAT inference type): int8 weights, the inputs of every matrix product quantized on the fly per row,
+ * int32 accumulation rescaled to fp32, gates, biases and the softmax in fp32.  No calibration.  A frozen snapshot of the weights.
+ * Scope: KWS_SIMPLE_GRU and KWS_SIMPLE_LSTM (48 units, one layer), feature_size F in 1..64 (the input product is one k-step),
+ * T = n_features in 1..KWS_QRNN_MAX_STEPS, 2 <= C <= KWS_QUANT_MAX_CLASSES; everything else is KWS_ERR_UNSUPPORTED.  A non-finite
+ * weight or bias is KWS_ERR_INVALID.  G = 3 gates (GRU: z, r, h) or 4 (LSTM: i, f, c, o), N = 48 G gate columns.
+ *
+ * Contract.
+ *   Weights: kernel (F, N), recurrent_kernel (48, N) and the head kernel (48, C), each per output column j, symmetric MAX_ABS in
+ *   double: a_j = max_k |w_kj|, s_j = a_j / 127, q = clamp(rint(w / s_j), -127, 127) (rint half to even), stored with s_j rounded
+ *   once to fp32; an all-zero column has codes 0 and s_j = 0.  Biases stay fp32: the GRU's (2, N) = b0 | b1, the LSTM's (N), the head's.
+ *   Dynamic rows: for every clip, each step's input x_t (F values), each step's recurrent input h_{t-1} (48 values, h_0 = 0) and the
+ *   final h_T are quantized as a row of their own: m = max|v|; m == 0: codes 0 and s = 0; otherwise, in fp32 with IEEE division,
+ *   inv = 127.f / m, code = clamp(rint(v * inv), -127, 127) (ties to even), s = m / 127.f.
+ *   Accumulators are exact int32 (|acc| <= 64 * 127^2 < 2^24, so (float)acc is exact).  Device arithmetic is fp32 with every
+ *   multiply and add rounded separately (no contraction), left to right as written:
+ *     X_j = ((float)acc_x * s_x) * sW_j,   H_j = ((float)acc_h * s_h) * sU_j
+ *     GRU (reset_after=True):  mx = X + b0,  mh = H + b1;  z = sg(mx_z + mh_z),  r = sg(mx_r + mh_r),  hh = mx_h + r * mh_h,
+ *                              h' = z * h + (1 - z) * hh                              (activation='linear': no tanh on hh)
+ *     LSTM:                    a = (X + H) + b;  i = sg(a_i), f = sg(a_f), g = th(a_c), o = sg(a_o);  c' = f * c + i * g,
+ *                              h' = o * th(c')
+ *     head:                    logit_c = ((float)acc * s_hT) * s_c + bias_c, then the fp32 softmax and arg-max of the other int8 heads
+ *                              (first maximum wins)
+ *   h and c are fp32 registers.  sg and th are the fp32 kernels' sigmoidf_ / tanh_fast_ (csrc/kws_gru.h: hardware exp2 and reciprocal,
+ *   each within a few ulp, absolute error below 1e-6): NOT bit-reproducible off the device.  A restatement that evaluates them in
+ *   float64 agrees with the device to that error per gate, and exactly where they saturate to 0 or 1; a requantized code may then
+ *   differ by one where v * inv lies within that error of a rounding tie.
+ * Divergences from TFLite: per-column weight scales; symmetric rows (TFLite's hybrid ops may quantize inputs asymmetrically); the fp32
+ * gate functions above.
+ * ---------------------------------------------------------------------- */
+#define KWS_QRNN_MAX_STEPS 128
+#define KWS_QRNN_MAX_FEATURES 64
+#define KWS_QRNN_UNITS 48
+enum { KWS_QUANT_DYNAMIC = 3 };
+
+/* The quantized simple_gru / simple_lstm on the HOST (Keras order, row-major, filled by kws_quantize_simple_rnn) */
+typedef struct kws_qsimple_rnn {
+    int32_t kind;                       /* KWS_SIMPLE_GRU / KWS_SIMPLE_LSTM */
+    int32_t num_classes;                /* C, 2..KWS_QUANT_MAX_CLASSES */
+    int32_t n_steps, feature_size;      /* T, F */
+    int32_t method;                     /* KWS_QUANT_DYNAMIC */
+    int32_t reserved;
+    int8_t kernel[KWS_QRNN_MAX_FEATURES * 4 * KWS_QRNN_UNITS];    /* (F, N): the first F N entries, row stride N */
+    int8_t recurrent_kernel[KWS_QRNN_UNITS * 4 * KWS_QRNN_UNITS]; /* (48, N): the first 48 N entries */
+    int8_t head_w[KWS_QRNN_UNITS * KWS_QUANT_MAX_CLASSES];       /* (48, C): the first 48 C entries, row stride C */
+    float kernel_scale[4 * KWS_QRNN_UNITS];                      /* sW_j, the first N */
+    float recurrent_scale[4 * KWS_QRNN_UNITS];                   /* sU_j, the first N */
+    float bias[2 * 4 * KWS_QRNN_UNITS];                          /* GRU: (2, N) = b0 | b1 (first 2N); LSTM: (N) (first N) */
+    float head_scale[KWS_QUANT_MAX_CLASSES], head_bias[KWS_QUANT_MAX_CLASSES];
+} kws_qsimple_rnn;
+
+/* Host only: params_host = the model's flat parameter buffer (kws_model_param_count floats, the layout of kws_model_tensor_info).
+ * Fills *q by the contract above (method = KWS_QUANT_DYNAMIC). */
+int kws_quantize_simple_rnn(const kws_model *m, const float *params_host, kws_qsimple_rnn *q);
+/* A quantized simple_gru / simple_lstm on the CURRENT device.  kws_qmodel_forward (ONE kernel from features (B, T, F) to logits,
+ * probabilities and arg-max, capturable), kws_qmodel_workspace_bytes (0) and kws_qmodel_destroy serve it as the CNN kinds. */
+int kws_qmodel_create_rnn(const kws_model *m, const kws_qsimple_rnn *q, kws_qmodel **out);
+
+/* ------------------------------------------------------------------------
  * Entropy (KL) calibration of the int8 models: what the reference's deployment recipe asks for
  * (inference/MNN/configs/quantizeConfig.json, "feature_quantize_method": "KL").  Modelled on MNN's KL method, itself TensorRT's 8-bit
  * entropy calibration; MNN's source being outside this project, the details below are this contract's own: zeros are not counted,

@@ -465,15 +465,25 @@ class KWSModel(object):
     def test_on_batch(self, x, y):
         return self.evaluate(x, y, batch_size=len(x))
 
-    def quantize(self, x_calib, method='max', batch_size=None):
+    def quantize(self, x_calib=None, method=None, batch_size=None):
         """int8 post-training quantization of a simple_cnn or simple_cnn_lite (what the reference's users do with the MNN quantizer or
         custom_tflite_convert.py --post_training_quantize before deploying): calibrates the quantized tensors (six for simple_cnn,
         ten for simple_cnn_lite) on x_calib (features or raw audio, as predict takes) with the fp32 forward on the GPU, quantizes the
-        CURRENT weights (kws_amd.quant, include/kws.h) with method 'max', 'relu6' or 'kl' and returns a QuantizedKWSModel (predict /
-        evaluate / save).  'kl' (the reference's MNN recipe) makes a second pass over x_calib that histograms the tensors against the
-        maxima of the first and takes the ranges of least KL divergence.  A snapshot: it does not follow later training."""
+        CURRENT weights (kws_amd.quant, include/kws.h) with method 'max' (the default), 'relu6' or 'kl' and returns a QuantizedKWSModel
+        (predict / evaluate / save).  'kl' (the reference's MNN recipe) makes a second pass over x_calib that histograms the tensors
+        against the maxima of the first and takes the ranges of least KL divergence.  simple_gru / simple_lstm: dynamic-range int8
+        (method 'dynamic', their only one and their default; kws_amd.quant.QuantizedRNN), which reads no calibration data (x_calib may
+        be None).  A snapshot: it does not follow later training."""
         import torch
-        from kws_amd.quant import QuantizedCNN, QuantizedCNNLite, calibrate, histograms
+        from kws_amd.quant import QuantizedCNN, QuantizedCNNLite, QuantizedRNN, calibrate, histograms
+        if self.model_type in ('simple_gru', 'simple_lstm'):
+            if method not in (None, 'dynamic'):
+                raise ValueError("simple_gru / simple_lstm quantize with method 'dynamic' (dynamic-range int8) only, not %r" % (method,))
+            return QuantizedKWSModel(self, QuantizedRNN.from_model(self._device()))
+        if method is None:
+            method = 'max'
+        if x_calib is None:
+            raise ValueError("quantizing %s needs calibration samples" % self.model_type)
         if method not in _l.QUANT_SNAPSHOT_METHODS:
             raise ValueError("method must be one of %s" % sorted(_l.QUANT_SNAPSHOT_METHODS))
         cls, n = (QuantizedCNNLite, _l.QLITE_TENSORS) if self.model_type == 'simple_cnn_lite' else (QuantizedCNN, _l.QUANT_TENSORS)

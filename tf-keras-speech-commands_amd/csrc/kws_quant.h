@@ -103,11 +103,17 @@ struct kws_qmodel {
     const int8_t *pw1 = nullptr;
     const kws::q8::i32x4 *fp[4] = {nullptr, nullptr, nullptr, nullptr};
     const int32_t *bq = nullptr;          // kLBqCount
+    // simple_gru / simple_lstm (kws_quant_rnn.hip): T steps of F features; fragments of kernel and recurrent_kernel (fh: the head, ep:
+    // the column scales and biases)
+    int T = 0, F = 0;
+    const kws::q8::i32x4 *rw = nullptr, *ru = nullptr;
 };
 
 namespace kws {
 namespace q8 {
 int lite_qforward(const kws_qmodel *q, const float *feat, int B, float *logits, float *probs, int32_t *argmax, hipStream_t s);
+// the dynamic-range int8 simple_gru / simple_lstm forward (kws_quant_rnn.hip)
+int rnn_qforward(const kws_qmodel *q, const float *feat, int B, float *logits, float *probs, int32_t *argmax, hipStream_t s);
 // kws_model_calibrate_hist for simple_cnn_lite (kws_quant_lite.hip)
 int lite_calibrate_hist(const kws_model *m, const float *feat, int B, const float *params, const float *state, const float *amax_host,
                         uint64_t *hist, hipStream_t s);

@@ -777,6 +777,8 @@ int kws_qmodel_forward(const kws_qmodel *q, const float *feat, int B, void *ws, 
     if (B == 0) return KWS_OK;
     if (!feat) return fail(KWS_ERR_INVALID, "null features");
     if (q->kind == KWS_SIMPLE_CNN_LITE) return lite_qforward(q, feat, B, logits, probs, argmax, static_cast<hipStream_t>(stream));
+    if (q->kind == KWS_SIMPLE_GRU || q->kind == KWS_SIMPLE_LSTM)
+        return rnn_qforward(q, feat, B, logits, probs, argmax, static_cast<hipStream_t>(stream));
     int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(qforward_kernel), kLds);
     if (rc) return rc;
     QFwdArgs a{feat, B, q->C, q->inv_s0, q->w1, q->f2, q->f3, q->f4, q->fd, q->fh, q->ep, logits, probs, argmax};

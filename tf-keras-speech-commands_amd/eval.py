@@ -37,13 +37,20 @@ def evaluate_accuracy(model, x, y, class_names, batch_size=4096):
     return (float(np.trace(cm)) / total if total else 0.0), cm
 
 
+RNN_TYPES = ('simple_gru', 'simple_lstm')
+
+
 def evaluate_int8(model, x, y, class_names, x_calib, calib_samples=1000, method='max', batch_size=4096, seed=0):
     """int8 post-training quantization (KWSModel.quantize) calibrated on `calib_samples` clips of x_calib drawn without replacement
-    (seeded), then scored on (x, y) -> (quantized model, int8 accuracy, fp32 / int8 arg-max agreement, int8 confusion matrix)"""
+    (seeded), then scored on (x, y) -> (quantized model, int8 accuracy, fp32 / int8 arg-max agreement, int8 confusion matrix).
+    x_calib None: the dynamic-range int8 of simple_gru / simple_lstm, which takes no calibration."""
     import torch
-    n_cal = min(int(calib_samples), len(x_calib))
-    idx = np.sort(np.random.default_rng(seed).choice(len(x_calib), n_cal, replace=False))
-    qmodel = model.quantize(np.asarray(x_calib)[idx], method=method, batch_size=batch_size)
+    if x_calib is None:
+        qmodel = model.quantize(None, method=method, batch_size=batch_size)
+    else:
+        n_cal = min(int(calib_samples), len(x_calib))
+        idx = np.sort(np.random.default_rng(seed).choice(len(x_calib), n_cal, replace=False))
+        qmodel = model.quantize(np.asarray(x_calib)[idx], method=method, batch_size=batch_size)
     dm = model._device()
     xd, is_audio = model._to_device_inputs(x)
     yd = model._labels(y, xd.shape[0])
@@ -80,14 +87,20 @@ def main():
     parser.add_argument('--params_path', type=str, default=None)
     parser.add_argument('--batch_size', type=int, default=4096)
     parser.add_argument('--int8', default=False, action='store_true',
-                        help='also quantize the model to int8 (post-training, simple_cnn / simple_cnn_lite) and report its accuracy and agreement')
+                        help='also quantize the model to int8 (post-training; dynamic-range for simple_gru / simple_lstm) and report its '
+                             'accuracy and agreement')
     parser.add_argument('--calib_path', type=str, default=None, help='dataset to calibrate the int8 ranges on (default: the evaluated set)')
     parser.add_argument('--calib_samples', type=int, default=1000, help='calibration clips, drawn with a fixed seed')
-    parser.add_argument('--quant_method', type=str, default='max', choices=['max', 'relu6', 'kl'],
-                        help="activation ranges: calibrated maxima ('max'), 6 for every ReLU6 tensor ('relu6'), or the ranges of least KL "
-                             "divergence of a second, histogram pass ('kl', the reference's MNN recipe)")
+    parser.add_argument('--quant_method', type=str, default=None, choices=['max', 'relu6', 'kl', 'dynamic'],
+                        help="simple_cnn / simple_cnn_lite activation ranges: calibrated maxima ('max', the default), 6 for every ReLU6 "
+                             "tensor ('relu6'), or the ranges of least KL divergence of a second, histogram pass ('kl', the reference's MNN "
+                             "recipe); simple_gru / simple_lstm: 'dynamic' (dynamic-range int8, no calibration: their only method)")
     parser.add_argument('--save_quantized', type=str, default=None, help='write the int8 model to this .npz')
     args = parser.parse_args()
+    rnn = args.model_type in RNN_TYPES
+    if args.int8 and args.quant_method is not None and (args.quant_method == 'dynamic') != rnn:
+        parser.error("--quant_method %s does not apply to %s: simple_gru / simple_lstm take 'dynamic' only, the CNNs max, relu6 or kl"
+                     % (args.quant_method, args.model_type))
     class_names = get_classes(args.classes_path)
     assert class_names[0] == 'background', '1st class should be background.'
     if args.params_path:
@@ -97,11 +110,17 @@ def main():
     acc, cm = evaluate_accuracy(model, x, y, class_names, args.batch_size)
     print('%d correct out of %d samples, accuracy %.4f' % (int(np.trace(cm)), int(cm.sum()), acc))
     print_confusion_matrix(cm, class_names)
-    if args.int8:
+    if args.int8 and rnn:
+        # dynamic-range int8: no calibration, so --calib_path / --calib_samples are not read
+        qmodel, acc8, agree, cm8 = evaluate_int8(model, x, y, class_names, None, method='dynamic', batch_size=args.batch_size)
+        print('int8 (dynamic range): %d correct out of %d samples, accuracy %.4f' % (int(np.trace(cm8)), int(cm8.sum()), acc8))
+    elif args.int8:
+        method = args.quant_method or 'max'
         x_calib = x if not args.calib_path else get_dataset(args.calib_path, class_names)[0]
-        qmodel, acc8, agree, cm8 = evaluate_int8(model, x, y, class_names, x_calib, args.calib_samples, args.quant_method, args.batch_size)
+        qmodel, acc8, agree, cm8 = evaluate_int8(model, x, y, class_names, x_calib, args.calib_samples, method, args.batch_size)
         print('int8 (%s calibration, %d clips): %d correct out of %d samples, accuracy %.4f'
-              % (args.quant_method, min(args.calib_samples, len(x_calib)), int(np.trace(cm8)), int(cm8.sum()), acc8))
+              % (method, min(args.calib_samples, len(x_calib)), int(np.trace(cm8)), int(cm8.sum()), acc8))
+    if args.int8:
         print('fp32 / int8 argmax agreement %.4f' % agree)
         print_confusion_matrix(cm8, class_names)
         if args.save_quantized:

@@ -120,6 +120,22 @@ class KwsQSimpleCnnLite(ctypes.Structure):
                 ("Mh", ctypes.c_float * QUANT_MAX_CLASSES), ("head_bias", ctypes.c_float * QUANT_MAX_CLASSES)]
 
 
+QUANT_DYNAMIC = 3               # the dynamic-range int8 of simple_gru / simple_lstm (no calibration)
+QRNN_MAX_STEPS, QRNN_MAX_FEATURES, QRNN_UNITS = 128, 64, 48
+
+
+class KwsQSimpleRnn(ctypes.Structure):
+    """kws_qsimple_rnn: the dynamic-range int8 simple_gru / simple_lstm on the host (include/kws.h)"""
+    _fields_ = [("kind", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("feature_size", ctypes.c_int32),
+                ("method", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("kernel", ctypes.c_int8 * (QRNN_MAX_FEATURES * 4 * QRNN_UNITS)),
+                ("recurrent_kernel", ctypes.c_int8 * (QRNN_UNITS * 4 * QRNN_UNITS)),
+                ("head_w", ctypes.c_int8 * (QRNN_UNITS * QUANT_MAX_CLASSES)),
+                ("kernel_scale", ctypes.c_float * (4 * QRNN_UNITS)), ("recurrent_scale", ctypes.c_float * (4 * QRNN_UNITS)),
+                ("bias", ctypes.c_float * (8 * QRNN_UNITS)),
+                ("head_scale", ctypes.c_float * QUANT_MAX_CLASSES), ("head_bias", ctypes.c_float * QUANT_MAX_CLASSES)]
+
+
 MODEL_KINDS = {"simple_cnn": 0, "simple_cnn_lite": 1, "simple_gru": 2, "simple_lstm": 3}
 BANK_MEL, BANK_BARK = 0, 1
 WAV_F32, WAV_I16 = 0, 1
@@ -250,6 +266,8 @@ def get_lib():
     L.kws_qmodel_create_lite.argtypes = [vp, ctypes.POINTER(KwsQSimpleCnnLite), ctypes.POINTER(vp)]
     L.kws_model_calibrate_hist.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]
     L.kws_quant_kl_ranges.argtypes = [vp, vp, i32, vp, vp]
+    L.kws_quantize_simple_rnn.argtypes = [vp, vp, ctypes.POINTER(KwsQSimpleRnn)]
+    L.kws_qmodel_create_rnn.argtypes = [vp, ctypes.POINTER(KwsQSimpleRnn), ctypes.POINTER(vp)]
     _lib = L
     return L
 

@@ -16,7 +16,11 @@ the same clips, then the KL search on the host:
     q = QuantizedCNN.from_model_histograms(dm, amax, hist)    # ranges kl_ranges(hist, amax); q.method == "kl"
 
 simple_cnn_lite: calibrate() returns its ten maxima (x and the depthwise outputs u1..u4 beside the activations) and QuantizedCNNLite
-takes the place of QuantizedCNN, with the same interface.  A quantized model is a frozen snapshot of the weights it was made from."""
+takes the place of QuantizedCNN, with the same interface.  A quantized model is a frozen snapshot of the weights it was made from.
+
+simple_gru / simple_lstm: dynamic-range int8 (custom_tflite_convert.py --post_training_quantize), no calibration:
+
+    q = QuantizedRNN.from_model(dm)                       # q.method == "dynamic"; forward / save / load as above"""
 import ctypes
 
 import numpy as np
@@ -289,21 +293,103 @@ class QuantizedCNNLite(QuantizedCNN):
     _SHAPES, _EPILOGUE, _FORMAT = _LITE_SHAPES, _LITE_EPILOGUE, _LITE_FORMAT
 
 
-_CLASSES = {"simple_cnn": QuantizedCNN, "simple_cnn_lite": QuantizedCNNLite}
+_RNN_FORMATS = {"simple_gru": "kws_int8_simple_gru/1", "simple_lstm": "kws_int8_simple_lstm/1"}
+_RNN_GATES = {"simple_gru": 3, "simple_lstm": 4}
+
+
+class QuantizedRNN(QuantizedCNN):
+    """A dynamic-range int8 simple_gru / simple_lstm on the current HIP device (kws_quantize_simple_rnn, kws_qmodel_create_rnn): int8
+    weights, every matrix input quantized per row on the fly, fp32 gates -- what custom_tflite_convert.py --post_training_quantize gives
+    the reference's recurrent models.  No calibration: from_weights / from_model take the float parameters alone, and method is always
+    "dynamic".  forward, arrays, save, load and close as QuantizedCNN's; the .npz formats are kws_int8_simple_gru/1 and
+    kws_int8_simple_lstm/1."""
+    _STRUCT = _l.KwsQSimpleRnn
+    _CREATE = "kws_qmodel_create_rnn"
+    _FORMAT = None
+    _FORMATS = tuple(_RNN_FORMATS.values())
+
+    @classmethod
+    def from_weights(cls, spec, params, method="dynamic"):
+        """Host only: quantize the flat float32 params buffer of a simple_gru / simple_lstm ModelSpec (the layout of spec.tensors)"""
+        if method != "dynamic":
+            raise ValueError("simple_gru / simple_lstm quantize with method 'dynamic' (dynamic-range int8) only, not %r" % (method,))
+        p = np.ascontiguousarray(np.asarray(params, np.float32).reshape(-1))
+        if p.size < spec.param_count:
+            raise ValueError("params are shorter than the model's %d floats" % spec.param_count)
+        q = cls._STRUCT()
+        _l.check(_l.get_lib().kws_quantize_simple_rnn(spec.handle, p.ctypes.data, ctypes.byref(q)))
+        return cls(spec, q)
+
+    @classmethod
+    def from_model(cls, dm, method="dynamic"):
+        """Quantize the CURRENT weights of a simple_gru / simple_lstm DeviceModel (see from_weights)"""
+        return cls.from_weights(dm.spec, dm.params.cpu().numpy(), method)
+
+    @classmethod
+    def from_histograms(cls, *args, **kwargs):
+        raise ValueError("dynamic-range int8 quantization takes no calibration")
+
+    @classmethod
+    def from_model_histograms(cls, *args, **kwargs):
+        raise ValueError("dynamic-range int8 quantization takes no calibration")
+
+    @property
+    def method(self):
+        return "dynamic"
+
+    @property
+    def arrays(self):
+        """numpy views of the host copy: the int8 kernel (F, N), recurrent_kernel (48, N) and head_w (48, C), their fp32 column scales
+        kernel_scale, recurrent_scale, head_scale, and the fp32 biases (the GRU's (2, N), the LSTM's (N,), head_bias (C,))"""
+        q, C = self._q, self.spec.num_classes
+        G, F = _RNN_GATES[self.spec.model_type], self.spec.feature_size
+        N, U = G * _l.QRNN_UNITS, _l.QRNN_UNITS
+        a = lambda n: np.ctypeslib.as_array(getattr(q, n))
+        return {"kernel": a("kernel")[:F * N].reshape(F, N), "recurrent_kernel": a("recurrent_kernel")[:U * N].reshape(U, N),
+                "head_w": a("head_w")[:U * C].reshape(U, C), "kernel_scale": a("kernel_scale")[:N],
+                "recurrent_scale": a("recurrent_scale")[:N], "bias": a("bias")[:2 * N].reshape(2, N) if G == 3 else a("bias")[:N],
+                "head_scale": a("head_scale")[:C], "head_bias": a("head_bias")[:C]}
+
+    def save(self, path):
+        """.npz: the arrays above plus the model's geometry; load() rebuilds the model from them"""
+        arrays = {k: np.asarray(v) for k, v in self.arrays.items()}
+        arrays["__meta__"] = np.array([_RNN_FORMATS[self.spec.model_type], self.spec.model_type, str(self.spec.num_classes),
+                                       str(self.spec.n_features), str(self.spec.feature_size), self.method])
+        np.savez(path, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        """a QuantizedRNN from a file save() wrote (bit-identical arrays)"""
+        from .model import ModelSpec
+        z = np.load(path, allow_pickle=False)
+        meta = [str(v) for v in z["__meta__"]]
+        if meta[0] not in cls._FORMATS or _RNN_FORMATS.get(meta[1]) != meta[0] or meta[5] != "dynamic":
+            raise ValueError("%s is not a quantized simple_gru / simple_lstm checkpoint" % path)
+        spec = ModelSpec(meta[1], int(meta[2]), int(meta[3]), int(meta[4]))
+        q = cls._STRUCT()
+        q.kind, q.num_classes = _l.MODEL_KINDS[meta[1]], spec.num_classes
+        q.n_steps, q.feature_size, q.method = spec.n_features, spec.feature_size, _l.QUANT_DYNAMIC
+        out = cls(spec, q)
+        for k, v in out.arrays.items():
+            v[...] = z[k]
+        return out
+
+
+_CLASSES = {"simple_cnn": QuantizedCNN, "simple_cnn_lite": QuantizedCNNLite, "simple_gru": QuantizedRNN, "simple_lstm": QuantizedRNN}
 
 
 def quantized_class(model_type):
     """the quantized class of a model type (ValueError for the types int8 does not cover)"""
     if model_type not in _CLASSES:
-        raise ValueError("int8 quantization covers %s, not %s" % (" and ".join(sorted(_CLASSES)), model_type))
+        raise ValueError("int8 quantization covers %s, not %s" % (", ".join(sorted(_CLASSES)), model_type))
     return _CLASSES[model_type]
 
 
 def load(path):
-    """a QuantizedCNN or QuantizedCNNLite from a file save() wrote, chosen by the file's format"""
+    """a QuantizedCNN, QuantizedCNNLite or QuantizedRNN from a file save() wrote, chosen by the file's format"""
     with np.load(path, allow_pickle=False) as z:
         fmt = str(z["__meta__"][0])
     for cls in _CLASSES.values():
-        if fmt == cls._FORMAT:
+        if fmt == cls._FORMAT or fmt in getattr(cls, "_FORMATS", ()):
             return cls.load(path)
     raise ValueError("%s is not a quantized model checkpoint (format %r)" % (path, fmt))

@@ -10,6 +10,9 @@ from a separate `rocprofv3 --kernel-trace --stats` run of `--kernel-only`.  Prin
 KWS_INFER_FP32 / KWS_INFER_FP16, weight tables prepared) and the three graph-captured featurize + forward sessions, at B = 4096 and
 16 384 (--batches).
 
+--model simple_gru / simple_lstm: the dynamic-range int8 forward (kws_qmodel_forward on a kws_qmodel_create_rnn handle) against the fp32
+recurrent forward + head (kws_model_forward), and the two graph-captured featurize + forward sessions, at B = 2048 and 16 384.
+
 --calib kl: the calibration passes of the KL method for both models at B = 4096 (--calib-batch): the max pass (kws_model_calibrate[_lite])
 and the histogram pass (kws_model_calibrate_hist) alternating within each round, then the KL search on the host (kws_quant_kl_ranges)
 over the histograms of that set.  With --kernel-only it only launches the two passes of both models."""
@@ -120,6 +123,72 @@ def lite_main(args):
     return out
 
 
+def rnn_floors(B, C, G, T=30, F=20):
+    """bytes (features in, probabilities and arg-max out), int8 matrix ops (the padded k-steps the kernel issues: K = 64 for x_t W and
+    h U, 3 G column tiles each, per step; the head's three tiles) and the VALU floor of the gate arithmetic (about 20 fp32 ops per
+    gate value and step, counted from the kernel's source) of one dynamic-range int8 forward"""
+    nbytes = B * (T * F * 4 + C * 4 + 4)
+    ops_m = 2 * B * (T * 2 * 64 * 48 * G + 64 * 48)
+    ops_v = B * T * 48 * G * 20
+    return {"bytes": int(nbytes), "int8_matrix_ops": int(ops_m), "valu_ops": int(ops_v),
+            "hbm_floor_ms": round(nbytes / (HBM_GBS * 1e6), 5), "matrix_floor_ms": round(ops_m / (I8_TOPS * 1e9), 5),
+            "valu_floor_ms": round(ops_v / (VALU_TOPS * 1e9), 5)}
+
+
+def rnn_main(args):
+    """--model simple_gru / simple_lstm: the fp32 recurrent forward + head (kws_model_forward) against the dynamic-range int8 kernel,
+    and the two graph-captured featurize + forward sessions, alternating within each round"""
+    from classifier.params import pr
+    from kws_amd.featurizer import Featurizer
+    from kws_amd.inference import InferenceSession
+    from kws_amd.init import init_weights
+    from kws_amd.model import DeviceModel, ModelSpec
+    from kws_amd.quant import QuantizedRNN
+    torch.manual_seed(0)
+    C, G = 36, 3 if args.model == "simple_gru" else 4
+    spec = ModelSpec(args.model, C, pr.n_features, pr.feature_size)
+    dm = DeviceModel(spec)
+    dm.set_weights(init_weights(spec, seed=0))
+    q = QuantizedRNN.from_model(dm)
+    fz = Featurizer(pr)
+    out = {"model": args.model, "C": C, "runs": []}
+    for B in args.batches:
+        feat = (3.0 * torch.randn((B, pr.n_features, pr.feature_size), device="cuda")).contiguous()
+        ws = dm.new_workspace(B)
+        dm.prepare_inference(B, workspace=ws)
+        probs = torch.empty((B, C), device="cuda")
+        am = torch.empty((B,), dtype=torch.int32, device="cuda")
+        fwd = {"fp32": lambda: dm.forward(feat, workspace=ws), "int8": lambda: q._launch(feat, B, None, probs, am)}
+        if args.kernel_only:
+            for _ in range(args.iters):
+                for f in fwd.values():
+                    f()
+            torch.cuda.synchronize()
+            out["runs"].append({"B": B, "kernel_only": True, "launches": len(fwd) * args.iters})
+            continue
+        sess = {"fp32": InferenceSession(dm, fz, B, wav_dtype=torch.int16),
+                "int8": InferenceSession(dm, fz, B, wav_dtype=torch.int16, quantized=q)}
+        pcm = torch.randint(-3000, 3000, (B, pr.max_samples), dtype=torch.int16, device="cuda")
+        for s in sess.values():
+            s.wav.copy_(pcm)
+        res = {"B": B, "int8_floors": rnn_floors(B, C, G, pr.n_features, pr.feature_size), "forward": {}, "featurize_forward_graph": {}}
+        ft = {n: [] for n in fwd}
+        gt = {n: [] for n in sess}
+        for _ in range(args.rounds):
+            for n, f in fwd.items():
+                ft[n].append(time_ms(f, args.iters))
+            for n, s in sess.items():
+                gt[n].append(time_ms(s.run, args.iters))
+        for n in fwd:
+            res["forward"][n] = {"median_ms": round(float(np.median(ft[n])), 4), "rounds": [round(x, 4) for x in ft[n]]}
+            res["featurize_forward_graph"][n] = {"median_ms": round(float(np.median(gt[n])), 4), "rounds": [round(x, 4) for x in gt[n]]}
+        res["fp32_int8_argmax_agreement_random_weights"] = round(float((sess["fp32"].argmax == sess["int8"].argmax).float().mean().item()), 4)
+        out["runs"].append(res)
+        del sess, ws
+    out["device"] = torch.cuda.get_device_name(0)
+    return out
+
+
 def calib_main(args):
     """--calib kl: max pass, histogram pass and host KL search for simple_cnn and simple_cnn_lite"""
     import time
@@ -182,13 +251,17 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--kernel-only", action="store_true", help="only launch the two forwards (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--model", default="simple_cnn", choices=["simple_cnn", "simple_cnn_lite"])
-    ap.add_argument("--batches", type=int, nargs="+", default=[4096, 16384], help="simple_cnn_lite: the batch sizes")
+    ap.add_argument("--model", default="simple_cnn", choices=["simple_cnn", "simple_cnn_lite", "simple_gru", "simple_lstm"])
+    ap.add_argument("--batches", type=int, nargs="+", default=None,
+                    help="simple_cnn_lite (default 4096 16384), simple_gru / simple_lstm (default 2048 16384): the batch sizes")
     ap.add_argument("--calib", default=None, choices=["kl"], help="time the calibration passes of the KL method instead of the forwards")
     ap.add_argument("--calib-batch", type=int, default=4096)
     args = ap.parse_args()
-    if args.calib or args.model == "simple_cnn_lite":
-        res = calib_main(args) if args.calib else lite_main(args)
+    rnn = args.model in ("simple_gru", "simple_lstm")
+    if args.batches is None:
+        args.batches = [2048, 16384] if rnn else [4096, 16384]
+    if args.calib or args.model != "simple_cnn":
+        res = calib_main(args) if args.calib else rnn_main(args) if rnn else lite_main(args)
         line = json.dumps(res)
         print(line)
         if args.out:
