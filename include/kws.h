@@ -758,6 +758,66 @@ int kws_rmsprop_step(float *params, const float *grads, float *accum, int64_t n,
                      float grad_scale, void *stream);
 
 /* ------------------------------------------------------------------------
+ * The tf.keras optimizer_v2 options the three steps above do not take: gradient clipping (clipvalue, clipnorm,
+ * global_clipnorm) on all three, momentum / nesterov on SGD, momentum / centered on RMSprop, amsgrad on Adam.
+ * The buffers are flat; a segment table names the variables (for a model: one segment per trainable entry of
+ * kws_model_tensor_info, padded to the next one).  With g = grad_scale * grads, the gradient transformations run
+ * in Keras' _transform_gradients order:
+ *   clipvalue        g = clip(g, -clipvalue, clipvalue)
+ *   clipnorm         per segment, tf.clip_by_norm: g = g*c / max(||g||, c); a zero norm leaves g as it is, an inf norm
+ *                    makes the finite entries 0 and the inf ones NaN, a NaN norm makes the segment NaN
+ *   global_clipnorm  over all segments, tf.clip_by_global_norm: g *= c*min(1/N, 1/c); a non-finite N makes every entry NaN
+ * clipnorm and global_clipnorm are exclusive; a value of 0 is "off".  Then, t the 1-based step count:
+ *   sgd      momentum == 0: p -= lr g  (nesterov ignored);  else a = momentum a - lr g;  p += a  or, nesterov, p += momentum a - lr g
+ *   rmsprop  ms = rho ms + (1-rho) g^2;  centered: mg = rho mg + (1-rho) g, d = ms - mg^2, else d = ms;
+ *            momentum == 0: p -= lr g / (sqrt(d) + eps);  else mom = momentum mom + lr g / sqrt(d + eps); p -= mom
+ *            (eps inside the sqrt with momentum: ResourceApply[Centered]RMSProp)
+ *   adam     as kws_adam_step; amsgrad: vhat = max(vhat, v), p -= lr_t m / (sqrt(vhat) + eps)
+ * Launches: one when no norm clipping is asked for; else two -- per-block sums of squares of the value-clipped g
+ * (every block lies inside one segment), then the fused update, each of whose blocks sums the partials it needs in a
+ * fixed order.  No atomics, no host synchronisation: the same inputs give the same bits.
+ * Elements outside every segment are not touched.
+ * ---------------------------------------------------------------------- */
+enum { KWS_OPT_SGD = 0, KWS_OPT_RMSPROP = 1, KWS_OPT_ADAM = 2 };
+enum { KWS_OPT_NESTEROV = 1, KWS_OPT_CENTERED = 2, KWS_OPT_AMSGRAD = 4 };
+
+/* Host only.  Segment i is [offsets[i], offsets[i] + sizes[i]): sorted, not overlapping, offsets multiples of 4, sizes > 0.
+ * Returns the bytes of the optimizer workspace (a block table, then one double per block), or a negative kws error code. */
+int64_t kws_optimizer_workspace_bytes(const int64_t *offsets, const int64_t *sizes, int n_segments);
+/* Host only: writes the workspace's block table into host_ws (ws_bytes >= kws_optimizer_workspace_bytes) and its block count
+ * into *n_blocks.  Copy host_ws to the device once; the steps only read the table and use the rest as scratch. */
+int kws_optimizer_plan(const int64_t *offsets, const int64_t *sizes, int n_segments, void *host_ws, int64_t ws_bytes,
+                       int32_t *n_blocks);
+
+typedef struct kws_optimizer_args {
+    int32_t kind;           /* KWS_OPT_SGD / KWS_OPT_RMSPROP / KWS_OPT_ADAM */
+    int32_t flags;          /* KWS_OPT_NESTEROV (sgd), KWS_OPT_CENTERED (rmsprop), KWS_OPT_AMSGRAD (adam) */
+    float *params;
+    const float *grads;
+    float *m;               /* adam: first moment */
+    float *v;               /* adam: second moment; rmsprop: ms (the accum of kws_rmsprop_step) */
+    float *vhat;            /* adam with amsgrad */
+    float *mg;              /* centered rmsprop */
+    float *mom;             /* sgd / rmsprop with momentum > 0 */
+    void *ws;               /* device copy of the planned workspace, 16-byte aligned */
+    int64_t ws_bytes;
+    int32_t n_blocks;       /* from kws_optimizer_plan */
+    float lr;
+    float beta1;            /* adam */
+    float beta2;            /* adam beta_2; rmsprop rho */
+    float eps;              /* adam / rmsprop */
+    float momentum;         /* sgd / rmsprop, in [0, 1] */
+    int64_t t;              /* 1-based step count (adam) */
+    float grad_scale;
+    float clipvalue;        /* 0: off */
+    float clipnorm;         /* 0: off */
+    float global_clipnorm;  /* 0: off */
+} kws_optimizer_args;
+
+/* One update on `stream` by the rules above.  The buffers the kind / flags / momentum need are non-NULL and 16-byte aligned. */
+int kws_optimizer_step(const kws_optimizer_args *args, void *stream);
+
+/* ------------------------------------------------------------------------
  * Streaming post-processing: replaces the per-chunk work of listen.py for S
  * concurrent audio streams that advance in lockstep (one chunk each per step):
  *   Listener.update_vectors   listen.py:96-114   sliding feature matrix

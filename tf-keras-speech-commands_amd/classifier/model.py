@@ -206,7 +206,9 @@ class KWSModel(object):
     def _apply_optimizer(self, dm):
         opt = self.optimizer
         lr = opt.current_lr()
-        if opt.kind == 'adam':
+        if opt.extended:                # clipping / momentum / centered / amsgrad: kws_optimizer_step on the (exchanged) gradient
+            dm.optimizer_step(opt, lr)
+        elif opt.kind == 'adam':
             dm.adam_step(lr, opt.beta_1, opt.beta_2, opt.epsilon)
         elif opt.kind == 'rmsprop':
             dm.rmsprop_step(lr, opt.rho, opt.epsilon)

@@ -47,6 +47,19 @@ class KwsTrainArgs(ctypes.Structure):
                 ("comm_state_weight", ctypes.c_float), ("feat_moments", ctypes.c_void_p)]
 
 
+OPT_KINDS = {"sgd": 0, "rmsprop": 1, "adam": 2}                                          # include/kws.h KWS_OPT_*
+OPT_NESTEROV, OPT_CENTERED, OPT_AMSGRAD = 1, 2, 4
+
+
+class KwsOptimizerArgs(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("flags", ctypes.c_int32), ("params", ctypes.c_void_p), ("grads", ctypes.c_void_p),
+                ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("vhat", ctypes.c_void_p), ("mg", ctypes.c_void_p),
+                ("mom", ctypes.c_void_p), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64), ("n_blocks", ctypes.c_int32),
+                ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("momentum", ctypes.c_float), ("t", ctypes.c_int64), ("grad_scale", ctypes.c_float), ("clipvalue", ctypes.c_float),
+                ("clipnorm", ctypes.c_float), ("global_clipnorm", ctypes.c_float)]
+
+
 AUG_MAX_SNR = 16
 
 
@@ -203,6 +216,10 @@ def get_lib():
     L.kws_sgd_step.argtypes = [vp, vp, i64, f32, f32, vp]
     L.kws_rmsprop_step.argtypes = [vp, vp, vp, i64, f32, f32, f32, f32, vp]
     L.kws_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, f32, vp]
+    L.kws_optimizer_workspace_bytes.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64), i32]
+    L.kws_optimizer_workspace_bytes.restype = i64
+    L.kws_optimizer_plan.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64), i32, vp, i64, ctypes.POINTER(ctypes.c_int32)]
+    L.kws_optimizer_step.argtypes = [ctypes.POINTER(KwsOptimizerArgs), vp]
     f64 = ctypes.c_double
     L.kws_featurizer_occupancy.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_size_t)]
     L.kws_decoder_create.argtypes = [ctypes.POINTER(f64), i32, f64, i32, f64, f64, ctypes.POINTER(vp)]

@@ -49,6 +49,30 @@ class ModelSpec(object):
     def workspace_bytes(self, batch, training):
         return int(self._L.kws_model_workspace_bytes(self._h, int(batch), int(bool(training))))
 
+    def optimizer_segments(self):
+        """(offsets, sizes) int64 of the variables kws_optimizer_step clips by norm: one per trainable tensor, in params order, each
+        running up to the next one (the zero padding that keeps offsets at multiples of 4 floats), so that they tile [0, param_count)"""
+        tr = sorted((t for t in self.tensors if t["trainable"]), key=lambda t: t["offset"])
+        offsets = np.array([t["offset"] for t in tr], np.int64)
+        ends = np.append(offsets[1:], self.param_count).astype(np.int64)
+        sizes = ends - offsets
+        pads = sizes - np.array([t["size"] for t in tr], np.int64)
+        assert len(tr) > 0 and offsets[0] == 0 and (pads >= 0).all() and (pads < 4).all() and (offsets % 4 == 0).all(), \
+            "%s: the trainable tensors do not tile the parameter buffer" % self.model_type
+        return offsets, sizes
+
+    def optimizer_plan(self):
+        """host image of the kws_optimizer_step workspace (block table + scratch) and its block count (kws_optimizer_plan)"""
+        offsets, sizes = self.optimizer_segments()
+        po, ps = (a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) for a in (offsets, sizes))
+        nbytes = int(self._L.kws_optimizer_workspace_bytes(po, ps, len(offsets)))
+        if nbytes < 0:
+            _l.check(nbytes)
+        host = np.zeros((nbytes,), np.uint8)
+        nb = ctypes.c_int32()
+        _l.check(self._L.kws_optimizer_plan(po, ps, len(offsets), host.ctypes.data, nbytes, ctypes.byref(nb)))
+        return host, int(nb.value)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._L.kws_model_destroy(self._h)
@@ -104,6 +128,10 @@ class DeviceModel(object):
         self._matrix = self._infer = None      # per-model precision attributes (None: library default)
         self.weights_version = 0               # bumped whenever params / state may have changed (invalidate_prepared)
         self._ws = None
+        # optimizer_step: its extra slots (zeroed when first needed) and its workspace (block table uploaded once, then scratch)
+        self.opt_vhat = self.opt_mg = self.opt_mom = None
+        self._opt_ws = None
+        self._opt_blocks = 0
         self._ws_key = None
 
     # ---- weights ---------------------------------------------------------------------------------------------
@@ -299,3 +327,49 @@ class DeviceModel(object):
         _l.check(self._L.kws_rmsprop_step(self.params.data_ptr(), self.grads.data_ptr(), self.adam_v.data_ptr(),
                                           self.params.numel(), float(lr), float(rho), float(eps), float(grad_scale),
                                           torch.cuda.current_stream().cuda_stream))
+
+    def _opt_slot(self, name):
+        torch = _torch()
+        if getattr(self, name) is None:
+            setattr(self, name, torch.zeros_like(self.params))
+        return getattr(self, name).data_ptr()
+
+    def optimizer_step(self, opt, lr=None, grad_scale=1.0):
+        """One kws_optimizer_step by the common.model_utils optimizer `opt` (any options), at `lr` (default: opt.current_lr()).
+        Slots: Adam m / v in adam_m / adam_v, RMSprop's mean square in adam_v (as rmsprop_step), and opt_vhat (amsgrad),
+        opt_mg (centered), opt_mom (momentum).  Asynchronous on the current stream."""
+        torch = _torch()
+        if opt.kind not in _l.OPT_KINDS:
+            raise ValueError("unknown optimizer kind %r" % (opt.kind,))
+        if self._opt_ws is None:
+            host, self._opt_blocks = self.spec.optimizer_plan()
+            self._opt_ws = torch.from_numpy(host).to(self.device)
+        a = _l.KwsOptimizerArgs()
+        a.kind = _l.OPT_KINDS[opt.kind]
+        a.params, a.grads = self.params.data_ptr(), self.grads.data_ptr()
+        a.ws, a.ws_bytes, a.n_blocks = self._opt_ws.data_ptr(), self._opt_ws.numel(), self._opt_blocks
+        a.lr = float(opt.current_lr() if lr is None else lr)
+        a.grad_scale = float(grad_scale)
+        a.clipvalue, a.clipnorm, a.global_clipnorm = (float(x or 0.0) for x in (opt.clipvalue, opt.clipnorm, opt.global_clipnorm))
+        if opt.kind == 'adam':
+            a.m, a.v = self.adam_m.data_ptr(), self.adam_v.data_ptr()
+            a.beta1, a.beta2, a.eps = opt.beta_1, opt.beta_2, opt.epsilon
+            if opt.amsgrad:
+                a.flags |= _l.OPT_AMSGRAD
+                a.vhat = self._opt_slot("opt_vhat")
+        elif opt.kind == 'rmsprop':
+            a.v = self.adam_v.data_ptr()
+            a.beta2, a.eps, a.momentum = opt.rho, opt.epsilon, opt.momentum
+            if opt.centered:
+                a.flags |= _l.OPT_CENTERED
+                a.mg = self._opt_slot("opt_mg")
+        else:
+            a.momentum = opt.momentum
+            if opt.nesterov:
+                a.flags |= _l.OPT_NESTEROV
+        if opt.kind != 'adam' and opt.momentum > 0:
+            a.mom = self._opt_slot("opt_mom")
+        self.step_count += 1
+        a.t = self.step_count
+        self.invalidate_prepared()
+        _l.check(self._L.kws_optimizer_step(ctypes.byref(a), torch.cuda.current_stream().cuda_stream))

@@ -11,7 +11,9 @@ offline tool tools/audio_process/add_noise.py (--snr, --noised_rate) and an opti
 (a folder of room impulse responses) or --simulate_rirs N (N simulated rooms) reverberates a --reverb_rate share of the training clips
 before the noise, as tools/audio_process/audio_reverberation.py does offline; either works without --noise_path.  --filter_rate filters
 that share of the training clips at zero phase with a Butterworth design drawn from a bank of --num_filters random ones
-(--filter_types, --filter_order), after the room and before the noise, as tools/audio_process/wav_filter.py does offline."""
+(--filter_types, --filter_order), after the room and before the noise, as tools/audio_process/wav_filter.py does offline.
+The optimizer takes the Keras options the reference's command line leaves at their defaults: --clipnorm, --global_clipnorm and
+--clipvalue (any optimizer), --momentum (sgd, rmsprop), --nesterov (sgd), --centered (rmsprop) and --amsgrad (adam)."""
 import argparse
 import os
 import sys
@@ -52,6 +54,7 @@ def main(argv=None):
         raise SystemExit('--filter_rate needs --raw_audio (the waveforms are filtered before featurization)')
     if args.num_filters < 1:
         raise SystemExit('--num_filters needs a positive bank size')
+    opt_options = optimizer_options(args)
 
     # callbacks for training process
     logging = JsonlLogger(os.path.join(log_dir, 'train_log.jsonl'))
@@ -112,7 +115,8 @@ def main(argv=None):
         callbacks.remove(reduce_lr)
     steps_per_epoch = max(1, len(x_train) // args.batch_size)
     decay_steps = steps_per_epoch * args.epochs
-    optimizer = get_optimizer(args.optimizer, args.learning_rate, average_type=None, decay_type=args.decay_type, decay_steps=decay_steps)
+    optimizer = get_optimizer(args.optimizer, args.learning_rate, average_type=None, decay_type=args.decay_type, decay_steps=decay_steps,
+                              **opt_options)
 
     # prepare loss according to loss type
     if args.background_bias:
@@ -140,6 +144,25 @@ def main(argv=None):
     # Finally store model
     model.save(os.path.join(log_dir, 'trained_final.npz'))
     return history
+
+
+# the optimizer options beyond the reference's command line, and the optimizers they belong to
+OPTIMIZER_FLAGS = {'clipnorm': ('adam', 'rmsprop', 'sgd'), 'global_clipnorm': ('adam', 'rmsprop', 'sgd'),
+                   'clipvalue': ('adam', 'rmsprop', 'sgd'), 'momentum': ('rmsprop', 'sgd'), 'nesterov': ('sgd',),
+                   'centered': ('rmsprop',), 'amsgrad': ('adam',)}
+
+
+def optimizer_options(args):
+    """keyword arguments of get_optimizer for the optimizer flags given on the command line (none: the reference's optimizer)"""
+    kw = {}
+    for name, kinds in OPTIMIZER_FLAGS.items():
+        value = getattr(args, name)
+        if value is None or value is False:
+            continue
+        if args.optimizer not in kinds:
+            raise SystemExit('--%s is an option of %s, not of --optimizer %s' % (name, ' / '.join(kinds), args.optimizer))
+        kw[name] = value
+    return kw
 
 
 def parse_args(argv=None):
@@ -171,6 +194,17 @@ def parse_args(argv=None):
                         help="optimizer for training (adam/rmsprop/sgd), default=%(default)s")
     parser.add_argument('--learning_rate', type=float, required=False, default=1e-3,
                         help="Initial learning rate, default=%(default)s")
+    parser.add_argument('--clipnorm', type=float, required=False, default=None,
+                        help="clip each variable's gradient to this L2 norm (tf.clip_by_norm), default off")
+    parser.add_argument('--global_clipnorm', type=float, required=False, default=None,
+                        help="clip the gradient of all variables together to this L2 norm (tf.clip_by_global_norm), default off")
+    parser.add_argument('--clipvalue', type=float, required=False, default=None,
+                        help="clip every gradient entry to [-clipvalue, clipvalue], default off")
+    parser.add_argument('--momentum', type=float, required=False, default=None,
+                        help="momentum of sgd / rmsprop, in [0, 1], default 0")
+    parser.add_argument('--nesterov', action='store_true', help="Nesterov momentum (sgd)")
+    parser.add_argument('--centered', action='store_true', help="centered RMSprop (rmsprop)")
+    parser.add_argument('--amsgrad', action='store_true', help="the AMSGrad variant of Adam (adam)")
     parser.add_argument('--decay_type', type=str, required=False, default=None, choices=[None, 'cosine', 'exponential', 'polynomial', 'piecewise_constant'],
                         help="Learning rate decay type, default=%(default)s")
     parser.add_argument('--epochs', type=int, required=False, default=100,
