@@ -117,6 +117,20 @@ int kws_featurize_raw_frames(const kws_featurizer *f, int32_t n_samples);
 int kws_featurize_raw(kws_featurizer *f, const void *wav, int wav_dtype, int B, int64_t stride, int32_t n_samples,
                       float *feat, void *stream);
 
+/*
+ * vectorize_raw of R whole recordings of ragged length in one launch: row j of recording r is vectorize_raw of its samples
+ * [j hop, j hop + window), i.e. the row Listener.update_vectors (listen.py:96-114) appends once those samples have arrived.
+ *   wav     : (R, stride) samples of `wav_dtype`, recording r from its first sample
+ *   lengths : R DEVICE int32 sample counts (clamped to 0..stride)
+ *   rows    : (R, max_frames, n_mfcc); recording r has kws_featurize_raw_frames(f, lengths[r]) rows (at most max_frames are
+ *             written), the rows after them are written as zeros
+ * Work is cut into (recording, tile of frames) jobs, so one long recording fills the device and no length is refused: the
+ * default geometry runs the tuned kernel's own frame loop per tile (a row has the bits kws_featurize_raw gives the same samples);
+ * other geometries go through the clip kernels as overlapping segments (stream-ordered scratch of about the audio's size).
+ */
+int kws_featurize_long(kws_featurizer *f, const void *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths,
+                       int max_frames, float *rows, void *stream);
+
 /* How much of every compute unit one launch of the tuned (default-geometry) kernel may hold.  2 (default): two persistent blocks of
  * 8 waves per CU (4 waves per SIMD, 2 x 52 KB of LDS), fastest when the featurizer has the chip to itself (inference, dataset
  * featurization); 1: ONE block of 12 waves (75 KB of LDS), so that kernels of OTHER streams still find wave slots and LDS on every
@@ -858,6 +872,37 @@ int kws_trigger_update(const int32_t *index, const double *score, int S, int bac
 int kws_stream_postprocess(const kws_decoder *dec, const float *probs, int S, int C, int background_index,
                            double sensitivity, int trigger_level, int chunk_size, int32_t *state, int32_t *index,
                            double *score, int32_t *fired, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Offline scan: the loop above over whole recordings that already lie in memory, parallel over time.  It returns per
+ * chunk what the chunk loop returns.  With W = window_samples, H = hop_samples, c = chunk_size and N samples:
+ *   chunks  T = ceil(N / c); after chunk k (1-based) n_k = min(k c, N) samples have arrived (wave.readframes delivers a short
+ *           last chunk, listen.py:403-428);
+ *   rows    update_vectors (listen.py:96-114) featurizes the carried + new samples and keeps the remainder from
+ *           len(new) * hop on, so the carry always starts on a frame boundary: after chunk k there are
+ *           r_k = 0 if n_k < W else (n_k - W) / H + 1 rows, row j = vectorize_raw of samples [j H, j H + W)
+ *           (kws_featurize_long computes them all at once);
+ *   window  the matrix predicted on at chunk k is rows [r_k - F, r_k), zeros for negative indices (listen.py:92); chunks
+ *           before the first row see the all-zero matrix and are predicted on like any other (listen.py:350-375).
+ * ------------------------------------------------------------------------ */
+
+/* feat (R * n_chunks, F, D): window i of recording r (at r * n_chunks + i) is the matrix of its chunk k0 + i (0-based), cut
+ * from rows (R, max_frames, D); lengths: R device int32 sample counts.  Chunks at or past a recording's T give zeros. */
+int kws_stream_gather_windows(const float *rows, int R, int max_frames, const int32_t *lengths, int chunk_size,
+                              int window_samples, int hop_samples, int F, int D, int64_t k0, int n_chunks, float *feat,
+                              void *stream);
+
+/* kws_stream_postprocess for the chunks k0 .. k0 + n_chunks of R recordings at once: probs (R, n_chunks, C) float32 as the
+ * forward pass gives the windows above; rec_chunks: R device int32 chunk counts T.  index / score / fired: element
+ * (r, i) at r * out_stride + i (out_stride >= n_chunks: a tile may be written into a column range of a larger matrix).
+ * argmax / max / decode (listen.py:361-367) run per chunk in parallel; TriggerDetector.update (listen.py:538-559) is
+ * walked in chunk order per recording from state (R, 2) = {activation, record_index}, which is left as after the last
+ * chunk walked: calls on consecutive tiles equal kws_stream_postprocess chunk by chunk.  Chunks at or past T leave
+ * the recording's state alone and get index -1, score 0, fired 0. */
+int kws_stream_scan_postprocess(const kws_decoder *dec, const float *probs, int R, int n_chunks, int C,
+                                const int32_t *rec_chunks, int64_t k0, int background_index, double sensitivity,
+                                int trigger_level, int chunk_size, int32_t *state, int32_t *index, double *score,
+                                int32_t *fired, int64_t out_stride, void *stream);
 
 #ifdef __cplusplus
 }

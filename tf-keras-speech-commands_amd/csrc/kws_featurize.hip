@@ -608,6 +608,42 @@ static int build_bark_bank(int sample_rate, int n_fft, int n_filt, std::vector<d
     return KWS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// kws_featurize_long for the geometries the tuned kernel does not cover: the recordings are cut into segments of `tile` frames
+// ((tile - 1) hop + window samples, consecutive segments overlapping by window - hop), the segments go through the clip kernels
+// above as a batch of clips of exactly that length (vectorize_raw of each), and their rows are put in place.
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename WavT>
+__global__ __launch_bounds__(256) void long_segments_kernel(const WavT *__restrict__ wav, int64_t stride, const int32_t *__restrict__ lengths,
+                                                            int jpc, int64_t seg_step, int seg_len, int64_t total, WavT *__restrict__ seg)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t sg = i / seg_len;
+        const int o = (int)(i - sg * seg_len);
+        const int r = (int)(sg / jpc);
+        const int64_t p = (sg - (int64_t)r * jpc) * seg_step + o;              // sample of recording r; zeros past its end
+        int64_t len = lengths[r];
+        len = len > stride ? stride : len;
+        seg[i] = p < len ? wav[(int64_t)r * stride + p] : (WavT)0;
+    }
+}
+
+// rows (R, max_frames, D) from the segments' rows (R, jpc * tile, D); zeros past each recording's own frame count
+__global__ __launch_bounds__(256) void long_rows_kernel(const float *__restrict__ seg_rows, const int32_t *__restrict__ lengths, int64_t stride,
+                                                        int window, int hop, int max_frames, int64_t seg_frames, int D, int64_t total,
+                                                        float *__restrict__ rows)
+{
+    const int64_t per = (int64_t)max_frames * D;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int r = (int)(i / per);
+        const int64_t o = i - (int64_t)r * per;
+        int64_t len = lengths[r];
+        len = len > stride ? stride : len;
+        const int64_t nf = len < window ? 0 : (len - window) / hop + 1;
+        rows[i] = o < nf * D ? seg_rows[(int64_t)r * seg_frames * D + o] : 0.f;
+    }
+}
+
 }  // namespace kws
 
 using namespace kws;
@@ -625,17 +661,29 @@ static size_t v3_smem_bytes(int chp, int waves)
     return (size_t)waves * 4 * (kV3Tile + TB * 64 + 64 + 4) + 4 * (size_t)(kTunedBands * kTunedCoefs + 64 * chp) + 8 * (size_t)(7 * 64 + 7 * 8 + 4 * 64) +
            4 * (size_t)round4(kTunedBands + 1);
 }
-template <typename WavT, int CHP, int WAVES, bool AUG = false>
+// LONG (kws_featurize_long): B recordings of d.n_frames output rows each, valid_len = their sample counts (kws_featurize_v3.h)
+template <typename WavT, int CHP, int WAVES, bool AUG = false, bool LONG = false>
 static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name, int bpc,
                      const AugDev &aug = {})
 {
     const int cus = device_cus();
     const size_t smem = v3_smem_bytes(CHP, WAVES);
     if ((size_t)WAVES * 4 * kV3Tile > 65536) return fail(KWS_ERR_UNSUPPORTED, "wave tiles must sit in the first 64 KiB of LDS (M0 holds 16 address bits)");
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, AUG>), (int)smem)) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, AUG, LONG>), (int)smem)) return rc;
     FeatDev dd = d;
     const long waves = (long)bpc * cus * WAVES;
-    {
+    if constexpr (LONG) {
+        // a job is a tile of fpw rows of one recording: one round of jobs over the grid's waves when the audio allows it (a one-hour
+        // recording is 112 499 frames = 28 per wave of 256 CUs x 16 waves), whole tail batches, at least 4 of them so that a job's fixed
+        // part (half a frame of loads, the table reads) stays under a tenth of it, at most 32 so that ragged batches still balance
+        const int tb = std::max(1, dd.tail_batch);
+        const long total = (long)B * dd.n_frames;
+        long fpw = (total + waves - 1) / waves;
+        fpw = (fpw + tb - 1) / tb * tb;
+        fpw = std::min<long>(std::max<long>(fpw, 4 * tb), 32 * tb);
+        dd.fpw = (int)fpw;
+        dd.jpc = (dd.n_frames + dd.fpw - 1) / dd.fpw;
+    } else {
         // cost of a candidate = rounds of jobs per wave x (frames per job + the job's fixed part: one extra half frame of loads
         // and a partly filled tail batch); candidates: the tail batch size and up, preferring divisors of the frame count
         double best = -1.0;
@@ -647,8 +695,12 @@ static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, c
         }
     }
     const long jobs = (long)B * dd.jpc;
+    if (jobs > 0x7fffffffL) return fail(KWS_ERR_UNSUPPORTED, "%ld featurizer jobs exceed the kernel's 32-bit job index", jobs);
     const unsigned grid = (unsigned)std::min<long>((long)bpc * cus, (jobs + WAVES - 1) / WAVES);
-    if constexpr (AUG)
+    if constexpr (LONG)
+        KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, false, true>), dim3(grid), dim3(WAVES * 64), smem, s, wav,
+                   stride, valid_len, B, dd, feat);
+    else if constexpr (AUG)
         KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, true>), dim3(grid), dim3(WAVES * 64), smem, s, wav, stride,
                    valid_len, B, dd, feat, aug);
     else
@@ -663,25 +715,25 @@ static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, c
 #ifndef KWS_V3_ALONE_BLOCKS
 #define KWS_V3_ALONE_BLOCKS 2
 #endif
-template <typename WavT, int WAVES, bool AUG = false>
+template <typename WavT, int WAVES, bool AUG = false, bool LONG = false>
 static int launch_v3_chp(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name, int bpc,
                          const AugDev &aug = {})
 {
     switch (d.chp3) {
-    case 12: return launch_v3<WavT, 12, WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
-    case 16: return launch_v3<WavT, 16, WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
-    default: return launch_v3<WavT, 20, WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
+    case 12: return launch_v3<WavT, 12, WAVES, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
+    case 16: return launch_v3<WavT, 16, WAVES, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
+    default: return launch_v3<WavT, 20, WAVES, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, bpc, aug);
     }
 }
 // The kernel holds its per-lane twiddles in registers (110 registers: 4 waves per SIMD = 16 per CU).  With the chip to itself: two blocks of 8
 // waves per CU; beside a train step (kws_featurizer_set_cu_share(f, 1)): ONE block of 12 waves per CU, which leaves a quarter of the wave
 // slots and half of the LDS to the step's kernels.
-template <typename WavT, bool AUG = false>
+template <typename WavT, bool AUG = false, bool LONG = false>
 static int launch_v3_any(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name,
                          const AugDev &aug = {})
 {
-    if (d.blocks_per_cu == 1) return launch_v3_chp<WavT, kV3Waves, AUG>(d, wav, B, stride, valid_len, feat, s, name, 1, aug);
-    return launch_v3_chp<WavT, KWS_V3_ALONE_WAVES, AUG>(d, wav, B, stride, valid_len, feat, s, name, KWS_V3_ALONE_BLOCKS, aug);
+    if (d.blocks_per_cu == 1) return launch_v3_chp<WavT, kV3Waves, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, 1, aug);
+    return launch_v3_chp<WavT, KWS_V3_ALONE_WAVES, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, KWS_V3_ALONE_BLOCKS, aug);
 }
 
 extern "C" {
@@ -1145,6 +1197,79 @@ int kws_featurize_raw(kws_featurizer *f, const void *wav, int wav_dtype, int B, 
     d.feature_size = d.n_out;
     d.blocks_per_cu = f->blocks_per_cu;
     return launch_featurize(d, wav, wav_dtype, B, stride, nullptr, feat, stream);
+}
+
+extern "C++" {
+template <typename WavT>
+static int featurize_long_segments(const kws_featurizer *f, const WavT *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths,
+                                   int max_frames, float *rows, hipStream_t s)
+{
+    const int window = f->geom.window_samples, hop = f->geom.hop_samples, D = f->dev.n_out;
+    // frames per segment: what the generic kernel can stage in LDS beside its FFT tiles, 256 at the most
+    int tile = 256;
+    if (f->dev.n_fft != 1024) {
+        const size_t fixed = (size_t)kGenWaves * f->dev.n_fft * 8 + kGenWaves * 256;
+        tile = (int)std::min<size_t>(256, (kMaxLdsBytes - fixed) / (4 * (size_t)D) - 4);
+    }
+    tile = std::max(1, std::min(tile, max_frames));
+    const int jpc = (max_frames + tile - 1) / tile;
+    const int64_t seg_len = (int64_t)(tile - 1) * hop + window, n_seg = (int64_t)R * jpc;
+    if (n_seg > 0x7fffffffL || seg_len > 0x7fffffffL) return fail(KWS_ERR_UNSUPPORTED, "%lld segments of %lld samples", (long long)n_seg, (long long)seg_len);
+    const size_t seg_bytes = (sizeof(WavT) * (size_t)n_seg * seg_len + 255) & ~(size_t)255;
+    unsigned char *tmp = nullptr;
+    KWS_HIP_CHECK(hipMallocAsync(reinterpret_cast<void **>(&tmp), seg_bytes + sizeof(float) * (size_t)n_seg * tile * D, s));
+    WavT *seg = reinterpret_cast<WavT *>(tmp);
+    float *seg_rows = reinterpret_cast<float *>(tmp + seg_bytes);
+    const int64_t n_in = n_seg * seg_len, n_out = (int64_t)R * max_frames * D;
+    const int cap = 64 * device_cus();
+    KWS_LAUNCH("long_segments_kernel", long_segments_kernel<WavT>, dim3((unsigned)std::min<int64_t>(cap, (n_in + 255) / 256)), dim3(256), 0, s, wav, stride,
+               lengths, jpc, (int64_t)tile * hop, (int)seg_len, n_in, seg);
+    KWS_LAUNCH_CHECK("long_segments_kernel");
+    FeatDev d = f->dev;
+    d.n_frames = tile;
+    d.max_samples = (int)seg_len;
+    d.use_delta = 0;
+    d.feature_size = d.n_out;
+    d.blocks_per_cu = f->blocks_per_cu;
+    d.index = nullptr;
+    int rc = launch_featurize(d, seg, wav_dtype, (int)n_seg, seg_len, nullptr, seg_rows, s);
+    if (rc == KWS_OK) {
+        KWS_LAUNCH("long_rows_kernel", long_rows_kernel, dim3((unsigned)std::min<int64_t>(cap, (n_out + 255) / 256)), dim3(256), 0, s, seg_rows, lengths,
+                   stride, window, hop, max_frames, (int64_t)jpc * tile, D, n_out, rows);
+        KWS_LAUNCH_CHECK("long_rows_kernel");
+    }
+    KWS_HIP_CHECK(hipFreeAsync(tmp, s));
+    return rc;
+}
+}  // extern "C++"
+
+int kws_featurize_long(kws_featurizer *f, const void *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths, int max_frames,
+                       float *rows, void *stream)
+{
+    if (!f) return fail(KWS_ERR_INVALID, "null argument");
+    if (R < 0 || max_frames < 0 || stride < 0) return fail(KWS_ERR_INVALID, "negative R / max_frames / stride");
+    if (wav_dtype != KWS_WAV_F32 && wav_dtype != KWS_WAV_I16) return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
+    if (R == 0 || max_frames == 0) return KWS_OK;
+    if (!wav || !lengths || !rows) return fail(KWS_ERR_INVALID, "null argument");
+    // lengths are int32, so a recording has fewer than 2^31 / hop frames; the kernels index samples and row elements with 32 bits
+    if ((int64_t)max_frames * std::max(f->geom.hop_samples, f->dev.n_out) > 0x7fffffffL - f->geom.window_samples)
+        return fail(KWS_ERR_INVALID, "max_frames=%d is more than an int32 sample count can hold", max_frames);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FeatDev d = f->dev;
+    d.n_frames = max_frames;
+    d.use_delta = 0;
+    d.feature_size = d.n_out;
+    d.blocks_per_cu = f->blocks_per_cu;
+    d.index = nullptr;
+    feat_job_shape(d);
+    if (d.n_fft == 1024 && v3_applies(d)) {      // the default geometry: tiles of frames are the tuned kernel's own jobs
+        if (wav_dtype == KWS_WAV_F32)
+            return launch_v3_any<float, false, true>(d, static_cast<const float *>(wav), R, stride, lengths, rows, s, "featurize_long_f32");
+        return launch_v3_any<short, false, true>(d, static_cast<const short *>(wav), R, stride, lengths, rows, s, "featurize_long_i16");
+    }
+    if (wav_dtype == KWS_WAV_F32)
+        return featurize_long_segments(f, static_cast<const float *>(wav), wav_dtype, R, stride, lengths, max_frames, rows, s);
+    return featurize_long_segments(f, static_cast<const short *>(wav), wav_dtype, R, stride, lengths, max_frames, rows, s);
 }
 
 }  // extern "C"

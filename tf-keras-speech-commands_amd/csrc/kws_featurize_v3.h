@@ -239,7 +239,13 @@ __device__ __forceinline__ void aug_load_half(float2 (&v)[4], const WavT *__rest
 // WAVES: waves per block.  The per-lane twiddles (7 + 7 + 4 complex values that never change for a lane) live in 36 registers instead of
 // being re-read from LDS for every frame (18 ds_read_b64 = 39 LDS cycles per frame, in a kernel bound by the LDS pipe): 110 registers,
 // 4 waves per SIMD.
-template <typename WavT, int CHP, int NF, int NO, int WAVES = kV3Waves, bool AUG = false>
+//
+// LONG = true (kws_featurize_long): the B rows are whole recordings instead of clips.  valid_len[b] is recording b's sample count, its
+// frame j is samples [512 j, 512 j + 1024) with no padding on either side (vectorize_raw of that stretch), c.n_frames is the row
+// count of EVERY recording's output block and a job is a tile of c.fpw of those rows: the frames the recording has go through the same
+// frame loop -- same loads, same arithmetic, so a row has the bits kws_featurize_raw gives the same 1024 samples -- and the rows past
+// its last frame are written as zeros.  The LONG = false instantiations are the clip kernels, unchanged.
+template <typename WavT, int CHP, int NF, int NO, int WAVES = kV3Waves, bool AUG = false, bool LONG = false>
 __global__ __launch_bounds__(WAVES * 64, 4) void featurize_fft1024_v3_kernel(const WavT *__restrict__ wav, int64_t stride,
                                                                                   const int32_t *__restrict__ valid_len, int B,
                                                                                   FeatDev c, float *__restrict__ feat, AugDev aug = {})
@@ -300,6 +306,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void featurize_fft1024_v3_kernel(con
     const int bc = b;
     const int row = c.index ? c.index[bc] : bc;                            // kws_featurize_gather: clip bc is a row of the caller's dataset
     int len;
+    int nf = c.n_frames;                                                   // frames this row really has (LONG: from its own length)
     const float *nz = nullptr;
     int a_shift = 0;
     float a_gain = 0.f;
@@ -311,20 +318,31 @@ __global__ __launch_bounds__(WAVES * 64, 4) void featurize_fft1024_v3_kernel(con
         a_gain = r.gain;
         a_noised = r.apply != 0;
         nz = aug.bank + (a_noised ? aug.seg_start[r.segment] + r.offset : 0);
+    } else if constexpr (LONG) {
+        len = valid_len[row];
+        len = len < 0 ? 0 : len;
+        if ((int64_t)len > stride) len = (int)stride;
+        nf = len < 1024 ? 0 : (len - 1024) / 512 + 1;
+        if (nf > c.n_frames) nf = c.n_frames;
     } else {
         len = valid_len ? valid_len[row] : (stride > c.max_samples ? c.max_samples : (int)stride);
         len = len < 0 ? 0 : len;
         if ((int64_t)len > stride) len = (int)stride;
         if (len > c.max_samples) len = c.max_samples;
     }
-    const int pad = c.max_samples - len;
+    const int pad = LONG ? 0 : c.max_samples - len;
     const WavT *src = wav + (int64_t)row * stride;
     const bool vec_ok = ((pad & 1) == 0) && ((reinterpret_cast<uintptr_t>(src) & (2 * sizeof(WavT) - 1)) == 0);
 
     float *dst = feat + (int64_t)bc * c.n_frames * NO;
 
     const int f_beg = (job - b * c.jpc) * c.fpw;
-    const int f_end = f_beg + c.fpw < c.n_frames ? f_beg + c.fpw : c.n_frames;
+    int f_end = f_beg + c.fpw < c.n_frames ? f_beg + c.fpw : c.n_frames;
+    if constexpr (LONG) {                // rows [max(f_beg, nf), f_end) of the tile lie past the recording: zeros
+        const int z_beg = f_beg > nf ? f_beg : nf;
+        for (int i = z_beg * NO + lane; i < f_end * NO; i += 64) dst[i] = 0.f;
+        f_end = f_end < nf ? f_end : nf;
+    }
 
     float2 xl[4], xh[4];                // lower / upper half of the next frame to transform
     if (f_beg < f_end) {

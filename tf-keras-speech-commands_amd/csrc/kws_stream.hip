@@ -5,6 +5,10 @@
 //   TriggerDetector.update    listen.py:538-559   -> kws_trigger_update
 //   update_vectors (rows)     listen.py:107-109   -> kws_stream_push_rows
 //   the prediction loop       listen.py:361-375   -> kws_stream_postprocess (argmax + max + decode + trigger, one kernel)
+// and the time-parallel form of the same loop over whole recordings (kws_amd.stream.scan):
+//   update_vectors (windows)  listen.py:96-114    -> kws_stream_gather_windows (every chunk's feature matrix from the recording's rows)
+//   the prediction loop       listen.py:361-375   -> kws_stream_scan_postprocess (argmax / max / decode per chunk in parallel, then the
+//                                                    trigger walked in chunk order, one wave per recording)
 // Everything here is a few bytes per stream and one thread per stream: the kernels are latency-sized, the point of doing
 // them on the device is that probabilities, scores and detector state never leave HBM between the forward pass of one
 // chunk and the next (the whole step can sit in one hipGraph).  Arithmetic is float64 wherever the reference computes
@@ -94,6 +98,20 @@ __global__ __launch_bounds__(256) void trigger_kernel(const int32_t *__restrict_
     fired[s] = trigger_one(index[s], score[s], background, sensitivity, level, refractory, state + 2 * (long)s);
 }
 
+// listen.py:361-367 for one row of probabilities: first maximum (np.argmax), np.max, decode unless background
+__device__ __forceinline__ int argmax_decode(const float *__restrict__ p, int C, int background, const DecDev &d, double &score)
+{
+    float best = p[0];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+        const float v = p[c];
+        if (v > best) { best = v; arg = c; }
+    }
+    score = (double)best;
+    if (arg != background && d.enabled) score = decode_f32(best, d);
+    return arg;
+}
+
 // one thread per stream: first maximum (np.argmax), decode unless background, detector update
 __global__ __launch_bounds__(256) void postprocess_kernel(const float *__restrict__ probs, int S, int C, int background, DecDev d,
                                                            double sensitivity, int level, int refractory,
@@ -102,15 +120,8 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float *__restric
 {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
-    const float *p = probs + (long)s * C;
-    float best = p[0];
-    int arg = 0;
-    for (int c = 1; c < C; ++c) {
-        const float v = p[c];
-        if (v > best) { best = v; arg = c; }
-    }
-    double sc = (double)best;
-    if (arg != background && d.enabled) sc = decode_f32(best, d);
+    double sc;
+    const int arg = argmax_decode(probs + (long)s * C, C, background, d, sc);
     index[s] = arg;
     score[s] = sc;
     fired[s] = trigger_one(arg, sc, background, sensitivity, level, refractory, state + 2 * (long)s);
@@ -141,6 +152,85 @@ __global__ __launch_bounds__(256) void push_rows_kernel(float *__restrict__ feat
         }
         __syncthreads();
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Offline scan of whole recordings.  With W = window, H = hop, c = chunk_size and a recording of N samples, the chunk loop
+// (StreamBatch.push per chunk) has after its k-th chunk (1-based) n_k = min(k c, N) samples and -- its carry buffer always
+// starts on a frame boundary -- r_k = 0 if n_k < W else (n_k - W) / H + 1 rows, row j being vectorize_raw of samples
+// [j H, j H + W); the matrix the model sees is rows [r_k - F, r_k), zeros for negative indices (listen.py:92).
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long scan_rows_after(long k, int chunk, long N, int W, int H)
+{
+    long n = k * chunk;
+    n = n < N ? n : N;
+    return n < W ? 0 : (n - W) / H + 1;
+}
+
+// block = one window (recording r, chunk k0 + i): F * D consecutive floats of the recording's rows ending at row r_k
+__global__ __launch_bounds__(256) void gather_windows_kernel(const float *__restrict__ rows, int max_frames, const int32_t *__restrict__ lengths,
+                                                              int chunk, int W, int H, int F, int D, long k0, int n_chunks, long n_windows,
+                                                              float *__restrict__ feat)
+{
+    const int total = F * D;
+    for (long w = blockIdx.x; w < n_windows; w += gridDim.x) {
+        const int r = (int)(w / n_chunks);
+        const long k = k0 + (w - (long)r * n_chunks) + 1;                          // 1-based chunk number
+        long N = lengths[r];
+        N = N < 0 ? 0 : N;
+        const long T = (N + chunk - 1) / chunk;
+        long rk = k <= T ? scan_rows_after(k, chunk, N, W, H) : 0;                 // past the recording: the all-zero matrix
+        rk = rk < max_frames ? rk : max_frames;
+        const float *src = rows + ((long)r * max_frames + rk - F) * D;             // element e of the window is src[e] when its row exists
+        const int first = rk >= F ? 0 : (int)(F - rk) * D;
+        float *dst = feat + w * total;
+        for (int e = threadIdx.x; e < total; e += 256) dst[e] = e >= first ? src[e] : 0.f;
+    }
+}
+
+// argmax / max / decode of every (recording, chunk) of a tile; chunks at or past the recording's count get index -1, score 0
+__global__ __launch_bounds__(256) void scan_decode_kernel(const float *__restrict__ probs, int n_chunks, int C, const int32_t *__restrict__ rec_chunks,
+                                                          long k0, int background, DecDev d, long n_windows, long out_stride,
+                                                          int32_t *__restrict__ index, double *__restrict__ score)
+{
+    const long w = (long)blockIdx.x * 256 + threadIdx.x;
+    if (w >= n_windows) return;
+    const int r = (int)(w / n_chunks);
+    const long i = w - (long)r * n_chunks;
+    int arg = -1;
+    double sc = 0.0;
+    if (k0 + i < rec_chunks[r]) arg = argmax_decode(probs + w * C, C, background, d, sc);
+    index[r * out_stride + i] = arg;
+    score[r * out_stride + i] = sc;
+}
+
+// block = one wave = one recording: 64 chunks' predictions are loaded at once (one per lane), then walked in order by
+// trigger_one with the state in registers; lane i ends up with the fired flag of chunk base + i
+__global__ __launch_bounds__(64) void scan_trigger_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, int n_chunks,
+                                                          const int32_t *__restrict__ rec_chunks, long k0, int background, double sensitivity,
+                                                          int level, int refractory, long out_stride, int32_t *__restrict__ state,
+                                                          int32_t *__restrict__ fired)
+{
+    const int r = blockIdx.x, lane = threadIdx.x;
+    long live = (long)rec_chunks[r] - k0;                                       // chunks of this tile the recording still has
+    live = live < 0 ? 0 : (live < n_chunks ? live : n_chunks);
+    int32_t st[2] = {state[2 * (long)r], state[2 * (long)r + 1]};
+    for (int base = 0; base < n_chunks; base += 64) {
+        const int i = base + lane;
+        int idx = -1;
+        double sc = 0.0;
+        if (i < live) { idx = index[r * out_stride + i]; sc = score[r * out_stride + i]; }
+        const int n = (int)(live - base < 64 ? (live - base < 0 ? 0 : live - base) : 64);
+        int mine = 0;
+        for (int j = 0; j < n; ++j) {                                             // wave-uniform: every lane carries the same state
+            const int ij = __shfl(idx, j);
+            const double sj = __shfl(sc, j);
+            const int f = trigger_one(ij, sj, background, sensitivity, level, refractory, st);
+            if (j == lane) mine = f;
+        }
+        if (i < n_chunks) fired[r * out_stride + i] = mine;
+    }
+    if (lane == 0) { state[2 * (long)r] = st[0]; state[2 * (long)r + 1] = st[1]; }
 }
 
 static DecDev dec_dev(const kws_decoder *d)
@@ -314,6 +404,42 @@ int kws_stream_postprocess(const kws_decoder *dec, const float *probs, int S, in
                probs, S, C, background_index, dec_dev(dec), sensitivity, trigger_level, refractory_of(chunk_size), state, index, score,
                fired);
     KWS_LAUNCH_CHECK("postprocess_kernel");
+    return KWS_OK;
+}
+
+int kws_stream_gather_windows(const float *rows, int R, int max_frames, const int32_t *lengths, int chunk_size, int window_samples,
+                              int hop_samples, int F, int D, int64_t k0, int n_chunks, float *feat, void *stream)
+{
+    if (R < 0 || n_chunks < 0 || max_frames < 0 || k0 < 0) return fail(KWS_ERR_INVALID, "bad scan geometry R=%d n_chunks=%d max_frames=%d", R, n_chunks, max_frames);
+    if (chunk_size < 1 || window_samples < 1 || hop_samples < 1 || F < 1 || D < 1)
+        return fail(KWS_ERR_INVALID, "bad chunk_size=%d window=%d hop=%d F=%d D=%d", chunk_size, window_samples, hop_samples, F, D);
+    if (R == 0 || n_chunks == 0) return KWS_OK;
+    if (!lengths || !feat || (!rows && max_frames > 0)) return fail(KWS_ERR_INVALID, "null argument");
+    const long n_windows = (long)R * n_chunks;
+    KWS_LAUNCH("gather_windows_kernel", gather_windows_kernel, dim3((unsigned)std::min<long>(n_windows, 1L << 20)), dim3(256), 0,
+               static_cast<hipStream_t>(stream), rows, max_frames, lengths, chunk_size, window_samples, hop_samples, F, D, (long)k0, n_chunks,
+               n_windows, feat);
+    KWS_LAUNCH_CHECK("gather_windows_kernel");
+    return KWS_OK;
+}
+
+int kws_stream_scan_postprocess(const kws_decoder *dec, const float *probs, int R, int n_chunks, int C, const int32_t *rec_chunks, int64_t k0,
+                                int background_index, double sensitivity, int trigger_level, int chunk_size, int32_t *state, int32_t *index,
+                                double *score, int32_t *fired, int64_t out_stride, void *stream)
+{
+    if (R < 0 || n_chunks < 0 || C < 1 || chunk_size == 0 || k0 < 0) return fail(KWS_ERR_INVALID, "bad R=%d n_chunks=%d C=%d chunk_size=%d", R, n_chunks, C, chunk_size);
+    if (out_stride < n_chunks) return fail(KWS_ERR_INVALID, "out_stride=%lld is shorter than the tile's %d chunks", (long long)out_stride, n_chunks);
+    if (R == 0 || n_chunks == 0) return KWS_OK;
+    if (!probs || !rec_chunks || !state || !index || !score || !fired) return fail(KWS_ERR_INVALID, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long n_windows = (long)R * n_chunks;
+    if ((n_windows + 255) / 256 > 0x7fffffffL) return fail(KWS_ERR_UNSUPPORTED, "%ld windows in one tile", n_windows);
+    KWS_LAUNCH("scan_decode_kernel", scan_decode_kernel, dim3((unsigned)((n_windows + 255) / 256)), dim3(256), 0, s, probs, n_chunks, C, rec_chunks,
+               (long)k0, background_index, dec_dev(dec), n_windows, (long)out_stride, index, score);
+    KWS_LAUNCH_CHECK("scan_decode_kernel");
+    KWS_LAUNCH("scan_trigger_kernel", scan_trigger_kernel, dim3((unsigned)R), dim3(64), 0, s, index, score, n_chunks, rec_chunks, (long)k0,
+               background_index, sensitivity, trigger_level, refractory_of(chunk_size), (long)out_stride, state, fired);
+    KWS_LAUNCH_CHECK("scan_trigger_kernel");
     return KWS_OK;
 }
 

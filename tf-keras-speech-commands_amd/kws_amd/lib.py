@@ -190,6 +190,7 @@ def get_lib():
     L.kws_featurize_gather.argtypes = [vp, vp, i32, vp, i32, i64, vp, fp, vp]
     L.kws_featurizer_set_cu_share.argtypes = [vp, i32]
     L.kws_featurize_raw.argtypes = [vp, vp, i32, i32, i64, i32, fp, vp]
+    L.kws_featurize_long.argtypes = [vp, vp, i32, i32, i64, vp, i32, fp, vp]
     u64, f32 = ctypes.c_uint64, ctypes.c_float
     L.kws_model_create.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
     L.kws_model_destroy.argtypes = [vp]
@@ -232,6 +233,8 @@ def get_lib():
     L.kws_stream_push_rows.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.kws_trigger_update.argtypes = [vp, vp, i32, i32, f64, i32, i32, vp, vp, vp]
     L.kws_stream_postprocess.argtypes = [vp, vp, i32, i32, i32, f64, i32, i32, vp, vp, vp, vp, vp]
+    L.kws_stream_gather_windows.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, i64, i32, fp, vp]
+    L.kws_stream_scan_postprocess.argtypes = [vp, vp, i32, i32, i32, vp, i64, i32, f64, i32, i32, vp, vp, vp, vp, i64, vp]
     L.kws_set_matrix_precision.argtypes = [i32]
     L.kws_get_matrix_precision.restype = i32
     L.kws_set_inference_precision.argtypes = [i32]

@@ -3,7 +3,8 @@
 Mirrors the two helper classes of the reference's listen.py with the same constructor arguments, attributes and
 methods -- `ThresholdDecoder` (listen.py:452-522) and `TriggerDetector` (listen.py:525-559) -- and adds `StreamBatch`,
 which runs the whole per-chunk loop of listen.py:350-375 (`update_vectors`, predict, argmax / max, decode, detector
-update) for S audio streams at once.  All arithmetic runs in the HIP library; there is no host fallback.
+update) for S audio streams at once, and `scan`, the same loop over whole recordings that already lie in memory,
+parallel over time.  All arithmetic runs in the HIP library; there is no host fallback.
 """
 import ctypes
 
@@ -209,3 +210,136 @@ class StreamBatch(object):
                                                 self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),
                                                 self.fired.data_ptr(), _stream()))
         return self.index, self.score, self.fired
+
+
+def scan_plan(n_samples, chunk_size, window_samples, hop_samples, n_features):
+    """What the chunk loop (`StreamBatch.push` once per chunk, listen.py:96-114) does to a recording of `n_samples` samples,
+    in closed form.  Returns (T, n, r, first):
+      T        number of chunks, ceil(N / chunk_size) (the last one may be short, as wave.readframes delivers it);
+      n[k-1]   samples that have arrived after chunk k = 1..T: min(k * chunk_size, N);
+      r[k-1]   feature rows that exist after chunk k: the carry buffer always starts on a frame boundary, so
+               0 if n < window else (n - window) // hop + 1, row j being vectorize_raw of samples [j*hop, j*hop + window);
+      first[k-1]  index of the first row of the matrix the model sees at chunk k, r - n_features: the matrix is rows
+               [first, r), all-zero rows standing for the negative indices (listen.py:92).
+    Pure Python, no device: the kernels behind `scan` compute the same numbers (csrc/kws_stream.hip)."""
+    N, c, W, H, F = int(n_samples), int(chunk_size), int(window_samples), int(hop_samples), int(n_features)
+    if N < 0 or c < 1 or W < 1 or H < 1 or F < 1:
+        raise ValueError("scan_plan needs n_samples >= 0 and positive chunk_size / window / hop / n_features")
+    T = -(-N // c)
+    n = [min(k * c, N) for k in range(1, T + 1)]
+    r = [0 if v < W else (v - W) // H + 1 for v in n]
+    return T, n, r, [v - F for v in r]
+
+
+class ScanResult(object):
+    """index / score / fired: (R, T_max) CUDA tensors, element (r, k) for chunk k of recording r (index -1, score 0,
+    fired 0 past the recording's own n_chunks[r]); n_chunks: list of R ints; state: (R, 2) int32 CUDA tensor, the
+    detector state {activation, record_index} after each recording's last chunk; probs: (R, T_max, C) or None."""
+
+    def __init__(self, index, score, fired, n_chunks, state, probs=None):
+        self.index, self.score, self.fired, self.n_chunks, self.state, self.probs = index, score, fired, n_chunks, state, probs
+
+    def __iter__(self):
+        return iter((self.index, self.score, self.fired, self.n_chunks, self.state))
+
+
+def _pack_recordings(torch, recordings, lengths, device):
+    """-> ((R, stride) int16 CUDA tensor, host list of lengths)"""
+    if isinstance(recordings, torch.Tensor) or (isinstance(recordings, np.ndarray) and recordings.ndim == 2):
+        t = recordings if isinstance(recordings, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(recordings))
+        if t.dim() != 2 or t.dtype != torch.int16:
+            raise ValueError("recordings must be int16 PCM of shape (R, n) (the 1/32768 scaling happens on the device)")
+        if lengths is None:
+            lens = [int(t.shape[1])] * int(t.shape[0])
+        else:
+            lens = [int(v) for v in (lengths.cpu().tolist() if isinstance(lengths, torch.Tensor) else np.asarray(lengths).tolist())]
+        if len(lens) != t.shape[0] or any(v < 0 or v > t.shape[1] for v in lens):
+            raise ValueError("lengths must give one sample count in 0..%d per recording" % t.shape[1])
+        return t.to(device, non_blocking=True).contiguous(), lens
+    if lengths is not None:
+        raise ValueError("lengths goes with a padded (R, n) array; a list of recordings carries its own")
+    arrs = [np.asarray(a) for a in recordings]
+    if any(a.ndim != 1 or a.dtype != np.int16 for a in arrs):
+        raise ValueError("recordings must be 1-D int16 PCM arrays (the 1/32768 scaling happens on the device)")
+    lens = [int(a.size) for a in arrs]
+    stride = max(2, (max(lens + [0]) + 1) & ~1)                # even rows: aligned two-sample loads for every recording
+    host = np.zeros((len(arrs), stride), np.int16)
+    for i, a in enumerate(arrs):
+        host[i, :a.size] = a
+    return torch.from_numpy(host).to(device, non_blocking=True), lens
+
+
+def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
+         decoder=None, featurizer=None, background_index=0, quantized=None, tile=4096, return_probs=False, timings=None):
+    """The chunk loop of `StreamBatch` over R whole recordings at once: for every chunk of every recording the (index,
+    score, fired) that `push` would have returned for it, and the final detector state, as a `ScanResult`.
+
+    recordings: a list of 1-D int16 arrays, or a padded (R, n) int16 array / CUDA tensor with `lengths`.  The rows of every
+    recording come from one kws_featurize_long launch; then, `tile` windows at a time (all recordings advance together,
+    tile // R chunks each), kws_stream_gather_windows -> the model's (or `quantized`'s) forward ->
+    kws_stream_scan_postprocess, which carries the detector state from tile to tile.  Everything is enqueued on the
+    current stream; the host does not wait for the device.  `timings`: an optional dict that receives lists of
+    (start, end) CUDA event pairs per stage ("rows", "gather", "forward", "scan") for tools/scanbench.py."""
+    torch = _torch()
+    if pr.use_delta:
+        raise ValueError("streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered")
+    if class_names is not None:
+        assert class_names[0] == 'background', '1st class should be background.'          # listen.py:66
+    L = _l.get_lib()
+    chunk_size, tile = int(chunk_size), int(tile)
+    if chunk_size < 1 or tile < 1:
+        raise ValueError("chunk_size and tile must be positive")
+    dev = device_model.device
+    featurizer = featurizer if featurizer is not None else Featurizer(pr)
+    decoder = decoder if decoder is not None else ThresholdDecoder(pr.threshold_config, pr.threshold_center)
+    W, H, F, D = pr.window_samples, pr.hop_samples, pr.n_features, pr.n_mfcc
+    wav, lens = _pack_recordings(torch, recordings, lengths, dev)
+    R = len(lens)
+    n_chunks = [-(-n // chunk_size) for n in lens]
+    T_max = max(n_chunks + [0])
+    C = quantized.num_classes if quantized is not None else device_model.spec.num_classes
+    index = torch.empty((R, T_max), dtype=torch.int32, device=dev)
+    score = torch.empty((R, T_max), dtype=torch.float64, device=dev)
+    fired = torch.empty((R, T_max), dtype=torch.int32, device=dev)
+    probs_all = torch.empty((R, T_max, C), dtype=torch.float32, device=dev) if return_probs else None
+    state = torch.zeros((R, 2), dtype=torch.int32, device=dev)
+    state[:, 1] = -1
+    if R == 0 or T_max == 0:
+        return ScanResult(index, score, fired, n_chunks, state, probs_all)
+    st = _stream()
+
+    def timed(name, fn):
+        if timings is None:
+            return fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        timings.setdefault(name, []).append((a, b))
+        return out
+
+    d_len = torch.tensor(lens, dtype=torch.int32).to(dev, non_blocking=True)
+    d_chunks = torch.tensor(n_chunks, dtype=torch.int32).to(dev, non_blocking=True)
+    max_frames = max(0 if n < W else (n - W) // H + 1 for n in lens)
+    rows = torch.empty((R, max(max_frames, 1), D), dtype=torch.float32, device=dev)
+    timed("rows", lambda: _l.check(L.kws_featurize_long(featurizer._h, wav.data_ptr(), _l.WAV_I16, R, wav.shape[1], d_len.data_ptr(),
+                                                          max_frames, rows.data_ptr(), st)))
+    per = max(1, tile // R)                                   # chunks of every recording per tile
+    feat = torch.empty((R * min(per, T_max), F, D), dtype=torch.float32, device=dev)
+    for k0 in range(0, T_max, per):
+        n = min(per, T_max - k0)
+        fv = feat[:R * n]
+        timed("gather", lambda: _l.check(L.kws_stream_gather_windows(rows.data_ptr(), R, max_frames, d_len.data_ptr(), chunk_size, W, H, F, D,
+                                                                       k0, n, fv.data_ptr(), st)))
+        if quantized is not None:
+            probs = timed("forward", lambda: quantized.forward(fv)[0])
+        else:
+            probs = timed("forward", lambda: device_model.forward(fv, want_probs=True, want_argmax=False)[0])
+        off = k0 * 4
+        timed("scan", lambda: _l.check(L.kws_stream_scan_postprocess(decoder.handle, probs.data_ptr(), R, n, C, d_chunks.data_ptr(), k0,
+                                                                       int(background_index), float(sensitivity), int(trigger_level), chunk_size,
+                                                                       state.data_ptr(), index.data_ptr() + off, score.data_ptr() + 2 * off,
+                                                                       fired.data_ptr() + off, T_max, st)))
+        if return_probs:
+            probs_all[:, k0:k0 + n] = probs.view(R, n, C)
+    return ScanResult(index, score, fired, n_chunks, state, probs_all)

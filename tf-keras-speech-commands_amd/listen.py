@@ -3,6 +3,8 @@
 """Streaming keyword detection on the MI355X path: the `Listener` of the reference's listen.py with the same
 constructor keywords and methods (`update_vectors`, `predict`, `run_wav`, `on_prediction`, `on_activation`), built on
 kws_amd.stream.StreamBatch -- feature update, forward pass, score decoding and trigger logic all run on the device.
+`Listener.scan_wav` (CLI: --scan) is the offline form for recorded audio: whole files, or a directory of them, go through
+kws_amd.stream.scan at once and give per chunk what `run_wav` gives.
 
 Differences from listen.py: checkpoints are the `.npz` files classifier.model writes (no h5/pb/tflite/onnx/mnn
 back ends); there is no PyAudio in this image, so `run_microphone` raises and `run_wav` does not play the audio while it
@@ -18,7 +20,7 @@ import numpy as np
 from classifier.model import get_model
 from classifier.params import inject_params, pr
 from common.utils import get_classes
-from kws_amd.stream import StreamBatch, ThresholdDecoder, TriggerDetector  # noqa: F401  (re-exported like listen.py:452,525)
+from kws_amd.stream import StreamBatch, ThresholdDecoder, TriggerDetector, scan  # noqa: F401  (re-exported like listen.py:452,525)
 
 default_config = {                                     # listen.py:31-40
     "model_path": '',
@@ -31,6 +33,8 @@ default_config = {                                     # listen.py:31-40
     "trigger_level": 3,
     "save_dir": None,
     "input_wav": None,
+    "scan": False,
+    "scan_tile": 4096,
 }
 
 
@@ -123,7 +127,56 @@ class Listener(object):
         wf.close()
         return results
 
+    def _read_wav(self, path):
+        wf = wave.open(path, 'rb')
+        assert wf.getnchannels() == 1, 'input wav channels mismatch'
+        assert wf.getframerate() == self.pr.sample_rate, 'input wav sample rate mismatch'
+        assert wf.getsampwidth() == self.pr.sample_depth, 'input wav sample depth mismatch'
+        pcm = np.frombuffer(wf.readframes(wf.getnframes()), dtype='<i2')
+        wf.close()
+        return pcm
+
+    def scan_wav(self, paths=None, quiet=True):
+        """run_wav for whole files at once (kws_amd.stream.scan): `paths` is one wav or a list of them (default: input_wav).
+        Returns per file the list run_wav returns, [(index, score, fired), ...] per chunk, every file starting from a fresh
+        detector; on_activation is called for every fired chunk in order (and on_prediction for every chunk unless quiet).
+        `self.scan_times[i]` lists the times, in seconds from the start of file i, of its activations."""
+        if paths is None:
+            paths = self.input_wav
+        single = isinstance(paths, (str, bytes, os.PathLike))
+        files = [paths] if single else list(paths)
+        pcm = [self._read_wav(p) for p in files]
+        res = scan(self.pr, self.model._device(), pcm, chunk_size=self.chunk_size, class_names=self.class_names,
+                   sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
+                   quantized=self.quantized, tile=self.scan_tile)
+        index, score, fired = res.index.cpu().numpy(), res.score.cpu().numpy(), res.fired.cpu().numpy()
+        out, self.scan_times = [], []
+        for r, n in enumerate(res.n_chunks):
+            rows = [(int(index[r, k]), float(score[r, k]), bool(fired[r, k])) for k in range(n)]
+            times = []
+            for k, (i, sc, f) in enumerate(rows):
+                if not quiet:
+                    self.on_prediction(i, sc)
+                if f:
+                    times.append(k * self.chunk_size / float(self.pr.sample_rate))
+                    self.on_activation(i, play_activate=False)
+            out.append(rows)
+            self.scan_times.append(times)
+        return out[0] if single else out
+
     def run(self):
+        if self.input_wav and self.scan:
+            paths = self.input_wav
+            if os.path.isdir(paths):
+                paths = sorted(os.path.join(paths, n) for n in os.listdir(paths) if n.lower().endswith('.wav'))
+            files = [paths] if isinstance(paths, str) else paths
+            results = self.scan_wav(files, quiet=True)
+            for path, rows, times in zip(files, results, self.scan_times):
+                hits = [i for i, _, f in rows if f]
+                print('%s: %d chunks, %d activations' % (path, len(rows), len(hits)))
+                for t, i in zip(times, hits):
+                    print('  %9.3f s  %s' % (t, self.class_names[i]))
+            return results
         if self.input_wav:
             return self.run_wav()
         return self.run_microphone()
@@ -140,7 +193,10 @@ def main():
     parser.add_argument('--chunk_size', type=int, default=1024)
     parser.add_argument('--sensitivity', type=float, default=0.5)
     parser.add_argument('--trigger_level', type=int, default=3)
-    parser.add_argument('--input_wav', type=str, required=True)
+    parser.add_argument('--input_wav', type=str, required=True, help='a wav file; with --scan also a directory of *.wav')
+    parser.add_argument('--scan', action='store_true',
+                        help='offline scan: the whole recording(s) at once instead of chunk by chunk; prints every activation with its time')
+    parser.add_argument('--scan_tile', type=int, default=default_config['scan_tile'], help='windows per forward launch of --scan')
     args = parser.parse_args()
     if not args.model_path and not args.quantized_path:
         parser.error('one of --model_path and --quantized_path is required')
