@@ -521,11 +521,14 @@ def softmax(z):
     return e / e.sum(-1, keepdims=True)
 
 
-def loss_and_grad(probs, labels, class_weights=None):
-    """Per-sample losses and d(mean loss)/d(logits).
+def loss_and_grad(probs, labels, class_weights=None, ignore_index=None, grad_scale=1.0):
+    """Per-sample losses and grad_scale * d(mean loss)/d(logits).
     plain   : K.categorical_crossentropy on probabilities (loss.py:36): renormalise, clip to [1e-7, 1-1e-7], -log
     weighted: -log(p[label]) * w[label], no clipping (loss.py:67-71)
-    Keras reduces the per-sample vector with a batch mean (train.py:75-77)."""
+    ignore_index (tested for truthiness, loss.py:25,59: None / 0 = off): samples with that label have loss 0 and a zero dlogits row
+    (losses *= mask, loss.py:38-40,73-75).
+    Keras reduces the per-sample vector with a batch mean over all B samples, masked ones included (train.py:75-77).
+    grad_scale (kws_train_args: local clips / global clips in data-parallel training) multiplies dlogits only, never the losses."""
     B, C = probs.shape
     labels = np.asarray(labels).reshape(-1).astype(np.int64)
     onehot = np.eye(C, dtype=probs.dtype)[labels]
@@ -541,15 +544,24 @@ def loss_and_grad(probs, labels, class_weights=None):
         w = np.asarray(class_weights, probs.dtype)[labels]
         losses = -np.log(py) * w
         dlogits = (probs - onehot) * w[:, None] / B
+    if ignore_index:
+        masked = labels == ignore_index
+        losses = np.where(masked, probs.dtype.type(0), losses)    # not `* mask`: a masked p_y = 0 under weights is 0, not inf * 0
+        dlogits = np.where(masked[:, None], probs.dtype.type(0), dlogits)
+    if grad_scale != 1.0:
+        dlogits = dlogits * probs.dtype.type(grad_scale)
     return losses, dlogits
 
 
-def train_forward_backward(model, x, labels, class_weights=None, dropout_seed=None, dropout_mask=None):
-    """One training forward + backward.  Returns (mean loss, accuracy, probs); grads via model.grad_list()."""
+def train_forward_backward(model, x, labels, class_weights=None, dropout_seed=None, dropout_mask=None, ignore_index=None,
+                           grad_scale=1.0):
+    """One training forward + backward.  Returns (mean loss, accuracy, probs); grads via model.grad_list().
+    The mean is over all B samples and the accuracy counts every sample, those of ignore_index included (the Keras metric does
+    not see the mask); grad_scale scales the gradients only."""
     model.set_dropout(dropout_seed, dropout_mask)
     z = model.logits(x, training=True)
     p = softmax(z)
-    losses, dlogits = loss_and_grad(p, labels, class_weights)
+    losses, dlogits = loss_and_grad(p, labels, class_weights, ignore_index, grad_scale)
     model.backward(dlogits)
     acc = float((p.argmax(-1) == np.asarray(labels).reshape(-1)).mean())
     return float(losses.mean()), acc, p

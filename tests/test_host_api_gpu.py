@@ -39,8 +39,60 @@ def test_losses_call_matches_oracle(torch):
     np.testing.assert_allclose(got_w, want_w, rtol=1e-5, atol=1e-6)
     ig = SparseCategoricalCrossEntropy(ignore_index=3)(y, p)
     assert np.all(ig[y == 3] == 0) and np.allclose(ig[y != 3], got[y != 3])
-    lg = SparseCategoricalCrossEntropy(from_logits=True)(y, np.log(p[1:] + 1e-30).astype(np.float32)) if False else None
-    assert lg is None
+    for ig in (0, None):                                 # a falsy ignore_index is off: label 0 keeps its loss
+        np.testing.assert_array_equal(SparseCategoricalCrossEntropy(ignore_index=ig)(y, p), got)
+    wig = WeightedSparseCategoricalCrossEntropy(w, ignore_index=3)(y[1:], p[1:])
+    want_wig, _ = mo.loss_and_grad(p[1:].astype(np.float64), y[1:], w, ignore_index=3)
+    assert (y[1:] == 3).any() and np.all(wig[y[1:] == 3] == 0)
+    np.testing.assert_allclose(wig, want_wig, rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize("C", [2, 6, 1024])
+@pytest.mark.parametrize("B", [1, 17, 256, 257])
+def test_losses_call_options_match_oracle(torch, B, C):
+    """kws_loss_forward (one thread per sample, 256 per block): from_logits plain and weighted on logits of scale 4 and 12 (scale 12
+    reaches both clip bounds of the plain form), weighted + ignore_index, and ignore_index 0 / None, against the float64 oracle on the
+    float32 logits; rows shifted by +-100 need the max subtraction.  The weighted form has no clip, so its labels stay where p_y is a normal float32 (logit within 60 of the largest)."""
+    from classifier.loss import SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy
+    from oracle import model_oracle as mo
+    rng = np.random.default_rng(1000 * B + C)
+    k = C - 1
+    w = rng.uniform(0.2, 1.0, C)
+    for scale in (4.0, 12.0):
+        z = (rng.standard_normal((B, C)) * scale).astype(np.float32)
+        y = rng.integers(0, C, B)
+        y[::3] = z[::3].argmax(-1)
+        if scale == 12.0:
+            z[np.arange(0, B, 3), y[::3]] += 30.0         # confidently right: the other classes sum to less than 1e-8
+        if B > 1:
+            y[1::4] = k
+        z += np.array([0.0, 100.0, -100.0], np.float32)[np.arange(B) % 3][:, None]     # softmax is shift-invariant; exp of these is not
+        reach = z.max(-1)[np.arange(B)] - z[np.arange(B), y] < 60.0
+        yw = np.where(reach, y, z.argmax(-1))
+        p64 = mo.softmax(z.astype(np.float64))
+        py = p64[np.arange(B), y]
+        if scale == 12.0 and B >= 17:
+            assert (py < 1e-8).any() and (py > 1 - 1e-8).any()
+        if scale == 4.0 and B >= 17:
+            assert ((py > 1e-5) & (py < 1 - 1e-5)).any()
+        for ig in (None, 0, k):
+            want, _ = mo.loss_and_grad(p64, y, ignore_index=ig)
+            got = SparseCategoricalCrossEntropy(ignore_index=ig, from_logits=True)(y, z)
+            np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6, err_msg="plain scale %g ignore_index %s" % (scale, ig))
+            want_w, _ = mo.loss_and_grad(p64, yw, w, ignore_index=ig)
+            got_w = WeightedSparseCategoricalCrossEntropy(w, ignore_index=ig, from_logits=True)(yw, z)
+            np.testing.assert_allclose(got_w, want_w, rtol=1e-5, atol=1e-6, err_msg="weighted scale %g ignore_index %s" % (scale, ig))
+            if ig:
+                assert np.all(got[y == k] == 0) and np.all(got_w[yw == k] == 0) and (B == 1 or (yw == k).any())
+                assert np.array_equal(got[y != k], plain[y != k])
+            else:
+                plain = got
+                assert np.all(got > 0) and np.array_equal(got_w, WeightedSparseCategoricalCrossEntropy(w, from_logits=True)(yw, z))
+        # probabilities instead of logits: the same losses where the float32 probability is accurate (the plain form renormalises and clips)
+        p32 = p64.astype(np.float32)
+        got_p = SparseCategoricalCrossEntropy(ignore_index=k)(y, p32)
+        want_p, _ = mo.loss_and_grad(p32.astype(np.float64) / p32.astype(np.float64).sum(-1, keepdims=True), y, ignore_index=k)
+        np.testing.assert_allclose(got_p, want_p, rtol=1e-5, atol=1e-6)
 
 
 def test_fit_learns_and_matches_predict_oracle(torch, tmp_path):

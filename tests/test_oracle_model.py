@@ -202,3 +202,131 @@ def test_tie_aware_matching_finds_a_flipped_decision():
     # the oracle is left with its baseline gradients
     for g, b in zip(m.grad_list(), tao.base):
         np.testing.assert_array_equal(g, b)
+
+
+# ---- the loss options: ignore_index and grad_scale --------------------------------------------------------------------
+def _keras_losses(p, y, weights, ignore_index):
+    """classifier/loss.py's two classes as float32 numpy: one-hot labels; plain = K.categorical_crossentropy (renormalise, clip to
+    [1e-7, 1 - 1e-7], -sum(onehot * log p)); weighted = -sum(onehot * log p) * sum(w * onehot); both `*= mask` under a truthy
+    ignore_index"""
+    f = np.float32
+    p = p.astype(f)
+    onehot = np.eye(p.shape[-1], dtype=f)[y]
+    if ignore_index:
+        mask = (y != ignore_index).astype(f)
+    if weights is None:
+        q = p / p.sum(-1, keepdims=True)
+        q = np.clip(q, f(1e-7), f(1) - f(1e-7))
+        losses = -np.sum(onehot * np.log(q), -1)
+    else:
+        losses = -np.sum(onehot * np.log(p), -1) * np.sum(weights.astype(f) * onehot, -1)
+    if ignore_index:
+        losses = losses * mask
+    return losses
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("C", [5, 12])
+def test_loss_options_match_the_keras_formulas(C, weighted):
+    """loss_and_grad with ignore_index in {None, 0, 3, C - 1} against the float32 transcription above, in float32 and in float64;
+    the plain rows reach both clip bounds (logits of scale 12)"""
+    rng = np.random.default_rng(C + weighted)
+    B = 64
+    z = rng.standard_normal((B, C)) * np.where(np.arange(B) % 2, 4.0, 12.0)[:, None]
+    y = rng.integers(0, C, B)
+    y[:14] = [0, C - 1, 3, 3, C - 1, C - 1, 0, 3, 0, 3, C - 1, 1, 3, C - 1]
+    z[8:14, :] = rng.standard_normal((6, C)) - 25.0 * (np.arange(C) != y[8:14, None])  # confidently right rows, labels 0, 3 and C - 1 among them
+    p64 = mo.softmax(z)
+    p32 = p64.astype(np.float32)
+    w = rng.uniform(0.2, 1.0, C) if weighted else None
+    py = p32[np.arange(B), y]
+    if weighted:
+        assert py.min() > 0                               # log(0) * mask is NaN in the formula: not a case of the contract
+    else:
+        assert (py < 1e-7).sum() >= 3 and (py > 1 - 1e-7).sum() >= 3
+    plain = _keras_losses(p32, y, w, None)
+    for ig in (None, 0, 3, C - 1):
+        want = _keras_losses(p32, y, w, ig)
+        assert want.dtype == np.float32
+        if ig:
+            assert (y == ig).sum() >= 3 and np.all(want[y == ig] == 0) and np.array_equal(want[y != ig], plain[y != ig])
+        else:
+            assert np.array_equal(want, plain)            # label 0 is not ignored
+        l32, d32 = mo.loss_and_grad(p32, y, w, ignore_index=ig)
+        l64, d64 = mo.loss_and_grad(p64, y, w, ignore_index=ig)
+        assert l32.dtype == d32.dtype == np.float32
+        np.testing.assert_allclose(l32, want, rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(l64, want, rtol=1e-5, atol=1e-6)
+        masked = (y == ig) if ig else np.zeros(B, bool)
+        assert np.all(l64[masked] == 0) and np.all(d64[masked] == 0) and np.all(d32[masked] == 0)
+        # the mean is over B, not over the live samples
+        assert abs(l64.mean() - want.astype(np.float64).sum() / B) < 1e-5
+        # grad_scale: dlogits only
+        ls, ds = mo.loss_and_grad(p64, y, w, ignore_index=ig, grad_scale=0.25)
+        assert np.array_equal(ls, l64) and np.array_equal(ds, d64 * 0.25)
+    # the defaults are the former function
+    l0, d0 = mo.loss_and_grad(p64, y, w)
+    l1, d1 = mo.loss_and_grad(p64, y, w, None, 1.0)
+    assert np.array_equal(l0, l1) and np.array_equal(d0, d1)
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("ignore_index", [None, 0, 3, 6])
+def test_loss_options_dlogits_against_finite_differences(weighted, ignore_index):
+    """dlogits = grad_scale * d(mean loss)/d(logits): central differences of the mean loss in float64 (step 1e-6), 1e-6 of the largest
+    entry, on samples whose clip gate is open (logits of scale 2: all of them)"""
+    C, B = 7, 10
+    rng = np.random.default_rng(5)
+    z = rng.standard_normal((B, C)) * 2.0
+    y = rng.integers(0, C, B)
+    y[:5] = [0, 3, 6, 3, 6]
+    w = rng.uniform(0.2, 1.0, C) if weighted else None
+    py = mo.softmax(z)[np.arange(B), y]
+    assert py.min() > 1e-5 and py.max() < 1 - 1e-5       # every gate open, far from the bounds on both sides of the step
+
+    def mean_loss(zz):
+        return mo.loss_and_grad(mo.softmax(zz), y, w, ignore_index=ignore_index)[0].mean()
+
+    h = 1e-6
+    fd = np.zeros_like(z)
+    for i in range(B):
+        for c in range(C):
+            e = np.zeros_like(z)
+            e[i, c] = h
+            fd[i, c] = (mean_loss(z + e) - mean_loss(z - e)) / (2 * h)
+    for gs in (1.0, 1.0 / 3.0, 2.0):
+        _, d = mo.loss_and_grad(mo.softmax(z), y, w, ignore_index=ignore_index, grad_scale=gs)
+        assert np.abs(d - gs * fd).max() < 1e-6 * np.abs(gs * fd).max()
+    if ignore_index:
+        assert np.all(fd[y == ignore_index] == 0) and np.abs(fd[y != ignore_index]).min() > 0
+
+
+@pytest.mark.parametrize("model_type", ["simple_cnn", "simple_gru"])
+def test_train_forward_backward_options(model_type):
+    """train_forward_backward passes both options through: the masked mean loss over B, the accuracy over every sample, gradients
+    linear in grad_scale; and the tie-aware oracle of the GPU tests stores the masked / scaled dlogits"""
+    import os, sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from tie_aware import TieAwareOracle
+    C = 6
+    m, x, y = make(model_type, C, seed=2, B=12)
+    y[:4] = [3, 3, 0, 5]
+    w = np.linspace(0.3, 1.0, C)
+    loss0, acc0, p0 = mo.train_forward_backward(m, x, y, w, dropout_seed=5)
+    g0 = [g.copy() for g in m.grad_list()]
+    loss, acc, p = mo.train_forward_backward(m, x, y, w, dropout_seed=5, ignore_index=3, grad_scale=0.5)
+    g = [a.copy() for a in m.grad_list()]
+    assert np.array_equal(p, p0) and acc == acc0
+    losses = mo.loss_and_grad(p, y, w)[0]
+    assert abs(loss - losses[y != 3].sum() / len(y)) < 1e-12 and loss < loss0
+    w0 = w.copy()
+    w0[3] = 0.0                                            # masking class 3 = giving it weight 0
+    mo.train_forward_backward(m, x, y, w0, dropout_seed=5)
+    for a, b in zip(g, m.grad_list()):
+        np.testing.assert_allclose(a, 0.5 * b, rtol=1e-12, atol=1e-15)
+    assert max(np.abs(a - 0.5 * b).max() for a, b in zip(g, g0)) > 1e-6
+    tao = TieAwareOracle(m, x, y, w, 5, ignore_index=3, grad_scale=0.5)
+    assert tao.loss == loss and np.all(tao.dlogits[y == 3] == 0)
+    np.testing.assert_array_equal(tao.dlogits, mo.loss_and_grad(p, y, w, 3, 0.5)[1])
+    for a, b in zip(tao.base, g):
+        np.testing.assert_array_equal(a, b)

@@ -26,7 +26,8 @@ def _rel_err(got, want):
 class TieAwareOracle(object):
     """One training forward + backward of `om` on (x, y) with the near-tie decisions recorded."""
 
-    def __init__(self, om, x, y, class_weights=None, dropout_seed=None, eps=3e-6, max_candidates=6):
+    def __init__(self, om, x, y, class_weights=None, dropout_seed=None, eps=3e-6, max_candidates=6, ignore_index=None,
+                 grad_scale=1.0):
         self.om = om
         rec, patched = {}, []
         for li, l in enumerate(om.layers):
@@ -39,12 +40,13 @@ class TieAwareOracle(object):
                 l.forward = wrap                      # instance attribute shadows the method for this one pass
                 patched.append(l)
         try:
-            self.loss, self.acc, self.probs = mo.train_forward_backward(om, x, y, class_weights, dropout_seed)
+            self.loss, self.acc, self.probs = mo.train_forward_backward(om, x, y, class_weights, dropout_seed, ignore_index=ignore_index,
+                                                                           grad_scale=grad_scale)
         finally:
             for l in patched:
                 del l.forward
         self.base = [g.copy() for g in om.grad_list()]
-        _, self.dlogits = mo.loss_and_grad(self.probs, y, class_weights)
+        _, self.dlogits = mo.loss_and_grad(self.probs, y, class_weights, ignore_index, grad_scale)
         cands = []                                    # (relative margin, layer index, kind, index, payload)
         for li, l in enumerate(om.layers):
             if isinstance(l, mo.ReLU6):

@@ -1055,15 +1055,16 @@ __global__ __launch_bounds__(256) void loss_forward_kernel(const float *__restri
     if (b >= B) return;
     const float *p = y_pred + (long)b * C;
     const int y = labels[b];
-    float py, sum = 0.f;
+    float py;
+    double sum = 0.0;                         // one thread adds up to 1024 terms in turn: a float sum is off by ~2e-6 of itself there
     if (from_logits) {
         float mx = p[0];
         for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
-        for (int c = 0; c < C; ++c) sum += expf(p[c] - mx);
-        py = expf(p[y] - mx) / sum;
+        for (int c = 0; c < C; ++c) sum += (double)expf(p[c] - mx);
+        py = expf(p[y] - mx) / (float)sum;
     } else {
-        for (int c = 0; c < C; ++c) sum += p[c];
-        py = class_w ? p[y] : p[y] / sum;     // K.categorical_crossentropy renormalises; the weighted form does not
+        for (int c = 0; c < C; ++c) sum += (double)p[c];
+        py = class_w ? p[y] : p[y] / (float)sum;     // K.categorical_crossentropy renormalises; the weighted form does not
     }
     float loss = class_w ? -logf(py) * class_w[y] : -logf(fminf(fmaxf(py, kCeEps), 1.f - kCeEps));
     if (ignore_index > 0 && y == ignore_index) loss = 0.f;
