@@ -1,5 +1,5 @@
 """Model builders shared by the classifier-head tests (tests/test_heads_gpu.py, tests/test_quant_heads_gpu.py): float models with a
-centred head, the head-dispatch formulas of the library (kws_model.hip: run_head, run_head_bwd, fused_tail_ok), tied head columns,
+centred head, the head-dispatch formulas of the library (kws_model.hip: run_head, run_head_bwd; kws_cnn_plan.h: CnnPlan::fused_tail), tied head columns,
 and the int8 test models of tests/test_quant_gpu.py and tests/test_quant_lite_gpu.py with their edge-case variants."""
 import numpy as np
 
@@ -14,7 +14,7 @@ def head_forms(kind, K, C, matrix_bf16=True):
     return dict(
         fast_fwd=64 * (K + 1) + 4 * C * (K + 16) <= 60 * 1024,       # run_head: head_fwd_fast_kernel, else head_fwd_kernel
         mfma_bwd=K % 16 == 0 and K <= 128 and C <= 48,               # run_head_bwd: head_bwd_mfma_kernel, else head_bwd_kernel
-        fused_tail=kind == "simple_cnn" and matrix_bf16 and C <= 48,  # fused_tail_ok: inference in infer_tail_kernel
+        fused_tail=kind == "simple_cnn" and matrix_bf16 and C <= 48,  # CnnPlan::fused_tail: inference in infer_tail_kernel
         slow_lds=64 * (K + C))                                      # dynamic LDS of head_fwd_kernel / head_bwd_kernel
 
 

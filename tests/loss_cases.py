@@ -23,7 +23,7 @@ def train_head_site(kind, K, C, matrix_bf16=True, deterministic=False):
     "fused" dense_head_fused_kernel, "mfma" head_bwd_mfma_kernel<.., FWD>, "fast" head_fwd_fast_kernel, "slow" head_fwd_kernel"""
     f = head_forms(kind, K, C, matrix_bf16)
     if kind == "simple_cnn" and f["mfma_bwd"] and not deterministic:
-        return "fused" if f["fused_tail"] else "mfma"          # dense_head_fused_ok: split-bf16 matrix mode, else the FWD head
+        return "fused" if f["fused_tail"] else "mfma"          # CnnPlan::dense_fused: split-bf16 matrix mode, else the FWD head
     if kind in RNN and f["mfma_bwd"]:
         return "mfma"
     return "fast" if f["fast_fwd"] else "slow"

@@ -1,6 +1,6 @@
 """Topology descriptors of the CNN backbones (what the reference builds with tf.keras layers in
 classifier/models/cnn.py:11-141).  Pure host-side metadata: names, output shapes and parameter counts used by
-`summary()`; the arithmetic is in csrc/ (kws_model.hip)."""
+`summary()`; the arithmetic is in csrc/ (kws_model.hip; kws_cnn_plan.h picks the kernel form of every stage)."""
 
 
 def _same(n, s):

@@ -21,6 +21,7 @@
 #include "kws_infer_fused.h"
 #include "kws_conv_group.h"
 #include "kws_dense_head.h"
+#include "kws_cnn_plan.h"
 
 using namespace kws;
 
@@ -67,7 +68,7 @@ constexpr int kMaxStatBlocks = kStatStride;
 
 // ---- workspace layout (simple_cnn) ---------------------------------------------------------------------------
 struct CnnWs {
-    float *z[4], *a[4], *d1, *logits_unused, *loss_i, *correct_i, *dlogits, *dd1, *da4, *gz[4], *da[3];
+    float *z[4], *a[4], *d1, *loss_i, *correct_i, *dlogits, *dd1, *da4, *gz[4], *da[3];
     float *dwo[4], *ddw[4];   // simple_cnn_lite: depthwise outputs and their gradients
     float *coef[4];     // 6*C floats per BN layer
     __bf16 *wsp[3][6];  // simple_cnn: bf16 h/m/l planes of conv3, conv4 and dense weights (original order x3, transposed x3; kws_conv.h)
@@ -128,9 +129,6 @@ CnnWs carve_cnn(const kws_model *m, int B, bool training, unsigned char *base)
 }
 
 BnCoef coef_of(float *base, int C) { return BnCoef{base, base + C, base + 2 * C, base + 3 * C, base + 4 * C, base + 5 * C}; }
-// A train step that is being CAPTURED into a hipGraph keeps the partial-sum forms: the accumulator sets' parity and the ticket counter are
-// host-side / device-side state that a replay would not advance (the second replay would add to sums nobody cleared)
-static bool stream_capturing(hipStream_t s) { return stream_is_capturing(s); }
 // accumulator set of (pass, layer, parity) -- kws_model_types.h: ModelRes::acc
 static double *acc_set(ModelRes *R, int pass, int layer, unsigned parity) { return R->acc + ((size_t)(pass * 4 + layer) * 2 + (parity & 1u)) * kAccDoubles; }
 static int acc_make_clean(ModelRes *R, hipStream_t s)
@@ -353,26 +351,14 @@ int launch_bf16(const char *what, const float *src, __bf16 *const planes[6], con
     return 0;
 }
 
-// h/m/l bf16 planes of the three GEMM weight tensors, once per step (one launch)
-// training at the default geometry: conv3 / conv4 forward run as clip-group kernels (kws_conv_group.h), whose weights are fragment-major
-static bool group_fwd_ok(const kws_model *m)
-{
-    const CnnDims &d = m->d;
-    return m->kind == KWS_SIMPLE_CNN && d.H2 == kFuH2 && d.W2 == kFuW2 && d.H3 == kFuH3 && d.W3 == kFuW3;
-}
-// non-deterministic training in split precision: Dense forward, head forward / backward and the Dense data gradient are one kernel
-// (kws_dense_head.h), whose Dense weights are fragment-major in both orders
-static bool dense_head_fused_ok(const kws_model *m, int mprec)
-{
-    return m->kind == KWS_SIMPLE_CNN && mprec == 1 && !m->deterministic && head_bwd_fuses(m) && m->head_K == kDhK && m->d.flat % (16 * kDhWaves) == 0 &&
-           m->d.flat <= 1024;
-}
-static SplitDescs split_descs(const kws_model *m, const float *params, CnnWs &w, bool group_fwd = false, bool dense_fused = false)
+// h/m/l bf16 planes of the three GEMM weight tensors, once per step (one launch).  group (CnnPlan): the clip-group kernels of conv3 / conv4
+// (kws_conv_group.h) read fragment-major weights; dense_fused: so does the fused Dense + head kernel (kws_dense_head.h), in both orders
+static SplitDescs split_descs(const kws_model *m, const float *params, CnnWs &w, bool group = false, bool dense_fused = false)
 {
     SplitDescs all{};
     const float *src[3] = {params + m->o_k[2], params + m->o_k[3], params + m->o_dk};
     const int taps[3] = {9, 9, m->d.H4 * m->d.W4}, ci[3] = {32, 64, 128}, co[3] = {64, 128, 128};
-    const int frag[3] = {group_fwd ? 1 : 0, group_fwd ? 2 : 0, dense_fused ? 1 : 0}, ofrag[3] = {group_fwd ? 1 : 0, group_fwd ? 1 : 0, dense_fused ? 1 : 0};
+    const int frag[3] = {group ? 1 : 0, group ? 2 : 0, dense_fused ? 1 : 0}, ofrag[3] = {group ? 1 : 0, group ? 1 : 0, dense_fused ? 1 : 0};
     for (int t = 0; t < 3; ++t)
         all.d[t] = SplitDesc{src[t], {w.wsp[t][0], w.wsp[t][1], w.wsp[t][2]}, {w.wsp[t][3], w.wsp[t][4], w.wsp[t][5]}, taps[t], ci[t], co[t], frag[t],
                              ofrag[t]};
@@ -380,9 +366,9 @@ static SplitDescs split_descs(const kws_model *m, const float *params, CnnWs &w,
     return all;
 }
 
-static int split_weights(const kws_model *m, const float *params, CnnWs &w, hipStream_t s, bool group_fwd = false, bool dense_fused = false)
+static int split_weights(const kws_model *m, const float *params, CnnWs &w, hipStream_t s, bool group = false, bool dense_fused = false)
 {
-    const SplitDescs all = split_descs(m, params, w, group_fwd, dense_fused);
+    const SplitDescs all = split_descs(m, params, w, group, dense_fused);
     KWS_LAUNCH("weight_split_kernel", weight_split_kernel, dim3(64, 3), dim3(256), 0, s, all);
     return KWS_OK;
 }
@@ -436,13 +422,7 @@ static int launch_group_conv4(const kws_model *m, int B, CnnWs &w, hipStream_t s
 
 // Inference of simple_cnn in split precision at the default geometry: everything behind the second pooling stage is ONE kernel
 // (kws_infer_fused.h).  Its weights are prepared fragment-major; they take the place of the transposed planes (same element counts), the
-// head's go to the head of the double partial slab (unused by the inference forward).
-static bool fused_tail_ok(const kws_model *m, bool bf16)
-{
-    const CnnDims &d = m->d;
-    return bf16 && m->kind == KWS_SIMPLE_CNN && d.H2 == kFuH2 && d.W2 == kFuW2 && d.H3 == kFuH3 && d.W3 == kFuW3 && d.H4 == kFuH4 && d.W4 == kFuW4 &&
-           m->C <= kFuHeadCols;
-}
+// head's go to the head of the double partial slab (unused by the inference forward).  CnnPlan::fused_tail decides.
 static __bf16 *fused_head_plane(CnnWs &w, int p) { return reinterpret_cast<__bf16 *>(w.partial) + (size_t)p * (kFuD / 32) * (kFuHeadCols / 16) * 512; }
 static int split_weights_fused(const kws_model *m, const float *params, CnnWs &w, hipStream_t s)
 {
@@ -481,603 +461,659 @@ ConvGeom geom3x3(int B, int H, int W, int stride)
 // (l1m_act_pool_moments_kernel<true>) split the conv3 / conv4 / dense weights into their bf16 planes and 16 clear the gradient
 // buffer.  Both jobs used to run on the side stream behind an event and were joined before conv3: two events on the main chain
 // (6-8 us each) for 12 us of work that hides under the activation pass.
-// conv2's backward pass in split precision keeps g compact (the routed value per pool window + the element index), when the clip
-// fits the kernels' staging; the forward activation kernel of layer 2 then also leaves zmax / arg for the routed backward reduction
-static bool cnn_compact_g2(const kws_model *m, bool bf16)
-{
-    const CnnDims &d = m->d;
-    return bf16 && d.H1 * d.W1 * 8 <= 1280 && (size_t)(d.H1 / 2) * (d.W1 / 2) * 32 <= sizeof(float) * (size_t)d.H3 * d.W3 * 64;
-}
-// training in split precision: conv4 and its weight gradient form a3 from z3 on the fly (kws_conv.h: ABN / XBN); the fp32 mode keeps
-// the activation kernel (same-box A/B at B = 4096: 0.6714 -> 0.666 ms per step)
-static bool cnn_a3_on_load(const kws_model *m, bool bf16, bool training) { return bf16 && training; }
 constexpr int kPrepSplitBlocks = 16, kPrepZeroBlocks = 16, kPrepBlocks = 3 * kPrepSplitBlocks + kPrepZeroBlocks;
 
-// ---- forward ------------------------------------------------------------------------------------------------
-// zero_grads (training, split precision): the gradient buffer of the backward pass that follows is cleared on the side
-// stream beside the weight split instead of on the main chain; *zeroed tells the caller whether that happened
-int cnn_forward(const kws_model *m, const float *feat, int B, const float *params, float *state, CnnWs &w, bool training,
-                uint64_t seed, hipStream_t s, float *zero_grads = nullptr, bool *zeroed = nullptr, OverlapHook *hook = nullptr,
-                const double *moments = nullptr, float *probs = nullptr, int32_t *argmax = nullptr, bool *head_done = nullptr)
-{
-    const DisarmOnExit disarm_guard;        // no armed fork event outlives this call, whichever way it returns
-    const CnnDims &d = m->d;
-    const int Hs[4] = {d.H0, d.H1, d.H2, d.H3}, Ws[4] = {d.W0, d.W1, d.W2, d.W3};   // conv input sizes
-    const int Hz[4] = {d.H0, d.H1, d.H3, d.H3}, Wz[4] = {d.W0, d.W1, d.W3, d.W3};   // conv output sizes
-    const bool pool[4] = {true, true, false, true};
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+// ---- one call of simple_cnn: what its stage functions share ---------------------------------------------------
+struct CnnCtx {
+    const kws_model *m;
+    const CnnDims &d;
+    int B;
+    const float *feat, *params;
+    float *state, *grads;           // grads: training
+    CnnWs &w;
+    ModelRes *R;                    // training; inference stays on ONE stream and needs none of the model's resources
+    hipStream_t s, s2;              // the caller's stream; the model's side stream (training)
+    const CnnPlan &P;
+    OverlapHook *hook;
+    uint64_t seed;
+    const double *moments;          // second moments Q of the feature map from the caller (kws_train_args.feat_moments), or nullptr
+    const kws_train_args *a;        // training: labels, loss options, events, communicator
+    float *probs;                   // inference: where the fused tail leaves the head's outputs
+    int32_t *argmax;
+    unsigned fpar[4], bpar[4];      // parity of each layer's accumulator sets in this call's forward / backward pass
+    bool bound6;                    // the caller's overlap event rides on layer 4's activation kernel
+    int fused_bn3_blocks;           // > 0: conv4's data gradient already did layer 3's BatchNorm-backward reduction
 
-    const bool bf16 = matrix_prec(m) == 1;
-    // inference after kws_model_prepare_inference on the same buffers: the weight planes and BatchNorm coefficients are in place
-    const bool prepared = !training && m->prepared_for(params, state, w.base, B, matrix_prec(m), infer_prec(m));
-    // inference with a caller that takes the head's outputs here: conv3 .. softmax as one kernel (kws_infer_fused.h)
-    const bool fused_tail = !training && head_done && fused_tail_ok(m, bf16);
-    // training in split precision at the default geometry: conv3 / conv4 forward as clip-group kernels (needs at most kStatStride blocks)
-    const bool group_fwd = training && bf16 && group_fwd_ok(m) && (long)blocks_for(B, kFuClips) <= kStatStride;
-    // training: the Dense layer's forward product runs inside the fused Dense + head kernel of the backward pass (kws_dense_head.h)
-    const bool dense_fused = training && dense_head_fused_ok(m, matrix_prec(m));
-    ModelRes *R = nullptr;       // only the split-on-the-side-stream branch below needs the model's stream / events
-    // training in split precision at a geometry the MFMA layer-1 kernels cover: the weight split and the gradient clear ride
-    // in the grid of the layer-1 activation kernel -- no side-stream branch, no events
-    const bool prep_in_stats = bf16 && training && d.H0 % 2 == 0 && d.W0 % 2 == 0 && (d.H0 + 2) * (d.W0 + 2) <= 64 * kL1Stage &&
-                               (d.H0 / 2) * (d.W0 / 2) <= 4 * kL1MaxTiles;
-    if (prep_in_stats) {
-        if (zero_grads && zeroed) *zeroed = true;
-    } else if (bf16 && training) {
-        // the h/m/l planes are first needed by conv3: split on the side stream beside layers 1-2, join before conv3
-        R = const_cast<kws_model *>(m)->dev_res();
-        if (!R) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
-        hipStream_t s2 = R->side;
+    uint32_t slo() const { return (uint32_t)(seed & 0xFFFFFFFFu); }
+    uint32_t shi() const { return (uint32_t)(seed >> 32); }
+    float drop_rate() const { return seed != 0 ? 0.5f : 0.f; }      // Dropout(0.5) after Flatten, cnn.py:63
+    BnCoef coef(int l) const { return coef_of(w.coef[l], kCh[l + 1]); }
+    // pixels of layer l's convolution output over the batch (conv3 has stride 2 and no pooling: conv4 works on the same map)
+    long pixels(int l) const { return (long)B * (l == 0 ? d.H0 * d.W0 : l == 1 ? d.H1 * d.W1 : d.H3 * d.W3); }
+    // the consumer's view of layer l's forward statistics / of its BatchNorm-backward sums
+    BnAccFwd acc_in(int l, unsigned parity) const
+    {
+        return BnAccFwd{acc_set(R, 0, l, parity), acc_set(R, 0, l, parity + 1), pixels(l), params + m->o_g[l], params + m->o_b[l],
+                        state + m->o_mm[l], state + m->o_mv[l], coef(l)};
+    }
+    BnAccBwd acc_out(int l) const { return BnAccBwd{acc_set(R, 1, l, bpar[l]), acc_set(R, 1, l, bpar[l] + 1), pixels(l), grads + m->o_g[l], grads + m->o_b[l]}; }
+
+    int forward();      // P.fused_tail: the head's outputs are in probs / argmax when it returns (conv2's stage launched the one-kernel tail)
+    int fwd_prepare(), fwd_layer1(), fwd_conv2(), fwd_conv3(), fwd_conv4(), fwd_dense();
+    int fwd_bn_finalize(int l, int C, int fused_stat_blocks);
+    int fwd_bn_act(int l, int H, int W, int C, bool pooled, float rate, float *zm = nullptr, unsigned char *ag = nullptr);
+    int backward();
+    int bwd_head_dense(), bwd_layer4(), bwd_layer3(), bwd_layer2(), bwd_layer1();
+    void bwd_arm(int ev) { arm_stop_event(R->ev[ev], s); }
+    int bwd_fork(int ev);
+    int bwd_bn_finalize(int l, int C, int nblk);
+    int bwd_reduce_pool(int l, int H, int W, int C, float *da, float rate, int nblk, int rows);
+};
+
+// launch geometry of the layer-1 kernels, forward and backward (conv1 is recomputed from the feature map wherever z1 is needed, kws_layer1.h)
+struct L1Geom {
+    int cpb, nb;        // clips per block and blocks of the block-per-clip forms
+    int cpw, nbm;       // clips per wave and blocks of the MFMA, wave-per-clip forms
+    size_t smem1, smemm;
+};
+static L1Geom l1_geom(const CnnDims &d, int B, const CnnPlan &P)
+{
+    L1Geom g;
+    g.cpb = std::max(1, (B + kMaxStatBlocks - 1) / kMaxStatBlocks); g.nb = (B + g.cpb - 1) / g.cpb;
+    g.smem1 = sizeof(float) * (size_t)(d.H0 + 2) * (d.W0 + 2);
+    g.cpw = std::max(1, (B + 4 * kMaxStatBlocks - 1) / (4 * kMaxStatBlocks)); g.nbm = (B + 4 * g.cpw - 1) / (4 * g.cpw);
+    // per-wave LDS tiles; the compile-time form of the default map reads two rows past the haloed map (kws_layer1.h: L1Runs)
+    g.smemm = sizeof(float) * 4 * (P.l1_default_map ? (size_t)L1Runs<30, 20>::TILE : (size_t)((((d.H0 + 2) * (d.W0 + 2)) + 3) & ~3));
+    return g;
+}
+
+// LDS sizes and persistent grids of conv2's clip-resident kernels (16 -> 32, 3x3, stride 1): the clip's tiles are staged in LDS once
+struct Conv2Clip {
+    int B;
+    size_t sm, smb;         // forward, fp32 / split precision
+    size_t smw, smwb;       // weight gradient, fp32 / split precision
+    size_t smd, smdb;       // data gradient, fp32 / split precision
+    // persistent grids: at most max_blocks (the LDS-limited residency), with an equal share of clips each
+    unsigned even_grid(int max_blocks) const { const int cpb = (B + max_blocks - 1) / max_blocks; return (unsigned)((B + cpb - 1) / cpb); }
+};
+static Conv2Clip conv2_clip(const CnnDims &d, int B)
+{
+    const int H1 = d.H1, W1 = d.W1;
+    Conv2Clip k;
+    k.B = B;
+    k.sm = std::max(sizeof(float) * (size_t)(H1 + 2) * (W1 + 2) * 20, sizeof(double) * 4 * 2 * 32);
+    k.smb = std::max((size_t)6 * 16 * (((H1 + 2) * (W1 + 2) + 15) & ~15), sizeof(double) * 4 * 2 * 16);
+    const size_t smw = sizeof(float) * ((size_t)(H1 + 2) * (W1 + 2) * 16 + (size_t)((H1 * W1 + 3) / 4) * 4 * stride16(32));
+    k.smw = std::max(smw, sizeof(float) * (size_t)(1024 + 16 * 32));
+    k.smwb = std::max((size_t)3 * 32 * (H1 + 2) * (W1 + 2) + (size_t)6 * 32 * (H1 * W1 + 1), sizeof(float) * 9 * 16 * 32);
+    // dgrad forms dz2 from (g, z2) while staging and leaves it in gz[1]; wgrad then overlaps with layer 1's kernels
+    k.smd = sizeof(float) * (size_t)(H1 + 2) * (W1 + 2) * (32 + 4);
+    // split-precision form: 2 blocks per CU by registers (the weight fragments of all nine taps stay in them)
+    k.smdb = (size_t)12 * 16 * (((H1 + 2) * (W1 + 2) + 15) & ~15);
+    return k;
+}
+
+// ---- forward ------------------------------------------------------------------------------------------------
+// weight planes, inference coefficients and the accumulator parities of this pass
+int CnnCtx::fwd_prepare()
+{
+    if (P.training && P.bf16 && !P.prep_in_stats) {
+        // the h/m/l planes are first needed by conv3: split on the side stream beside layers 1-2, join before conv3; the gradient buffer
+        // of the backward pass that follows is cleared there too, instead of on the main chain
         KWS_HIP_CHECK(hipEventRecord(R->ev[10], s));
         KWS_HIP_CHECK(hipStreamWaitEvent(s2, R->ev[10], 0));
-        if (zero_grads) {
-            KWS_HIP_CHECK(hipMemsetAsync(zero_grads, 0, sizeof(float) * (size_t)m->P, s2));
-            if (zeroed) *zeroed = true;
-        }
-        if (int rc = split_weights(m, params, w, s2, group_fwd, dense_fused)) return rc;
+        KWS_HIP_CHECK(hipMemsetAsync(grads, 0, sizeof(float) * (size_t)m->P, s2));
+        if (int rc = split_weights(m, params, w, s2, P.group, P.dense_fused)) return rc;
         KWS_HIP_CHECK(hipEventRecord(R->ev[11], s2));
-    } else if (bf16) {
+    } else if (!P.training && P.bf16 && !P.prepared) {
         // inference stays on ONE stream: callers capture it into hipGraphs, and a fork to the library's side stream inside
         // several captured graphs made every graph after the first replay 0.2 ms slower
-        if (!prepared)
-            if (int rc = fused_tail ? split_weights_fused(m, params, w, s) : split_weights(m, params, w, s)) return rc;
+        if (int rc = P.fused_tail ? split_weights_fused(m, params, w, s) : split_weights(m, params, w, s)) return rc;
     }
-    if (!training && !prepared)
+    if (!P.training && !P.prepared)
         if (int rc = infer_coefs(m, params, state, w, s)) return rc;
-    const bool routed_bwd2 = cnn_compact_g2(m, bf16);
-    const bool fuse_pool2 = group_fwd && routed_bwd2 && d.H1 == kGrH1 && d.W1 == kGrW1;
     // finalize-free batch statistics (kws_device.h: acc_add), non-deterministic training at the default geometry: conv2 .. conv4 add their
     // sums to accumulator sets and the next kernel of the chain derives scale / shift in its prologue -- three launches less
-    const bool acc_fwd = fuse_pool2 && !m->deterministic && kCh[4] <= 128 && !stream_capturing(s);
-    unsigned fpar[4] = {0, 0, 0, 0};
-    if (acc_fwd) {
-        if (!R) R = const_cast<kws_model *>(m)->dev_res();
-        if (!R) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
+    if (P.acc_fwd) {
         for (int l = 1; l < 4; ++l) fpar[l] = R->acc_uses[0][l]++;
         KWS_TRY(acc_make_clean(R, s));
-        R->acc_dirty = true;               // until every kernel of this pass is enqueued
+        R->acc_dirty = true;             // until every kernel of this pass is enqueued
     }
-    // layer 1 and conv2's forward as ONE clip-resident kernel (kws_l1_conv2.h): split-precision training at the default map with the
-    // PREP blocks in the layer-1 grid and conv2's sums in the accumulator form; every other case keeps the two kernels
-    const bool l1_conv2 = prep_in_stats && acc_fwd && d.H0 == 30 && d.W0 == 20;
-    // layer 1: conv1 is recomputed from the feature map wherever z1 is needed (kws_layer1.h)
-    {
-        const int cpb = std::max(1, (B + kMaxStatBlocks - 1) / kMaxStatBlocks), nb = (B + cpb - 1) / cpb;
-        const size_t smem1 = sizeof(float) * (size_t)(d.H0 + 2) * (d.W0 + 2);
-        // every pixel in a pool window, a haloed map of at most 768 floats and at most 40 tiles: the MFMA, wave-per-clip forms
-        const bool l1m = d.H0 % 2 == 0 && d.W0 % 2 == 0 && (d.H0 + 2) * (d.W0 + 2) <= 64 * kL1Stage &&
-                         (d.H0 / 2) * (d.W0 / 2) <= 4 * kL1MaxTiles;
-        const int cpw = std::max(1, (B + 4 * kMaxStatBlocks - 1) / (4 * kMaxStatBlocks)), nbm = (B + 4 * cpw - 1) / (4 * cpw);
-        // per-wave LDS tiles; the compile-time form of the default map reads two rows past the haloed map (kws_layer1.h: L1Runs)
-        const size_t smemm = sizeof(float) * 4 * (d.H0 == 30 && d.W0 == 20 ? (size_t)L1Runs<30, 20>::TILE : (size_t)((((d.H0 + 2) * (d.W0 + 2)) + 3) & ~3));
-        const long M1 = (long)B * d.H0 * d.W0;
-        BnCoef k1 = coef_of(w.coef[0], 16);
-        const float *kern1 = params + m->o_k[0];
-        if (training && l1m) {
-            // batch statistics of BatchNorm 1 from the second moments Q of the features (kws_layer1_moments.h): no statistics pass
-            // over z1, no finalize launch; Q comes from the caller (input pipeline) or is computed here
-            const double *q = moments;
-            if (!q) {
-                KWS_LAUNCH("l1_moments_kernel", l1_moments_kernel, dim3(nbm), dim3(256), smemm, s, feat, B, d.H0, d.W0, cpw, w.partial);
-                KWS_LAUNCH("l1_moments_finalize_kernel", l1_moments_finalize_kernel, dim3(kMomCount), dim3(64), 0, s, w.partial, nbm, w.moments);
-                q = w.moments;
-            }
-            L1PrepArgs pa{};
-            if (prep_in_stats) {
-                pa.all = split_descs(m, params, w, group_fwd, dense_fused); pa.zero_buf = zero_grads; pa.zero_n = (long)m->P;
-                pa.nsplit = kPrepSplitBlocks; pa.nzero = kPrepZeroBlocks;
-            }
-            if (l1_conv2) {
-                // conv2's grid (one block per clip up to kMaxStatBlocks, then clips b + k * nblk) plus the PREP blocks
-                const int nblk = std::min(B, kMaxStatBlocks);
-                const size_t sml = L1Conv2Lds<30, 20>::BYTES;
-                KWS_LAUNCH("l1_conv2_fwd_bf16<30,20>", (l1_conv2_fwd_bf16_kernel<30, 20>), dim3(nblk + kPrepBlocks), dim3(256), sml, s, feat, kern1,
-                           q, params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], params + m->o_k[1], w.z[1],
-                           acc_set(R, 0, 1, fpar[1]), B, nblk, pa);
-            } else if (prep_in_stats) {
-                KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_moments_kernel<true>, dim3(nbm + kPrepBlocks), dim3(256), smemm, s, feat, kern1, q,
-                           params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], B, d.H0, d.W0, cpw, nbm, pa);
-            } else {
-                KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_moments_kernel<false>, dim3(nbm), dim3(256), smemm, s, feat, kern1, q,
-                           params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], B, d.H0, d.W0, cpw, nbm, pa);
-            }
-        } else if (training) {
-            KWS_LAUNCH("l1_stats_kernel", l1_stats_kernel<16>, dim3(nb), dim3(256), smem1, s, feat, kern1, B, d.H0, d.W0, cpb, w.partial);
-            KWS_LAUNCH(prof_name("bn_finalize_train_kernel", 1), bn_finalize_train_kernel, dim3(16), dim3(64), 0, s, w.partial, nb, M1, 16,
-                       params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1);
+    return KWS_OK;
+}
+
+// layer 1 (and conv2's forward where the two are one kernel)
+int CnnCtx::fwd_layer1()
+{
+    const L1Geom g = l1_geom(d, B, P);
+    BnCoef k1 = coef(0);
+    const float *kern1 = params + m->o_k[0];
+    if (P.training && P.l1m) {
+        // batch statistics of BatchNorm 1 from the second moments Q of the features (kws_layer1_moments.h): no statistics pass
+        // over z1, no finalize launch; Q comes from the caller (input pipeline) or is computed here
+        const double *q = moments;
+        if (!q) {
+            KWS_LAUNCH("l1_moments_kernel", l1_moments_kernel, dim3(g.nbm), dim3(256), g.smemm, s, feat, B, d.H0, d.W0, g.cpw, w.partial);
+            KWS_LAUNCH("l1_moments_finalize_kernel", l1_moments_finalize_kernel, dim3(kMomCount), dim3(64), 0, s, w.partial, g.nbm, w.moments);
+            q = w.moments;
         }
-        if (training && l1m) ;
-        else if (l1m) KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_kernel, dim3(nbm), dim3(256), smemm, s, feat, kern1, k1.scale, k1.shift, w.a[0], B,
-                   d.H0, d.W0, cpw);
-        else KWS_LAUNCH("l1_act_pool_kernel", l1_act_pool_kernel<16>, dim3(nb), dim3(256), smem1, s, feat, kern1, k1.scale, k1.shift, w.a[0], B,
-                   d.H0, d.W0, cpb);
-    }
-    if (hook) KWS_TRY(hook->fire(8, s));                 // behind layer 1: the featurizer then shares the chip with the forward convolutions
-    bool bound6 = false;
-    const bool a3_on_load = cnn_a3_on_load(m, bf16, training);
-    auto acc_in = [&](int l) {             // the consumer's view of layer l's statistics
-        return BnAccFwd{acc_set(R, 0, l, fpar[l]), acc_set(R, 0, l, fpar[l] + 1), (long)B * Hz[l] * Wz[l], params + m->o_g[l], params + m->o_b[l],
-                        state + m->o_mm[l], state + m->o_mv[l], coef_of(w.coef[l], kCh[l + 1])};
-    };
-    for (int l = 1; l < 4; ++l) {
-        const float *in = w.a[l - 1];
-        const float *kern = params + m->o_k[l];
-        const long M = (long)B * Hz[l] * Wz[l];
-        const int C = kCh[l + 1];
-        int fused_stat_blocks = 0;           // > 0: the conv kernel already wrote the BN partial sums
-        if (l == 1) {
-            // conv2: clip-resident kernel, batch statistics fused into the epilogue when training
-            const unsigned nblk = (unsigned)std::min(B, kMaxStatBlocks);
-            const size_t sm = std::max(sizeof(float) * (size_t)(Hs[1] + 2) * (Ws[1] + 2) * 20, sizeof(double) * 4 * 2 * 32);
-            const size_t smb = std::max((size_t)6 * 16 * (((Hs[1] + 2) * (Ws[1] + 2) + 15) & ~15), sizeof(double) * 4 * 2 * 16);
-            if (l1_conv2) {
-                fused_stat_blocks = (int)nblk;     // ran inside the layer-1 launch above
-            } else if (training && bf16) {
-                KWS_LAUNCH("conv_fwd_clip_bf16<16,32>", (conv_fwd_clip_bf16_kernel<true>), dim3(nblk), dim3(256), smb, s, in, kern, w.z[1], B, Hs[1],
-                           Ws[1], w.partial, kStatStride, nullptr, nullptr, acc_fwd ? acc_set(R, 0, 1, fpar[1]) : nullptr);
-                fused_stat_blocks = (int)nblk;
-            } else if (training) {
-                KWS_LAUNCH("conv_fwd_clip<16,32>", (conv_fwd_clip_kernel<32, true>), dim3(nblk), dim3(256), sm, s, in, kern, w.z[1], B, Hs[1], Ws[1],
-                           w.partial, kStatStride);
-                fused_stat_blocks = (int)nblk;
-            } else if (bf16) {
-                const BnCoef k2 = coef_of(w.coef[1], 32);
-                KWS_LAUNCH("conv_fwd_clip_pool_bf16<16,32>", (conv_fwd_clip_bf16_kernel<false, true>), dim3(nblk), dim3(256), smb, s, in, kern, w.a[1], B,
-                           Hs[1], Ws[1], w.partial, kStatStride, k2.scale, k2.shift);
-                if (fused_tail) {
-                    KWS_TRY(launch_fused_tail(m, B, params, w, probs, argmax, s));
-                    *head_done = true;
-                    KWS_LAUNCH_CHECK("simple_cnn forward");
-                    return KWS_OK;
-                }
-                continue;
-            } else {
-                // inference: BatchNorm affine + ReLU6 + 2x2 max in the kernel's epilogue, a2 written directly
-                const BnCoef k2 = coef_of(w.coef[1], 32);
-                KWS_LAUNCH("conv_fwd_clip_pool<16,32>", (conv_fwd_clip_kernel<32, false, true>), dim3(nblk), dim3(256), sm, s, in, kern, w.a[1], B,
-                           Hs[1], Ws[1], w.partial, kStatStride, k2.scale, k2.shift);
-                continue;
-            }
-        } else if (l == 2 && bf16 && !training) {
-            // inference: BatchNorm affine + ReLU6 in the epilogue, a3 written directly (conv3 has no pool)
-            const BnCoef k3 = coef_of(w.coef[2], 64);
-            KWS_TRY_NB(launch_bf16<32, 64, MODE_FWD, EPI_BN_RELU6>("conv_bf16_fwd_bn", in, w.wsp[0], k3.scale, w.a[2], geom3x3(B, Hs[2], Ws[2], 2), s, nullptr, k3.shift));
-            continue;
-        } else if (l == 2) {
-            if (bf16 && training && !prep_in_stats) KWS_HIP_CHECK(hipStreamWaitEvent(s, R->ev[11], 0));     // the weight planes are ready
-            // the split-precision kernels write the BatchNorm partial sums from their epilogue when training
-            if (group_fwd) {
-                if (acc_fwd) { const BnAccFwd in2 = acc_in(1); fused_stat_blocks = launch_group_conv3(m, B, w, s, fuse_pool2, &in2, acc_set(R, 0, 2, fpar[2])); }
-                else fused_stat_blocks = launch_group_conv3(m, B, w, s, fuse_pool2);
-                if (fused_stat_blocks < 0) return fused_stat_blocks;
-            } else if (bf16) {
-                fused_stat_blocks = launch_bf16<32, 64, MODE_FWD, EPI_NONE>("conv_bf16_fwd", in, w.wsp[0], nullptr, w.z[2], geom3x3(B, Hs[2], Ws[2], 2), s,
-                                                                          training ? w.partial : nullptr);
-                if (fused_stat_blocks < 0) return fused_stat_blocks;
-            } else KWS_TRY(launch_gemm<32, 64, MODE_FWD, EPI_NONE>(in, kern, nullptr, w.z[2], geom3x3(B, Hs[2], Ws[2], 2), s));
+        L1PrepArgs pa{};
+        if (P.prep_in_stats) {
+            pa.all = split_descs(m, params, w, P.group, P.dense_fused); pa.zero_buf = grads; pa.zero_n = (long)m->P;
+            pa.nsplit = kPrepSplitBlocks; pa.nzero = kPrepZeroBlocks;
+        }
+        if (P.l1_conv2) {
+            // conv2's grid (one block per clip up to kMaxStatBlocks, then clips b + k * nblk) plus the PREP blocks
+            const int nblk = std::min(B, kMaxStatBlocks);
+            const size_t sml = L1Conv2Lds<30, 20>::BYTES;
+            KWS_LAUNCH("l1_conv2_fwd_bf16<30,20>", (l1_conv2_fwd_bf16_kernel<30, 20>), dim3(nblk + kPrepBlocks), dim3(256), sml, s, feat, kern1,
+                       q, params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], params + m->o_k[1], w.z[1],
+                       acc_set(R, 0, 1, fpar[1]), B, nblk, pa);
+        } else if (P.prep_in_stats) {
+            KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_moments_kernel<true>, dim3(g.nbm + kPrepBlocks), dim3(256), g.smemm, s, feat, kern1, q,
+                       params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], B, d.H0, d.W0, g.cpw, g.nbm, pa);
         } else {
-            // activation='relu', cnn.py:55
-            if (group_fwd) {
-                // forms a3 = relu6(BN3(z3)) while staging, like the ABN form below
-                if (acc_fwd) { const BnAccFwd in3 = acc_in(2); fused_stat_blocks = launch_group_conv4(m, B, w, s, &in3, acc_set(R, 0, 3, fpar[3])); }
-                else fused_stat_blocks = launch_group_conv4(m, B, w, s);
-                if (fused_stat_blocks < 0) return fused_stat_blocks;
-            } else if (bf16) {
-                // training: a3 = relu6(BN3(z3)) is never written -- conv4 forms it from z3 while it stages its rows, and so does conv4's
-                // weight gradient (conv3 has no pooling, so the activation is a per-element map)
-                fused_stat_blocks = launch_bf16<64, 128, MODE_FWD, EPI_RELU>("conv_bf16_fwd", a3_on_load ? w.z[2] : in, w.wsp[1], nullptr, w.z[3],
-                                                                           geom3x3(B, Hs[3], Ws[3], 1), s, training ? w.partial : nullptr, nullptr, nullptr,
-                                                                           a3_on_load ? coef_of(w.coef[2], 64).scale : nullptr);
-                if (fused_stat_blocks < 0) return fused_stat_blocks;
-            } else KWS_TRY(launch_gemm<64, 128, MODE_FWD, EPI_RELU>(in, kern, nullptr, w.z[3], geom3x3(B, Hs[3], Ws[3], 1), s));
+            KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_moments_kernel<false>, dim3(g.nbm), dim3(256), g.smemm, s, feat, kern1, q,
+                       params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1, w.a[0], B, d.H0, d.W0, g.cpw, g.nbm, pa);
         }
-        if (hook && l < 3) KWS_TRY(hook->fire(8 + l, s));     // 9 behind conv2's forward, 10 behind conv3's
-        BnCoef k = coef_of(w.coef[l], C);
-        if (training && acc_fwd) ;          // the next kernel of the chain derives the coefficients from the accumulator set
-        else if (training) {
-            int nblk, rows;
-            stat_grid(M, C, nblk, rows);
-            if (fused_stat_blocks) nblk = fused_stat_blocks;
-            else KWS_LAUNCH(prof_name("channel_stats_kernel", l + 1), channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.z[l], M, C, rows, w.partial);
-            KWS_LAUNCH(prof_name("bn_finalize_train_kernel", l + 1), bn_finalize_train_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, M, C, params + m->o_g[l],
-                               params + m->o_b[l], state + m->o_mm[l], state + m->o_mv[l], k);
-        }
-        const float rate = (training && l == 3 && seed != 0) ? 0.5f : 0.f;   // Dropout(0.5) after Flatten, cnn.py:63
-        // behind the last convolution: from here to BN4's backward the main chain is small kernels (activation, dense, head),
-        // the best place for the caller to start the next batch's featurizer (kws_train_args.overlap_event)
-        if (l == 3 && hook) KWS_TRY(hook->fire(0, s));
-        // overlap point 6 sits right behind this layer's activation kernel: the caller's event rides on that kernel's completion signal
-        // instead of a marker packet of its own (kws_common.h: ArmedEvent)
-        // layer 4's activation rides in the fused Dense + head kernel of the backward pass (kws_dense_head.h: z4): no kernel here
-        const bool pool4_fused = l == 3 && acc_fwd && dense_fused;
-        const bool arm6 = l == 3 && hook && hook->wants(6) && hook->ev && !pool4_fused;
-        if (arm6) arm_stop_event(hook->ev, s);
-        if (pool4_fused) { R->pool4_pending = true; R->pool4_mm = state + m->o_mm[3]; R->pool4_mv = state + m->o_mv[3]; }
-        else if (l == 1 && fuse_pool2) ;               // conv3's group kernel forms a2 (and zmax2 / arg2) from z2 while it stages its tile
-        else if (pool[l]) {
-            const long total = (long)B * (Hz[l] / 2) * (Wz[l] / 2) * C;
-            // training: the routed element of every window for the backward reduction (layer 2: compact g; layer 4: full-size g)
-            float *zm = nullptr;
-            unsigned char *ag = nullptr;
-            if (l == 1 && training && routed_bwd2) { zm = w.zmax2; ag = w.arg2; }
-            if (l == 3 && training && bf16) { zm = w.zmax4; ag = w.arg4; }
-            if (l == 3 && acc_fwd)
-                KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_acc_kernel, dim3(std::min<unsigned>(1024u, blocks_for(total, 256))), dim3(256), 0, s,
-                           w.z[l], acc_in(3), w.a[l], B, Hz[l], Wz[l], C, rate, slo, shi, zm, ag);
-            else
-                KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_kernel<true>, dim3(blocks_for(total, 256)), dim3(256), 0, s, w.z[l], k.scale, k.shift,
-                           w.a[l], B, Hz[l], Wz[l], C, rate, slo, shi, zm, ag);
-        } else if (!(l == 2 && a3_on_load)) {
-            const long total = M * C;
-            KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_kernel<false>, dim3(blocks_for(total, 256)), dim3(256), 0, s, w.z[l], k.scale, k.shift,
-                               w.a[l], B, Hz[l], Wz[l], C, rate, slo, shi);
-        }
-        if (arm6) bound6 = stop_event_bound(hook->ev);
+        return KWS_OK;
     }
-    // Dense(128, use_bias=True) + ReLU6 as a (H4 x W4) 'valid' convolution over the pooled map (Flatten is h,w,c)
+    if (P.training) {
+        KWS_LAUNCH("l1_stats_kernel", l1_stats_kernel<16>, dim3(g.nb), dim3(256), g.smem1, s, feat, kern1, B, d.H0, d.W0, g.cpb, w.partial);
+        KWS_LAUNCH(prof_name("bn_finalize_train_kernel", 1), bn_finalize_train_kernel, dim3(16), dim3(64), 0, s, w.partial, g.nb, pixels(0), 16,
+                   params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1);
+    }
+    if (P.l1m) KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_kernel, dim3(g.nbm), dim3(256), g.smemm, s, feat, kern1, k1.scale, k1.shift, w.a[0], B,
+               d.H0, d.W0, g.cpw);
+    else KWS_LAUNCH("l1_act_pool_kernel", l1_act_pool_kernel<16>, dim3(g.nb), dim3(256), g.smem1, s, feat, kern1, k1.scale, k1.shift, w.a[0], B,
+               d.H0, d.W0, g.cpb);
+    return KWS_OK;
+}
+
+// Training without the accumulator form: BatchNorm coefficients of conv2 .. conv4 (l = 1 .. 3) from the batch statistics.
+// fused_stat_blocks > 0: the conv kernel already wrote the partial sums of that many blocks
+int CnnCtx::fwd_bn_finalize(int l, int C, int fused_stat_blocks)
+{
+    const long M = pixels(l);
+    int nblk, rows;
+    stat_grid(M, C, nblk, rows);
+    if (fused_stat_blocks) nblk = fused_stat_blocks;
+    else KWS_LAUNCH(prof_name("channel_stats_kernel", l + 1), channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.z[l], M, C, rows, w.partial);
+    KWS_LAUNCH(prof_name("bn_finalize_train_kernel", l + 1), bn_finalize_train_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, M, C, params + m->o_g[l],
+               params + m->o_b[l], state + m->o_mm[l], state + m->o_mv[l], coef(l));
+    return KWS_OK;
+}
+// BatchNorm affine -> ReLU6 (-> 2x2 max-pool, dropout) of conv2 .. conv4 from the coefficients; zm / ag (training): the routed element of
+// every pool window for the backward reduction (layer 2: compact g; layer 4: full-size g)
+int CnnCtx::fwd_bn_act(int l, int H, int W, int C, bool pooled, float rate, float *zm, unsigned char *ag)
+{
+    const BnCoef k = coef(l);
+    if (pooled) {
+        const long total = (long)B * (H / 2) * (W / 2) * C;
+        KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_kernel<true>, dim3(blocks_for(total, 256)), dim3(256), 0, s, w.z[l], k.scale, k.shift,
+                   w.a[l], B, H, W, C, rate, slo(), shi(), zm, ag);
+    } else {
+        const long total = pixels(l) * C;
+        KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_kernel<false>, dim3(blocks_for(total, 256)), dim3(256), 0, s, w.z[l], k.scale, k.shift,
+                           w.a[l], B, H, W, C, rate, slo(), shi());
+    }
+    return KWS_OK;
+}
+
+// conv2: clip-resident kernel, batch statistics fused into the epilogue when training
+int CnnCtx::fwd_conv2()
+{
+    const float *in = w.a[0], *kern = params + m->o_k[1];
+    const unsigned nblk = (unsigned)std::min(B, kMaxStatBlocks);
+    const Conv2Clip cc = conv2_clip(d, B);
+    if (!P.training) {
+        // inference: BatchNorm affine + ReLU6 + 2x2 max in the kernel's epilogue, a2 written directly
+        const BnCoef k2 = coef(1);
+        if (P.bf16) {
+            KWS_LAUNCH("conv_fwd_clip_pool_bf16<16,32>", (conv_fwd_clip_bf16_kernel<false, true>), dim3(nblk), dim3(256), cc.smb, s, in, kern, w.a[1], B,
+                       d.H1, d.W1, w.partial, kStatStride, k2.scale, k2.shift);
+            if (P.fused_tail) KWS_TRY(launch_fused_tail(m, B, params, w, probs, argmax, s));
+        } else
+            KWS_LAUNCH("conv_fwd_clip_pool<16,32>", (conv_fwd_clip_kernel<32, false, true>), dim3(nblk), dim3(256), cc.sm, s, in, kern, w.a[1], B,
+                       d.H1, d.W1, w.partial, kStatStride, k2.scale, k2.shift);
+        return KWS_OK;
+    }
+    if (P.l1_conv2) ;                      // ran inside the layer-1 launch
+    else if (P.bf16)
+        KWS_LAUNCH("conv_fwd_clip_bf16<16,32>", (conv_fwd_clip_bf16_kernel<true>), dim3(nblk), dim3(256), cc.smb, s, in, kern, w.z[1], B, d.H1,
+                   d.W1, w.partial, kStatStride, nullptr, nullptr, P.acc_fwd ? acc_set(R, 0, 1, fpar[1]) : nullptr);
+    else
+        KWS_LAUNCH("conv_fwd_clip<16,32>", (conv_fwd_clip_kernel<32, true>), dim3(nblk), dim3(256), cc.sm, s, in, kern, w.z[1], B, d.H1, d.W1,
+                   w.partial, kStatStride);
+    if (hook) KWS_TRY(hook->fire(9, s));
+    // acc_fwd: the next kernel of the chain derives the coefficients from the accumulator set
+    if (!P.acc_fwd) KWS_TRY(fwd_bn_finalize(1, 32, (int)nblk));
+    // fuse_pool2: conv3's group kernel forms a2 (and zmax2 / arg2) from z2 while it stages its tile
+    if (!P.fuse_pool2) KWS_TRY(fwd_bn_act(1, d.H1, d.W1, 32, true, 0.f, P.routed_g2 ? w.zmax2 : nullptr, P.routed_g2 ? w.arg2 : nullptr));
+    return KWS_OK;
+}
+
+int CnnCtx::fwd_conv3()
+{
+    const float *in = w.a[1], *kern = params + m->o_k[2];
+    const ConvGeom g = geom3x3(B, d.H2, d.W2, 2);
+    if (P.bf16 && !P.training) {
+        // inference: BatchNorm affine + ReLU6 in the epilogue, a3 written directly (conv3 has no pool)
+        const BnCoef k3 = coef(2);
+        KWS_TRY_NB(launch_bf16<32, 64, MODE_FWD, EPI_BN_RELU6>("conv_bf16_fwd_bn", in, w.wsp[0], k3.scale, w.a[2], g, s, nullptr, k3.shift));
+        return KWS_OK;
+    }
+    if (P.bf16 && P.training && !P.prep_in_stats) KWS_HIP_CHECK(hipStreamWaitEvent(s, R->ev[11], 0));     // the weight planes are ready
+    // the split-precision kernels write the BatchNorm partial sums from their epilogue when training
+    int fused_stat_blocks = 0;
+    if (P.group) {
+        if (P.acc_fwd) { const BnAccFwd in2 = acc_in(1, fpar[1]); fused_stat_blocks = launch_group_conv3(m, B, w, s, P.fuse_pool2, &in2, acc_set(R, 0, 2, fpar[2])); }
+        else fused_stat_blocks = launch_group_conv3(m, B, w, s, P.fuse_pool2);
+        if (fused_stat_blocks < 0) return fused_stat_blocks;
+    } else if (P.bf16) {
+        fused_stat_blocks = launch_bf16<32, 64, MODE_FWD, EPI_NONE>("conv_bf16_fwd", in, w.wsp[0], nullptr, w.z[2], g, s, P.training ? w.partial : nullptr);
+        if (fused_stat_blocks < 0) return fused_stat_blocks;
+    } else KWS_TRY(launch_gemm<32, 64, MODE_FWD, EPI_NONE>(in, kern, nullptr, w.z[2], g, s));
+    if (hook) KWS_TRY(hook->fire(10, s));
+    if (P.training && !P.acc_fwd) KWS_TRY(fwd_bn_finalize(2, 64, fused_stat_blocks));
+    // a3_on_load: a3 = relu6(BN3(z3)) is never written -- conv4 forms it from z3 while it stages its rows, and so does conv4's
+    // weight gradient (conv3 has no pooling, so the activation is a per-element map)
+    if (!P.a3_on_load) KWS_TRY(fwd_bn_act(2, d.H3, d.W3, 64, false, 0.f));
+    return KWS_OK;
+}
+
+// conv4 (activation='relu', cnn.py:55) and layer 4's BatchNorm -> ReLU6 -> max-pool -> dropout
+int CnnCtx::fwd_conv4()
+{
+    const float *in = w.a[2], *kern = params + m->o_k[3];
+    const ConvGeom g = geom3x3(B, d.H3, d.W3, 1);
+    int fused_stat_blocks = 0;
+    if (P.group) {
+        // forms a3 = relu6(BN3(z3)) while staging, like the ABN form below
+        if (P.acc_fwd) { const BnAccFwd in3 = acc_in(2, fpar[2]); fused_stat_blocks = launch_group_conv4(m, B, w, s, &in3, acc_set(R, 0, 3, fpar[3])); }
+        else fused_stat_blocks = launch_group_conv4(m, B, w, s);
+        if (fused_stat_blocks < 0) return fused_stat_blocks;
+    } else if (P.bf16) {
+        fused_stat_blocks = launch_bf16<64, 128, MODE_FWD, EPI_RELU>("conv_bf16_fwd", P.a3_on_load ? w.z[2] : in, w.wsp[1], nullptr, w.z[3], g, s,
+                                                                   P.training ? w.partial : nullptr, nullptr, nullptr,
+                                                                   P.a3_on_load ? coef(2).scale : nullptr);
+        if (fused_stat_blocks < 0) return fused_stat_blocks;
+    } else KWS_TRY(launch_gemm<64, 128, MODE_FWD, EPI_RELU>(in, kern, nullptr, w.z[3], g, s));
+    if (P.training && !P.acc_fwd) KWS_TRY(fwd_bn_finalize(3, 128, fused_stat_blocks));
+    const float rate = P.training ? drop_rate() : 0.f;
+    // behind the last convolution: from here to BN4's backward the main chain is small kernels (activation, dense, head),
+    // the best place for the caller to start the next batch's featurizer (kws_train_args.overlap_event)
+    if (hook) KWS_TRY(hook->fire(0, s));
+    // pool4_fused: layer 4's activation rides in the fused Dense + head kernel of the backward pass (kws_dense_head.h: z4): no kernel here
+    if (P.pool4_fused) return KWS_OK;
+    // overlap point 6 sits right behind this layer's activation kernel: the caller's event rides on that kernel's completion signal
+    // instead of a marker packet of its own (kws_common.h: ArmedEvent)
+    const bool arm6 = hook && hook->wants(6) && hook->ev;
+    if (arm6) arm_stop_event(hook->ev, s);
+    float *zm = P.training && P.bf16 ? w.zmax4 : nullptr;
+    unsigned char *ag = P.training && P.bf16 ? w.arg4 : nullptr;
+    if (P.acc_fwd) {
+        const long total = (long)B * (d.H3 / 2) * (d.W3 / 2) * 128;
+        KWS_LAUNCH(prof_name("bn_act_pool_kernel", 4), bn_act_pool_acc_kernel, dim3(std::min<unsigned>(1024u, blocks_for(total, 256))), dim3(256), 0, s,
+                   w.z[3], acc_in(3, fpar[3]), w.a[3], B, d.H3, d.W3, 128, rate, slo(), shi(), zm, ag);
+    } else KWS_TRY(fwd_bn_act(3, d.H3, d.W3, 128, true, rate, zm, ag));
+    if (arm6) bound6 = stop_event_bound(hook->ev);
+    return KWS_OK;
+}
+
+// Dense(128, use_bias=True) + ReLU6 as a (H4 x W4) 'valid' convolution over the pooled map (Flatten is h,w,c)
+static ConvGeom dense_geom(const CnnDims &d, int B)
+{
     ConvGeom g;
     g.B = B; g.H = d.H4; g.W = d.W4; g.Ho = 1; g.Wo = 1; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = d.H4; g.KW = d.W4;
+    return g;
+}
+int CnnCtx::fwd_dense()
+{
+    const ConvGeom g = dense_geom(m->d, B);
     if (hook) KWS_TRY(hook->fire(6, s, bound6));
-    if (dense_fused) ;                              // d1 is formed by dense_head_fused_kernel (cnn_backward)
-    else if (bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_FWD, EPI_BIAS_RELU6>("conv_bf16_fwd", w.a[3], w.wsp[2], params + m->o_db, w.d1, g, s));
+    if (P.dense_fused) ;                          // d1 is formed by dense_head_fused_kernel (bwd_head_dense)
+    else if (P.bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_FWD, EPI_BIAS_RELU6>("conv_bf16_fwd", w.a[3], w.wsp[2], params + m->o_db, w.d1, g, s));
     else KWS_TRY(launch_gemm<128, 128, MODE_FWD, EPI_BIAS_RELU6>(w.a[3], params + m->o_dk, params + m->o_db, w.d1, g, s));
     if (hook) KWS_TRY(hook->fire(7, s));
+    return KWS_OK;
+}
+
+// P.fused_tail: the head's outputs are in probs / argmax when this returns (conv2's stage launched the one-kernel tail)
+int CnnCtx::forward()
+{
+    const DisarmOnExit disarm_guard;        // no armed fork event outlives this call, whichever way it returns
+    KWS_TRY(fwd_prepare());
+    KWS_TRY(fwd_layer1());
+    if (hook) KWS_TRY(hook->fire(8, s));           // behind layer 1: the featurizer then shares the chip with the forward convolutions
+    KWS_TRY(fwd_conv2());
+    if (!P.fused_tail) {
+        KWS_TRY(fwd_conv3());
+        KWS_TRY(fwd_conv4());
+        KWS_TRY(fwd_dense());
+    }
     KWS_LAUNCH_CHECK("simple_cnn forward");
-    if (acc_fwd) R->acc_dirty = false;
+    if (P.acc_fwd) R->acc_dirty = false;
     return KWS_OK;
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------
-int cnn_backward(const kws_model *m, const float *feat, int B, const float *params, float *grads, CnnWs &w, uint64_t seed,
-                 hipEvent_t bucket_event, hipStream_t s, float *stats, bool grads_zeroed = false, const double *moments = nullptr,
-                 OverlapHook *hook = nullptr, kws_comm *comm = nullptr, const kws_train_args *fused_head = nullptr)
+// The weight-gradient GEMM of a layer only READS (x, dz) and adds into grads; the data-gradient GEMM and the next
+// layer's BN backward do not depend on it.  Each of them alone leaves the MFMA pipe more than half idle, so wgrad runs
+// on the library's side stream (fork after dz is final, one join at the end) and shares the chip with the main chain.
+// fork: the side stream waits for everything enqueued on s so far.  arm(ev) in front of the LAST kernel before the fork lets that
+// kernel's own completion signal be the event (kws_common.h: ArmedEvent) instead of a marker packet on the main chain
+int CnnCtx::bwd_fork(int ev)
 {
-    // fused_head != nullptr: the head's forward pass (logits, softmax, loss, dlogits) has NOT run; the head's backward kernel does it
-    // (cnn_head_fwd_fused below decides)
-    const DisarmOnExit disarm_guard;        // no armed fork event outlives this call, whichever way it returns
-    const CnnDims &d = m->d;
-    const int Hs[4] = {d.H0, d.H1, d.H2, d.H3}, Ws[4] = {d.W0, d.W1, d.W2, d.W3};
-    const int Hz[4] = {d.H0, d.H1, d.H3, d.H3}, Wz[4] = {d.W0, d.W1, d.W3, d.W3};
-    const bool pool[4] = {true, true, false, true};
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+    if (!stop_event_bound(R->ev[ev])) KWS_HIP_CHECK(hipEventRecord(R->ev[ev], s));
+    KWS_HIP_CHECK(hipStreamWaitEvent(s2, R->ev[ev], 0));
+    return KWS_OK;
+}
 
-    if (!grads_zeroed) KWS_HIP_CHECK(hipMemsetAsync(grads, 0, sizeof(float) * (size_t)m->P, s));
-    // The weight-gradient GEMM of a layer only READS (x, dz) and adds into grads; the data-gradient GEMM and the next
-    // layer's BN backward do not depend on it.  Each of them alone leaves the MFMA pipe more than half idle, so wgrad runs
-    // on the library's side stream (fork after dz is final, one join at the end) and shares the chip with the main chain.
-    ModelRes *R = const_cast<kws_model *>(m)->dev_res();
-    if (!R) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
-    hipStream_t s2 = R->side;
-    const int mprec = matrix_prec(m);
-    const bool det = m->deterministic != 0;
-    // fork: the side stream waits for everything enqueued on s so far.  arm(ev) in front of the LAST kernel before the fork lets that
-    // kernel's own completion signal be the event (kws_common.h: ArmedEvent) instead of a marker packet on the main chain
-    constexpr bool no_arm = false;
-    hipEvent_t fork0_ev = nullptr;
-    bool fork0_bound = false, dense_fused = false;
-    auto arm = [&](int ev) { if (!no_arm) arm_stop_event(R->ev[ev], s); };
-    auto fork = [&](int ev) -> int {
-        if (!stop_event_bound(R->ev[ev])) KWS_HIP_CHECK(hipEventRecord(R->ev[ev], s));
-        KWS_HIP_CHECK(hipStreamWaitEvent(s2, R->ev[ev], 0));
-        return KWS_OK;
-    };
-    const bool routed_bwd2 = cnn_compact_g2(m, mprec == 1);      // the forward pass left zmax2 / arg2 (same predicate)
-    // the clip-group form of conv4's / conv3's data gradients (the forward pass prepared the weights for it: cnn_forward's group_fwd)
-    const bool group_bwd = mprec == 1 && group_fwd_ok(m) && (long)blocks_for(B, kFuClips) <= kStatStride;
-    // finalize-free BatchNorm backward (kws_device.h: acc_add), non-deterministic mode.  Layer 2: conv3's data gradient does the reduction
-    // in its epilogue and conv2's clip kernels derive k2 / k3 from the accumulator set.  Layer 3: conv4's data gradient adds its sums to the
-    // set and the apply kernel derives the coefficients.  Layer 4: the fused Dense + head kernel's epilogue is the reduction, the apply
-    // kernel expands the compact gradient.
-    const bool acc_ok = !det && !stream_capturing(s);
-    const bool acc_bn2 = group_bwd && acc_ok && routed_bwd2 && Hs[1] * Ws[1] <= 160 && Hs[1] * Ws[1] * 8 <= 1280 && Hs[1] * Ws[1] * 4 <= 768;
-    const bool acc_bn3 = group_bwd && acc_ok;
-    const bool acc_bn4 = fused_head && dense_head_fused_ok(m, mprec) && acc_ok && kCh[4] == kDhK && d.flat == d.H4 * d.W4 * kCh[4];
-    // parity of each layer's sets: flipped only by a pass that uses them (its consumer is what clears the other parity)
-    const unsigned bpar[4] = {0u, acc_bn2 ? R->acc_uses[1][1]++ : 0u, acc_bn3 ? R->acc_uses[1][2]++ : 0u, acc_bn4 ? R->acc_uses[1][3]++ : 0u};
-    KWS_TRY(acc_make_clean(R, s));
-    R->acc_dirty = true;               // until every kernel of this pass is enqueued
-    // head: dW2, db2, dd1 (gated by dense's ReLU6)
-    {
-        // the MFMA head kernel also leaves the dense bias gradient (column sums of dd1) and the loss / accuracy sums
-        const bool fuse = head_bwd_fuses(m);
-        // the head's backward kernel is the last one in front of the dense fork AND of overlap point 2: its completion signal carries the
-        // caller's overlap event when there is one (the side stream then waits for that event too), the fork event otherwise
-        // (deterministic mode launches two kernels here and keeps the recorded events)
-        fork0_ev = (hook && hook->wants(2) && hook->ev) ? hook->ev : R->ev[0];
-        if (!det && !no_arm) arm_stop_event(fork0_ev, s);
-        if (fused_head && dense_head_fused_ok(m, mprec)) {
-            const kws_train_args *a = fused_head;
-            DenseHeadArgs da{};
-            da.a4 = w.a[3]; da.db = params + m->o_db; da.w2 = params + m->o_hk;
-            for (int p = 0; p < 3; ++p) { da.fd[p] = w.wsp[2][3 + p]; da.fo[p] = w.wsp[2][p]; }
-            da.d1 = w.d1; da.dd1 = w.dd1; da.da4 = w.da4; da.dw2 = grads + m->o_hk; da.db2 = grads + m->o_hb; da.ddb = grads + m->o_db;
-            da.B = B; da.C = m->C; da.flat = d.flat;
-            if (acc_bn4) {
-                da.zmax4 = w.zmax4; da.coef4 = coef_of(w.coef[3], 128).scale; da.acc4 = acc_set(R, 1, 3, bpar[3]);
-                da.drop_rate = seed != 0 ? 0.5f : 0.f; da.seed_lo = slo; da.seed_hi = shi;
-            }
-            if (R->pool4_pending) {             // the forward pass of this step left layer 4's activation to this kernel
-                const unsigned fpar = R->acc_uses[0][3] - 1;
-                da.z4 = w.z[3]; da.a4w = w.a[3]; da.zmax4w = w.zmax4; da.arg4w = w.arg4; da.H3 = Hz[3]; da.W3 = Wz[3];
-                da.in4 = BnAccFwd{acc_set(R, 0, 3, fpar), acc_set(R, 0, 3, fpar + 1), (long)B * Hz[3] * Wz[3], params + m->o_g[3], params + m->o_b[3],
-                                  R->pool4_mm, R->pool4_mv, coef_of(w.coef[3], 128)};
-                da.drop_rate = seed != 0 ? 0.5f : 0.f; da.seed_lo = slo; da.seed_hi = shi;
-                R->pool4_pending = false;
-            }
-            da.fw = HeadFwdArgs{params + m->o_hb, a->labels, a->class_weights, a->probs, w.loss_i, w.correct_i, a->grad_scale / (float)B, a->ignore_index};
-            const size_t smem = sizeof(float) * (size_t)(16 * (d.flat + 8) + 2 * 16 * kDhKS + 16 * kDhCS + kDhK * kDhCS);
-            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(dense_head_fused_kernel), (int)smem)) return rc;
-            KWS_LAUNCH("dense_head_fused_kernel", dense_head_fused_kernel, dim3(blocks_for(B, 16)), dim3(kDhThreads), smem, s, da);
-            dense_fused = true;
-        } else if (fused_head) {
-            const kws_train_args *a = fused_head;
-            const HeadFwdArgs hf{params + m->o_hb, a->labels, a->class_weights, a->probs, w.loss_i, w.correct_i, a->grad_scale / (float)B, a->ignore_index};
-            KWS_TRY(run_head_bwd(m, B, params, w.d1, nullptr, w.dd1, grads, true, s, grads + m->o_db, nullptr, nullptr, nullptr, false, &hf));
-        } else
-            KWS_TRY(run_head_bwd(m, B, params, w.d1, w.dlogits, w.dd1, grads, true, s, fuse && !det ? grads + m->o_db : nullptr, w.loss_i, w.correct_i,
-                                 fuse ? stats : nullptr, det));
-        fork0_bound = stop_event_bound(fork0_ev);
-        if (fused_head) {
-            // the forward pass and the loss are enqueued only now
-            if (fused_head->forward_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(fused_head->forward_event), s));
-            if (hook) KWS_TRY(hook->fire(1, s));
+// BatchNorm backward of layer l + 1 without the accumulator form: the coefficients k2 / k3 and dgamma / dbeta from nblk blocks' partial sums
+int CnnCtx::bwd_bn_finalize(int l, int C, int nblk)
+{
+    KWS_LAUNCH(prof_name("bn_bwd_finalize_kernel", l + 1), bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, pixels(l), C, params + m->o_g[l],
+               grads + m->o_g[l], grads + m->o_b[l], coef(l));
+    return KWS_OK;
+}
+// the reduction of a pooled layer (2 or 4) with a full-size g and no routing tables: gates by ReLU6, routes through the pool, stores g
+int CnnCtx::bwd_reduce_pool(int l, int H, int W, int C, float *da, float rate, int nblk, int rows)
+{
+    KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", l + 1), bn_bwd_reduce_pool_kernel<false>, dim3(nblk), dim3(256), 0, s, w.z[l], da, coef(l),
+               w.gz[l], B, H, W, C, rows, w.partial, rate, slo(), shi());
+    return KWS_OK;
+}
+
+// head: dW2, db2, dd1 (gated by dense's ReLU6); dense 256->128: bias grad (column sums), wgrad, dgrad -> da4 (gradient w.r.t. the dropped,
+// flattened map).  P.fuse_head_fwd: the head's forward pass (logits, softmax, loss, dlogits) has NOT run; the head's backward kernel does it
+int CnnCtx::bwd_head_dense()
+{
+    float *stats = P.head_bwd_fuses ? a->stats : nullptr;      // the MFMA head kernel also leaves the dense bias gradient (column sums of dd1) and the loss / accuracy sums
+    // the head's backward kernel is the last one in front of the dense fork AND of overlap point 2: its completion signal carries the
+    // caller's overlap event when there is one (the side stream then waits for that event too), the fork event otherwise
+    // (deterministic mode launches two kernels here and keeps the recorded events)
+    const hipEvent_t fork0_ev = (hook && hook->wants(2) && hook->ev) ? hook->ev : R->ev[0];
+    if (!P.det) arm_stop_event(fork0_ev, s);
+    if (P.dense_fused) {
+        DenseHeadArgs da{};
+        da.a4 = w.a[3]; da.db = params + m->o_db; da.w2 = params + m->o_hk;
+        for (int p = 0; p < 3; ++p) { da.fd[p] = w.wsp[2][3 + p]; da.fo[p] = w.wsp[2][p]; }
+        da.d1 = w.d1; da.dd1 = w.dd1; da.da4 = w.da4; da.dw2 = grads + m->o_hk; da.db2 = grads + m->o_hb; da.ddb = grads + m->o_db;
+        da.B = B; da.C = m->C; da.flat = d.flat;
+        if (P.acc_bn4) {
+            da.zmax4 = w.zmax4; da.coef4 = coef(3).scale; da.acc4 = acc_set(R, 1, 3, bpar[3]);
+            da.drop_rate = drop_rate(); da.seed_lo = slo(); da.seed_hi = shi();
         }
+        if (P.pool4_fused) {               // the forward pass of this step left layer 4's activation to this kernel
+            da.z4 = w.z[3]; da.a4w = w.a[3]; da.zmax4w = w.zmax4; da.arg4w = w.arg4; da.H3 = d.H3; da.W3 = d.W3;
+            da.in4 = acc_in(3, R->acc_uses[0][3] - 1);
+            da.drop_rate = drop_rate(); da.seed_lo = slo(); da.seed_hi = shi();
+        }
+        da.fw = HeadFwdArgs{params + m->o_hb, a->labels, a->class_weights, a->probs, w.loss_i, w.correct_i, a->grad_scale / (float)B, a->ignore_index};
+        const size_t smem = sizeof(float) * (size_t)(16 * (d.flat + 8) + 2 * 16 * kDhKS + 16 * kDhCS + kDhK * kDhCS);
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(dense_head_fused_kernel), (int)smem)) return rc;
+        KWS_LAUNCH("dense_head_fused_kernel", dense_head_fused_kernel, dim3(blocks_for(B, 16)), dim3(kDhThreads), smem, s, da);
+    } else if (P.fuse_head_fwd) {
+        const HeadFwdArgs hf{params + m->o_hb, a->labels, a->class_weights, a->probs, w.loss_i, w.correct_i, a->grad_scale / (float)B, a->ignore_index};
+        KWS_TRY(run_head_bwd(m, B, params, w.d1, nullptr, w.dd1, grads, true, s, grads + m->o_db, nullptr, nullptr, nullptr, false, &hf));
+    } else
+        KWS_TRY(run_head_bwd(m, B, params, w.d1, w.dlogits, w.dd1, grads, true, s, nullptr, w.loss_i, w.correct_i,
+                             stats, P.det));
+    const bool fork0_bound = stop_event_bound(fork0_ev);
+    if (P.fuse_head_fwd) {
+        // the forward pass and the loss are enqueued only now
+        if (a->forward_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->forward_event), s));
+        if (hook) KWS_TRY(hook->fire(1, s));
     }
-    // dense 256->128: bias grad (column sums), wgrad, dgrad -> da4 (gradient w.r.t. the dropped, flattened map)
-    {
-        ConvGeom g;
-        g.B = B; g.H = d.H4; g.W = d.W4; g.Ho = 1; g.Wo = 1; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = d.H4; g.KW = d.W4;
-        const bool hook_ev_here = hook && hook->wants(2) && hook->ev;
-        if (hook) KWS_TRY(hook->fire(2, s, fork0_bound && hook_ev_here));
-        // its own fork: started later, together with conv4's weight gradient, the step was 2 % slower (same-box A/B)
-        if (hook_ev_here) {
-            KWS_HIP_CHECK(hipStreamWaitEvent(s2, fork0_ev, 0));       // the overlap event (recorded or bound just above) is the fork event
-        } else {
-            if (!fork0_bound) KWS_HIP_CHECK(hipEventRecord(R->ev[0], s));
-            KWS_HIP_CHECK(hipStreamWaitEvent(s2, R->ev[0], 0));
-        }
-        // fused head: the sums of the per-sample losses / correct flags, in a fixed order, off the main chain
-        if (fused_head && stats) KWS_LAUNCH("loss_reduce_kernel", loss_reduce_kernel, dim3(1), dim3(256), 0, s2, w.loss_i, w.correct_i, B, stats);
-        KWS_TRY(launch_wgrad<128, 128, 1>(w.a[3], w.dd1, grads + m->o_dk, g, s2, det));
+    const ConvGeom g = dense_geom(d, B);
+    const bool hook_ev_here = hook && hook->wants(2) && hook->ev;
+    if (hook) KWS_TRY(hook->fire(2, s, fork0_bound && hook_ev_here));
+    // its own fork: started later, together with conv4's weight gradient, the step was 2 % slower (same-box A/B)
+    if (hook_ev_here) {
+        KWS_HIP_CHECK(hipStreamWaitEvent(s2, fork0_ev, 0));       // the overlap event (recorded or bound just above) is the fork event
+    } else {
+        if (!fork0_bound) KWS_HIP_CHECK(hipEventRecord(R->ev[0], s));
+        KWS_HIP_CHECK(hipStreamWaitEvent(s2, R->ev[0], 0));
+    }
+    // fused head: the sums of the per-sample losses / correct flags, in a fixed order, off the main chain
+    if (P.fuse_head_fwd && stats) KWS_LAUNCH("loss_reduce_kernel", loss_reduce_kernel, dim3(1), dim3(256), 0, s2, w.loss_i, w.correct_i, B, stats);
+    KWS_TRY(launch_wgrad<128, 128, 1>(w.a[3], w.dd1, grads + m->o_dk, g, s2, P.det));
+    if (!P.fuse_head_fwd) {                 // no MFMA head kernel, or deterministic mode: the dense bias gradient takes its own two kernels
         int nblk, rows;
         stat_grid(B, 128, nblk, rows);
-        if (!head_bwd_fuses(m) || det) {
-            KWS_LAUNCH("channel_stats_kernel.dense", channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.dd1, (long)B, 128, rows, w.partial);
-            KWS_LAUNCH("colsum_finalize_kernel", colsum_finalize_kernel, dim3(128), dim3(256), 0, s, w.partial, nblk, 128, grads + m->o_db);
-        }
-        if (dense_fused) ;                          // da4 came out of dense_head_fused_kernel
-        else if (mprec == 1) KWS_TRY_NB(launch_bf16<128, 128, MODE_DGRAD, EPI_NONE>("conv_bf16_dgrad", w.dd1, w.wsp[2], nullptr, w.da4, g, s));
-        else KWS_TRY(launch_dgrad<128, 128, 1>(w.dd1, params + m->o_dk, w.da4, g, s));
-        if (hook) KWS_TRY(hook->fire(3, s));
+        KWS_LAUNCH("channel_stats_kernel.dense", channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.dd1, (long)B, 128, rows, w.partial);
+        KWS_LAUNCH("colsum_finalize_kernel", colsum_finalize_kernel, dim3(128), dim3(256), 0, s, w.partial, nblk, 128, grads + m->o_db);
     }
-    int fused_bn3_blocks = 0;          // > 0: conv4's data gradient already did layer 3's BatchNorm-backward reduction
-    for (int l = 3; l >= 1; --l) {
-        if (hook && l == 2) KWS_TRY(hook->fire(5, s));
-        const int C = kCh[l + 1];
-        const long M = (long)B * Hz[l] * Wz[l];
-        const float *da = l == 3 ? w.da4 : w.da[l];
-        BnCoef k = coef_of(w.coef[l], C);
-        int nblk, rows;
-        stat_grid(M, C, nblk, rows);
-        // the forward applied dropout to a[3]; its mask is re-derived from the seed here
-        const float rate = (l == 3 && seed != 0) ? 0.5f : 0.f;
-        // conv2 (split precision): g stays compact -- the routed value per pool window in place of da[1], the element index as
-        // a byte in the (dead by now) da[2] buffer -- and the clip data gradient rebuilds it while staging: 54 MB less to
-        // write here and 54 MB less to read there at B = 4096
-        const bool compact_g = l == 1 && cnn_compact_g2(m, mprec == 1);
-        if (pool[l]) {
-            const long NW = (long)B * (Hz[l] / 2) * (Wz[l] / 2);       // one thread per (pool window, channel)
-            stat_grid(NW, C, nblk, rows);
-            if (l == 1 && acc_bn2) ;                            // done by conv3_group_dgrad_kernel's epilogue
-            else if (l == 3 && acc_bn4) ;                       // done by dense_head_fused_kernel's epilogue
-            else if (compact_g && routed_bwd2)
-                KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", l + 1), bn_bwd_reduce_routed_kernel, dim3(nblk), dim3(256), 0, s, w.zmax2, w.da[1], k, NW, C,
-                           rows, w.partial);
-            else if (compact_g)
-                KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", l + 1), bn_bwd_reduce_pool_kernel<true>, dim3(nblk), dim3(256), 0, s, w.z[l], w.da[1], k,
-                           w.gz[l], B, Hz[l], Wz[l], C, rows, w.partial, rate, slo, shi, reinterpret_cast<unsigned char *>(w.da[2]));
-            else if (l == 3 && mprec == 1)
-                KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", l + 1), bn_bwd_reduce_routed_full_kernel, dim3(nblk), dim3(256), 0, s, w.zmax4, w.arg4, da, k,
-                           w.gz[l], B, Hz[l], Wz[l], C, rows, w.partial, rate, slo, shi);
-            else
-                KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", l + 1), bn_bwd_reduce_pool_kernel<false>, dim3(nblk), dim3(256), 0, s, w.z[l],
-                           const_cast<float *>(da), k, w.gz[l], B, Hz[l], Wz[l], C, rows, w.partial, rate, slo, shi);
-        } else if (l == 2 && fused_bn3_blocks > 0)
-            nblk = fused_bn3_blocks;
+    if (P.dense_fused) ;                        // da4 came out of dense_head_fused_kernel
+    else if (P.bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_DGRAD, EPI_NONE>("conv_bf16_dgrad", w.dd1, w.wsp[2], nullptr, w.da4, g, s));
+    else KWS_TRY(launch_dgrad<128, 128, 1>(w.dd1, params + m->o_dk, w.da4, g, s));
+    if (hook) KWS_TRY(hook->fire(3, s));
+    return KWS_OK;
+}
+
+// layer 4: BatchNorm backward (through dropout, the pool and ReLU6), conv4's weight gradient on the side stream, its data gradient
+int CnnCtx::bwd_layer4()
+{
+    const int C = 128, H = d.H3, W = d.W3;
+    const long M = pixels(3);
+    const BnCoef k = coef(3);
+    const float *gamma = params + m->o_g[3];
+    // the forward applied dropout to a[3]; its mask is re-derived from the seed here
+    const float rate = drop_rate();
+    int nblk, rows;
+    stat_grid((long)B * (H / 2) * (W / 2), C, nblk, rows);      // one thread per (pool window, channel)
+    if (P.acc_bn4) ;                        // done by dense_head_fused_kernel's epilogue
+    else if (P.bf16)
+        KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", 4), bn_bwd_reduce_routed_full_kernel, dim3(nblk), dim3(256), 0, s, w.zmax4, w.arg4, w.da4, k,
+                   w.gz[3], B, H, W, C, rows, w.partial, rate, slo(), shi());
+    else KWS_TRY(bwd_reduce_pool(3, H, W, C, w.da4, rate, nblk, rows));
+    if (!P.acc_bn4) KWS_TRY(bwd_bn_finalize(3, C, nblk));
+    bwd_arm(3);                          // the apply kernel below is the last one in front of fork(3)
+    const Bf16PlanesOut dzp{{w.dzp[0], w.dzp[1], w.dzp[2]}};
+    if (P.acc_bn4)
+        KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", 4), bn_bwd_apply_routed_planes_kernel<true>, dim3(std::min<unsigned>(1024u, blocks_for(M * C / 4, 256))),
+                   dim3(256), 0, s, w.z[3], w.da4, w.arg4, k, gamma, B, H, W, C, acc_out(3), dzp);
+    else if (P.bf16)
+        // split precision: dz4 leaves as bf16 h/m/l planes, which is what both of its consumers stage (no fp32 dz4)
+        KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", 4), bn_bwd_apply_planes_kernel<true>, dim3(blocks_for(M * C / 4, 256)), dim3(256), 0, s,
+                   w.z[3], w.gz[3], k, gamma, M * C / 4, C, dzp);
+    else
+        KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", 4), bn_bwd_apply_kernel<true>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[3], w.gz[3], k,
+                   gamma, M * C, C);
+    if (hook) KWS_TRY(hook->fire(4, s));
+    KWS_TRY(bwd_fork(3));                // dz4 is final: wgrad may start on the side stream
+    const float *in = w.a[2], *kern = params + m->o_k[3];
+    float *dk = grads + m->o_k[3];
+    const ConvGeom g = geom3x3(B, H, W, 1);
+    if (P.bf16 && P.a3_on_load)
+        KWS_TRY((launch_wgrad_bf16<64, 128, 1, true, true>(w.z[2], nullptr, dk, g, s2, w.dzp, P.det, coef(2).scale)));
+    else if (P.bf16) KWS_TRY(launch_wgrad_bf16<64, 128, 1, true>(in, nullptr, dk, g, s2, w.dzp, P.det));
+    else KWS_TRY(launch_wgrad<64, 128, 1>(in, w.gz[3], dk, g, s2, P.det));
+    // grads[o_k[3] ..] (conv4, bn4, dense, head = 82 % of the bytes) are final once the side stream gets here: it
+    // runs the dense and conv4 weight gradients in order and joined the caller's stream at fork(3), i.e. after
+    // head_bwd, the dense bias sums and BN4's backward.  The early bucket's all-reduce goes right here, on the side stream
+    // (the caller's stream does not wait for the conv4 wgrad, and the collective runs under the rest of the backward pass).
+    if (a->comm) KWS_TRY(comm_allreduce_early(a->comm, grads + m->o_k[3], m->P - m->o_k[3], s2));
+    if (a->bucket_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->bucket_event), s2));
+    if (P.group) {
+        fused_bn3_blocks = launch_group_dgrad4(m, B, w, s, P.acc_bn3 ? acc_set(R, 1, 2, bpar[2]) : nullptr);
+        if (fused_bn3_blocks < 0) return fused_bn3_blocks;
+    } else if (P.bf16 && blocks_for(M, 64) <= (unsigned)kStatStride) {
+        // the data gradient's epilogue is BatchNorm 3's backward reduction (conv3 has no pooling): it gates by ReLU6(y3), stores
+        // g in gz[2] and leaves the partial sums of g and g xhat -- no bn_bwd_reduce pass over (z3, da3)
+        const BnCoef k3 = coef(2);
+        fused_bn3_blocks = launch_bf16<128, 64, MODE_DGRAD, EPI_BNBWD_GATE6>("conv_bf16_dgrad", nullptr, w.wsp[1], k3.scale, w.gz[2], g, s, w.partial,
+                                                                             w.z[2], w.dzp);
+        if (fused_bn3_blocks < 0) return fused_bn3_blocks;
+    } else if (P.bf16)
+        KWS_TRY_NB(launch_bf16<128, 64, MODE_DGRAD, EPI_NONE>("conv_bf16_dgrad", nullptr, w.wsp[1], nullptr, w.da[2], g, s, nullptr, nullptr, w.dzp));
+    else KWS_TRY(launch_dgrad<128, 64, 1>(w.gz[3], kern, w.da[2], g, s));
+    return KWS_OK;
+}
+
+// layer 3: BatchNorm backward (no pooling), conv3's weight gradient on the side stream, its data gradient
+int CnnCtx::bwd_layer3()
+{
+    const int C = 64, H = d.H3, W = d.W3;
+    if (hook) KWS_TRY(hook->fire(5, s));
+    const long M = pixels(2);
+    const BnCoef k = coef(2);
+    const float *gamma = params + m->o_g[2];
+    int nblk, rows;
+    stat_grid(M, C, nblk, rows);
+    if (fused_bn3_blocks > 0) nblk = fused_bn3_blocks;
+    else
+        KWS_LAUNCH(prof_name("bn_bwd_reduce_kernel", 3), bn_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, s, w.z[2], w.da[2], k, w.gz[2], B, H, W, C,
+                   rows, w.partial, 0.f, slo(), shi());
+    // acc_bn3 (implies the group data gradient of conv4, which put the sums into the accumulator set): the apply kernel derives the coefficients
+    if (!P.acc_bn3) KWS_TRY(bwd_bn_finalize(2, C, nblk));
+    bwd_arm(2);                          // the apply kernel below is the last one in front of fork(2)
+    if (P.acc_bn3)
+        KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", 3), bn_bwd_apply_acc_kernel<false>, dim3(std::min<unsigned>(1024u, blocks_for(M * C / 4, 256))), dim3(256), 0, s,
+                   w.z[2], w.gz[2], k, gamma, M * C / 4, C, acc_out(2));
+    else
+        KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", 3), bn_bwd_apply_kernel<false>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[2], w.gz[2], k,
+                   gamma, M * C, C);
+    KWS_TRY(bwd_fork(2));                // dz3 is final: wgrad may start on the side stream
+    const float *in = w.a[1], *kern = params + m->o_k[2];
+    float *dk = grads + m->o_k[2];
+    const ConvGeom g = geom3x3(B, d.H2, d.W2, 2);
+    if (P.bf16) KWS_TRY(launch_wgrad_bf16<32, 64, 3>(in, w.gz[2], dk, g, s2, nullptr, P.det));
+    else KWS_TRY(launch_wgrad<32, 64, 3>(in, w.gz[2], dk, g, s2, P.det));
+    if (P.group) {
+        if (P.acc_bn2) bwd_arm(1);       // the last kernel in front of conv2's early weight-gradient fork
+        KWS_TRY(launch_group_dgrad3(m, B, w, s, P.acc_bn2 ? acc_set(R, 1, 1, bpar[1]) : nullptr));
+    }
+    else KWS_TRY(launch_dgrad<64, 32, 2>(w.gz[2], kern, w.da[1], g, s));
+    return KWS_OK;
+}
+
+// layer 2: BatchNorm backward reduction; its apply step is fused into the staging of conv2's clip-resident gradient kernels
+int CnnCtx::bwd_layer2()
+{
+    const int C = 32, H1 = d.H1, W1 = d.W1;
+    const long M = pixels(1);
+    const BnCoef k = coef(1);
+    // compact_g2: g stays compact -- the routed value per pool window in place of da[1], the element index as a byte (arg2, or the dead by
+    // now da[2] buffer without the routing tables) -- and the clip data gradient rebuilds it while staging: 54 MB less to
+    // write here and 54 MB less to read there at B = 4096
+    const long NW = (long)B * (H1 / 2) * (W1 / 2);       // one thread per (pool window, channel)
+    int nblk, rows;
+    stat_grid(NW, C, nblk, rows);
+    if (P.acc_bn2) ;                        // done by conv3_group_dgrad_kernel's epilogue
+    else if (P.compact_g2 && P.routed_g2)
+        KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", 2), bn_bwd_reduce_routed_kernel, dim3(nblk), dim3(256), 0, s, w.zmax2, w.da[1], k, NW, C,
+                   rows, w.partial);
+    else if (P.compact_g2)
+        KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", 2), bn_bwd_reduce_pool_kernel<true>, dim3(nblk), dim3(256), 0, s, w.z[1], w.da[1], k,
+                   w.gz[1], B, H1, W1, C, rows, w.partial, 0.f, slo(), shi(), reinterpret_cast<unsigned char *>(w.da[2]));
+    else KWS_TRY(bwd_reduce_pool(1, H1, W1, C, w.da[1], 0.f, nblk, rows));
+    // acc_bn2: the consumers derive k2 / k3 themselves (fork(1) was armed in front of conv3's data gradient)
+    if (!P.acc_bn2) {
+        if (P.wgrad2_early) bwd_arm(1);  // conv2's early weight gradient forks right behind this finalize kernel
+        KWS_TRY(bwd_bn_finalize(1, C, nblk));
+    }
+    const float *in = w.a[0], *kern = params + m->o_k[1];
+    float *dk = grads + m->o_k[1];
+    const Conv2Clip cc = conv2_clip(d, B);
+    BnBwdArgs bn = {w.z[1], params + m->o_g[1], k.mean, k.inv, k.k2, k.k3};
+    if (P.compact_g2) { bn.gw = w.da[1]; bn.arg = P.routed_g2 ? w.arg2 : reinterpret_cast<const unsigned char *>(w.da[2]); }
+    BnBwdArgs bn_w = bn;                                // the weight gradient's copy: it only reads the accumulator set
+    if (P.acc_bn2) {
+        bn.acc = bn_w.acc = acc_set(R, 1, 1, bpar[1]);
+        bn.M = bn_w.M = M;
+        bn.acc_clear_set = acc_set(R, 1, 1, bpar[1] + 1);
+        bn.dgamma = grads + m->o_g[1]; bn.dbeta = grads + m->o_b[1]; bn.k2w = k.k2; bn.k3w = k.k3;
+    }
+    // two blocks per CU although three fit: the third takes the LDS the layer-1 kernels of the main chain need beside it
+    // (same-box A/B: 0.785 ms/step with one or two, 0.800 with three); deterministic: one persistent block walks every clip
+    auto wgrad_grid = [&](int occ) { return dim3(P.det ? 1u : cc.even_grid(cu_count() * std::min(occ, 2))); };
+    // wgrad2_early: the weight gradient forms dz itself (from the routed g and z2), so it forks BEFORE the data gradient and runs beside it
+    // and beside layer 1 on the side stream; the data gradient then does not write dz back
+    if (P.wgrad2_early) {
+        KWS_TRY(bwd_fork(1));
+        static const int occ = resident_blocks(conv_wgrad_clip_bf16_kernel<true>, 256, cc.smwb);
+        arm_stop_event(R->ev[9], s2);                 // the last kernel of the side stream: its completion is the join event
+        KWS_LAUNCH("conv_wgrad_clip_bf16<16,32>", conv_wgrad_clip_bf16_kernel<true>, wgrad_grid(occ), dim3(256), cc.smwb, s2, in, nullptr, dk, B, H1, W1, bn_w);
+    }
+    if (P.bf16) {
+        const dim3 grid(cc.even_grid(cu_count() * 2));
+        if (P.wgrad2_early)
+            KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv_dgrad_clip_bf16_kernel<true, true, false>), grid, dim3(256), cc.smdb, s,
+                       w.gz[1], kern, w.da[0], B, H1, W1, bn);
+        else if (P.compact_g2)
+            KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv_dgrad_clip_bf16_kernel<true, true>), grid, dim3(256), cc.smdb, s,
+                       w.gz[1], kern, w.da[0], B, H1, W1, bn);
         else
-            KWS_LAUNCH(prof_name("bn_bwd_reduce_kernel", l + 1), bn_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, s, w.z[l], da, k, w.gz[l], B, Hz[l], Wz[l], C,
-                       rows, w.partial, rate, slo, shi);
-        // conv2's early weight gradient forks right behind this finalize kernel
-        const bool wgrad_early_l1 = compact_g && Hs[1] * Ws[1] <= 160 && Hs[1] * Ws[1] * 8 <= 1280 && Hs[1] * Ws[1] * 4 <= 768;
-        const bool acc_l = (l == 1 && acc_bn2) || (l == 2 && acc_bn3 && fused_bn3_blocks > 0) || (l == 3 && acc_bn4);
-        const BnAccBwd ab{acc_set(R, 1, l, bpar[l]), acc_set(R, 1, l, bpar[l] + 1), M, grads + m->o_g[l], grads + m->o_b[l]};
-        if (acc_l) ;                                            // the consumers derive k2 / k3 themselves (layer 2: fork(1) was armed in front of conv3's data gradient)
-        else {
-            if (l == 1 && wgrad_early_l1) arm(1);
-            KWS_LAUNCH(prof_name("bn_bwd_finalize_kernel", l + 1), bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, M, C, params + m->o_g[l],
-                       grads + m->o_g[l], grads + m->o_b[l], k);
-        }
-        if (l != 1) arm(l);                                 // the apply kernel below is the last one in front of fork(l)
-        if (l == 1)
-            ;                                                   // fused into conv_dgrad_clip's staging below
-        else if (l == 3 && acc_bn4)
-            KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", l + 1), bn_bwd_apply_routed_planes_kernel<true>, dim3(std::min<unsigned>(1024u, blocks_for(M * C / 4, 256))),
-                       dim3(256), 0, s, w.z[l], w.da4, w.arg4, k, params + m->o_g[l], B, Hz[l], Wz[l], C, ab, (Bf16PlanesOut{{w.dzp[0], w.dzp[1], w.dzp[2]}}));
-        else if (l == 2 && acc_l)
-            KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", l + 1), bn_bwd_apply_acc_kernel<false>, dim3(std::min<unsigned>(1024u, blocks_for(M * C / 4, 256))), dim3(256), 0, s,
-                       w.z[l], w.gz[l], k, params + m->o_g[l], M * C / 4, C, ab);
-        else if (l == 3 && mprec == 1)
-            // split precision: dz4 leaves as bf16 h/m/l planes, which is what both of its consumers stage (no fp32 dz4)
-            KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", l + 1), bn_bwd_apply_planes_kernel<true>, dim3(blocks_for(M * C / 4, 256)), dim3(256), 0, s,
-                       w.z[l], w.gz[l], k, params + m->o_g[l], M * C / 4, C, (Bf16PlanesOut{{w.dzp[0], w.dzp[1], w.dzp[2]}}));
-        else if (l == 3)
-            KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", l + 1), bn_bwd_apply_kernel<true>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[l], w.gz[l], k,
-                       params + m->o_g[l], M * C, C);
+            KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv_dgrad_clip_bf16_kernel<true, false>), grid, dim3(256), cc.smdb, s,
+                       w.gz[1], kern, w.da[0], B, H1, W1, bn);
+    } else
+        // at most the LDS-limited residency: 5 blocks per CU (3 for the weight gradient below)
+        KWS_LAUNCH("conv_dgrad_clip<32,16>", (conv_dgrad_clip_kernel<32, true>), dim3(cc.even_grid(cu_count() * 5)), dim3(256), cc.smd, s, w.gz[1], kern, w.da[0],
+                   B, H1, W1, bn);
+    if (P.wgrad2_early) return KWS_OK;
+    KWS_TRY(bwd_fork(1));
+    if (P.wgrad2_bf16) {
+        static const int occ = resident_blocks(conv_wgrad_clip_bf16_kernel<false>, 256, cc.smwb);
+        KWS_LAUNCH("conv_wgrad_clip_bf16<16,32>", conv_wgrad_clip_bf16_kernel<false>, wgrad_grid(occ), dim3(256), cc.smwb, s2, in, w.gz[1], dk, B, H1, W1, bn);
+    } else
+        KWS_LAUNCH("conv_wgrad_clip<16,32>", conv_wgrad_clip_kernel<32>, dim3(P.det ? 1u : cc.even_grid(cu_count() * 3)), dim3(256), cc.smw, s2, in, w.gz[1], dk,
+                   B, H1, W1);
+    return KWS_OK;
+}
+
+// layer 1: da1 -> (dgamma1, dbeta1, dW1) with conv1 recomputed; no z1-sized tensor is read or written
+int CnnCtx::bwd_layer1()
+{
+    const L1Geom g = l1_geom(d, B, P);
+    BnCoef k1 = coef(0);
+    const float *kern1 = params + m->o_k[0];
+    if (P.l1m) {
+        // one pass collects G, sum g, sum g z per block (double partials, fixed order); the closed forms of dW1, dgamma, dbeta use Q
+        const double *q = moments ? moments : w.moments;
+        // the default map (30 frames x 20 coefficients) has a fully unrolled form with its own window walk (kws_layer1_fast.h)
+        // non-deterministic mode, default map: the kernel's last block evaluates the closed forms itself (no finalize launch); layer 0's
+        // backward set of the model's accumulators holds the sums, its last word the ticket counter (kAccSlots * kL1BwdRows < kAccDoubles)
+        if (P.l1_fin_in_kernel) {
+            double *acc0 = acc_set(R, 1, 0, 0);
+            const L1FinalizeArgs fin{acc0, reinterpret_cast<unsigned *>(acc0 + kAccDoubles - 1), q, params + m->o_g[0], grads + m->o_k[0],
+                                     grads + m->o_g[0], grads + m->o_b[0]};
+            KWS_LAUNCH("l1m_bwd_onepass_kernel", (l1f_bwd_onepass_kernel<30, 20>), dim3(g.nbm), dim3(256), g.smemm, s, feat, kern1, w.da[0], k1, B, g.cpw, w.partial, fin);
+        } else if (P.l1_default_map)
+            KWS_LAUNCH("l1m_bwd_onepass_kernel", (l1f_bwd_onepass_kernel<30, 20>), dim3(g.nbm), dim3(256), g.smemm, s, feat, kern1, w.da[0], k1, B, g.cpw, w.partial);
         else
-            KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", l + 1), bn_bwd_apply_kernel<false>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[l], w.gz[l], k,
-                       params + m->o_g[l], M * C, C);
-        const float *in = w.a[l - 1];
-        float *dk = grads + m->o_k[l];
-        const float *kern = params + m->o_k[l];
-        if (hook && l == 3) KWS_TRY(hook->fire(4, s));
-        if (l != 1)
-            if (int rc = fork(l)) return rc;                   // dz of layer l is final: wgrad may start on the side stream
-        if (l == 3) {
-            const ConvGeom g = geom3x3(B, Hs[3], Ws[3], 1);
-            if (mprec == 1 && cnn_a3_on_load(m, true, true))
-                KWS_TRY((launch_wgrad_bf16<64, 128, 1, true, true>(w.z[2], nullptr, dk, g, s2, w.dzp, det, coef_of(w.coef[2], 64).scale)));
-            else if (mprec == 1) KWS_TRY(launch_wgrad_bf16<64, 128, 1, true>(in, nullptr, dk, g, s2, w.dzp, det));
-            else KWS_TRY(launch_wgrad<64, 128, 1>(in, w.gz[3], dk, g, s2, det));
-            // grads[o_k[3] ..] (conv4, bn4, dense, head = 82 % of the bytes) are final once the side stream gets here: it
-            // runs the dense and conv4 weight gradients in order and joined the caller's stream at fork(3), i.e. after
-            // head_bwd, the dense bias sums and BN4's backward.  The early bucket's all-reduce goes right here, on the side stream
-            // (the caller's stream does not wait for the conv4 wgrad, and the collective runs under the rest of the backward pass).
-            if (comm) KWS_TRY(comm_allreduce_early(comm, grads + m->o_k[3], m->P - m->o_k[3], s2));
-            if (bucket_event) KWS_HIP_CHECK(hipEventRecord(bucket_event, s2));
-            if (group_bwd) {
-                fused_bn3_blocks = launch_group_dgrad4(m, B, w, s, acc_bn3 ? acc_set(R, 1, 2, bpar[2]) : nullptr);
-                if (fused_bn3_blocks < 0) return fused_bn3_blocks;
-            } else if (mprec == 1 && blocks_for((long)B * Hs[3] * Ws[3], 64) <= (unsigned)kStatStride) {
-                // the data gradient's epilogue is BatchNorm 3's backward reduction (conv3 has no pooling): it gates by ReLU6(y3), stores
-                // g in gz[2] and leaves the partial sums of g and g xhat -- no bn_bwd_reduce pass over (z3, da3)
-                const BnCoef k3 = coef_of(w.coef[2], 64);
-                fused_bn3_blocks = launch_bf16<128, 64, MODE_DGRAD, EPI_BNBWD_GATE6>("conv_bf16_dgrad", nullptr, w.wsp[1], k3.scale, w.gz[2], g, s, w.partial,
-                                                                                   w.z[2], w.dzp);
-                if (fused_bn3_blocks < 0) return fused_bn3_blocks;
-            } else if (mprec == 1)
-                KWS_TRY_NB(launch_bf16<128, 64, MODE_DGRAD, EPI_NONE>("conv_bf16_dgrad", nullptr, w.wsp[1], nullptr, w.da[2], g, s, nullptr, nullptr, w.dzp));
-            else KWS_TRY(launch_dgrad<128, 64, 1>(w.gz[3], kern, w.da[2], g, s));
-        } else if (l == 2) {
-            const ConvGeom g = geom3x3(B, Hs[2], Ws[2], 2);
-            if (mprec == 1) KWS_TRY(launch_wgrad_bf16<32, 64, 3>(in, w.gz[2], dk, g, s2, nullptr, det));
-            else KWS_TRY(launch_wgrad<32, 64, 3>(in, w.gz[2], dk, g, s2, det));
-            if (group_bwd) {
-                if (acc_bn2) arm(1);                            // the last kernel in front of conv2's early weight-gradient fork
-                KWS_TRY(launch_group_dgrad3(m, B, w, s, acc_bn2 ? acc_set(R, 1, 1, bpar[1]) : nullptr));
-            }
-            else KWS_TRY(launch_dgrad<64, 32, 2>(w.gz[2], kern, w.da[1], g, s));
-        } else {
-            // conv2 (16 -> 32, 3x3, stride 1): clip-resident kernels, the clip's tiles are staged in LDS once
-            const int H1 = Hs[1], W1 = Ws[1];
-            // persistent grids: at most the LDS-limited residency (3 resp. 5 blocks per CU), with an equal share of clips each
-            auto even_grid = [&](int max_blocks) { const int cpb = (B + max_blocks - 1) / max_blocks; return (unsigned)((B + cpb - 1) / cpb); };
-            const unsigned nblk = even_grid(cu_count() * 3), nblk_d = even_grid(cu_count() * 5);
-            const size_t smw = sizeof(float) * ((size_t)(H1 + 2) * (W1 + 2) * 16 + (size_t)((H1 * W1 + 3) / 4) * 4 * stride16(32));
-            const size_t smw2 = std::max(smw, sizeof(float) * (size_t)(1024 + 16 * 32));
-            // dgrad forms dz2 from (g, z2) while staging and leaves it in gz[1]; wgrad then overlaps with layer 1's kernels
-            const size_t smd = sizeof(float) * (size_t)(H1 + 2) * (W1 + 2) * (32 + 4);
-            BnBwdArgs bn = {w.z[1], params + m->o_g[1], k.mean, k.inv, k.k2, k.k3};
-            if (compact_g) { bn.gw = w.da[1]; bn.arg = routed_bwd2 ? w.arg2 : reinterpret_cast<const unsigned char *>(w.da[2]); }
-            BnBwdArgs bn_w = bn;                                // the weight gradient's copy: it only reads the accumulator set
-            if (acc_bn2) {
-                bn.acc = bn_w.acc = acc_set(R, 1, 1, bpar[1]);
-                bn.M = bn_w.M = M;
-                bn.acc_clear_set = acc_set(R, 1, 1, bpar[1] + 1);
-                bn.dgamma = grads + m->o_g[1]; bn.dbeta = grads + m->o_b[1]; bn.k2w = k.k2; bn.k3w = k.k3;
-            }
-            const bool wgrad_bf16 = mprec == 1 && H1 * W1 <= 160;
-            // compact g and a clip that fits the kernels' register staging: the weight gradient forms dz itself (from the routed g
-            // and z2), so it forks BEFORE the data gradient and runs beside it and beside layer 1 on the side stream; the data
-            // gradient then does not write dz back
-            const bool wgrad_early = compact_g && wgrad_bf16 && H1 * W1 * 8 <= 1280 && H1 * W1 * 4 <= 768;
-            const size_t smwb = std::max((size_t)3 * 32 * (H1 + 2) * (W1 + 2) + (size_t)6 * 32 * (H1 * W1 + 1), sizeof(float) * 9 * 16 * 32);
-            // two blocks per CU although three fit: the third takes the LDS the layer-1 kernels of the main chain need beside it
-            // (same-box A/B: 0.785 ms/step with one or two, 0.800 with three); deterministic: one persistent block walks every clip
-            auto wgrad_grid = [&](int occ) { return dim3(det ? 1u : even_grid(cu_count() * std::min(occ, 2))); };
-            if (wgrad_early) {
-                if (int rc = fork(1)) return rc;
-                static const int occ = resident_blocks(conv_wgrad_clip_bf16_kernel<true>, 256, smwb);
-                if (!no_arm) arm_stop_event(R->ev[9], s2);       // the last kernel of the side stream: its completion is the join event
-                KWS_LAUNCH("conv_wgrad_clip_bf16<16,32>", conv_wgrad_clip_bf16_kernel<true>, wgrad_grid(occ), dim3(256), smwb, s2, in, nullptr, dk, B, H1, W1, bn_w);
-            }
-            if (mprec == 1) {
-                // split-precision form: 2 blocks per CU by registers (the weight fragments of all nine taps stay in them)
-                const size_t smdb = (size_t)12 * 16 * (((H1 + 2) * (W1 + 2) + 15) & ~15);
-                if (wgrad_early)
-                    KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv_dgrad_clip_bf16_kernel<true, true, false>), dim3(even_grid(cu_count() * 2)), dim3(256), smdb, s,
-                               w.gz[1], kern, w.da[0], B, H1, W1, bn);
-                else if (compact_g)
-                    KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv_dgrad_clip_bf16_kernel<true, true>), dim3(even_grid(cu_count() * 2)), dim3(256), smdb, s,
-                               w.gz[1], kern, w.da[0], B, H1, W1, bn);
-                else
-                    KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv_dgrad_clip_bf16_kernel<true, false>), dim3(even_grid(cu_count() * 2)), dim3(256), smdb, s,
-                               w.gz[1], kern, w.da[0], B, H1, W1, bn);
-            } else
-                KWS_LAUNCH("conv_dgrad_clip<32,16>", (conv_dgrad_clip_kernel<32, true>), dim3(nblk_d), dim3(256), smd, s, w.gz[1], kern, w.da[0], B, H1, W1, bn);
-            if (wgrad_early) {
-                ;
-            } else if (wgrad_bf16) {
-                if (int rc = fork(1)) return rc;
-                static const int occ = resident_blocks(conv_wgrad_clip_bf16_kernel<false>, 256, smwb);
-                KWS_LAUNCH("conv_wgrad_clip_bf16<16,32>", conv_wgrad_clip_bf16_kernel<false>, wgrad_grid(occ), dim3(256), smwb, s2, in, w.gz[1], dk, B, H1, W1, bn);
-            } else {
-                if (int rc = fork(1)) return rc;
-                KWS_LAUNCH("conv_wgrad_clip<16,32>", conv_wgrad_clip_kernel<32>, dim3(det ? 1u : nblk), dim3(256), smw2, s2, in, w.gz[1], dk, B, H1, W1);
-            }
-        }
+            KWS_LAUNCH("l1m_bwd_onepass_kernel", l1m_bwd_onepass_kernel, dim3(g.nbm), dim3(256), g.smemm, s, feat, kern1, w.da[0], k1, B, d.H0, d.W0, g.cpw,
+                       w.partial);
+        if (!P.l1_fin_in_kernel)
+            KWS_LAUNCH("l1_bwd_finalize_moments_kernel", l1_bwd_finalize_moments_kernel, dim3(144 + 16), dim3(64), 0, s, w.partial, g.nbm, q, kern1,
+                       params + m->o_g[0], k1, grads + m->o_k[0], grads + m->o_g[0], grads + m->o_b[0]);
+    } else {
+        KWS_LAUNCH("l1_bwd_reduce_kernel", l1_bwd_reduce_kernel<16>, dim3(g.nb), dim3(256), g.smem1, s, feat, kern1, w.da[0], k1, B, d.H0, d.W0,
+                   g.cpb, w.partial);
+        KWS_TRY(bwd_bn_finalize(0, 16, g.nb));
+        KWS_LAUNCH("l1_bwd_wgrad_kernel", l1_bwd_wgrad_kernel<16>, dim3(P.det ? 1 : g.nb), dim3(256), g.smem1, s, feat, kern1, w.da[0], k1, params + m->o_g[0],
+                   grads + m->o_k[0], B, d.H0, d.W0, P.det ? B : g.cpb);
     }
-    // layer 1: da1 -> (dgamma1, dbeta1, dW1) with conv1 recomputed; no z1-sized tensor is read or written
-    {
-        const int cpb = std::max(1, (B + kMaxStatBlocks - 1) / kMaxStatBlocks), nb = (B + cpb - 1) / cpb;
-        const size_t smem1 = sizeof(float) * (size_t)(d.H0 + 2) * (d.W0 + 2);
-        // every pixel in a pool window, a haloed map of at most 768 floats and at most 40 tiles: the MFMA, wave-per-clip forms
-        const bool l1m = d.H0 % 2 == 0 && d.W0 % 2 == 0 && (d.H0 + 2) * (d.W0 + 2) <= 64 * kL1Stage &&
-                         (d.H0 / 2) * (d.W0 / 2) <= 4 * kL1MaxTiles;
-        const int cpw = std::max(1, (B + 4 * kMaxStatBlocks - 1) / (4 * kMaxStatBlocks)), nbm = (B + 4 * cpw - 1) / (4 * cpw);
-        // per-wave LDS tiles; the compile-time form of the default map reads two rows past the haloed map (kws_layer1.h: L1Runs)
-        const size_t smemm = sizeof(float) * 4 * (d.H0 == 30 && d.W0 == 20 ? (size_t)L1Runs<30, 20>::TILE : (size_t)((((d.H0 + 2) * (d.W0 + 2)) + 3) & ~3));
-        const long M1 = (long)B * d.H0 * d.W0;
-        BnCoef k1 = coef_of(w.coef[0], 16);
-        const float *kern1 = params + m->o_k[0];
-        if (l1m) {
-            // one pass collects G, sum g, sum g z per block (double partials, fixed order); the closed forms of dW1, dgamma, dbeta use Q
-            const double *q = moments ? moments : w.moments;
-            // the default map (30 frames x 20 coefficients) has a fully unrolled form with its own window walk (kws_layer1_fast.h)
-            // non-deterministic mode, default map: the kernel's last block evaluates the closed forms itself (no finalize launch); layer 0's
-            // backward set of the model's accumulators holds the sums, its last word the ticket counter (kAccSlots * kL1BwdRows < kAccDoubles)
-            const bool fin_in_kernel = acc_ok && d.H0 == 30 && d.W0 == 20;
-            if (fin_in_kernel) {
-                double *acc0 = acc_set(R, 1, 0, 0);
-                const L1FinalizeArgs fin{acc0, reinterpret_cast<unsigned *>(acc0 + kAccDoubles - 1), q, params + m->o_g[0], grads + m->o_k[0],
-                                         grads + m->o_g[0], grads + m->o_b[0]};
-                KWS_LAUNCH("l1m_bwd_onepass_kernel", (l1f_bwd_onepass_kernel<30, 20>), dim3(nbm), dim3(256), smemm, s, feat, kern1, w.da[0], k1, B, cpw, w.partial, fin);
-            } else if (d.H0 == 30 && d.W0 == 20)
-                KWS_LAUNCH("l1m_bwd_onepass_kernel", (l1f_bwd_onepass_kernel<30, 20>), dim3(nbm), dim3(256), smemm, s, feat, kern1, w.da[0], k1, B, cpw, w.partial);
-            else
-                KWS_LAUNCH("l1m_bwd_onepass_kernel", l1m_bwd_onepass_kernel, dim3(nbm), dim3(256), smemm, s, feat, kern1, w.da[0], k1, B, d.H0, d.W0, cpw,
-                           w.partial);
-            if (!fin_in_kernel)
-                KWS_LAUNCH("l1_bwd_finalize_moments_kernel", l1_bwd_finalize_moments_kernel, dim3(144 + 16), dim3(64), 0, s, w.partial, nbm, q, kern1,
-                           params + m->o_g[0], k1, grads + m->o_k[0], grads + m->o_g[0], grads + m->o_b[0]);
-        } else {
-            KWS_LAUNCH("l1_bwd_reduce_kernel", l1_bwd_reduce_kernel<16>, dim3(nb), dim3(256), smem1, s, feat, kern1, w.da[0], k1, B, d.H0, d.W0,
-                       cpb, w.partial);
-            KWS_LAUNCH(prof_name("bn_bwd_finalize_kernel", 1), bn_bwd_finalize_kernel, dim3(16), dim3(64), 0, s, w.partial, nb, M1, 16,
-                       params + m->o_g[0], grads + m->o_g[0], grads + m->o_b[0], k1);
-            KWS_LAUNCH("l1_bwd_wgrad_kernel", l1_bwd_wgrad_kernel<16>, dim3(det ? 1 : nb), dim3(256), smem1, s, feat, kern1, w.da[0], k1, params + m->o_g[0],
-                       grads + m->o_k[0], B, d.H0, d.W0, det ? B : cpb);
-        }
-    }
+    return KWS_OK;
+}
+
+int CnnCtx::backward()
+{
+    const DisarmOnExit disarm_guard;        // no armed fork event outlives this call, whichever way it returns
+    // split precision: the forward pass cleared the gradient buffer beside the weight split (fwd_prepare, or the PREP blocks of layer 1)
+    if (!P.bf16) KWS_HIP_CHECK(hipMemsetAsync(grads, 0, sizeof(float) * (size_t)m->P, s));
+    // parity of each layer's sets: flipped only by a pass that uses them (its consumer is what clears the other parity)
+    bpar[1] = P.acc_bn2 ? R->acc_uses[1][1]++ : 0u;
+    bpar[2] = P.acc_bn3 ? R->acc_uses[1][2]++ : 0u;
+    bpar[3] = P.acc_bn4 ? R->acc_uses[1][3]++ : 0u;
+    KWS_TRY(acc_make_clean(R, s));
+    R->acc_dirty = true;               // until every kernel of this pass is enqueued
+    KWS_TRY(bwd_head_dense());
+    KWS_TRY(bwd_layer4());
+    KWS_TRY(bwd_layer3());
+    KWS_TRY(bwd_layer2());
+    KWS_TRY(bwd_layer1());
     if (!stop_event_bound(R->ev[9])) KWS_HIP_CHECK(hipEventRecord(R->ev[9], s2));   // join: every wgrad is part of the caller's stream order again
     KWS_HIP_CHECK(hipStreamWaitEvent(s, R->ev[9], 0));
     KWS_LAUNCH_CHECK("simple_cnn backward");
@@ -1451,7 +1487,11 @@ int kws_model_prepare_inference(kws_model *m, int B, const float *params, const 
     if (int rc = check_ws(m, B, false, ws, ws_bytes, w)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     KWS_TRY(infer_coefs(m, params, state, w, s));
-    if (m->kind == KWS_SIMPLE_CNN && matrix_prec(m) == 1) KWS_TRY(fused_tail_ok(m, true) ? split_weights_fused(m, params, w, s) : split_weights(m, params, w, s));
+    if (m->kind == KWS_SIMPLE_CNN && matrix_prec(m) == 1) {
+        // the planes the prepared forward will read: the plan of an inference call that takes the head's outputs (kws_model_forward)
+        const CnnPlan plan = plan_cnn(m, B, matrix_prec(m), false, false, true, false);
+        KWS_TRY(plan.fused_tail ? split_weights_fused(m, params, w, s) : split_weights(m, params, w, s));
+    }
     if (m->kind == KWS_SIMPLE_CNN_LITE && infer_prec(m) == KWS_INFER_FP16)
         KWS_LAUNCH("lite_f16_prepare_kernel", lite_f16_prepare_kernel, dim3(32), dim3(256), 0, s, params + m->o_pwk[2], params + m->o_pwk[3],
                    params + m->o_dk, params + m->o_hk, m->C, m->d.flat, reinterpret_cast<_Float16 *>(w.partial));
@@ -1614,11 +1654,15 @@ int kws_model_forward(kws_model *m, const float *feat, int B, const float *param
     if (m->prep.ws == ws && !m->prepared_for(params, state, ws, B, matrix_prec(m), infer_prec(m))) m->prep = kws_model::Prepared{};
     if (m->kind == KWS_SIMPLE_CNN_LITE && infer_prec(m) == KWS_INFER_FP16)
         return lite_forward_f16(m, feat, B, params, state, w, probs, argmax, s);
-    bool head_done = false;
-    rc = m->kind == KWS_SIMPLE_CNN_LITE ? lite_forward(m, feat, B, params, const_cast<float *>(state), w, false, 0, s)
-                                        : cnn_forward(m, feat, B, params, const_cast<float *>(state), w, false, 0, s, nullptr, nullptr, nullptr, nullptr,
-                                                      probs, argmax, &head_done);
-    if (rc || head_done) return rc;
+    if (m->kind == KWS_SIMPLE_CNN_LITE) rc = lite_forward(m, feat, B, params, const_cast<float *>(state), w, false, 0, s);
+    else {
+        // no path of the inference forward depends on the stream's capture state
+        const CnnPlan plan = plan_cnn(m, B, matrix_prec(m), false, false, true, m->prepared_for(params, state, ws, B, matrix_prec(m), infer_prec(m)));
+        CnnCtx c{m, m->d, B, feat, params, const_cast<float *>(state), nullptr, w, nullptr, s, nullptr, plan, nullptr, 0, nullptr, nullptr, probs, argmax};
+        rc = c.forward();
+        if (plan.fused_tail) return rc;     // conv3 .. softmax ran as one kernel
+    }
+    if (rc) return rc;
     return run_head(m, B, params, w.d1, w.loss_i, w.correct_i, nullptr, nullptr, probs, argmax, nullptr, 0.f, nullptr, 0, s);
 }
 
@@ -1638,7 +1682,6 @@ int kws_model_train_fwd_bwd(kws_model *m, const kws_train_args *a, void *stream)
     m->prep = kws_model::Prepared{};       // a train step rewrites the BatchNorm coefficients (and is followed by a weight update)
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool lite = m->kind == KWS_SIMPLE_CNN_LITE;
-    bool grads_zeroed = false;     // cleared beside the weight split (the main chain joins that branch before conv3)
     // point 0 = behind the last forward convolution (simple_cnn); swept again with the persistent featurizer (same box, ms/step):
     // 0: 0.722, behind the loss 0.753, behind the head's backward 0.721, behind the dense data gradient 0.734, behind BN4's
     // backward 0.760, behind conv4's data gradient 0.727
@@ -1655,16 +1698,20 @@ int kws_model_train_fwd_bwd(kws_model *m, const kws_train_args *a, void *stream)
     // the featurizer's persistent blocks (62 KB of LDS per CU) then run beside conv4's forward, the activation and the Dense + head kernel,
     // which fit beside them, and are gone when conv4's data gradient needs 147 KB of every CU.
     hook.at = lite ? 1 : (m->overlap_point >= 0 ? m->overlap_point : 10);     // kws_model_set_overlap_point re-runs the sweep
-    rc = lite ? lite_forward(m, a->feat, a->B, a->params, a->state, w, true, a->dropout_seed, s)
-              : cnn_forward(m, a->feat, a->B, a->params, a->state, w, true, a->dropout_seed, s, a->grads, &grads_zeroed, &hook, a->feat_moments);
+    // simple_cnn: ONE plan for both passes (kws_cnn_plan.h); the stream's capture state is queried here, once
+    ModelRes *R = nullptr;
+    if (!lite && !(R = m->dev_res())) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
+    const CnnPlan plan = lite ? CnnPlan{} : plan_cnn(m, a->B, matrix_prec(m), true, stream_is_capturing(s), false, false);
+    CnnCtx c{m, m->d, a->B, a->feat, a->params, a->state, a->grads, w, R, s, R ? R->side : nullptr, plan, &hook, a->dropout_seed, a->feat_moments, a};
+    rc = lite ? lite_forward(m, a->feat, a->B, a->params, a->state, w, true, a->dropout_seed, s) : c.forward();
     if (rc) return rc;
     if (lite) KWS_TRY(hook.fire(1, s));
     // Keras reduces the per-sample losses with a batch mean (train.py:75-77): d(mean)/d(logits) carries 1/B
     // simple_cnn: the head's backward kernel also sums the per-sample losses (no separate loss_reduce launch)
-    const bool fuse_stats = !lite && head_bwd_fuses(m);
+    const bool fuse_stats = !lite && plan.head_bwd_fuses;
     // simple_cnn (non-deterministic mode): the head's forward pass rides in its backward kernel (kws_layers.h: head_bwd_mfma_kernel<.., FWD>):
     // one launch and the dlogits round trip less on the main chain (same-box: -11 us upper bound measured by skipping the launch)
-    const bool fuse_head_fwd = fuse_stats && !m->deterministic;
+    const bool fuse_head_fwd = !lite && plan.fuse_head_fwd;
     if (!fuse_head_fwd) {
         rc = run_head(m, a->B, a->params, w.d1, w.loss_i, w.correct_i, a->labels, a->class_weights, a->probs, nullptr, w.dlogits,
                       a->grad_scale / (float)a->B, fuse_stats ? nullptr : a->stats, a->ignore_index, s);
@@ -1672,9 +1719,7 @@ int kws_model_train_fwd_bwd(kws_model *m, const kws_train_args *a, void *stream)
         if (a->forward_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->forward_event), s));
         if (!lite) KWS_TRY(hook.fire(1, s));
     }
-    rc = lite ? lite_backward(m, a->feat, a->B, a->params, a->grads, w, a->dropout_seed, static_cast<hipEvent_t>(a->bucket_event), s)
-              : cnn_backward(m, a->feat, a->B, a->params, a->grads, w, a->dropout_seed, static_cast<hipEvent_t>(a->bucket_event), s,
-                             fuse_stats ? a->stats : nullptr, grads_zeroed, a->feat_moments, &hook, a->comm, fuse_head_fwd ? a : nullptr);
+    rc = lite ? lite_backward(m, a->feat, a->B, a->params, a->grads, w, a->dropout_seed, static_cast<hipEvent_t>(a->bucket_event), s) : c.backward();
     if (rc || !a->comm) return rc;
     // simple_cnn reduced its early bucket on the side stream (joined again by now); the rest, and the BatchNormalization moving
     // statistics, go behind the backward pass on the caller's stream.  simple_cnn_lite has no side stream: both buckets here.
