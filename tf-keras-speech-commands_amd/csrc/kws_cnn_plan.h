@@ -12,6 +12,8 @@
 #include "kws_infer_fused.h"
 #include "kws_conv_group.h"
 #include "kws_dense_head.h"
+#include "kws_conv.h"
+#include "kws_conv2_wgrad_fast.h"
 
 namespace kws {
 
@@ -34,6 +36,7 @@ struct CnnPlan {
     bool pool4_fused;        // layer 4's activation rides in the fused Dense + head kernel of the backward pass (kws_dense_head.h: z4)
     bool wgrad2_bf16;        // conv2's weight gradient in split precision
     bool wgrad2_early;       // ... forming dz itself, forked BEFORE conv2's data gradient
+    bool wgrad2_fast;        // ... as the wave-per-clip kernel of the default 15 x 10 map (kws_conv2_wgrad_fast.h)
     bool l1_fin_in_kernel;   // layer 1's backward kernel evaluates the closed forms in its last block (no finalize launch)
     bool head_bwd_fuses;     // the MFMA head kernel also leaves the dense bias gradient and the loss / accuracy sums
     bool fuse_head_fwd;      // the head's forward pass rides in its backward kernel
@@ -85,6 +88,8 @@ inline CnnPlan plan_cnn(const kws_model *m, int B, int mprec, bool training, boo
     p.acc_bn3 = p.group && acc_ok;
     p.acc_bn4 = p.dense_fused && acc_ok && d.flat == d.H4 * d.W4 * kDhK;
     p.l1_fin_in_kernel = acc_ok && p.l1_default_map;
+    // the compile-time map, coefficients from the accumulator set (so neither deterministic mode nor a captured step)
+    p.wgrad2_fast = p.wgrad2_early && p.acc_bn2 && d.H1 == kW2fH && d.W1 == kW2fW;
     return p;
 }
 

@@ -16,6 +16,7 @@
 #include "kws_layer1_moments.h"
 #include "kws_layer1_fast.h"
 #include "kws_l1_conv2.h"
+#include "kws_conv2_wgrad_fast.h"
 #include "kws_lite.h"
 #include "kws_lite_f16.h"
 #include "kws_infer_fused.h"
@@ -1033,9 +1034,17 @@ int CnnCtx::bwd_layer2()
     // and beside layer 1 on the side stream; the data gradient then does not write dz back
     if (P.wgrad2_early) {
         KWS_TRY(bwd_fork(1));
-        static const int occ = resident_blocks(conv_wgrad_clip_bf16_kernel<true>, 256, cc.smwb);
         arm_stop_event(R->ev[9], s2);                 // the last kernel of the side stream: its completion is the join event
-        KWS_LAUNCH("conv_wgrad_clip_bf16<16,32>", conv_wgrad_clip_bf16_kernel<true>, wgrad_grid(occ), dim3(256), cc.smwb, s2, in, nullptr, dk, B, H1, W1, bn_w);
+        if (P.wgrad2_fast) {
+            // the default map: one wave per clip, no barrier in the clip loop (kws_conv2_wgrad_fast.h); two blocks per CU as below
+            using G = Conv2WgradFast<kW2fH, kW2fW>;
+            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(conv2_wgrad_fast_kernel<kW2fH, kW2fW>), G::BYTES)) return rc;
+            KWS_LAUNCH("conv_wgrad_clip_bf16<16,32>", (conv2_wgrad_fast_kernel<kW2fH, kW2fW>), dim3(G::grid(B, cu_count() * 2)), dim3(256), G::BYTES, s2, in, dk,
+                       B, bn_w);
+        } else {
+            static const int occ = resident_blocks(conv_wgrad_clip_bf16_kernel<true>, 256, cc.smwb);
+            KWS_LAUNCH("conv_wgrad_clip_bf16<16,32>", conv_wgrad_clip_bf16_kernel<true>, wgrad_grid(occ), dim3(256), cc.smwb, s2, in, nullptr, dk, B, H1, W1, bn_w);
+        }
     }
     if (P.bf16) {
         const dim3 grid(cc.even_grid(cu_count() * 2));
