@@ -299,6 +299,68 @@ int kws_filter_apply(const kws_filter_bank *bank, const kws_filter_params *param
                      float *out, int64_t out_stride, int32_t *lengths, int32_t *filter_used, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Speed and loudness perturbation of raw audio: tools/audio_process/audio_convert.py of the reference (audio_resample / set_frame_rate
+ * changes the rate of a file; --loudness sets its level with pydub's apply_gain(target - dBFS)), drawn afresh for every clip of every
+ * train step on the device instead of written once as converted copies.  Clip b sits at global batch position p = position_base + b; its
+ * source v is row index[b] of wav (int16 scaled by 1/32768), Ls = valid_len[row] or stride -- NOT clipped to max_samples: a clip played
+ * faster reaches past the head the featurizer would otherwise keep.  Draws: h_f = aug_hash(seed, step, 4 p + f) (kws_augment.h; kws_amd
+ * passes seed_s = WaveAugment seed ^ 0xA0761D6478BD642F, so the noise, reverb and filter draws are unchanged), u_f = (h_f >> 8) * 2^-24:
+ *   f = 0: resampled = u_0 < speed_rate;  f = 1: r = fmaf(u_1, speed_hi - speed_lo, speed_lo)      (float32)
+ *   f = 2: levelled  = u_2 < loud_rate;   f = 3: target = fmaf(u_3, loud_hi_db - loud_lo_db, loud_lo_db) dBFS
+ *   resampled: the clip is played r times faster (tempo and pitch move together) by band-limited interpolation with the table h of a
+ *         kws_resampler (Z zero crossings, P phases).  L' = min(ceil((double)Ls / (double)r), max_samples) (0 when Ls = 0).  For n < L':
+ *         s = min(1, 1 / r); t = n r, n0 = floor(t), phi = t - n0 (float64; n r is exact);
+ *         left wing,  k = 0, 1, ... while n0 - k >= 0 and pos = ((phi + k) s) P < Z P:  i = floor(pos), eta = pos - i,
+ *                     acc += (h[i] + eta (h[i + 1] - h[i])) v[n0 - k];
+ *         right wing, k = 0, 1, ... while n0 + 1 + k < Ls and pos = ((1 - phi + k) s) P < Z P: the same weight times v[n0 + 1 + k];
+ *         y[n] = s acc.  t, pos, i and eta are float64 (a float32 phase is off by 1e-3 of a sample at n = 16000); the weight
+ *         (fmaf(eta, h[i + 1] - h[i], h[i])), the products and the sum are float32, in this order: left wing, then right wing, k ascending.
+ *   not resampled: L' = min(Ls, max_samples), y = v (bit for bit after the f32 conversion), speed_used = 0
+ *   levelled: m = mean(y[0:L']^2) in float64 (fixed order; 0 when L' = 0), g = sqrtf((float)(10^(target / 10) / (m + FLT_EPSILON))),
+ *         y *= g: pydub's apply_gain(target - dBFS) with full scale 1.0 (the 1/32768 scaling).  A silent clip stays silent.
+ *   not levelled: gain_used = 1
+ * This stage runs first; reverb, filter and noise (time shift included) then run unchanged on (out, lengths) with index = NULL and the
+ * same position_base.  Divergences from the reference: a Kaiser-windowed sinc table instead of audioop.ratecv / sox; the number of
+ * samples changes and the rate stays (a speed change), where the tool keeps the duration and changes the rate; only max_samples
+ * outputs are made; no int16 quantisation and no clipping of the levelled result; fresh draws every step.
+ * ---------------------------------------------------------------------- */
+typedef struct kws_resampler kws_resampler;
+
+/* The interpolation table, a HOST object (no device is needed to create or query it; the float32 device copy is made by the first
+ * kws_speed_apply): the right half of a Kaiser-windowed sinc, h[i] = rolloff sinc(rolloff i / P) kaiser_beta(i / (P Z)), i = 0 .. Z P,
+ * sinc(x) = sin(pi x) / (pi x), kaiser_beta(u) = I0(beta sqrt(1 - u^2)) / I0(beta), computed in float64 and rounded to float32.
+ * zero_crossings Z in [4, 32], phases P in [32, 1024], beta in [0, 20], rolloff in (0, 1] (KWS_ERR_INVALID outside), and the table's
+ * (Z P + 1) floats must fit 64 KiB of LDS (KWS_ERR_UNSUPPORTED above). */
+int kws_resampler_create(int zero_crossings, int phases, double beta, double rolloff, kws_resampler **out);
+void kws_resampler_destroy(kws_resampler *rs);
+/* host: the arguments of kws_resampler_create (each may be NULL) */
+int kws_resampler_info(const kws_resampler *rs, int *zero_crossings, int *phases, double *beta, double *rolloff);
+/* host: the table as the device holds it, h[0 .. Z P] float32 (n >= Z P + 1) */
+int kws_resampler_table(const kws_resampler *rs, float *out, size_t n);
+
+typedef struct kws_speed_params {
+    float speed_rate;      /* fraction of clips resampled, [0, 1]; 0 switches the speed half off */
+    float speed_lo, speed_hi;     /* ratio r uniform in [lo, hi], 0.5 <= lo <= hi <= 2 (checked when speed_rate > 0) */
+    float loud_rate;       /* fraction of clips levelled, [0, 1]; 0 switches the loudness half off */
+    float loud_lo_db, loud_hi_db; /* target dBFS uniform in [lo, hi], -80 <= lo <= hi <= 0 (checked when loud_rate > 0) */
+    int32_t max_samples;   /* the head the featurizer keeps, >= 1 */
+    int32_t reserved;      /* 0 */
+    uint64_t seed;         /* seed_s */
+} kws_speed_params;
+
+/* Perturb B clips, no atomics and no host synchronisation (the explicit arrays are copied from the host first).  out: B x out_stride
+ * float32 (out_stride >= max_samples; never wav itself), row b = y[0:L'] then zeros; lengths (device int32 B, required) = L';
+ * speed_used (device float32 B, may be NULL unless explicit_speed is given: the ratios are staged there) = r, or 0 for a clip that was
+ * not resampled; gain_used (device float32 B, may be NULL unless explicit_db is given) = g, or 1 for a clip that was not levelled.
+ * explicit_speed (HOST float32 B, or NULL): r from the caller, 0 = not resampled, other values in [0.5, 2].  explicit_db (HOST float32
+ * B, or NULL): the target from the caller in [-80, 0], NaN = not levelled.  rs may be NULL when no clip can be resampled: speed_rate == 0 and
+ * explicit_speed NULL or all zeros.  Fixed summation order: two calls give the same bits. */
+int kws_speed_apply(const kws_resampler *rs, const kws_speed_params *params, const void *wav, int wav_dtype, const int32_t *index, int B,
+                    int64_t stride, const int32_t *valid_len, int64_t position_base, int64_t step, const float *explicit_speed,
+                    const float *explicit_db, float *out, int64_t out_stride, int32_t *lengths, float *speed_used, float *gain_used,
+                    void *stream);
+
+/* ------------------------------------------------------------------------
  * Model: replaces the tf.keras objects built by classifier/model.py:14-46
  * get_model() (backbones classifier/models/cnn.py, rnn.py) and the work
  * Keras does inside model.fit / model.predict (train.py:75-92).

@@ -1,5 +1,5 @@
-"""Background-noise, room-reverberation and filter augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*, kws_augment_*,
-kws_rir_bank_*, kws_reverb_apply, kws_filter_bank_*, kws_filter_apply).
+"""Background-noise, room-reverberation, filter, speed and loudness augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*,
+kws_augment_*, kws_rir_bank_*, kws_reverb_apply, kws_filter_bank_*, kws_filter_apply, kws_resampler_*, kws_speed_apply).
 
 The reference makes training data robust offline: tools/audio_process/add_noise.py mixes a randomly chosen background recording into a
 `noised_rate` fraction of the clips at an SNR drawn from a list and writes one fixed *_noised.wav copy per clip.  Here the same mix is
@@ -21,6 +21,15 @@ The third tool, tools/audio_process/wav_filter.py, filters a clip with a Butterw
 every step is filtered with one drawn afresh, after the reverberation and before the noise:
 
     aug = WaveAugment(noise, filters=random_filters(64, seed=0), filter_rate=0.5, seed=1)   # noise may be None
+
+The fourth tool, tools/audio_process/audio_convert.py, resamples a file and sets it to a target loudness (pydub's apply_gain(target -
+dBFS)).  Here a `speed_rate` share of the clips of every step is played at a ratio drawn from `speed` (tempo and pitch move together,
+band-limited interpolation with the Kaiser-windowed sinc table of a Resampler), and a `loudness_rate` share is set to a level drawn from
+`loudness` (dBFS), before every other stage:
+
+    aug = WaveAugment(noise, speed=(0.9, 1.1), loudness=(-30, -15), seed=1)                 # noise may be None
+
+resample(wav, orig_sr, target_sr) is the tool's file-conversion use of the same kernel at one fixed ratio.
 
 Argument checks run on the host; the device copy of a bank is made on first use."""
 import ctypes
@@ -478,19 +487,91 @@ def random_filters(count, types=("lowpass", "highpass", "bandpass"), order=4, se
     return out
 
 
+# the speed / loudness draws use seed ^ SPEED_SEED_MIX, independent of the noise, reverb and filter draws of the same seed (include/kws.h)
+SPEED_SEED_MIX = 0xA0761D6478BD642F
+KAISER_BEST_BETA = 8.555504641634386      # the window of the widely used "kaiser_best" resampling table (stop band about -100 dB)
+
+
+class Resampler(object):
+    """The interpolation table of the speed change (kws_resampler): the right half of a Kaiser-windowed sinc with `zero_crossings`
+    lobes on each side, `phases` entries per zero crossing, window parameter `beta` and cutoff `rolloff` (a fraction of the lower
+    Nyquist frequency).  A host object: the device copy is made by the first clip resampled with it."""
+
+    def __init__(self, zero_crossings=16, phases=512, beta=KAISER_BEST_BETA, rolloff=0.85):
+        self.zero_crossings, self.phases, self.beta, self.rolloff = int(zero_crossings), int(phases), float(beta), float(rolloff)
+        if self.zero_crossings != zero_crossings or self.phases != phases:
+            raise ValueError("zero_crossings and phases must be integers, got %r and %r" % (zero_crossings, phases))
+        L = _l.get_lib()
+        h = ctypes.c_void_p()
+        rc = L.kws_resampler_create(self.zero_crossings, self.phases, self.beta, self.rolloff, ctypes.byref(h))
+        if rc != 0:
+            raise ValueError(L.kws_last_error().decode("utf-8", "replace"))
+        self._h, self._L = h, L
+
+    def __len__(self):
+        return self.zero_crossings * self.phases + 1
+
+    def table(self):
+        """h[0 .. zero_crossings * phases] as the device holds it (float32)"""
+        out = np.zeros(len(self), np.float32)
+        _l.check(self._L.kws_resampler_table(self.handle(), out.ctypes.data, out.size))
+        return out
+
+    def handle(self):
+        if self._h is None:
+            raise ValueError("this Resampler is closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.kws_resampler_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _range(name, value, lo, hi, unit=""):
+    try:
+        a, b = (float(x) for x in value)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a (low, high) pair, got %r" % (name, value))
+    if not lo <= a <= b <= hi:
+        raise ValueError("%s range must satisfy %g <= low <= high <= %g%s, got %r" % (name, lo, hi, unit, value))
+    return a, b
+
+
 class WaveAugment(object):
     """Per-clip background noise (add_noise.py:19-35) at an SNR drawn from `snr` for a `noised_rate` fraction of the clips, and an
     optional time shift of up to +-time_shift_ms (off by default; the reference has none).  With `rirs` (a RirBank, or anything RirBank
     accepts) a `reverb_rate` fraction of the clips is first convolved with a RIR drawn from the bank (audio_reverberation.py), with the
     clip's energy kept when `rescale` is on; `noise` may then be None.  With `filters` (a FilterBank, or specs FilterBank accepts) a
     `filter_rate` fraction of the clips is then filtered at zero phase with a design drawn from the bank (wav_filter.py), energy kept
-    likewise.  Draws are counter-based, keyed by (seed, step) and indexed by the clip's position in the global batch."""
+    likewise.  With `speed` = (low, high) a `speed_rate` fraction of the clips is first of all played at a ratio drawn uniformly from
+    it (0.5..2; `resampler`: the interpolation table, default Resampler()), and with `loudness` = (low_db, high_db) a `loudness_rate`
+    fraction is set to a level drawn uniformly from it (dBFS, -80..0), as audio_convert.py does offline.  Draws are counter-based,
+    keyed by (seed, step) and indexed by the clip's position in the global batch."""
 
     def __init__(self, noise, snr=(50,), noised_rate=1.0, time_shift_ms=0, seed=None, sample_rate=None, rirs=None, reverb_rate=1.0,
-                 rescale=True, filters=None, filter_rate=1.0):
+                 rescale=True, filters=None, filter_rate=1.0, speed=None, speed_rate=1.0, loudness=None, loudness_rate=1.0, resampler=None):
         from classifier.params import pr
-        if noise is None and rirs is None and filters is None:
+        if noise is None and rirs is None and filters is None and speed is None and loudness is None:
             raise ValueError("WaveAugment needs a noise bank, a RIR bank or both")
+        srate = float(speed_rate)
+        if not 0.0 <= srate <= 1.0:
+            raise ValueError("speed_rate must be in [0, 1], got %r" % speed_rate)
+        lrate = float(loudness_rate)
+        if not 0.0 <= lrate <= 1.0:
+            raise ValueError("loudness_rate must be in [0, 1], got %r" % loudness_rate)
+        self.speed = None if speed is None else _range("speed", speed, 0.5, 2.0)
+        self.loudness = None if loudness is None else _range("loudness", loudness, -80.0, 0.0, " dBFS")
+        if resampler is not None and not isinstance(resampler, Resampler):
+            raise ValueError("resampler must be a kws_amd.augment.Resampler, got %r" % (resampler,))
+        self.resampler = resampler if resampler is not None or self.speed is None else Resampler()
+        self.speed_rate, self.loudness_rate = srate, lrate
         frate = float(filter_rate)
         if not 0.0 <= frate <= 1.0:
             raise ValueError("filter_rate must be in [0, 1], got %r" % filter_rate)
@@ -515,6 +596,85 @@ class WaveAugment(object):
         sr = int(sample_rate or pr.sample_rate)
         self.max_shift = int(round(self.time_shift_ms * sr / 1000.0))
         self.seed = int(np.random.randint(0, 2 ** 62) if seed is None else seed) & (2 ** 64 - 1)
+
+    @property
+    def perturbs(self):
+        """whether the speed / loudness stage is configured"""
+        return self.speed is not None or self.loudness is not None
+
+    @property
+    def speed_seed(self):
+        return self.seed ^ SPEED_SEED_MIX
+
+    def speed_params(self, max_samples):
+        p = _l.KwsSpeedParams()
+        if self.speed is not None:
+            p.speed_rate, p.speed_lo, p.speed_hi = self.speed_rate, self.speed[0], self.speed[1]
+        if self.loudness is not None:
+            p.loud_rate, p.loud_lo_db, p.loud_hi_db = self.loudness_rate, self.loudness[0], self.loudness[1]
+        p.max_samples, p.reserved, p.seed = int(max_samples), 0, self.speed_seed
+        return p
+
+    def perturb(self, wav, valid_len=None, index=None, step=0, position_base=0, explicit_speed=None, explicit_db=None, max_samples=None,
+                out=None, lengths=None, speed_used=None, gain_used=None):
+        """-> (out (B, max_samples) float32, lengths (B,) int32, speed_used (B,) float32, gain_used (B,) float32): the B clips
+        wav[index] (default: every row), each played at the ratio drawn for (seed, step) at global position position_base + b
+        (speed_used = the ratio, 0 for a clip left at its speed: that one is the float32 conversion, bit for bit) and set to the level
+        drawn for it (gain_used = the gain, 1 for a clip left at its level), head-aligned, zeros after.  A clip's whole valid length is
+        the source, not only its first max_samples.  explicit_speed: B ratios (0, or 0.5..2) instead of the draws; explicit_db: B
+        targets in dBFS (NaN: not levelled) instead of the draws.  out / lengths / speed_used / gain_used: optional preallocated CUDA
+        buffers (out may be wider than max_samples; speed_used=False / gain_used=False skip them)."""
+        from classifier.params import pr
+        torch = _torch()
+        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
+            raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
+        rows, stride = wav.shape
+        B, ix = rows, 0
+        if index is not None:
+            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
+                raise ValueError("index must be a contiguous CUDA int32 vector")
+            B, ix = index.numel(), index.data_ptr()
+        vl = 0
+        if valid_len is not None:
+            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
+                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
+            vl = valid_len.data_ptr()
+        ms = int(pr.max_samples if max_samples is None else max_samples)
+        exs = exd = None
+        if explicit_speed is not None:
+            exs = np.ascontiguousarray(np.asarray(explicit_speed).reshape(-1), np.float32)
+            if exs.shape != (B,):
+                raise ValueError("explicit speed has %s entries for %d clips" % (exs.shape, B))
+            if speed_used is False:
+                speed_used = None                           # the explicit ratios are staged there
+            if self.resampler is None and exs.any():
+                raise ValueError("this WaveAugment has no resampler: give speed=... or resampler=... to change a clip's speed")
+        if explicit_db is not None:
+            exd = np.ascontiguousarray(np.asarray(explicit_db).reshape(-1), np.float32)
+            if exd.shape != (B,):
+                raise ValueError("explicit loudness has %s entries for %d clips" % (exd.shape, B))
+            if gain_used is False:
+                gain_used = None                            # the explicit targets are staged there
+        if out is None:
+            out = torch.empty((B, ms), dtype=torch.float32, device=wav.device)
+        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] < ms or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError("out must be a contiguous float32 CUDA tensor of at least (%d, %d)" % (B, ms))
+        if lengths is None:
+            lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
+        if speed_used is None:
+            speed_used = torch.empty((B,), dtype=torch.float32, device=wav.device)
+        if gain_used is None:
+            gain_used = torch.empty((B,), dtype=torch.float32, device=wav.device)
+        _l.check(_l.get_lib().kws_speed_apply(None if self.resampler is None else self.resampler.handle(), ctypes.byref(self.speed_params(ms)),
+                                              wav.data_ptr(), _wav_code(wav), ix, B, stride, vl, int(position_base), int(step),
+                                              None if exs is None else exs.ctypes.data, None if exd is None else exd.ctypes.data,
+                                              out.data_ptr(), out.shape[1], lengths.data_ptr(),
+                                              speed_used.data_ptr() if speed_used is not False else None,
+                                              gain_used.data_ptr() if gain_used is not False else None,
+                                              torch.cuda.current_stream().cuda_stream))
+        if exs is not None or exd is not None:
+            torch.cuda.current_stream().synchronize()       # the host values are copied from pageable memory
+        return out, lengths, (speed_used if speed_used is not False else None), (gain_used if gain_used is not False else None)
 
     @property
     def reverb_seed(self):
@@ -689,6 +849,40 @@ class WaveAugment(object):
         _l.check(_l.get_lib().kws_augment_apply(self.noise.handle(), plan.data_ptr(), wav.data_ptr(), _wav_code(wav), ix, B, wav.shape[1], ms,
                                                 out.data_ptr(), ms, lens.data_ptr(), torch.cuda.current_stream().cuda_stream))
         return out, lens
+
+
+def resample(wav, orig_sr, target_sr, resampler=None):
+    """-> (B, ceil(n / r)) float32 CUDA tensor: the rows of wav (a contiguous CUDA tensor (B, n), float32 or int16 scaled by 1/32768)
+    converted from orig_sr to target_sr, r = orig_sr / target_sr in [0.5, 2]: the file-conversion use of audio_convert.py
+    (audio_resample), with the band-limited interpolation of WaveAugment's speed change at one fixed ratio.  Equal rates give the
+    float32 conversion.  common.data_utils.load_wav keeps its own (scipy) resampling."""
+    torch = _torch()
+    if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
+        raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, samples)")
+    if not (orig_sr > 0 and target_sr > 0):
+        raise ValueError("sample rates must be positive, got %r and %r" % (orig_sr, target_sr))
+    r = np.float32(float(orig_sr) / float(target_sr))
+    if not 0.5 <= r <= 2.0:
+        raise ValueError("orig_sr / target_sr must be in [0.5, 2], got %g" % r)
+    if resampler is not None and not isinstance(resampler, Resampler):
+        raise ValueError("resampler must be a kws_amd.augment.Resampler, got %r" % (resampler,))
+    rs = resampler if resampler is not None else Resampler()
+    B, n = wav.shape
+    if n < 1:
+        raise ValueError("wav has no samples")
+    same = float(orig_sr) == float(target_sr)
+    n_out = n if same else int(math.ceil(float(n) / float(r)))
+    out = torch.empty((B, n_out), dtype=torch.float32, device=wav.device)
+    lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
+    used = torch.empty((B,), dtype=torch.float32, device=wav.device)
+    p = _l.KwsSpeedParams()
+    p.max_samples = n_out
+    ex = np.full((B,), 0.0 if same else r, np.float32)
+    _l.check(_l.get_lib().kws_speed_apply(rs.handle(), ctypes.byref(p), wav.data_ptr(), _wav_code(wav), 0, B, n, 0, 0, 0, ex.ctypes.data, None,
+                                          out.data_ptr(), out.shape[1], lengths.data_ptr(), used.data_ptr(), None,
+                                          torch.cuda.current_stream().cuda_stream))
+    torch.cuda.current_stream().synchronize()               # ex is copied from pageable memory
+    return out
 
 
 def records(plan):

@@ -87,7 +87,9 @@ class Featurizer(object):
         augment: optional kws_amd.augment.WaveAugment: featurize the clips with background noise mixed in, drawn for (its seed, `step`)
         at global batch positions position_base + b (kws_augment_plan + kws_featurize_gather_augmented).  With a RIR bank the clips are
         reverberated first (kws_reverb_apply into a scratch buffer of this featurizer); with a filter bank they are filtered next
-        (kws_filter_apply, in place in that scratch); then noised (if it has a noise bank) and featurized from there."""
+        (kws_filter_apply, in place in that scratch); then noised (if it has a noise bank) and featurized from there.  With a speed or
+        loudness range the clips are perturbed before all of that (kws_speed_apply into the scratch; into a second buffer when a
+        reverberation follows, which does not run in place)."""
         torch = _torch()
         if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous CUDA tensor of shape (B, stride)")
@@ -108,10 +110,16 @@ class Featurizer(object):
             if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
                 raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
             vl = valid_len.data_ptr()
-        if augment is not None and (augment.rirs is not None or augment.filters is not None):
-            # reverberation, then the filter (in place), into this featurizer's scratch on the call's stream; then noise (or nothing)
+        if augment is not None and (augment.perturbs or augment.rirs is not None or augment.filters is not None):
+            # speed / loudness, reverberation, then the filter (in place), into this featurizer's scratch on the call's stream; then
+            # noise (or nothing)
             ms = g["max_samples"]
             wet, lens = self._reverb_scratch(B, ms, wav.device), self._reverb_lengths(B, wav.device)
+            if augment.perturbs:
+                pre, pre_lens = (wet, lens) if augment.rirs is None else self._scratch(B, ms, wav.device, "_sp_bufs")
+                augment.perturb(wav, valid_len=valid_len, index=index, step=step, position_base=position_base, max_samples=ms, out=pre,
+                                lengths=pre_lens, speed_used=False, gain_used=False)
+                wav, index, valid_len = pre, None, pre_lens
             if augment.rirs is not None:
                 augment.reverberate(wav, valid_len=valid_len, index=index, step=step, position_base=position_base, max_samples=ms, out=wet,
                                     lengths=lens, rir_used=False)
@@ -132,15 +140,19 @@ class Featurizer(object):
                                               torch.cuda.current_stream().cuda_stream))
         return out
 
-    def _reverb_scratch(self, B, ms, device):
-        """(B, ms) float32 rows the reverberated clips go to, one buffer per stream (grown on demand)"""
+    def _scratch(self, B, ms, device, name):
+        """((B, ms) float32 rows, (B,) int32 lengths) of the scratch `name`, one buffer per stream (grown on demand)"""
         torch = _torch()
         key = torch.cuda.current_stream().cuda_stream
-        bufs = self.__dict__.setdefault("_rv_bufs", {})
+        bufs = self.__dict__.setdefault(name, {})
         buf = bufs.get(key)
         if buf is None or buf[0].shape[0] < B or buf[0].shape[1] != ms or buf[0].device != device:
             buf = bufs[key] = (torch.empty((B, ms), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.int32, device=device))
-        return buf[0][:B]
+        return buf[0][:B], buf[1][:B]
+
+    def _reverb_scratch(self, B, ms, device):
+        """(B, ms) float32 rows the reverberated clips go to"""
+        return self._scratch(B, ms, device, "_rv_bufs")[0]
 
     def _reverb_lengths(self, B, device):
         return self._rv_bufs[_torch().cuda.current_stream().cuda_stream][1][:B]

@@ -90,6 +90,13 @@ FILTER_MAX_SECTIONS = 4
 FILTER_MAX_PADLEN = 32
 FILTER_MAX_SAMPLES = 16320
 
+
+class KwsSpeedParams(ctypes.Structure):
+    _fields_ = [("speed_rate", ctypes.c_float), ("speed_lo", ctypes.c_float), ("speed_hi", ctypes.c_float),
+                ("loud_rate", ctypes.c_float), ("loud_lo_db", ctypes.c_float), ("loud_hi_db", ctypes.c_float),
+                ("max_samples", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
 QUANT_TENSORS = 6
 QUANT_MAX_CLASSES = 48
 QUANT_MAX, QUANT_RELU6, QUANT_KL = 0, 1, 2
@@ -273,6 +280,12 @@ def get_lib():
     L.kws_filter_bank_destroy.restype = None
     L.kws_filter_bank_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.kws_filter_apply.argtypes = [vp, ctypes.POINTER(KwsFilterParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp]
+    L.kws_resampler_create.argtypes = [i32, i32, f64, f64, ctypes.POINTER(vp)]
+    L.kws_resampler_destroy.argtypes = [vp]
+    L.kws_resampler_destroy.restype = None
+    L.kws_resampler_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(f64), ctypes.POINTER(f64)]
+    L.kws_resampler_table.argtypes = [vp, vp, ctypes.c_size_t]
+    L.kws_speed_apply.argtypes = [vp, ctypes.POINTER(KwsSpeedParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
     L.kws_model_calibrate.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp]
     L.kws_quantize_simple_cnn.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(KwsQSimpleCnn)]
     L.kws_qmodel_create.argtypes = [vp, ctypes.POINTER(KwsQSimpleCnn), ctypes.POINTER(vp)]

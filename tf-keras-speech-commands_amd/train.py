@@ -12,6 +12,9 @@ offline tool tools/audio_process/add_noise.py (--snr, --noised_rate) and an opti
 before the noise, as tools/audio_process/audio_reverberation.py does offline; either works without --noise_path.  --filter_rate filters
 that share of the training clips at zero phase with a Butterworth design drawn from a bank of --num_filters random ones
 (--filter_types, --filter_order), after the room and before the noise, as tools/audio_process/wav_filter.py does offline.
+--speed_range LO,HI plays a --speed_rate share of the training clips at a ratio drawn from the range (tempo and pitch together) and
+--loudness_range LO_DB,HI_DB sets a --loudness_rate share to a level drawn from the range (dBFS), before every other stage, as
+tools/audio_process/audio_convert.py resamples and levels files offline.
 The optimizer takes the Keras options the reference's command line leaves at their defaults: --clipnorm, --global_clipnorm and
 --clipvalue (any optimizer), --momentum (sgd, rmsprop), --nesterov (sgd), --centered (rmsprop) and --amsgrad (adam)."""
 import argparse
@@ -54,6 +57,14 @@ def main(argv=None):
         raise SystemExit('--filter_rate needs --raw_audio (the waveforms are filtered before featurization)')
     if args.num_filters < 1:
         raise SystemExit('--num_filters needs a positive bank size')
+    for flag in ('speed_range', 'speed_rate', 'loudness_range', 'loudness_rate'):
+        if getattr(args, flag) is not None and not args.raw_audio:
+            raise SystemExit('--%s needs --raw_audio (the waveforms are perturbed before featurization)' % flag)
+    if args.speed_rate is not None and args.speed_range is None:
+        raise SystemExit('--speed_rate needs --speed_range')
+    if args.loudness_rate is not None and args.loudness_range is None:
+        raise SystemExit('--loudness_rate needs --loudness_range')
+    perturb = perturb_options(args)
     opt_options = optimizer_options(args)
 
     # callbacks for training process
@@ -103,12 +114,12 @@ def main(argv=None):
     if args.noise_path:
         from kws_amd.augment import NoiseBank, WaveAugment
         augment = WaveAugment(NoiseBank(args.noise_path), snr=args.snr, noised_rate=args.noised_rate, time_shift_ms=args.time_shift_ms,
-                              rirs=rirs, reverb_rate=reverb_rate, filters=filters, filter_rate=filter_rate)
+                              rirs=rirs, reverb_rate=reverb_rate, filters=filters, filter_rate=filter_rate, **perturb)
     elif args.time_shift_ms:
         raise SystemExit('--time_shift_ms is part of the noise augmentation: give --noise_path too')
-    elif rirs is not None or filters is not None:
+    elif rirs is not None or filters is not None or perturb:
         from kws_amd.augment import WaveAugment
-        augment = WaveAugment(None, rirs=rirs, reverb_rate=reverb_rate, filters=filters, filter_rate=filter_rate)
+        augment = WaveAugment(None, rirs=rirs, reverb_rate=reverb_rate, filters=filters, filter_rate=filter_rate, **perturb)
 
     # prepare optimizer
     if args.decay_type:
@@ -162,6 +173,32 @@ def optimizer_options(args):
         if args.optimizer not in kinds:
             raise SystemExit('--%s is an option of %s, not of --optimizer %s' % (name, ' / '.join(kinds), args.optimizer))
         kw[name] = value
+    return kw
+
+
+def parse_range(flag, text, lo, hi):
+    """'LO,HI' -> (LO, HI) with lo <= LO <= HI <= hi"""
+    try:
+        a, b = (float(x) for x in text.split(','))
+    except ValueError:
+        raise SystemExit('--%s needs two numbers LO,HI, got %r' % (flag, text))
+    if not lo <= a <= b <= hi:
+        raise SystemExit('--%s needs %g <= LO <= HI <= %g, got %r' % (flag, lo, hi, text))
+    return a, b
+
+
+def perturb_options(args):
+    """keyword arguments of WaveAugment for the speed / loudness flags given on the command line (none: no such stage)"""
+    kw = {}
+    if args.speed_range is not None:
+        kw['speed'] = parse_range('speed_range', args.speed_range, 0.5, 2.0)
+        kw['speed_rate'] = 1.0 if args.speed_rate is None else args.speed_rate
+    if args.loudness_range is not None:
+        kw['loudness'] = parse_range('loudness_range', args.loudness_range, -80.0, 0.0)
+        kw['loudness_rate'] = 1.0 if args.loudness_rate is None else args.loudness_rate
+    for flag in ('speed_rate', 'loudness_rate'):
+        if flag in kw and not 0.0 <= kw[flag] <= 1.0:
+            raise SystemExit('--%s must be in 0.0~1.0, got %r' % (flag, kw[flag]))
     return kw
 
 
@@ -239,6 +276,20 @@ def parse_args(argv=None):
                         help="order of the Butterworth filters. default=%(default)s")
     parser.add_argument('--num_filters', type=int, required=False, default=64,
                         help="number of random filters in the bank. default=%(default)s")
+    # Speed and loudness perturbation (tools/audio_process/audio_convert.py, drawn per clip and per step)
+    parser.add_argument('--speed_range', type=str, required=False, default=None,
+                        help="LO,HI: play the training clips at a random ratio in this range, 0.5~2.0 (needs --raw_audio). default: off")
+    parser.add_argument('--speed_rate', type=float, required=False, default=None,
+                        help="random percentage rate of changing the speed of the training clips (0.0~1.0). default=1.0")
+    parser.add_argument('--loudness_range', type=str, required=False, default=None,
+                        help="LO_DB,HI_DB: set the training clips to a random loudness in this range in dBFS, -80~0, written --loudness_range -30,-15 or --loudness_range=-30,-15 (needs --raw_audio). default: off")
+    parser.add_argument('--loudness_rate', type=float, required=False, default=None,
+                        help="random percentage rate of setting the loudness of the training clips (0.0~1.0). default=1.0")
+    # "--loudness_range -30,-15": argparse takes a value that starts with '-' and is no plain number for an option, so bind it with '='
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 2, -1, -1):
+        if argv[i] == '--loudness_range':
+            argv[i:i + 2] = ['--loudness_range=' + argv[i + 1]]
     return parser.parse_args(argv)
 
 
