@@ -966,6 +966,63 @@ int kws_stream_scan_postprocess(const kws_decoder *dec, const float *probs, int 
                                 int trigger_level, int chunk_size, int32_t *state, int32_t *index, double *score,
                                 int32_t *fired, int64_t out_stride, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Voice-activity detection of whole recordings: where the speech is, which files are silent, and the clips.  Replaces
+ *   VoiceActivityDetector.detect_speech              tools/audio_process/speech_duration_check.py:149-176
+ *   ._median_filter / ._smooth_speech_detection      speech_duration_check.py:88-106
+ *   .convert_windows_to_readable_labels              speech_duration_check.py:108-130
+ *   speech_duration_check (the `simple` type)        speech_duration_check.py:301-330
+ *   silent_check                                     tools/audio_process/silent_check.py:14-24
+ * for R recordings of ragged length in one packed (R, stride) buffer, int16 or float32, with device `lengths`.
+ * With N = int(rate * window_t), H = int(rate * hop_t) and L samples: window w covers [w H, w H + N) for every w with
+ * w H < L - N; E_k = |X_k|^2 of its N-point DFT; full = sum_{k=1..N/2} 2 E_k (Nyquist counted twice, as the
+ * reference's dict does), band = the same sum over band_lo < k rate / N < band_hi; raw = band / full > energy_threshold
+ * (false when full == 0); smoothed = median of int(smooth_t / window_t) windows (made odd), first and last value
+ * replicated at the ends; an interval begins at the first sample of the first smoothed-1 window and ends at the first
+ * sample of the next smoothed-0 window; an interval still open at the last window is dropped.
+ * ------------------------------------------------------------------------ */
+typedef struct kws_vad kws_vad;
+
+/* VoiceActivityDetector.__init__ (speech_duration_check.py:25-32 holds the defaults 0.02, 0.01, 300, 3000, 0.6, 0.5).
+ * Host only: the cos/sin matrix of the band bins is built in double here and uploaded by the first kws_vad_detect on a
+ * device.  Geometries other than N == 2 H, N <= 1024 and a band of at most 56 bins return KWS_ERR_UNSUPPORTED. */
+int kws_vad_create(int sample_rate, double window_t, double hop_t, double band_lo, double band_hi, double energy_threshold,
+                   double smooth_t, kws_vad **out);
+void kws_vad_destroy(kws_vad *vad);
+/* N, H, the first and last band bin (inclusive) and the median's length; any pointer may be NULL */
+int kws_vad_info(const kws_vad *vad, int32_t *window_samples, int32_t *hop_samples, int32_t *bin_lo, int32_t *bin_hi,
+                 int32_t *median);
+/* Host only: the window count of a recording of n_samples (the loop condition of speech_duration_check.py:162), or a
+ * negative kws error code. */
+int64_t kws_vad_windows(const kws_vad *vad, int64_t n_samples);
+/* Host only: bytes of the device workspace kws_vad_detect needs (one 8-byte sum per job), or a negative error code. */
+int64_t kws_vad_workspace_bytes(const kws_vad *vad, int R, int max_windows);
+
+/* detect_speech + convert_windows_to_readable_labels + the span of speech_duration_check.py:314-330 + the energy of
+ * silent_check.py:17-18 for all recordings, in two launches on `stream` without host synchronisation.  All pointers
+ * but `vad` are device memory; max_windows >= kws_vad_windows(stride).
+ *   ratio (R, max_windows) float32       band / full; 0 where full <= 0 and past a recording's window count
+ *   smoothed (R, max_windows) uint8      the smoothed flags; 0 past the window count
+ *   segments (R, max_segments, 2) int32  {begin, end} sample indices in window order; 0 past the count
+ *   n_segments (R) int32                 the true count, also when it exceeds max_segments
+ *   span (R, 2) int32                    {min begin, max end}, or {0, 0} without an interval
+ *   energy_per_second (R) float64        sum((x / 32768)^2) / (L / rate) (float32 input: sum(x^2)); 0 for L == 0
+ * The same inputs give the same bits (fixed summation order, no float atomics); samples at or past lengths[r] are never
+ * read. */
+int kws_vad_detect(const kws_vad *vad, const void *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths,
+                   int max_windows, int max_segments, void *workspace, int64_t workspace_bytes, float *ratio,
+                   uint8_t *smoothed, int32_t *segments, int32_t *n_segments, int32_t *span, double *energy_per_second,
+                   void *stream);
+
+/* Clips for kws_featurize / raw-audio training from n device triples {recording, begin, end} (sample indices, e.g. the
+ * segments above): clip i is cut from [max(0, begin - pad_before), min(L, end + pad_after)) and scaled as the featurizer
+ * scales (int16 / 32768).  KWS_VAD_ALIGN_LEFT_PAD: zeros in front of a shorter cut (audio_to_feature, common/data_utils.py:77-80);
+ * KWS_VAD_ALIGN_CENTER: zeros on both sides, the odd one at the end.  A longer cut keeps its head.  A recording index
+ * outside [0, R) gives a clip of zeros.  clips: (n, clip_samples) float32. */
+enum { KWS_VAD_ALIGN_LEFT_PAD = 0, KWS_VAD_ALIGN_CENTER = 1 };
+int kws_vad_gather_clips(const void *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths, const int32_t *triples,
+                         int n, int clip_samples, int pad_before, int pad_after, int align, float *clips, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

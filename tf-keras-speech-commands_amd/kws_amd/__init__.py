@@ -4,3 +4,4 @@ There is no CPU fallback: importing `kws_amd.lib` without the built library rais
 compute entry point raises `KwsError` when no HIP device is present.
 """
 from .lib import KwsError, check, get_lib, device_count, version  # noqa: F401
+from .vad import Vad, VadResult, speech_duration, silent_check  # noqa: F401

@@ -160,6 +160,7 @@ MODEL_KINDS = {"simple_cnn": 0, "simple_cnn_lite": 1, "simple_gru": 2, "simple_l
 BANK_MEL, BANK_BARK = 0, 1
 WAV_F32, WAV_I16 = 0, 1
 RAW_F64, RAW_F32 = 0, 1
+VAD_ALIGN = {"left": 0, "center": 1}                                                    # include/kws.h KWS_VAD_ALIGN_*
 
 _lib = None
 
@@ -301,6 +302,17 @@ def get_lib():
     L.kws_quant_kl_ranges.argtypes = [vp, vp, i32, vp, vp]
     L.kws_quantize_simple_rnn.argtypes = [vp, vp, ctypes.POINTER(KwsQSimpleRnn)]
     L.kws_qmodel_create_rnn.argtypes = [vp, ctypes.POINTER(KwsQSimpleRnn), ctypes.POINTER(vp)]
+    f64 = ctypes.c_double
+    L.kws_vad_create.argtypes = [i32, f64, f64, f64, f64, f64, f64, ctypes.POINTER(vp)]
+    L.kws_vad_destroy.argtypes = [vp]
+    L.kws_vad_destroy.restype = None
+    L.kws_vad_info.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 5
+    L.kws_vad_windows.argtypes = [vp, i64]
+    L.kws_vad_windows.restype = i64
+    L.kws_vad_workspace_bytes.argtypes = [vp, i32, i32]
+    L.kws_vad_workspace_bytes.restype = i64
+    L.kws_vad_detect.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.kws_vad_gather_clips.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     _lib = L
     return L
 
