@@ -966,6 +966,22 @@ int kws_stream_scan_postprocess(const kws_decoder *dec, const float *probs, int 
                                 int trigger_level, int chunk_size, int32_t *state, int32_t *index, double *score,
                                 int32_t *fired, int64_t out_stride, void *stream);
 
+/* Operating-point sweep: TriggerDetector.update (listen.py:538-559) walked over what a scan wrote, index / score (R, stride)
+ * with rec_chunks (R) chunks per recording, once per operating point p = (sensitivity[p], trigger_level[p]), p < P, every
+ * walk starting from {activation 0, record_index none}.  Argmax and decoding do not depend on the point, so a scan is
+ * made once and swept; one wave walks a recording at 64 points, one per lane.  Entries at or past rec_chunks[r] are not
+ * read.  counts (R, P, 5) int32 = {fires, hits, false_alarms, duplicates, latency_chunks_sum}.
+ * ev_off == NULL: no labels, fires alone is counted and the other four are 0.  Otherwise ev_off (R + 1) are CSR offsets
+ * into ev_class / ev_lo / ev_hi (E): recording r's events, in chunk units, sorted, ev_lo[e] <= ev_hi[e] < ev_lo[e + 1].
+ * A fire at chunk k of class c (the chunk's index) belongs to the event e with ev_lo[e] <= k <= ev_hi[e] if there is one
+ * and ev_class[e] == c: the first such fire is a hit and adds k - ev_lo[e] to the latency sum, later ones are duplicates.
+ * Every other fire is a false alarm, a fire of another class inside an event's window included.  All arrays are device
+ * memory; nothing is synchronised.  R == 0 or P == 0 does nothing. */
+int kws_stream_sweep(const int32_t *index, const double *score, int R, int64_t stride, const int32_t *rec_chunks,
+                     int background_index, int chunk_size, const double *sensitivity, const int32_t *trigger_level, int P,
+                     const int32_t *ev_off, const int32_t *ev_class, const int32_t *ev_lo, const int32_t *ev_hi,
+                     int32_t *counts, void *stream);
+
 /* ------------------------------------------------------------------------
  * Voice-activity detection of whole recordings: where the speech is, which files are silent, and the clips.  Replaces
  *   VoiceActivityDetector.detect_speech              tools/audio_process/speech_duration_check.py:149-176

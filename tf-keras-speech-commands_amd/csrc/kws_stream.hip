@@ -9,6 +9,8 @@
 //   update_vectors (windows)  listen.py:96-114    -> kws_stream_gather_windows (every chunk's feature matrix from the recording's rows)
 //   the prediction loop       listen.py:361-375   -> kws_stream_scan_postprocess (argmax / max / decode per chunk in parallel, then the
 //                                                    trigger walked in chunk order, one wave per recording)
+//   TriggerDetector.update    listen.py:538-559   -> kws_stream_sweep (the same walk over a scan's decoded scores at 64 operating points
+//                                                    per wave, one per lane, counted against labelled events)
 // Everything here is a few bytes per stream and one thread per stream: the kernels are latency-sized, the point of doing
 // them on the device is that probabilities, scores and detector state never leave HBM between the forward pass of one
 // chunk and the next (the whole step can sit in one hipGraph).  Arithmetic is float64 wherever the reference computes
@@ -233,6 +235,70 @@ __global__ __launch_bounds__(64) void scan_trigger_kernel(const int32_t *__restr
     if (lane == 0) { state[2 * (long)r] = st[0]; state[2 * (long)r + 1] = st[1]; }
 }
 
+// wave-uniform broadcast of lane j's value (j is the same in every lane): v_readlane into scalar registers, no LDS round trip
+__device__ __forceinline__ int lane_value(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
+__device__ __forceinline__ double lane_value(double v, int j)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+
+// Operating-point sweep.  block = one wave = (recording r, 64 operating points): lane l owns point p = 64 blockIdx.y + l and carries
+// ITS detector state, event cursor and counters in registers; the recording's (index, score) are loaded 64 chunks at a time, one per
+// lane, and handed to every lane's walk by lane_value.  A lane with p >= P walks like the others (the loads and broadcasts need the
+// whole wave) with a level no activation count exceeds, and stores nothing.  counts (R, P, 5) = {fires, hits, false alarms,
+// duplicates, sum over hits of (fire chunk - event's first chunk)}; every cell has one writer.
+__global__ __launch_bounds__(64) void sweep_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, long stride,
+                                                   const int32_t *__restrict__ rec_chunks, int background, int refractory,
+                                                   const double *__restrict__ sensitivity, const int32_t *__restrict__ trigger_level, int P,
+                                                   const int32_t *__restrict__ ev_off, const int32_t *__restrict__ ev_class,
+                                                   const int32_t *__restrict__ ev_lo, const int32_t *__restrict__ ev_hi,
+                                                   int32_t *__restrict__ counts)
+{
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int p = blockIdx.y * 64 + lane;
+    const bool owner = p < P;
+    const double sens = owner ? sensitivity[p] : 0.0;
+    const int level = owner ? trigger_level[p] : 0x7fffffff;
+    long T = rec_chunks[r];
+    T = T < 0 ? 0 : (T < stride ? T : stride);                                  // never past the row, whatever rec_chunks holds
+    const bool labelled = ev_off != nullptr;
+    int e = labelled ? ev_off[r] : 0;                                           // cursor: the first event that does not end before the last fire
+    const int e_end = labelled ? ev_off[r + 1] : 0;
+    bool found = false;                                                         // event e already detected by this point
+    int32_t st[2] = {0, -1};
+    int fires = 0, hits = 0, false_alarms = 0, duplicates = 0, latency = 0;
+    for (long base = 0; base < T; base += 64) {
+        const long i = base + lane;
+        int idx = -1;
+        double sc = 0.0;
+        if (i < T) { idx = index[r * stride + i]; sc = score[r * stride + i]; }
+        const int n = (int)(T - base < 64 ? T - base : 64);
+        for (int j = 0; j < n; ++j) {
+            const int ij = lane_value(idx, j);
+            const double sj = lane_value(sc, j);
+            if (!trigger_one(ij, sj, background, sens, level, refractory, st)) continue;
+            fires += 1;
+            if (!labelled) continue;
+            const int k = (int)base + j;
+            while (e < e_end && ev_hi[e] < k) { e += 1; found = false; }
+            if (e < e_end && ev_lo[e] <= k && ev_class[e] == ij) {
+                if (found) {
+                    duplicates += 1;
+                } else {
+                    found = true;
+                    hits += 1;
+                    latency += k - ev_lo[e];
+                }
+            } else {
+                false_alarms += 1;                                              // outside every window, or the wrong class inside one
+            }
+        }
+    }
+    if (!owner) return;
+    int32_t *out = counts + ((long)r * P + p) * 5;
+    out[0] = fires; out[1] = hits; out[2] = false_alarms; out[3] = duplicates; out[4] = latency;
+}
+
 static DecDev dec_dev(const kws_decoder *d)
 {
     DecDev v;
@@ -440,6 +506,22 @@ int kws_stream_scan_postprocess(const kws_decoder *dec, const float *probs, int 
     KWS_LAUNCH("scan_trigger_kernel", scan_trigger_kernel, dim3((unsigned)R), dim3(64), 0, s, index, score, n_chunks, rec_chunks, (long)k0,
                background_index, sensitivity, trigger_level, refractory_of(chunk_size), (long)out_stride, state, fired);
     KWS_LAUNCH_CHECK("scan_trigger_kernel");
+    return KWS_OK;
+}
+
+int kws_stream_sweep(const int32_t *index, const double *score, int R, int64_t stride, const int32_t *rec_chunks, int background_index,
+                     int chunk_size, const double *sensitivity, const int32_t *trigger_level, int P, const int32_t *ev_off,
+                     const int32_t *ev_class, const int32_t *ev_lo, const int32_t *ev_hi, int32_t *counts, void *stream)
+{
+    if (R < 0 || P < 0 || stride < 0 || chunk_size < 1) return fail(KWS_ERR_INVALID, "bad R=%d P=%d stride=%lld chunk_size=%d", R, P, (long long)stride, chunk_size);
+    if (R == 0 || P == 0) return KWS_OK;
+    if (!rec_chunks || !sensitivity || !trigger_level || !counts || ((!index || !score) && stride > 0)) return fail(KWS_ERR_INVALID, "null argument");
+    const long groups = ((long)P + 63) / 64;
+    if (groups > 65535) return fail(KWS_ERR_UNSUPPORTED, "%d operating points in one sweep (at most %d)", P, 65535 * 64);
+    KWS_LAUNCH("sweep_kernel", sweep_kernel, dim3((unsigned)R, (unsigned)groups), dim3(64), 0, static_cast<hipStream_t>(stream), index, score,
+               (long)stride, rec_chunks, background_index, refractory_of(chunk_size), sensitivity, trigger_level, P, ev_off, ev_class, ev_lo, ev_hi,
+               counts);
+    KWS_LAUNCH_CHECK("sweep_kernel");
     return KWS_OK;
 }
 

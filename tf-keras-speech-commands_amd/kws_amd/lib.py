@@ -243,6 +243,7 @@ def get_lib():
     L.kws_stream_postprocess.argtypes = [vp, vp, i32, i32, i32, f64, i32, i32, vp, vp, vp, vp, vp]
     L.kws_stream_gather_windows.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, i64, i32, fp, vp]
     L.kws_stream_scan_postprocess.argtypes = [vp, vp, i32, i32, i32, vp, i64, i32, f64, i32, i32, vp, vp, vp, vp, i64, vp]
+    L.kws_stream_sweep.argtypes = [vp, vp, i32, i64, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.kws_set_matrix_precision.argtypes = [i32]
     L.kws_get_matrix_precision.restype = i32
     L.kws_set_inference_precision.argtypes = [i32]

@@ -4,7 +4,9 @@ Mirrors the two helper classes of the reference's listen.py with the same constr
 methods -- `ThresholdDecoder` (listen.py:452-522) and `TriggerDetector` (listen.py:525-559) -- and adds `StreamBatch`,
 which runs the whole per-chunk loop of listen.py:350-375 (`update_vectors`, predict, argmax / max, decode, detector
 update) for S audio streams at once, and `scan`, the same loop over whole recordings that already lie in memory,
-parallel over time.  All arithmetic runs in the HIP library; there is no host fallback.
+parallel over time, and `sweep`, which walks the detector over a scan's decoded scores at a whole grid of operating points
+and counts hits, false alarms and misses against labelled events.  All arithmetic runs in the HIP library; there is no
+host fallback.
 """
 import ctypes
 
@@ -242,6 +244,10 @@ class ScanResult(object):
     def __iter__(self):
         return iter((self.index, self.score, self.fired, self.n_chunks, self.state))
 
+    def sweep(self, sensitivities, trigger_levels, chunk_size, **kwargs):
+        """`sweep` of this scan: the detector at every (sensitivity, trigger_level) of the grid, from the scores decoded once."""
+        return sweep(self, sensitivities, trigger_levels, chunk_size, **kwargs)
+
 
 def _pack_recordings(torch, recordings, lengths, device):
     """-> ((R, stride) int16 CUDA tensor, host list of lengths)"""
@@ -343,3 +349,149 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
         if return_probs:
             probs_all[:, k0:k0 + n] = probs.view(R, n, C)
     return ScanResult(index, score, fired, n_chunks, state, probs_all)
+
+
+def events_to_chunks(events, n_samples, chunk_size, tolerance_samples, background_index=0, num_classes=None):
+    """Labelled events in samples -> the chunk ranges in which a detection counts for them.  Pure Python, no device.
+
+    events: per recording a list of (class_index, start_sample, end_sample) with 0 <= start < end; n_samples: per recording
+    its sample count N.  An event becomes (class_index, lo, hi) with lo = start // chunk_size and
+    hi = min(T - 1, (end - 1 + tolerance_samples) // chunk_size), T = ceil(N / chunk_size): the detector may fire from the
+    chunk in which the keyword starts until `tolerance_samples` after its last sample, for as long as the keyword is still
+    inside the model's buffer.  Returns per recording the list sorted by lo.  Raises ValueError, naming the recording, for
+    an event that starts at or after the recording's end, a class that is the background or outside 0 .. num_classes - 1,
+    and events whose chunk ranges overlap (lo[e + 1] <= hi[e]): kws_stream_sweep gives every fire to one event at most."""
+    c, tol = int(chunk_size), int(tolerance_samples)
+    if c < 1 or tol < 0:
+        raise ValueError("events_to_chunks needs a positive chunk_size and tolerance_samples >= 0")
+    if len(events) != len(n_samples):
+        raise ValueError("%d event lists for %d recordings" % (len(events), len(n_samples)))
+    out = []
+    for r, (evs, N) in enumerate(zip(events, n_samples)):
+        N = int(N)
+        T = -(-N // c)
+        rows = []
+        for cls, start, end in evs:
+            cls, start, end = int(cls), int(start), int(end)
+            if not 0 <= start < end:
+                raise ValueError("recording %d: event (%d, %d, %d) needs 0 <= start < end" % (r, cls, start, end))
+            if start >= N:
+                raise ValueError("recording %d: event (%d, %d, %d) starts at or after the recording's end (%d samples)" % (r, cls, start, end, N))
+            if cls == background_index or cls < 0 or (num_classes is not None and cls >= int(num_classes)):
+                raise ValueError("recording %d: event (%d, %d, %d) has the background's class or one outside the model's" % (r, cls, start, end))
+            rows.append((cls, start // c, min(T - 1, (end - 1 + tol) // c)))
+        rows.sort(key=lambda v: v[1])
+        for a, b in zip(rows, rows[1:]):
+            if b[1] <= a[2]:
+                raise ValueError("recording %d: the chunk ranges %d..%d and %d..%d of two events overlap" % (r, a[1], a[2], b[1], b[2]))
+        out.append(rows)
+    return out
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+class SweepResult(object):
+    """What `sweep` counted.  fires / hits / false_alarms / duplicates / latency_chunks: (R, S, L) int32 tensors, element
+    (r, s, l) for recording r at sensitivities[s] and trigger_levels[l]; latency_chunks is the sum over the hits of
+    (chunk of the fire - first chunk of the event).  n_events: list of R ints; seconds: per-recording durations or None."""
+
+    def __init__(self, fires, hits, false_alarms, duplicates, latency_chunks, n_events, sensitivities, trigger_levels, seconds=None):
+        self.fires, self.hits, self.false_alarms, self.duplicates, self.latency_chunks = fires, hits, false_alarms, duplicates, latency_chunks
+        self.n_events = [int(v) for v in n_events]
+        self.sensitivities = [float(v) for v in sensitivities]
+        self.trigger_levels = [int(v) for v in trigger_levels]
+        self.seconds = seconds
+
+    def det(self, seconds=None):
+        """(miss_rate, fa_per_hour): host (S, L) float64 arrays over all recordings, miss_rate = 1 - sum(hits) / sum(n_events)
+        and fa_per_hour = sum(false_alarms) * 3600 / sum(seconds); NaN where the denominator is 0."""
+        seconds = self.seconds if seconds is None else seconds
+        if seconds is None:
+            raise ValueError("det needs the recordings' durations in seconds")
+        S, L = len(self.sensitivities), len(self.trigger_levels)
+        hits = _host(self.hits).astype(np.int64).reshape(-1, S, L).sum(axis=0)
+        fas = _host(self.false_alarms).astype(np.int64).reshape(-1, S, L).sum(axis=0)
+        n_ev, total_s = sum(self.n_events), float(np.sum(np.asarray(seconds, dtype=np.float64)))
+        nan = np.full((S, L), np.nan)
+        miss = 1.0 - hits / float(n_ev) if n_ev > 0 else nan
+        fa = fas * 3600.0 / total_s if total_s > 0 else nan.copy()
+        return miss, fa
+
+    def best(self, seconds=None, max_fa_per_hour=0.0):
+        """The operating point to ship: among the points with fa_per_hour <= max_fa_per_hour the one with the lowest miss
+        rate; ties go to the lower fa_per_hour, then the higher sensitivity, then the lower trigger level.  Returns a dict
+        (s, l, sensitivity, trigger_level, miss_rate, fa_per_hour) or None when no point qualifies.  Without events every
+        miss rate is NaN and the tie-breaks alone decide."""
+        miss, fa = self.det(seconds)
+        pick = None
+        for s, sens in enumerate(self.sensitivities):
+            for l, level in enumerate(self.trigger_levels):
+                if not fa[s, l] <= max_fa_per_hour:                  # NaN does not qualify
+                    continue
+                m = float(miss[s, l])
+                key = (float("inf") if m != m else m, float(fa[s, l]), -sens, level)
+                if pick is None or key < pick[0]:
+                    pick = (key, {"s": s, "l": l, "sensitivity": sens, "trigger_level": level, "miss_rate": m, "fa_per_hour": float(fa[s, l])})
+        return None if pick is None else pick[1]
+
+
+def sweep(result, sensitivities, trigger_levels, chunk_size, events=None, lengths=None, tolerance_samples=None, background_index=0,
+          pr=None):
+    """The trigger detector over scanned recordings at every point of the grid sensitivities x trigger_levels (sensitivity
+    the major axis) in one kws_stream_sweep launch: the scan's argmax and decoded scores do not depend on the operating
+    point, so they are computed once and only TriggerDetector.update is walked again, 64 points per wave.
+
+    result: a `ScanResult`, or (index, score, n_chunks) with (R, stride) int32 / float64 CUDA tensors as `scan` writes
+    them.  events: per recording a list of (class_index, start_sample, end_sample), converted by `events_to_chunks` with
+    `lengths` (sample counts; default n_chunks * chunk_size) and `tolerance_samples` (default pr.max_samples: the keyword
+    stays inside the model's buffer for that long after it ends); None counts fires only.  The decoder is the scan's.
+    Returns a `SweepResult`; nothing is synchronised."""
+    torch = _torch()
+    if isinstance(result, ScanResult):
+        index, score, n_chunks = result.index, result.score, result.n_chunks
+    else:
+        index, score, n_chunks = result
+    n_chunks = [int(v) for v in n_chunks]
+    chunk_size = int(chunk_size)
+    if chunk_size < 1:
+        raise ValueError("chunk_size must be positive")
+    if not (index.is_cuda and score.is_cuda and index.dtype == torch.int32 and score.dtype == torch.float64 and index.dim() == 2
+            and index.shape == score.shape):
+        raise ValueError("index / score must be (R, stride) int32 / float64 CUDA tensors of one shape")
+    R, stride = int(index.shape[0]), int(index.shape[1])
+    if len(n_chunks) != R or any(v < 0 or v > stride for v in n_chunks):
+        raise ValueError("n_chunks must give one chunk count in 0..%d per recording" % stride)
+    sens = [float(v) for v in sensitivities]
+    levels = [int(v) for v in trigger_levels]
+    S, L = len(sens), len(levels)
+    P = S * L
+    dev = index.device
+    index, score = index.contiguous(), score.contiguous()
+    n_events = [0] * R
+    ev = [0, 0, 0, 0]                                              # ev_off, ev_class, ev_lo, ev_hi: NULL without labels
+    if events is not None:
+        if tolerance_samples is None:
+            if pr is None:
+                from classifier.params import pr
+            tolerance_samples = pr.max_samples
+        lens = [n * chunk_size for n in n_chunks] if lengths is None else [int(v) for v in _host(lengths).tolist()]
+        if [-(-n // chunk_size) for n in lens] != n_chunks:
+            raise ValueError("lengths do not give the scan's chunk counts at chunk_size=%d" % chunk_size)
+        rows = events_to_chunks(events, lens, chunk_size, tolerance_samples, background_index)
+        n_events = [len(v) for v in rows]
+        off = np.concatenate(([0], np.cumsum(n_events))).astype(np.int32)
+        flat = np.array([e for v in rows for e in v] or [(0, 0, 0)], dtype=np.int32).reshape(-1, 3)
+        keep = [torch.from_numpy(off).to(dev)] + [torch.from_numpy(np.ascontiguousarray(flat[:, i])).to(dev) for i in range(3)]
+        ev = [t.data_ptr() for t in keep]
+    counts = torch.zeros((R, P, 5), dtype=torch.int32, device=dev)
+    if R > 0 and P > 0:
+        d_chunks = torch.tensor(n_chunks, dtype=torch.int32).to(dev)
+        d_sens = torch.tensor(np.repeat(sens, L), dtype=torch.float64).to(dev)
+        d_level = torch.tensor(np.tile(levels, S), dtype=torch.int32).to(dev)
+        _l.check(_l.get_lib().kws_stream_sweep(index.data_ptr(), score.data_ptr(), R, stride, d_chunks.data_ptr(), int(background_index),
+                                               chunk_size, d_sens.data_ptr(), d_level.data_ptr(), P, ev[0], ev[1], ev[2], ev[3],
+                                               counts.data_ptr(), _stream()))
+    f = counts.permute(2, 0, 1).contiguous().view(5, R, S, L)
+    return SweepResult(f[0], f[1], f[2], f[3], f[4], n_events, sens, levels)

@@ -4,13 +4,15 @@
 constructor keywords and methods (`update_vectors`, `predict`, `run_wav`, `on_prediction`, `on_activation`), built on
 kws_amd.stream.StreamBatch -- feature update, forward pass, score decoding and trigger logic all run on the device.
 `Listener.scan_wav` (CLI: --scan) is the offline form for recorded audio: whole files, or a directory of them, go through
-kws_amd.stream.scan at once and give per chunk what `run_wav` gives.
+kws_amd.stream.scan at once and give per chunk what `run_wav` gives.  `Listener.sweep_wav` (CLI: --sweep) scans labelled
+recordings once and evaluates the detector at a whole grid of (sensitivity, trigger_level): miss rate against false alarms per hour.
 
 Differences from listen.py: checkpoints are the `.npz` files classifier.model writes (no h5/pb/tflite/onnx/mnn
 back ends); there is no PyAudio in this image, so `run_microphone` raises and `run_wav` does not play the audio while it
 analyses it; `Listener.batch(n)` gives the many-stream form for serving.
 """
 import argparse
+import json
 import os
 import wave
 from shutil import get_terminal_size
@@ -21,6 +23,7 @@ from classifier.model import get_model
 from classifier.params import inject_params, pr
 from common.utils import get_classes
 from kws_amd.stream import StreamBatch, ThresholdDecoder, TriggerDetector, scan  # noqa: F401  (re-exported like listen.py:452,525)
+from kws_amd.stream import sweep
 
 default_config = {                                     # listen.py:31-40
     "model_path": '',
@@ -36,6 +39,52 @@ default_config = {                                     # listen.py:31-40
     "scan": False,
     "scan_tile": 4096,
 }
+
+
+def parse_sensitivities(text):
+    """--sensitivities: 'a,b,c' (a list) or 'lo:hi:n' (n evenly spaced values from lo to hi, both ends included)"""
+    text = text.strip()
+    if ':' in text:
+        parts = text.split(':')
+        if len(parts) != 3:
+            raise ValueError("expected lo:hi:n, got %r" % text)
+        lo, hi, n = float(parts[0]), float(parts[1]), int(parts[2])
+        if n < 1 or (n == 1 and lo != hi):
+            raise ValueError("lo:hi:n needs n >= 2 (or lo == hi), got %r" % text)
+        return [lo] if n == 1 else [lo + (hi - lo) * i / (n - 1) for i in range(n - 1)] + [hi]
+    vals = [float(v) for v in text.split(',') if v.strip()]
+    if not vals:
+        raise ValueError("no sensitivity in %r" % text)
+    return vals
+
+
+def parse_trigger_levels(text):
+    """--trigger_levels: '1,2,3'"""
+    vals = [int(v) for v in text.split(',') if v.strip()]
+    if not vals or min(vals) < 0:
+        raise ValueError("expected non-negative trigger levels, got %r" % text)
+    return vals
+
+
+def parse_labels(path, class_names, sample_rate):
+    """The labels file of --sweep: text, one event per line, `wav_name class_name start_seconds end_seconds`; '#' starts a
+    comment.  -> {wav_name: [(class_index, start_sample, end_sample), ...]}; a wav it does not mention has no events."""
+    out = {}
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            fields = line.split('#', 1)[0].split()
+            if not fields:
+                continue
+            if len(fields) != 4:
+                raise ValueError("%s:%d: expected `wav_name class_name start_seconds end_seconds`" % (path, no))
+            name, cls, start, end = fields
+            if cls not in class_names:
+                raise ValueError("%s:%d: unknown class name %r" % (path, no, cls))
+            a, b = int(round(float(start) * sample_rate)), int(round(float(end) * sample_rate))
+            if not 0 <= a < b:
+                raise ValueError("%s:%d: an event needs 0 <= start < end" % (path, no))
+            out.setdefault(os.path.basename(name), []).append((class_names.index(cls), a, b))
+    return out
 
 
 class Listener(object):
@@ -136,6 +185,14 @@ class Listener(object):
         wf.close()
         return pcm
 
+    def _scan_files(self, files):
+        """-> (ScanResult of the files, their sample counts): read, packed and scanned at once"""
+        pcm = [self._read_wav(p) for p in files]
+        res = scan(self.pr, self.model._device(), pcm, chunk_size=self.chunk_size, class_names=self.class_names,
+                   sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
+                   quantized=self.quantized, tile=self.scan_tile)
+        return res, [int(a.size) for a in pcm]
+
     def scan_wav(self, paths=None, quiet=True):
         """run_wav for whole files at once (kws_amd.stream.scan): `paths` is one wav or a list of them (default: input_wav).
         Returns per file the list run_wav returns, [(index, score, fired), ...] per chunk, every file starting from a fresh
@@ -145,10 +202,7 @@ class Listener(object):
             paths = self.input_wav
         single = isinstance(paths, (str, bytes, os.PathLike))
         files = [paths] if single else list(paths)
-        pcm = [self._read_wav(p) for p in files]
-        res = scan(self.pr, self.model._device(), pcm, chunk_size=self.chunk_size, class_names=self.class_names,
-                   sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
-                   quantized=self.quantized, tile=self.scan_tile)
+        res, _ = self._scan_files(files)
         index, score, fired = res.index.cpu().numpy(), res.score.cpu().numpy(), res.fired.cpu().numpy()
         out, self.scan_times = [], []
         for r, n in enumerate(res.n_chunks):
@@ -164,7 +218,56 @@ class Listener(object):
             self.scan_times.append(times)
         return out[0] if single else out
 
+    def sweep_wav(self, paths, labels, sensitivities, trigger_levels, tolerance_s=None):
+        """One scan of the files, then the detector at every (sensitivity, trigger_level) of the grid (kws_amd.stream.sweep).
+        `labels`: a labels file (see parse_labels), a dict {wav_name: [(class_index, start_sample, end_sample), ...]} keyed by
+        file name without its directory, or None (fires are counted, nothing else); a wav without an entry is a negative
+        recording.  tolerance_s: how long after a keyword's end a detection still counts for it (default: the model's buffer).
+        Returns the SweepResult, its `seconds` set to the files' durations; `self.sweep_scan` keeps the scan."""
+        files = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+        if isinstance(labels, (str, bytes, os.PathLike)):
+            labels = parse_labels(labels, self.class_names, self.pr.sample_rate)
+        res, lens = self._scan_files(files)
+        events = None if labels is None else [labels.get(os.path.basename(p), []) for p in files]
+        tol = None if tolerance_s is None else int(round(tolerance_s * self.pr.sample_rate))
+        out = sweep(res, sensitivities, trigger_levels, self.chunk_size, events=events, lengths=lens, tolerance_samples=tol, pr=self.pr)
+        out.seconds = [n / float(self.pr.sample_rate) for n in lens]
+        self.sweep_scan = res
+        return out
+
+    def run_sweep(self):
+        """--sweep: the (S, L) table of miss rate and false alarms per hour, and the chosen point under --max_fa_per_hour"""
+        paths = self.input_wav
+        if os.path.isdir(paths):
+            paths = sorted(os.path.join(paths, n) for n in os.listdir(paths) if n.lower().endswith('.wav'))
+        files = [paths] if isinstance(paths, str) else paths
+        sens = parse_sensitivities(getattr(self, 'sensitivities', None) or str(self.sensitivity))
+        levels = parse_trigger_levels(getattr(self, 'trigger_levels', None) or str(self.trigger_level))
+        res = self.sweep_wav(files, getattr(self, 'labels_path', None), sens, levels, tolerance_s=getattr(self, 'tolerance_s', None))
+        miss, fa = res.det()
+        print('%d files, %.1f s, %d events; miss rate / false alarms per hour' % (len(files), sum(res.seconds), sum(res.n_events)))
+        print('%11s' % 'sensitivity' + ''.join('%18s' % ('level %d' % l) for l in levels))
+        for s, v in enumerate(sens):
+            print('%11.4f' % v + ''.join('%9.4f /%7.2f' % (miss[s, l], fa[s, l]) for l in range(len(levels))))
+        budget = getattr(self, 'max_fa_per_hour', None)
+        best = None if budget is None else res.best(max_fa_per_hour=budget)
+        if budget is not None:
+            if best is None:
+                print('no operating point stays within %g false alarms per hour' % budget)
+            else:
+                print('chosen: sensitivity %.4f, trigger_level %d (miss rate %.4f, %.2f false alarms per hour)'
+                      % (best['sensitivity'], best['trigger_level'], best['miss_rate'], best['fa_per_hour']))
+        if getattr(self, 'sweep_out', None):
+            nan = lambda a: [[None if v != v else float(v) for v in row] for row in a]          # noqa: E731  (JSON has no NaN)
+            with open(self.sweep_out, 'w') as f:
+                json.dump({"files": files, "seconds": res.seconds, "n_events": res.n_events, "sensitivities": sens, "trigger_levels": levels,
+                           "miss_rate": nan(miss), "fa_per_hour": nan(fa), "max_fa_per_hour": budget, "chosen": best}, f, indent=1)
+                f.write("\n")
+        return res
+
     def run(self):
+        if self.input_wav and getattr(self, 'sweep', False):
+            return self.run_sweep()
         if self.input_wav and self.scan:
             paths = self.input_wav
             if os.path.isdir(paths):
@@ -197,6 +300,17 @@ def main():
     parser.add_argument('--scan', action='store_true',
                         help='offline scan: the whole recording(s) at once instead of chunk by chunk; prints every activation with its time')
     parser.add_argument('--scan_tile', type=int, default=default_config['scan_tile'], help='windows per forward launch of --scan')
+    parser.add_argument('--sweep', action='store_true',
+                        help='scan the recording(s) once and evaluate the detector at every (sensitivity, trigger level) of a grid')
+    parser.add_argument('--labels_path', type=str, default=None,
+                        help='--sweep: text file, one event per line: wav_name class_name start_seconds end_seconds (# comments)')
+    parser.add_argument('--sensitivities', type=str, default=None, help='--sweep: a,b,c or lo:hi:n (default: --sensitivity alone)')
+    parser.add_argument('--trigger_levels', type=str, default=None, help='--sweep: 1,2,3,... (default: --trigger_level alone)')
+    parser.add_argument('--tolerance_s', type=float, default=None,
+                        help='--sweep: seconds after an event\'s end in which a detection still counts for it (default: the buffer length)')
+    parser.add_argument('--max_fa_per_hour', type=float, default=None,
+                        help='--sweep: report the point with the lowest miss rate within this many false alarms per hour')
+    parser.add_argument('--sweep_out', type=str, default=None, help='--sweep: write the table and the chosen point to this JSON file')
     args = parser.parse_args()
     if not args.model_path and not args.quantized_path:
         parser.error('one of --model_path and --quantized_path is required')
