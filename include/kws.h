@@ -853,9 +853,18 @@ int kws_rmsprop_step(float *params, const float *grads, float *accum, int64_t n,
  * (every block lies inside one segment), then the fused update, each of whose blocks sums the partials it needs in a
  * fixed order.  No atomics, no host synchronisation: the same inputs give the same bits.
  * Elements outside every segment are not touched.
+ *
+ * Weight averaging (tensorflow-addons' MovingAverage, SWA and Lookahead) is folded into the update pass: with p' the new
+ * parameter and avg the averaging slot,
+ *   KWS_AVG_BLEND    avg = avg - (avg - p') * avg_alpha;  p' is stored unchanged   (avg_alpha == 1: avg = p')
+ *   KWS_AVG_SYNC     s = avg + avg_alpha * (p' - avg);  avg = s and p = s
+ *   KWS_AVG_NONE     avg is neither read nor written
+ * The step keeps no schedule: the caller chooses mode and alpha per step (common/model_utils.py: average_args) and starts the
+ * slot as a copy of params.  No further launch, no atomics.
  * ---------------------------------------------------------------------- */
 enum { KWS_OPT_SGD = 0, KWS_OPT_RMSPROP = 1, KWS_OPT_ADAM = 2 };
 enum { KWS_OPT_NESTEROV = 1, KWS_OPT_CENTERED = 2, KWS_OPT_AMSGRAD = 4 };
+enum { KWS_AVG_NONE = 0, KWS_AVG_BLEND = 1, KWS_AVG_SYNC = 2 };
 
 /* Host only.  Segment i is [offsets[i], offsets[i] + sizes[i]): sorted, not overlapping, offsets multiples of 4, sizes > 0.
  * Returns the bytes of the optimizer workspace (a block table, then one double per block), or a negative kws error code. */
@@ -888,10 +897,18 @@ typedef struct kws_optimizer_args {
     float clipvalue;        /* 0: off */
     float clipnorm;         /* 0: off */
     float global_clipnorm;  /* 0: off */
+    /* appended: a zero-filled tail is "no averaging" */
+    float *avg;             /* averaging slot: same length and layout as params, 16-byte aligned; NULL when avg_mode == 0 */
+    int32_t avg_mode;       /* KWS_AVG_NONE / KWS_AVG_BLEND / KWS_AVG_SYNC */
+    float avg_alpha;        /* BLEND: weight of the new parameter; SYNC: slow_step_size; in [0, 1] */
 } kws_optimizer_args;
 
 /* One update on `stream` by the rules above.  The buffers the kind / flags / momentum need are non-NULL and 16-byte aligned. */
 int kws_optimizer_step(const kws_optimizer_args *args, void *stream);
+
+/* Exchanges params and avg inside the segments of the planned workspace `ws` (device copy, as kws_optimizer_args.ws); padding is
+ * not touched.  Exact: two calls restore every bit. */
+int kws_optimizer_swap(float *params, float *avg, const void *ws, int64_t ws_bytes, int32_t n_blocks, void *stream);
 
 /* ------------------------------------------------------------------------
  * Streaming post-processing: replaces the per-chunk work of listen.py for S

@@ -7,6 +7,7 @@ HIP kernels behind include/kws.h; there is no CPU path (using the model without 
 
 Beyond the reference: `fit` / `predict` / `evaluate` also accept raw audio (N, samples) and featurize it on the GPU in
 front of the network, and under torch.distributed `fit` runs data-parallel (kws_amd.parallel)."""
+import contextlib
 import math
 import os
 import time
@@ -203,10 +204,39 @@ class KWSModel(object):
             return self._class_weights_dev, int(self.loss.ignore_index or 0)
         return None, int(self.loss.ignore_index or 0)
 
+    # ---- weight averaging (common.model_utils MovingAverage / SWA) -------------------------------------------------
+    def _averaging(self):
+        """the compiled optimizer when its slot is an average of the weights, else None"""
+        opt = self.optimizer
+        return opt if getattr(opt, "average_args", None) is not None and opt.swappable else None
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the context the trainable weights are the optimizer's averages (predict / evaluate / save see them); on leaving, the
+        training weights are back, bit for bit (kws_optimizer_swap on the device, twice).  BatchNormalization moving statistics have
+        no slot and are the same inside and outside.  Before the first update the averages are the weights: nothing is swapped."""
+        if self._averaging() is None:
+            raise TypeError("averaged_weights() needs a model compiled with a MovingAverage or SWA optimizer")
+        dm = self._dm
+        if dm is None or dm.opt_avg is None:
+            yield self
+            return
+        dm.swap_average()
+        try:
+            yield self
+        finally:
+            dm.swap_average()
+
+    def _assign_average(self):
+        dm = self._dm
+        if dm is not None and dm.opt_avg is not None:
+            dm.params.copy_(dm.opt_avg)     # the padding between variables is the same in both (the slot started as a copy)
+            dm.invalidate_prepared()
+
     def _apply_optimizer(self, dm):
         opt = self.optimizer
         lr = opt.current_lr()
-        if opt.extended:                # clipping / momentum / centered / amsgrad: kws_optimizer_step on the (exchanged) gradient
+        if opt.extended:                # clipping / momentum / centered / amsgrad / averaging: kws_optimizer_step on the (exchanged) gradient
             dm.optimizer_step(opt, lr)
         elif opt.kind == 'adam':
             dm.adam_step(lr, opt.beta_1, opt.beta_2, opt.epsilon)
@@ -276,6 +306,9 @@ class KWSModel(object):
         on the host waits for the device inside an epoch.  `pipeline=False` runs the same arithmetic step by step on one stream
         (bit-identical results in the deterministic gradient mode: tests/test_host_api_gpu.py).
 
+        `validate_averaged=True` under a MovingAverage / SWA optimizer runs the epoch-end evaluate inside averaged_weights(): val_loss and
+        val_accuracy then describe the averaged weights (the ones common.callbacks.AverageModelCheckpoint saves).
+
         Raw audio only: `sample_lengths` (N,) is the valid length of every row (a shorter clip keeps its head and is left-padded with zeros
         by the featurizer, as extract_features does); `augment` (kws_amd.augment.WaveAugment) mixes background noise into every training
         clip, drawn afresh for every step (tools/audio_process/add_noise.py of the reference, done offline there).  Validation and
@@ -289,6 +322,7 @@ class KWSModel(object):
         pipelined = bool(kwargs.pop("pipeline", True))
         augment = kwargs.pop("augment", None)
         sample_lengths = kwargs.pop("sample_lengths", None)
+        validate_averaged = bool(kwargs.pop("validate_averaged", False)) and self._averaging() is not None
         if dp.active:
             dp.broadcast_(dm.params)
             dp.broadcast_(dm.state)
@@ -415,7 +449,8 @@ class KWSModel(object):
             dt = time.time() - t0                # the device is idle again here (tot.cpu() waited for the last step)
             logs = {'loss': float(tot[0] / tot[2]), 'accuracy': float(tot[1] / tot[2])}
             if validation_data is not None and (epoch + 1) % validation_freq == 0:
-                vl, va = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size, verbose=0)
+                with (self.averaged_weights() if validate_averaged else contextlib.nullcontext()):
+                    vl, va = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size, verbose=0)
                 logs['val_loss'], logs['val_accuracy'] = vl, va
             logs['lr'] = self.optimizer.current_lr()
             logs['clips_per_sec'] = float(tot[2] / dt) if dt > 0 else 0.0

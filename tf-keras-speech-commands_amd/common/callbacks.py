@@ -49,9 +49,35 @@ class ModelCheckpoint(Callback):
             self.best = cur
         path = self.filepath.format(epoch=epoch + 1, **logs)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        self.model.save(path)
+        self._save(path)
         if self.verbose:
             print('Epoch %05d: saving model to %s' % (epoch + 1, path))
+
+    def _save(self, path):
+        self.model.save(path)
+
+
+class AverageModelCheckpoint(ModelCheckpoint):
+    """ModelCheckpoint for a model trained under MovingAverage / SWA (tensorflow-addons' callback of this name): with
+    update_weights=False the file holds the averaged weights and training goes on from its own; with True the averages are first
+    assigned to the model for good (optimizer.assign_average_vars) and then saved."""
+
+    def __init__(self, update_weights, filepath, **kwargs):
+        ModelCheckpoint.__init__(self, filepath, **kwargs)
+        self.update_weights = bool(update_weights)
+
+    def set_model(self, model):
+        if getattr(model.optimizer, "average_args", None) is None or not model.optimizer.swappable:
+            raise TypeError("AverageModelCheckpoint is only used when training with MovingAverage or SWA")
+        ModelCheckpoint.set_model(self, model)
+
+    def _save(self, path):
+        if self.update_weights:
+            self.model.optimizer.assign_average_vars(self.model)
+            self.model.save(path)
+        else:
+            with self.model.averaged_weights():
+                self.model.save(path)
 
 
 class ReduceLROnPlateau(Callback):

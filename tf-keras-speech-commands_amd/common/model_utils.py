@@ -1,10 +1,13 @@
 """Optimizer / learning-rate schedule factory (host mirror of the reference's common/model_utils.py:17-58).
 
 The returned objects are small descriptors; the arithmetic runs in the fused HIP optimizer kernels
-(kws_adam_step / kws_rmsprop_step / kws_sgd_step, and kws_optimizer_step when clipping, momentum, centered or amsgrad is on).  The schedules restate the tf.keras ones the reference picks:
+(kws_adam_step / kws_rmsprop_step / kws_sgd_step, and kws_optimizer_step when clipping, momentum, centered or amsgrad is on).
+MovingAverage / SWA / Lookahead (get_averaged_optimizer) wrap one of them; their averaging slot is updated inside kws_optimizer_step.
+The schedules restate the tf.keras ones the reference picks:
 CosineDecay(alpha=0.2), ExponentialDecay(decay_rate=0.9), PolynomialDecay(end = lr/100, power 1),
 PiecewiseConstantDecay([500, 0.9*S, S] -> [1e-3, lr, lr/10, lr/100])."""
 import math
+import struct
 
 
 class LearningRateSchedule(object):
@@ -187,7 +190,130 @@ def get_optimizer(optim_type, learning_rate, average_type=None, decay_type='cosi
         raise ValueError('Unsupported optimizer type')
 
     if average_type:
-        # the reference wraps with tensorflow-addons (MovingAverage / SWA / Lookahead), which is out of scope here
+        # the factory itself stays without averaging (the reference's train.py passes average_type=None too); wrap its result with
+        # get_averaged_optimizer(average_type, optimizer) below
         raise ValueError('Unsupported average type')
 
     return optimizer
+
+
+AVG_NONE, AVG_BLEND, AVG_SYNC = 0, 1, 2          # include/kws.h KWS_AVG_*
+
+
+def _f32(x):
+    """a double rounded to float32, as the kernel receives it"""
+    return struct.unpack('f', struct.pack('f', float(x)))[0]
+
+
+class AveragedOptimizer(Optimizer):
+    """Base of the weight-averaging wrappers (tensorflow-addons' MovingAverage, SWA, Lookahead) around one Optimizer.
+
+    The wrapped optimizer keeps the hyperparameters, the clip options, the learning rate and `iterations`; the wrapper only decides,
+    per step, what happens to the averaging slot: average_args(k) -> (mode, alpha) for the update after k earlier ones
+    (include/kws.h KWS_AVG_*; alpha computed in double, then rounded to float32).  The slot lives on the device beside the parameters
+    (DeviceModel.opt_avg, a copy of them when first needed) and is updated inside kws_optimizer_step, so `extended` is always True."""
+    swappable = True       # the slot is an average to evaluate / save with (MovingAverage, SWA); Lookahead's is not
+
+    def __init__(self, optimizer):
+        if isinstance(optimizer, AveragedOptimizer):
+            raise TypeError("cannot wrap %s: it is an averaging wrapper already" % type(optimizer).__name__)
+        if not isinstance(optimizer, Optimizer):
+            raise TypeError("optimizer must come from common.model_utils.get_optimizer")
+        self.__dict__['optimizer'] = optimizer
+
+    def __getattr__(self, name):       # hyperparameters, clip options, ...: the wrapped optimizer's
+        if 'optimizer' not in self.__dict__:
+            raise AttributeError(name)
+        return getattr(self.__dict__['optimizer'], name)
+
+    kind = property(lambda self: self.optimizer.kind)
+    extended = property(lambda self: True)
+    iterations = property(lambda self: self.optimizer.iterations, lambda self, v: setattr(self.optimizer, 'iterations', v))
+    learning_rate = property(lambda self: self.optimizer.learning_rate, lambda self, v: setattr(self.optimizer, 'learning_rate', v))
+
+    def current_lr(self):
+        return self.optimizer.current_lr()
+
+    def set_lr(self, value):
+        self.optimizer.set_lr(value)
+
+    def average_args(self, k):
+        raise NotImplementedError
+
+    def assign_average_vars(self, model):
+        """copy the averages into `model`'s trainable weights for good (tfa's method of that name).  BatchNormalization moving
+        statistics have no slot and stay.  Before the first update the averages are the weights: nothing to do."""
+        if not self.swappable:
+            raise TypeError("%s keeps slow weights, not an average to assign" % type(self).__name__)
+        model._assign_average()
+
+
+def _check_unit(name, value):
+    if not (0 <= float(value) <= 1):
+        raise ValueError("`%s` must be between [0, 1], got %r" % (name, value))
+    return float(value)
+
+
+def _check_int(name, value, least):
+    if int(value) != value or int(value) < least:
+        raise ValueError("`%s` must be an integer >= %d, got %r" % (name, least, value))
+    return int(value)
+
+
+class MovingAverage(AveragedOptimizer):
+    """exponential moving average of the weights: avg -= (avg - p) (1 - average_decay) after every update from `start_step` on; before
+    that the average follows the weights"""
+
+    def __init__(self, optimizer, average_decay=0.99, start_step=0):
+        AveragedOptimizer.__init__(self, optimizer)
+        self.average_decay, self.start_step = _check_unit("average_decay", average_decay), _check_int("start_step", start_step, 0)
+
+    def average_args(self, k):
+        return AVG_BLEND, (1.0 if k < self.start_step else _f32(1.0 - self.average_decay))
+
+
+class SWA(AveragedOptimizer):
+    """stochastic weight averaging: the running mean of the weights after updates start_averaging, start_averaging + average_period, ..."""
+
+    def __init__(self, optimizer, start_averaging=0, average_period=10):
+        AveragedOptimizer.__init__(self, optimizer)
+        self.start_averaging = _check_int("start_averaging", start_averaging, 0)
+        self.average_period = _check_int("average_period", average_period, 1)
+
+    def average_args(self, k):
+        d = k - self.start_averaging
+        if d < 0 or d % self.average_period:
+            return AVG_NONE, 0.0
+        return AVG_BLEND, _f32(1.0 / (d // self.average_period + 1))
+
+
+class Lookahead(AveragedOptimizer):
+    """every sync_period updates the slow weights move slow_step_size of the way to the fast ones, and the fast ones restart there"""
+    swappable = False
+
+    def __init__(self, optimizer, sync_period=6, slow_step_size=0.5):
+        AveragedOptimizer.__init__(self, optimizer)
+        self.sync_period = _check_int("sync_period", sync_period, 1)
+        self.slow_step_size = _check_unit("slow_step_size", slow_step_size)
+
+    def average_args(self, k):
+        if (k + 1) % self.sync_period:
+            return AVG_NONE, 0.0
+        return AVG_SYNC, _f32(self.slow_step_size)
+
+
+# the reference's constants for its three average types
+AVERAGE_TYPES = {'ema': lambda o: MovingAverage(o, average_decay=0.99),
+                 'swa': lambda o: SWA(o, start_averaging=0, average_period=10),
+                 'lookahead': lambda o: Lookahead(o, sync_period=6, slow_step_size=0.5)}
+
+
+def get_averaged_optimizer(average_type, optimizer):
+    """`optimizer` under the averaging wrapper `average_type` names ('ema' / 'swa' / 'lookahead', any case), with the constants the
+    reference's function of the same name uses; None returns the optimizer as it is"""
+    if average_type is None:
+        return optimizer
+    wrap = AVERAGE_TYPES.get(average_type.lower()) if isinstance(average_type, str) else None
+    if wrap is None:
+        raise ValueError('Unsupported average type')
+    return wrap(optimizer)

@@ -8,6 +8,11 @@
 //   2. opt_update_kernel: a block sums the partials it needs -- its own segment's, or all of them for the global norm -- in a fixed
 //      order, forms the scale, and updates its float4s.  Every block of a segment runs the same sum, so they agree on the bits.
 // No atomics and no arrival ticket: two launches, the same bits from run to run.
+//
+// Weight averaging (kws_optimizer_args.avg / avg_mode / avg_alpha) rides in opt_update_kernel: the new parameter is still in registers
+// when the averaging slot is read, folded and stored, so MovingAverage / SWA / Lookahead cost one more read-modify-write of that pass
+// and no launch.  The mode is a template parameter: with KWS_AVG_NONE the slot is not touched and the code is the one without it.
+// kws_optimizer_swap exchanges params and the slot over the same block table.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -30,7 +35,7 @@ static_assert(sizeof(OptBlock) == 32, "OptBlock layout");
 enum { kNormNone = 0, kNormVar = 1, kNormGlobal = 2 };
 
 struct OptCoef {
-    float lr, lr_t, b1, b2, eps, mom, gs, clipvalue, clipnorm;
+    float lr, lr_t, b1, b2, eps, mom, gs, clipvalue, clipnorm, alpha;
     int flags, n_blocks;
 };
 
@@ -111,11 +116,26 @@ __device__ __forceinline__ void update_one(float &p, float ge, float &m, float &
     }
 }
 
-template <int KIND, int NORM>
+// the averaging slot a against the new parameter p.  BLEND is tfa's moving_average_update form (a -= (a - p) alpha: alpha == 1 gives p
+// exactly) and leaves p; SYNC is Lookahead's slow step, which both take.  Contraction off, as in update_one.
+template <int AVG>
+__device__ __forceinline__ void average_one(float &p, float &a, float alpha)
+{
+#pragma clang fp contract(off)
+    if (AVG == KWS_AVG_BLEND) {
+        a = a - (a - p) * alpha;
+    } else if (AVG == KWS_AVG_SYNC) {
+        a = a + alpha * (p - a);
+        p = a;
+    }
+}
+
+template <int KIND, int NORM, int AVG>
 __global__ __launch_bounds__(kOptThreads) void opt_update_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                                  float *__restrict__ v, float *__restrict__ vh, float *__restrict__ mg,
-                                                                 float *__restrict__ mo, const OptBlock *__restrict__ tab,
-                                                                 const double *__restrict__ partial, OptCoef c)
+                                                                 float *__restrict__ mo, float *__restrict__ av,
+                                                                 const OptBlock *__restrict__ tab, const double *__restrict__ partial,
+                                                                 OptCoef c)
 {
     const OptBlock b = tab[blockIdx.x];
     float num = 1.f, den = 1.f, scale = 1.f;        // per variable: g*num/den (tf.clip_by_norm); global: g*scale
@@ -156,6 +176,13 @@ __global__ __launch_bounds__(kOptThreads) void opt_update_kernel(float *__restri
         float *pp = &pv.x, *gp = &gv.x, *mp = &mv.x, *vp = &vv.x, *hp = &hv.x, *gmp = &gm.x, *op = &ov.x;
 #pragma unroll
         for (int e = 0; e < 4; ++e) update_one<KIND>(pp[e], xform(gp[e]), mp[e], vp[e], hp[e], gmp[e], op[e], c);
+        if (AVG != KWS_AVG_NONE) {
+            float4 av4 = *reinterpret_cast<float4 *>(av + i);
+            float *ap = &av4.x;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) average_one<AVG>(pp[e], ap[e], c.alpha);
+            *reinterpret_cast<float4 *>(av + i) = av4;
+        }
         *reinterpret_cast<float4 *>(p + i) = pv;
         if (need_m) *reinterpret_cast<float4 *>(m + i) = mv;
         if (need_v) *reinterpret_cast<float4 *>(v + i) = vv;
@@ -167,6 +194,11 @@ __global__ __launch_bounds__(kOptThreads) void opt_update_kernel(float *__restri
             float pe = p[j], me = need_m ? m[j] : 0.f, ve = need_v ? v[j] : 0.f, he = need_vh ? vh[j] : 0.f;
             float ge2 = need_mg ? mg[j] : 0.f, oe = need_mo ? mo[j] : 0.f;
             update_one<KIND>(pe, xform(g[j]), me, ve, he, ge2, oe, c);
+            if (AVG != KWS_AVG_NONE) {
+                float ae = av[j];
+                average_one<AVG>(pe, ae, c.alpha);
+                av[j] = ae;
+            }
             p[j] = pe;
             if (need_m) m[j] = me;
             if (need_v) v[j] = ve;
@@ -193,22 +225,48 @@ static int check_segments(const int64_t *offsets, const int64_t *sizes, int n_se
     return KWS_OK;
 }
 
-template <int KIND>
-static int launch_update(int norm, const kws_optimizer_args *a, const OptBlock *tab, const double *partial, const OptCoef &c, hipStream_t s)
+// exchanges params and the averaging slot inside the blocks of the table; whole words move, so two calls restore every bit
+__global__ __launch_bounds__(kOptThreads) void opt_swap_kernel(float *__restrict__ p, float *__restrict__ av, const OptBlock *__restrict__ tab)
+{
+    const OptBlock b = tab[blockIdx.x];
+    const int64_t i = b.begin + 4 * (int64_t)threadIdx.x;
+    if (i + 3 < b.end) {
+        const float4 pv = *reinterpret_cast<float4 *>(p + i), a4 = *reinterpret_cast<float4 *>(av + i);
+        *reinterpret_cast<float4 *>(p + i) = a4;
+        *reinterpret_cast<float4 *>(av + i) = pv;
+    } else {
+        for (int64_t j = i; j < b.end; ++j) {
+            const float pe = p[j], ae = av[j];
+            p[j] = ae;
+            av[j] = pe;
+        }
+    }
+}
+
+template <int KIND, int NORM>
+static int launch_update_avg(const kws_optimizer_args *a, const OptBlock *tab, const double *partial, const OptCoef &c, hipStream_t s)
 {
     const dim3 grid(a->n_blocks), block(kOptThreads);
-    if (norm == kNormNone) {
-        KWS_LAUNCH("opt_update_kernel", (opt_update_kernel<KIND, kNormNone>), grid, block, 0, s, a->params, a->grads, a->m, a->v, a->vhat,
-                   a->mg, a->mom, tab, partial, c);
-    } else if (norm == kNormVar) {
-        KWS_LAUNCH("opt_update_kernel", (opt_update_kernel<KIND, kNormVar>), grid, block, 0, s, a->params, a->grads, a->m, a->v, a->vhat,
-                   a->mg, a->mom, tab, partial, c);
+    if (a->avg_mode == KWS_AVG_NONE) {
+        KWS_LAUNCH("opt_update_kernel", (opt_update_kernel<KIND, NORM, KWS_AVG_NONE>), grid, block, 0, s, a->params, a->grads, a->m, a->v,
+                   a->vhat, a->mg, a->mom, a->avg, tab, partial, c);
+    } else if (a->avg_mode == KWS_AVG_BLEND) {
+        KWS_LAUNCH("opt_update_kernel", (opt_update_kernel<KIND, NORM, KWS_AVG_BLEND>), grid, block, 0, s, a->params, a->grads, a->m, a->v,
+                   a->vhat, a->mg, a->mom, a->avg, tab, partial, c);
     } else {
-        KWS_LAUNCH("opt_update_kernel", (opt_update_kernel<KIND, kNormGlobal>), grid, block, 0, s, a->params, a->grads, a->m, a->v,
-                   a->vhat, a->mg, a->mom, tab, partial, c);
+        KWS_LAUNCH("opt_update_kernel", (opt_update_kernel<KIND, NORM, KWS_AVG_SYNC>), grid, block, 0, s, a->params, a->grads, a->m, a->v,
+                   a->vhat, a->mg, a->mom, a->avg, tab, partial, c);
     }
     KWS_LAUNCH_CHECK("opt_update_kernel");
     return KWS_OK;
+}
+
+template <int KIND>
+static int launch_update(int norm, const kws_optimizer_args *a, const OptBlock *tab, const double *partial, const OptCoef &c, hipStream_t s)
+{
+    if (norm == kNormNone) return launch_update_avg<KIND, kNormNone>(a, tab, partial, c, s);
+    if (norm == kNormVar) return launch_update_avg<KIND, kNormVar>(a, tab, partial, c, s);
+    return launch_update_avg<KIND, kNormGlobal>(a, tab, partial, c, s);
 }
 
 }  // namespace opt
@@ -268,6 +326,12 @@ int kws_optimizer_step(const kws_optimizer_args *a, void *stream)
     if (!(a->momentum >= 0.f && a->momentum <= 1.f)) return fail(KWS_ERR_INVALID, "momentum must be in [0, 1]");
     if (a->kind == KWS_OPT_ADAM && a->t < 1) return fail(KWS_ERR_INVALID, "the step count t must be >= 1");
     if (a->n_blocks < 0) return fail(KWS_ERR_INVALID, "n_blocks < 0");
+    if (a->avg_mode < KWS_AVG_NONE || a->avg_mode > KWS_AVG_SYNC) return fail(KWS_ERR_INVALID, "unknown averaging mode %d", a->avg_mode);
+    if (a->avg_mode != KWS_AVG_NONE) {
+        if (!a->avg) return fail(KWS_ERR_INVALID, "avg_mode %d needs the averaging slot, avg is NULL", a->avg_mode);
+        if (reinterpret_cast<uintptr_t>(a->avg) & 15) return fail(KWS_ERR_INVALID, "the averaging slot must be 16-byte aligned");
+    }
+    if (!(a->avg_alpha >= 0.f && a->avg_alpha <= 1.f)) return fail(KWS_ERR_INVALID, "avg_alpha must be in [0, 1]");
     if (a->n_blocks == 0) return KWS_OK;
     const bool adam = a->kind == KWS_OPT_ADAM, rms = a->kind == KWS_OPT_RMSPROP;
     const bool mom = !adam && a->momentum > 0.f;
@@ -296,6 +360,7 @@ int kws_optimizer_step(const kws_optimizer_args *a, void *stream)
     c.gs = a->grad_scale;
     c.clipvalue = a->clipvalue;
     c.clipnorm = norm == kNormVar ? a->clipnorm : a->global_clipnorm;
+    c.alpha = a->avg_alpha;
     c.flags = a->flags;
     c.n_blocks = a->n_blocks;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -307,6 +372,23 @@ int kws_optimizer_step(const kws_optimizer_args *a, void *stream)
     if (adam) return launch_update<KWS_OPT_ADAM>(norm, a, tab, partial, c, s);
     if (rms) return launch_update<KWS_OPT_RMSPROP>(norm, a, tab, partial, c, s);
     return launch_update<KWS_OPT_SGD>(norm, a, tab, partial, c, s);
+}
+
+int kws_optimizer_swap(float *params, float *avg, const void *ws, int64_t ws_bytes, int32_t n_blocks, void *stream)
+{
+    if (n_blocks < 0) return fail(KWS_ERR_INVALID, "n_blocks < 0");
+    if (!params || !avg || !ws) return fail(KWS_ERR_INVALID, "optimizer swap: null buffer");
+    if (params == avg) return fail(KWS_ERR_INVALID, "optimizer swap: params and avg are the same buffer");
+    if ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(avg) | reinterpret_cast<uintptr_t>(ws)) & 15)
+        return fail(KWS_ERR_INVALID, "optimizer buffers must be 16-byte aligned");
+    if (ws_bytes < ws_bytes_for(n_blocks))
+        return fail(KWS_ERR_WORKSPACE, "optimizer workspace of %lld bytes, %lld needed for %d blocks", (long long)ws_bytes,
+                    (long long)ws_bytes_for(n_blocks), n_blocks);
+    if (n_blocks == 0) return KWS_OK;
+    KWS_LAUNCH("opt_swap_kernel", opt_swap_kernel, dim3(n_blocks), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream), params, avg,
+               static_cast<const OptBlock *>(ws));
+    KWS_LAUNCH_CHECK("opt_swap_kernel");
+    return KWS_OK;
 }
 
 }  // extern "C"

@@ -49,6 +49,7 @@ class KwsTrainArgs(ctypes.Structure):
 
 OPT_KINDS = {"sgd": 0, "rmsprop": 1, "adam": 2}                                          # include/kws.h KWS_OPT_*
 OPT_NESTEROV, OPT_CENTERED, OPT_AMSGRAD = 1, 2, 4
+AVG_NONE, AVG_BLEND, AVG_SYNC = 0, 1, 2                                                  # include/kws.h KWS_AVG_*
 
 
 class KwsOptimizerArgs(ctypes.Structure):
@@ -57,7 +58,8 @@ class KwsOptimizerArgs(ctypes.Structure):
                 ("mom", ctypes.c_void_p), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64), ("n_blocks", ctypes.c_int32),
                 ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("momentum", ctypes.c_float), ("t", ctypes.c_int64), ("grad_scale", ctypes.c_float), ("clipvalue", ctypes.c_float),
-                ("clipnorm", ctypes.c_float), ("global_clipnorm", ctypes.c_float)]
+                ("clipnorm", ctypes.c_float), ("global_clipnorm", ctypes.c_float), ("avg", ctypes.c_void_p),
+                ("avg_mode", ctypes.c_int32), ("avg_alpha", ctypes.c_float)]
 
 
 AUG_MAX_SNR = 16
@@ -229,6 +231,7 @@ def get_lib():
     L.kws_optimizer_workspace_bytes.restype = i64
     L.kws_optimizer_plan.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64), i32, vp, i64, ctypes.POINTER(ctypes.c_int32)]
     L.kws_optimizer_step.argtypes = [ctypes.POINTER(KwsOptimizerArgs), vp]
+    L.kws_optimizer_swap.argtypes = [vp, vp, vp, i64, i32, vp]
     f64 = ctypes.c_double
     L.kws_featurizer_occupancy.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_size_t)]
     L.kws_decoder_create.argtypes = [ctypes.POINTER(f64), i32, f64, i32, f64, f64, ctypes.POINTER(vp)]

@@ -130,6 +130,7 @@ class DeviceModel(object):
         self._ws = None
         # optimizer_step: its extra slots (zeroed when first needed) and its workspace (block table uploaded once, then scratch)
         self.opt_vhat = self.opt_mg = self.opt_mom = None
+        self.opt_avg = None                    # weight-averaging slot of MovingAverage / SWA / Lookahead: a copy of params when first needed
         self._opt_ws = None
         self._opt_blocks = 0
         self._ws_key = None
@@ -328,6 +329,23 @@ class DeviceModel(object):
                                           self.params.numel(), float(lr), float(rho), float(eps), float(grad_scale),
                                           torch.cuda.current_stream().cuda_stream))
 
+    def _opt_plan(self):
+        torch = _torch()
+        if self._opt_ws is None:
+            host, self._opt_blocks = self.spec.optimizer_plan()
+            self._opt_ws = torch.from_numpy(host).to(self.device)
+
+    def swap_average(self):
+        """kws_optimizer_swap: exchange params and the averaging slot opt_avg inside the variables (padding stays); a second call
+        restores every bit.  Asynchronous on the current stream."""
+        torch = _torch()
+        if self.opt_avg is None:
+            raise RuntimeError("no averaging slot yet: no optimizer step under MovingAverage / SWA / Lookahead has run")
+        self._opt_plan()
+        self.invalidate_prepared()
+        _l.check(self._L.kws_optimizer_swap(self.params.data_ptr(), self.opt_avg.data_ptr(), self._opt_ws.data_ptr(), self._opt_ws.numel(),
+                                            self._opt_blocks, torch.cuda.current_stream().cuda_stream))
+
     def _opt_slot(self, name):
         torch = _torch()
         if getattr(self, name) is None:
@@ -337,13 +355,12 @@ class DeviceModel(object):
     def optimizer_step(self, opt, lr=None, grad_scale=1.0):
         """One kws_optimizer_step by the common.model_utils optimizer `opt` (any options), at `lr` (default: opt.current_lr()).
         Slots: Adam m / v in adam_m / adam_v, RMSprop's mean square in adam_v (as rmsprop_step), and opt_vhat (amsgrad),
-        opt_mg (centered), opt_mom (momentum).  Asynchronous on the current stream."""
+        opt_mg (centered), opt_mom (momentum).  Under a MovingAverage / SWA / Lookahead wrapper the same launch also updates the
+        averaging slot opt_avg by opt.average_args(opt.iterations).  Asynchronous on the current stream."""
         torch = _torch()
         if opt.kind not in _l.OPT_KINDS:
             raise ValueError("unknown optimizer kind %r" % (opt.kind,))
-        if self._opt_ws is None:
-            host, self._opt_blocks = self.spec.optimizer_plan()
-            self._opt_ws = torch.from_numpy(host).to(self.device)
+        self._opt_plan()
         a = _l.KwsOptimizerArgs()
         a.kind = _l.OPT_KINDS[opt.kind]
         a.params, a.grads = self.params.data_ptr(), self.grads.data_ptr()
@@ -369,6 +386,13 @@ class DeviceModel(object):
                 a.flags |= _l.OPT_NESTEROV
         if opt.kind != 'adam' and opt.momentum > 0:
             a.mom = self._opt_slot("opt_mom")
+        average_args = getattr(opt, "average_args", None)
+        if average_args is not None:
+            if self.opt_avg is None:           # every wrapper starts its slot at the variable's value, before the first update
+                self.opt_avg = self.params.clone()
+            mode, alpha = average_args(opt.iterations)
+            if mode != _l.AVG_NONE:
+                a.avg, a.avg_mode, a.avg_alpha = self.opt_avg.data_ptr(), int(mode), float(alpha)
         self.step_count += 1
         a.t = self.step_count
         self.invalidate_prepared()

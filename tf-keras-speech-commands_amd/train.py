@@ -16,7 +16,9 @@ that share of the training clips at zero phase with a Butterworth design drawn f
 --loudness_range LO_DB,HI_DB sets a --loudness_rate share to a level drawn from the range (dBFS), before every other stage, as
 tools/audio_process/audio_convert.py resamples and levels files offline.
 The optimizer takes the Keras options the reference's command line leaves at their defaults: --clipnorm, --global_clipnorm and
---clipvalue (any optimizer), --momentum (sgd, rmsprop), --nesterov (sgd), --centered (rmsprop) and --amsgrad (adam)."""
+--clipvalue (any optimizer), --momentum (sgd, rmsprop), --nesterov (sgd), --centered (rmsprop) and --amsgrad (adam).
+--average_type wraps the optimizer as the reference's get_averaged_optimizer does: ema and swa keep an average of the weights on the
+GPU, which is what gets validated, checkpointed and written as trained_final; lookahead changes the trained weights themselves."""
 import argparse
 import os
 import sys
@@ -32,9 +34,9 @@ def main(argv=None):
     from classifier.loss import SparseCategoricalCrossEntropy, WeightedSparseCategoricalCrossEntropy
     from classifier.model import get_model
     from classifier.params import inject_params
-    from common.callbacks import (CheckpointCleanCallBack, EarlyStopping, JsonlLogger, ModelCheckpoint, ReduceLROnPlateau,
-                                  TerminateOnNaN)
-    from common.model_utils import get_optimizer
+    from common.callbacks import (AverageModelCheckpoint, CheckpointCleanCallBack, EarlyStopping, JsonlLogger, ModelCheckpoint,
+                                  ReduceLROnPlateau, TerminateOnNaN)
+    from common.model_utils import get_averaged_optimizer, get_optimizer
     from common.utils import get_classes
 
     log_dir = args.log_dir
@@ -69,8 +71,11 @@ def main(argv=None):
 
     # callbacks for training process
     logging = JsonlLogger(os.path.join(log_dir, 'train_log.jsonl'))
-    checkpoint = ModelCheckpoint(os.path.join(log_dir, 'ep{epoch:03d}-loss{loss:.3f}-accuracy{accuracy:.3f}-val_loss{val_loss:.3f}-val_accuracy{val_accuracy:.3f}.npz'),
-                                 monitor='val_accuracy', mode='max', verbose=1, save_weights_only=False, save_best_only=True, period=1)
+    averaged = args.average_type in ('ema', 'swa')       # the optimizer keeps an average to validate and save; lookahead does not
+    checkpoint_path = os.path.join(log_dir, 'ep{epoch:03d}-loss{loss:.3f}-accuracy{accuracy:.3f}-val_loss{val_loss:.3f}-val_accuracy{val_accuracy:.3f}.npz')
+    checkpoint_kw = dict(monitor='val_accuracy', mode='max', verbose=1, save_weights_only=False, save_best_only=True, period=1)
+    checkpoint = AverageModelCheckpoint(False, checkpoint_path, **checkpoint_kw) if averaged else \
+        ModelCheckpoint(checkpoint_path, **checkpoint_kw)
     reduce_lr = ReduceLROnPlateau(monitor='val_accuracy', factor=0.5, mode='max', patience=10, verbose=1, cooldown=0, min_lr=1e-10)
     early_stopping = EarlyStopping(monitor='val_accuracy', min_delta=0, patience=50, verbose=1, mode='max')
     checkpoint_clean = CheckpointCleanCallBack(log_dir, max_keep=5)
@@ -128,6 +133,7 @@ def main(argv=None):
     decay_steps = steps_per_epoch * args.epochs
     optimizer = get_optimizer(args.optimizer, args.learning_rate, average_type=None, decay_type=args.decay_type, decay_steps=decay_steps,
                               **opt_options)
+    optimizer = get_averaged_optimizer(args.average_type, optimizer)
 
     # prepare loss according to loss type
     if args.background_bias:
@@ -149,10 +155,14 @@ def main(argv=None):
         x_val = get_featurizer()(torch.from_numpy(x_val).cuda(), torch.from_numpy(len_val).cuda()).cpu().numpy()
     print('Train on {} samples, val on {} samples, with batch size {}.'.format(len(x_train), len(x_val), args.batch_size))
     fit_kw = dict(sample_lengths=len_train, augment=augment) if args.raw_audio else {}
+    if averaged:
+        fit_kw['validate_averaged'] = True
     history = model.fit(x_train, y_train, batch_size=args.batch_size, epochs=args.epochs, validation_data=(x_val, y_val),
                         validation_freq=1, callbacks=callbacks, shuffle=True, verbose=1, **fit_kw)
 
     # Finally store model
+    if averaged:
+        optimizer.assign_average_vars(model)
     model.save(os.path.join(log_dir, 'trained_final.npz'))
     return history
 
@@ -208,7 +218,8 @@ def parse_args(argv=None):
     parser.add_argument('--model_type', type=str, required=False, default='simple_cnn',
                         help='classifier model type: simple_cnn/simple_cnn_lite/simple_gru/simple_lstm, default=%(default)s')
     parser.add_argument('--weights_path', type=str, required=False, default=None,
-                        help="Pretrained model/weights file for fine tune")
+                        help="Pretrained model/weights file for fine tune (the file holds no optimizer state: with --average_type the "
+                             "average starts from the loaded weights)")
 
     # Data options
     parser.add_argument('--train_data_path', type=str, required=True,
@@ -242,6 +253,11 @@ def parse_args(argv=None):
     parser.add_argument('--nesterov', action='store_true', help="Nesterov momentum (sgd)")
     parser.add_argument('--centered', action='store_true', help="centered RMSprop (rmsprop)")
     parser.add_argument('--amsgrad', action='store_true', help="the AMSGrad variant of Adam (adam)")
+    parser.add_argument('--average_type', type=str, required=False, default=None, choices=[None, 'ema', 'swa', 'lookahead'],
+                        help="weights average type: ema keeps an exponential moving average (decay 0.99) and swa the mean of every 10th "
+                             "step's weights, which are then what is validated, checkpointed and saved; lookahead pulls the trained weights "
+                             "to slow ones every 6 steps. Checkpoints hold no optimizer state, so a run resumed with --weights_path starts "
+                             "its average from the loaded weights. default=%(default)s")
     parser.add_argument('--decay_type', type=str, required=False, default=None, choices=[None, 'cosine', 'exponential', 'polynomial', 'piecewise_constant'],
                         help="Learning rate decay type, default=%(default)s")
     parser.add_argument('--epochs', type=int, required=False, default=100,

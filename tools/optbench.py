@@ -4,7 +4,12 @@ Each variant runs --steps back-to-back steps between two device events after a w
 and the medians are reported.  These times include the host's launch cost per step; the kernels' own durations and the kernel count per
 step come from a separate `rocprofv3 --kernel-trace --stats` run of --kernel-only.  Prints one JSON line; --out also writes it to a file.
 
-    python tools/optbench.py [--rounds 7] [--steps 200] [--out optbench.json] [--kernel-only]"""
+--averaging measures the weight-averaging wrappers instead (MovingAverage, SWA, Lookahead over Adam, SGD with momentum and centered
+RMSprop).  Per optimizer: the step without a wrapper; that step followed by a separate torch lerp_ of an average towards the parameters
+(what the fusion replaces); and the step under each wrapper.  MovingAverage folds the slot into every step, SWA and Lookahead (periods
+10 and 6, the reference's) into one step of their period.
+
+    python tools/optbench.py [--rounds 7] [--steps 200] [--out optbench.json] [--kernel-only] [--averaging]"""
 import argparse
 import json
 import os
@@ -25,8 +30,44 @@ def variants():
             ("rmsprop_centered_momentum", mu.RMSprop(1e-3, momentum=0.9, centered=True))]
 
 
+def averaging_variants():
+    """[(name, inner optimizer factory, wrapper name or None, lerp after the step)]"""
+    from common import model_utils as mu
+    inner = [("adam", lambda: mu.Adam(1e-3)), ("sgd_momentum", lambda: mu.SGD(0.01, momentum=0.9)),
+             ("rmsprop_centered", lambda: mu.RMSprop(1e-3, centered=True))]
+    out = []
+    for name, make in inner:
+        out.append((name + "/plain", make, None, False))
+        out.append((name + "/plain_then_lerp", make, None, True))
+        for w in ("ema", "swa", "lookahead"):
+            out.append((name + "/" + w, make, w, False))
+    return out
+
+
+def averaging_steps(spec, rng):
+    from common import model_utils as mu
+    from kws_amd.model import DeviceModel
+    models = {}
+    for name, make, wrapper, lerp in averaging_variants():
+        dm = DeviceModel(spec)
+        dm.params[:spec.param_count].copy_(torch.from_numpy((0.1 * rng.standard_normal(spec.param_count)).astype(np.float32)))
+        dm.grads[:spec.param_count].copy_(torch.from_numpy((0.01 * rng.standard_normal(spec.param_count)).astype(np.float32)))
+        opt = mu.get_averaged_optimizer(wrapper, make())
+        avg = dm.params.clone() if lerp else None
+
+        def step(dm=dm, opt=opt, avg=avg):
+            dm.optimizer_step(opt, 1e-3)
+            opt.iterations += 1                 # the wrappers' schedules run on the update count
+            if avg is not None:
+                avg.lerp_(dm.params, 0.01)
+        step()
+        models[name] = step
+    return models
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--averaging", action="store_true", help="measure the weight-averaging wrappers instead of the optimizer options")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--out", default=None)
@@ -35,8 +76,8 @@ def main():
     from kws_amd.model import DeviceModel, ModelSpec
     spec = ModelSpec("simple_cnn", 36, 30, 20)
     rng = np.random.default_rng(0)
-    models = {}
-    for name, opt in variants():
+    models = averaging_steps(spec, rng) if a.averaging else {}
+    for name, opt in ([] if a.averaging else variants()):
         dm = DeviceModel(spec)
         dm.params[:spec.param_count].copy_(torch.from_numpy((0.1 * rng.standard_normal(spec.param_count)).astype(np.float32)))
         dm.grads[:spec.param_count].copy_(torch.from_numpy((0.01 * rng.standard_normal(spec.param_count)).astype(np.float32)))
