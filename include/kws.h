@@ -999,6 +999,36 @@ int kws_stream_sweep(const int32_t *index, const double *score, int R, int64_t s
                      const int32_t *ev_off, const int32_t *ev_class, const int32_t *ev_lo, const int32_t *ev_hi,
                      int32_t *counts, void *stream);
 
+/* The activations of R scanned recordings at ONE operating point, each with its chunk, class and kind: what
+ * Listener.on_activation (listen.py:291-308) sees, for the files a scan or a sweep has already decoded.  index / score / stride /
+ * rec_chunks and the event arrays are kws_stream_sweep's, with the same preconditions; the walk is TriggerDetector.update from
+ * {activation 0, record_index none} per recording, recomputed here rather than read from a scan's `fired`, so any point of a
+ * sweep can be collected from the same scan.  det (R, max_det, 4) int32 = {chunk, class, kind, event} in chunk order and
+ * det_score (R, max_det) the chunk's decoded score; `kind` follows the rule above (the first fire of the event's class inside its
+ * window is a hit, later ones duplicates, every other fire a false alarm; KWS_DET_UNLABELLED when ev_off == NULL) and `event`
+ * is the event's position within its recording, -1 when the fire belongs to none.  n_det (R) is the true count, also when
+ * it exceeds max_det; only the first max_det activations are stored, and the slots past min(n_det[r], max_det) are written
+ * as {-1, -1, 0, -1} with score 0.  max_det == 0 only counts (det / det_score may be NULL); R == 0 does nothing.  One wave per
+ * recording; nothing is synchronised. */
+enum { KWS_DET_UNLABELLED = 0, KWS_DET_HIT = 1, KWS_DET_DUPLICATE = 2, KWS_DET_FALSE_ALARM = 3 };
+int kws_stream_collect(const int32_t *index, const double *score, int R, int64_t stride, const int32_t *rec_chunks,
+                       int background_index, int chunk_size, double sensitivity, int trigger_level,
+                       const int32_t *ev_off, const int32_t *ev_class, const int32_t *ev_lo, const int32_t *ev_hi,
+                       int max_det, int32_t *n_det, int32_t *det, double *det_score, void *stream);
+
+/* The near misses of R scanned recordings: per recording the up to K highest-scoring, well-separated non-background chunks.
+ * Chunk k < rec_chunks[r] is a candidate when index != background_index, score > min_score (strict) and, with events
+ * (ev_off != NULL; CSR as above, the classes are not needed), k lies in no [ev_lo[e], ev_hi[e]] of its recording, whatever the
+ * event's class.  Greedy, at most K times: the candidate with the largest score, ties to the lowest chunk, whose distance to
+ * every chunk already picked is >= min_gap.  peaks (R, K, 2) int32 = {chunk, class} and peak_score (R, K) in pick order,
+ * n_peaks (R) <= K; unused slots are {-1, -1} with score 0.  The comparisons are on the stored doubles: the result is exact and
+ * the same on every run.  1 <= K <= 64 and min_gap >= 1, anything else is KWS_ERR_INVALID.  One wave per recording, no atomics;
+ * nothing is synchronised. */
+int kws_stream_peaks(const int32_t *index, const double *score, int R, int64_t stride, const int32_t *rec_chunks,
+                     int background_index, double min_score, int min_gap,
+                     const int32_t *ev_off, const int32_t *ev_lo, const int32_t *ev_hi,
+                     int K, int32_t *n_peaks, int32_t *peaks, double *peak_score, void *stream);
+
 /* ------------------------------------------------------------------------
  * Voice-activity detection of whole recordings: where the speech is, which files are silent, and the clips.  Replaces
  *   VoiceActivityDetector.detect_speech              tools/audio_process/speech_duration_check.py:149-176

@@ -11,6 +11,10 @@
 //                                                    trigger walked in chunk order, one wave per recording)
 //   TriggerDetector.update    listen.py:538-559   -> kws_stream_sweep (the same walk over a scan's decoded scores at 64 operating points
 //                                                    per wave, one per lane, counted against labelled events)
+// and the harvest of a scan for the next training run (kws_amd.stream.collect / peaks):
+//   Listener.on_activation    listen.py:291-308   -> kws_stream_collect (the walk once more at one operating point, every activation
+//                                                    recorded with its chunk, class and kind -- hit, duplicate, false alarm)
+//   (nothing in the reference)                    -> kws_stream_peaks (the near misses: the best well-separated non-background chunks)
 // Everything here is a few bytes per stream and one thread per stream: the kernels are latency-sized, the point of doing
 // them on the device is that probabilities, scores and detector state never leave HBM between the forward pass of one
 // chunk and the next (the whole step can sit in one hipGraph).  Arithmetic is float64 wherever the reference computes
@@ -299,6 +303,171 @@ __global__ __launch_bounds__(64) void sweep_kernel(const int32_t *__restrict__ i
     out[0] = fires; out[1] = hits; out[2] = false_alarms; out[3] = duplicates; out[4] = latency;
 }
 
+// Activations of one operating point.  block = one wave = one recording: the walk of sweep_kernel with ONE state, so state, event
+// cursor and write position are wave-uniform (scalar registers); lane 0 stores each record, and the whole wave fills the unused
+// slots afterwards.  det (R, max_det, 4) = {chunk, class, kind, event}; the first max_det activations are kept, all are counted.
+__global__ __launch_bounds__(64) void collect_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, long stride,
+                                                     const int32_t *__restrict__ rec_chunks, int background, int refractory, double sensitivity,
+                                                     int level, const int32_t *__restrict__ ev_off, const int32_t *__restrict__ ev_class,
+                                                     const int32_t *__restrict__ ev_lo, const int32_t *__restrict__ ev_hi, int max_det,
+                                                     int32_t *__restrict__ n_det, int32_t *__restrict__ det, double *__restrict__ det_score)
+{
+    const int r = blockIdx.x, lane = threadIdx.x;
+    long T = rec_chunks[r];
+    T = T < 0 ? 0 : (T < stride ? T : stride);                                  // never past the row, whatever rec_chunks holds
+    const bool labelled = ev_off != nullptr;
+    const int e_begin = labelled ? ev_off[r] : 0;
+    const int e_end = labelled ? ev_off[r + 1] : 0;
+    int e = e_begin;                                                            // cursor: the first event that does not end before the last fire
+    bool found = false;                                                         // event e already detected
+    int32_t st[2] = {0, -1};
+    int n = 0;
+    int32_t *out = det + (long)r * max_det * 4;
+    double *out_score = det_score + (long)r * max_det;
+    for (long base = 0; base < T; base += 64) {
+        const long i = base + lane;
+        int idx = -1;
+        double sc = 0.0;
+        if (i < T) { idx = index[r * stride + i]; sc = score[r * stride + i]; }
+        const int m = (int)(T - base < 64 ? T - base : 64);
+        for (int j = 0; j < m; ++j) {
+            const int ij = lane_value(idx, j);
+            const double sj = lane_value(sc, j);
+            if (!trigger_one(ij, sj, background, sensitivity, level, refractory, st)) continue;
+            const int k = (int)base + j;
+            int kind = KWS_DET_UNLABELLED, event = -1;
+            if (labelled) {
+                while (e < e_end && ev_hi[e] < k) { e += 1; found = false; }
+                if (e < e_end && ev_lo[e] <= k && ev_class[e] == ij) {
+                    kind = found ? KWS_DET_DUPLICATE : KWS_DET_HIT;
+                    found = true;
+                    event = e - e_begin;
+                } else {
+                    kind = KWS_DET_FALSE_ALARM;                                 // outside every window, or the wrong class inside one
+                }
+            }
+            if (n < max_det && lane == 0) {
+                out[4 * n] = k; out[4 * n + 1] = ij; out[4 * n + 2] = kind; out[4 * n + 3] = event;
+                out_score[n] = sj;
+            }
+            n += 1;
+        }
+    }
+    if (lane == 0) n_det[r] = n;
+    for (int s = (n < max_det ? n : max_det) + lane; s < max_det; s += 64) {
+        out[4 * s] = -1; out[4 * s + 1] = -1; out[4 * s + 2] = KWS_DET_UNLABELLED; out[4 * s + 3] = -1;
+        out_score[s] = 0.0;
+    }
+}
+
+// One lane's candidate peak; `chunk` kNoPeak = none.  The order is score descending, then chunk ascending: total over the candidates
+// of a recording (chunks are distinct), so the maximum does not depend on the order in which lanes are combined.
+struct Peak {
+    double score;
+    int chunk;
+};
+constexpr int kNoPeak = 0x7fffffff;
+
+__device__ __forceinline__ Peak better_of(const Peak &a, const Peak &b)
+{
+    return (b.score > a.score || (b.score == a.score && b.chunk < a.chunk)) ? b : a;
+}
+
+// the value of the lane a DPP control names, all 64 lanes active (every control used below names a lane of the same row)
+template <int kCtrl>
+__device__ __forceinline__ Peak dpp_peak(const Peak &p)
+{
+    const int hi = __double2hiint(p.score), lo = __double2loint(p.score);
+    Peak q;
+    q.score = __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, kCtrl, 0xf, 0xf, false),
+                               __builtin_amdgcn_update_dpp(lo, lo, kCtrl, 0xf, 0xf, false));
+    q.chunk = __builtin_amdgcn_update_dpp(p.chunk, p.chunk, kCtrl, 0xf, 0xf, false);
+    return q;
+}
+
+// Maximum of the wave's 64 candidates, the same in every lane.  Inside a row of 16 lanes four DPP exchanges (lane ^ 1, lane ^ 2, the
+// mirror of each half row, the mirror of the row) leave the row's maximum in all of its lanes; the four rows are then read with
+// v_readlane and combined in scalar registers.  No LDS, no atomics.
+__device__ __forceinline__ Peak wave_best(Peak p)
+{
+    p = better_of(p, dpp_peak<0xB1>(p));                                        // quad_perm:[1,0,3,2]
+    p = better_of(p, dpp_peak<0x4E>(p));                                        // quad_perm:[2,3,0,1]
+    p = better_of(p, dpp_peak<0x141>(p));                                       // row_half_mirror
+    p = better_of(p, dpp_peak<0x140>(p));                                       // row_mirror
+    Peak w;
+    w.score = lane_value(p.score, 0);
+    w.chunk = lane_value(p.chunk, 0);
+#pragma unroll
+    for (int row = 1; row < 4; ++row) {
+        Peak q;
+        q.score = lane_value(p.score, 16 * row);
+        q.chunk = lane_value(p.chunk, 16 * row);
+        w = better_of(w, q);
+    }
+    return w;
+}
+
+// Near misses.  block = one wave = one recording, K <= 64 greedy picks.  For every pick the lanes stride over the recording's chunks
+// (lane l sees l, l + 64, ... in ascending order, so a strict `>` keeps the lowest chunk among its equal scores) and each keeps its
+// best candidate that is min_gap away from every earlier pick; wave_best names the winner.  Pick j lives in lane j's `mine`
+// and is handed to the gap test by v_readlane.  The (index, score) rows are re-read per pick: they are a few KiB and stay in cache.
+__global__ __launch_bounds__(64) void peaks_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, long stride,
+                                                   const int32_t *__restrict__ rec_chunks, int background, double min_score, int min_gap,
+                                                   const int32_t *__restrict__ ev_off, const int32_t *__restrict__ ev_lo,
+                                                   const int32_t *__restrict__ ev_hi, int K, int32_t *__restrict__ n_peaks,
+                                                   int32_t *__restrict__ peaks, double *__restrict__ peak_score)
+{
+    const int r = blockIdx.x, lane = threadIdx.x;
+    long T = rec_chunks[r];
+    T = T < 0 ? 0 : (T < stride ? T : stride);
+    const bool labelled = ev_off != nullptr;
+    const int e_begin = labelled ? ev_off[r] : 0;
+    const int e_end = labelled ? ev_off[r + 1] : 0;
+    const int32_t *row_index = index + r * stride;
+    const double *row_score = score + r * stride;
+    int32_t *out = peaks + (long)r * K * 2;
+    double *out_score = peak_score + (long)r * K;
+    int mine = -1;                                                              // lane j: the chunk of pick j
+    int n = 0;
+    for (; n < K; ++n) {
+        Peak best;
+        best.score = -INFINITY;
+        best.chunk = kNoPeak;
+        int e = e_begin;                                                        // this lane's event cursor: its chunks ascend
+        for (long base = 0; base < T; base += 64) {
+            const long k = base + lane;
+            double sc = 0.0;
+            bool cand = false;
+            if (k < T) {
+                sc = row_score[k];
+                cand = row_index[k] != background && sc > min_score && sc > best.score;
+                if (cand && labelled) {                                         // inside an event's window, whatever its class: not a negative
+                    while (e < e_end && ev_hi[e] < k) e += 1;
+                    if (e < e_end && ev_lo[e] <= k) cand = false;
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(cand) == 0) continue;
+            for (int j = 0; j < n; ++j) {                                       // wave-uniform trip count
+                const long d = k - (long)lane_value(mine, j);
+                if ((d < 0 ? -d : d) < (long)min_gap) cand = false;
+            }
+            if (cand) { best.score = sc; best.chunk = (int)k; }
+        }
+        const Peak w = wave_best(best);
+        if (w.chunk == kNoPeak) break;
+        if (lane == n) mine = w.chunk;
+        if (lane == 0) {
+            out[2 * n] = w.chunk; out[2 * n + 1] = row_index[w.chunk];
+            out_score[n] = w.score;
+        }
+    }
+    if (lane == 0) n_peaks[r] = n;
+    for (int s = n + lane; s < K; s += 64) {
+        out[2 * s] = -1; out[2 * s + 1] = -1;
+        out_score[s] = 0.0;
+    }
+}
+
 static DecDev dec_dev(const kws_decoder *d)
 {
     DecDev v;
@@ -522,6 +691,41 @@ int kws_stream_sweep(const int32_t *index, const double *score, int R, int64_t s
                (long)stride, rec_chunks, background_index, refractory_of(chunk_size), sensitivity, trigger_level, P, ev_off, ev_class, ev_lo, ev_hi,
                counts);
     KWS_LAUNCH_CHECK("sweep_kernel");
+    return KWS_OK;
+}
+
+int kws_stream_collect(const int32_t *index, const double *score, int R, int64_t stride, const int32_t *rec_chunks, int background_index,
+                       int chunk_size, double sensitivity, int trigger_level, const int32_t *ev_off, const int32_t *ev_class,
+                       const int32_t *ev_lo, const int32_t *ev_hi, int max_det, int32_t *n_det, int32_t *det, double *det_score, void *stream)
+{
+    if (R < 0 || stride < 0 || chunk_size < 1 || max_det < 0)
+        return fail(KWS_ERR_INVALID, "bad R=%d stride=%lld chunk_size=%d max_det=%d", R, (long long)stride, chunk_size, max_det);
+    if (stride >= 0x7fffffffLL) return fail(KWS_ERR_UNSUPPORTED, "rows of %lld chunks: a chunk number must fit 31 bits", (long long)stride);
+    if (R == 0) return KWS_OK;
+    if (!rec_chunks || !n_det || ((!index || !score) && stride > 0) || ((!det || !det_score) && max_det > 0))
+        return fail(KWS_ERR_INVALID, "null argument");
+    if (ev_off && (!ev_class || !ev_lo || !ev_hi)) return fail(KWS_ERR_INVALID, "null argument: ev_off without ev_class / ev_lo / ev_hi");
+    KWS_LAUNCH("collect_kernel", collect_kernel, dim3((unsigned)R), dim3(64), 0, static_cast<hipStream_t>(stream), index, score, (long)stride,
+               rec_chunks, background_index, refractory_of(chunk_size), sensitivity, trigger_level, ev_off, ev_class, ev_lo, ev_hi, max_det,
+               n_det, det, det_score);
+    KWS_LAUNCH_CHECK("collect_kernel");
+    return KWS_OK;
+}
+
+int kws_stream_peaks(const int32_t *index, const double *score, int R, int64_t stride, const int32_t *rec_chunks, int background_index,
+                     double min_score, int min_gap, const int32_t *ev_off, const int32_t *ev_lo, const int32_t *ev_hi, int K,
+                     int32_t *n_peaks, int32_t *peaks, double *peak_score, void *stream)
+{
+    if (K < 1 || K > 64) return fail(KWS_ERR_INVALID, "K=%d peaks per recording is outside 1..64", K);
+    if (min_gap < 1) return fail(KWS_ERR_INVALID, "min_gap=%d must be at least 1", min_gap);
+    if (R < 0 || stride < 0) return fail(KWS_ERR_INVALID, "bad R=%d stride=%lld", R, (long long)stride);
+    if (stride >= 0x7fffffffLL) return fail(KWS_ERR_UNSUPPORTED, "rows of %lld chunks: a chunk number must fit 31 bits", (long long)stride);
+    if (R == 0) return KWS_OK;
+    if (!rec_chunks || !n_peaks || !peaks || !peak_score || ((!index || !score) && stride > 0)) return fail(KWS_ERR_INVALID, "null argument");
+    if (ev_off && (!ev_lo || !ev_hi)) return fail(KWS_ERR_INVALID, "null argument: ev_off without ev_lo / ev_hi");
+    KWS_LAUNCH("peaks_kernel", peaks_kernel, dim3((unsigned)R), dim3(64), 0, static_cast<hipStream_t>(stream), index, score, (long)stride,
+               rec_chunks, background_index, min_score, min_gap, ev_off, ev_lo, ev_hi, K, n_peaks, peaks, peak_score);
+    KWS_LAUNCH_CHECK("peaks_kernel");
     return KWS_OK;
 }
 

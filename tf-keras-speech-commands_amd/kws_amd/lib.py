@@ -163,6 +163,7 @@ BANK_MEL, BANK_BARK = 0, 1
 WAV_F32, WAV_I16 = 0, 1
 RAW_F64, RAW_F32 = 0, 1
 VAD_ALIGN = {"left": 0, "center": 1}                                                    # include/kws.h KWS_VAD_ALIGN_*
+DET_UNLABELLED, DET_HIT, DET_DUPLICATE, DET_FALSE_ALARM = 0, 1, 2, 3                     # include/kws.h KWS_DET_*
 
 _lib = None
 
@@ -247,6 +248,8 @@ def get_lib():
     L.kws_stream_gather_windows.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, i64, i32, fp, vp]
     L.kws_stream_scan_postprocess.argtypes = [vp, vp, i32, i32, i32, vp, i64, i32, f64, i32, i32, vp, vp, vp, vp, i64, vp]
     L.kws_stream_sweep.argtypes = [vp, vp, i32, i64, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.kws_stream_collect.argtypes = [vp, vp, i32, i64, vp, i32, i32, f64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.kws_stream_peaks.argtypes = [vp, vp, i32, i64, vp, i32, f64, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     L.kws_set_matrix_precision.argtypes = [i32]
     L.kws_get_matrix_precision.restype = i32
     L.kws_set_inference_precision.argtypes = [i32]

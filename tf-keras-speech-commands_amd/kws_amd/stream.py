@@ -5,8 +5,9 @@ methods -- `ThresholdDecoder` (listen.py:452-522) and `TriggerDetector` (listen.
 which runs the whole per-chunk loop of listen.py:350-375 (`update_vectors`, predict, argmax / max, decode, detector
 update) for S audio streams at once, and `scan`, the same loop over whole recordings that already lie in memory,
 parallel over time, and `sweep`, which walks the detector over a scan's decoded scores at a whole grid of operating points
-and counts hits, false alarms and misses against labelled events.  All arithmetic runs in the HIP library; there is no
-host fallback.
+and counts hits, false alarms and misses against labelled events, and `collect` / `peaks`, which turn a scan's activations and
+near misses into `Detections`: the clips (`Detections.clips`, `.save`) the next training run needs as `background` examples.
+All arithmetic runs in the HIP library; there is no host fallback.
 """
 import ctypes
 
@@ -236,10 +237,13 @@ def scan_plan(n_samples, chunk_size, window_samples, hop_samples, n_features):
 class ScanResult(object):
     """index / score / fired: (R, T_max) CUDA tensors, element (r, k) for chunk k of recording r (index -1, score 0,
     fired 0 past the recording's own n_chunks[r]); n_chunks: list of R ints; state: (R, 2) int32 CUDA tensor, the
-    detector state {activation, record_index} after each recording's last chunk; probs: (R, T_max, C) or None."""
+    detector state {activation, record_index} after each recording's last chunk; probs: (R, T_max, C) or None.  With
+    scan(..., keep_audio=True) also wav, the packed (R, stride) int16 CUDA tensor the scan read, and lengths, the host list of
+    sample counts (both None otherwise): `Detections.clips` / `.save` then need no recordings."""
 
-    def __init__(self, index, score, fired, n_chunks, state, probs=None):
+    def __init__(self, index, score, fired, n_chunks, state, probs=None, wav=None, lengths=None):
         self.index, self.score, self.fired, self.n_chunks, self.state, self.probs = index, score, fired, n_chunks, state, probs
+        self.wav, self.lengths = wav, lengths
 
     def __iter__(self):
         return iter((self.index, self.score, self.fired, self.n_chunks, self.state))
@@ -276,7 +280,8 @@ def _pack_recordings(torch, recordings, lengths, device):
 
 
 def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
-         decoder=None, featurizer=None, background_index=0, quantized=None, tile=4096, return_probs=False, timings=None):
+         decoder=None, featurizer=None, background_index=0, quantized=None, tile=4096, return_probs=False, timings=None,
+         keep_audio=False):
     """The chunk loop of `StreamBatch` over R whole recordings at once: for every chunk of every recording the (index,
     score, fired) that `push` would have returned for it, and the final detector state, as a `ScanResult`.
 
@@ -285,7 +290,8 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     tile // R chunks each), kws_stream_gather_windows -> the model's (or `quantized`'s) forward ->
     kws_stream_scan_postprocess, which carries the detector state from tile to tile.  Everything is enqueued on the
     current stream; the host does not wait for the device.  `timings`: an optional dict that receives lists of
-    (start, end) CUDA event pairs per stage ("rows", "gather", "forward", "scan") for tools/scanbench.py."""
+    (start, end) CUDA event pairs per stage ("rows", "gather", "forward", "scan") for tools/scanbench.py.  keep_audio: the
+    result keeps the packed int16 tensor and the lengths built here (`ScanResult.wav`, `.lengths`)."""
     torch = _torch()
     if pr.use_delta:
         raise ValueError("streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered")
@@ -310,8 +316,9 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     probs_all = torch.empty((R, T_max, C), dtype=torch.float32, device=dev) if return_probs else None
     state = torch.zeros((R, 2), dtype=torch.int32, device=dev)
     state[:, 1] = -1
+    kept = (wav, lens) if keep_audio else (None, None)
     if R == 0 or T_max == 0:
-        return ScanResult(index, score, fired, n_chunks, state, probs_all)
+        return ScanResult(index, score, fired, n_chunks, state, probs_all, *kept)
     st = _stream()
 
     def timed(name, fn):
@@ -348,7 +355,7 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
                                                                        fired.data_ptr() + off, T_max, st)))
         if return_probs:
             probs_all[:, k0:k0 + n] = probs.view(R, n, C)
-    return ScanResult(index, score, fired, n_chunks, state, probs_all)
+    return ScanResult(index, score, fired, n_chunks, state, probs_all, *kept)
 
 
 def events_to_chunks(events, n_samples, chunk_size, tolerance_samples, background_index=0, num_classes=None):
@@ -472,18 +479,9 @@ def sweep(result, sensitivities, trigger_levels, chunk_size, events=None, length
     n_events = [0] * R
     ev = [0, 0, 0, 0]                                              # ev_off, ev_class, ev_lo, ev_hi: NULL without labels
     if events is not None:
-        if tolerance_samples is None:
-            if pr is None:
-                from classifier.params import pr
-            tolerance_samples = pr.max_samples
-        lens = [n * chunk_size for n in n_chunks] if lengths is None else [int(v) for v in _host(lengths).tolist()]
-        if [-(-n // chunk_size) for n in lens] != n_chunks:
-            raise ValueError("lengths do not give the scan's chunk counts at chunk_size=%d" % chunk_size)
-        rows = events_to_chunks(events, lens, chunk_size, tolerance_samples, background_index)
+        rows = _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr)
         n_events = [len(v) for v in rows]
-        off = np.concatenate(([0], np.cumsum(n_events))).astype(np.int32)
-        flat = np.array([e for v in rows for e in v] or [(0, 0, 0)], dtype=np.int32).reshape(-1, 3)
-        keep = [torch.from_numpy(off).to(dev)] + [torch.from_numpy(np.ascontiguousarray(flat[:, i])).to(dev) for i in range(3)]
+        keep = _event_tensors(torch, rows, dev)
         ev = [t.data_ptr() for t in keep]
     counts = torch.zeros((R, P, 5), dtype=torch.int32, device=dev)
     if R > 0 and P > 0:
@@ -495,3 +493,263 @@ def sweep(result, sensitivities, trigger_levels, chunk_size, events=None, length
                                                counts.data_ptr(), _stream()))
     f = counts.permute(2, 0, 1).contiguous().view(5, R, S, L)
     return SweepResult(f[0], f[1], f[2], f[3], f[4], n_events, sens, levels)
+
+
+def _scan_arrays(result, chunk_size):
+    """The checks `collect` and `peaks` share with `sweep`, before any device use -> (index, score, n_chunks, audio)"""
+    import torch
+    audio = None
+    if isinstance(result, ScanResult):
+        index, score, n_chunks = result.index, result.score, result.n_chunks
+        if result.wav is not None:
+            audio = (result.wav, result.lengths)
+    else:
+        index, score, n_chunks = result
+    if int(chunk_size) < 1:
+        raise ValueError("chunk_size must be positive")
+    if not (isinstance(index, torch.Tensor) and isinstance(score, torch.Tensor) and index.dtype == torch.int32
+            and score.dtype == torch.float64 and index.dim() == 2 and index.shape == score.shape):
+        raise ValueError("index / score must be (R, stride) int32 / float64 CUDA tensors of one shape")
+    n_chunks = [int(v) for v in n_chunks]
+    R, stride = int(index.shape[0]), int(index.shape[1])
+    if len(n_chunks) != R or any(v < 0 or v > stride for v in n_chunks):
+        raise ValueError("n_chunks must give one chunk count in 0..%d per recording" % stride)
+    return index, score, n_chunks, audio
+
+
+def _on_device(index, score):
+    """the last of the checks: every other one has passed on host data alone"""
+    if not (index.is_cuda and score.is_cuda):
+        raise ValueError("index / score must be (R, stride) int32 / float64 CUDA tensors of one shape")
+
+
+def _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr):
+    """`sweep`'s handling of labelled events -> per recording [(class, lo, hi), ...] in chunk units.  Pure Python."""
+    if tolerance_samples is None:
+        if pr is None:
+            from classifier.params import pr
+        tolerance_samples = pr.max_samples
+    lens = [n * chunk_size for n in n_chunks] if lengths is None else [int(v) for v in _host(lengths).tolist()]
+    if [-(-n // chunk_size) for n in lens] != n_chunks:
+        raise ValueError("lengths do not give the scan's chunk counts at chunk_size=%d" % chunk_size)
+    return events_to_chunks(events, lens, chunk_size, tolerance_samples, background_index)
+
+
+def _event_tensors(torch, rows, dev):
+    """-> [ev_off, ev_class, ev_lo, ev_hi] device tensors (CSR over the recordings)"""
+    off = np.concatenate(([0], np.cumsum([len(v) for v in rows]))).astype(np.int32)
+    flat = np.array([e for v in rows for e in v] or [(0, 0, 0)], dtype=np.int32).reshape(-1, 3)
+    return [torch.from_numpy(off).to(dev)] + [torch.from_numpy(np.ascontiguousarray(flat[:, i])).to(dev) for i in range(3)]
+
+
+class Detections(object):
+    """Chunks of scanned recordings worth keeping: the activations `collect` found, or the near misses of `peaks`.
+
+    n: host list, per recording the number found (for `collect` also when a given max_det stored fewer: n_stored).
+    recording / chunk / cls / kind / event (int32) and score (float64): CUDA tensors with one entry per stored detection,
+    flattened recording by recording -- in chunk order for `collect`, in pick order (best first) for `peaks`.  kind is one of
+    kws_amd.lib.DET_UNLABELLED / DET_HIT / DET_DUPLICATE / DET_FALSE_ALARM; event is the position of the matched event within
+    its recording's (sorted) events, or -1."""
+
+    def __init__(self, n, recording, chunk, cls, kind, event, score, chunk_size, n_stored=None, audio=None):
+        self.n = [int(v) for v in n]
+        self.n_stored = self.n if n_stored is None else [int(v) for v in n_stored]
+        self.recording, self.chunk, self.cls, self.kind, self.event, self.score = recording, chunk, cls, kind, event, score
+        self.chunk_size = int(chunk_size)
+        self._audio = audio                                        # (packed int16 tensor, lengths) of a scan made with keep_audio
+
+    def __len__(self):
+        return int(self.chunk.shape[0])
+
+    def select(self, kind=None):
+        """The detections of one kind, or of any of several (an int or an iterable of ints; None keeps all), in the same
+        order.  Reads the mask back to count per recording (one synchronisation)."""
+        torch = _torch()
+        if kind is None:
+            return self
+        kinds = [int(kind)] if isinstance(kind, (int, np.integer)) else [int(v) for v in kind]
+        mask = torch.zeros_like(self.kind, dtype=torch.bool)
+        for v in kinds:
+            mask |= self.kind == v
+        n = torch.bincount(self.recording[mask].to(torch.int64), minlength=len(self.n)).cpu().tolist() if len(self.n) else []
+        return Detections(n, self.recording[mask], self.chunk[mask], self.cls[mask], self.kind[mask], self.event[mask], self.score[mask],
+                          self.chunk_size, audio=self._audio)
+
+    def times(self, chunk_size=None, sample_rate=None):
+        """float64 CUDA tensor: seconds from the start of the recording to the first sample of each detection's chunk"""
+        if sample_rate is None:
+            from classifier.params import pr
+            sample_rate = pr.sample_rate
+        torch = _torch()
+        c = self.chunk_size if chunk_size is None else int(chunk_size)
+        first = (self.chunk.to(torch.int64) * c).to(torch.float64)
+        # a tensor divisor: dividing by a Python scalar multiplies by its reciprocal on the device, one ulp off k * c / rate
+        return first / torch.full_like(first, float(sample_rate))
+
+    def clips(self, recordings=None, lengths=None, pr=None):
+        """(len(self), pr.buffer_samples) float32 CUDA tensor: clip i is the listener's audio_buffer right after its chunk k
+        (listen.py:90,100) -- samples [n_k - B, n_k) of its recording with n_k = min((k + 1) * chunk_size, N), scaled by
+        1/32768, zeros in front where n_k < B.  It feeds `Featurizer` and raw-audio training as it is.  recordings: what `scan`
+        takes (with `lengths` for a padded array); None uses the audio a scan(..., keep_audio=True) kept.  The triples are
+        built with torch on the device and cut by kws_vad_gather_clips; nothing is synchronised."""
+        torch = _torch()
+        if pr is None:
+            from classifier.params import pr
+        B = int(pr.buffer_samples)
+        if recordings is None:
+            if self._audio is None:
+                raise ValueError("clips needs the recordings, or detections of a scan made with keep_audio=True")
+            wav, lens = self._audio
+        else:
+            wav, lens = _pack_recordings(torch, recordings, lengths, self.chunk.device)
+        if len(lens) != len(self.n):
+            raise ValueError("%d recordings for detections of %d" % (len(lens), len(self.n)))
+        dev = wav.device
+        n = len(self)
+        out = torch.empty((n, B), dtype=torch.float32, device=dev)
+        if n == 0:
+            return out
+        d_len = torch.tensor(lens, dtype=torch.int32).to(dev)
+        rec = self.recording.to(torch.int64)
+        end = torch.minimum((self.chunk.to(torch.int64) + 1) * self.chunk_size, d_len.to(torch.int64)[rec])
+        tri = torch.stack([rec, torch.clamp(end - B, min=0), end], dim=1).to(torch.int32).contiguous()
+        _l.check(_l.get_lib().kws_vad_gather_clips(wav.data_ptr(), _l.WAV_I16, int(wav.shape[0]), int(wav.shape[1]), d_len.data_ptr(),
+                                                  tri.data_ptr(), n, B, 0, 0, _l.VAD_ALIGN["left"], out.data_ptr(), _stream()))
+        return out
+
+    def save(self, recordings, save_dir, class_names, names=None, session_id=None, pr=None, lengths=None, record_start=0):
+        """Writes every detection's clip as <save_dir>/<class_names[cls]>/<session_id>_<record_num>.wav, the layout of the
+        reference's Listener.on_activation (listen.py:299-308; record_num counts from record_start, session_id defaults to nine
+        random digits as in listen.py:94), or, with `names` (one stem per recording), <stem>_<chunk>.wav.  16-bit mono at
+        pr.sample_rate with the samples of the reference's save_audio, (audio * 32767).astype(int16) of the float64 buffer:
+        truncated toward zero, not a copy of the PCM.  -> the list of paths, in detection order."""
+        import os
+        import wave
+        from random import randint
+        torch = _torch()
+        if pr is None:
+            from classifier.params import pr
+        if pr.sample_depth != 2:
+            raise ValueError("only 16-bit sample depth is supported")               # data_utils.py:44
+        if names is not None and len(names) != len(self.n):
+            raise ValueError("%d names for %d recordings" % (len(names), len(self.n)))
+        if session_id is None:
+            session_id = '%09d' % randint(0, 999999999)
+        clips = self.clips(recordings, lengths=lengths, pr=pr)
+        pcm = (clips.to(torch.float64) * 32767).to(torch.int16).cpu().numpy()    # float -> int conversion truncates toward zero
+        rec, chunk, cls = self.recording.cpu().tolist(), self.chunk.cpu().tolist(), self.cls.cpu().tolist()
+        paths = []
+        for i in range(len(rec)):
+            folder = os.path.join(save_dir, class_names[cls[i]])
+            os.makedirs(folder, exist_ok=True)
+            stem = '%s_%d' % (session_id, record_start + i) if names is None else '%s_%d' % (names[rec[i]], chunk[i])
+            paths.append(os.path.join(folder, stem + '.wav'))
+            wf = wave.open(paths[-1], 'wb')
+            wf.setnchannels(1)
+            wf.setsampwidth(pr.sample_depth)
+            wf.setframerate(pr.sample_rate)
+            wf.writeframes(pcm[i].astype('<i2').tobytes())
+            wf.close()
+        return paths
+
+
+def _flatten(torch, counts, fields, score):
+    """(R, cap, F) records and (R, cap) scores with counts (R) valid ones per recording -> (records, recording, score) of the
+    valid ones, recording by recording"""
+    R, cap = int(fields.shape[0]), int(fields.shape[1])
+    dev = fields.device
+    keep = torch.arange(cap, device=dev)[None, :] < counts[:, None]                       # (R, cap)
+    rec = torch.arange(R, device=dev, dtype=torch.int32)[:, None].expand(-1, cap)[keep]
+    return fields[keep], rec, score[keep]
+
+
+def collect(result, chunk_size, sensitivity=0.5, trigger_level=3, events=None, lengths=None, tolerance_samples=None, background_index=0,
+            max_det=None, pr=None):
+    """The activations of scanned recordings at one operating point (kws_stream_collect): what Listener.on_activation
+    (listen.py:291-308) would have been called for, file by file, with each activation classified against labelled events --
+    hit, duplicate or false alarm, by `sweep`'s rule -- so the false alarms can become `background` clips.
+
+    result / events / lengths / tolerance_samples / background_index / pr: as `sweep` takes them, with the same checks.  The
+    walk is recomputed from the scan's index / score, so any point of a sweep can be collected without scanning again.
+    max_det: slots per recording; the default is the largest count, found by a counting launch (max_det = 0) whose result
+    is read back -- the one host synchronisation here.  Returns `Detections` in (recording, chunk) order."""
+    chunk_size = int(chunk_size)
+    index, score, n_chunks, audio = _scan_arrays(result, chunk_size)
+    if max_det is not None and int(max_det) < 0:
+        raise ValueError("max_det must be >= 0")
+    rows = None if events is None else _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr)
+    _on_device(index, score)
+    torch = _torch()
+    L = _l.get_lib()
+    R, stride = int(index.shape[0]), int(index.shape[1])
+    dev = index.device
+    index, score = index.contiguous(), score.contiguous()
+    keep = None if rows is None else _event_tensors(torch, rows, dev)
+    ev = [0, 0, 0, 0] if keep is None else [t.data_ptr() for t in keep]
+    d_chunks = torch.tensor(n_chunks, dtype=torch.int32).to(dev)
+    n_det = torch.zeros(R, dtype=torch.int32, device=dev)
+
+    def launch(cap, det, det_score):
+        _l.check(L.kws_stream_collect(index.data_ptr(), score.data_ptr(), R, stride, d_chunks.data_ptr(), int(background_index), chunk_size,
+                                      float(sensitivity), int(trigger_level), ev[0], ev[1], ev[2], ev[3], cap, n_det.data_ptr(), det,
+                                      det_score, _stream()))
+
+    n = None
+    if max_det is None:
+        launch(0, 0, 0)
+        n = n_det.cpu().tolist()
+        cap = max(n + [0])
+    else:
+        cap = int(max_det)
+    det = torch.empty((R, cap, 4), dtype=torch.int32, device=dev)
+    det_score = torch.empty((R, cap), dtype=torch.float64, device=dev)
+    if n is None or cap > 0:
+        launch(cap, det.data_ptr(), det_score.data_ptr())
+    if n is None:
+        n = n_det.cpu().tolist()
+    f, rec, sc = _flatten(torch, torch.clamp(n_det, max=cap), det, det_score)
+    return Detections(n, rec, f[:, 0].contiguous(), f[:, 1].contiguous(), f[:, 2].contiguous(), f[:, 3].contiguous(), sc, chunk_size,
+                      n_stored=[min(v, cap) for v in n], audio=audio)
+
+
+def _check_peaks(k, min_gap):
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k=%d peaks per recording is outside 1..64" % int(k))
+    if min_gap is not None and int(min_gap) < 1:
+        raise ValueError("min_gap=%d must be at least 1" % int(min_gap))
+
+
+def peaks(result, chunk_size, k=8, min_score=0.0, min_gap=None, events=None, lengths=None, tolerance_samples=None, background_index=0,
+          pr=None):
+    """The near misses of scanned recordings (kws_stream_peaks): per recording the up to k highest-scoring non-background
+    chunks with score > min_score, at least min_gap chunks apart (default ceil(pr.buffer_samples / chunk_size): their
+    clips do not overlap), chosen greedily, best first, ties to the earlier chunk.  With `events` (as `sweep` takes them) the
+    chunks inside any event's window are left out, whatever the class: labelled keywords are no negatives.  Returns
+    `Detections` in (recording, pick) order with kind DET_UNLABELLED and event -1; n is read back (one synchronisation)."""
+    chunk_size = int(chunk_size)
+    _check_peaks(k, min_gap)
+    index, score, n_chunks, audio = _scan_arrays(result, chunk_size)
+    if min_gap is None:
+        if pr is None:
+            from classifier.params import pr
+        min_gap = max(1, -(-int(pr.buffer_samples) // chunk_size))
+    rows = None if events is None else _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr)
+    _on_device(index, score)
+    torch = _torch()
+    k, min_gap = int(k), int(min_gap)
+    R, stride = int(index.shape[0]), int(index.shape[1])
+    dev = index.device
+    index, score = index.contiguous(), score.contiguous()
+    keep = None if rows is None else _event_tensors(torch, rows, dev)
+    ev = [0, 0, 0, 0] if keep is None else [t.data_ptr() for t in keep]
+    d_chunks = torch.tensor(n_chunks, dtype=torch.int32).to(dev)
+    n_peaks = torch.zeros(R, dtype=torch.int32, device=dev)
+    found = torch.empty((R, k, 2), dtype=torch.int32, device=dev)
+    found_score = torch.empty((R, k), dtype=torch.float64, device=dev)
+    _l.check(_l.get_lib().kws_stream_peaks(index.data_ptr(), score.data_ptr(), R, stride, d_chunks.data_ptr(), int(background_index),
+                                           float(min_score), min_gap, ev[0], ev[2], ev[3], k, n_peaks.data_ptr(), found.data_ptr(),
+                                           found_score.data_ptr(), _stream()))
+    n = n_peaks.cpu().tolist()
+    f, rec, sc = _flatten(torch, n_peaks, found, found_score)
+    chunk = f[:, 0].contiguous()
+    return Detections(n, rec, chunk, f[:, 1].contiguous(), torch.zeros_like(chunk), torch.full_like(chunk, -1), sc, chunk_size, audio=audio)

@@ -6,6 +6,9 @@ kws_amd.stream.StreamBatch -- feature update, forward pass, score decoding and t
 `Listener.scan_wav` (CLI: --scan) is the offline form for recorded audio: whole files, or a directory of them, go through
 kws_amd.stream.scan at once and give per chunk what `run_wav` gives.  `Listener.sweep_wav` (CLI: --sweep) scans labelled
 recordings once and evaluates the detector at a whole grid of (sensitivity, trigger_level): miss rate against false alarms per hour.
+`--save_dir` saves the audio buffer of every activation as the reference does (listen.py:299-308): chunk by chunk in `run_wav`, and
+for whole files at once in --scan / --sweep through `Listener.collect_wav` (kws_amd.stream.collect / peaks), which with labels
+tells false alarms from hits and can add the near misses that never fired (--mine_peaks).
 
 Differences from listen.py: checkpoints are the `.npz` files classifier.model writes (no h5/pb/tflite/onnx/mnn
 back ends); there is no PyAudio in this image, so `run_microphone` raises and `run_wav` does not play the audio while it
@@ -15,6 +18,7 @@ import argparse
 import json
 import os
 import wave
+from random import randint
 from shutil import get_terminal_size
 
 import numpy as np
@@ -22,8 +26,16 @@ import numpy as np
 from classifier.model import get_model
 from classifier.params import inject_params, pr
 from common.utils import get_classes
+from kws_amd import lib as _lib
 from kws_amd.stream import StreamBatch, ThresholdDecoder, TriggerDetector, scan  # noqa: F401  (re-exported like listen.py:452,525)
-from kws_amd.stream import sweep
+from kws_amd.stream import collect, peaks, sweep
+
+SAVE_KINDS = {                                         # --save_kind -> the kinds of kws_amd.stream.Detections it keeps
+    "false_alarms": (_lib.DET_FALSE_ALARM,),
+    "hits": (_lib.DET_HIT,),
+    "duplicates": (_lib.DET_DUPLICATE,),
+    "all": None,
+}
 
 default_config = {                                     # listen.py:31-40
     "model_path": '',
@@ -116,6 +128,11 @@ class Listener(object):
         self._sb = self.batch(1)
         self.detector = self._sb                       # detector state lives in the stream batch (device)
         self.activations = []
+        # listen.py:90,94: the last buffer_samples samples (kept as the PCM that arrived; `audio_buffer` scales them) and the
+        # names of the clips --save_dir writes
+        self._pcm_ring = np.zeros(self.pr.buffer_samples, dtype=np.int16)
+        self.session_id, self.record_num = '%09d' % randint(0, 999999999), 0
+        self.saved_paths = []
 
     def batch(self, n_streams):
         """A StreamBatch of n lock-stepped streams sharing this listener's model, decoder and settings."""
@@ -123,8 +140,18 @@ class Listener(object):
                            sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
                            quantized=self.quantized)
 
+    @property
+    def audio_buffer(self):
+        """listen.py:90,100: the last buffer_samples samples as buffer_to_audio scales them (float64, zeros before the first)"""
+        return self._pcm_ring.astype(np.float64) / 32768.0
+
+    def _push_audio(self, chunk):
+        new = np.frombuffer(chunk, dtype='<i2')[-self._pcm_ring.size:]
+        self._pcm_ring = np.concatenate((self._pcm_ring[new.size:], new))
+
     def update_vectors(self, chunk):
         """listen.py:96-114: bytes of int16 PCM in, the (n_features, n_mfcc, 1) feature matrix out."""
+        self._push_audio(chunk)
         feats = self._sb.update_vectors([chunk])
         return np.expand_dims(feats[0].cpu().numpy(), axis=-1)
 
@@ -136,6 +163,7 @@ class Listener(object):
 
     def step(self, chunk):
         """One iteration of the loop listen.py:350-375: (index, score, activated)."""
+        self._push_audio(chunk)
         index, score, fired = self._sb.push([chunk])
         return int(index[0]), float(score[0]), bool(fired[0])
 
@@ -150,9 +178,24 @@ class Listener(object):
         cutoff = round(self.sensitivity * width)
         print(bar[:cutoff] + bar[cutoff:].replace('X', 'x') + class_name)
 
-    def on_activation(self, index, play_activate=False):
+    def on_activation(self, index, play_activate=False, save=True):
+        """listen.py:291-308.  save=False: the caller saves the clips itself (scan_wav: whole files at once, collect_wav)."""
         print('command {} detected!'.format(self.class_names[index]))
         self.activations.append(index)
+        if self.save_dir and save:
+            save_class_dir = os.path.join(self.save_dir, self.class_names[index])
+            os.makedirs(save_class_dir, exist_ok=True)
+            wav_path = os.path.join(save_class_dir, self.session_id + '_' + str(self.record_num) + '.wav')
+            assert self.pr.sample_depth == 2, 'only support 16-bit sample depth.'
+            wf = wave.open(wav_path, 'wb')
+            wf.setnchannels(1)
+            wf.setsampwidth(self.pr.sample_depth)
+            wf.setframerate(self.pr.sample_rate)
+            wf.writeframes((self.audio_buffer * 32767).astype('<i2').tobytes())      # save_audio, data_utils.py:46
+            wf.close()
+            print('Saved to ' + wav_path + '.')
+            self.saved_paths.append(wav_path)
+            self.record_num += 1
 
     def run_microphone(self):
         raise RuntimeError("PyAudio is not available in this image; feed chunks with Listener.step() or use run_wav()")
@@ -185,24 +228,25 @@ class Listener(object):
         wf.close()
         return pcm
 
-    def _scan_files(self, files):
+    def _scan_files(self, files, keep_audio=False):
         """-> (ScanResult of the files, their sample counts): read, packed and scanned at once"""
         pcm = [self._read_wav(p) for p in files]
         res = scan(self.pr, self.model._device(), pcm, chunk_size=self.chunk_size, class_names=self.class_names,
                    sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
-                   quantized=self.quantized, tile=self.scan_tile)
+                   quantized=self.quantized, tile=self.scan_tile, keep_audio=keep_audio)
         return res, [int(a.size) for a in pcm]
 
     def scan_wav(self, paths=None, quiet=True):
         """run_wav for whole files at once (kws_amd.stream.scan): `paths` is one wav or a list of them (default: input_wav).
         Returns per file the list run_wav returns, [(index, score, fired), ...] per chunk, every file starting from a fresh
         detector; on_activation is called for every fired chunk in order (and on_prediction for every chunk unless quiet).
-        `self.scan_times[i]` lists the times, in seconds from the start of file i, of its activations."""
+        `self.scan_times[i]` lists the times, in seconds from the start of file i, of its activations.  `self.last_scan` keeps
+        (ScanResult, sample counts); with save_dir set the scan keeps its audio, for `collect_wav(..., scan=self.last_scan)`."""
         if paths is None:
             paths = self.input_wav
         single = isinstance(paths, (str, bytes, os.PathLike))
         files = [paths] if single else list(paths)
-        res, _ = self._scan_files(files)
+        res, lens = self.last_scan = self._scan_files(files, keep_audio=bool(self.save_dir))
         index, score, fired = res.index.cpu().numpy(), res.score.cpu().numpy(), res.fired.cpu().numpy()
         out, self.scan_times = [], []
         for r, n in enumerate(res.n_chunks):
@@ -213,7 +257,7 @@ class Listener(object):
                     self.on_prediction(i, sc)
                 if f:
                     times.append(k * self.chunk_size / float(self.pr.sample_rate))
-                    self.on_activation(i, play_activate=False)
+                    self.on_activation(i, play_activate=False, save=False)
             out.append(rows)
             self.scan_times.append(times)
         return out[0] if single else out
@@ -227,13 +271,56 @@ class Listener(object):
         files = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
         if isinstance(labels, (str, bytes, os.PathLike)):
             labels = parse_labels(labels, self.class_names, self.pr.sample_rate)
-        res, lens = self._scan_files(files)
+        res, lens = self._scan_files(files, keep_audio=bool(self.save_dir))
         events = None if labels is None else [labels.get(os.path.basename(p), []) for p in files]
         tol = None if tolerance_s is None else int(round(tolerance_s * self.pr.sample_rate))
         out = sweep(res, sensitivities, trigger_levels, self.chunk_size, events=events, lengths=lens, tolerance_samples=tol, pr=self.pr)
         out.seconds = [n / float(self.pr.sample_rate) for n in lens]
-        self.sweep_scan = res
+        self.sweep_scan, self.sweep_lengths = res, lens
         return out
+
+    def collect_wav(self, paths, labels=None, sensitivity=None, trigger_level=None, tolerance_s=None, save_dir=None, save_kind=None,
+                    mine_peaks=0, min_peak_score=0.0, scan=None):
+        """The activations of whole files as training clips (kws_amd.stream.collect -> Detections.save): what run_wav with
+        save_dir writes file by file, for all files in one pass.  `labels` as sweep_wav takes them: every activation is then a
+        hit, a duplicate or a false alarm, and save_kind ('false_alarms', the default, 'hits', 'duplicates' or 'all') says
+        which are saved; without labels every activation is.  sensitivity / trigger_level default to the listener's (a sweep's
+        chosen point goes here); save_dir defaults to the listener's, and nothing is written without one.  mine_peaks = K > 0
+        also takes the K best well-separated non-background chunks per file above min_peak_score (kws_amd.stream.peaks; with
+        labels outside every event's window) and saves them under <save_dir>/near_miss/<class>/.  scan: a (ScanResult made with
+        keep_audio=True, sample counts) pair of the same files, e.g. (self.sweep_scan, self.sweep_lengths), instead of scanning.
+        Returns the Detections (all kinds); `self.collected_paths` lists the files written, `self.near_misses` the peaks."""
+        files = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+        if isinstance(labels, (str, bytes, os.PathLike)):
+            labels = parse_labels(labels, self.class_names, self.pr.sample_rate)
+        save_dir = self.save_dir if save_dir is None else save_dir
+        save_kind = save_kind or getattr(self, 'save_kind', None) or 'false_alarms'
+        if save_kind not in SAVE_KINDS:
+            raise ValueError("save_kind must be one of %s, got %r" % (', '.join(sorted(SAVE_KINDS)), save_kind))
+        res, lens = scan if scan is not None else self._scan_files(files, keep_audio=True)
+        if res.wav is None:
+            raise ValueError("collect_wav needs a scan made with keep_audio=True")
+        events = None if labels is None else [labels.get(os.path.basename(p), []) for p in files]
+        tol = None if tolerance_s is None else int(round(tolerance_s * self.pr.sample_rate))
+        common = dict(events=events, lengths=lens, tolerance_samples=tol, pr=self.pr)
+        det = collect(res, self.chunk_size, sensitivity=self.sensitivity if sensitivity is None else sensitivity,
+                      trigger_level=self.trigger_level if trigger_level is None else trigger_level, **common)
+        self.near_misses = peaks(res, self.chunk_size, k=int(mine_peaks), min_score=float(min_peak_score), **common) if mine_peaks else None
+        self.collected_paths = []
+        if save_dir:
+            keep = det if events is None else det.select(kind=SAVE_KINDS[save_kind])
+            self.collected_paths = keep.save(None, save_dir, self.class_names, session_id=self.session_id, pr=self.pr,
+                                             record_start=self.record_num)
+            self.record_num += len(keep)
+            if self.near_misses is not None:
+                stems = [os.path.splitext(os.path.basename(p))[0] for p in files]
+                self.collected_paths += self.near_misses.save(None, os.path.join(save_dir, 'near_miss'), self.class_names, names=stems,
+                                                              pr=self.pr)
+        return det
+
+    def _collect_options(self):
+        return dict(tolerance_s=getattr(self, 'tolerance_s', None), mine_peaks=getattr(self, 'mine_peaks', 0) or 0,
+                    min_peak_score=getattr(self, 'min_peak_score', 0.0) or 0.0)
 
     def run_sweep(self):
         """--sweep: the (S, L) table of miss rate and false alarms per hour, and the chosen point under --max_fa_per_hour"""
@@ -263,6 +350,12 @@ class Listener(object):
                 json.dump({"files": files, "seconds": res.seconds, "n_events": res.n_events, "sensitivities": sens, "trigger_levels": levels,
                            "miss_rate": nan(miss), "fa_per_hour": nan(fa), "max_fa_per_hour": budget, "chosen": best}, f, indent=1)
                 f.write("\n")
+        if self.save_dir and (budget is None or best is not None):
+            # the clips of the chosen point (without a budget: the listener's own), from the scan the sweep made
+            point = {} if best is None else dict(sensitivity=best['sensitivity'], trigger_level=best['trigger_level'])
+            self.collect_wav(files, getattr(self, 'labels_path', None), scan=(self.sweep_scan, self.sweep_lengths), **point,
+                             **self._collect_options())
+            print('saved %d clips under %s' % (len(self.collected_paths), self.save_dir))
         return res
 
     def run(self):
@@ -279,6 +372,9 @@ class Listener(object):
                 print('%s: %d chunks, %d activations' % (path, len(rows), len(hits)))
                 for t, i in zip(times, hits):
                     print('  %9.3f s  %s' % (t, self.class_names[i]))
+            if self.save_dir:
+                self.collect_wav(files, getattr(self, 'labels_path', None), scan=self.last_scan, **self._collect_options())
+                print('saved %d clips under %s' % (len(self.collected_paths), self.save_dir))
             return results
         if self.input_wav:
             return self.run_wav()
@@ -303,7 +399,7 @@ def main():
     parser.add_argument('--sweep', action='store_true',
                         help='scan the recording(s) once and evaluate the detector at every (sensitivity, trigger level) of a grid')
     parser.add_argument('--labels_path', type=str, default=None,
-                        help='--sweep: text file, one event per line: wav_name class_name start_seconds end_seconds (# comments)')
+                        help='--sweep (and --scan with --save_dir): text file, one event per line: wav_name class_name start_seconds end_seconds (# comments)')
     parser.add_argument('--sensitivities', type=str, default=None, help='--sweep: a,b,c or lo:hi:n (default: --sensitivity alone)')
     parser.add_argument('--trigger_levels', type=str, default=None, help='--sweep: 1,2,3,... (default: --trigger_level alone)')
     parser.add_argument('--tolerance_s', type=float, default=None,
@@ -311,6 +407,15 @@ def main():
     parser.add_argument('--max_fa_per_hour', type=float, default=None,
                         help='--sweep: report the point with the lowest miss rate within this many false alarms per hour')
     parser.add_argument('--sweep_out', type=str, default=None, help='--sweep: write the table and the chosen point to this JSON file')
+    parser.add_argument('--save_dir', type=str, default=None,
+                        help='folder to save false positives: the audio buffer of every activation, as <class>/<session>_<n>.wav; '
+                             'with --scan / --sweep all files are collected in one pass (with --sweep at the chosen point)')
+    parser.add_argument('--save_kind', type=str, default='false_alarms', choices=sorted(SAVE_KINDS),
+                        help='--scan / --sweep with --labels_path: which activations --save_dir keeps (without labels: all)')
+    parser.add_argument('--mine_peaks', type=int, default=0,
+                        help='--scan / --sweep with --save_dir: also save the K best well-separated non-background chunks of every file '
+                             '(1..64), fired or not, under <save_dir>/near_miss/<class>/; with labels outside the event windows')
+    parser.add_argument('--min_peak_score', type=float, default=0.0, help='--mine_peaks: only chunks scoring above this')
     args = parser.parse_args()
     if not args.model_path and not args.quantized_path:
         parser.error('one of --model_path and --quantized_path is required')
