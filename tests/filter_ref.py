@@ -2,32 +2,14 @@
 kws_filter_apply and scipy.signal.filtfilt's defaults on second-order sections, batched over clips."""
 import numpy as np
 
-M32 = np.uint64(0xFFFFFFFF)
+from aug_ref import np_pick
+
 MIX = 0xD1B54A32D192ED03
-
-
-def np_hash(seed, step, index):
-    """csrc/kws_augment.h aug_hash"""
-    index = np.asarray(index, np.uint64) & M32
-    key_lo = np.uint64((seed & 0xFFFFFFFF) ^ ((step * 0x27D4EB2F) & 0xFFFFFFFF))
-    key_hi = np.uint64(((seed >> 32) + step) & 0xFFFFFFFF)
-    h = index ^ key_lo
-    h = (h + key_hi * np.uint64(0x9E3779B9)) & M32
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85EBCA6B)) & M32
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xC2B2AE35)) & M32
-    h ^= h >> np.uint64(16)
-    return h
 
 
 def np_draws(seed, step, pos, rate, K):
     """filter index per clip, -1 when not drawn (before the Lv <= padlen rule)"""
-    seed_f = seed ^ MIX
-    pos = np.asarray(pos, np.uint64)
-    u = (np_hash(seed_f, step, 2 * pos) >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
-    k = ((np_hash(seed_f, step, 2 * pos + 1) * np.uint64(K)) >> np.uint64(32)).astype(np.int64)
-    return np.where(u < np.float32(rate), k, -1)
+    return np_pick(seed ^ MIX, step, pos, rate, K)
 
 
 def _norm(sos):

@@ -6,25 +6,11 @@ import math
 
 import numpy as np
 
-M32 = np.uint64(0xFFFFFFFF)
+from aug_ref import np_hash, np_unit
+
 MIX = 0xA0761D6478BD642F
 EPS32 = float(np.finfo(np.float32).eps)
 DEFAULTS = dict(zero_crossings=16, phases=512, beta=8.555504641634386, rolloff=0.85)
-
-
-def np_hash(seed, step, index):
-    """csrc/kws_augment.h aug_hash"""
-    index = np.asarray(index, np.uint64) & M32
-    key_lo = np.uint64((seed & 0xFFFFFFFF) ^ ((step * 0x27D4EB2F) & 0xFFFFFFFF))
-    key_hi = np.uint64(((seed >> 32) + step) & 0xFFFFFFFF)
-    h = index ^ key_lo
-    h = (h + key_hi * np.uint64(0x9E3779B9)) & M32
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85EBCA6B)) & M32
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xC2B2AE35)) & M32
-    h ^= h >> np.uint64(16)
-    return h
 
 
 def _fmaf(a, b, c):
@@ -36,8 +22,7 @@ def np_draws(seed, step, pos, speed_rate=0.0, speed=(1.0, 1.0), loud_rate=0.0, l
     """-> (resampled bool, r float32, levelled bool, target float32) per clip at the global positions pos, seed = WaveAugment's"""
     seed_s = seed ^ MIX
     pos = np.asarray(pos, np.uint64)
-    u = [(np_hash(seed_s, step, np.uint64(4) * pos + np.uint64(f)) >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
-         for f in range(4)]
+    u = [np_unit(np_hash(seed_s, step, np.uint64(4) * pos + np.uint64(f))) for f in range(4)]
     lo, hi = np.float32(speed[0]), np.float32(speed[1])
     dlo, dhi = np.float32(loudness[0]), np.float32(loudness[1])
     return (u[0] < np.float32(speed_rate), _fmaf(u[1], hi - lo, lo), u[2] < np.float32(loud_rate), _fmaf(u[3], dhi - dlo, dlo))

@@ -7,10 +7,11 @@ import os
 import numpy as np
 import pytest
 
+from aug_ref import M32, np_hash, np_uniform, np_unit
+
 pytestmark = pytest.mark.gpu
 
 ATOL = 2e-4            # the featurizer suite's tolerance against the float64 oracle
-M32 = np.uint64(0xFFFFFFFF)
 
 
 @pytest.fixture(scope="module")
@@ -26,30 +27,12 @@ def _oracle():
     return fo
 
 
-# ---- numpy restatement of csrc/kws_augment.h -----------------------------------------------------------------------------------------
-def np_hash(seed, step, index):
-    index = np.asarray(index, np.uint64)
-    key_lo = np.uint64((seed & 0xFFFFFFFF) ^ ((step * 0x27D4EB2F) & 0xFFFFFFFF))
-    key_hi = np.uint64(((seed >> 32) + step) & 0xFFFFFFFF)
-    h = index ^ key_lo
-    h = (h + key_hi * np.uint64(0x9E3779B9)) & M32
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85EBCA6B)) & M32
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xC2B2AE35)) & M32
-    h ^= h >> np.uint64(16)
-    return h
-
-
-def np_uniform(h, n):
-    return ((h * np.asarray(n, np.uint64)) >> np.uint64(32)).astype(np.int64)
-
-
+# ---- numpy restatement of csrc/kws_augment.hip's plan (the draws: tests/aug_ref.py) ----------------------------------------------------
 def np_plan(seed, step, pos, lv, seg_len, snr, rate, max_shift):
     """-> dict of int / float arrays: the records kws_augment_plan draws for global positions `pos` with voice lengths `lv`"""
     base = (np.asarray(pos, np.uint64) * np.uint64(5)) & M32
     h = [np_hash(seed, step, (base + np.uint64(f)) & M32) for f in range(5)]
-    u = (h[0] >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    u = np_unit(h[0])
     apply = (u < np.float32(rate)).astype(np.int32)
     seg = np_uniform(h[1], len(seg_len))
     s = np.asarray(snr, np.float32)[np_uniform(h[2], len(snr))]

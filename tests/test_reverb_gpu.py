@@ -6,11 +6,12 @@ import os
 import numpy as np
 import pytest
 
+from aug_ref import np_pick
+
 pytestmark = pytest.mark.gpu
 
 ATOL = 2e-4            # the featurizer suite's tolerance against the float64 oracle
 CONV_TOL = 1e-7        # max |error| <= CONV_TOL * scale * ||v||_2 * ||h||_2
-M32 = np.uint64(0xFFFFFFFF)
 MIX = 0x9E3779B97F4A7C15
 
 
@@ -27,27 +28,9 @@ def _oracle():
     return fo
 
 
-# ---- numpy restatement of the draws (csrc/kws_augment.h aug_hash, fields 2 p + f) -----------------------------------------------------
-def np_hash(seed, step, index):
-    index = np.asarray(index, np.uint64) & M32
-    key_lo = np.uint64((seed & 0xFFFFFFFF) ^ ((step * 0x27D4EB2F) & 0xFFFFFFFF))
-    key_hi = np.uint64(((seed >> 32) + step) & 0xFFFFFFFF)
-    h = index ^ key_lo
-    h = (h + key_hi * np.uint64(0x9E3779B9)) & M32
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85EBCA6B)) & M32
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xC2B2AE35)) & M32
-    h ^= h >> np.uint64(16)
-    return h
-
-
+# ---- numpy restatement of the draws (tests/aug_ref.py, fields 2 p + f) ----------------------------------------------------------------
 def np_draws(seed, step, pos, rate, K):
-    seed_r = seed ^ MIX
-    pos = np.asarray(pos, np.uint64)
-    u = (np_hash(seed_r, step, 2 * pos) >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
-    k = ((np_hash(seed_r, step, 2 * pos + 1) * np.uint64(K)) >> np.uint64(32)).astype(np.int64)
-    return np.where(u < np.float32(rate), k, -1)
+    return np_pick(seed ^ MIX, step, pos, rate, K)
 
 
 def np_reverb(v, h, ms, rescale):

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "kws.h"
+#include "kws_wave_stage.h"
 
 struct kws_noise_bank {
     int K = 0;                 // segments (recordings)
@@ -30,10 +31,6 @@ struct AugDev {
     const int64_t *seg_start;
 };
 
-// the featurizer's sample conversion (kws_featurize.hip: to_f32, data_utils.py:21)
-__device__ __forceinline__ float aug_to_f32(float v) { return v; }
-__device__ __forceinline__ float aug_to_f32(short v) { return (float)v * (1.0f / 32768.0f); }
-
 // Sample t of the clip the featurizer sees: m'[t] = m[t - d] for 0 <= t - d < L (0 elsewhere and for t outside [0, L)), with
 // m[u] = v[u] + g * n[u] when the clip is noised (n = the noise window, already offset), else v[u].  One explicit fused multiply-add, so
 // no surrounding code can contract it differently.
@@ -49,23 +46,8 @@ __device__ __forceinline__ float aug_sample(const WavT *__restrict__ v, const fl
     return x;
 }
 
-// Counter-based draws (the mixing of dropout_keep, kws_device.h), keyed by (seed, step) and indexed by 5 * position + field, position =
-// the clip's GLOBAL position in the batch.  tests/test_augment_gpu.py restates this in numpy.
+// the draw fields of a clip: aug_hash(seed, step, 5 * position + field) (kws_wave_stage.h)
 enum { kAugApply = 0, kAugSegment = 1, kAugSnr = 2, kAugOffset = 3, kAugShift = 4, kAugFields = 5 };
-__host__ __device__ inline uint32_t aug_hash(uint64_t seed, uint32_t step, uint32_t index)
-{
-    const uint32_t key_lo = (uint32_t)seed ^ (step * 0x27D4EB2Fu), key_hi = (uint32_t)(seed >> 32) + step;
-    uint32_t h = index ^ key_lo;
-    h += key_hi * 0x9E3779B9u;
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
-// uniform integer in [0, n)
-__host__ __device__ inline uint32_t aug_uniform(uint32_t h, uint32_t n) { return (uint32_t)(((uint64_t)h * n) >> 32); }
 
 // featurize(apply(...)) for the featurizer configurations without a fused path (kws_augment.hip)
 int augment_apply_launch(const kws_noise_bank *bank, const kws_aug_clip *plan, const void *wav, int wav_dtype, const int32_t *index, int B,

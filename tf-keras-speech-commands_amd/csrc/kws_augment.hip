@@ -22,19 +22,15 @@ __global__ __launch_bounds__(256) void augment_plan_kernel(const WavT *__restric
     const int lane = threadIdx.x & 63;
     const int b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (b >= B) return;
-    const int row = index ? index[b] : b;
-    int lv = valid_len ? valid_len[row] : (stride > p.max_samples ? p.max_samples : (int)stride);   // the featurizer's clipping
-    lv = lv < 0 ? 0 : lv;
-    if ((int64_t)lv > stride) lv = (int)stride;
-    if (lv > p.max_samples) lv = p.max_samples;
+    const ClipSrc src = clip_src(index, valid_len, stride, p.max_samples, b);
+    const int lv = src.clipped;
 
     kws_aug_clip r;
     if (explicit_plan) {
         r = plan[b];
     } else {
-        const uint32_t pos = (uint32_t)(position_base + b) * kAugFields;
-        const uint32_t ha = aug_hash(p.seed, step, pos + kAugApply);
-        r.apply = (float)(ha >> 8) * (1.0f / 16777216.0f) < p.noised_rate ? 1 : 0;
+        const uint32_t pos = aug_pos(position_base, b, kAugFields);
+        r.apply = aug_unit(aug_hash(p.seed, step, pos + kAugApply)) < p.noised_rate ? 1 : 0;
         r.segment = (int)aug_uniform(aug_hash(p.seed, step, pos + kAugSegment), (uint32_t)K);
         r.snr_db = p.snr_db[aug_uniform(aug_hash(p.seed, step, pos + kAugSnr), (uint32_t)p.n_snr)];
         const int Lk = lv < seg_len[r.segment] ? lv : seg_len[r.segment];
@@ -46,7 +42,7 @@ __global__ __launch_bounds__(256) void augment_plan_kernel(const WavT *__restric
     if (r.apply && r.offset > seg_len[k] - L) r.offset = seg_len[k] - L;
     float g = 0.f;
     if (r.apply && L > 0) {
-        const WavT *v = wav + (int64_t)row * stride;
+        const WavT *v = wav + (int64_t)src.row * stride;
         float part = 0.f;
         for (int t = lane; t < L; t += 64) {
             const float x = aug_to_f32(v[t]);
@@ -86,14 +82,13 @@ int augment_apply_launch(const kws_noise_bank *bank, const kws_aug_clip *plan, c
 {
     if (B == 0 || max_samples == 0) return KWS_OK;
     const dim3 grid((unsigned)B), block(256);
-    if (wav_dtype == KWS_WAV_F32)
-        KWS_LAUNCH("augment_apply_f32", augment_apply_kernel<float>, grid, block, 0, s, static_cast<const float *>(wav), stride, index, plan,
-                   bank->samples, bank->d_start, max_samples, out, out_stride, lengths);
-    else
-        KWS_LAUNCH("augment_apply_i16", augment_apply_kernel<short>, grid, block, 0, s, static_cast<const short *>(wav), stride, index, plan,
-                   bank->samples, bank->d_start, max_samples, out, out_stride, lengths);
-    KWS_LAUNCH_CHECK("augment_apply_kernel");
-    return KWS_OK;
+    return for_wav_type(wav_dtype, "augment_apply_f32", "augment_apply_i16", [&](auto t, const char *name) -> int {
+        using WavT = decltype(t);
+        KWS_LAUNCH(name, augment_apply_kernel<WavT>, grid, block, 0, s, static_cast<const WavT *>(wav), stride, index, plan, bank->samples,
+                   bank->d_start, max_samples, out, out_stride, lengths);
+        KWS_LAUNCH_CHECK("augment_apply_kernel");
+        return KWS_OK;
+    });
 }
 
 }  // namespace kws
@@ -172,7 +167,6 @@ static int check_params(const kws_augment_params *p)
         if (!std::isfinite(p->snr_db[i])) return fail(KWS_ERR_INVALID, "SNR %d is not finite", i);
     if (p->max_shift < 0) return fail(KWS_ERR_INVALID, "max_shift %d is negative", p->max_shift);
     if (p->max_shift > (1 << 24)) return fail(KWS_ERR_INVALID, "max_shift %d is too large", p->max_shift);
-    if (p->max_samples < 1) return fail(KWS_ERR_INVALID, "max_samples must be >= 1");
     return KWS_OK;
 }
 
@@ -183,9 +177,7 @@ int kws_augment_plan(const kws_noise_bank *bank, const kws_augment_params *param
     if (!bank || !plan || (!wav && B > 0)) return fail(KWS_ERR_INVALID, "null argument");
     if (bank->K < 1) return fail(KWS_ERR_INVALID, "empty noise bank");
     if (int rc = check_params(params)) return rc;
-    if (B < 0 || stride < 0 || position_base < 0) return fail(KWS_ERR_INVALID, "negative batch, stride or position_base");
-    if (!valid_len && stride < 1 && B > 0) return fail(KWS_ERR_INVALID, "stride must be >= 1 when valid_len is NULL");
-    if (wav_dtype != KWS_WAV_F32 && wav_dtype != KWS_WAV_I16) return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
+    if (int rc = check_clip_batch(params->max_samples, INT_MAX, B, stride, false, valid_len, position_base, nullptr, wav_dtype)) return rc;
     if (explicit_plan)
         for (int b = 0; b < B; ++b) {
             const kws_aug_clip &r = explicit_plan[b];
@@ -199,14 +191,13 @@ int kws_augment_plan(const kws_noise_bank *bank, const kws_augment_params *param
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (explicit_plan) KWS_HIP_CHECK(hipMemcpyAsync(plan, explicit_plan, sizeof(kws_aug_clip) * B, hipMemcpyHostToDevice, s));
     const dim3 grid((unsigned)((B + 3) / 4)), block(256);
-    if (wav_dtype == KWS_WAV_F32)
-        KWS_LAUNCH("augment_plan_f32", augment_plan_kernel<float>, grid, block, 0, s, static_cast<const float *>(wav), stride, index, valid_len, B, *params,
+    return for_wav_type(wav_dtype, "augment_plan_f32", "augment_plan_i16", [&](auto t, const char *name) -> int {
+        using WavT = decltype(t);
+        KWS_LAUNCH(name, augment_plan_kernel<WavT>, grid, block, 0, s, static_cast<const WavT *>(wav), stride, index, valid_len, B, *params,
                    bank->K, bank->d_len, bank->prefix, bank->d_start, position_base, (uint32_t)step, explicit_plan ? 1 : 0, plan);
-    else
-        KWS_LAUNCH("augment_plan_i16", augment_plan_kernel<short>, grid, block, 0, s, static_cast<const short *>(wav), stride, index, valid_len, B, *params,
-                   bank->K, bank->d_len, bank->prefix, bank->d_start, position_base, (uint32_t)step, explicit_plan ? 1 : 0, plan);
-    KWS_LAUNCH_CHECK("augment_plan_kernel");
-    return KWS_OK;
+        KWS_LAUNCH_CHECK("augment_plan_kernel");
+        return KWS_OK;
+    });
 }
 
 int kws_augment_apply(const kws_noise_bank *bank, const kws_aug_clip *plan, const void *wav, int wav_dtype, const int32_t *index, int B,

@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "kws_common.h"
-#include "kws_augment.h"
+#include "kws_wave_stage.h"
 #include "kws_device.h"
 #include "kws_filter.h"
 
@@ -79,26 +79,17 @@ __global__ __launch_bounds__(64) void filter_apply_kernel(const WavT *wav, int64
     constexpr int n = 2 * S;
     __shared__ float edge[kLanes];                          // ext[0, padlen) then ext[padlen + Lv, Lv + 2 padlen); later y_fwd there
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int row = index ? index[b] : b;
-    const int ms = p.max_samples;
-    int lv = valid_len ? valid_len[row] : (stride > ms ? ms : (int)stride);   // the featurizer's clipping (kws_augment_plan)
-    lv = lv < 0 ? 0 : lv;
-    if ((int64_t)lv > stride) lv = (int)stride;
-    if (lv > ms) lv = ms;
+    const ClipSrc src = clip_src(index, valid_len, stride, p.max_samples, b);
+    const int lv = src.clipped;
 
-    int k;
-    if (explicit_filter) {
-        k = filter_used[b];                                 // the host's choices, staged in `filter_used` by kws_filter_apply
-    } else {
-        const uint32_t pos = (uint32_t)(position_base + b) * kFltFields;
-        const uint32_t ha = aug_hash(p.seed, step, pos + kFltApply);
-        k = (float)(ha >> 8) * (1.0f / 16777216.0f) < p.filter_rate ? (int)aug_uniform(aug_hash(p.seed, step, pos + kFltFilter), (uint32_t)K) : -1;
-    }
+    // the host's choices are staged in `filter_used` by kws_filter_apply
+    int k = explicit_filter ? filter_used[b]
+                            : aug_pick(p.seed, step, aug_pos(position_base, b, kFltFields), kFltApply, kFltFilter, p.filter_rate, K);
     k = __builtin_amdgcn_readfirstlane(k);
     const int padlen = k >= 0 ? padlens[k] : 0;
     if (lv <= padlen) k = -1;                               // too short for the odd extension (scipy raises): dry
     // in place, `wav` and `out` are one buffer: no __restrict__ on either
-    const WavT *v = wav + (int64_t)row * stride;
+    const WavT *v = wav + (int64_t)src.row * stride;
     float *dst = out + (int64_t)b * out_stride;
     __syncthreads();                                        // every lane has read valid_len / filter_used before lane 0 overwrites them
     if (lane == 0) {
@@ -106,8 +97,7 @@ __global__ __launch_bounds__(64) void filter_apply_kernel(const WavT *wav, int64
         if (filter_used) filter_used[b] = k;
     }
     if (k < 0) {                                            // dry: the f32 conversion
-        for (int t = lane; t < ms; t += kLanes) dst[t] = t < lv ? aug_to_f32(v[t]) : 0.f;
-        for (int64_t t = (int64_t)ms + lane; t < out_stride; t += kLanes) dst[t] = 0.f;
+        dry_copy<kLanes>(dst, v, lv, out_stride);
         return;
     }
 
@@ -211,16 +201,13 @@ int launch(const kws_filter_bank *fb, const kws_filter_params *p, const void *wa
            int32_t *lengths, int32_t *filter_used, hipStream_t s)
 {
     const dim3 grid((unsigned)B), block(kLanes);
-    if (wav_dtype == KWS_WAV_F32)
-        KWS_LAUNCH("filter_apply_f32", (filter_apply_kernel<S, float>), grid, block, 0, s, static_cast<const float *>(wav), stride, index,
-                   valid_len, *p, fb->K, fb->table, fb->d_padlen, position_base, (uint32_t)step, explicit_filter, out, out_stride, lengths,
-                   filter_used);
-    else
-        KWS_LAUNCH("filter_apply_i16", (filter_apply_kernel<S, short>), grid, block, 0, s, static_cast<const short *>(wav), stride, index,
-                   valid_len, *p, fb->K, fb->table, fb->d_padlen, position_base, (uint32_t)step, explicit_filter, out, out_stride, lengths,
-                   filter_used);
-    KWS_LAUNCH_CHECK("filter_apply_kernel");
-    return KWS_OK;
+    return for_wav_type(wav_dtype, "filter_apply_f32", "filter_apply_i16", [&](auto t, const char *name) -> int {
+        using WavT = decltype(t);
+        KWS_LAUNCH(name, (filter_apply_kernel<S, WavT>), grid, block, 0, s, static_cast<const WavT *>(wav), stride, index, valid_len, *p,
+                   fb->K, fb->table, fb->d_padlen, position_base, (uint32_t)step, explicit_filter, out, out_stride, lengths, filter_used);
+        KWS_LAUNCH_CHECK("filter_apply_kernel");
+        return KWS_OK;
+    });
 }
 
 // one zero-input step of the cascade (the kernel's recurrence in fp64): s' = A s
@@ -352,12 +339,8 @@ int kws_filter_apply(const kws_filter_bank *fb, const kws_filter_params *p, cons
     if (!fb || !p || (B > 0 && (!wav || !out || !lengths))) return fail(KWS_ERR_INVALID, "null argument");
     if (fb->K < 1) return fail(KWS_ERR_INVALID, "empty filter bank");
     if (!(p->filter_rate >= 0.f && p->filter_rate <= 1.f)) return fail(KWS_ERR_INVALID, "filter_rate %g is outside [0, 1]", (double)p->filter_rate);
-    if (p->max_samples < 1) return fail(KWS_ERR_INVALID, "max_samples must be >= 1");
-    if (p->max_samples > KWS_FILTER_MAX_SAMPLES) return fail(KWS_ERR_UNSUPPORTED, "max_samples %d > %d", p->max_samples, KWS_FILTER_MAX_SAMPLES);
-    if (B < 0 || stride < 0 || position_base < 0) return fail(KWS_ERR_INVALID, "negative batch, stride or position_base");
-    if (!valid_len && stride < 1 && B > 0) return fail(KWS_ERR_INVALID, "stride must be >= 1 when valid_len is NULL");
-    if (out_stride < p->max_samples) return fail(KWS_ERR_INVALID, "out_stride %lld < max_samples %d", (long long)out_stride, p->max_samples);
-    if (wav_dtype != KWS_WAV_F32 && wav_dtype != KWS_WAV_I16) return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
+    if (int rc = check_clip_batch(p->max_samples, KWS_FILTER_MAX_SAMPLES, B, stride, false, valid_len, position_base, &out_stride, wav_dtype))
+        return rc;
     if (B > 0 && (const void *)out == wav && (wav_dtype != KWS_WAV_F32 || index || out_stride != stride))
         return fail(KWS_ERR_INVALID, "in place (out == wav) needs float32 input, no index and out_stride == stride");
     if (explicit_filter) {

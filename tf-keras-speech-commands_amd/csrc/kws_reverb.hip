@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "kws_common.h"
-#include "kws_augment.h"
+#include "kws_wave_stage.h"
 #include "kws_device.h"
 #include "kws_reverb.h"
 
@@ -185,22 +185,13 @@ __global__ __launch_bounds__(1024) void reverb_apply_kernel(const WavT *__restri
     extern __shared__ float lds[];
     __shared__ double red[2][kThreads / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int row = index ? index[b] : b;
     const int ms = p.max_samples;
-    int lv = valid_len ? valid_len[row] : (stride > ms ? ms : (int)stride);   // the featurizer's clipping (kws_augment_plan)
-    lv = lv < 0 ? 0 : lv;
-    if ((int64_t)lv > stride) lv = (int)stride;
-    if (lv > ms) lv = ms;
+    const ClipSrc src = clip_src(index, valid_len, stride, ms, b);
+    const int lv = src.clipped;
 
-    int k;
-    if (explicit_rir) {
-        k = lengths[b];                                     // the host's choices, staged in `lengths` by kws_reverb_apply
-    } else {
-        const uint32_t pos = (uint32_t)(position_base + b) * kRevFields;
-        const uint32_t ha = aug_hash(p.seed, step, pos + kRevApply);
-        k = (float)(ha >> 8) * (1.0f / 16777216.0f) < p.reverb_rate ? (int)aug_uniform(aug_hash(p.seed, step, pos + kRevRir), (uint32_t)K) : -1;
-    }
-    const WavT *v = wav + (int64_t)row * stride;
+    // the host's choices are staged in `lengths` by kws_reverb_apply
+    const int k = explicit_rir ? lengths[b] : aug_pick(p.seed, step, aug_pos(position_base, b, kRevFields), kRevApply, kRevRir, p.reverb_rate, K);
+    const WavT *v = wav + (int64_t)src.row * stride;
     float *dst = out + (int64_t)b * out_stride;
     const int len_out = k < 0 ? lv : (lv == 0 ? 0 : (lv + rir_len[k] - 1 < ms ? lv + rir_len[k] - 1 : ms));
     __syncthreads();                                        // every thread has read lengths[b] before thread 0 overwrites it
@@ -208,11 +199,11 @@ __global__ __launch_bounds__(1024) void reverb_apply_kernel(const WavT *__restri
         lengths[b] = len_out;
         if (rir_used) rir_used[b] = k;
     }
-    for (int64_t t = (int64_t)ms + tid; t < out_stride; t += kThreads) dst[t] = 0.f;
     if (k < 0 || lv == 0) {                                 // dry (or empty): a copy
-        for (int t = tid; t < ms; t += kThreads) dst[t] = t < lv ? aug_to_f32(v[t]) : 0.f;
+        dry_copy<kThreads>(dst, v, lv, out_stride);
         return;
     }
+    for (int64_t t = (int64_t)ms + tid; t < out_stride; t += kThreads) dst[t] = 0.f;
 
     // z[n] = v[2n] + i v[2n+1], n = tid + 1024 r; n < lv / 2 <= 8192, so r < 8 (the upper half of the input is zero: pruned loads)
     float2 a[16];
@@ -397,30 +388,23 @@ int kws_reverb_apply(const kws_rir_bank *rb, const kws_reverb_params *p, const v
     if (!rb || !p || (B > 0 && (!wav || !out || !lengths))) return fail(KWS_ERR_INVALID, "null argument");
     if (rb->K < 1) return fail(KWS_ERR_INVALID, "empty RIR bank");
     if (!(p->reverb_rate >= 0.f && p->reverb_rate <= 1.f)) return fail(KWS_ERR_INVALID, "reverb_rate %g is outside [0, 1]", (double)p->reverb_rate);
-    if (p->max_samples < 1) return fail(KWS_ERR_INVALID, "max_samples must be >= 1");
-    if (p->max_samples > kMaxSamples) return fail(KWS_ERR_UNSUPPORTED, "max_samples %d > %d", p->max_samples, kMaxSamples);
-    if (B < 0 || stride < 0 || position_base < 0) return fail(KWS_ERR_INVALID, "negative batch, stride or position_base");
-    if (!valid_len && stride < 1 && B > 0) return fail(KWS_ERR_INVALID, "stride must be >= 1 when valid_len is NULL");
-    if (out_stride < p->max_samples) return fail(KWS_ERR_INVALID, "out_stride %lld < max_samples %d", (long long)out_stride, p->max_samples);
-    if (wav_dtype != KWS_WAV_F32 && wav_dtype != KWS_WAV_I16) return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
+    if (int rc = check_clip_batch(p->max_samples, kMaxSamples, B, stride, false, valid_len, position_base, &out_stride, wav_dtype)) return rc;
     if (explicit_rir)
         for (int b = 0; b < B; ++b)
             if (explicit_rir[b] < -1 || explicit_rir[b] >= rb->K)
                 return fail(KWS_ERR_INVALID, "clip %d: RIR %d is outside [-1, %d)", b, explicit_rir[b], rb->K);
     if (B == 0) return KWS_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(reverb_apply_kernel<float>), kLdsBytes)) return rc;
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(reverb_apply_kernel<short>), kLdsBytes)) return rc;
     if (explicit_rir) KWS_HIP_CHECK(hipMemcpyAsync(lengths, explicit_rir, sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
     const dim3 grid((unsigned)B), block(kThreads);
-    if (wav_dtype == KWS_WAV_F32)
-        KWS_LAUNCH("reverb_apply_f32", reverb_apply_kernel<float>, grid, block, kLdsBytes, s, static_cast<const float *>(wav), stride, index, valid_len,
-                   *p, rb->K, rb->d_len, rb->spec, rb->tw, position_base, (uint32_t)step, explicit_rir ? 1 : 0, out, out_stride, lengths, rir_used);
-    else
-        KWS_LAUNCH("reverb_apply_i16", reverb_apply_kernel<short>, grid, block, kLdsBytes, s, static_cast<const short *>(wav), stride, index, valid_len,
-                   *p, rb->K, rb->d_len, rb->spec, rb->tw, position_base, (uint32_t)step, explicit_rir ? 1 : 0, out, out_stride, lengths, rir_used);
-    KWS_LAUNCH_CHECK("reverb_apply_kernel");
-    return KWS_OK;
+    return for_wav_type(wav_dtype, "reverb_apply_f32", "reverb_apply_i16", [&](auto t, const char *name) -> int {
+        using WavT = decltype(t);
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(reverb_apply_kernel<WavT>), kLdsBytes)) return rc;
+        KWS_LAUNCH(name, reverb_apply_kernel<WavT>, grid, block, kLdsBytes, s, static_cast<const WavT *>(wav), stride, index, valid_len, *p,
+                   rb->K, rb->d_len, rb->spec, rb->tw, position_base, (uint32_t)step, explicit_rir ? 1 : 0, out, out_stride, lengths, rir_used);
+        KWS_LAUNCH_CHECK("reverb_apply_kernel");
+        return KWS_OK;
+    });
 }
 
 }  // extern "C"

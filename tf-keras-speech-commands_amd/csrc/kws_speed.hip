@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "kws_common.h"
-#include "kws_augment.h"
+#include "kws_wave_stage.h"
 #include "kws_device.h"
 
 struct kws_resampler {
@@ -34,8 +34,6 @@ namespace spd {
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr size_t kMaxTableBytes = 64 * 1024;
 enum { kSpdApply = 0, kSpdRatio = 1, kSpdLevel = 2, kSpdTarget = 3, kSpdFields = 4 };   // draw fields: aug_hash(seed_s, step, 4 p + f)
-
-__device__ __forceinline__ float unit(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
 
 // one wing of output n: taps at v[j], j = j0, j0 + dj, ... while 0 <= j < Ls and pos = ((x0 + k) s) P < Z P
 template <typename WavT>
@@ -66,27 +64,26 @@ __global__ __launch_bounds__(kThreads) void speed_apply_kernel(const WavT *__res
     extern __shared__ float h[];                             // the table, when this clip is resampled
     __shared__ double part[kWaves];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int row = index ? index[b] : b;
-    int64_t ls64 = valid_len ? (int64_t)valid_len[row] : stride;
-    ls64 = ls64 < 0 ? 0 : ls64 > stride ? stride : ls64;
-    const int Ls = (int)ls64, ms = p.max_samples;
+    const int ms = p.max_samples;
+    const ClipSrc src = clip_src(index, valid_len, stride, ms, b);
+    const int Ls = src.len;                                  // the whole valid length is the source of a resampled clip
 
-    const uint32_t pos0 = (uint32_t)(position_base + b) * kSpdFields;
+    const uint32_t pos0 = aug_pos(position_base, b, kSpdFields);
     float r = 0.f, target = 0.f;
     bool levelled;
     if (explicit_speed) r = speed_used[b];                   // the host's values, staged in the outputs by kws_speed_apply
-    else if (unit(aug_hash(p.seed, step, pos0 + kSpdApply)) < p.speed_rate)
-        r = __fmaf_rn(unit(aug_hash(p.seed, step, pos0 + kSpdRatio)), p.speed_hi - p.speed_lo, p.speed_lo);
+    else if (aug_unit(aug_hash(p.seed, step, pos0 + kSpdApply)) < p.speed_rate)
+        r = __fmaf_rn(aug_unit(aug_hash(p.seed, step, pos0 + kSpdRatio)), p.speed_hi - p.speed_lo, p.speed_lo);
     if (explicit_db) {
         target = gain_used[b];
         levelled = !(target != target);
     } else {
-        levelled = unit(aug_hash(p.seed, step, pos0 + kSpdLevel)) < p.loud_rate;
-        target = __fmaf_rn(unit(aug_hash(p.seed, step, pos0 + kSpdTarget)), p.loud_hi_db - p.loud_lo_db, p.loud_lo_db);
+        levelled = aug_unit(aug_hash(p.seed, step, pos0 + kSpdLevel)) < p.loud_rate;
+        target = __fmaf_rn(aug_unit(aug_hash(p.seed, step, pos0 + kSpdTarget)), p.loud_hi_db - p.loud_lo_db, p.loud_lo_db);
     }
     const bool resampled = r != 0.f;
     const double rd = (double)r;
-    int lo = Ls < ms ? Ls : ms;
+    int lo = src.clipped;
     if (resampled && Ls > 0) {
         const double q = ceil((double)Ls / rd);
         lo = q < (double)ms ? (int)q : ms;
@@ -97,8 +94,12 @@ __global__ __launch_bounds__(kThreads) void speed_apply_kernel(const WavT *__res
         if (speed_used) speed_used[b] = r;
         if (gain_used && !levelled) gain_used[b] = 1.f;
     }
-    const WavT *v = wav + (int64_t)row * stride;
+    const WavT *v = wav + (int64_t)src.row * stride;
     float *dst = out + (int64_t)b * out_stride;
+    if (!resampled && !levelled) {                           // left as it is: the f32 conversion
+        dry_copy<kThreads>(dst, v, lo, out_stride);
+        return;
+    }
     double sq = 0.0;
     if (resampled) {
         const int n_table = Z * P + 1;
@@ -115,13 +116,11 @@ __global__ __launch_bounds__(kThreads) void speed_apply_kernel(const WavT *__res
             dst[n] = y;
             sq += (double)y * (double)y;
         }
-    } else if (levelled) {
+    } else {
         for (int n = tid; n < lo; n += kThreads) {
             const float y = aug_to_f32(v[n]);
             sq += (double)y * (double)y;
         }
-    } else {
-        for (int n = tid; n < lo; n += kThreads) dst[n] = aug_to_f32(v[n]);
     }
     if (levelled) {
         sq = wave_sum(sq);
@@ -254,12 +253,7 @@ int kws_speed_apply(const kws_resampler *rs, const kws_speed_params *p, const vo
         return fail(KWS_ERR_INVALID, "speed range [%g, %g] needs 0.5 <= lo <= hi <= 2", (double)p->speed_lo, (double)p->speed_hi);
     if (p->loud_rate > 0.f && !(-80.f <= p->loud_lo_db && p->loud_lo_db <= p->loud_hi_db && p->loud_hi_db <= 0.f))
         return fail(KWS_ERR_INVALID, "loudness range [%g, %g] dBFS needs -80 <= lo <= hi <= 0", (double)p->loud_lo_db, (double)p->loud_hi_db);
-    if (p->max_samples < 1) return fail(KWS_ERR_INVALID, "max_samples must be >= 1");
-    if (B < 0 || stride < 0 || position_base < 0) return fail(KWS_ERR_INVALID, "negative batch, stride or position_base");
-    if (stride > INT_MAX) return fail(KWS_ERR_UNSUPPORTED, "stride %lld does not fit 31 bits", (long long)stride);
-    if (!valid_len && stride < 1 && B > 0) return fail(KWS_ERR_INVALID, "stride must be >= 1 when valid_len is NULL");
-    if (out_stride < p->max_samples) return fail(KWS_ERR_INVALID, "out_stride %lld < max_samples %d", (long long)out_stride, p->max_samples);
-    if (wav_dtype != KWS_WAV_F32 && wav_dtype != KWS_WAV_I16) return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
+    if (int rc = check_clip_batch(p->max_samples, INT_MAX, B, stride, true, valid_len, position_base, &out_stride, wav_dtype)) return rc;
     if (B > 0 && (const void *)out == wav) return fail(KWS_ERR_INVALID, "the perturbation cannot run in place (out == wav)");
     bool needs_table = !explicit_speed && p->speed_rate > 0.f;
     if (explicit_speed) {
@@ -290,23 +284,15 @@ int kws_speed_apply(const kws_resampler *rs, const kws_speed_params *p, const vo
     if (explicit_db) KWS_HIP_CHECK(hipMemcpyAsync(gain_used, explicit_db, sizeof(float) * B, hipMemcpyHostToDevice, s));
     const int Z = rs ? rs->Z : 0, P = rs ? rs->P : 0, exs = explicit_speed ? 1 : 0, exd = explicit_db ? 1 : 0;
     const dim3 grid((unsigned)B), block(kThreads);
-    if (wav_dtype == KWS_WAV_F32) {
-        if (lds) {
-            const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&speed_apply_kernel<float>), (int)lds);
-            if (rc != KWS_OK) return rc;
-        }
-        KWS_LAUNCH("speed_apply_f32", (speed_apply_kernel<float>), grid, block, lds, s, static_cast<const float *>(wav), stride, index,
-                   valid_len, *p, table, Z, P, position_base, (uint32_t)step, exs, exd, out, out_stride, lengths, speed_used, gain_used);
-    } else {
-        if (lds) {
-            const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&speed_apply_kernel<short>), (int)lds);
-            if (rc != KWS_OK) return rc;
-        }
-        KWS_LAUNCH("speed_apply_i16", (speed_apply_kernel<short>), grid, block, lds, s, static_cast<const short *>(wav), stride, index,
-                   valid_len, *p, table, Z, P, position_base, (uint32_t)step, exs, exd, out, out_stride, lengths, speed_used, gain_used);
-    }
-    KWS_LAUNCH_CHECK("speed_apply_kernel");
-    return KWS_OK;
+    return for_wav_type(wav_dtype, "speed_apply_f32", "speed_apply_i16", [&](auto t, const char *name) -> int {
+        using WavT = decltype(t);
+        if (lds)
+            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&speed_apply_kernel<WavT>), (int)lds)) return rc;
+        KWS_LAUNCH(name, (speed_apply_kernel<WavT>), grid, block, lds, s, static_cast<const WavT *>(wav), stride, index, valid_len, *p, table,
+                   Z, P, position_base, (uint32_t)step, exs, exd, out, out_stride, lengths, speed_used, gain_used);
+        KWS_LAUNCH_CHECK("speed_apply_kernel");
+        return KWS_OK;
+    });
 }
 
 }  // extern "C"

@@ -61,7 +61,92 @@ def _wav_code(t):
     raise TypeError("waveforms must be float32 or int16, got %s" % t.dtype)
 
 
-class NoiseBank(object):
+def _clip_batch(wav, valid_len, index, shape="(rows, stride)"):
+    """-> (rows, stride, B, index pointer, valid_len pointer; 0 for None) of the B clips wav[index] (default: every row): the tensor
+    checks of every stage and of the featurizer"""
+    import torch
+    if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
+        raise ValueError("wav must be a contiguous CUDA tensor of shape %s" % shape)
+    rows, stride = wav.shape
+    B, ix, vl = rows, 0, 0
+    if index is not None:
+        if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError("index must be a contiguous CUDA int32 vector")
+        B, ix = index.numel(), index.data_ptr()
+    if valid_len is not None:
+        if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
+            raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
+        vl = valid_len.data_ptr()
+    return rows, stride, B, ix, vl
+
+
+def _explicit(values, dtype, B, what, noun="entries", flat=True):
+    """the host's per-clip values of a stage (instead of its draws) as a contiguous (B,) array; None stays None"""
+    if values is None:
+        return None
+    ex = np.asarray(values)
+    ex = np.ascontiguousarray(ex.reshape(-1) if flat else ex, dtype)
+    if ex.shape != (B,):
+        raise ValueError("explicit %s has %s %s for %d clips" % (what, ex.shape, noun, B))
+    return ex
+
+
+def _outputs(wav, B, ms, out, lengths, *used):
+    """-> [out, lengths, *used]: the caller's buffers, or fresh ones for None: out (B, ms) float32, lengths (B,) int32 and per
+    (tensor, dtype) of `used` a (B,) vector, where False means "skip it" and comes back as None"""
+    import torch
+    if out is None:
+        out = torch.empty((B, ms), dtype=torch.float32, device=wav.device)
+    elif out.dim() != 2 or out.shape[0] < B or out.shape[1] < ms or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("out must be a contiguous float32 CUDA tensor of at least (%d, %d)" % (B, ms))
+    if lengths is None:
+        lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
+    return [out, lengths] + [torch.empty((B,), dtype=dt, device=wav.device) if u is None else None if u is False else u for u, dt in used]
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _host_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _rate(name, value):
+    r = float(value)
+    if not 0.0 <= r <= 1.0:
+        raise ValueError("%s must be in [0, 1], got %r" % (name, value))
+    return r
+
+
+class _Handle(object):
+    """Owner of one native handle: made on first use by _create(L, pointer to the handle) -> status, destroyed by the library
+    function named _destroy."""
+    _h = None
+    _destroy = None
+
+    def handle(self):
+        if self._h is None:
+            _torch()
+            L = _l.get_lib()
+            h = ctypes.c_void_p()
+            _l.check(self._create(L, ctypes.byref(h)))
+            self._h, self._L = h, L
+        return self._h
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            getattr(self._L, self._destroy)(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NoiseBank(_Handle):
     """Background recordings (add_noise.py's noise_files): a folder of *.wav (read with common.data_utils.load_wav) or a list of 1-D
     float32 / int16 arrays (int16 is scaled by 1/32768, as the featurizer does)."""
 
@@ -87,7 +172,6 @@ class NoiseBank(object):
             f = [a.astype(np.float32) / 32768.0 if a.dtype == np.int16 else a.astype(np.float32) for a in segs]
             self.samples, self.dtype = np.ascontiguousarray(np.concatenate(f).astype(np.float32)), _l.WAV_F32
         self.seg_len = np.array([a.size for a in segs], np.int32)
-        self._h = None
 
     def __len__(self):
         return len(self.seg_len)
@@ -96,25 +180,10 @@ class NoiseBank(object):
         """the bank as the device holds it (float32)"""
         return self.samples.astype(np.float32) / 32768.0 if self.dtype == _l.WAV_I16 else self.samples
 
-    def handle(self):
-        if self._h is None:
-            _torch()
-            L = _l.get_lib()
-            h = ctypes.c_void_p()
-            _l.check(L.kws_noise_bank_create(self.samples.ctypes.data, self.dtype, self.seg_len.ctypes.data, len(self.seg_len), ctypes.byref(h)))
-            self._h, self._L = h, L
-        return self._h
+    _destroy = "kws_noise_bank_destroy"
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            self._L.kws_noise_bank_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self, L, out):
+        return L.kws_noise_bank_create(self.samples.ctypes.data, self.dtype, self.seg_len.ctypes.data, len(self.seg_len), out)
 
 
 def parse_snr(snr):
@@ -132,7 +201,7 @@ SPEED_OF_SOUND = 343.0            # m/s
 SINC_HALF_WIDTH = 16              # samples: the Hann-windowed sinc of a fractional delay spans [-16, 16] around it, shifted to be causal
 
 
-class RirBank(object):
+class RirBank(_Handle):
     """Room impulse responses: a folder (searched recursively) or file of *.wav read with common.data_utils.load_wav (resampled to
     pr.sample_rate), or a list of 1-D float arrays.  Every RIR is trimmed to start at its peak argmax|h| (the propagation and
     fractional-delay lead-in goes, so labels keep their timing) and divided by it (the direct path is +1); taps at index >= max_samples
@@ -166,31 +235,15 @@ class RirBank(object):
             raise ValueError("a RIR bank needs at least one RIR")
         self.taps, self.max_samples = taps, ms
         self.rir_len = np.array([t.size for t in taps], np.int32)
-        self._h = None
 
     def __len__(self):
         return len(self.taps)
 
-    def handle(self):
-        if self._h is None:
-            _torch()
-            L = _l.get_lib()
-            h = ctypes.c_void_p()
-            flat = np.ascontiguousarray(np.concatenate(self.taps), np.float32)
-            _l.check(L.kws_rir_bank_create(flat.ctypes.data, self.rir_len.ctypes.data, len(self.taps), self.max_samples, ctypes.byref(h)))
-            self._h, self._L = h, L
-        return self._h
+    _destroy = "kws_rir_bank_destroy"
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            self._L.kws_rir_bank_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self, L, out):
+        flat = np.ascontiguousarray(np.concatenate(self.taps), np.float32)
+        return L.kws_rir_bank_create(flat.ctypes.data, self.rir_len.ctypes.data, len(self.taps), self.max_samples, out)
 
 
 def _windowed_sinc_add(h, delay, amp):
@@ -382,7 +435,7 @@ def filter_padlen(order, btype):
     return 3 * (n + 1)
 
 
-class FilterBank(object):
+class FilterBank(_Handle):
     """Butterworth designs (tools/audio_process/wav_filter.py): specs (btype, order, freq) for 'lowpass' / 'highpass' or (btype, order,
     (low, high)) for 'bandpass' / 'bandstop', frequencies in Hz below the Nyquist frequency of sample_rate (default pr.sample_rate).
     Every design is butter_sos(order, 2 f / sample_rate, btype); at most FILTER_MAX_SECTIONS sections (order 8 for lowpass / highpass,
@@ -427,30 +480,14 @@ class FilterBank(object):
         for i, s in enumerate(sos):
             table[i, :s.shape[0]] = s
         self.table = np.ascontiguousarray(table, np.float64)          # (K, n_sections, 6), identity sections pad the lower orders
-        self._h = None
 
     def __len__(self):
         return len(self.sos)
 
-    def handle(self):
-        if self._h is None:
-            _torch()
-            L = _l.get_lib()
-            h = ctypes.c_void_p()
-            _l.check(L.kws_filter_bank_create(self.table.ctypes.data, self.n_sections, self.padlen.ctypes.data, len(self.sos), ctypes.byref(h)))
-            self._h, self._L = h, L
-        return self._h
+    _destroy = "kws_filter_bank_destroy"
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            self._L.kws_filter_bank_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self, L, out):
+        return L.kws_filter_bank_create(self.table.ctypes.data, self.n_sections, self.padlen.ctypes.data, len(self.sos), out)
 
 
 def _log_uniform(rng, lo, hi):
@@ -492,10 +529,11 @@ SPEED_SEED_MIX = 0xA0761D6478BD642F
 KAISER_BEST_BETA = 8.555504641634386      # the window of the widely used "kaiser_best" resampling table (stop band about -100 dB)
 
 
-class Resampler(object):
+class Resampler(_Handle):
     """The interpolation table of the speed change (kws_resampler): the right half of a Kaiser-windowed sinc with `zero_crossings`
     lobes on each side, `phases` entries per zero crossing, window parameter `beta` and cutoff `rolloff` (a fraction of the lower
-    Nyquist frequency).  A host object: the device copy is made by the first clip resampled with it."""
+    Nyquist frequency).  A host object, made at once: the device copy is made by the first clip resampled with it."""
+    _destroy = "kws_resampler_destroy"
 
     def __init__(self, zero_crossings=16, phases=512, beta=KAISER_BEST_BETA, rolloff=0.85):
         self.zero_crossings, self.phases, self.beta, self.rolloff = int(zero_crossings), int(phases), float(beta), float(rolloff)
@@ -521,17 +559,6 @@ class Resampler(object):
         if self._h is None:
             raise ValueError("this Resampler is closed")
         return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.kws_resampler_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _range(name, value, lo, hi, unit=""):
@@ -560,27 +587,14 @@ class WaveAugment(object):
         from classifier.params import pr
         if noise is None and rirs is None and filters is None and speed is None and loudness is None:
             raise ValueError("WaveAugment needs a noise bank, a RIR bank or both")
-        srate = float(speed_rate)
-        if not 0.0 <= srate <= 1.0:
-            raise ValueError("speed_rate must be in [0, 1], got %r" % speed_rate)
-        lrate = float(loudness_rate)
-        if not 0.0 <= lrate <= 1.0:
-            raise ValueError("loudness_rate must be in [0, 1], got %r" % loudness_rate)
+        srate, lrate = _rate("speed_rate", speed_rate), _rate("loudness_rate", loudness_rate)
         self.speed = None if speed is None else _range("speed", speed, 0.5, 2.0)
         self.loudness = None if loudness is None else _range("loudness", loudness, -80.0, 0.0, " dBFS")
         if resampler is not None and not isinstance(resampler, Resampler):
             raise ValueError("resampler must be a kws_amd.augment.Resampler, got %r" % (resampler,))
         self.resampler = resampler if resampler is not None or self.speed is None else Resampler()
         self.speed_rate, self.loudness_rate = srate, lrate
-        frate = float(filter_rate)
-        if not 0.0 <= frate <= 1.0:
-            raise ValueError("filter_rate must be in [0, 1], got %r" % filter_rate)
-        rrate = float(reverb_rate)
-        if not 0.0 <= rrate <= 1.0:
-            raise ValueError("reverb_rate must be in [0, 1], got %r" % reverb_rate)
-        rate = float(noised_rate)
-        if not 0.0 <= rate <= 1.0:
-            raise ValueError("noised_rate must be in [0, 1], got %r" % noised_rate)
+        frate, rrate, rate = _rate("filter_rate", filter_rate), _rate("reverb_rate", reverb_rate), _rate("noised_rate", noised_rate)
         snr = parse_snr(snr)
         if not 1 <= len(snr) <= _l.AUG_MAX_SNR:
             raise ValueError("the SNR list needs 1..%d values, got %d" % (_l.AUG_MAX_SNR, len(snr)))
@@ -626,55 +640,24 @@ class WaveAugment(object):
         buffers (out may be wider than max_samples; speed_used=False / gain_used=False skip them)."""
         from classifier.params import pr
         torch = _torch()
-        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
-            raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
-        rows, stride = wav.shape
-        B, ix = rows, 0
-        if index is not None:
-            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
-                raise ValueError("index must be a contiguous CUDA int32 vector")
-            B, ix = index.numel(), index.data_ptr()
-        vl = 0
-        if valid_len is not None:
-            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
-                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
-            vl = valid_len.data_ptr()
+        _, stride, B, ix, vl = _clip_batch(wav, valid_len, index)
         ms = int(pr.max_samples if max_samples is None else max_samples)
-        exs = exd = None
-        if explicit_speed is not None:
-            exs = np.ascontiguousarray(np.asarray(explicit_speed).reshape(-1), np.float32)
-            if exs.shape != (B,):
-                raise ValueError("explicit speed has %s entries for %d clips" % (exs.shape, B))
-            if speed_used is False:
-                speed_used = None                           # the explicit ratios are staged there
-            if self.resampler is None and exs.any():
-                raise ValueError("this WaveAugment has no resampler: give speed=... or resampler=... to change a clip's speed")
-        if explicit_db is not None:
-            exd = np.ascontiguousarray(np.asarray(explicit_db).reshape(-1), np.float32)
-            if exd.shape != (B,):
-                raise ValueError("explicit loudness has %s entries for %d clips" % (exd.shape, B))
-            if gain_used is False:
-                gain_used = None                            # the explicit targets are staged there
-        if out is None:
-            out = torch.empty((B, ms), dtype=torch.float32, device=wav.device)
-        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] < ms or not out.is_contiguous() or out.dtype != torch.float32:
-            raise ValueError("out must be a contiguous float32 CUDA tensor of at least (%d, %d)" % (B, ms))
-        if lengths is None:
-            lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
-        if speed_used is None:
-            speed_used = torch.empty((B,), dtype=torch.float32, device=wav.device)
-        if gain_used is None:
-            gain_used = torch.empty((B,), dtype=torch.float32, device=wav.device)
+        exs = _explicit(explicit_speed, np.float32, B, "speed")
+        if exs is not None and self.resampler is None and exs.any():
+            raise ValueError("this WaveAugment has no resampler: give speed=... or resampler=... to change a clip's speed")
+        exd = _explicit(explicit_db, np.float32, B, "loudness")
+        if exs is not None and speed_used is False:
+            speed_used = None                               # the explicit ratios are staged there
+        if exd is not None and gain_used is False:
+            gain_used = None                                # the explicit targets are staged there
+        out, lengths, speed_used, gain_used = _outputs(wav, B, ms, out, lengths, (speed_used, torch.float32), (gain_used, torch.float32))
         _l.check(_l.get_lib().kws_speed_apply(None if self.resampler is None else self.resampler.handle(), ctypes.byref(self.speed_params(ms)),
                                               wav.data_ptr(), _wav_code(wav), ix, B, stride, vl, int(position_base), int(step),
-                                              None if exs is None else exs.ctypes.data, None if exd is None else exd.ctypes.data,
-                                              out.data_ptr(), out.shape[1], lengths.data_ptr(),
-                                              speed_used.data_ptr() if speed_used is not False else None,
-                                              gain_used.data_ptr() if gain_used is not False else None,
-                                              torch.cuda.current_stream().cuda_stream))
+                                              _host_ptr(exs), _host_ptr(exd), out.data_ptr(), out.shape[1], lengths.data_ptr(),
+                                              _ptr(speed_used), _ptr(gain_used), torch.cuda.current_stream().cuda_stream))
         if exs is not None or exd is not None:
             torch.cuda.current_stream().synchronize()       # the host values are copied from pageable memory
-        return out, lengths, (speed_used if speed_used is not False else None), (gain_used if gain_used is not False else None)
+        return out, lengths, speed_used, gain_used
 
     @property
     def reverb_seed(self):
@@ -695,41 +678,16 @@ class WaveAugment(object):
         torch = _torch()
         if self.rirs is None:
             raise ValueError("this WaveAugment has no RIR bank")
-        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
-            raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
-        rows, stride = wav.shape
-        B, ix = rows, 0
-        if index is not None:
-            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
-                raise ValueError("index must be a contiguous CUDA int32 vector")
-            B, ix = index.numel(), index.data_ptr()
-        vl = 0
-        if valid_len is not None:
-            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
-                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
-            vl = valid_len.data_ptr()
+        _, stride, B, ix, vl = _clip_batch(wav, valid_len, index)
         ms = int(pr.max_samples if max_samples is None else max_samples)
-        ex = None
-        if explicit is not None:
-            ex = np.ascontiguousarray(np.asarray(explicit).reshape(-1), np.int32)
-            if ex.shape != (B,):
-                raise ValueError("explicit RIR choice has %s entries for %d clips" % (ex.shape, B))
-        if out is None:
-            out = torch.empty((B, ms), dtype=torch.float32, device=wav.device)
-        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] < ms or not out.is_contiguous() or out.dtype != torch.float32:
-            raise ValueError("out must be a contiguous float32 CUDA tensor of at least (%d, %d)" % (B, ms))
-        if lengths is None:
-            lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
-        if rir_used is None:
-            rir_used = torch.empty((B,), dtype=torch.int32, device=wav.device)
+        ex = _explicit(explicit, np.int32, B, "RIR choice")
+        out, lengths, rir_used = _outputs(wav, B, ms, out, lengths, (rir_used, torch.int32))
         _l.check(_l.get_lib().kws_reverb_apply(self.rirs.handle(), ctypes.byref(self.reverb_params(ms)), wav.data_ptr(), _wav_code(wav), ix, B,
-                                               stride, vl, int(position_base), int(step), None if ex is None else ex.ctypes.data,
-                                               out.data_ptr(), out.shape[1], lengths.data_ptr(),
-                                               rir_used.data_ptr() if rir_used is not False else None,
-                                               torch.cuda.current_stream().cuda_stream))
+                                               stride, vl, int(position_base), int(step), _host_ptr(ex), out.data_ptr(), out.shape[1],
+                                               lengths.data_ptr(), _ptr(rir_used), torch.cuda.current_stream().cuda_stream))
         if ex is not None:
             torch.cuda.current_stream().synchronize()       # the host choices are copied from pageable memory
-        return out, lengths, (rir_used if rir_used is not False else None)
+        return out, lengths, rir_used
 
     @property
     def filter_seed(self):
@@ -751,43 +709,18 @@ class WaveAugment(object):
         torch = _torch()
         if self.filters is None:
             raise ValueError("this WaveAugment has no filter bank")
-        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
-            raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
-        rows, stride = wav.shape
-        B, ix = rows, 0
-        if index is not None:
-            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
-                raise ValueError("index must be a contiguous CUDA int32 vector")
-            B, ix = index.numel(), index.data_ptr()
-        vl = 0
-        if valid_len is not None:
-            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
-                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
-            vl = valid_len.data_ptr()
+        _, stride, B, ix, vl = _clip_batch(wav, valid_len, index)
         ms = int(pr.max_samples if max_samples is None else max_samples)
-        ex = None
-        if explicit is not None:
-            ex = np.ascontiguousarray(np.asarray(explicit).reshape(-1), np.int32)
-            if ex.shape != (B,):
-                raise ValueError("explicit filter choice has %s entries for %d clips" % (ex.shape, B))
-            if filter_used is False:
-                filter_used = None                          # the explicit choices are staged there
-        if out is None:
-            out = torch.empty((B, ms), dtype=torch.float32, device=wav.device)
-        elif out.dim() != 2 or out.shape[0] < B or out.shape[1] < ms or not out.is_contiguous() or out.dtype != torch.float32:
-            raise ValueError("out must be a contiguous float32 CUDA tensor of at least (%d, %d)" % (B, ms))
-        if lengths is None:
-            lengths = torch.empty((B,), dtype=torch.int32, device=wav.device)
-        if filter_used is None:
-            filter_used = torch.empty((B,), dtype=torch.int32, device=wav.device)
+        ex = _explicit(explicit, np.int32, B, "filter choice")
+        if ex is not None and filter_used is False:
+            filter_used = None                              # the explicit choices are staged there
+        out, lengths, filter_used = _outputs(wav, B, ms, out, lengths, (filter_used, torch.int32))
         _l.check(_l.get_lib().kws_filter_apply(self.filters.handle(), ctypes.byref(self.filter_params(ms)), wav.data_ptr(), _wav_code(wav), ix,
-                                               B, stride, vl, int(position_base), int(step), None if ex is None else ex.ctypes.data,
-                                               out.data_ptr(), out.shape[1], lengths.data_ptr(),
-                                               filter_used.data_ptr() if filter_used is not False else None,
-                                               torch.cuda.current_stream().cuda_stream))
+                                               B, stride, vl, int(position_base), int(step), _host_ptr(ex), out.data_ptr(), out.shape[1],
+                                               lengths.data_ptr(), _ptr(filter_used), torch.cuda.current_stream().cuda_stream))
         if ex is not None:
             torch.cuda.current_stream().synchronize()       # the host choices are copied from pageable memory
-        return out, lengths, (filter_used if filter_used is not False else None)
+        return out, lengths, filter_used
 
     def params(self, max_samples):
         p = _l.KwsAugmentParams()
@@ -805,29 +738,13 @@ class WaveAugment(object):
         torch = _torch()
         if self.noise is None:
             raise ValueError("this WaveAugment has no noise bank")
-        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
-            raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, stride)")
-        rows, stride = wav.shape
-        B, ix = rows, 0
-        if index is not None:
-            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
-                raise ValueError("index must be a contiguous CUDA int32 vector")
-            B, ix = index.numel(), index.data_ptr()
-        vl = 0
-        if valid_len is not None:
-            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
-                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
-            vl = valid_len.data_ptr()
-        ex = None
-        if explicit is not None:
-            ex = np.ascontiguousarray(np.asarray(explicit, CLIP_DTYPE))
-            if ex.shape != (B,):
-                raise ValueError("explicit plan has %s records for %d clips" % (ex.shape, B))
+        _, stride, B, ix, vl = _clip_batch(wav, valid_len, index)
+        ex = _explicit(explicit, CLIP_DTYPE, B, "plan", "records", flat=False)
         if out is None:
             out = torch.empty((B, 8), dtype=torch.int32, device=wav.device)
         p = self.params(pr.max_samples if max_samples is None else max_samples)
         _l.check(_l.get_lib().kws_augment_plan(self.noise.handle(), ctypes.byref(p), wav.data_ptr(), _wav_code(wav), ix, B, stride, vl,
-                                               int(position_base), int(step), out.data_ptr(), None if ex is None else ex.ctypes.data,
+                                               int(position_base), int(step), out.data_ptr(), _host_ptr(ex),
                                                torch.cuda.current_stream().cuda_stream))
         if ex is not None:
             torch.cuda.current_stream().synchronize()       # the host records are copied from pageable memory

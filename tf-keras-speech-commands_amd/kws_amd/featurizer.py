@@ -4,6 +4,7 @@ import ctypes
 import numpy as np
 
 from . import lib as _l
+from .augment import _clip_batch
 
 
 def _torch():
@@ -91,25 +92,12 @@ class Featurizer(object):
         loudness range the clips are perturbed before all of that (kws_speed_apply into the scratch; into a second buffer when a
         reverberation follows, which does not run in place)."""
         torch = _torch()
-        if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
-            raise ValueError("wav must be a contiguous CUDA tensor of shape (B, stride)")
-        rows, stride = wav.shape
-        B = rows
-        ix = 0
-        if index is not None:
-            if index.dtype != torch.int32 or not index.is_cuda or index.dim() != 1 or not index.is_contiguous():
-                raise ValueError("index must be a contiguous CUDA int32 vector")
-            B, ix = index.numel(), index.data_ptr()
+        _, stride, B, ix, vl = _clip_batch(wav, valid_len, index, "(B, stride)")
         g = self.geometry
         if out is None:
             out = torch.empty((B, g["n_features"], g["feature_size"]), dtype=torch.float32, device=wav.device)
         elif out.numel() < B * g["n_features"] * g["feature_size"] or not out.is_contiguous():
             raise ValueError("out is too small for %d clips" % B)
-        vl = 0
-        if valid_len is not None:
-            if valid_len.dtype != torch.int32 or not valid_len.is_cuda or valid_len.numel() != rows:
-                raise ValueError("valid_len must be a CUDA int32 tensor with one element per row of wav")
-            vl = valid_len.data_ptr()
         if augment is not None and (augment.perturbs or augment.rirs is not None or augment.filters is not None):
             # speed / loudness, reverberation, then the filter (in place), into this featurizer's scratch on the call's stream; then
             # noise (or nothing)
