@@ -361,6 +361,72 @@ int kws_speed_apply(const kws_resampler *rs, const kws_speed_params *params, con
                     void *stream);
 
 /* ------------------------------------------------------------------------
+ * SpecAugment of the FEATURES (time warp, time masks, frequency masks): the one augmentation stage behind the featurizer (or behind the
+ * gather of cached features) and in front of the model.  The reference has no counterpart; this comment is the definition.  Clip b sits
+ * at global batch position p = position_base + b; its features are x[T][F], T = n_features frames of F = feature_size coefficients.
+ * Draws: h_f = aug_hash(seed, step, 32 p + f) (kws_wave_stage.h; 32 fields per clip; kws_amd passes seed_m = FeatureMask seed ^
+ * 0xE7037ED1A0B428DB, so the draws of the wave stages are unchanged under the same user seed).  In this order:
+ *   apply (f = 0):  the clip is transformed iff ((h_0 >> 8) * 2^-24) < rate; any other clip is bit-identical on output.
+ *   time warp (max_warp = W > 0, needs T >= 2 W + 3): c = W + 1 + aug_uniform(h_1, T - 2 W - 2), d = (int)aug_uniform(h_2, 2 W + 1) - W,
+ *         so frame c moves to c + d in [1, T - 2].  Source position of output frame t, in float32 with exactly these operations:
+ *           t <= c + d:  s = (float)(t c) / (float)(c + d)
+ *           otherwise:   s = (float)c + (float)((t - c - d) (T - 1 - c)) / (float)(T - 1 - c - d)
+ *         k = min((int)s, T - 2), fr = s - k, y[t][f] = (1 - fr) x[k][f] + fr x[k + 1][f] (float32: one subtraction, two products,
+ *         one sum; fr = 0 takes x[k] and fr = 1 takes x[k + 1] as they are).  Frames 0 and T - 1 map to themselves; d = 0 is the
+ *         identity.  W = 0: y = x.
+ *   fill value, per clip and per coefficient: KWS_FMASK_ZERO: 0; KWS_FMASK_MEAN: (sum over t ascending of y[t][f], float32) / (float)T
+ *         -- an MFCC's 0th coefficient is a large log-energy offset, for which zero is an outlier value.
+ *   time masks i < n_time:  w = aug_uniform(h_{3+2i}, max_time_width + 1), t0 = aug_uniform(h_{4+2i}, T - w + 1); the frames t0 <= t <
+ *         t0 + w take the fill value in every coefficient.
+ *   frequency masks j < n_freq:  w = aug_uniform(h_{11+2j}, max_freq_width + 1), f0 = aug_uniform(h_{12+2j}, F - w + 1); the
+ *         coefficients f0 <= f < f0 + w take the fill value in every frame.
+ * Masks may overlap; width 0 is a no-op.  Validation, evaluation, prediction and quantization never see this stage.
+ * ---------------------------------------------------------------------- */
+#define KWS_FMASK_MAX 4                /* time masks, and frequency masks, per clip */
+#define KWS_FMASK_ZERO 0
+#define KWS_FMASK_MEAN 1
+
+typedef struct kws_feature_mask_params {
+    float rate;              /* fraction of clips transformed, [0, 1] */
+    int32_t n_time;          /* time masks per clip, 0..KWS_FMASK_MAX */
+    int32_t max_time_width;  /* widths uniform in [0, max_time_width], 0..T */
+    int32_t n_freq;          /* frequency masks per clip, 0..KWS_FMASK_MAX */
+    int32_t max_freq_width;  /* widths uniform in [0, max_freq_width], 0..F */
+    int32_t max_warp;        /* W: 0 = no time warp, otherwise T >= 2 W + 3 */
+    int32_t fill;            /* KWS_FMASK_ZERO or KWS_FMASK_MEAN */
+    int32_t reserved;        /* 0 */
+    uint64_t seed;           /* seed_m */
+} kws_feature_mask_params;
+
+/* one clip's plan (84 bytes) */
+typedef struct kws_fmask_clip {
+    int32_t apply;           /* 1: transformed */
+    int32_t warp_center;     /* c; 0 = not warped */
+    int32_t warp_shift;      /* d */
+    int32_t n_time, n_freq;
+    int32_t t0[KWS_FMASK_MAX], tw[KWS_FMASK_MAX];   /* time masks: start, width */
+    int32_t f0[KWS_FMASK_MAX], fw[KWS_FMASK_MAX];   /* frequency masks: start, width */
+} kws_fmask_clip;
+
+/* HOST only (no GPU needed): the plan the kernel draws for the clip at global position `position`, made by the same __host__ __device__
+ * code.  Every field is drawn whether or not the clip is applied.  KWS_ERR_INVALID: rate outside [0, 1], a count outside
+ * [0, KWS_FMASK_MAX], max_time_width outside [0, T], max_freq_width outside [0, F], T < 2 W + 3 with W > 0 (or W < 0), an unknown fill. */
+int kws_feature_mask_draw(const kws_feature_mask_params *params, int T, int F, int64_t position, int64_t step, kws_fmask_clip *out);
+
+/* Transform B clips feat (B x T x F float32, contiguous) into out (the same layout; out == feat is allowed: a clip that is not applied
+ * then moves no bytes), one wave per clip, no atomics and no host synchronisation.  explicit_plan (HOST, B records, or NULL): the plans
+ * from the caller instead of the draws (apply in {0, 1}; counts in [0, KWS_FMASK_MAX]; every mask inside [0, T] or [0, F], whatever the
+ * params' maximum widths; warp_center = warp_shift = 0, or 1 <= c <= T - 2 and 1 <= c + d <= T - 2); they are copied into plan_out,
+ * which is required then.  plan_out (device, B records, or NULL): the plans that were applied.  B == 0 is KWS_OK without a launch; the
+ * parameter errors of kws_feature_mask_draw apply; T * F > kws_feature_mask_max_clip() is KWS_ERR_UNSUPPORTED and launches nothing.
+ * Fixed summation order: two calls give the same bits. */
+int kws_feature_mask(const kws_feature_mask_params *params, const float *feat, float *out, int B, int T, int F, int64_t position_base,
+                     int64_t step, const kws_fmask_clip *explicit_plan, kws_fmask_clip *plan_out, void *stream);
+
+/* the largest T * F kws_feature_mask takes: a clip and its F fill values stay in a wave's share of the LDS (5120; the default is 600) */
+int64_t kws_feature_mask_max_clip(void);
+
+/* ------------------------------------------------------------------------
  * Model: replaces the tf.keras objects built by classifier/model.py:14-46
  * get_model() (backbones classifier/models/cnn.py, rnn.py) and the work
  * Keras does inside model.fit / model.predict (train.py:75-92).

@@ -311,8 +311,10 @@ class KWSModel(object):
 
         Raw audio only: `sample_lengths` (N,) is the valid length of every row (a shorter clip keeps its head and is left-padded with zeros
         by the featurizer, as extract_features does); `augment` (kws_amd.augment.WaveAugment) mixes background noise into every training
-        clip, drawn afresh for every step (tools/audio_process/add_noise.py of the reference, done offline there).  Validation and
-        evaluate are never augmented."""
+        clip, drawn afresh for every step (tools/audio_process/add_noise.py of the reference, done offline there).  Features or raw
+        audio: `feature_mask` (kws_amd.augment.FeatureMask) is SpecAugment -- time warp, time masks, frequency masks -- of every
+        training batch's features, behind the featurizer or the gather and in front of the model, drawn for the same (step, position)
+        as `augment`; the dataset itself is never written.  Validation and evaluate are never augmented or masked."""
         import torch
         from kws_amd.parallel import DataParallel
         from kws_amd.pipeline import FeaturePipeline
@@ -322,6 +324,7 @@ class KWSModel(object):
         pipelined = bool(kwargs.pop("pipeline", True))
         augment = kwargs.pop("augment", None)
         sample_lengths = kwargs.pop("sample_lengths", None)
+        feature_mask = kwargs.pop("feature_mask", None)
         validate_averaged = bool(kwargs.pop("validate_averaged", False)) and self._averaging() is not None
         if dp.active:
             dp.broadcast_(dm.params)
@@ -392,7 +395,10 @@ class KWSModel(object):
                 if idx.numel() > 0:
                     if is_audio and in_place:
                         pipe.submit(wav=xd, valid_len=lens_d, index=idx, labels=yd, after=after, augment=augment, step=step0 + i + 1,
-                                    position_base=lo)
+                                    position_base=lo, feature_mask=feature_mask)
+                    elif feature_mask is not None:
+                        pipe.submit(index=idx, labels=yd, after=after, step=step0 + i + 1, position_base=lo, feature_mask=feature_mask,
+                                    **({"wav": xd} if is_audio else {"features": xd}))
                     elif is_audio:
                         pipe.submit(wav=xd, index=idx, labels=yd, after=after)
                     else:
@@ -418,6 +424,8 @@ class KWSModel(object):
                     else:
                         xb = xd.index_select(0, idx)
                         feat, yb = self._features_of(xb, is_audio), yd.index_select(0, idx)
+                    if pipe is None and feature_mask is not None:
+                        feat = feature_mask(feat, step=step0 + i + 1, position_base=lo, out=feat)    # the batch's own copy, never xd
                     kw = dict(dropout_seed=seed, ignore_index=ig, feat_moments=mom, stats_out=stats_all[i])
                     if more:
                         kw.update(overlap_event=overlap_ev, overlap_callback=lambda j=i + 1: submit(j, after=overlap_ev))

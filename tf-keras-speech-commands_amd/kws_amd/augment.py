@@ -1,5 +1,6 @@
 """Background-noise, room-reverberation, filter, speed and loudness augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*,
-kws_augment_*, kws_rir_bank_*, kws_reverb_apply, kws_filter_bank_*, kws_filter_apply, kws_resampler_*, kws_speed_apply).
+kws_augment_*, kws_rir_bank_*, kws_reverb_apply, kws_filter_bank_*, kws_filter_apply, kws_resampler_*, kws_speed_apply), and SpecAugment
+of the features behind them (kws_feature_mask: FeatureMask, at the end of this file).
 
 The reference makes training data robust offline: tools/audio_process/add_noise.py mixes a randomly chosen background recording into a
 `noised_rate` fraction of the clips at an SNR drawn from a list and writes one fixed *_noised.wav copy per clip.  Here the same mix is
@@ -805,6 +806,84 @@ def resample(wav, orig_sr, target_sr, resampler=None):
 def records(plan):
     """(B, 8) int32 plan tensor -> numpy CLIP_DTYPE records"""
     return np.ascontiguousarray(plan.cpu().numpy()).view(CLIP_DTYPE).reshape(-1)
+
+
+# the feature-mask draws use seed ^ FMASK_SEED_MIX, independent of every wave stage's draws of the same seed (include/kws.h)
+FMASK_SEED_MIX = 0xE7037ED1A0B428DB
+# one kws_fmask_clip record
+FMASK_DTYPE = np.dtype([("apply", "<i4"), ("warp_center", "<i4"), ("warp_shift", "<i4"), ("n_time", "<i4"), ("n_freq", "<i4"),
+                        ("t0", "<i4", (_l.FMASK_MAX,)), ("tw", "<i4", (_l.FMASK_MAX,)), ("f0", "<i4", (_l.FMASK_MAX,)),
+                        ("fw", "<i4", (_l.FMASK_MAX,))])
+
+
+def _count(name, value, hi=None):
+    n = int(value)
+    if n != value or n < 0 or (hi is not None and n > hi):
+        raise ValueError("%s must be an integer in [0, %s], got %r" % (name, "inf" if hi is None else hi, value))
+    return n
+
+
+class FeatureMask(object):
+    """SpecAugment of the features (include/kws.h: kws_feature_mask): a `rate` share of the clips of every step gets `time_masks` blocks
+    of up to `time_width` frames and `freq_masks` blocks of up to `freq_width` coefficients overwritten with the fill value ('mean': the
+    clip's own mean of that coefficient; 'zero'), after an optional time warp that moves one frame by up to `warp` frames and
+    interpolates the rest.  It works on features, so it applies to cached-feature training as well as behind the featurizer; draws are
+    counter-based, keyed by (seed, step) and indexed by the clip's position in the global batch.
+
+        model.fit(x, y, feature_mask=FeatureMask(time_masks=2, time_width=4, freq_masks=2, freq_width=3))"""
+
+    def __init__(self, time_masks=2, time_width=4, freq_masks=2, freq_width=3, warp=0, rate=1.0, fill='mean', seed=0):
+        self.time_masks, self.freq_masks = _count("time_masks", time_masks, _l.FMASK_MAX), _count("freq_masks", freq_masks, _l.FMASK_MAX)
+        self.time_width, self.freq_width, self.warp = _count("time_width", time_width), _count("freq_width", freq_width), _count("warp", warp)
+        self.rate = _rate("rate", rate)
+        if fill not in _l.FMASK_FILL:
+            raise ValueError("fill must be one of %s, got %r" % (", ".join(sorted(_l.FMASK_FILL)), fill))
+        self.fill = fill
+        self.seed = int(np.random.randint(0, 2 ** 62) if seed is None else seed) & (2 ** 64 - 1)
+
+    @property
+    def mask_seed(self):
+        return self.seed ^ FMASK_SEED_MIX
+
+    def params(self):
+        p = _l.KwsFeatureMaskParams()
+        p.rate, p.n_time, p.max_time_width, p.n_freq, p.max_freq_width = self.rate, self.time_masks, self.time_width, self.freq_masks, self.freq_width
+        p.max_warp, p.fill, p.reserved, p.seed = self.warp, _l.FMASK_FILL[self.fill], 0, self.mask_seed
+        return p
+
+    def draw(self, T, F, position, step):
+        """-> one FMASK_DTYPE record: the plan of the clip at global batch position `position` in step `step` (host only, no GPU)"""
+        rec = _l.KwsFmaskClip()
+        _l.check(_l.get_lib().kws_feature_mask_draw(ctypes.byref(self.params()), int(T), int(F), int(position), int(step), ctypes.byref(rec)))
+        return np.frombuffer(bytes(rec), FMASK_DTYPE)[0]
+
+    def __call__(self, feat, step, position_base=0, out=None, plan=None, return_plan=False):
+        """-> out (or (out, plan tensor) with return_plan): the clips feat (B, T, F) float32 CUDA, each transformed by the plan drawn for
+        (seed, step) at global position position_base + b, on the current stream.  out: None (a new tensor), feat itself (in place) or a
+        contiguous float32 CUDA tensor of feat's shape.  plan: B FMASK_DTYPE records from the caller instead of the draws.  The plan
+        tensor is (B, 21) int32 (mask_records() reads it)."""
+        torch = _torch()
+        if not feat.is_cuda or feat.dim() != 3 or not feat.is_contiguous() or feat.dtype != torch.float32:
+            raise ValueError("feat must be a contiguous float32 CUDA tensor of shape (clips, n_features, feature_size)")
+        B, T, F = feat.shape
+        if out is None:
+            out = torch.empty_like(feat)
+        elif out.shape != feat.shape or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s" % (tuple(feat.shape),))
+        ex = _explicit(plan, FMASK_DTYPE, B, "plan", "records", flat=False)
+        plan_t = None
+        if ex is not None or return_plan:
+            plan_t = torch.empty((B, FMASK_DTYPE.itemsize // 4), dtype=torch.int32, device=feat.device)
+        _l.check(_l.get_lib().kws_feature_mask(ctypes.byref(self.params()), feat.data_ptr(), out.data_ptr(), B, T, F, int(position_base),
+                                               int(step), _host_ptr(ex), _ptr(plan_t), torch.cuda.current_stream().cuda_stream))
+        if ex is not None:
+            torch.cuda.current_stream().synchronize()       # the host records are copied from pageable memory
+        return (out, plan_t) if return_plan else out
+
+
+def mask_records(plan):
+    """(B, 21) int32 plan tensor of FeatureMask.__call__ -> numpy FMASK_DTYPE records"""
+    return np.ascontiguousarray(plan.cpu().numpy()).view(FMASK_DTYPE).reshape(-1)
 
 
 def white_noise(length_ms=1000, sample_rate=16000, amplitude=0.7, seed=None):

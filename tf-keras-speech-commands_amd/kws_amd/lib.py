@@ -99,6 +99,22 @@ class KwsSpeedParams(ctypes.Structure):
                 ("max_samples", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
 
 
+FMASK_MAX = 4
+FMASK_FILL = {"zero": 0, "mean": 1}                                                      # include/kws.h KWS_FMASK_*
+
+
+class KwsFeatureMaskParams(ctypes.Structure):
+    _fields_ = [("rate", ctypes.c_float), ("n_time", ctypes.c_int32), ("max_time_width", ctypes.c_int32), ("n_freq", ctypes.c_int32),
+                ("max_freq_width", ctypes.c_int32), ("max_warp", ctypes.c_int32), ("fill", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("seed", ctypes.c_uint64)]
+
+
+class KwsFmaskClip(ctypes.Structure):
+    _fields_ = [("apply", ctypes.c_int32), ("warp_center", ctypes.c_int32), ("warp_shift", ctypes.c_int32), ("n_time", ctypes.c_int32),
+                ("n_freq", ctypes.c_int32), ("t0", ctypes.c_int32 * FMASK_MAX), ("tw", ctypes.c_int32 * FMASK_MAX),
+                ("f0", ctypes.c_int32 * FMASK_MAX), ("fw", ctypes.c_int32 * FMASK_MAX)]
+
+
 QUANT_TENSORS = 6
 QUANT_MAX_CLASSES = 48
 QUANT_MAX, QUANT_RELU6, QUANT_KL = 0, 1, 2
@@ -294,6 +310,9 @@ def get_lib():
     L.kws_resampler_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(f64), ctypes.POINTER(f64)]
     L.kws_resampler_table.argtypes = [vp, vp, ctypes.c_size_t]
     L.kws_speed_apply.argtypes = [vp, ctypes.POINTER(KwsSpeedParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.kws_feature_mask_draw.argtypes = [ctypes.POINTER(KwsFeatureMaskParams), i32, i32, i64, i64, ctypes.POINTER(KwsFmaskClip)]
+    L.kws_feature_mask.argtypes = [ctypes.POINTER(KwsFeatureMaskParams), vp, vp, i32, i32, i32, i64, i64, vp, vp, vp]
+    L.kws_feature_mask_max_clip.restype = i64
     L.kws_model_calibrate.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp]
     L.kws_quantize_simple_cnn.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(KwsQSimpleCnn)]
     L.kws_qmodel_create.argtypes = [vp, ctypes.POINTER(KwsQSimpleCnn), ctypes.POINTER(vp)]

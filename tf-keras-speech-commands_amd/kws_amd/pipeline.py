@@ -41,7 +41,8 @@ class FeaturePipeline(object):
         # labels=True: submit(labels=..., index=...) also gathers the batch's labels; take() then returns them as the last element
         self.lab_bufs = [torch.empty((batch,), dtype=torch.int32, device=device) for _ in range(2)] if labels else None
 
-    def submit(self, wav=None, valid_len=None, after=None, index=None, features=None, labels=None, augment=None, step=0, position_base=0):
+    def submit(self, wav=None, valid_len=None, after=None, index=None, features=None, labels=None, augment=None, step=0, position_base=0,
+               feature_mask=None):
         """Enqueue the preparation of one batch on the side stream (returns at once).  Source: `wav` (rows, samples) raw audio,
         featurized here, or `features` (rows, n_features, feature_size); `index` (CUDA int32) picks the batch's rows from either
         (default: every row); `labels` (rows,) int32 are gathered with the same index.  `after`: an event on the main stream to
@@ -49,7 +50,9 @@ class FeaturePipeline(object):
         of the step that a sweep found best for this -- for simple_cnn behind conv3's forward kernel (round 3's sweep),
         include/kws.h); call submit from train_fwd_bwd's overlap_callback so that the launch also sits there in host order;
         default: everything enqueued so far.  augment / step / position_base: background-noise augmentation of raw audio
-        (Featurizer.__call__)."""
+        (Featurizer.__call__).  feature_mask (kws_amd.augment.FeatureMask, with wav= or features=): SpecAugment of the batch, in place
+        on the pipeline's own buffer with the same step / position_base, behind the features and in front of the moments, which then
+        describe what the model sees; the source tensor is never written."""
         torch = _torch()
         if augment is not None and features is not None:
             raise ValueError("augment needs raw audio (wav=...), not features")
@@ -74,6 +77,8 @@ class FeaturePipeline(object):
                 torch.index_select(features.reshape(features.shape[0], out.shape[1], out.shape[2]), 0, index, out=out)
             else:
                 out.copy_(features.reshape(out.shape))
+            if feature_mask is not None and n > 0:
+                feature_mask(out, step=step, position_base=position_base, out=out)
             if labels is not None:
                 if self.lab_bufs is None:
                     raise ValueError("the pipeline was built without label buffers")

@@ -15,6 +15,8 @@ that share of the training clips at zero phase with a Butterworth design drawn f
 --speed_range LO,HI plays a --speed_rate share of the training clips at a ratio drawn from the range (tempo and pitch together) and
 --loudness_range LO_DB,HI_DB sets a --loudness_rate share to a level drawn from the range (dBFS), before every other stage, as
 tools/audio_process/audio_convert.py resamples and levels files offline.
+--time_mask N,W / --freq_mask N,W / --time_warp W are SpecAugment of the features (--mask_rate, --mask_fill), drawn per clip and per
+step behind the featurizer or the cached features: they work with and without --raw_audio.
 The optimizer takes the Keras options the reference's command line leaves at their defaults: --clipnorm, --global_clipnorm and
 --clipvalue (any optimizer), --momentum (sgd, rmsprop), --nesterov (sgd), --centered (rmsprop) and --amsgrad (adam).
 --average_type wraps the optimizer as the reference's get_averaged_optimizer does: ema and swa keep an average of the weights on the
@@ -67,6 +69,7 @@ def main(argv=None):
     if args.loudness_rate is not None and args.loudness_range is None:
         raise SystemExit('--loudness_rate needs --loudness_range')
     perturb = perturb_options(args)
+    mask = mask_options(args)
     opt_options = optimizer_options(args)
 
     # callbacks for training process
@@ -126,6 +129,12 @@ def main(argv=None):
         from kws_amd.augment import WaveAugment
         augment = WaveAugment(None, rirs=rirs, reverb_rate=reverb_rate, filters=filters, filter_rate=filter_rate, **perturb)
 
+    # SpecAugment of the features: with cached features as well as with --raw_audio
+    feature_mask = None
+    if mask:
+        from kws_amd.augment import FeatureMask
+        feature_mask = FeatureMask(**mask)
+
     # prepare optimizer
     if args.decay_type:
         callbacks.remove(reduce_lr)
@@ -157,6 +166,8 @@ def main(argv=None):
     fit_kw = dict(sample_lengths=len_train, augment=augment) if args.raw_audio else {}
     if averaged:
         fit_kw['validate_averaged'] = True
+    if feature_mask is not None:
+        fit_kw['feature_mask'] = feature_mask
     history = model.fit(x_train, y_train, batch_size=args.batch_size, epochs=args.epochs, validation_data=(x_val, y_val),
                         validation_freq=1, callbacks=callbacks, shuffle=True, verbose=1, **fit_kw)
 
@@ -209,6 +220,43 @@ def perturb_options(args):
     for flag in ('speed_rate', 'loudness_rate'):
         if flag in kw and not 0.0 <= kw[flag] <= 1.0:
             raise SystemExit('--%s must be in 0.0~1.0, got %r' % (flag, kw[flag]))
+    return kw
+
+
+def parse_mask(flag, text):
+    """'N,W' -> (N, W): N masks of up to W frames or coefficients"""
+    try:
+        n, w = (int(x) for x in text.split(','))
+    except ValueError:
+        raise SystemExit('--%s needs two integers N,W, got %r' % (flag, text))
+    if not 0 <= n <= 4 or w < 0:
+        raise SystemExit('--%s needs 0 <= N <= 4 masks of width W >= 0, got %r' % (flag, text))
+    return n, w
+
+
+def mask_options(args):
+    """keyword arguments of FeatureMask for the SpecAugment flags given on the command line (none: no such stage, and no object); a
+    kind of mask that is not asked for is off"""
+    if args.time_mask is None and args.freq_mask is None and args.time_warp is None:
+        for flag in ('mask_rate', 'mask_fill'):
+            if getattr(args, flag) is not None:
+                raise SystemExit('--%s needs --time_mask, --freq_mask or --time_warp' % flag)
+        return {}
+    kw = dict(time_masks=0, time_width=0, freq_masks=0, freq_width=0, warp=0, rate=1.0, fill='mean')
+    if args.time_mask is not None:
+        kw['time_masks'], kw['time_width'] = parse_mask('time_mask', args.time_mask)
+    if args.freq_mask is not None:
+        kw['freq_masks'], kw['freq_width'] = parse_mask('freq_mask', args.freq_mask)
+    if args.time_warp is not None:
+        if args.time_warp < 0:
+            raise SystemExit('--time_warp needs W >= 0 frames, got %r' % args.time_warp)
+        kw['warp'] = args.time_warp
+    if args.mask_rate is not None:
+        if not 0.0 <= args.mask_rate <= 1.0:
+            raise SystemExit('--mask_rate must be in 0.0~1.0, got %r' % args.mask_rate)
+        kw['rate'] = args.mask_rate
+    if args.mask_fill is not None:
+        kw['fill'] = args.mask_fill
     return kw
 
 
@@ -301,6 +349,17 @@ def parse_args(argv=None):
                         help="LO_DB,HI_DB: set the training clips to a random loudness in this range in dBFS, -80~0, written --loudness_range -30,-15 or --loudness_range=-30,-15 (needs --raw_audio). default: off")
     parser.add_argument('--loudness_rate', type=float, required=False, default=None,
                         help="random percentage rate of setting the loudness of the training clips (0.0~1.0). default=1.0")
+    # SpecAugment of the features (time warp, time masks, frequency masks; drawn per clip and per step, with or without --raw_audio)
+    parser.add_argument('--time_mask', type=str, required=False, default=None,
+                        help="N,W: overwrite N blocks of up to W frames of every training clip's features (N <= 4). default: off")
+    parser.add_argument('--freq_mask', type=str, required=False, default=None,
+                        help="N,W: overwrite N blocks of up to W coefficients of every training clip's features (N <= 4). default: off")
+    parser.add_argument('--time_warp', type=int, required=False, default=None,
+                        help="W: move one random frame of every training clip by up to W frames and interpolate the rest. default: off")
+    parser.add_argument('--mask_rate', type=float, required=False, default=None,
+                        help="random percentage rate of masking / warping the training clips (0.0~1.0). default=1.0")
+    parser.add_argument('--mask_fill', type=str, required=False, default=None, choices=['zero', 'mean'],
+                        help="what a masked entry becomes: zero, or the clip's own mean of that coefficient. default=mean")
     # "--loudness_range -30,-15": argparse takes a value that starts with '-' and is no plain number for an option, so bind it with '='
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 2, -1, -1):

@@ -4,10 +4,12 @@ import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tf-keras-speech-commands_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kws_amd.lib as L
 lib = sys.argv[1]
 if lib != "-":
-    L.LIB_PATH = os.path.abspath(lib)
+    import foreign_lib
+    foreign_lib.use(lib)
 sys.argv = ["bench.py"] + sys.argv[2:]
 import json, io, contextlib
 import bench
