@@ -37,6 +37,25 @@ int check(const kws_model *m, int B, bool training, void *ws, size_t ws_bytes, G
     return KWS_OK;
 }
 
+constexpr size_t kRnnMaxSmem = 160 * 1024;      // the most dynamic LDS a workgroup can opt in to
+
+const char *rnn_name(const kws_model *m) { return m->kind == KWS_SIMPLE_LSTM ? "LSTM" : "GRU"; }
+
+// Both kernels keep a 16-clip feature tile in LDS, and the backward tile is the larger one: a geometry whose forward kernel fits and
+// whose backward kernel does not must be refused BEFORE anything is launched, recorded or called back -- the forward kernel clears the
+// caller's gradient buffer.
+int check_tiles(const kws_model *m, bool training)
+{
+    const size_t fwd = gru_fwd_smem(m->n_features, m->feature_size), bwd = gru_bwd_smem(m->n_features, m->feature_size);
+    if (fwd > kRnnMaxSmem)
+        return fail(KWS_ERR_UNSUPPORTED, "%s forward tile of %d x %d needs %zu B of LDS (limit %zu)", rnn_name(m), m->n_features,
+                    m->feature_size, fwd, kRnnMaxSmem);
+    if (training && bwd > kRnnMaxSmem)
+        return fail(KWS_ERR_UNSUPPORTED, "%s backward tile of %d x %d needs %zu B of LDS (limit %zu)", rnn_name(m), m->n_features,
+                    m->feature_size, bwd, kRnnMaxSmem);
+    return KWS_OK;
+}
+
 template <int KX>
 int launch_fwd(const kws_model *m, const float *feat, int B, const float *params, GruWs &w, bool save, float rate, uint64_t seed,
                hipStream_t s, float *zero_buf, long zero_n)
@@ -44,7 +63,7 @@ int launch_fwd(const kws_model *m, const float *feat, int B, const float *params
     const int T = m->n_features, F = m->feature_size;
     const size_t smem = gru_fwd_smem(T, F);
     const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    if (smem > 160 * 1024) return fail(KWS_ERR_UNSUPPORTED, "GRU tile needs %zu B of LDS", smem);
+    if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
     if (m->kind == KWS_SIMPLE_LSTM) {
         if (save) {
             if (smem > 64 * 1024)
@@ -86,7 +105,7 @@ int launch_bwd(const kws_model *m, const float *feat, int B, const float *params
     const int T = m->n_features, F = m->feature_size;
     const size_t smem = gru_bwd_smem(T, F);
     const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    if (smem > 160 * 1024) return fail(KWS_ERR_UNSUPPORTED, "GRU tile needs %zu B of LDS", smem);
+    if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
     if (m->kind == KWS_SIMPLE_LSTM) {
         if (smem > 64 * 1024)
             KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_bwd_kernel<KX>),
@@ -133,6 +152,8 @@ int gru_forward(kws_model *m, const float *feat, int B, const float *params, voi
     GruWs w;
     int rc = check(m, B, false, ws, ws_bytes, w);
     if (rc) return rc;
+    rc = check_tiles(m, false);
+    if (rc) return rc;
     rc = dispatch_fwd(m, feat, B, params, w, false, 0.f, 0, s);
     if (rc) return rc;
     return run_head(m, B, params, w.h_last, w.loss_i, w.correct_i, nullptr, nullptr, probs, argmax, nullptr, 0.f, nullptr, 0, s);
@@ -142,6 +163,8 @@ int gru_train_fwd_bwd(kws_model *m, const kws_train_args *a, hipStream_t s)
 {
     GruWs w;
     int rc = check(m, a->B, true, a->ws, a->ws_bytes, w);
+    if (rc) return rc;
+    rc = check_tiles(m, true);
     if (rc) return rc;
     const float rate = a->dropout_seed != 0 ? 0.2f : 0.f;          // GRU / LSTM(dropout=0.2): input dropout, rnn.py:34-35,70-71
     if (head_bwd_fuses(m)) {
