@@ -361,6 +361,79 @@ int kws_speed_apply(const kws_resampler *rs, const kws_speed_params *params, con
                     void *stream);
 
 /* ------------------------------------------------------------------------
+ * Tempo and pitch perturbation of raw audio by a phase vocoder: tempo without pitch, pitch without tempo, or both, where the speed
+ * change above moves them together.  The reference has no counterpart; this comment is the definition (tests/pitch_ref.py restates it in
+ * float64 numpy).  Clip b sits at global batch position p = position_base + b; its source v is row index[b] of wav (int16 scaled by
+ * 1/32768), Ls = valid_len[row] or stride, NOT clipped to max_samples, as in the speed stage.
+ * Draws: h_f = aug_hash(seed, step, 4 p + f) (kws_amd passes seed_p = WaveAugment seed ^ 0x8EBC6AF09C88C6E3, so the draws of every
+ * other stage are unchanged), u_f = (h_f >> 8) * 2^-24:
+ *   f = 0: stretched = u_0 < tempo_rate;  f = 1: tempo = fmaf(u_1, tempo_hi - tempo_lo, tempo_lo)      (float32, 0.5 .. 2)
+ *   f = 2: pitched   = u_2 < pitch_rate;  f = 3: n = fmaf(u_3, pitch_hi - pitch_lo, pitch_lo) semitones (float32, -12 .. 12)
+ *   r = (float)exp2((double)n / 12), 1 for a clip that is not pitched; rho = (double)tempo / (double)r, tempo 1 when not stretched.
+ *   A clip neither stretched nor pitched: L' = min(Ls, max_samples), y = v (bit for bit after the f32 conversion), tempo_used = 0,
+ *   pitch_used = NaN.  Every other clip:
+ * Analysis.  N = n_fft in {256, 512, 1024}, H = N / 4, w[i] = 0.5 - 0.5 cos(2 pi i / N) (periodic Hann; float32, evaluated as
+ *   sinpif(i / N)^2, which keeps its relative precision at the window's ends).  The source, N / 2 zeros in front of it and zeros behind
+ *   it, is cut into the frames m = 0 .. M - 1, M = 1 + floor(Ls / H): x_m[i] = w[i] v[m H + i - N / 2].  D[m][k], k = 0 .. N / 2, is the
+ *   real FFT of x_m in float32 (bins 0 and N / 2 have imaginary part +0); D[m] = 0 for m >= M.
+ * Vocoder.  J = ceil(M / rho) output frames.  For frame j: t_j = j rho (float64, contraction off), m0 = floor(t_j), alpha = t_j - m0;
+ *   mag = (1 - alpha) |D[m0]| + alpha |D[m0 + 1]|; ang(z) = atan2f(im, re), and 0 when re == 0 and im == 0 (signed zeros decide no
+ *   phase); delta_j = ang(D[m0 + 1]) - ang(D[m0]) - (pi / 2) k, wrapped into [-pi, pi] by subtracting 2 pi rint(delta / 2 pi);
+ *   Phi_j = ang(D[0]) + sum_{i < j} delta_i, accumulated in frame order (float32; only exp(i Phi) is used, and the device keeps Phi
+ *   itself wrapped into [-pi, pi] so that its rounding does not grow with j; (pi / 2) k is taken off as (pi / 2)(k mod 4));
+ *   Y_j[k] = mag i^((j k) mod 4) exp(i Phi_j).  With H = N / 4 the nominal advance 2 pi k H / N is a quarter turn per bin index: it is
+ *   applied as an exact power of i and never enters the accumulator.
+ * Synthesis.  y_j = the inverse real FFT of Y_j (the imaginary parts of bins 0 and N / 2 do not count) times w, overlap-added at hop H
+ *   in frame order; every sample is divided by the sum of w^2 over the frames j < J that cover it where that sum is > 1e-8; the leading
+ *   N / 2 samples are dropped; the stretched signal has Lst = floor(Ls / rho + 0.5) samples.
+ * Pitch.  r != 1: the stretched signal is played r times faster by exactly kws_speed_apply's interpolation (the same table, the same
+ *   order of operations), L' = min(ceil(Lst / r), max_samples); r == 1: L' = min(Lst, max_samples).  Only the frames and stretched
+ *   samples that the L' outputs read are computed.
+ * This stage runs first: speed and loudness, reverb, filter and noise then run unchanged on (out, lengths) with index = NULL and the
+ * same position_base, so the loudness levels the final signal.  Divergences from the usual tools (librosa's phase_vocoder /
+ * pitch_shift, sox): the plain vocoder, with no phase locking and no transient handling, so a stretched transient smears over a
+ * window; bins below the rounding floor carry arbitrary phases (an exact zero: phase 0); the Kaiser-windowed sinc table instead of a
+ * polyphase resampler; only max_samples outputs are made; fresh draws every step.
+ * ---------------------------------------------------------------------- */
+typedef struct kws_pitch_params {
+    float tempo_rate;      /* fraction of clips stretched, [0, 1]; 0 switches the tempo half off */
+    float tempo_lo, tempo_hi;     /* tempo uniform in [lo, hi], 0.5 <= lo <= hi <= 2 (checked when tempo_rate > 0) */
+    float pitch_rate;      /* fraction of clips pitched, [0, 1]; 0 switches the pitch half off */
+    float pitch_lo, pitch_hi;     /* semitones uniform in [lo, hi], -12 <= lo <= hi <= 12 (checked when pitch_rate > 0) */
+    int32_t n_fft;         /* 256, 512 or 1024 */
+    int32_t max_samples;   /* the head the featurizer keeps, 1 .. 2^20 */
+    int32_t reserved;      /* 0 */
+    uint64_t seed;         /* seed_p */
+} kws_pitch_params;
+
+/* host only (no device needed): the bytes with which kws_pitch_apply works on at least tile_clips clips at a time: per clip the spectrum
+ * of the frames and the stretched samples that max_samples outputs can need at the ends of the ranges, rho = 4 and r = 2 (2.2 MB at n_fft
+ * 512 and max_samples 16000; a 1 s clip at rho = 1 touches 260 KB of it).  kws_pitch_apply walks a batch in tiles of as many clips as
+ * its workspace holds at the largest rho and r of that call (its ranges' ends, or its explicit values'), which is more than tile_clips
+ * for narrower ranges. */
+int kws_pitch_workspace_bytes(int n_fft, int max_samples, int tile_clips, size_t *bytes);
+
+/* The analysis alone (a spectrogram): out (device, B x frames x (n_fft / 2 + 1) complex float32, re and im interleaved) = D[m][k] of the
+ * B clips wav[index[b]] (index, valid_len as above), rows m >= M of a clip zeros.  frames >= 1; 1 + floor(stride / (n_fft / 4)) holds
+ * every frame of every clip.  kws_pitch_apply's analysis is this one, bit for bit. */
+int kws_pitch_stft(const void *wav, int wav_dtype, const int32_t *index, int B, int64_t stride, const int32_t *valid_len, int n_fft,
+                   float *out, int frames, void *stream);
+
+/* Perturb B clips, no atomics and no host synchronisation (the explicit arrays are copied from the host first).  out: B x out_stride
+ * float32 (out_stride >= max_samples; never wav itself), row b = y[0:L'] then zeros; lengths (device int32 B, required) = L';
+ * tempo_used (device float32 B, may be NULL unless explicit_tempo is given: the values are staged there) = tempo, or 0 for a clip that
+ * was not stretched; pitch_used (device float32 B, may be NULL unless explicit_semitones is given) = n, or NaN for a clip that was not
+ * pitched.  explicit_tempo (HOST float32 B, or NULL): tempo from the caller, 0 = not stretched, other values in [0.5, 2].
+ * explicit_semitones (HOST float32 B, or NULL): n from the caller in [-12, 12], NaN = not pitched.  rs may be NULL when no clip can be
+ * pitched, workspace when no clip can be stretched or pitched either.  workspace (device, workspace_bytes >= the bytes of one clip:
+ * KWS_ERR_WORKSPACE below) is free again when the call's work on `stream` is done.  Fixed order of every sum: two calls give the same
+ * bits, whatever the tile. */
+int kws_pitch_apply(const kws_resampler *rs, const kws_pitch_params *params, const void *wav, int wav_dtype, const int32_t *index, int B,
+                    int64_t stride, const int32_t *valid_len, int64_t position_base, int64_t step, const float *explicit_tempo,
+                    const float *explicit_semitones, float *out, int64_t out_stride, int32_t *lengths, float *tempo_used,
+                    float *pitch_used, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * SpecAugment of the FEATURES (time warp, time masks, frequency masks): the one augmentation stage behind the featurizer (or behind the
  * gather of cached features) and in front of the model.  The reference has no counterpart; this comment is the definition.  Clip b sits
  * at global batch position p = position_base + b; its features are x[T][F], T = n_features frames of F = feature_size coefficients.

@@ -4,7 +4,7 @@
 // One 256-thread block per clip.  A resampled clip's block copies the table (Z P + 1 floats, 32 KiB at the default geometry) into LDS;
 // thread i then makes the outputs n = i, i + 256, ...: neighbouring outputs read overlapping source windows, so a wave's source loads
 // fall into a few cache lines and the source stays in global memory.  The phase arithmetic (t = n r, pos = ((phi + k) s) P, its floor
-// and its fraction) is fp64 with contraction off, so that the table index and the last tap of a wing are the ones the float64
+// and its fraction; kws_resample.h, shared with kws_pitch.hip) is fp64 with contraction off, so that the table index and the last tap of a wing are the ones the float64
 // restatement of the tests takes; weights, products and sums are fp32 in a fixed order (left wing, right wing, k ascending).
 // The level needs the mean square of the whole output before it can scale: every thread sums the squares of its own outputs in fp64,
 // the block adds them in a fixed order (butterfly within a wave, waves in order), and every thread then scales the outputs it wrote
@@ -12,46 +12,17 @@
 #include <cfloat>
 #include <climits>
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <vector>
 
 #include "kws_common.h"
 #include "kws_wave_stage.h"
 #include "kws_device.h"
-
-struct kws_resampler {
-    int Z = 0, P = 0;
-    double beta = 0.0, rolloff = 0.0;
-    std::vector<float> table;            // h[0 .. Z P]
-    std::mutex mu;
-    std::map<int, float *> dev;          // device id -> the table's copy there (made by the first kws_speed_apply on that device)
-};
+#include "kws_resample.h"
 
 namespace kws {
 namespace spd {
 
 constexpr int kThreads = 256, kWaves = kThreads / 64;
-constexpr size_t kMaxTableBytes = 64 * 1024;
 enum { kSpdApply = 0, kSpdRatio = 1, kSpdLevel = 2, kSpdTarget = 3, kSpdFields = 4 };   // draw fields: aug_hash(seed_s, step, 4 p + f)
-
-// one wing of output n: taps at v[j], j = j0, j0 + dj, ... while 0 <= j < Ls and pos = ((x0 + k) s) P < Z P
-template <typename WavT>
-__device__ __forceinline__ float wing(const WavT *__restrict__ v, const float *h, int j0, int dj, int Ls, double x0, double s, double dP,
-                                      double lim, float acc)
-{
-#pragma clang fp contract(off)
-    double k = 0.0;
-    for (int j = j0; j >= 0 && j < Ls; j += dj, k += 1.0) {
-        const double pos = ((x0 + k) * s) * dP;
-        if (!(pos < lim)) break;
-        const int i = (int)pos;
-        const float eta = (float)(pos - (double)i);
-        const float h0 = h[i], h1 = h[i + 1];
-        acc = __fmaf_rn(__fmaf_rn(eta, h1 - h0, h0), aug_to_f32(v[j]), acc);
-    }
-    return acc;
-}
 
 template <typename WavT>
 __global__ __launch_bounds__(kThreads) void speed_apply_kernel(const WavT *__restrict__ wav, int64_t stride, const int32_t *__restrict__ index,
@@ -108,11 +79,7 @@ __global__ __launch_bounds__(kThreads) void speed_apply_kernel(const WavT *__res
         const double s = rd > 1.0 ? 1.0 / rd : 1.0, dP = (double)P, lim = (double)(Z * P);
         const float sf = (float)s;
         for (int n = tid; n < lo; n += kThreads) {
-            const double t = (double)n * rd, f0 = floor(t), phi = t - f0;   // n r is exact: 15 x 24 bits
-            const int n0 = (int)f0;
-            float acc = wing(v, h, n0, -1, Ls, phi, s, dP, lim, 0.f);
-            acc = wing(v, h, n0 + 1, 1, Ls, 1.0 - phi, s, dP, lim, acc);
-            const float y = sf * acc;
+            const float y = resample_at(v, h, n, Ls, rd, s, sf, dP, lim);
             dst[n] = y;
             sq += (double)y * (double)y;
         }

@@ -1,6 +1,6 @@
-"""Background-noise, room-reverberation, filter, speed and loudness augmentation of raw audio on the GPU (include/kws.h: kws_noise_bank_*,
-kws_augment_*, kws_rir_bank_*, kws_reverb_apply, kws_filter_bank_*, kws_filter_apply, kws_resampler_*, kws_speed_apply), and SpecAugment
-of the features behind them (kws_feature_mask: FeatureMask, at the end of this file).
+"""Background-noise, room-reverberation, filter, speed, loudness, tempo and pitch augmentation of raw audio on the GPU (include/kws.h:
+kws_noise_bank_*, kws_augment_*, kws_rir_bank_*, kws_reverb_apply, kws_filter_bank_*, kws_filter_apply, kws_resampler_*, kws_speed_apply,
+kws_pitch_*), and SpecAugment of the features behind them (kws_feature_mask: FeatureMask, at the end of this file).
 
 The reference makes training data robust offline: tools/audio_process/add_noise.py mixes a randomly chosen background recording into a
 `noised_rate` fraction of the clips at an SNR drawn from a list and writes one fixed *_noised.wav copy per clip.  Here the same mix is
@@ -31,6 +31,14 @@ band-limited interpolation with the Kaiser-windowed sinc table of a Resampler), 
     aug = WaveAugment(noise, speed=(0.9, 1.1), loudness=(-30, -15), seed=1)                 # noise may be None
 
 resample(wav, orig_sr, target_sr) is the tool's file-conversion use of the same kernel at one fixed ratio.
+
+The reference has no tool that changes a clip's tempo without its pitch or its pitch without its tempo.  Here a `tempo_rate` share of
+the clips of every step is stretched in time at a tempo drawn from `tempo` and a `pitch_rate` share is shifted by a number of semitones
+drawn from `pitch`, by a phase vocoder (and, for the pitch, the Resampler's interpolation behind it), before every other stage:
+
+    aug = WaveAugment(noise, tempo=(0.85, 1.2), pitch=(-2, 2), seed=1)                      # noise may be None
+
+time_stretch(wav, rate), pitch_shift(wav, n_steps) and stft(wav, n_fft) are the one-shot uses of the same kernels.
 
 Argument checks run on the host; the device copy of a bank is made on first use."""
 import ctypes
@@ -572,6 +580,18 @@ def _range(name, value, lo, hi, unit=""):
     return a, b
 
 
+# the tempo / pitch draws use seed ^ PITCH_SEED_MIX, independent of every other stage's draws of the same seed (include/kws.h)
+PITCH_SEED_MIX = 0x8EBC6AF09C88C6E3
+PITCH_TILE_CLIPS = 256            # clips the vocoder's workspace holds at a time by default
+
+
+def pitch_workspace_bytes(n_fft, max_samples, tile_clips):
+    """bytes of a vocoder workspace for tile_clips clips at a time (host only, no GPU)"""
+    n = ctypes.c_size_t(0)
+    _l.check(_l.get_lib().kws_pitch_workspace_bytes(int(n_fft), int(max_samples), int(tile_clips), ctypes.byref(n)))
+    return n.value
+
+
 class WaveAugment(object):
     """Per-clip background noise (add_noise.py:19-35) at an SNR drawn from `snr` for a `noised_rate` fraction of the clips, and an
     optional time shift of up to +-time_shift_ms (off by default; the reference has none).  With `rirs` (a RirBank, or anything RirBank
@@ -580,20 +600,30 @@ class WaveAugment(object):
     `filter_rate` fraction of the clips is then filtered at zero phase with a design drawn from the bank (wav_filter.py), energy kept
     likewise.  With `speed` = (low, high) a `speed_rate` fraction of the clips is first of all played at a ratio drawn uniformly from
     it (0.5..2; `resampler`: the interpolation table, default Resampler()), and with `loudness` = (low_db, high_db) a `loudness_rate`
-    fraction is set to a level drawn uniformly from it (dBFS, -80..0), as audio_convert.py does offline.  Draws are counter-based,
-    keyed by (seed, step) and indexed by the clip's position in the global batch."""
+    fraction is set to a level drawn uniformly from it (dBFS, -80..0), as audio_convert.py does offline.  With `tempo` = (low, high) a
+    `tempo_rate` fraction of the clips is, before all of that, stretched in time at a tempo drawn uniformly from it (0.5..2, pitch
+    unchanged), and with `pitch` = (low, high) a `pitch_rate` fraction is shifted by a number of semitones drawn uniformly from it
+    (-12..12, duration unchanged), by a phase vocoder of `pitch_n_fft` points (256, 512 or 1024; the pitch also uses `resampler`).
+    Draws are counter-based, keyed by (seed, step) and indexed by the clip's position in the global batch."""
 
     def __init__(self, noise, snr=(50,), noised_rate=1.0, time_shift_ms=0, seed=None, sample_rate=None, rirs=None, reverb_rate=1.0,
-                 rescale=True, filters=None, filter_rate=1.0, speed=None, speed_rate=1.0, loudness=None, loudness_rate=1.0, resampler=None):
+                 rescale=True, filters=None, filter_rate=1.0, speed=None, speed_rate=1.0, loudness=None, loudness_rate=1.0, resampler=None,
+                 tempo=None, tempo_rate=1.0, pitch=None, pitch_rate=1.0, pitch_n_fft=512):
         from classifier.params import pr
-        if noise is None and rirs is None and filters is None and speed is None and loudness is None:
+        if noise is None and rirs is None and filters is None and speed is None and loudness is None and tempo is None and pitch is None:
             raise ValueError("WaveAugment needs a noise bank, a RIR bank or both")
         srate, lrate = _rate("speed_rate", speed_rate), _rate("loudness_rate", loudness_rate)
         self.speed = None if speed is None else _range("speed", speed, 0.5, 2.0)
         self.loudness = None if loudness is None else _range("loudness", loudness, -80.0, 0.0, " dBFS")
+        trate, prate = _rate("tempo_rate", tempo_rate), _rate("pitch_rate", pitch_rate)
+        self.tempo = None if tempo is None else _range("tempo", tempo, 0.5, 2.0)
+        self.pitch = None if pitch is None else _range("pitch", pitch, -12.0, 12.0, " semitones")
+        if isinstance(pitch_n_fft, bool) or pitch_n_fft not in _l.PITCH_N_FFT:
+            raise ValueError("pitch_n_fft must be one of %s, got %r" % (", ".join(str(n) for n in _l.PITCH_N_FFT), pitch_n_fft))
+        self.tempo_rate, self.pitch_rate, self.pitch_n_fft = trate, prate, int(pitch_n_fft)
         if resampler is not None and not isinstance(resampler, Resampler):
             raise ValueError("resampler must be a kws_amd.augment.Resampler, got %r" % (resampler,))
-        self.resampler = resampler if resampler is not None or self.speed is None else Resampler()
+        self.resampler = resampler if resampler is not None or (self.speed is None and self.pitch is None) else Resampler()
         self.speed_rate, self.loudness_rate = srate, lrate
         frate, rrate, rate = _rate("filter_rate", filter_rate), _rate("reverb_rate", reverb_rate), _rate("noised_rate", noised_rate)
         snr = parse_snr(snr)
@@ -659,6 +689,63 @@ class WaveAugment(object):
         if exs is not None or exd is not None:
             torch.cuda.current_stream().synchronize()       # the host values are copied from pageable memory
         return out, lengths, speed_used, gain_used
+
+    @property
+    def vocodes(self):
+        """whether the tempo / pitch stage is configured"""
+        return self.tempo is not None or self.pitch is not None
+
+    @property
+    def pitch_seed(self):
+        return self.seed ^ PITCH_SEED_MIX
+
+    def pitch_params(self, max_samples):
+        p = _l.KwsPitchParams()
+        if self.tempo is not None:
+            p.tempo_rate, p.tempo_lo, p.tempo_hi = self.tempo_rate, self.tempo[0], self.tempo[1]
+        if self.pitch is not None:
+            p.pitch_rate, p.pitch_lo, p.pitch_hi = self.pitch_rate, self.pitch[0], self.pitch[1]
+        p.n_fft, p.max_samples, p.reserved, p.seed = self.pitch_n_fft, int(max_samples), 0, self.pitch_seed
+        return p
+
+    def pitch_perturb(self, wav, valid_len=None, index=None, step=0, position_base=0, explicit_tempo=None, explicit_semitones=None,
+                      max_samples=None, out=None, lengths=None, tempo_used=None, pitch_used=None, workspace=None, tile_clips=None):
+        """-> (out (B, max_samples) float32, lengths (B,) int32, tempo_used (B,) float32, pitch_used (B,) float32): the B clips
+        wav[index] (default: every row), each stretched at the tempo drawn for (seed, step) at global position position_base + b
+        (tempo_used = the tempo, 0 for a clip left at its tempo) and shifted by the semitones drawn for it (pitch_used = the shift,
+        NaN for a clip left at its pitch; a clip left at both is the float32 conversion, bit for bit), head-aligned, zeros after.  A
+        clip's whole valid length is the source, not only its first max_samples.  explicit_tempo: B tempos (0, or 0.5..2) instead of
+        the draws; explicit_semitones: B shifts in -12..12 (NaN: not pitched) instead of the draws.  out / lengths / tempo_used /
+        pitch_used: optional preallocated CUDA buffers (out may be wider than max_samples; tempo_used=False / pitch_used=False skip
+        them).  workspace: an optional CUDA uint8 tensor of at least pitch_workspace_bytes(pitch_n_fft, max_samples, 1) bytes (the
+        batch is walked in tiles of as many clips as it holds); default: a fresh one for min(B, tile_clips or PITCH_TILE_CLIPS)
+        clips.  The result does not depend on the tile."""
+        from classifier.params import pr
+        torch = _torch()
+        _, stride, B, ix, vl = _clip_batch(wav, valid_len, index)
+        ms = int(pr.max_samples if max_samples is None else max_samples)
+        ext = _explicit(explicit_tempo, np.float32, B, "tempo")
+        exp = _explicit(explicit_semitones, np.float32, B, "pitch")
+        if exp is not None and self.resampler is None and not np.isnan(exp).all():
+            raise ValueError("this WaveAugment has no resampler: give pitch=... or resampler=... to shift a clip's pitch")
+        if ext is not None and tempo_used is False:
+            tempo_used = None                               # the explicit tempos are staged there
+        if exp is not None and pitch_used is False:
+            pitch_used = None                               # the explicit shifts are staged there
+        out, lengths, tempo_used, pitch_used = _outputs(wav, B, ms, out, lengths, (tempo_used, torch.float32), (pitch_used, torch.float32))
+        if workspace is None and B > 0:
+            tile = max(1, min(B, int(tile_clips or PITCH_TILE_CLIPS)))
+            workspace = torch.empty((pitch_workspace_bytes(self.pitch_n_fft, ms, tile),), dtype=torch.uint8, device=wav.device)
+        elif workspace is not None and (workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous()):
+            raise ValueError("workspace must be a contiguous CUDA uint8 tensor")
+        _l.check(_l.get_lib().kws_pitch_apply(None if self.resampler is None else self.resampler.handle(), ctypes.byref(self.pitch_params(ms)),
+                                              wav.data_ptr(), _wav_code(wav), ix, B, stride, vl, int(position_base), int(step),
+                                              _host_ptr(ext), _host_ptr(exp), out.data_ptr(), out.shape[1], lengths.data_ptr(),
+                                              _ptr(tempo_used), _ptr(pitch_used), _ptr(workspace),
+                                              0 if workspace is None else workspace.numel(), torch.cuda.current_stream().cuda_stream))
+        if ext is not None or exp is not None:
+            torch.cuda.current_stream().synchronize()       # the host values are copied from pageable memory
+        return out, lengths, tempo_used, pitch_used
 
     @property
     def reverb_seed(self):
@@ -801,6 +888,58 @@ def resample(wav, orig_sr, target_sr, resampler=None):
                                           torch.cuda.current_stream().cuda_stream))
     torch.cuda.current_stream().synchronize()               # ex is copied from pageable memory
     return out
+
+
+def _one_shot(wav, what):
+    if not wav.is_cuda or wav.dim() != 2 or not wav.is_contiguous():
+        raise ValueError("wav must be a contiguous CUDA tensor of shape (rows, samples)")
+    if wav.shape[1] < 1:
+        raise ValueError("wav has no samples")
+    if wav.shape[1] > _l.PITCH_MAX_SAMPLES:
+        raise ValueError("%s takes rows of at most %d samples, got %d" % (what, _l.PITCH_MAX_SAMPLES, wav.shape[1]))
+
+
+def time_stretch(wav, rate, n_fft=512):
+    """-> (B, floor(n / rate + 0.5)) float32 CUDA tensor: the rows of wav (a contiguous CUDA tensor (B, n), float32 or int16 scaled by
+    1/32768) played `rate` times faster (0.5..2) at their pitch: WaveAugment's phase vocoder at one fixed tempo."""
+    _torch()
+    _one_shot(wav, "time_stretch")
+    rate = np.float32(rate)
+    if not 0.5 <= rate <= 2.0:
+        raise ValueError("rate must be in [0.5, 2], got %g" % rate)
+    B, n = wav.shape
+    n_out = max(int(math.floor(float(n) / float(rate) + 0.5)), 1)
+    aug = WaveAugment(None, tempo=(1.0, 1.0), tempo_rate=0.0, pitch_n_fft=n_fft, seed=0)
+    return aug.pitch_perturb(wav, explicit_tempo=np.full((B,), rate, np.float32), max_samples=n_out, tempo_used=None, pitch_used=False)[0]
+
+
+def pitch_shift(wav, n_steps, n_fft=512, resampler=None):
+    """-> (B, n) float32 CUDA tensor: the rows of wav (a contiguous CUDA tensor (B, n), float32 or int16 scaled by 1/32768) shifted by
+    n_steps semitones (-12..12) at their duration (the last sample or two of a row may be zero: the length is rounded twice):
+    WaveAugment's phase vocoder and resampling at one fixed shift."""
+    _torch()
+    _one_shot(wav, "pitch_shift")
+    n_steps = np.float32(n_steps)
+    if not -12.0 <= n_steps <= 12.0:
+        raise ValueError("n_steps must be in [-12, 12] semitones, got %g" % n_steps)
+    B, n = wav.shape
+    aug = WaveAugment(None, pitch=(0.0, 0.0), pitch_rate=0.0, pitch_n_fft=n_fft, resampler=resampler, seed=0)
+    return aug.pitch_perturb(wav, explicit_semitones=np.full((B,), n_steps, np.float32), max_samples=n, tempo_used=False, pitch_used=None)[0]
+
+
+def stft(wav, n_fft=512, valid_len=None, index=None):
+    """-> (B, 1 + n // (n_fft / 4), n_fft / 2 + 1) complex64 CUDA tensor: the vocoder's analysis of the clips wav[index] (a contiguous
+    CUDA tensor (rows, n), float32 or int16 scaled by 1/32768; valid_len: their lengths): frames of n_fft samples at hop n_fft / 4 under a
+    periodic Hann window, the first one centred on sample 0 (n_fft / 2 zeros in front); frames past a clip's last are zeros."""
+    torch = _torch()
+    if isinstance(n_fft, bool) or n_fft not in _l.PITCH_N_FFT:
+        raise ValueError("n_fft must be one of %s, got %r" % (", ".join(str(n) for n in _l.PITCH_N_FFT), n_fft))
+    _, stride, B, ix, vl = _clip_batch(wav, valid_len, index)
+    frames = 1 + stride // (n_fft // 4)
+    out = torch.empty((B, frames, n_fft // 2 + 1, 2), dtype=torch.float32, device=wav.device)
+    _l.check(_l.get_lib().kws_pitch_stft(wav.data_ptr(), _wav_code(wav), ix, B, stride, vl, int(n_fft), out.data_ptr(), frames,
+                                         torch.cuda.current_stream().cuda_stream))
+    return torch.view_as_complex(out)
 
 
 def records(plan):

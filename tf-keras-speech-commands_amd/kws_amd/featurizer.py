@@ -90,7 +90,9 @@ class Featurizer(object):
         reverberated first (kws_reverb_apply into a scratch buffer of this featurizer); with a filter bank they are filtered next
         (kws_filter_apply, in place in that scratch); then noised (if it has a noise bank) and featurized from there.  With a speed or
         loudness range the clips are perturbed before all of that (kws_speed_apply into the scratch; into a second buffer when a
-        reverberation follows, which does not run in place)."""
+        reverberation follows, which does not run in place).  With a tempo or pitch range the clips go through the phase vocoder first
+        of all (kws_pitch_apply into a scratch buffer of its own when another of these stages follows; its workspace is this
+        featurizer's too, one per stream)."""
         torch = _torch()
         _, stride, B, ix, vl = _clip_batch(wav, valid_len, index, "(B, stride)")
         g = self.geometry
@@ -98,11 +100,18 @@ class Featurizer(object):
             out = torch.empty((B, g["n_features"], g["feature_size"]), dtype=torch.float32, device=wav.device)
         elif out.numel() < B * g["n_features"] * g["feature_size"] or not out.is_contiguous():
             raise ValueError("out is too small for %d clips" % B)
-        if augment is not None and (augment.perturbs or augment.rirs is not None or augment.filters is not None):
-            # speed / loudness, reverberation, then the filter (in place), into this featurizer's scratch on the call's stream; then
-            # noise (or nothing)
+        if augment is not None and (augment.vocodes or augment.perturbs or augment.rirs is not None or augment.filters is not None):
+            # tempo / pitch, speed / loudness, reverberation, then the filter (in place), into this featurizer's scratch on the call's
+            # stream; then noise (or nothing)
             ms = g["max_samples"]
             wet, lens = self._reverb_scratch(B, ms, wav.device), self._reverb_lengths(B, wav.device)
+            if augment.vocodes:
+                last = not (augment.perturbs or augment.rirs is not None or augment.filters is not None)
+                pv, pv_lens = (wet, lens) if last else self._scratch(B, ms, wav.device, "_pv_bufs")
+                augment.pitch_perturb(wav, valid_len=valid_len, index=index, step=step, position_base=position_base, max_samples=ms, out=pv,
+                                      lengths=pv_lens, tempo_used=False, pitch_used=False,
+                                      workspace=self._pitch_workspace(B, ms, augment.pitch_n_fft, wav.device))
+                wav, index, valid_len = pv, None, pv_lens
             if augment.perturbs:
                 pre, pre_lens = (wet, lens) if augment.rirs is None else self._scratch(B, ms, wav.device, "_sp_bufs")
                 augment.perturb(wav, valid_len=valid_len, index=index, step=step, position_base=position_base, max_samples=ms, out=pre,
@@ -137,6 +146,18 @@ class Featurizer(object):
         if buf is None or buf[0].shape[0] < B or buf[0].shape[1] != ms or buf[0].device != device:
             buf = bufs[key] = (torch.empty((B, ms), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.int32, device=device))
         return buf[0][:B], buf[1][:B]
+
+    def _pitch_workspace(self, B, ms, n_fft, device):
+        """the vocoder's workspace for min(B, PITCH_TILE_CLIPS) clips at a time, one per stream (grown on demand)"""
+        from .augment import PITCH_TILE_CLIPS, pitch_workspace_bytes
+        torch = _torch()
+        key = torch.cuda.current_stream().cuda_stream
+        need = pitch_workspace_bytes(n_fft, ms, max(1, min(B, PITCH_TILE_CLIPS)))
+        bufs = self.__dict__.setdefault("_pv_ws", {})
+        ws = bufs.get(key)
+        if ws is None or ws.numel() < need or ws.device != device:
+            ws = bufs[key] = torch.empty((need,), dtype=torch.uint8, device=device)
+        return ws
 
     def _reverb_scratch(self, B, ms, device):
         """(B, ms) float32 rows the reverberated clips go to"""

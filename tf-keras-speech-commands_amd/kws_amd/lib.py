@@ -99,6 +99,16 @@ class KwsSpeedParams(ctypes.Structure):
                 ("max_samples", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
 
 
+class KwsPitchParams(ctypes.Structure):
+    _fields_ = [("tempo_rate", ctypes.c_float), ("tempo_lo", ctypes.c_float), ("tempo_hi", ctypes.c_float),
+                ("pitch_rate", ctypes.c_float), ("pitch_lo", ctypes.c_float), ("pitch_hi", ctypes.c_float),
+                ("n_fft", ctypes.c_int32), ("max_samples", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
+PITCH_N_FFT = (256, 512, 1024)
+PITCH_MAX_SAMPLES = 1 << 20
+
+
 FMASK_MAX = 4
 FMASK_FILL = {"zero": 0, "mean": 1}                                                      # include/kws.h KWS_FMASK_*
 
@@ -310,6 +320,10 @@ def get_lib():
     L.kws_resampler_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(f64), ctypes.POINTER(f64)]
     L.kws_resampler_table.argtypes = [vp, vp, ctypes.c_size_t]
     L.kws_speed_apply.argtypes = [vp, ctypes.POINTER(KwsSpeedParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.kws_pitch_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.kws_pitch_stft.argtypes = [vp, i32, vp, i32, i64, vp, i32, vp, i32, vp]
+    L.kws_pitch_apply.argtypes = [vp, ctypes.POINTER(KwsPitchParams), vp, i32, vp, i32, i64, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp,
+                                  ctypes.c_size_t, vp]
     L.kws_feature_mask_draw.argtypes = [ctypes.POINTER(KwsFeatureMaskParams), i32, i32, i64, i64, ctypes.POINTER(KwsFmaskClip)]
     L.kws_feature_mask.argtypes = [ctypes.POINTER(KwsFeatureMaskParams), vp, vp, i32, i32, i32, i64, i64, vp, vp, vp]
     L.kws_feature_mask_max_clip.restype = i64

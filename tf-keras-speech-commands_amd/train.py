@@ -15,6 +15,8 @@ that share of the training clips at zero phase with a Butterworth design drawn f
 --speed_range LO,HI plays a --speed_rate share of the training clips at a ratio drawn from the range (tempo and pitch together) and
 --loudness_range LO_DB,HI_DB sets a --loudness_rate share to a level drawn from the range (dBFS), before every other stage, as
 tools/audio_process/audio_convert.py resamples and levels files offline.
+--tempo_range LO,HI stretches a --tempo_rate share of the training clips in time without changing their pitch and --pitch_range LO,HI
+shifts a --pitch_rate share by that many semitones without changing their duration (a phase vocoder, before the speed change).
 --time_mask N,W / --freq_mask N,W / --time_warp W are SpecAugment of the features (--mask_rate, --mask_fill), drawn per clip and per
 step behind the featurizer or the cached features: they work with and without --raw_audio.
 The optimizer takes the Keras options the reference's command line leaves at their defaults: --clipnorm, --global_clipnorm and
@@ -61,13 +63,17 @@ def main(argv=None):
         raise SystemExit('--filter_rate needs --raw_audio (the waveforms are filtered before featurization)')
     if args.num_filters < 1:
         raise SystemExit('--num_filters needs a positive bank size')
-    for flag in ('speed_range', 'speed_rate', 'loudness_range', 'loudness_rate'):
+    for flag in ('speed_range', 'speed_rate', 'loudness_range', 'loudness_rate', 'tempo_range', 'tempo_rate', 'pitch_range', 'pitch_rate'):
         if getattr(args, flag) is not None and not args.raw_audio:
             raise SystemExit('--%s needs --raw_audio (the waveforms are perturbed before featurization)' % flag)
     if args.speed_rate is not None and args.speed_range is None:
         raise SystemExit('--speed_rate needs --speed_range')
     if args.loudness_rate is not None and args.loudness_range is None:
         raise SystemExit('--loudness_rate needs --loudness_range')
+    if args.tempo_rate is not None and args.tempo_range is None:
+        raise SystemExit('--tempo_rate needs --tempo_range')
+    if args.pitch_rate is not None and args.pitch_range is None:
+        raise SystemExit('--pitch_rate needs --pitch_range')
     perturb = perturb_options(args)
     mask = mask_options(args)
     opt_options = optimizer_options(args)
@@ -209,7 +215,7 @@ def parse_range(flag, text, lo, hi):
 
 
 def perturb_options(args):
-    """keyword arguments of WaveAugment for the speed / loudness flags given on the command line (none: no such stage)"""
+    """keyword arguments of WaveAugment for the speed / loudness / tempo / pitch flags given on the command line (none: no such stage)"""
     kw = {}
     if args.speed_range is not None:
         kw['speed'] = parse_range('speed_range', args.speed_range, 0.5, 2.0)
@@ -217,7 +223,13 @@ def perturb_options(args):
     if args.loudness_range is not None:
         kw['loudness'] = parse_range('loudness_range', args.loudness_range, -80.0, 0.0)
         kw['loudness_rate'] = 1.0 if args.loudness_rate is None else args.loudness_rate
-    for flag in ('speed_rate', 'loudness_rate'):
+    if args.tempo_range is not None:
+        kw['tempo'] = parse_range('tempo_range', args.tempo_range, 0.5, 2.0)
+        kw['tempo_rate'] = 1.0 if args.tempo_rate is None else args.tempo_rate
+    if args.pitch_range is not None:
+        kw['pitch'] = parse_range('pitch_range', args.pitch_range, -12.0, 12.0)
+        kw['pitch_rate'] = 1.0 if args.pitch_rate is None else args.pitch_rate
+    for flag in ('speed_rate', 'loudness_rate', 'tempo_rate', 'pitch_rate'):
         if flag in kw and not 0.0 <= kw[flag] <= 1.0:
             raise SystemExit('--%s must be in 0.0~1.0, got %r' % (flag, kw[flag]))
     return kw
@@ -349,6 +361,15 @@ def parse_args(argv=None):
                         help="LO_DB,HI_DB: set the training clips to a random loudness in this range in dBFS, -80~0, written --loudness_range -30,-15 or --loudness_range=-30,-15 (needs --raw_audio). default: off")
     parser.add_argument('--loudness_rate', type=float, required=False, default=None,
                         help="random percentage rate of setting the loudness of the training clips (0.0~1.0). default=1.0")
+    # Tempo and pitch perturbation (a phase vocoder, drawn per clip and per step, before the speed change)
+    parser.add_argument('--tempo_range', type=str, required=False, default=None,
+                        help="LO,HI: stretch the training clips in time at a random tempo in this range, 0.5~2.0, pitch unchanged (needs --raw_audio). default: off")
+    parser.add_argument('--tempo_rate', type=float, required=False, default=None,
+                        help="random percentage rate of changing the tempo of the training clips (0.0~1.0). default=1.0")
+    parser.add_argument('--pitch_range', type=str, required=False, default=None,
+                        help="LO,HI: shift the pitch of the training clips by a random number of semitones in this range, -12~12, duration unchanged, written --pitch_range -2,2 or --pitch_range=-2,2 (needs --raw_audio). default: off")
+    parser.add_argument('--pitch_rate', type=float, required=False, default=None,
+                        help="random percentage rate of shifting the pitch of the training clips (0.0~1.0). default=1.0")
     # SpecAugment of the features (time warp, time masks, frequency masks; drawn per clip and per step, with or without --raw_audio)
     parser.add_argument('--time_mask', type=str, required=False, default=None,
                         help="N,W: overwrite N blocks of up to W frames of every training clip's features (N <= 4). default: off")
@@ -363,8 +384,8 @@ def parse_args(argv=None):
     # "--loudness_range -30,-15": argparse takes a value that starts with '-' and is no plain number for an option, so bind it with '='
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 2, -1, -1):
-        if argv[i] == '--loudness_range':
-            argv[i:i + 2] = ['--loudness_range=' + argv[i + 1]]
+        if argv[i] in ('--loudness_range', '--pitch_range'):
+            argv[i:i + 2] = [argv[i] + '=' + argv[i + 1]]
     return parser.parse_args(argv)
 
 
