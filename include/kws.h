@@ -1225,6 +1225,87 @@ enum { KWS_VAD_ALIGN_LEFT_PAD = 0, KWS_VAD_ALIGN_CENTER = 1 };
 int kws_vad_gather_clips(const void *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths, const int32_t *triples,
                          int n, int clip_samples, int pad_before, int pad_after, int align, float *clips, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Labelled streaming test recordings from clips: what TensorFlow's speech_commands example does on the host with
+ * generate_streaming_test_wav.py (clips laid at random gaps over a continuous background, their positions written down), on the device
+ * and for R recordings at once.  Recording r has N_r samples and sits at global position p = position_base + r; every draw is
+ * h(i) = aug_hash(seed, (uint32)p, i) (csrc/kws_wave_stage.h, restated in tests/aug_ref.py):
+ *   bed     k = aug_uniform(h(0), K), o = aug_uniform(h(1), seg_len[k]), bed_gain = fmaf(aug_unit(h(2)), hi - lo, lo): the bed of the
+ *           whole recording is segment k of the noise bank read circularly from o at ONE gain, so it stays continuous
+ *   slot j  row_j = pick[aug_uniform(h(4 + 3 j), M)] (no pick table: the drawn number itself, M = rows),
+ *           gap_j = gap_lo + aug_uniform(h(5 + 3 j), gap_hi - gap_lo + 1), snr_j = snr_db[aug_uniform(h(6 + 3 j), n_snr)];
+ *           the index depends on j alone, so a larger max_events changes no earlier draw
+ *   place   len_j = min(clamp(valid_len[row_j], 0, stride), clip_cap); start_j = lead_in + sum_{i<j} (len_i + gap_i) + gap_j;
+ *           n_events = the number of leading slots with start_j + len_j <= N_r: the first slot that does not fit ends the recording
+ *   gain    p_v = mean(v[0:len]^2), p_n = bed_gain^2 mean(n_k[(o + start + i) mod seg_len[k]]^2, i < len), both in fp64;
+ *           gain = min(max_gain, (float)sqrt(10^(snr/10) p_n / (p_v + FLT_EPSILON))); gain = 1 when n_snr == 0 or there is no bank,
+ *           0 for len == 0.  The voice is scaled against the bed under it (the noise mix above scales the noise against the voice)
+ *   sample  x[t] = bed_gain n_k[(o + t) mod seg_len[k]] (0 without a bank); inside event e, u = t - start_e:
+ *           w = min(1, (u + 1) inv_fade, (len_e - u) inv_fade), inv_fade = 1.0f / (fade + 1);
+ *           x[t] = fmaf(gain_e w, v[row_e][u], x[t]); t in [N_r, out_stride) is 0
+ * Divergences from the TensorFlow tool: the draws are counter-based and made per recording on the device (no host loop over events);
+ * the gap is uniform between two bounds; the clip's level is set by an SNR against the bed under it instead of a fixed gain; a
+ * linear fade at both ends of a clip; the bed is one circular segment per recording instead of a fresh cut per second; clips of
+ * every class are drawn alike (the caller leaves the background's clips out of its events).
+ * ---------------------------------------------------------------------- */
+typedef struct kws_synth_params {
+    int32_t gap_lo, gap_hi;            /* samples between two clips, 0 <= gap_lo <= gap_hi */
+    int32_t lead_in;                   /* samples before the first gap, >= 0 */
+    int32_t clip_cap;                  /* a clip is cut to this many samples, >= 1 */
+    int32_t n_snr;                     /* 0..KWS_AUG_MAX_SNR; 0: every gain is 1 */
+    float snr_db[KWS_AUG_MAX_SNR];
+    float bed_gain_lo, bed_gain_hi;    /* bed_gain_lo <= bed_gain_hi */
+    float max_gain;                    /* > 0 */
+    int32_t fade;                      /* samples of the linear fade at both ends of a clip, 0 = off */
+    int32_t reserved;
+    uint64_t seed;
+} kws_synth_params;
+
+/* one recording's bed (16 bytes, device memory); without a bank {-1, 0, 0, n_events} */
+typedef struct kws_synth_rec {
+    int32_t segment;      /* k */
+    int32_t offset;       /* o */
+    float bed_gain;
+    int32_t n_events;
+} kws_synth_rec;
+
+/* one slot of a recording (32 bytes, device memory); a slot at or past n_events is {-1, 0, 0, 0, 0} */
+typedef struct kws_synth_event {
+    int32_t row;          /* row of the clip store */
+    int32_t start;        /* first sample in the recording */
+    int32_t length;       /* len */
+    float snr_db;         /* the drawn SNR (0 when n_snr == 0) */
+    float gain;
+    int32_t reserved[3];
+} kws_synth_event;
+
+#define KWS_SYNTH_MAX_EVENTS 4096
+
+/* Plan R recordings without host synchronisation: the draws and the placement by one wave per recording (lanes stride over the slots,
+ * an inclusive scan in int64 with a carry between groups of 64), then the gains by one wave per placed slot (fp32 lane partials, an
+ * fp64 wave sum: a fixed order, the same bits on every run; p_n from the bank's prefix sums as whole loops of the segment plus at most
+ * two pieces).  wav (rows x stride) of wav_dtype, valid_len (rows device int32, NULL: stride), pick (M device int32 row numbers, NULL:
+ * every row), bank (NULL: a silent bed), lengths (R device int32, each N_r >= 0), rec (R) and events (R x max_events) device records.
+ * KWS_ERR_INVALID: gap_lo < 0 or gap_hi < gap_lo, lead_in < 0, clip_cap < 1, n_snr outside 0..KWS_AUG_MAX_SNR or an SNR that is not
+ * finite, bed_gain_hi < bed_gain_lo, max_gain <= 0, fade < 0, max_events outside 1..KWS_SYNTH_MAX_EVENTS, an unknown wav_dtype, a
+ * negative R, stride or position_base, rows or M < 1; KWS_ERR_UNSUPPORTED: stride > INT_MAX.  All of it is reported before any device
+ * work.  R == 0 does nothing. */
+int kws_synth_plan(const kws_noise_bank *bank, const kws_synth_params *params, const void *wav, int wav_dtype, int rows, int64_t stride,
+                   const int32_t *valid_len, const int32_t *pick, int M, const int32_t *lengths, int R, int max_events,
+                   int64_t position_base, kws_synth_rec *rec, kws_synth_event *events, void *stream);
+
+/* Render the planned recordings: out (R x out_stride) of out_dtype, KWS_WAV_F32 or KWS_WAV_I16 = rint(x * 32768) saturated to
+ * [-32768, 32767].  max_len: the largest N_r (host; lengths[r] above it is cut to it), out_stride >= max_len.  The grid is (tiles of
+ * a row, R); a block finds the events that meet its tile by binary search over the sorted slots and stages them in LDS; the stores are 128 bits wide when
+ * out and out_stride allow it.  Precondition, NOT checked (rec and events are device memory): the first n_events slots of a
+ * recording are sorted by start and do not overlap, as kws_synth_plan writes them.  A slot whose row lies outside [0, rows) is
+ * skipped and its length is cut to stride, so no clip is read past its row; the bank is read inside segment k only (a segment
+ * outside [0, K) gives a silent bed).  KWS_ERR_INVALID: fade < 0, max_events outside 1..KWS_SYNTH_MAX_EVENTS, an unknown dtype,
+ * out_stride < max_len, a negative R, rows, stride or max_len; KWS_ERR_UNSUPPORTED: stride or max_len > INT_MAX.  R == 0 does nothing. */
+int kws_synth_render(const kws_noise_bank *bank, const void *wav, int wav_dtype, int rows, int64_t stride, const kws_synth_rec *rec,
+                     const kws_synth_event *events, int max_events, const int32_t *lengths, int R, int64_t max_len, int fade,
+                     void *out, int out_dtype, int64_t out_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

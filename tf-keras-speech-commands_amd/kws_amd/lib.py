@@ -75,6 +75,13 @@ class KwsAugClip(ctypes.Structure):
                 ("length", ctypes.c_int32), ("snr_db", ctypes.c_float), ("gain", ctypes.c_float), ("voice_length", ctypes.c_int32)]
 
 
+class KwsSynthParams(ctypes.Structure):
+    _fields_ = [("gap_lo", ctypes.c_int32), ("gap_hi", ctypes.c_int32), ("lead_in", ctypes.c_int32), ("clip_cap", ctypes.c_int32),
+                ("n_snr", ctypes.c_int32), ("snr_db", ctypes.c_float * AUG_MAX_SNR), ("bed_gain_lo", ctypes.c_float),
+                ("bed_gain_hi", ctypes.c_float), ("max_gain", ctypes.c_float), ("fade", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("seed", ctypes.c_uint64)]
+
+
 class KwsReverbParams(ctypes.Structure):
     _fields_ = [("reverb_rate", ctypes.c_float), ("rescale", ctypes.c_int32), ("max_samples", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64)]
@@ -353,6 +360,8 @@ def get_lib():
     L.kws_vad_workspace_bytes.restype = i64
     L.kws_vad_detect.argtypes = [vp, vp, i32, i32, i64, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.kws_vad_gather_clips.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+    L.kws_synth_plan.argtypes = [vp, ctypes.POINTER(KwsSynthParams), vp, i32, i32, i64, vp, vp, i32, vp, i32, i32, i64, vp, vp, vp]
+    L.kws_synth_render.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, vp, i32, i64, i32, vp, i32, i64, vp]
     _lib = L
     return L
 

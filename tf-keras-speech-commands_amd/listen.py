@@ -8,7 +8,9 @@ kws_amd.stream.scan at once and give per chunk what `run_wav` gives.  `Listener.
 recordings once and evaluates the detector at a whole grid of (sensitivity, trigger_level): miss rate against false alarms per hour.
 `--save_dir` saves the audio buffer of every activation as the reference does (listen.py:299-308): chunk by chunk in `run_wav`, and
 for whole files at once in --scan / --sweep through `Listener.collect_wav` (kws_amd.stream.collect / peaks), which with labels
-tells false alarms from hits and can add the near misses that never fired (--mine_peaks).
+tells false alarms from hits and can add the near misses that never fired (--mine_peaks).  `Listener.sweep_synth` (CLI: --sweep
+--synth_from DATASET_DIR) needs no labelled recordings: it synthesizes them on the device from a dataset's one-second clips and a
+folder of background noise (kws_amd.synth) and sweeps those.
 
 Differences from listen.py: checkpoints are the `.npz` files classifier.model writes (no h5/pb/tflite/onnx/mnn
 back ends); there is no PyAudio in this image, so `run_microphone` raises and `run_wav` does not play the audio while it
@@ -29,6 +31,7 @@ from common.utils import get_classes
 from kws_amd import lib as _lib
 from kws_amd.stream import StreamBatch, ThresholdDecoder, TriggerDetector, scan  # noqa: F401  (re-exported like listen.py:452,525)
 from kws_amd.stream import collect, peaks, sweep
+from kws_amd.synth import synthesize
 
 SAVE_KINDS = {                                         # --save_kind -> the kinds of kws_amd.stream.Detections it keeps
     "false_alarms": (_lib.DET_FALSE_ALARM,),
@@ -97,6 +100,14 @@ def parse_labels(path, class_names, sample_rate):
                 raise ValueError("%s:%d: an event needs 0 <= start < end" % (path, no))
             out.setdefault(os.path.basename(name), []).append((class_names.index(cls), a, b))
     return out
+
+
+def parse_gap(text):
+    """--synth_gap_s: 'LO,HI' in seconds"""
+    vals = [float(v) for v in text.split(',') if v.strip()]
+    if len(vals) != 2 or not 0 <= vals[0] <= vals[1]:
+        raise ValueError("expected LO,HI with 0 <= LO <= HI, got %r" % text)
+    return vals[0], vals[1]
 
 
 class Listener(object):
@@ -279,6 +290,32 @@ class Listener(object):
         self.sweep_scan, self.sweep_lengths = res, lens
         return out
 
+    def sweep_synth(self, dataset_dir, sensitivities, trigger_levels, noise_path=None, recordings=8, seconds=600, gap_s=(1.0, 3.0), snr=None,
+                    seed=0, save_dir=None, tolerance_s=None):
+        """sweep_wav without recordings: the clips under dataset_dir (one folder per class, or a dataset folder with `sounds` in it;
+        classifier.data.load_audio_samples) are laid over the noise under noise_path (classifier.data.load_noise_bank; None: silence)
+        by kws_amd.synth.synthesize, scanned once and swept.  save_dir: also write the recordings and their labels.txt there, for
+        sweep_wav / --labels_path later.  tolerance_s defaults to SynthSet.tolerance_samples (kept in `self.synth_tolerance_s`).  Returns the
+        SweepResult; `self.synth_set` keeps the SynthSet, `self.sweep_scan` the scan."""
+        from classifier.data import load_audio_samples, load_noise_bank
+        sounds = os.path.join(dataset_dir, 'sounds')
+        x, lengths, words = load_audio_samples(sounds if os.path.isdir(sounds) else dataset_dir, self.class_names)
+        if len(x) == 0:
+            raise ValueError('no clips of the listed classes under ' + str(dataset_dir))
+        labels = [self.class_names.index(w.lower()) for w in words]
+        noise = load_noise_bank(noise_path) if noise_path else None
+        self.synth_set = synthesize(x, labels, valid_len=lengths, noise=noise, recordings=recordings, seconds=seconds, gap_s=gap_s, snr=snr,
+                                    seed=seed, sample_rate=self.pr.sample_rate, clip_cap=self.pr.max_samples)
+        if save_dir:
+            self.synth_set.save(save_dir, self.class_names)
+        tol = self.synth_set.tolerance_samples(self.chunk_size, self.pr) if tolerance_s is None else int(round(tolerance_s * self.pr.sample_rate))
+        self.synth_tolerance_s = tol / float(self.pr.sample_rate)
+        out = self.synth_set.sweep(self.pr, self.model._device(), sensitivities, trigger_levels, chunk_size=self.chunk_size,
+                                   tolerance_samples=tol, class_names=self.class_names, decoder=self.threshold_decoder,
+                                   quantized=self.quantized, tile=self.scan_tile, keep_audio=bool(self.save_dir))
+        self.sweep_scan, self.sweep_lengths = self.synth_set.last_scan, self.synth_set.lengths
+        return out
+
     def collect_wav(self, paths, labels=None, sensitivity=None, trigger_level=None, tolerance_s=None, save_dir=None, save_kind=None,
                     mine_peaks=0, min_peak_score=0.0, scan=None):
         """The activations of whole files as training clips (kws_amd.stream.collect -> Detections.save): what run_wav with
@@ -324,13 +361,26 @@ class Listener(object):
 
     def run_sweep(self):
         """--sweep: the (S, L) table of miss rate and false alarms per hour, and the chosen point under --max_fa_per_hour"""
-        paths = self.input_wav
-        if os.path.isdir(paths):
-            paths = sorted(os.path.join(paths, n) for n in os.listdir(paths) if n.lower().endswith('.wav'))
-        files = [paths] if isinstance(paths, str) else paths
         sens = parse_sensitivities(getattr(self, 'sensitivities', None) or str(self.sensitivity))
         levels = parse_trigger_levels(getattr(self, 'trigger_levels', None) or str(self.trigger_level))
-        res = self.sweep_wav(files, getattr(self, 'labels_path', None), sens, levels, tolerance_s=getattr(self, 'tolerance_s', None))
+        synth_from = getattr(self, 'synth_from', None)
+        if synth_from:
+            res = self.sweep_synth(synth_from, sens, levels, noise_path=getattr(self, 'noise_path', None),
+                                   recordings=getattr(self, 'synth_recordings', 8), seconds=getattr(self, 'synth_seconds', 600),
+                                   gap_s=parse_gap(getattr(self, 'synth_gap_s', None) or '1.0,3.0'), snr=getattr(self, 'synth_snr', None),
+                                   seed=getattr(self, 'synth_seed', 0), save_dir=getattr(self, 'synth_save_dir', None),
+                                   tolerance_s=getattr(self, 'tolerance_s', None))
+            # the names SynthSet.save gives the recordings; their events and the sweep's tolerance go to collect_wav below
+            files = ['synth_%d.wav' % r for r in range(len(res.seconds))]
+            labels = dict(zip(files, self.synth_set.events))
+            options = dict(self._collect_options(), tolerance_s=self.synth_tolerance_s)
+        else:
+            paths = self.input_wav
+            if os.path.isdir(paths):
+                paths = sorted(os.path.join(paths, n) for n in os.listdir(paths) if n.lower().endswith('.wav'))
+            files = [paths] if isinstance(paths, str) else paths
+            labels, options = getattr(self, 'labels_path', None), self._collect_options()
+            res = self.sweep_wav(files, labels, sens, levels, tolerance_s=getattr(self, 'tolerance_s', None))
         miss, fa = res.det()
         print('%d files, %.1f s, %d events; miss rate / false alarms per hour' % (len(files), sum(res.seconds), sum(res.n_events)))
         print('%11s' % 'sensitivity' + ''.join('%18s' % ('level %d' % l) for l in levels))
@@ -353,13 +403,12 @@ class Listener(object):
         if self.save_dir and (budget is None or best is not None):
             # the clips of the chosen point (without a budget: the listener's own), from the scan the sweep made
             point = {} if best is None else dict(sensitivity=best['sensitivity'], trigger_level=best['trigger_level'])
-            self.collect_wav(files, getattr(self, 'labels_path', None), scan=(self.sweep_scan, self.sweep_lengths), **point,
-                             **self._collect_options())
+            self.collect_wav(files, labels, scan=(self.sweep_scan, self.sweep_lengths), **point, **options)
             print('saved %d clips under %s' % (len(self.collected_paths), self.save_dir))
         return res
 
     def run(self):
-        if self.input_wav and getattr(self, 'sweep', False):
+        if (self.input_wav or getattr(self, 'synth_from', None)) and getattr(self, 'sweep', False):
             return self.run_sweep()
         if self.input_wav and self.scan:
             paths = self.input_wav
@@ -381,7 +430,7 @@ class Listener(object):
         return self.run_microphone()
 
 
-def main():
+def parse_args(argv=None):
     parser = argparse.ArgumentParser(description='keyword detection on a wav file (MI355X path)')
     parser.add_argument('--model_path', type=str, default=None, help='.npz weights written by classifier.model')
     parser.add_argument('--quantized_path', type=str, default=None,
@@ -392,7 +441,8 @@ def main():
     parser.add_argument('--chunk_size', type=int, default=1024)
     parser.add_argument('--sensitivity', type=float, default=0.5)
     parser.add_argument('--trigger_level', type=int, default=3)
-    parser.add_argument('--input_wav', type=str, required=True, help='a wav file; with --scan also a directory of *.wav')
+    parser.add_argument('--input_wav', type=str, default=None,
+                        help='a wav file; with --scan also a directory of *.wav (required unless --synth_from is given)')
     parser.add_argument('--scan', action='store_true',
                         help='offline scan: the whole recording(s) at once instead of chunk by chunk; prints every activation with its time')
     parser.add_argument('--scan_tile', type=int, default=default_config['scan_tile'], help='windows per forward launch of --scan')
@@ -416,10 +466,34 @@ def main():
                         help='--scan / --sweep with --save_dir: also save the K best well-separated non-background chunks of every file '
                              '(1..64), fired or not, under <save_dir>/near_miss/<class>/; with labels outside the event windows')
     parser.add_argument('--min_peak_score', type=float, default=0.0, help='--mine_peaks: only chunks scoring above this')
-    args = parser.parse_args()
+    parser.add_argument('--synth_from', type=str, default=None,
+                        help='--sweep without recordings: synthesize labelled ones on the device from this dataset folder (one folder of '
+                             'one-second clips per class, as train.py reads it) and sweep those')
+    parser.add_argument('--noise_path', type=str, default=None, help='--synth_from: folder (or file) of background wavs; default: a silent bed')
+    parser.add_argument('--synth_recordings', type=int, default=8, help='--synth_from: number of recordings')
+    parser.add_argument('--synth_seconds', type=float, default=600.0, help='--synth_from: length of every recording')
+    parser.add_argument('--synth_gap_s', type=str, default='1.0,3.0', help='--synth_from: LO,HI seconds of pause in front of every clip')
+    parser.add_argument('--synth_snr', type=str, default=None,
+                        help='--synth_from: dB values, a,b,c: every clip is scaled to one of them against the noise under it (default: clips as they are)')
+    parser.add_argument('--synth_seed', type=int, default=0)
+    parser.add_argument('--synth_save_dir', type=str, default=None, help='--synth_from: also write the recordings and labels.txt here')
+    args = parser.parse_args(argv)
     if not args.model_path and not args.quantized_path:
         parser.error('one of --model_path and --quantized_path is required')
-    Listener(**vars(args)).run()
+    if not args.input_wav and not args.synth_from:
+        parser.error('one of --input_wav and --synth_from is required')
+    if args.synth_from and not args.sweep:
+        parser.error('--synth_from goes with --sweep')
+    if args.synth_from:
+        try:
+            parse_gap(args.synth_gap_s)
+        except ValueError as e:
+            parser.error('--synth_gap_s: %s' % e)
+    return args
+
+
+def main():
+    Listener(**vars(parse_args())).run()
 
 
 if __name__ == '__main__':
