@@ -1,5 +1,6 @@
 // csrc/kws_quant.hip -- int8 post-training quantization of simple_cnn (include/kws.h: kws_model_calibrate, kws_quantize_simple_cnn,
-// kws_qmodel_*): the calibration kernel, the host quantizer and the int8 forward, features to probabilities in ONE kernel.
+// kws_qmodel_*): the per-clip fp32 forward the calibration kernels of kws_quant.h run, the host quantizer, the host helpers the other
+// int8 models share (kws_quant.h) and the int8 forward, features to probabilities in ONE kernel.
 //
 // The forward (qforward_kernel): a block of 256 threads owns kG = 8 clips for the whole network, every activation an int8 code in LDS,
 // stored haloed ([clip][row + 1][col + 1][channel], the halo holding code 0 = the "same" padding), so no tap is ever masked:
@@ -14,6 +15,7 @@
 //          max(acc, 0) (the layer's relu) before the epilogue, pooled over registers as conv2
 //   Dense, head: M = clips (rows 8..15 of the tile read clips 0..7 again and are dropped); the head's logits stay fp32 in LDS, then
 //          softmax and the arg-max per clip
+// t0 and the pooled epilogue of a conv4 accumulator tile are the functions of kws_quant_fwd.h, shared with lite_qforward_kernel.
 // LDS regions are reused as layers die (kLds = 42 240 B: three blocks per CU).  Weights are read fragment-major from global memory (L2-
 // resident, 140 KB in all); the epilogue constants likewise.
 #include <cmath>
@@ -21,27 +23,18 @@
 #include <thread>
 #include <vector>
 
-#include "kws_common.h"
-#include "kws_model_types.h"
-#include "kws_quant.h"
+#include "kws_quant_fwd.h"
 
 namespace kws {
 namespace q8 {
 
-constexpr int kG = 8;                   // clips per block
-constexpr int kThreads = 256;           // four waves
-// haloed int8 maps: [clip][H + 2][W + 2][C] (conv3 is stride 2 with 'same' padding 1 before and 1 after on both axes)
-constexpr int kXW = kW0 + 2, kXClip = (kH0 + 2) * kXW;        // 704 B
-constexpr int kA1W = 12, kA1Pix = 17 * kA1W, kA1Clip = kA1Pix * kC1;      // 15 x 10 x 16 -> 3264 B
-constexpr int kA2W = 7, kA2Pix = 9 * kA2W, kA2Clip = kA2Pix * kC2;        // 7 x 5 x 32   -> 2016 B
-constexpr int kA3W = 5, kA3Pix = 6 * kA3W, kA3Clip = kA3Pix * kC3;        // 4 x 3 x 64   -> 1920 B
 // regions: a1 and a3 share [0, 26112); t0, then a2, then a4 / d / logits share the rest
 constexpr int kOffA1 = 0, kOffA3 = 0;
 constexpr int kOffX = kG * kA1Clip, kOffA2 = kOffX, kOffA4 = kOffX;
 constexpr int kOffD = kOffA4 + kG * kFlat, kOffLG = kOffD + kG * kD, kOffMS = kOffLG + 4 * kG * kHead;
 constexpr int kLds = kOffA2 + kG * kA2Clip;
 static_assert(kG * kA3Clip <= kOffX && kOffMS + 8 * kG <= kLds && kOffX + kG * kXClip <= kLds, "LDS regions");
-static_assert(kA1Clip % 16 == 0 && kA2Clip % 16 == 0 && kA3Clip % 16 == 0 && kOffX % 16 == 0, "16-byte fragment reads");
+static_assert(kOffX % 16 == 0, "16-byte fragment reads");
 
 struct QFwdArgs {
     const float *feat;
@@ -65,19 +58,7 @@ __global__ __launch_bounds__(kThreads) void qforward_kernel(QFwdArgs g)
     const i32x4 zero4 = {0, 0, 0, 0};
 
     // ---- t0: codes of the features, halo = 0; a1's halo = 0 ----
-    for (int i = tid; i < kG * kXClip; i += kThreads) {
-        const int c = i / kXClip, p = i - c * kXClip, y = p / kXW - 1, x = p % kXW - 1;
-        int code = 0;
-        if (y >= 0 && y < kH0 && x >= 0 && x < kW0 && b0 + c < g.B) {
-            const float v = g.feat[(long)(b0 + c) * (kH0 * kW0) + y * kW0 + x];
-            code = (int)fminf(fmaxf(rintf(__fmul_rn(v, g.inv_s0)), -127.f), 127.f);
-        }
-        X[i] = (int8_t)code;
-    }
-    for (int i = tid; i < kG * kA1Pix; i += kThreads) {
-        const int p = i % kA1Pix, y = p / kA1W, x = p % kA1W;
-        if (y == 0 || y > 15 || x == 0 || x > 10) *reinterpret_cast<i32x4 *>(A1 + i * kC1) = zero4;
-    }
+    fwd_prologue(g.feat, g.B, b0, g.inv_s0, X, A1);
     __syncthreads();
 
     // ---- conv1 (vector ALU) + BN + ReLU6 + pool: one thread per (clip, pool window) ----
@@ -197,13 +178,12 @@ __global__ __launch_bounds__(kThreads) void qforward_kernel(QFwdArgs g)
 
     // ---- conv4 + relu + BN + ReLU6 + pool (positions of rows 0..3, columns 0..1): wave = column tiles 2 wave, 2 wave + 1 ----
     {
-        constexpr int kT = kG * 2 * 4 / 16;      // row tiles: (clip, window, pixel)
-        i32x4 acc[kT][2];
+        i32x4 acc[kT4][2];
 #pragma unroll
-        for (int t = 0; t < kT; ++t) acc[t][0] = acc[t][1] = zero4;
-        const int8_t *base[kT];
+        for (int t = 0; t < kT4; ++t) acc[t][0] = acc[t][1] = zero4;
+        const int8_t *base[kT4];
 #pragma unroll
-        for (int t = 0; t < kT; ++t) {
+        for (int t = 0; t < kT4; ++t) {
             const int p = 4 * t + (li >> 2), c = p >> 1, wy = p & 1, y = 2 * wy + ((li >> 1) & 1), x = li & 1;
             base[t] = A3 + c * kA3Clip + (y * kA3W + x) * kC3 + 16 * q;
         }
@@ -212,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void qforward_kernel(QFwdArgs g)
             const i32x4 w0 = g.f4[(s * kN4 + 2 * wave) * 64 + lane], w1 = g.f4[(s * kN4 + 2 * wave + 1) * 64 + lane];
             const int off = ((s / 3) * kA3W + s % 3) * kC3;
 #pragma unroll
-            for (int t = 0; t < kT; ++t) {
+            for (int t = 0; t < kT4; ++t) {
                 const i32x4 a = *reinterpret_cast<const i32x4 *>(base[t] + off);
                 acc[t][0] = mfma_i8(a, w0, acc[t][0]);
                 acc[t][1] = mfma_i8(a, w1, acc[t][1]);
@@ -223,13 +203,7 @@ __global__ __launch_bounds__(kThreads) void qforward_kernel(QFwdArgs g)
             const int ch = 16 * (2 * wave + u) + li;
             const float M = ep[kEpM4 + ch], Bq = ep[kEpB4 + ch];
 #pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                const int p = 4 * t + q, c = p >> 1, wy = p & 1;
-                int best = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) best = max(best, requant(max(acc[t][u][r], 0), M, Bq));
-                A4[c * kFlat + wy * kC4 + ch] = (int8_t)best;
-            }
+            for (int t = 0; t < kT4; ++t) fwd_pool4(acc[t][u], t, q, ch, M, Bq, A4);
         }
     }
     __syncthreads();
@@ -297,30 +271,36 @@ __global__ __launch_bounds__(kThreads) void qforward_kernel(QFwdArgs g)
         }
 }
 
-// ---- calibration: the fp32 inference forward of one clip (plain loops), every value of a quantized tensor handed to an observer ------
-// Two observers: CalMax (qcalibrate_kernel, one block per clip, max-reduced into amax) and CalHist (qhist_kernel, persistent, counted
-// into LDS histograms).  Both passes run this one function, so the histogram pass sees exactly the values the max pass reduced.
-struct CalArgs {
-    const float *feat;
-    const float *k[4], *gamma[4], *beta[4], *mm[4], *mv[4];
-    const float *dk, *db;
-    float *amax;
+// ---- calibration: the fp32 inference forward of one clip (plain loops), every value of a quantized tensor handed to an observer; the
+// network the calibration kernels and launchers of kws_quant.h run for simple_cnn (launch labels qcalibrate_kernel / qhist_kernel) ------
+struct CnnCal {
+    static constexpr int T = KWS_QUANT_TENSORS;
+    struct Args {
+        const float *feat;
+        const float *k[4], *gamma[4], *beta[4], *mm[4], *mv[4];
+        const float *dk, *db;
+        float *amax;
+    };
+    struct Smem {
+        float x0[kH0 * kW0], a1[15 * 10 * kC1], a2[7 * 5 * kC2], a3[4 * 3 * kC3], a4[kFlat];
+    };
+    static Args args(const kws_model *m, const float *params, const float *state)
+    {
+        Args a{};
+        for (int l = 0; l < 4; ++l) {
+            a.k[l] = params + m->o_k[l]; a.gamma[l] = params + m->o_g[l]; a.beta[l] = params + m->o_b[l];
+            a.mm[l] = state + m->o_mm[l]; a.mv[l] = state + m->o_mv[l];
+        }
+        a.dk = params + m->o_dk; a.db = params + m->o_db;
+        return a;
+    }
+    template <class Obs>
+    static __device__ __forceinline__ void forward(const Args &a, const float *f, Smem &sm, Obs &obs);
 };
 
-struct CalSmem {
-    float x0[kH0 * kW0], a1[15 * 10 * kC1], a2[7 * 5 * kC2], a3[4 * 3 * kC3], a4[kFlat];
-};
-
-__device__ __forceinline__ float bn_relu6(float y, const CalArgs &a, int l, int c)
-{
-    const float gm = a.gamma[l][c] / sqrtf(a.mv[l][c] + 1e-3f);
-    const float v = (y - a.mm[l][c]) * gm + a.beta[l][c];
-    return fminf(fmaxf(v, 0.f), 6.f);
-}
-
-// obs(t, v): v >= 0 is |x| for t0, the activation itself for t1..t5.  Ends without a barrier after the Dense stage (it reads a4 only).
+// obs(t, v): v >= 0 is |x| for t0, the activation itself for t1..t5
 template <class Obs>
-__device__ __forceinline__ void cal_forward(const CalArgs &a, const float *f, CalSmem &sm, Obs &obs)
+__device__ __forceinline__ void CnnCal::forward(const Args &a, const float *f, Smem &sm, Obs &obs)
 {
     const int tid = threadIdx.x;
     float *x0 = sm.x0, *a1 = sm.a1, *a2 = sm.a2, *a3 = sm.a3, *a4 = sm.a4;
@@ -407,67 +387,30 @@ __device__ __forceinline__ void cal_forward(const CalArgs &a, const float *f, Ca
         obs(4, best);
     }
     __syncthreads();
-    // Dense(128) + ReLU6
-    for (int o = tid; o < kD; o += 256) {
-        float s = a.db[o];
-#pragma unroll 4
-        for (int k = 0; k < kFlat; ++k) s += a4[k] * a.dk[k * kD + o];
-        obs(5, fminf(fmaxf(s, 0.f), 6.f));
-    }
-}
-
-__global__ __launch_bounds__(256) void qcalibrate_kernel(CalArgs a)
-{
-    __shared__ CalSmem sm;
-    __shared__ int red[KWS_QUANT_TENSORS];
-    const int tid = threadIdx.x;
-    CalMax<KWS_QUANT_TENSORS> obs;
-    if (tid < KWS_QUANT_TENSORS) red[tid] = 0;
-    cal_forward(a, a.feat + (long)blockIdx.x * (kH0 * kW0), sm, obs);
-    // non-negative floats order like their bit patterns as int (a NaN's pattern would win: the host rejects it)
-#pragma unroll
-    for (int t = 0; t < KWS_QUANT_TENSORS; ++t) atomicMax(&red[t], __float_as_int(obs.mx[t]));
-    __syncthreads();
-    if (tid < KWS_QUANT_TENSORS) atomicMax(reinterpret_cast<int *>(a.amax) + tid, red[tid]);
-}
-
-struct HistArgs {
-    CalArgs c;
-    int B;
-    float k[KWS_QUANT_TENSORS];       // 2048 / amax_t, 0 for a tensor that gets no counts
-    unsigned long long *hist;
-};
-
-// persistent: block b counts clips b, b + grid, ... into its LDS histograms (48 KB beside the forward's 20.6 KB: two blocks per CU)
-// and adds its nonzero bins to hist once at its end
-__global__ __launch_bounds__(256) void qhist_kernel(HistArgs g)
-{
-    __shared__ CalSmem sm;
-    __shared__ unsigned cnt[KWS_QUANT_TENSORS * KWS_QUANT_HIST_BINS];
-    for (int i = threadIdx.x; i < KWS_QUANT_TENSORS * KWS_QUANT_HIST_BINS; i += 256) cnt[i] = 0u;
-    CalHist<KWS_QUANT_TENSORS> obs;
-    obs.cnt = cnt;
-#pragma unroll
-    for (int t = 0; t < KWS_QUANT_TENSORS; ++t) obs.k[t] = g.k[t];
-    for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
-        __syncthreads();      // the previous clip's Dense stage has read a4; the counters are cleared
-        cal_forward(g.c, g.c.feat + (long)b * (kH0 * kW0), sm, obs);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < KWS_QUANT_TENSORS * KWS_QUANT_HIST_BINS; i += 256) {
-        const unsigned c = cnt[i];
-        if (c) atomicAdd(g.hist + i, (unsigned long long)c);
-    }
+    cal_dense(a, a4, 5, obs);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-int check_model(const kws_model *m)
+int check_cnn_geometry(const kws_model *m, int kind, const char *what)
 {
     if (!m) return fail(KWS_ERR_INVALID, "null model");
-    if (m->kind != KWS_SIMPLE_CNN) return fail(KWS_ERR_UNSUPPORTED, "int8 quantization covers simple_cnn only (model kind %d)", m->kind);
+    if (m->kind != kind) return fail(KWS_ERR_UNSUPPORTED, "%s only (model kind %d)", what, m->kind);
     if (m->n_features != kH0 || m->feature_size != kW0)
         return fail(KWS_ERR_UNSUPPORTED, "int8 quantization covers the default %dx%d geometry, not %dx%d", kH0, kW0, m->n_features, m->feature_size);
     if (m->C > KWS_QUANT_MAX_CLASSES) return fail(KWS_ERR_UNSUPPORTED, "int8 quantization covers up to %d classes, not %d", KWS_QUANT_MAX_CLASSES, m->C);
+    return KWS_OK;
+}
+int check_model(const kws_model *m) { return check_cnn_geometry(m, KWS_SIMPLE_CNN, "int8 quantization covers simple_cnn"); }
+
+int check_method_amax(int method, const float *amax_host, int T)
+{
+    if (method != KWS_QUANT_MAX && method != KWS_QUANT_RELU6 && method != KWS_QUANT_KL)
+        return fail(KWS_ERR_INVALID, "unknown quantization method %d", method);
+    for (int t = 0; t < T; ++t) {
+        const double v = amax_host[t];
+        if (!std::isfinite(v) || v < 0.0) return fail(KWS_ERR_INVALID, "calibrated maximum of t%d is %g (must be finite and >= 0)", t, v);
+    }
+    if (amax_host[0] == 0.f) return fail(KWS_ERR_INVALID, "calibrated max|x| of the features is 0");
     return KWS_OK;
 }
 
@@ -497,6 +440,31 @@ void pack_frags(const int8_t *W, int K, int N, int S, int NCT, std::vector<int8_
                     const int k = 64 * s + 16 * (l >> 4) + j, col = 16 * ct + (l & 15);
                     if (k < K && col < N) out[(((size_t)s * NCT + ct) * 64 + l) * 16 + j] = W[(size_t)k * N + col];
                 }
+}
+
+size_t QBlob::put(const void *p, size_t n)
+{
+    const size_t off = al256(img.size());
+    img.resize(off + n);
+    std::memcpy(img.data() + off, p, n);
+    return off;
+}
+
+unsigned char *QBlob::upload(kws_qmodel *qm) const
+{
+    if (hipGetDevice(&qm->device) != hipSuccess || hipMalloc(&qm->blob, img.size()) != hipSuccess) {
+        (void)hipGetLastError();
+        qm->blob = nullptr;
+        fail(KWS_ERR_HIP, "no HIP device / out of device memory for the quantized model");
+        return nullptr;
+    }
+    if (hipMemcpy(qm->blob, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(qm->blob);
+        qm->blob = nullptr;
+        fail(KWS_ERR_HIP, "upload of the quantized model failed");
+        return nullptr;
+    }
+    return static_cast<unsigned char *>(qm->blob);
 }
 
 int hist_grid(const void *kernel, int B)
@@ -572,19 +540,7 @@ int kws_model_calibrate(kws_model *m, const float *feat, int B, const float *par
     (void)ws; (void)ws_bytes;
     int rc = check_model(m);
     if (rc) return rc;
-    if (B < 0) return fail(KWS_ERR_INVALID, "batch must be >= 0");
-    if (B == 0) return KWS_OK;
-    if (!feat || !params || !state || !amax) return fail(KWS_ERR_INVALID, "null argument");
-    CalArgs a{};
-    a.feat = feat;
-    for (int l = 0; l < 4; ++l) {
-        a.k[l] = params + m->o_k[l]; a.gamma[l] = params + m->o_g[l]; a.beta[l] = params + m->o_b[l];
-        a.mm[l] = state + m->o_mm[l]; a.mv[l] = state + m->o_mv[l];
-    }
-    a.dk = params + m->o_dk; a.db = params + m->o_db; a.amax = amax;
-    KWS_LAUNCH("qcalibrate_kernel", qcalibrate_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    KWS_LAUNCH_CHECK("calibration");
-    return KWS_OK;
+    return cal_max_launch<CnnCal>("qcalibrate_kernel", "calibration", m, feat, B, params, state, amax, static_cast<hipStream_t>(stream));
 }
 
 int kws_model_calibrate_hist(kws_model *m, const float *feat, int B, const float *params, const float *state, void *ws, size_t ws_bytes,
@@ -595,26 +551,8 @@ int kws_model_calibrate_hist(kws_model *m, const float *feat, int B, const float
         return lite_calibrate_hist(m, feat, B, params, state, amax_host, hist, static_cast<hipStream_t>(stream));
     int rc = check_model(m);
     if (rc) return rc;
-    if (B < 0) return fail(KWS_ERR_INVALID, "batch must be >= 0");
-    if (B == 0) return KWS_OK;
-    if (!feat || !params || !state || !amax_host || !hist) return fail(KWS_ERR_INVALID, "null argument");
-    float k[KWS_QUANT_TENSORS];
-    rc = hist_factors(amax_host, KWS_QUANT_TENSORS, k);
-    if (rc) return rc;
-    HistArgs g{};
-    g.c.feat = feat;
-    for (int l = 0; l < 4; ++l) {
-        g.c.k[l] = params + m->o_k[l]; g.c.gamma[l] = params + m->o_g[l]; g.c.beta[l] = params + m->o_b[l];
-        g.c.mm[l] = state + m->o_mm[l]; g.c.mv[l] = state + m->o_mv[l];
-    }
-    g.c.dk = params + m->o_dk; g.c.db = params + m->o_db;
-    g.B = B;
-    for (int t = 0; t < KWS_QUANT_TENSORS; ++t) g.k[t] = k[t];
-    g.hist = reinterpret_cast<unsigned long long *>(hist);
-    KWS_LAUNCH("qhist_kernel", qhist_kernel, dim3(hist_grid(reinterpret_cast<const void *>(qhist_kernel), B)), dim3(256), 0,
-               static_cast<hipStream_t>(stream), g);
-    KWS_LAUNCH_CHECK("calibration histograms");
-    return KWS_OK;
+    return cal_hist_launch<CnnCal>("qhist_kernel", "calibration histograms", m, feat, B, params, state, amax_host, hist,
+                                   static_cast<hipStream_t>(stream));
 }
 
 int kws_quant_kl_ranges(const uint64_t *hist_host, const float *amax_host, int T, float *ranges_out, int32_t *bins_out)
@@ -649,15 +587,13 @@ int kws_quantize_simple_cnn(const kws_model *m, const float *params_host, const 
     int rc = check_model(m);
     if (rc) return rc;
     if (!params_host || !state_host || !amax_host || !out) return fail(KWS_ERR_INVALID, "null argument");
-    if (method != KWS_QUANT_MAX && method != KWS_QUANT_RELU6 && method != KWS_QUANT_KL)
-        return fail(KWS_ERR_INVALID, "unknown quantization method %d", method);
+    rc = check_method_amax(method, amax_host, KWS_QUANT_TENSORS);
+    if (rc) return rc;
     double A[KWS_QUANT_TENSORS];
     for (int t = 0; t < KWS_QUANT_TENSORS; ++t) {
         const double v = amax_host[t];
-        if (!std::isfinite(v) || v < 0.0) return fail(KWS_ERR_INVALID, "calibrated maximum of t%d is %g (must be finite and >= 0)", t, v);
         A[t] = t == 0 ? v : method == KWS_QUANT_RELU6 || v == 0.0 ? 6.0 : std::min(v, 6.0);
     }
-    if (A[0] == 0.0) return fail(KWS_ERR_INVALID, "calibrated max|x| of the features is 0");
     std::memset(out, 0, sizeof(*out));
     out->num_classes = m->C;
     out->method = method;
@@ -682,16 +618,7 @@ int kws_quantize_simple_cnn(const kws_model *m, const float *params_host, const 
             Bo[l][c] = (float)(h / s[l + 1]);
         }
     }
-    quantize_weight(params_host + m->o_dk, kFlat, kD, out->dense_w, sw);
-    for (int c = 0; c < kD; ++c) {
-        out->Md[c] = (float)((s[4] * sw[c]) / s[5]);
-        out->Bd[c] = (float)((double)params_host[m->o_db + c] / s[5]);
-    }
-    quantize_weight(params_host + m->o_hk, kD, m->C, out->head_w, sw);
-    for (int c = 0; c < m->C; ++c) {
-        out->Mh[c] = (float)(s[5] * sw[c]);
-        out->head_bias[c] = params_host[m->o_hb + c];
-    }
+    quantize_dense_head(m, params_host, s[4], s[5], out);
     return KWS_OK;
 }
 
@@ -718,26 +645,16 @@ int kws_qmodel_create(const kws_model *m, const kws_qsimple_cnn *q, kws_qmodel *
     pack_frags(q->conv_w4, 9 * kC3, kC4, kS4, kN4, f4);
     pack_frags(q->dense_w, kFlat, kD, kSd, kNd, fd);
     pack_frags(q->head_w, kD, m->C, kSh, kNh, fh);
-    std::vector<unsigned char> img;
-    auto put = [&img](const void *p, size_t n) { const size_t off = al256(img.size()); img.resize(off + n); std::memcpy(img.data() + off, p, n); return off; };
-    const size_t o1 = put(w1.data(), w1.size() * 4), o2 = put(f2.data(), f2.size()), o3 = put(f3.data(), f3.size()),
-                 o4 = put(f4.data(), f4.size()), od = put(fd.data(), fd.size()), oh = put(fh.data(), fh.size()),
-                 oe = put(ep, sizeof(float) * kEpCount);
+    QBlob img;
+    const size_t o1 = img.put(w1.data(), w1.size() * 4), o2 = img.put(f2.data(), f2.size()), o3 = img.put(f3.data(), f3.size()),
+                 o4 = img.put(f4.data(), f4.size()), od = img.put(fd.data(), fd.size()), oh = img.put(fh.data(), fh.size()),
+                 oe = img.put(ep, sizeof(float) * kEpCount);
     auto *qm = new kws_qmodel();
     qm->kind = KWS_SIMPLE_CNN;
     qm->C = m->C;
     qm->inv_s0 = q->inv_s0;
-    if (hipGetDevice(&qm->device) != hipSuccess || hipMalloc(&qm->blob, img.size()) != hipSuccess) {
-        (void)hipGetLastError();
-        delete qm;
-        return fail(KWS_ERR_HIP, "no HIP device / out of device memory for the quantized model");
-    }
-    if (hipMemcpy(qm->blob, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(qm->blob);
-        delete qm;
-        return fail(KWS_ERR_HIP, "upload of the quantized model failed");
-    }
-    auto *b = static_cast<unsigned char *>(qm->blob);
+    const unsigned char *b = img.upload(qm);
+    if (!b) { delete qm; return KWS_ERR_HIP; }
     qm->w1 = reinterpret_cast<const int32_t *>(b + o1);
     qm->f2 = reinterpret_cast<const i32x4 *>(b + o2);
     qm->f3 = reinterpret_cast<const i32x4 *>(b + o3);

@@ -1,6 +1,6 @@
 // csrc/kws_quant_lite.hip -- int8 post-training quantization of simple_cnn_lite (include/kws.h: kws_model_calibrate_lite,
-// kws_quantize_simple_cnn_lite, kws_qmodel_create_lite; kws_qmodel_forward dispatches here): the calibration kernel, the host quantizer
-// and the int8 forward, features to probabilities in ONE kernel.
+// kws_quantize_simple_cnn_lite, kws_qmodel_create_lite; kws_qmodel_forward dispatches here): the per-clip fp32 forward the calibration
+// kernels of kws_quant.h run, the host quantizer and the int8 forward, features to probabilities in ONE kernel.
 //
 // The forward (lite_qforward_kernel) follows qforward_kernel (kws_quant.hip): a block of 256 threads owns kG = 8 clips for the whole
 // network, every activation an int8 code in LDS, the maps a 3 x 3 stage reads stored haloed ([clip][row + 1][col + 1][channel], halo
@@ -17,6 +17,7 @@
 //            accumulator registers of a lane are one pool window and pooling is a max over registers (stage 2 as conv2, stage 4 as
 //            conv4 of the simple_cnn kernel); stage 3 rows are (clip, output position)
 //   Dense, head, softmax, arg-max: those of qforward_kernel
+//   t0 and the pooled epilogue of a stage-4 accumulator tile are the functions of kws_quant_fwd.h both kernels call
 // LDS: two regions reused as stages die: R0 = a1 -> a2 -> a3 -> a4 / d / logits, R1 = t0 -> u2 -> u3 -> u4 (kLLds = 44 544 B, three
 // blocks per CU).  Weights and constants are packed by kws_qmodel_create_lite and read from global memory (L2-resident, 56 KB).
 #include <cmath>
@@ -24,31 +25,23 @@
 #include <cstring>
 #include <vector>
 
-#include "kws_common.h"
-#include "kws_model_types.h"
-#include "kws_quant.h"
+#include "kws_quant_fwd.h"
 
 namespace kws {
 namespace q8 {
 namespace {
 
-constexpr int kG = 8;                   // clips per block
-constexpr int kThreads = 256;           // four waves
-constexpr int kL1 = 16, kL2 = 32, kL3 = 64, kL4 = 128;
-constexpr int kXW = kW0 + 2, kXClip = (kH0 + 2) * kXW;                    // 32 x 22 haloed features: 704 B
-constexpr int kA1W = 12, kA1Pix = 17 * kA1W, kA1Clip = kA1Pix * kL1;      // 15 x 10 x 16 haloed: 3264 B
-constexpr int kU2Rows = 36 * 4, kU2Clip = kU2Rows * kL1;                  // (window 0..35, pixel 0..3) x 16: 2304 B (window 35 unused)
-constexpr int kA2W = 7, kA2Pix = 9 * kA2W, kA2Clip = kA2Pix * kL2;        // 7 x 5 x 32 haloed: 2016 B
-constexpr int kU3Clip = 12 * kL2;                                         // 4 x 3 positions x 32: 384 B
-constexpr int kA3W = 5, kA3Pix = 6 * kA3W, kA3Clip = kA3Pix * kL3;        // 4 x 3 x 64 haloed: 1920 B
-constexpr int kU4Clip = 8 * kL3;                                          // (window 0..1, pixel 0..3) x 64: 512 B
+// the depthwise outputs, rows of the pointwise GEMMs (the haloed a_l maps are those of kws_quant_fwd.h)
+constexpr int kU2Rows = 36 * 4, kU2Clip = kU2Rows * kC1;                  // (window 0..35, pixel 0..3) x 16: 2304 B (window 35 unused)
+constexpr int kU3Clip = 12 * kC2;                                         // 4 x 3 positions x 32: 384 B
+constexpr int kU4Clip = 8 * kC3;                                          // (window 0..1, pixel 0..3) x 64: 512 B
 constexpr int kR1 = kG * kA1Clip;                                         // R0 = [0, kR1), R1 = [kR1, kLLds)
 constexpr int kOffA1 = 0, kOffA2 = 0, kOffA3 = 0, kOffA4 = 0, kOffD = kG * kFlat, kOffLG = kOffD + kG * kD, kOffMS = kOffLG + 4 * kG * kHead;
 constexpr int kOffX = kR1, kOffU2 = kR1, kOffU3 = kR1, kOffU4 = kR1;
 constexpr int kLLds = kR1 + kG * kU2Clip;
 static_assert(kG * kA2Clip <= kR1 && kG * kA3Clip <= kR1 && kOffMS + 8 * kG <= kR1, "R0");
 static_assert(kG * kXClip <= kG * kU2Clip && kG * kU3Clip <= kG * kU2Clip && kG * kU4Clip <= kG * kU2Clip, "R1");
-static_assert(kA1Clip % 16 == 0 && kA2Clip % 16 == 0 && kA3Clip % 16 == 0 && kR1 % 16 == 0, "16-byte reads");
+static_assert(kR1 % 16 == 0, "16-byte reads");
 
 // u = clamp(rint((float)dacc * Mu), -127, 127)
 __device__ __forceinline__ int requant_u(int acc, float Mu)
@@ -98,19 +91,7 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
     const i32x4 zero4 = {0, 0, 0, 0};
 
     // ---- t0: codes of the features, halo = 0; a1's halo = 0 ----
-    for (int i = tid; i < kG * kXClip; i += kThreads) {
-        const int c = i / kXClip, p = i - c * kXClip, y = p / kXW - 1, x = p % kXW - 1;
-        int code = 0;
-        if (y >= 0 && y < kH0 && x >= 0 && x < kW0 && b0 + c < g.B) {
-            const float v = g.feat[(long)(b0 + c) * (kH0 * kW0) + y * kW0 + x];
-            code = (int)fminf(fmaxf(rintf(__fmul_rn(v, g.inv_s0)), -127.f), 127.f);
-        }
-        X[i] = (int8_t)code;
-    }
-    for (int i = tid; i < kG * kA1Pix; i += kThreads) {
-        const int p = i % kA1Pix, y = p / kA1W, x = p % kA1W;
-        if (y == 0 || y > 15 || x == 0 || x > 10) *reinterpret_cast<i32x4 *>(A1 + i * kL1) = zero4;
-    }
+    fwd_prologue(g.feat, g.B, b0, g.inv_s0, X, A1);
     __syncthreads();
 
     // ---- stage 1: depthwise (one channel) + pointwise (K = 1) + bias + BN + ReLU6 + pool, one thread per (clip, pool window) ----
@@ -136,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
             }
             int out[4] = {0, 0, 0, 0};
 #pragma unroll
-            for (int co = 0; co < kL1; ++co) {
+            for (int co = 0; co < kC1; ++co) {
                 const int wq = g.pw1[co], b = bq[kLBq1 + co];
                 const float M = ep[kLEpM1 + co], Bq = ep[kLEpB1 + co];
                 int best = 0;
@@ -145,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
                 out[co >> 2] |= best << (8 * (co & 3));
             }
             const i32x4 o = {out[0], out[1], out[2], out[3]};
-            *reinterpret_cast<i32x4 *>(A1 + c * kA1Clip + ((wy + 1) * kA1W + wx + 1) * kL1) = o;
+            *reinterpret_cast<i32x4 *>(A1 + c * kA1Clip + ((wy + 1) * kA1W + wx + 1) * kC1) = o;
         }
     }
     __syncthreads();
@@ -154,8 +135,8 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
     for (int t = tid; t < kG * 140 * 4; t += kThreads) {
         const int c = t / 560, r = t - c * 560, px = r >> 2, wd = r & 3, y = px / 10, x = px - y * 10;
         const int row = 4 * ((y >> 1) * 5 + (x >> 1)) + 2 * (y & 1) + (x & 1);
-        *reinterpret_cast<int *>(U2 + c * kU2Clip + row * kL1 + 4 * wd) =
-            dw_word(A1 + c * kA1Clip + (y * kA1W + x) * kL1 + 4 * wd, kA1W * kL1, kL1, g.dw2 + 9 * wd, ep + kLEpMu2 + 4 * wd);
+        *reinterpret_cast<int *>(U2 + c * kU2Clip + row * kC1 + 4 * wd) =
+            dw_word(A1 + c * kA1Clip + (y * kA1W + x) * kC1 + 4 * wd, kA1W * kC1, kC1, g.dw2 + 9 * wd, ep + kLEpMu2 + 4 * wd);
     }
     __syncthreads();
 
@@ -172,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
             const int c = tile / 9, t = tile - c * 9;
             const int m = min(16 * t + li, 139);          // the 36th window (padding) re-reads the 35th's last pixel
             i32x4 a = zero4;
-            if (q == 0) a = *reinterpret_cast<const i32x4 *>(U2 + c * kU2Clip + m * kL1);
+            if (q == 0) a = *reinterpret_cast<const i32x4 *>(U2 + c * kU2Clip + m * kC1);
             i32x4 acc[2];
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
@@ -188,15 +169,15 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
                     int best = 0;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) best = max(best, requant(acc[ct][r], M, Bq));
-                    A2[c * kA2Clip + ((w / 5 + 1) * kA2W + w % 5 + 1) * kL2 + ch] = (int8_t)best;
+                    A2[c * kA2Clip + ((w / 5 + 1) * kA2W + w % 5 + 1) * kC2 + ch] = (int8_t)best;
                 }
             }
         }
         for (int i = tid; i < kG * kA2Pix; i += kThreads) {
             const int p = i % kA2Pix, y = p / kA2W, x = p % kA2W;
             if (y == 0 || y > 7 || x == 0 || x > 5) {
-                *reinterpret_cast<i32x4 *>(A2 + i * kL2) = zero4;
-                *reinterpret_cast<i32x4 *>(A2 + i * kL2 + 16) = zero4;
+                *reinterpret_cast<i32x4 *>(A2 + i * kC2) = zero4;
+                *reinterpret_cast<i32x4 *>(A2 + i * kC2 + 16) = zero4;
             }
         }
     }
@@ -205,8 +186,8 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
     // ---- depthwise 3 (stride 2, padding 1 / 1): 4 x 3 positions x 8 words (u2 is dead) ----
     for (int t = tid; t < kG * 12 * 8; t += kThreads) {
         const int c = t / 96, r = t - c * 96, pos = r >> 3, wd = r & 7, oy = pos / 3, ox = pos - oy * 3;
-        *reinterpret_cast<int *>(U3 + c * kU3Clip + pos * kL2 + 4 * wd) =
-            dw_word(A2 + c * kA2Clip + (2 * oy * kA2W + 2 * ox) * kL2 + 4 * wd, kA2W * kL2, kL2, g.dw3 + 9 * wd, ep + kLEpMu3 + 4 * wd);
+        *reinterpret_cast<int *>(U3 + c * kU3Clip + pos * kC2 + 4 * wd) =
+            dw_word(A2 + c * kA2Clip + (2 * oy * kA2W + 2 * ox) * kC2 + 4 * wd, kA2W * kC2, kC2, g.dw3 + 9 * wd, ep + kLEpMu3 + 4 * wd);
     }
     __syncthreads();
 
@@ -219,19 +200,19 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
         const float M = ep[kLEpM3 + ch], Bq = ep[kLEpB3 + ch];
         for (int t = 0; t < kG * 12 / 16; ++t) {
             i32x4 a = zero4;
-            if (q < 2) a = *reinterpret_cast<const i32x4 *>(U3 + (16 * t + li) * kL2 + 16 * q);
+            if (q < 2) a = *reinterpret_cast<const i32x4 *>(U3 + (16 * t + li) * kC2 + 16 * q);
             const i32x4 acc = mfma_i8(a, bw, bias);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int mo = 16 * t + 4 * q + r, co = mo / 12, po = mo - co * 12;
-                A3[co * kA3Clip + ((po / 3 + 1) * kA3W + po % 3 + 1) * kL3 + ch] = (int8_t)requant(max(acc[r], 0), M, Bq);
+                A3[co * kA3Clip + ((po / 3 + 1) * kA3W + po % 3 + 1) * kC3 + ch] = (int8_t)requant(max(acc[r], 0), M, Bq);
             }
         }
         for (int i = tid; i < kG * kA3Pix; i += kThreads) {
             const int p = i % kA3Pix, y = p / kA3W, x = p % kA3W;
             if (y == 0 || y > 4 || x == 0 || x > 3)
 #pragma unroll
-                for (int u = 0; u < 4; ++u) *reinterpret_cast<i32x4 *>(A3 + i * kL3 + 16 * u) = zero4;
+                for (int u = 0; u < 4; ++u) *reinterpret_cast<i32x4 *>(A3 + i * kC3 + 16 * u) = zero4;
         }
     }
     __syncthreads();
@@ -239,14 +220,13 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
     // ---- depthwise 4: the 4 x 2 positions pooling keeps, rows (window, pixel in window) x 16 words (u3 is dead) ----
     for (int t = tid; t < kG * 8 * 16; t += kThreads) {
         const int c = t >> 7, r = t & 127, pos = r >> 4, wd = r & 15, y = 2 * (pos >> 2) + ((pos >> 1) & 1), x = pos & 1;
-        *reinterpret_cast<int *>(U4 + c * kU4Clip + pos * kL3 + 4 * wd) =
-            dw_word(A3 + c * kA3Clip + (y * kA3W + x) * kL3 + 4 * wd, kA3W * kL3, kL3, g.dw4 + 9 * wd, ep + kLEpMu4 + 4 * wd);
+        *reinterpret_cast<int *>(U4 + c * kU4Clip + pos * kC3 + 4 * wd) =
+            dw_word(A3 + c * kA3Clip + (y * kA3W + x) * kC3 + 4 * wd, kA3W * kC3, kC3, g.dw4 + 9 * wd, ep + kLEpMu4 + 4 * wd);
     }
     __syncthreads();
 
     // ---- pointwise 4 (K = 64) + bias + relu + BN + ReLU6 + pool: wave = column tiles 2 wave, 2 wave + 1 (a3 is dead) ----
     {
-        constexpr int kT = kG * 8 / 16;         // row tiles: (clip, window, pixel)
         i32x4 bw[2], bias[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -254,10 +234,10 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
             const int b = bq[kLBq4 + 16 * (2 * wave + u) + li];
             bias[u] = i32x4{b, b, b, b};
         }
-        i32x4 acc[kT][2];
+        i32x4 acc[kT4][2];
 #pragma unroll
-        for (int t = 0; t < kT; ++t) {
-            const i32x4 a = *reinterpret_cast<const i32x4 *>(U4 + (16 * t + li) * kL3 + 16 * q);
+        for (int t = 0; t < kT4; ++t) {
+            const i32x4 a = *reinterpret_cast<const i32x4 *>(U4 + (16 * t + li) * kC3 + 16 * q);
             acc[t][0] = mfma_i8(a, bw[0], bias[0]);
             acc[t][1] = mfma_i8(a, bw[1], bias[1]);
         }
@@ -266,13 +246,7 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
             const int ch = 16 * (2 * wave + u) + li;
             const float M = ep[kLEpM4 + ch], Bq = ep[kLEpB4 + ch];
 #pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                const int p = 4 * t + q, c = p >> 1, wy = p & 1;
-                int best = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) best = max(best, requant(max(acc[t][u][r], 0), M, Bq));
-                A4[c * kFlat + wy * kL4 + ch] = (int8_t)best;
-            }
+            for (int t = 0; t < kT4; ++t) fwd_pool4(acc[t][u], t, q, ch, M, Bq, A4);
         }
     }
     __syncthreads();
@@ -340,21 +314,8 @@ __global__ __launch_bounds__(kThreads) void lite_qforward_kernel(LQFwdArgs g)
         }
 }
 
-// ---- calibration: the fp32 inference forward of one clip (plain loops) for the max pass (one block per clip, max-reduced into amax)
-// and the histogram pass (persistent, LDS counts): one function, two observers (kws_quant.h) ------------------------------------------
-struct LCalArgs {
-    const float *feat;
-    const float *dwk[4], *pwk[4], *pwb[4], *gamma[4], *beta[4], *mm[4], *mv[4];
-    const float *dk, *db;
-    float *amax;
-};
-
-__device__ __forceinline__ float lbn_relu6(float y, const LCalArgs &a, int l, int c)
-{
-    const float gm = a.gamma[l][c] / sqrtf(a.mv[l][c] + 1e-3f);
-    const float v = (y - a.mm[l][c]) * gm + a.beta[l][c];
-    return fminf(fmaxf(v, 0.f), 6.f);
-}
+// ---- calibration: the fp32 inference forward of one clip (plain loops), the network the calibration kernels and launchers of
+// kws_quant.h run for simple_cnn_lite (launch labels lite_qcalibrate_kernel / lite_qhist_kernel) --------------------------------------
 
 // depthwise 3 x 3 output (oy, ox, channel c) of an H x W x C map, 'same' padding 1 before (stride 1 or 2)
 __device__ float ldw(const float *in, int H, int W, int C, const float *k, int oy, int ox, int c, int stride)
@@ -377,14 +338,35 @@ __device__ float lpw(const float *u, int CI, const float *k, const float *b, int
     return relu ? fmaxf(s, 0.f) : s;
 }
 
-struct LCalSmem {
-    float x0[kH0 * kW0], u1[kH0 * kW0], a1[150 * kL1], u2[150 * kL1], a2[35 * kL2], u3[12 * kL2], a3[12 * kL3], u4[12 * kL3], a4[kFlat];
+struct LiteCal {
+    static constexpr int T = KWS_QLITE_TENSORS;
+    struct Args {
+        const float *feat;
+        const float *dwk[4], *pwk[4], *pwb[4], *gamma[4], *beta[4], *mm[4], *mv[4];
+        const float *dk, *db;
+        float *amax;
+    };
+    struct Smem {
+        float x0[kH0 * kW0], u1[kH0 * kW0], a1[150 * kC1], u2[150 * kC1], a2[35 * kC2], u3[12 * kC2], a3[12 * kC3], u4[12 * kC3], a4[kFlat];
+    };
+    static Args args(const kws_model *m, const float *params, const float *state)
+    {
+        Args a{};
+        for (int l = 0; l < 4; ++l) {
+            a.dwk[l] = params + m->o_dwk[l]; a.pwk[l] = params + m->o_pwk[l]; a.pwb[l] = params + m->o_pwb[l];
+            a.gamma[l] = params + m->o_g[l]; a.beta[l] = params + m->o_b[l];
+            a.mm[l] = state + m->o_mm[l]; a.mv[l] = state + m->o_mv[l];
+        }
+        a.dk = params + m->o_dk; a.db = params + m->o_db;
+        return a;
+    }
+    template <class Obs>
+    static __device__ __forceinline__ void forward(const Args &a, const float *f, Smem &sm, Obs &obs);
 };
 
-// the fp32 forward of one clip; obs(t, v) as in kws_quant.h (|u_l| for the signed depthwise outputs).  Ends without a barrier after
-// the Dense stage (it reads a4 only).
+// obs(t, v) as in kws_quant.h (|u_l| for the signed depthwise outputs)
 template <class Obs>
-__device__ __forceinline__ void lite_cal_forward(const LCalArgs &a, const float *f, LCalSmem &sm, Obs &obs)
+__device__ __forceinline__ void LiteCal::forward(const Args &a, const float *f, Smem &sm, Obs &obs)
 {
     const int tid = threadIdx.x;
     float *x0 = sm.x0, *u1 = sm.u1, *a1 = sm.a1, *u2 = sm.u2, *a2 = sm.a2, *u3 = sm.u3, *a3 = sm.a3, *u4 = sm.u4, *a4 = sm.a4;
@@ -399,124 +381,67 @@ __device__ __forceinline__ void lite_cal_forward(const LCalArgs &a, const float 
         obs(1, fabsf(u1[o]));
     }
     __syncthreads();
-    for (int o = tid; o < 150 * kL1; o += 256) {      // pointwise 1 + BN + ReLU6 + pool: 15 x 10 x 16
-        const int w = o / kL1, co = o % kL1, wy = w / 10, wx = w % 10;
+    for (int o = tid; o < 150 * kC1; o += 256) {      // pointwise 1 + BN + ReLU6 + pool: 15 x 10 x 16
+        const int w = o / kC1, co = o % kC1, wy = w / 10, wx = w % 10;
         float best = 0.f;
         for (int p = 0; p < 4; ++p) {
             const int y = 2 * wy + (p >> 1), x = 2 * wx + (p & 1);
-            best = fmaxf(best, lbn_relu6(lpw(u1 + y * kW0 + x, 1, a.pwk[0], a.pwb[0], kL1, co, false), a, 0, co));
+            best = fmaxf(best, bn_relu6(lpw(u1 + y * kW0 + x, 1, a.pwk[0], a.pwb[0], kC1, co, false), a, 0, co));
         }
         a1[o] = best;
         obs(2, best);
     }
     __syncthreads();
-    for (int o = tid; o < 150 * kL1; o += 256) {
-        u2[o] = ldw(a1, 15, 10, kL1, a.dwk[1], (o / kL1) / 10, (o / kL1) % 10, o % kL1, 1);
+    for (int o = tid; o < 150 * kC1; o += 256) {
+        u2[o] = ldw(a1, 15, 10, kC1, a.dwk[1], (o / kC1) / 10, (o / kC1) % 10, o % kC1, 1);
         obs(3, fabsf(u2[o]));
     }
     __syncthreads();
-    for (int o = tid; o < 35 * kL2; o += 256) {       // pointwise 2 + BN + ReLU6 + pool: 7 x 5 x 32
-        const int w = o / kL2, co = o % kL2, wy = w / 5, wx = w % 5;
+    for (int o = tid; o < 35 * kC2; o += 256) {       // pointwise 2 + BN + ReLU6 + pool: 7 x 5 x 32
+        const int w = o / kC2, co = o % kC2, wy = w / 5, wx = w % 5;
         float best = 0.f;
         for (int p = 0; p < 4; ++p) {
             const int y = 2 * wy + (p >> 1), x = 2 * wx + (p & 1);
-            best = fmaxf(best, lbn_relu6(lpw(u2 + (y * 10 + x) * kL1, kL1, a.pwk[1], a.pwb[1], kL2, co, false), a, 1, co));
+            best = fmaxf(best, bn_relu6(lpw(u2 + (y * 10 + x) * kC1, kC1, a.pwk[1], a.pwb[1], kC2, co, false), a, 1, co));
         }
         a2[o] = best;
         obs(4, best);
     }
     __syncthreads();
-    for (int o = tid; o < 12 * kL2; o += 256) {       // depthwise 3, stride 2: 4 x 3 x 32
-        u3[o] = ldw(a2, 7, 5, kL2, a.dwk[2], (o / kL2) / 3, (o / kL2) % 3, o % kL2, 2);
+    for (int o = tid; o < 12 * kC2; o += 256) {       // depthwise 3, stride 2: 4 x 3 x 32
+        u3[o] = ldw(a2, 7, 5, kC2, a.dwk[2], (o / kC2) / 3, (o / kC2) % 3, o % kC2, 2);
         obs(5, fabsf(u3[o]));
     }
     __syncthreads();
-    for (int o = tid; o < 12 * kL3; o += 256) {
-        const float v = lbn_relu6(lpw(u3 + (o / kL3) * kL2, kL2, a.pwk[2], a.pwb[2], kL3, o % kL3, true), a, 2, o % kL3);
+    for (int o = tid; o < 12 * kC3; o += 256) {
+        const float v = bn_relu6(lpw(u3 + (o / kC3) * kC2, kC2, a.pwk[2], a.pwb[2], kC3, o % kC3, true), a, 2, o % kC3);
         a3[o] = v;
         obs(6, v);
     }
     __syncthreads();
-    for (int o = tid; o < 12 * kL3; o += 256) {
-        u4[o] = ldw(a3, 4, 3, kL3, a.dwk[3], (o / kL3) / 3, (o / kL3) % 3, o % kL3, 1);
+    for (int o = tid; o < 12 * kC3; o += 256) {
+        u4[o] = ldw(a3, 4, 3, kC3, a.dwk[3], (o / kC3) / 3, (o / kC3) % 3, o % kC3, 1);
         obs(7, fabsf(u4[o]));
     }
     __syncthreads();
     for (int o = tid; o < kFlat; o += 256) {          // pointwise 4 + relu + BN + ReLU6 + pool: 2 x 1 x 128
-        const int wy = o / kL4, co = o % kL4;
+        const int wy = o / kC4, co = o % kC4;
         float best = 0.f;
         for (int p = 0; p < 4; ++p) {
             const int y = 2 * wy + (p >> 1), x = p & 1;
-            best = fmaxf(best, lbn_relu6(lpw(u4 + (y * 3 + x) * kL3, kL3, a.pwk[3], a.pwb[3], kL4, co, true), a, 3, co));
+            best = fmaxf(best, bn_relu6(lpw(u4 + (y * 3 + x) * kC3, kC3, a.pwk[3], a.pwb[3], kC4, co, true), a, 3, co));
         }
         a4[o] = best;
         obs(8, best);
     }
     __syncthreads();
-    for (int o = tid; o < kD; o += 256) {             // Dense(128) + ReLU6
-        float s = a.db[o];
-#pragma unroll 4
-        for (int k = 0; k < kFlat; ++k) s += a4[k] * a.dk[k * kD + o];
-        obs(9, fminf(fmaxf(s, 0.f), 6.f));
-    }
-}
-
-__global__ __launch_bounds__(256) void lite_qcalibrate_kernel(LCalArgs a)
-{
-    __shared__ LCalSmem sm;
-    __shared__ int red[KWS_QLITE_TENSORS];
-    const int tid = threadIdx.x;
-    CalMax<KWS_QLITE_TENSORS> obs;
-    if (tid < KWS_QLITE_TENSORS) red[tid] = 0;
-    lite_cal_forward(a, a.feat + (long)blockIdx.x * (kH0 * kW0), sm, obs);
-    // non-negative floats order like their bit patterns as int (a NaN's pattern would win: the host rejects it)
-#pragma unroll
-    for (int t = 0; t < KWS_QLITE_TENSORS; ++t) atomicMax(&red[t], __float_as_int(obs.mx[t]));
-    __syncthreads();
-    if (tid < KWS_QLITE_TENSORS) atomicMax(reinterpret_cast<int *>(a.amax) + tid, red[tid]);
-}
-
-struct LHistArgs {
-    LCalArgs c;
-    int B;
-    float k[KWS_QLITE_TENSORS];
-    unsigned long long *hist;
-};
-
-// persistent, as qhist_kernel (kws_quant.hip): 80 KB of LDS counts beside the forward's 37.2 KB, one block per CU
-__global__ __launch_bounds__(256) void lite_qhist_kernel(LHistArgs g)
-{
-    __shared__ LCalSmem sm;
-    __shared__ unsigned cnt[KWS_QLITE_TENSORS * KWS_QUANT_HIST_BINS];
-    for (int i = threadIdx.x; i < KWS_QLITE_TENSORS * KWS_QUANT_HIST_BINS; i += 256) cnt[i] = 0u;
-    CalHist<KWS_QLITE_TENSORS> obs;
-    obs.cnt = cnt;
-#pragma unroll
-    for (int t = 0; t < KWS_QLITE_TENSORS; ++t) obs.k[t] = g.k[t];
-    for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
-        __syncthreads();      // the previous clip's Dense stage has read a4; the counters are cleared
-        lite_cal_forward(g.c, g.c.feat + (long)b * (kH0 * kW0), sm, obs);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < KWS_QLITE_TENSORS * KWS_QUANT_HIST_BINS; i += 256) {
-        const unsigned c = cnt[i];
-        if (c) atomicAdd(g.hist + i, (unsigned long long)c);
-    }
+    cal_dense(a, a4, 9, obs);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-int check_lite(const kws_model *m)
-{
-    if (!m) return fail(KWS_ERR_INVALID, "null model");
-    if (m->kind != KWS_SIMPLE_CNN_LITE)
-        return fail(KWS_ERR_UNSUPPORTED, "the lite int8 entry points cover simple_cnn_lite only (model kind %d)", m->kind);
-    if (m->n_features != kH0 || m->feature_size != kW0)
-        return fail(KWS_ERR_UNSUPPORTED, "int8 quantization covers the default %dx%d geometry, not %dx%d", kH0, kW0, m->n_features, m->feature_size);
-    if (m->C > KWS_QUANT_MAX_CLASSES) return fail(KWS_ERR_UNSUPPORTED, "int8 quantization covers up to %d classes, not %d", KWS_QUANT_MAX_CLASSES, m->C);
-    return KWS_OK;
-}
+int check_lite(const kws_model *m) { return check_cnn_geometry(m, KWS_SIMPLE_CNN_LITE, "the lite int8 entry points cover simple_cnn_lite"); }
 
-constexpr int kCin[4] = {1, kL1, kL2, kL3}, kCout[4] = {kL1, kL2, kL3, kL4};
+constexpr int kCin[4] = {1, kC1, kC2, kC3}, kCout[4] = {kC1, kC2, kC3, kC4};
 
 static_assert(offsetof(kws_qsimple_cnn_lite, head_bias) - offsetof(kws_qsimple_cnn_lite, Mu1) == sizeof(float) * kLEpHb &&
                   sizeof(kws_qsimple_cnn_lite::head_bias) == sizeof(float) * (kLEpCount - kLEpHb),
@@ -543,25 +468,7 @@ int lite_calibrate_hist(const kws_model *m, const float *feat, int B, const floa
 {
     int rc = check_lite(m);
     if (rc) return rc;
-    if (B < 0) return fail(KWS_ERR_INVALID, "batch must be >= 0");
-    if (B == 0) return KWS_OK;
-    if (!feat || !params || !state || !amax_host || !hist) return fail(KWS_ERR_INVALID, "null argument");
-    LHistArgs g{};
-    rc = hist_factors(amax_host, KWS_QLITE_TENSORS, g.k);
-    if (rc) return rc;
-    g.c.feat = feat;
-    for (int l = 0; l < 4; ++l) {
-        g.c.dwk[l] = params + m->o_dwk[l]; g.c.pwk[l] = params + m->o_pwk[l]; g.c.pwb[l] = params + m->o_pwb[l];
-        g.c.gamma[l] = params + m->o_g[l]; g.c.beta[l] = params + m->o_b[l];
-        g.c.mm[l] = state + m->o_mm[l]; g.c.mv[l] = state + m->o_mv[l];
-    }
-    g.c.dk = params + m->o_dk; g.c.db = params + m->o_db;
-    g.B = B;
-    g.hist = reinterpret_cast<unsigned long long *>(hist);
-    KWS_LAUNCH("lite_qhist_kernel", lite_qhist_kernel, dim3(hist_grid(reinterpret_cast<const void *>(lite_qhist_kernel), B)), dim3(256), 0, s,
-               g);
-    KWS_LAUNCH_CHECK("lite calibration histograms");
-    return KWS_OK;
+    return cal_hist_launch<LiteCal>("lite_qhist_kernel", "lite calibration histograms", m, feat, B, params, state, amax_host, hist, s);
 }
 
 }  // namespace q8
@@ -578,20 +485,8 @@ int kws_model_calibrate_lite(kws_model *m, const float *feat, int B, const float
     (void)ws; (void)ws_bytes;
     int rc = check_lite(m);
     if (rc) return rc;
-    if (B < 0) return fail(KWS_ERR_INVALID, "batch must be >= 0");
-    if (B == 0) return KWS_OK;
-    if (!feat || !params || !state || !amax) return fail(KWS_ERR_INVALID, "null argument");
-    LCalArgs a{};
-    a.feat = feat;
-    for (int l = 0; l < 4; ++l) {
-        a.dwk[l] = params + m->o_dwk[l]; a.pwk[l] = params + m->o_pwk[l]; a.pwb[l] = params + m->o_pwb[l];
-        a.gamma[l] = params + m->o_g[l]; a.beta[l] = params + m->o_b[l];
-        a.mm[l] = state + m->o_mm[l]; a.mv[l] = state + m->o_mv[l];
-    }
-    a.dk = params + m->o_dk; a.db = params + m->o_db; a.amax = amax;
-    KWS_LAUNCH("lite_qcalibrate_kernel", lite_qcalibrate_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    KWS_LAUNCH_CHECK("lite calibration");
-    return KWS_OK;
+    return cal_max_launch<LiteCal>("lite_qcalibrate_kernel", "lite calibration", m, feat, B, params, state, amax,
+                                   static_cast<hipStream_t>(stream));
 }
 
 int kws_quantize_simple_cnn_lite(const kws_model *m, const float *params_host, const float *state_host, const float *amax_host, int method,
@@ -600,18 +495,16 @@ int kws_quantize_simple_cnn_lite(const kws_model *m, const float *params_host, c
     int rc = check_lite(m);
     if (rc) return rc;
     if (!params_host || !state_host || !amax_host || !out) return fail(KWS_ERR_INVALID, "null argument");
-    if (method != KWS_QUANT_MAX && method != KWS_QUANT_RELU6 && method != KWS_QUANT_KL)
-        return fail(KWS_ERR_INVALID, "unknown quantization method %d", method);
+    rc = check_method_amax(method, amax_host, KWS_QLITE_TENSORS);
+    if (rc) return rc;
     double A[KWS_QLITE_TENSORS];
     for (int t = 0; t < KWS_QLITE_TENSORS; ++t) {
         const double v = amax_host[t];
-        if (!std::isfinite(v) || v < 0.0) return fail(KWS_ERR_INVALID, "calibrated maximum of t%d is %g (must be finite and >= 0)", t, v);
         const bool relu6_tensor = t == 9 || (t > 0 && t % 2 == 0);     // a1..a4, d; the odd t are the depthwise outputs u1..u4
         if (t == 0) A[t] = v;
         else if (relu6_tensor) A[t] = method == KWS_QUANT_RELU6 || v == 0.0 ? 6.0 : std::min(v, 6.0);
         else A[t] = v == 0.0 ? 1.0 : v;
     }
-    if (A[0] == 0.0) return fail(KWS_ERR_INVALID, "calibrated max|x| of the features is 0");
     std::memset(out, 0, sizeof(*out));
     out->num_classes = m->C;
     out->method = method;
@@ -643,17 +536,7 @@ int kws_quantize_simple_cnn_lite(const kws_model *m, const float *params_host, c
             Bo[l][c] = (float)(h / s_out);
         }
     }
-    std::vector<double> sw;
-    quantize_weight(params_host + m->o_dk, kFlat, kD, out->dense_w, sw);
-    for (int c = 0; c < kD; ++c) {
-        out->Md[c] = (float)((s[8] * sw[c]) / s[9]);
-        out->Bd[c] = (float)((double)params_host[m->o_db + c] / s[9]);
-    }
-    quantize_weight(params_host + m->o_hk, kD, m->C, out->head_w, sw);
-    for (int c = 0; c < m->C; ++c) {
-        out->Mh[c] = (float)(s[9] * sw[c]);
-        out->head_bias[c] = params_host[m->o_hb + c];
-    }
+    quantize_dense_head(m, params_host, s[8], s[9], out);
     return KWS_OK;
 }
 
@@ -684,32 +567,23 @@ int kws_qmodel_create_lite(const kws_model *m, const kws_qsimple_cnn_lite *q, kw
                     dwn[l][9 * wd + tap] |= (int32_t)((uint32_t)(uint8_t)qdw[l][tap * C + 4 * wd + j] << (8 * j));
     }
     std::vector<int8_t> f2, f3, f4, fd, fh;
-    pack_frags(q->pw_w2, kL1, kL2, 1, kL2 / 16, f2);
-    pack_frags(q->pw_w3, kL2, kL3, 1, kL3 / 16, f3);
-    pack_frags(q->pw_w4, kL3, kL4, 1, kL4 / 16, f4);
+    pack_frags(q->pw_w2, kC1, kC2, 1, kC2 / 16, f2);
+    pack_frags(q->pw_w3, kC2, kC3, 1, kC3 / 16, f3);
+    pack_frags(q->pw_w4, kC3, kC4, 1, kC4 / 16, f4);
     pack_frags(q->dense_w, kFlat, kD, kSd, kNd, fd);
     pack_frags(q->head_w, kD, m->C, kSh, kNh, fh);
-    std::vector<unsigned char> img;
-    auto put = [&img](const void *p, size_t n) { const size_t off = al256(img.size()); img.resize(off + n); std::memcpy(img.data() + off, p, n); return off; };
-    const size_t o1 = put(dw1.data(), dw1.size() * 4), o2 = put(dwn[0].data(), dwn[0].size() * 4), o3 = put(dwn[1].data(), dwn[1].size() * 4),
-                 o4 = put(dwn[2].data(), dwn[2].size() * 4), op = put(q->pw_w1, kL1), of2 = put(f2.data(), f2.size()),
-                 of3 = put(f3.data(), f3.size()), of4 = put(f4.data(), f4.size()), od = put(fd.data(), fd.size()), oh = put(fh.data(), fh.size()),
-                 oe = put(ep, sizeof(float) * kLEpCount), ob = put(q->bq1, sizeof(int32_t) * kLBqCount);
+    QBlob img;
+    const size_t o1 = img.put(dw1.data(), dw1.size() * 4), o2 = img.put(dwn[0].data(), dwn[0].size() * 4),
+                 o3 = img.put(dwn[1].data(), dwn[1].size() * 4), o4 = img.put(dwn[2].data(), dwn[2].size() * 4), op = img.put(q->pw_w1, kC1),
+                 of2 = img.put(f2.data(), f2.size()), of3 = img.put(f3.data(), f3.size()), of4 = img.put(f4.data(), f4.size()),
+                 od = img.put(fd.data(), fd.size()), oh = img.put(fh.data(), fh.size()), oe = img.put(ep, sizeof(float) * kLEpCount),
+                 ob = img.put(q->bq1, sizeof(int32_t) * kLBqCount);
     auto *qm = new kws_qmodel();
     qm->kind = KWS_SIMPLE_CNN_LITE;
     qm->C = m->C;
     qm->inv_s0 = q->inv_s0;
-    if (hipGetDevice(&qm->device) != hipSuccess || hipMalloc(&qm->blob, img.size()) != hipSuccess) {
-        (void)hipGetLastError();
-        delete qm;
-        return fail(KWS_ERR_HIP, "no HIP device / out of device memory for the quantized model");
-    }
-    if (hipMemcpy(qm->blob, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(qm->blob);
-        delete qm;
-        return fail(KWS_ERR_HIP, "upload of the quantized model failed");
-    }
-    auto *b = static_cast<unsigned char *>(qm->blob);
+    const unsigned char *b = img.upload(qm);
+    if (!b) { delete qm; return KWS_ERR_HIP; }
     qm->dw[0] = reinterpret_cast<const int32_t *>(b + o1);
     qm->dw[1] = reinterpret_cast<const int32_t *>(b + o2);
     qm->dw[2] = reinterpret_cast<const int32_t *>(b + o3);

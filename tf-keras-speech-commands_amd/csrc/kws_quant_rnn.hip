@@ -326,26 +326,16 @@ int kws_qmodel_create_rnn(const kws_model *m, const kws_qsimple_rnn *q, kws_qmod
     pack_frags(q->kernel, F, N, 1, 3 * G, fw);
     pack_frags(q->recurrent_kernel, kRU, N, 1, 3 * G, fu);
     pack_frags(q->head_w, kRU, C, 1, 3, fh);
-    std::vector<unsigned char> img;
-    auto put = [&img](const void *p, size_t n) { const size_t off = al256(img.size()); img.resize(off + n); std::memcpy(img.data() + off, p, n); return off; };
-    const size_t ow = put(fw.data(), fw.size()), ou = put(fu.data(), fu.size()), oh = put(fh.data(), fh.size()),
-                 oe = put(ep.data(), sizeof(float) * ep.size());
+    QBlob img;
+    const size_t ow = img.put(fw.data(), fw.size()), ou = img.put(fu.data(), fu.size()), oh = img.put(fh.data(), fh.size()),
+                 oe = img.put(ep.data(), sizeof(float) * ep.size());
     auto *qm = new kws_qmodel();
     qm->kind = m->kind;
     qm->C = C;
     qm->T = m->n_features;
     qm->F = F;
-    if (hipGetDevice(&qm->device) != hipSuccess || hipMalloc(&qm->blob, img.size()) != hipSuccess) {
-        (void)hipGetLastError();
-        delete qm;
-        return fail(KWS_ERR_HIP, "no HIP device / out of device memory for the quantized model");
-    }
-    if (hipMemcpy(qm->blob, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(qm->blob);
-        delete qm;
-        return fail(KWS_ERR_HIP, "upload of the quantized model failed");
-    }
-    auto *b = static_cast<unsigned char *>(qm->blob);
+    const unsigned char *b = img.upload(qm);
+    if (!b) { delete qm; return KWS_ERR_HIP; }
     qm->rw = reinterpret_cast<const i32x4 *>(b + ow);
     qm->ru = reinterpret_cast<const i32x4 *>(b + ou);
     qm->fh = reinterpret_cast<const i32x4 *>(b + oh);
