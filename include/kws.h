@@ -532,6 +532,14 @@ typedef struct kws_tensor_info {
 /* host only (no GPU needed).  kind outside the enum -> KWS_ERR_INVALID "Unsupported model type"
  * (classifier/model.py:32). n_features / feature_size: classifier/params.py:66-68,86-91. */
 int kws_model_create(int kind, int num_classes, int n_features, int feature_size, kws_model **out);
+/* simple_gru / simple_lstm with num_layers = 1 .. 4 recurrent layers of 48 units (the reference's `num_layers` argument, rnn.py): every
+ * layer but the last returns its whole sequence (B, T, 48) to the next one, the last returns its final state to Dense(C).  Tensors in
+ * Keras get_weights() order: gru_unit_<l>/kernel (F_l, 144), /recurrent_kernel (48, 144), /bias (2, 144) -- lstm_unit_<l>/...: (F_l, 192),
+ * (48, 192), (192) -- for l = 0 .. num_layers - 1 with F_0 = feature_size and F_l = 48 above, then score_predict/kernel, /bias.
+ * num_layers outside 1 .. 4, or != 1 for a CNN kind: KWS_ERR_INVALID.  kws_model_create is num_layers = 1.  A stacked model trains and
+ * infers like any other; kws_quantize_simple_rnn / kws_qmodel_create_rnn refuse it with KWS_ERR_UNSUPPORTED (one layer only). */
+int kws_model_create_stacked(int kind, int num_classes, int n_features, int feature_size, int num_layers, kws_model **out);
+int kws_model_num_layers(const kws_model *m);
 void kws_model_destroy(kws_model *m);
 int64_t kws_model_param_count(const kws_model *m);
 int64_t kws_model_state_count(const kws_model *m);
@@ -564,6 +572,8 @@ int kws_model_invalidate_prepared(kws_model *m);
  * loss = classifier/loss.py SparseCategoricalCrossEntropy (class_weights NULL) or
  * WeightedSparseCategoricalCrossEntropy (class_weights: C device floats), reduced by the batch mean.
  * grads <- grad_scale * d(mean loss)/d(params)  (data parallel: grad_scale = 1/world, then sum-all-reduce). */
+/* seed of recurrent layer l's input-dropout mask: dropout_seed + l * 0x9E3779B97F4A7C15 modulo 2^64 (layer 0: dropout_seed itself) */
+#define KWS_LAYER_DROPOUT_SEED(seed, l) ((uint64_t)(seed) + (uint64_t)(l) * 0x9E3779B97F4A7C15ull)
 struct kws_comm;
 typedef struct kws_train_args {
     const float *feat;          /* (B, n_features, feature_size)                                   */
@@ -577,7 +587,8 @@ typedef struct kws_train_args {
     float *grads;
     void *ws;
     size_t ws_bytes;
-    uint64_t dropout_seed;
+    uint64_t dropout_seed;      /* 0 = no dropout anywhere.  Recurrent layer l of a stacked model draws its (B, F_l) input mask with
+                                   KWS_LAYER_DROPOUT_SEED(dropout_seed, l) at index b * F_l + f; layer 0's seed is dropout_seed   */
     float grad_scale;
     float *probs;               /* NULL or (B, C)                                                   */
     float *stats;               /* NULL or 2 floats: {sum of per-sample losses, number of top-1 hits} */

@@ -1,6 +1,6 @@
 """Model factory (host mirror of the reference's classifier/model.py:14-46).
 
-`get_model(model_type, num_classes, batch_size=None, weights_path=None)` returns an object with the part of the
+`get_model(model_type, num_classes, batch_size=None, weights_path=None, num_layers=1)` returns an object with the part of the
 tf.keras.Model API the reference's callers use (train.py:75-95, eval.py:29, listen.py:139): compile / fit / predict /
 evaluate / summary / save / load_weights / get_weights / set_weights.  Every batch of `fit` and `predict` runs in the
 HIP kernels behind include/kws.h; there is no CPU path (using the model without a GPU raises kws_amd.KwsError).
@@ -36,20 +36,27 @@ class History(object):
 class KWSModel(object):
     """A compiled-once keyword-spotting classifier living on one HIP device."""
 
-    def __init__(self, model_type, num_classes, batch_size=None, seed=None):
+    def __init__(self, model_type, num_classes, batch_size=None, seed=None, num_layers=1):
         cnn = model_type in ('simple_cnn', 'simple_cnn_lite')
+        num_layers = int(num_layers)
+        # the reference's recurrent builders take num_layers (rnn.py:13,49); 1..4 here.  The CNNs have no such argument.
+        if cnn and num_layers != 1:
+            raise ValueError("num_layers = %d: only simple_gru / simple_lstm stack layers" % num_layers)
+        if model_type in ('simple_gru', 'simple_lstm') and not 1 <= num_layers <= 4:
+            raise ValueError("num_layers = %d outside 1..4" % num_layers)
+        self.num_layers = num_layers
         # RNN models take 2-D input per clip, CNNs 3-D (reference :16-20)
         self.input_shape = (pr.n_features, pr.feature_size, 1) if cnn else (pr.n_features, pr.feature_size)
         self.batch_size = batch_size
-        self.spec = ModelSpec(model_type, num_classes, pr.n_features, pr.feature_size)   # ValueError('Unsupported model type')
+        self.spec = ModelSpec(model_type, num_classes, pr.n_features, pr.feature_size, num_layers)   # ValueError('Unsupported model type')
         if model_type == 'simple_cnn':
             self.layers = SimpleCNN(input_shape=self.input_shape, feature_size=128)
         elif model_type == 'simple_cnn_lite':
             self.layers = SimpleCNNLite(input_shape=self.input_shape, feature_size=128)
         elif model_type == 'simple_gru':
-            self.layers = SimpleGRU(input_shape=self.input_shape, recurrent_units=48)
+            self.layers = SimpleGRU(input_shape=self.input_shape, recurrent_units=48, num_layers=num_layers)
         else:
-            self.layers = SimpleLSTM(input_shape=self.input_shape, recurrent_units=48)
+            self.layers = SimpleLSTM(input_shape=self.input_shape, recurrent_units=48, num_layers=num_layers)
         feat = self.layers[-1]["output_shape"][-1]
         self.layers.append(dict(name='score_predict', type='Dense', output_shape=(num_classes,),
                                 params=feat * num_classes + num_classes, activation='softmax'))
@@ -112,6 +119,8 @@ class KWSModel(object):
         arrays = {n: w for n, w in zip(self.weight_names, self.get_weights())}
         arrays["__meta__"] = np.array([self.model_type, str(self.num_classes), str(pr.n_features), str(pr.feature_size)])
         arrays["__order__"] = np.array(self.weight_names)
+        if self.num_layers != 1:            # a one-layer file holds exactly what it always held
+            arrays["__num_layers__"] = np.array(self.num_layers, np.int32)
         np.savez(filepath, **arrays)
 
     save = save_weights   # model.save(path) (train.py:95): the optimizer state is not part of the file
@@ -119,6 +128,9 @@ class KWSModel(object):
     def load_weights(self, filepath, by_name=False, skip_mismatch=False):
         path = filepath if os.path.exists(filepath) else filepath + '.npz'
         z = np.load(path, allow_pickle=False)
+        file_layers = int(z["__num_layers__"]) if "__num_layers__" in z.files else 1
+        if file_layers != self.num_layers:
+            raise ValueError("%s holds a model of num_layers = %d, this model has num_layers = %d" % (path, file_layers, self.num_layers))
         order = [str(n) for n in z["__order__"]] if "__order__" in z.files else [n for n in z.files if not n.startswith("__")]
         if by_name:
             cur = dict(zip(self.weight_names, self.get_weights()))
@@ -518,7 +530,7 @@ class KWSModel(object):
         (predict / evaluate / save).  'kl' (the reference's MNN recipe) makes a second pass over x_calib that histograms the tensors
         against the maxima of the first and takes the ranges of least KL divergence.  simple_gru / simple_lstm: dynamic-range int8
         (method 'dynamic', their only one and their default; kws_amd.quant.QuantizedRNN), which reads no calibration data (x_calib may
-        be None).  A snapshot: it does not follow later training."""
+        be None); with num_layers > 1 the library refuses (kws_amd.KwsError, KWS_ERR_UNSUPPORTED).  A snapshot: it does not follow later training."""
         import torch
         from kws_amd.quant import QuantizedCNN, QuantizedCNNLite, QuantizedRNN, calibrate, histograms
         if self.model_type in ('simple_gru', 'simple_lstm'):
@@ -599,9 +611,10 @@ class QuantizedKWSModel(object):
         return [float(loss_sum.item()) / max(n, 1), float(hits.item()) / max(n, 1)]
 
 
-def get_model(model_type, num_classes, batch_size=None, weights_path=None):
-    """simple_cnn / simple_cnn_lite (4-D input) or simple_gru / simple_lstm (3-D input) + Dense softmax 'score_predict'"""
-    model = KWSModel(model_type, num_classes, batch_size=batch_size)
+def get_model(model_type, num_classes, batch_size=None, weights_path=None, num_layers=1):
+    """simple_cnn / simple_cnn_lite (4-D input) or simple_gru / simple_lstm (3-D input, num_layers stacked recurrent layers) + Dense
+    softmax 'score_predict'"""
+    model = KWSModel(model_type, num_classes, batch_size=batch_size, num_layers=num_layers)
 
     if weights_path:
         model.load_weights(weights_path, by_name=False)

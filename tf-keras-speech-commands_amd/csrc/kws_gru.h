@@ -66,11 +66,14 @@ __device__ __forceinline__ void gru_stage_x(const float *__restrict__ feat, floa
 // step's dependent chain is a third as long (65 -> see DESIGN.md for the measured time); the arithmetic per output is unchanged.
 constexpr int kGruFwdThreads = 768;     // nine product waves + three more so that the gate arithmetic is one output per thread
 constexpr int kGruPS = 50;                // row stride of a pre-activation plane
-template <int KX, bool SAVE>
+// SEQ (a layer of a stacked model that is not the last one): h_t of every step goes to seq_out (B, T, 48), the input of the layer above,
+// and h_out is not written.
+template <int KX, bool SAVE, bool SEQ = false>
 __global__ __launch_bounds__(kGruFwdThreads) void gru_fwd_kernel(const float *__restrict__ feat, const float *__restrict__ Wk,
                                                                   const float *__restrict__ Uk, const float *__restrict__ bias,
                                                                   float *__restrict__ h_out, float *__restrict__ saved, int B, int T,
-                                                                  int F, float drop_rate, uint32_t slo, uint32_t shi, float *__restrict__ zero_buf = nullptr, long zero_n = 0)
+                                                                  int F, float drop_rate, uint32_t slo, uint32_t shi, float *__restrict__ zero_buf = nullptr, long zero_n = 0,
+                                                                  float *__restrict__ seq_out = nullptr)
 {
     // training: the gradient buffer of the backward pass that follows is cleared here (zero_n floats over the whole grid) instead of by a
     // memset node on the step's chain
@@ -141,7 +144,9 @@ __global__ __launch_bounds__(kGruFwdThreads) void gru_fwd_kernel(const float *__
             const float mhh = P[(48 + c) * kGruPS + k];
             const float hh = P[(32 + c) * kGruPS + k] + rg * mhh;
             const float hp = hc[c * kGruHS + k];
-            hn[c * kGruHS + k] = z * hp + (1.f - z) * hh;
+            const float hnew = z * hp + (1.f - z) * hh;
+            hn[c * kGruHS + k] = hnew;
+            if (SEQ && b0 + c < B) seq_out[((long)(b0 + c) * T + t) * kGruU + k] = hnew;
             if (SAVE && b0 + c < B) {
                 float *sv = saved + (((long)(b0 + c) * T + t) * kGruSave) * kGruU + k;
                 sv[0] = hp; sv[kGruU] = z; sv[2 * kGruU] = rg; sv[3 * kGruU] = hh; sv[4 * kGruU] = mhh;
@@ -150,6 +155,7 @@ __global__ __launch_bounds__(kGruFwdThreads) void gru_fwd_kernel(const float *__
         cur ^= 1;
         __syncthreads();
     }
+    if (SEQ) return;
     const float *hf = hs + cur * 16 * kGruHS;
     for (int e = threadIdx.x; e < 16 * kGruU; e += kGruFwdThreads) {
         const int c = e / kGruU, k = e - c * kGruU;
@@ -165,13 +171,22 @@ __global__ __launch_bounds__(kGruFwdThreads) void gru_fwd_kernel(const float *__
 // and 6-8 take the two weight-gradient products of the SAME step (dU: 36, dW: 24 of the step's 96 MFMAs, none of which feeds the
 // recurrence) from the G / h_prev / x tiles in LDS, between the same two barriers.  The step's critical path is then 36 MFMAs instead of 96
 // (three waves doing everything: 109 us at B = 2048; six waves, dU + dW together: 90 us).
-constexpr int kGruBwdThreads = 576;
-template <int KX>
-__global__ __launch_bounds__(kGruBwdThreads) void gru_bwd_kernel(const float *__restrict__ feat, const float *__restrict__ Uk,
+// Stacked models add two things, both compiled out of the one-layer kernel:
+//   DSEQ (every layer but the last): the dh entering step t is the recurrent dh plus dseq_in[b, t, :], the input gradient written by the
+//        layer above; the gradient of the last state is zero and dh_last is not read.  The values ride in the look-ahead of the saved ones.
+//   DX   (every layer but the first; F == 48): dx_t = dmx_t W^T times the layer's dropout mask goes to dx_out (B, T, 48).  Three more
+//        waves (9-11) hold W^T's fragments in registers and take the 36 MFMAs per step from the G tile between the same two barriers
+//        as the dU / dW waves: nothing of it is on the recurrence waves' chain.
+constexpr int kGruBwdThreads = 576, kGruBwdDxThreads = 768;
+template <int KX, bool DSEQ = false, bool DX = false>
+__global__ __launch_bounds__(DX ? kGruBwdDxThreads : kGruBwdThreads) void gru_bwd_kernel(const float *__restrict__ feat, const float *__restrict__ Uk,
                                                                   const float *__restrict__ saved, const float *__restrict__ dh_last,
                                                                   float *__restrict__ dW, float *__restrict__ dU, float *__restrict__ db,
-                                                                  int B, int T, int F, float drop_rate, uint32_t slo, uint32_t shi)
+                                                                  int B, int T, int F, float drop_rate, uint32_t slo, uint32_t shi,
+                                                                  const float *__restrict__ dseq_in = nullptr,
+                                                                  const float *__restrict__ Wk = nullptr, float *__restrict__ dx_out = nullptr)
 {
+    constexpr int NT = DX ? kGruBwdDxThreads : kGruBwdThreads;
     constexpr int MTW = (KX * 4 + 15) / 16;            // 16-row tiles covering the F input features
     constexpr int WT = (MTW * 9 + 2) / 3;              // dW tiles per wave
     extern __shared__ float gsm[];
@@ -187,9 +202,9 @@ __global__ __launch_bounds__(kGruBwdThreads) void gru_bwd_kernel(const float *__
     const int b0 = blockIdx.x * 16, u = 16 * w3 + li;
 
     gru_stage_x(feat, xs, b0, B, T, F, XS, drop_rate, slo, shi);
-    for (int i = threadIdx.x; i < 16 * kGruU; i += kGruBwdThreads) {
+    for (int i = threadIdx.x; i < 16 * kGruU; i += NT) {
         const int c = i / kGruU, k = i % kGruU;
-        dhs[c * kGruHS + k] = (b0 + c < B) ? dh_last[(long)(b0 + c) * kGruU + k] : 0.f;
+        dhs[c * kGruHS + k] = (!DSEQ && b0 + c < B) ? dh_last[(long)(b0 + c) * kGruU + k] : 0.f;
     }
     __syncthreads();
 
@@ -201,14 +216,15 @@ __global__ __launch_bounds__(kGruBwdThreads) void gru_bwd_kernel(const float *__
         float sbz = 0.f, sbr = 0.f, sbh = 0.f, sbm = 0.f;
         // the step's saved forward values (h_prev, z, r, hh, mh_h of this lane's four clips) come from global memory: they are requested
         // one step AHEAD, under the previous step's products, by unconditional loads on clamped (clip, step) addresses, masked afterwards
-        float svn[4][kGruSave];
-        const float *svbase[4];
+        float svn[4][kGruSave], dsn[4] = {0.f, 0.f, 0.f, 0.f};
+        const float *svbase[4], *dsbase[4];
         float svmask[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int c = 4 * lq + r;
             const bool in = b0 + c < B;
             svbase[r] = saved + ((long)(in ? b0 + c : b0) * T * kGruSave) * kGruU + u;
+            dsbase[r] = DSEQ ? dseq_in + ((long)(in ? b0 + c : b0) * T) * kGruU + u : nullptr;
             svmask[r] = in ? 1.f : 0.f;
         }
         auto fetch_saved = [&](int t) {
@@ -218,23 +234,26 @@ __global__ __launch_bounds__(kGruBwdThreads) void gru_bwd_kernel(const float *__
                 const float *sv = svbase[r] + (long)tc * kGruSave * kGruU;
 #pragma unroll
                 for (int q = 0; q < kGruSave; ++q) svn[r][q] = sv[q * kGruU] * svmask[r];
+                if (DSEQ) dsn[r] = dsbase[r][(long)tc * kGruU] * svmask[r];
             }
         };
         fetch_saved(T - 1);
         int cur = 0;
         for (int t = T - 1; t >= 0; --t) {
             const float *dc = dhs + cur * 16 * kGruHS;
-            float dhz[4], svc[4][kGruSave];
+            float dhz[4], svc[4][kGruSave], dsc[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+            for (int r = 0; r < 4; ++r) {
 #pragma unroll
                 for (int q = 0; q < kGruSave; ++q) svc[r][q] = svn[r][q];
+                dsc[r] = dsn[r];
+            }
             fetch_saved(t - 1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int c = 4 * lq + r;
                 const float hp = svc[r][0], z = svc[r][1], rg = svc[r][2], hh = svc[r][3], mhh = svc[r][4];
-                const float dh = dc[c * kGruHS + u];
+                const float dh = DSEQ ? dc[c * kGruHS + u] + dsc[r] : dc[c * kGruHS + u];
                 const float dhh = dh * (1.f - z);
                 const float gz = dh * (hp - hh) * z * (1.f - z), gr = dhh * mhh * rg * (1.f - rg), gm = dhh * rg;
                 G[c * kGruGS + u] = gz;
@@ -278,6 +297,36 @@ __global__ __launch_bounds__(kGruBwdThreads) void gru_bwd_kernel(const float *__
             atomicAdd(db + kGruN + u, sbz);
             atomicAdd(db + kGruN + kGruU + u, sbr);
             atomicAdd(db + kGruN + 2 * kGruU + u, sbm);
+        }
+    } else if (DX && wave >= 9) {
+        // dx_t[clip][f] = sum_n dmx_t[clip][n] W[f][n] over the 144 dmx columns (the first 144 of G); this wave owns f = 16 w3 + li
+        float wt[36], mk[4];
+#pragma unroll
+        for (int j = 0; j < 36; ++j) wt[j] = u < F ? Wk[u * kGruN + 4 * j + lq] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int b = b0 + 4 * lq + r;
+            mk[r] = 1.f;
+            if (drop_rate > 0.f && b < B && u < F) mk[r] = dropout_keep(slo, shi, (uint32_t)(b * F + u), drop_rate) ? 1.f / (1.f - drop_rate) : 0.f;
+        }
+        for (int t = T - 1; t >= 0; --t) {
+            __syncthreads();                           // G of step t complete
+            float ga[36];
+#pragma unroll
+            for (int j = 0; j < 36; ++j) ga[j] = G[li * kGruGS + 4 * j + lq];
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0;
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                acc0 = mfma16(ga[3 * j], wt[3 * j], acc0);
+                acc1 = mfma16(ga[3 * j + 1], wt[3 * j + 1], acc1);
+                acc2 = mfma16(ga[3 * j + 2], wt[3 * j + 2], acc2);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int b = b0 + 4 * lq + r;
+                if (b < B && u < F) dx_out[((long)b * T + t) * F + u] = ((acc0[r] + acc1[r]) + acc2[r]) * mk[r];
+            }
+            __syncthreads();                           // the recurrence waves may overwrite G
         }
     } else {
         f32x4 accU[9], accW[WT];

@@ -24,11 +24,13 @@ constexpr int kLstmSave = 7;               // saved per (clip, step): h_prev, c_
 
 constexpr int kLstmFwdThreads = 768, kLstmBwdThreads = 576;
 
-template <int KX, bool SAVE>
+// SEQ: as gru_fwd_kernel -- h_t of every step to seq_out (B, T, 48), h_out not written
+template <int KX, bool SAVE, bool SEQ = false>
 __global__ __launch_bounds__(kLstmFwdThreads) void lstm_fwd_kernel(const float *__restrict__ feat, const float *__restrict__ Wk,
                                                                     const float *__restrict__ Uk, const float *__restrict__ bias,
                                                                     float *__restrict__ h_out, float *__restrict__ saved, int B, int T,
-                                                                    int F, float drop_rate, uint32_t slo, uint32_t shi, float *__restrict__ zero_buf = nullptr, long zero_n = 0)
+                                                                    int F, float drop_rate, uint32_t slo, uint32_t shi, float *__restrict__ zero_buf = nullptr, long zero_n = 0,
+                                                                    float *__restrict__ seq_out = nullptr)
 {
     // training: the gradient buffer of the backward pass that follows is cleared here (zero_n floats over the whole grid) instead of by a
     // memset node on the step's chain
@@ -91,6 +93,7 @@ __global__ __launch_bounds__(kLstmFwdThreads) void lstm_fwd_kernel(const float *
             const float hp = hc[ec * kGruHS + ek];
             cst = cn;
             hn[ec * kGruHS + ek] = og * tc;
+            if (SEQ && b0 + ec < B) seq_out[((long)(b0 + ec) * T + t) * kGruU + ek] = og * tc;
             if (SAVE && b0 + ec < B) {
                 float *sv = saved + (((long)(b0 + ec) * T + t) * kLstmSave) * kGruU + ek;
                 sv[0] = hp; sv[kGruU] = cp; sv[2 * kGruU] = ig; sv[3 * kGruU] = fg; sv[4 * kGruU] = gg; sv[5 * kGruU] = og;
@@ -100,19 +103,25 @@ __global__ __launch_bounds__(kLstmFwdThreads) void lstm_fwd_kernel(const float *
         cur ^= 1;
         __syncthreads();
     }
-    if (b0 + ec < B) h_out[(long)(b0 + ec) * kGruU + ek] = hs[cur * 16 * kGruHS + ec * kGruHS + ek];
+    if (!SEQ && b0 + ec < B) h_out[(long)(b0 + ec) * kGruU + ek] = hs[cur * 16 * kGruHS + ec * kGruHS + ek];
 }
 
 // BPTT.  Per step (t = T-1 .. 0) and 16-clip tile, with dh and dc carried backwards:
 //   do = dh tanh(c');  dc += dh o (1 - tanh(c')^2)
 //   da = [dc g i(1-i) | dc c_prev f(1-f) | dc i (1-g^2) | do o(1-o)]          (192 columns, tile G)
 //   dW += x_t^T da;  dU += h_prev^T da;  db += sum da;  dh_prev = da U^T;  dc_prev = dc f
-template <int KX>
-__global__ __launch_bounds__(kLstmBwdThreads) void lstm_bwd_kernel(const float *__restrict__ feat, const float *__restrict__ Uk,
+// DSEQ / DX: as gru_bwd_kernel -- a per-step gradient from the layer above, and dx_t = da_t W^T (192 columns, 48 MFMAs per step on waves
+// 9-11) times the layer's dropout mask to dx_out
+constexpr int kLstmBwdDxThreads = 768;
+template <int KX, bool DSEQ = false, bool DX = false>
+__global__ __launch_bounds__(DX ? kLstmBwdDxThreads : kLstmBwdThreads) void lstm_bwd_kernel(const float *__restrict__ feat, const float *__restrict__ Uk,
                                                                     const float *__restrict__ saved, const float *__restrict__ dh_last,
                                                                     float *__restrict__ dW, float *__restrict__ dU, float *__restrict__ db,
-                                                                    int B, int T, int F, float drop_rate, uint32_t slo, uint32_t shi)
+                                                                    int B, int T, int F, float drop_rate, uint32_t slo, uint32_t shi,
+                                                                    const float *__restrict__ dseq_in = nullptr,
+                                                                    const float *__restrict__ Wk = nullptr, float *__restrict__ dx_out = nullptr)
 {
+    constexpr int NT = DX ? kLstmBwdDxThreads : kLstmBwdThreads;
     constexpr int MTW = (KX * 4 + 15) / 16;            // 16-row tiles covering the F input features
     constexpr int WT = (MTW * 12 + 2) / 3;             // dW tiles per wave
     extern __shared__ float gsm[];
@@ -128,9 +137,9 @@ __global__ __launch_bounds__(kLstmBwdThreads) void lstm_bwd_kernel(const float *
     const int b0 = blockIdx.x * 16, u = 16 * w3 + li;
 
     gru_stage_x(feat, xs, b0, B, T, F, XS, drop_rate, slo, shi);
-    for (int i = threadIdx.x; i < 16 * kGruU; i += kLstmBwdThreads) {
+    for (int i = threadIdx.x; i < 16 * kGruU; i += NT) {
         const int c = i / kGruU, k = i % kGruU;
-        dhs[c * kGruHS + k] = (b0 + c < B) ? dh_last[(long)(b0 + c) * kGruU + k] : 0.f;
+        dhs[c * kGruHS + k] = (!DSEQ && b0 + c < B) ? dh_last[(long)(b0 + c) * kGruU + k] : 0.f;
     }
     __syncthreads();
 
@@ -142,14 +151,15 @@ __global__ __launch_bounds__(kLstmBwdThreads) void lstm_bwd_kernel(const float *
         float dcs[4] = {0.f, 0.f, 0.f, 0.f};           // dL/dc of (clip 4 lq + r, unit u), carried backwards
         // the step's saved forward values come from global memory: requested one step AHEAD by unconditional loads on clamped (clip, step)
         // addresses, masked afterwards (kws_gru.h: gru_bwd_kernel has the measurements)
-        float svn[4][kLstmSave];
-        const float *svbase[4];
+        float svn[4][kLstmSave], dsn[4] = {0.f, 0.f, 0.f, 0.f};
+        const float *svbase[4], *dsbase[4];
         float svmask[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int c = 4 * lq + r;
             const bool in = b0 + c < B;
             svbase[r] = saved + ((long)(in ? b0 + c : b0) * T * kLstmSave) * kGruU + u;
+            dsbase[r] = DSEQ ? dseq_in + ((long)(in ? b0 + c : b0) * T) * kGruU + u : nullptr;
             svmask[r] = in ? 1.f : 0.f;
         }
         auto fetch_saved = [&](int t) {
@@ -159,23 +169,26 @@ __global__ __launch_bounds__(kLstmBwdThreads) void lstm_bwd_kernel(const float *
                 const float *sv = svbase[r] + (long)tcl * kLstmSave * kGruU;
 #pragma unroll
                 for (int q = 0; q < kLstmSave; ++q) svn[r][q] = sv[q * kGruU] * svmask[r];
+                if (DSEQ) dsn[r] = dsbase[r][(long)tcl * kGruU] * svmask[r];
             }
         };
         fetch_saved(T - 1);
         int cur = 0;
         for (int t = T - 1; t >= 0; --t) {
             const float *dcur = dhs + cur * 16 * kGruHS;
-            float svc[4][kLstmSave];
+            float svc[4][kLstmSave], dsc[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+            for (int r = 0; r < 4; ++r) {
 #pragma unroll
                 for (int q = 0; q < kLstmSave; ++q) svc[r][q] = svn[r][q];
+                dsc[r] = dsn[r];
+            }
             fetch_saved(t - 1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int c = 4 * lq + r;
                 const float hp = svc[r][0], cp = svc[r][1], ig = svc[r][2], fg = svc[r][3], gg = svc[r][4], og = svc[r][5], tc = svc[r][6];
-                const float dh = dcur[c * kGruHS + u];
+                const float dh = DSEQ ? dcur[c * kGruHS + u] + dsc[r] : dcur[c * kGruHS + u];
                 const float dc = dcs[r] + dh * og * (1.f - tc * tc);
                 const float gi = dc * gg * ig * (1.f - ig), gf = dc * cp * fg * (1.f - fg), gc = dc * ig * (1.f - gg * gg), go = dh * tc * og * (1.f - og);
                 G[c * kGruGS + u] = gi;
@@ -209,6 +222,36 @@ __global__ __launch_bounds__(kLstmBwdThreads) void lstm_bwd_kernel(const float *
             sbq[q] += __shfl_xor(sbq[q], 16, 64);
             sbq[q] += __shfl_xor(sbq[q], 32, 64);
             if (lq == 0) atomicAdd(db + q * kGruU + u, sbq[q]);
+        }
+    } else if (DX && wave >= 9) {
+        // dx_t[clip][f] = sum_n da_t[clip][n] W[f][n] over the 192 gate columns; this wave owns f = 16 w3 + li
+        float wt[48], mk[4];
+#pragma unroll
+        for (int j = 0; j < 48; ++j) wt[j] = u < F ? Wk[u * kLstmN + 4 * j + lq] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int b = b0 + 4 * lq + r;
+            mk[r] = 1.f;
+            if (drop_rate > 0.f && b < B && u < F) mk[r] = dropout_keep(slo, shi, (uint32_t)(b * F + u), drop_rate) ? 1.f / (1.f - drop_rate) : 0.f;
+        }
+        for (int t = T - 1; t >= 0; --t) {
+            __syncthreads();                           // G of step t complete
+            float ga[48];
+#pragma unroll
+            for (int j = 0; j < 48; ++j) ga[j] = G[li * kGruGS + 4 * j + lq];
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                acc0 = mfma16(ga[3 * j], wt[3 * j], acc0);
+                acc1 = mfma16(ga[3 * j + 1], wt[3 * j + 1], acc1);
+                acc2 = mfma16(ga[3 * j + 2], wt[3 * j + 2], acc2);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int b = b0 + 4 * lq + r;
+                if (b < B && u < F) dx_out[((long)b * T + t) * F + u] = ((acc0[r] + acc1[r]) + acc2[r]) * mk[r];
+            }
+            __syncthreads();                           // the recurrence waves may overwrite G
         }
     } else {
         f32x4 accU[12], accW[WT];

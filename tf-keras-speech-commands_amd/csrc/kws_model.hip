@@ -1549,36 +1549,48 @@ int kws_model_set_deterministic(kws_model *m, int on)
 {
     if (!m) return fail(KWS_ERR_INVALID, "null argument");
     if (on && (m->kind == KWS_SIMPLE_GRU || m->kind == KWS_SIMPLE_LSTM))
-        return fail(KWS_ERR_UNSUPPORTED, "the deterministic weight-gradient mode covers simple_cnn and simple_cnn_lite");
+        return fail(KWS_ERR_UNSUPPORTED, "the deterministic weight-gradient mode covers simple_cnn and simple_cnn_lite, not a recurrent model (num_layers = %d)",
+                    m->num_layers);
     m->deterministic = on ? 1 : 0;
     return KWS_OK;
 }
 
 int kws_model_create(int kind, int num_classes, int n_features, int feature_size, kws_model **out)
 {
+    return kws_model_create_stacked(kind, num_classes, n_features, feature_size, 1, out);
+}
+
+int kws_model_num_layers(const kws_model *m) { return m ? m->num_layers : 0; }
+
+int kws_model_create_stacked(int kind, int num_classes, int n_features, int feature_size, int num_layers, kws_model **out)
+{
     if (!out) return fail(KWS_ERR_INVALID, "null argument");
     *out = nullptr;
     if (kind < KWS_SIMPLE_CNN || kind > KWS_SIMPLE_LSTM) return fail(KWS_ERR_INVALID, "Unsupported model type");   // model.py:32
     if (num_classes < 2 || num_classes > 1024) return fail(KWS_ERR_INVALID, "num_classes must be in 2..1024");
     if (n_features < 1 || feature_size < 1) return fail(KWS_ERR_INVALID, "bad input geometry");
+    const bool rnn = kind == KWS_SIMPLE_GRU || kind == KWS_SIMPLE_LSTM;
+    if (rnn && (num_layers < 1 || num_layers > kRnnMaxLayers))
+        return fail(KWS_ERR_INVALID, "num_layers = %d outside 1 .. %d", num_layers, kRnnMaxLayers);
+    if (!rnn && num_layers != 1) return fail(KWS_ERR_INVALID, "num_layers = %d: only the recurrent models stack layers", num_layers);
     auto *m = new kws_model();
-    m->kind = kind; m->C = num_classes; m->n_features = n_features; m->feature_size = feature_size;
+    m->kind = kind; m->C = num_classes; m->n_features = n_features; m->feature_size = feature_size; m->num_layers = num_layers;
     if (kind == KWS_SIMPLE_GRU || kind == KWS_SIMPLE_LSTM) {
         if (feature_size > 64) {
             delete m;
             return fail(KWS_ERR_UNSUPPORTED, "the recurrent models support feature_size <= 64");
         }
-        if (kind == KWS_SIMPLE_GRU) {
-            // GRU(48, activation='linear', dropout=0.2) -> Dense(C, softmax)   (rnn.py:34-35, model.py:37)
-            m->o_rk = m->add("gru_unit_0/kernel", {feature_size, 144}, true);
-            m->o_ru = m->add("gru_unit_0/recurrent_kernel", {48, 144}, true);
-            m->o_rb = m->add("gru_unit_0/bias", {2, 144}, true);
-        } else {
-            // LSTM(48, activation='tanh', dropout=0.2) -> Dense(C, softmax)    (rnn.py:70-71, model.py:37)
-            m->o_rk = m->add("lstm_unit_0/kernel", {feature_size, 192}, true);
-            m->o_ru = m->add("lstm_unit_0/recurrent_kernel", {48, 192}, true);
-            m->o_rb = m->add("lstm_unit_0/bias", {192}, true);
+        // num_layers - 1 GRU / LSTM(48, return_sequences=True, dropout=0.2) in front of GRU(48, activation='linear', dropout=0.2) or
+        // LSTM(48, activation='tanh', dropout=0.2) -> Dense(C, softmax)   (rnn.py:10-43, 46-79, model.py:37); Keras get_weights() order
+        const bool gru = kind == KWS_SIMPLE_GRU;
+        const int N = gru ? 144 : 192;
+        for (int l = 0; l < num_layers; ++l) {
+            const std::string name = std::string(gru ? "gru_unit_" : "lstm_unit_") + std::to_string(l);
+            m->o_lk[l] = m->add(name + "/kernel", {l == 0 ? feature_size : 48, N}, true);
+            m->o_lu[l] = m->add(name + "/recurrent_kernel", {48, N}, true);
+            m->o_lb[l] = gru ? m->add(name + "/bias", {2, 144}, true) : m->add(name + "/bias", {192}, true);
         }
+        m->o_rk = m->o_lk[0]; m->o_ru = m->o_lu[0]; m->o_rb = m->o_lb[0];
         m->head_K = 48;
         m->o_hk = m->add("score_predict/kernel", {48, num_classes}, true);
         m->o_hb = m->add("score_predict/bias", {num_classes}, true);

@@ -33,6 +33,8 @@ struct ModelRes {
 
 struct CnnDims { int H0, W0, H1, W1, H2, W2, H3, W3, H4, W4, flat; };
 
+constexpr int kRnnMaxLayers = 4;          // kws_model_create_stacked: num_layers 1 .. 4
+
 inline int64_t al4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline unsigned blocks_for(long n, int per) { return (unsigned)((n + per - 1) / per); }
@@ -76,8 +78,10 @@ struct kws_model {
     int64_t o_k[4], o_g[4], o_b[4], o_dk, o_db, o_mm[4], o_mv[4];
     // simple_cnn_lite: depthwise / pointwise kernels and pointwise bias of the four SeparableConv2D stages
     int64_t o_dwk[4], o_pwk[4], o_pwb[4];
-    // simple_gru offsets
+    // simple_gru / simple_lstm: layer 0's kernel, recurrent kernel and bias (the one-layer models' names for them), then every layer's
     int64_t o_rk, o_ru, o_rb;
+    int num_layers = 1;
+    int64_t o_lk[4], o_lu[4], o_lb[4];
     // head (all models): Dense(C) on a K-wide feature vector
     int64_t o_hk, o_hb;
     int head_K = 128;

@@ -223,6 +223,8 @@ int check_rnn(const kws_model *m)
     if (!m) return fail(KWS_ERR_INVALID, "null model");
     if (m->kind != KWS_SIMPLE_GRU && m->kind != KWS_SIMPLE_LSTM)
         return fail(KWS_ERR_UNSUPPORTED, "dynamic-range int8 quantization covers simple_gru and simple_lstm only (model kind %d)", m->kind);
+    if (m->num_layers != 1)
+        return fail(KWS_ERR_UNSUPPORTED, "dynamic-range int8 quantization covers one recurrent layer, not num_layers = %d", m->num_layers);
     if (m->feature_size < 1 || m->feature_size > KWS_QRNN_MAX_FEATURES)
         return fail(KWS_ERR_UNSUPPORTED, "dynamic-range int8 quantization covers feature_size 1..%d, not %d", KWS_QRNN_MAX_FEATURES, m->feature_size);
     if (m->n_features < 1 || m->n_features > KWS_QRNN_MAX_STEPS)

@@ -1,4 +1,4 @@
-// csrc/kws_rnn.hip -- the recurrent models behind the C ABI: GRU(48, linear) or LSTM(48, tanh) -> Dense(C, softmax)
+// csrc/kws_rnn.hip -- the recurrent models behind the C ABI: 1 .. 4 stacked GRU(48, linear) or LSTM(48, tanh) -> Dense(C, softmax)
 // (classifier/models/rnn.py:10-43 and 46-79, classifier/model.py:20-29,37).
 #include "kws_lstm.h"
 #include "kws_model_types.h"
@@ -9,9 +9,17 @@ namespace {
 
 struct GruWs {
     float *h_last, *loss_i, *correct_i, *saved, *dlogits, *dh_last;
+    // stacked models (layer l = 1 .. num_layers - 1): the sequence written by layer l - 1, its saved values, the input gradient it writes
+    float *seq[kRnnMaxLayers], *saved_l[kRnnMaxLayers], *dseq[kRnnMaxLayers];
     size_t bytes;
 };
 
+size_t saved_floats(const kws_model *m, int B)
+{
+    return (size_t)B * m->n_features * (m->kind == KWS_SIMPLE_LSTM ? kLstmSave : kGruSave) * kGruU;
+}
+
+// the one-layer carve first and unchanged, what the upper layers need behind it
 GruWs carve_gru(const kws_model *m, int B, bool training, void *base)
 {
     WsCarver c(base);
@@ -20,9 +28,17 @@ GruWs carve_gru(const kws_model *m, int B, bool training, void *base)
     w.loss_i = c.take(B);
     w.correct_i = c.take(B);
     if (training) {
-        w.saved = c.take((size_t)B * m->n_features * (m->kind == KWS_SIMPLE_LSTM ? kLstmSave : kGruSave) * kGruU);
+        w.saved = c.take(saved_floats(m, B));
         w.dlogits = c.take((size_t)B * m->C);
         w.dh_last = c.take((size_t)B * kGruU);
+    }
+    w.saved_l[0] = w.saved;
+    for (int l = 1; l < m->num_layers; ++l) {
+        w.seq[l] = c.take((size_t)B * m->n_features * kGruU);
+        if (training) {
+            w.saved_l[l] = c.take(saved_floats(m, B));
+            w.dseq[l] = c.take((size_t)B * m->n_features * kGruU);
+        }
     }
     w.bytes = c.off;
     return w;
@@ -41,105 +57,157 @@ constexpr size_t kRnnMaxSmem = 160 * 1024;      // the most dynamic LDS a workgr
 
 const char *rnn_name(const kws_model *m) { return m->kind == KWS_SIMPLE_LSTM ? "LSTM" : "GRU"; }
 
+int layer_width(const kws_model *m, int l) { return l == 0 ? m->feature_size : kGruU; }
+
 // Both kernels keep a 16-clip feature tile in LDS, and the backward tile is the larger one: a geometry whose forward kernel fits and
 // whose backward kernel does not must be refused BEFORE anything is launched, recorded or called back -- the forward kernel clears the
-// caller's gradient buffer.
+// caller's gradient buffer.  Every layer of a stacked model is checked here, before the first one runs.
 int check_tiles(const kws_model *m, bool training)
 {
-    const size_t fwd = gru_fwd_smem(m->n_features, m->feature_size), bwd = gru_bwd_smem(m->n_features, m->feature_size);
-    if (fwd > kRnnMaxSmem)
-        return fail(KWS_ERR_UNSUPPORTED, "%s forward tile of %d x %d needs %zu B of LDS (limit %zu)", rnn_name(m), m->n_features,
-                    m->feature_size, fwd, kRnnMaxSmem);
-    if (training && bwd > kRnnMaxSmem)
-        return fail(KWS_ERR_UNSUPPORTED, "%s backward tile of %d x %d needs %zu B of LDS (limit %zu)", rnn_name(m), m->n_features,
-                    m->feature_size, bwd, kRnnMaxSmem);
+    for (int l = 0; l < m->num_layers; ++l) {
+        const int F = layer_width(m, l);
+        const size_t fwd = gru_fwd_smem(m->n_features, F), bwd = gru_bwd_smem(m->n_features, F);
+        if (fwd > kRnnMaxSmem)
+            return fail(KWS_ERR_UNSUPPORTED, "%s forward tile of %d x %d (layer %d of num_layers = %d) needs %zu B of LDS (limit %zu)",
+                        rnn_name(m), m->n_features, F, l, m->num_layers, fwd, kRnnMaxSmem);
+        if (training && bwd > kRnnMaxSmem)
+            return fail(KWS_ERR_UNSUPPORTED, "%s backward tile of %d x %d (layer %d of num_layers = %d) needs %zu B of LDS (limit %zu)",
+                        rnn_name(m), m->n_features, F, l, m->num_layers, bwd, kRnnMaxSmem);
+    }
     return KWS_OK;
 }
 
-template <int KX>
-int launch_fwd(const kws_model *m, const float *feat, int B, const float *params, GruWs &w, bool save, float rate, uint64_t seed,
-               hipStream_t s, float *zero_buf, long zero_n)
+// one layer's view of the step: its input (B, T, F), where its outputs go, its dropout seed
+struct LayerIo {
+    int l, F;
+    const float *in;
+    float *h_out, *seq_out, *saved;              // forward: last state (last layer) or whole sequence (the others)
+    const float *dh_last, *dseq_in;              // backward: gradient at the last state (last layer) or at every step
+    float *dx_out;                               // backward: input gradient (layers >= 1)
+    uint64_t seed;
+};
+
+LayerIo layer_io(const kws_model *m, int l, const float *feat, const GruWs &w, uint64_t dropout_seed)
 {
-    const int T = m->n_features, F = m->feature_size;
-    const size_t smem = gru_fwd_smem(T, F);
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
-    if (m->kind == KWS_SIMPLE_LSTM) {
-        if (save) {
-            if (smem > 64 * 1024)
-                KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_fwd_kernel<KX, true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            KWS_LAUNCH("lstm_fwd_kernel", (lstm_fwd_kernel<KX, true>), dim3(blocks_for(B, 16)), dim3(kLstmFwdThreads), smem, s, feat, params + m->o_rk,
-                       params + m->o_ru, params + m->o_rb, w.h_last, w.saved, B, T, F, rate, slo, shi, zero_buf, zero_n);
-        } else {
-            if (smem > 64 * 1024)
-                KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_fwd_kernel<KX, false>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            KWS_LAUNCH("lstm_fwd_kernel", (lstm_fwd_kernel<KX, false>), dim3(blocks_for(B, 16)), dim3(kLstmFwdThreads), smem, s, feat, params + m->o_rk,
-                       params + m->o_ru, params + m->o_rb, w.h_last, w.saved, B, T, F, rate, slo, shi);
-        }
-        KWS_LAUNCH_CHECK("lstm_fwd_kernel");
-        return KWS_OK;
-    }
-    if (save) {
-        if (smem > 64 * 1024)
-            KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gru_fwd_kernel<KX, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        KWS_LAUNCH("gru_fwd_kernel", (gru_fwd_kernel<KX, true>), dim3(blocks_for(B, 16)), dim3(kGruFwdThreads), smem, s, feat, params + m->o_rk,
-                   params + m->o_ru, params + m->o_rb, w.h_last, w.saved, B, T, F, rate, slo, shi, zero_buf, zero_n);
-    } else {
-        if (smem > 64 * 1024)
-            KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gru_fwd_kernel<KX, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        KWS_LAUNCH("gru_fwd_kernel", (gru_fwd_kernel<KX, false>), dim3(blocks_for(B, 16)), dim3(kGruFwdThreads), smem, s, feat, params + m->o_rk,
-                   params + m->o_ru, params + m->o_rb, w.h_last, w.saved, B, T, F, rate, slo, shi);
-    }
-    KWS_LAUNCH_CHECK("gru_fwd_kernel");
-    return KWS_OK;
+    const bool last = l == m->num_layers - 1;
+    LayerIo io{};
+    io.l = l; io.F = layer_width(m, l);
+    io.in = l == 0 ? feat : w.seq[l];
+    io.h_out = last ? w.h_last : nullptr;
+    io.seq_out = last ? nullptr : w.seq[l + 1];
+    io.saved = w.saved_l[l];
+    io.dh_last = last ? w.dh_last : nullptr;
+    io.dseq_in = last ? nullptr : w.dseq[l + 1];
+    io.dx_out = l == 0 ? nullptr : w.dseq[l];
+    io.seed = KWS_LAYER_DROPOUT_SEED(dropout_seed, l);
+    return io;
 }
 
-template <int KX>
-int launch_bwd(const kws_model *m, const float *feat, int B, const float *params, float *grads, GruWs &w, float rate, uint64_t seed,
-               hipStream_t s)
+template <typename Kern, typename... Args>
+int launch_rnn(const char *name, Kern kern, unsigned threads, size_t smem, int B, hipStream_t s, Args... args)
 {
-    const int T = m->n_features, F = m->feature_size;
-    const size_t smem = gru_bwd_smem(T, F);
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
-    if (m->kind == KWS_SIMPLE_LSTM) {
-        if (smem > 64 * 1024)
-            KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_bwd_kernel<KX>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        KWS_LAUNCH("lstm_bwd_kernel", lstm_bwd_kernel<KX>, dim3(blocks_for(B, 16)), dim3(kLstmBwdThreads), smem, s, feat, params + m->o_ru, w.saved,
-                   w.dh_last, grads + m->o_rk, grads + m->o_ru, grads + m->o_rb, B, T, F, rate, slo, shi);
-        KWS_LAUNCH_CHECK("lstm_bwd_kernel");
-        return KWS_OK;
-    }
     if (smem > 64 * 1024)
-        KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gru_bwd_kernel<KX>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    KWS_LAUNCH("gru_bwd_kernel", gru_bwd_kernel<KX>, dim3(blocks_for(B, 16)), dim3(kGruBwdThreads), smem, s, feat, params + m->o_ru, w.saved,
-               w.dh_last, grads + m->o_rk, grads + m->o_ru, grads + m->o_rb, B, T, F, rate, slo, shi);
-    KWS_LAUNCH_CHECK("gru_bwd_kernel");
+        KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    KWS_LAUNCH(name, kern, dim3(blocks_for(B, 16)), dim3(threads), smem, s, args...);
+    KWS_LAUNCH_CHECK(name);
     return KWS_OK;
 }
 
-int dispatch_fwd(const kws_model *m, const float *feat, int B, const float *params, GruWs &w, bool save, float rate, uint64_t seed,
-                 hipStream_t s, float *zero_buf = nullptr, long zero_n = 0)
+template <int KX, bool SEQ>
+int launch_fwd(const kws_model *m, const LayerIo &io, int B, const float *params, bool save, float rate, hipStream_t s, float *zero_buf,
+               long zero_n)
 {
-    const int kx = (m->feature_size + 3) / 4;
-    if (kx <= 5) return launch_fwd<5>(m, feat, B, params, w, save, rate, seed, s, zero_buf, zero_n);
-    if (kx <= 10) return launch_fwd<10>(m, feat, B, params, w, save, rate, seed, s, zero_buf, zero_n);
-    return launch_fwd<16>(m, feat, B, params, w, save, rate, seed, s, zero_buf, zero_n);
+    const int T = m->n_features, F = io.F;
+    const size_t smem = gru_fwd_smem(T, F);
+    const uint32_t slo = (uint32_t)(io.seed & 0xFFFFFFFFu), shi = (uint32_t)(io.seed >> 32);
+    if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
+    const float *Wk = params + m->o_lk[io.l], *Uk = params + m->o_lu[io.l], *bias = params + m->o_lb[io.l];
+    if (m->kind == KWS_SIMPLE_LSTM) {
+        if (save)
+            return launch_rnn("lstm_fwd_kernel", &lstm_fwd_kernel<KX, true, SEQ>, kLstmFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out,
+                              io.saved, B, T, F, rate, slo, shi, zero_buf, zero_n, io.seq_out);
+        return launch_rnn("lstm_fwd_kernel", &lstm_fwd_kernel<KX, false, SEQ>, kLstmFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out,
+                          io.saved, B, T, F, rate, slo, shi, (float *)nullptr, 0L, io.seq_out);
+    }
+    if (save)
+        return launch_rnn("gru_fwd_kernel", &gru_fwd_kernel<KX, true, SEQ>, kGruFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out, io.saved,
+                          B, T, F, rate, slo, shi, zero_buf, zero_n, io.seq_out);
+    return launch_rnn("gru_fwd_kernel", &gru_fwd_kernel<KX, false, SEQ>, kGruFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out, io.saved, B,
+                      T, F, rate, slo, shi, (float *)nullptr, 0L, io.seq_out);
 }
 
-int dispatch_bwd(const kws_model *m, const float *feat, int B, const float *params, float *grads, GruWs &w, float rate, uint64_t seed,
-                 hipStream_t s)
+template <int KX, bool DSEQ, bool DX>
+int launch_bwd(const kws_model *m, const LayerIo &io, int B, const float *params, float *grads, float rate, hipStream_t s)
 {
-    const int kx = (m->feature_size + 3) / 4;
-    if (kx <= 5) return launch_bwd<5>(m, feat, B, params, grads, w, rate, seed, s);
-    if (kx <= 10) return launch_bwd<10>(m, feat, B, params, grads, w, rate, seed, s);
-    return launch_bwd<16>(m, feat, B, params, grads, w, rate, seed, s);
+    const int T = m->n_features, F = io.F;
+    const size_t smem = gru_bwd_smem(T, F);
+    const uint32_t slo = (uint32_t)(io.seed & 0xFFFFFFFFu), shi = (uint32_t)(io.seed >> 32);
+    if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
+    const float *Wk = params + m->o_lk[io.l], *Uk = params + m->o_lu[io.l];
+    float *dW = grads + m->o_lk[io.l], *dU = grads + m->o_lu[io.l], *db = grads + m->o_lb[io.l];
+    if (m->kind == KWS_SIMPLE_LSTM)
+        return launch_rnn("lstm_bwd_kernel", &lstm_bwd_kernel<KX, DSEQ, DX>, DX ? kLstmBwdDxThreads : kLstmBwdThreads, smem, B, s, io.in, Uk,
+                          (const float *)io.saved, io.dh_last, dW, dU, db, B, T, F, rate, slo, shi, io.dseq_in, Wk, io.dx_out);
+    return launch_rnn("gru_bwd_kernel", &gru_bwd_kernel<KX, DSEQ, DX>, DX ? kGruBwdDxThreads : kGruBwdThreads, smem, B, s, io.in, Uk,
+                      (const float *)io.saved, io.dh_last, dW, dU, db, B, T, F, rate, slo, shi, io.dseq_in, Wk, io.dx_out);
+}
+
+// Layer 0 takes the template of its width, as the one-layer models always did (their instantiations are SEQ = DSEQ = DX = false and
+// unchanged); the layers above are 48 wide and run the KX = 12 instantiations.
+int dispatch_fwd(const kws_model *m, const LayerIo &io, int B, const float *params, bool save, float rate, hipStream_t s,
+                 float *zero_buf = nullptr, long zero_n = 0)
+{
+    const bool seq = io.seq_out != nullptr;
+    if (io.l > 0)
+        return seq ? launch_fwd<12, true>(m, io, B, params, save, rate, s, zero_buf, zero_n)
+                   : launch_fwd<12, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+    const int kx = (io.F + 3) / 4;
+    if (seq) {
+        if (kx <= 5) return launch_fwd<5, true>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+        if (kx <= 10) return launch_fwd<10, true>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+        return launch_fwd<16, true>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+    }
+    if (kx <= 5) return launch_fwd<5, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+    if (kx <= 10) return launch_fwd<10, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+    return launch_fwd<16, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+}
+
+int dispatch_bwd(const kws_model *m, const LayerIo &io, int B, const float *params, float *grads, float rate, hipStream_t s)
+{
+    const bool dseq = io.dseq_in != nullptr;
+    if (io.l > 0)
+        return dseq ? launch_bwd<12, true, true>(m, io, B, params, grads, rate, s) : launch_bwd<12, false, true>(m, io, B, params, grads, rate, s);
+    const int kx = (io.F + 3) / 4;
+    if (dseq) {
+        if (kx <= 5) return launch_bwd<5, true, false>(m, io, B, params, grads, rate, s);
+        if (kx <= 10) return launch_bwd<10, true, false>(m, io, B, params, grads, rate, s);
+        return launch_bwd<16, true, false>(m, io, B, params, grads, rate, s);
+    }
+    if (kx <= 5) return launch_bwd<5, false, false>(m, io, B, params, grads, rate, s);
+    if (kx <= 10) return launch_bwd<10, false, false>(m, io, B, params, grads, rate, s);
+    return launch_bwd<16, false, false>(m, io, B, params, grads, rate, s);
+}
+
+// forward of layers 0 .. N-1 in order; the first one clears zero_buf (the fused-head chain's gradient buffer) when given
+int forward_layers(const kws_model *m, const float *feat, int B, const float *params, const GruWs &w, bool save, float rate, uint64_t seed,
+                   hipStream_t s, float *zero_buf = nullptr, long zero_n = 0)
+{
+    for (int l = 0; l < m->num_layers; ++l) {
+        const int rc = dispatch_fwd(m, layer_io(m, l, feat, w, seed), B, params, save, rate, s, l == 0 ? zero_buf : nullptr, l == 0 ? zero_n : 0);
+        if (rc) return rc;
+    }
+    return KWS_OK;
+}
+
+// backward of layers N-1 .. 0: each writes the input gradient that the one below adds to its recurrent gradient at every step
+int backward_layers(const kws_model *m, const float *feat, int B, const float *params, float *grads, const GruWs &w, float rate, uint64_t seed,
+                    hipStream_t s)
+{
+    for (int l = m->num_layers - 1; l >= 0; --l) {
+        const int rc = dispatch_bwd(m, layer_io(m, l, feat, w, seed), B, params, grads, rate, s);
+        if (rc) return rc;
+    }
+    return KWS_OK;
 }
 
 }  // namespace
@@ -154,7 +222,7 @@ int gru_forward(kws_model *m, const float *feat, int B, const float *params, voi
     if (rc) return rc;
     rc = check_tiles(m, false);
     if (rc) return rc;
-    rc = dispatch_fwd(m, feat, B, params, w, false, 0.f, 0, s);
+    rc = forward_layers(m, feat, B, params, w, false, 0.f, 0, s);
     if (rc) return rc;
     return run_head(m, B, params, w.h_last, w.loss_i, w.correct_i, nullptr, nullptr, probs, argmax, nullptr, 0.f, nullptr, 0, s);
 }
@@ -168,10 +236,10 @@ int gru_train_fwd_bwd(kws_model *m, const kws_train_args *a, hipStream_t s)
     if (rc) return rc;
     const float rate = a->dropout_seed != 0 ? 0.2f : 0.f;          // GRU / LSTM(dropout=0.2): input dropout, rnn.py:34-35,70-71
     if (head_bwd_fuses(m)) {
-        // The recurrent kernel clears the gradient buffer in its own grid, and the head's forward pass (logits, softmax, loss, dlogits)
+        // The first recurrent kernel clears the gradient buffer in its own grid, and the head's forward pass (logits, softmax, loss, dlogits)
         // runs inside its backward kernel (kws_layers.h: head_bwd_mfma_kernel<.., FWD>), as in the simple_cnn step: between the
         // recurrent forward and backward kernels the chain is ONE launch instead of four (head forward, loss sums, memset, head backward)
-        rc = dispatch_fwd(m, a->feat, a->B, a->params, w, true, rate, a->dropout_seed, s, a->grads, (long)m->P);
+        rc = forward_layers(m, a->feat, a->B, a->params, w, true, rate, a->dropout_seed, s, a->grads, (long)m->P);
         if (rc) return rc;
         const HeadFwdArgs hf{a->params + m->o_hb, a->labels, a->class_weights, a->probs, w.loss_i, w.correct_i, a->grad_scale / (float)a->B, a->ignore_index};
         rc = run_head_bwd(m, a->B, a->params, w.h_last, nullptr, w.dh_last, a->grads, false, s, nullptr, nullptr, nullptr, nullptr, false, &hf);
@@ -179,13 +247,13 @@ int gru_train_fwd_bwd(kws_model *m, const kws_train_args *a, hipStream_t s)
         if (a->overlap_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->overlap_event), s));
         if (a->overlap_callback) a->overlap_callback(a->overlap_user);
         if (a->forward_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->forward_event), s));
-        rc = dispatch_bwd(m, a->feat, a->B, a->params, a->grads, w, rate, a->dropout_seed, s);
+        rc = backward_layers(m, a->feat, a->B, a->params, a->grads, w, rate, a->dropout_seed, s);
         if (rc) return rc;
         if (a->stats) { rc = run_loss_reduce(w.loss_i, w.correct_i, a->B, a->stats, s); if (rc) return rc; }   // fixed-order sums of the per-sample values
         if (a->bucket_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->bucket_event), s));
         return KWS_OK;
     }
-    rc = dispatch_fwd(m, a->feat, a->B, a->params, w, true, rate, a->dropout_seed, s);
+    rc = forward_layers(m, a->feat, a->B, a->params, w, true, rate, a->dropout_seed, s);
     if (rc) return rc;
     rc = run_head(m, a->B, a->params, w.h_last, w.loss_i, w.correct_i, a->labels, a->class_weights, a->probs, nullptr, w.dlogits,
                   a->grad_scale / (float)a->B, a->stats, a->ignore_index, s);
@@ -196,7 +264,7 @@ int gru_train_fwd_bwd(kws_model *m, const kws_train_args *a, hipStream_t s)
     KWS_HIP_CHECK(hipMemsetAsync(a->grads, 0, sizeof(float) * (size_t)m->P, s));
     rc = run_head_bwd(m, a->B, a->params, w.h_last, w.dlogits, w.dh_last, a->grads, false, s);
     if (rc) return rc;
-    rc = dispatch_bwd(m, a->feat, a->B, a->params, a->grads, w, rate, a->dropout_seed, s);
+    rc = backward_layers(m, a->feat, a->B, a->params, a->grads, w, rate, a->dropout_seed, s);
     if (rc) return rc;
     if (a->bucket_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->bucket_event), s));
     return KWS_OK;

@@ -78,9 +78,10 @@ def print_confusion_matrix(cm, class_names):
         print('%*s' % (w, c[:w - 1]) + ''.join('%*d' % (w, v) for v in cm[i]))
 
 
-def main():
+def parse_args(argv=None):
     parser = argparse.ArgumentParser(description='evaluate a trained model (.npz weights) on a dataset')
     parser.add_argument('--model_type', type=str, default='simple_cnn')
+    parser.add_argument('--rnn_layers', type=int, default=1, help="recurrent layers of simple_gru / simple_lstm, 1..4 (the reference's num_layers); the CNN types take 1 only, default=%(default)s")
     parser.add_argument('--weights_path', type=str, required=True)
     parser.add_argument('--dataset_path', type=str, required=True)
     parser.add_argument('--classes_path', type=str, required=True)
@@ -96,17 +97,25 @@ def main():
                              "tensor ('relu6'), or the ranges of least KL divergence of a second, histogram pass ('kl', the reference's MNN "
                              "recipe); simple_gru / simple_lstm: 'dynamic' (dynamic-range int8, no calibration: their only method)")
     parser.add_argument('--save_quantized', type=str, default=None, help='write the int8 model to this .npz')
-    args = parser.parse_args()
+    args = parser.parse_args(argv)
     rnn = args.model_type in RNN_TYPES
+    if args.rnn_layers != 1 and not rnn:
+        parser.error('--rnn_layers %d does not apply to %s: only simple_gru / simple_lstm stack layers' % (args.rnn_layers, args.model_type))
     if args.int8 and args.quant_method is not None and (args.quant_method == 'dynamic') != rnn:
         parser.error("--quant_method %s does not apply to %s: simple_gru / simple_lstm take 'dynamic' only, the CNNs max, relu6 or kl"
                      % (args.quant_method, args.model_type))
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    rnn = args.model_type in RNN_TYPES
     class_names = get_classes(args.classes_path)
     assert class_names[0] == 'background', '1st class should be background.'
     if args.params_path:
         inject_params(args.params_path)
     x, y, _, _ = get_dataset(args.dataset_path, class_names)
-    model = get_model(args.model_type, len(class_names), weights_path=args.weights_path)
+    model = get_model(args.model_type, len(class_names), weights_path=args.weights_path, num_layers=args.rnn_layers)
     acc, cm = evaluate_accuracy(model, x, y, class_names, args.batch_size)
     print('%d correct out of %d samples, accuracy %.4f' % (int(np.trace(cm)), int(cm.sum()), acc))
     print_confusion_matrix(cm, class_names)

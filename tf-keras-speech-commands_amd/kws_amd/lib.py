@@ -237,6 +237,8 @@ def get_lib():
     L.kws_featurize_long.argtypes = [vp, vp, i32, i32, i64, vp, i32, fp, vp]
     u64, f32 = ctypes.c_uint64, ctypes.c_float
     L.kws_model_create.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.kws_model_create_stacked.argtypes = [i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.kws_model_num_layers.argtypes = [vp]
     L.kws_model_destroy.argtypes = [vp]
     L.kws_model_destroy.restype = None
     for n in ("kws_model_param_count", "kws_model_state_count"):

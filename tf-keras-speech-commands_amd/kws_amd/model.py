@@ -16,17 +16,24 @@ def _torch():
 
 
 class ModelSpec(object):
-    """Host-only descriptor (no GPU needed): tensor table in Keras get_weights() order."""
+    """Host-only descriptor (no GPU needed): tensor table in Keras get_weights() order.  num_layers: recurrent layers of simple_gru /
+    simple_lstm, 1..4 (kws_model_create_stacked; the CNN types take 1 only); None, the default, is the plain kws_model_create call,
+    which is the one-layer model."""
 
-    def __init__(self, model_type, num_classes, n_features, feature_size):
+    def __init__(self, model_type, num_classes, n_features, feature_size, num_layers=None):
         if model_type not in _l.MODEL_KINDS:
             raise ValueError('Unsupported model type')            # classifier/model.py:32
         self._L = _l.get_lib()
         self._h = ctypes.c_void_p()
         self.model_type, self.num_classes = model_type, int(num_classes)
         self.n_features, self.feature_size = int(n_features), int(feature_size)
-        _l.check(self._L.kws_model_create(_l.MODEL_KINDS[model_type], self.num_classes, self.n_features,
-                                          self.feature_size, ctypes.byref(self._h)))
+        if num_layers is None:
+            _l.check(self._L.kws_model_create(_l.MODEL_KINDS[model_type], self.num_classes, self.n_features, self.feature_size,
+                                              ctypes.byref(self._h)))
+        else:
+            _l.check(self._L.kws_model_create_stacked(_l.MODEL_KINDS[model_type], self.num_classes, self.n_features,
+                                                      self.feature_size, int(num_layers), ctypes.byref(self._h)))
+        self.num_layers = int(self._L.kws_model_num_layers(self._h))
         self.param_count = int(self._L.kws_model_param_count(self._h))
         self.state_count = int(self._L.kws_model_state_count(self._h))
         self.tensors = []

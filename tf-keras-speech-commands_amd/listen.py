@@ -44,6 +44,7 @@ default_config = {                                     # listen.py:31-40
     "model_path": '',
     "quantized_path": None,
     "model_type": 'simple_cnn',
+    "rnn_layers": 1,
     "classes_path": os.path.join('configs', 'direction_classes.txt'),
     "params_path": None,
     "chunk_size": 1024,
@@ -134,7 +135,8 @@ class Listener(object):
                 raise ValueError("%s has %d classes, %s lists %d" % (self.quantized_path, self.quantized.num_classes, self.classes_path,
                                                                     len(self.class_names)))
             self.model_type = self.quantized.spec.model_type
-        self.model = kwargs.get("model") or get_model(self.model_type, len(self.class_names), weights_path=self.model_path or None)
+        self.model = kwargs.get("model") or get_model(self.model_type, len(self.class_names), weights_path=self.model_path or None,
+                                                      num_layers=self.rnn_layers)
         self.threshold_decoder = ThresholdDecoder(self.pr.threshold_config, self.pr.threshold_center)
         self._sb = self.batch(1)
         self.detector = self._sb                       # detector state lives in the stream batch (device)
@@ -436,6 +438,7 @@ def parse_args(argv=None):
     parser.add_argument('--quantized_path', type=str, default=None,
                         help='stream with an int8 model written by eval.py --save_quantized (instead of, or beside, --model_path)')
     parser.add_argument('--model_type', type=str, default=default_config['model_type'])
+    parser.add_argument('--rnn_layers', type=int, default=default_config['rnn_layers'], help="recurrent layers of simple_gru / simple_lstm, 1..4 (the reference's num_layers); the CNN types take 1 only, default=%(default)s")
     parser.add_argument('--classes_path', type=str, default=default_config['classes_path'])
     parser.add_argument('--params_path', type=str, default=None)
     parser.add_argument('--chunk_size', type=int, default=1024)
@@ -480,6 +483,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if not args.model_path and not args.quantized_path:
         parser.error('one of --model_path and --quantized_path is required')
+    if args.rnn_layers != 1 and args.model_type not in ('simple_gru', 'simple_lstm'):
+        parser.error('--rnn_layers %d does not apply to %s: only simple_gru / simple_lstm stack layers' % (args.rnn_layers, args.model_type))
     if not args.input_wav and not args.synth_from:
         parser.error('one of --input_wav and --synth_from is required')
     if args.synth_from and not args.sweep:

@@ -159,7 +159,7 @@ def main(argv=None):
         losses = SparseCategoricalCrossEntropy()
 
     # get train model
-    model = get_model(args.model_type, num_classes, weights_path=args.weights_path)
+    model = get_model(args.model_type, num_classes, weights_path=args.weights_path, num_layers=args.rnn_layers)
     model.compile(optimizer=optimizer, loss=losses, metrics=['accuracy'])
     model.summary()
 
@@ -277,6 +277,8 @@ def parse_args(argv=None):
     # Model definition options
     parser.add_argument('--model_type', type=str, required=False, default='simple_cnn',
                         help='classifier model type: simple_cnn/simple_cnn_lite/simple_gru/simple_lstm, default=%(default)s')
+    parser.add_argument('--rnn_layers', type=int, required=False, default=1,
+                        help="recurrent layers of simple_gru / simple_lstm, 1..4 (the reference's num_layers); the CNN types take 1 only, default=%(default)s")
     parser.add_argument('--weights_path', type=str, required=False, default=None,
                         help="Pretrained model/weights file for fine tune (the file holds no optimizer state: with --average_type the "
                              "average starts from the loaded weights)")
@@ -386,7 +388,10 @@ def parse_args(argv=None):
     for i in range(len(argv) - 2, -1, -1):
         if argv[i] in ('--loudness_range', '--pitch_range'):
             argv[i:i + 2] = [argv[i] + '=' + argv[i + 1]]
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.rnn_layers != 1 and args.model_type not in ('simple_gru', 'simple_lstm'):
+        parser.error('--rnn_layers %d does not apply to %s: only simple_gru / simple_lstm stack layers' % (args.rnn_layers, args.model_type))
+    return args
 
 
 if __name__ == '__main__':
