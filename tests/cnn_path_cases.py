@@ -100,7 +100,11 @@ def _rows():
     for C, weighted in ((49, False), (100, True)):
         rows.append(Row("c%d" % C, 30, 20, C, 40, weighted, FEAT_SEED["c%d" % C], 2000 + C, 0xC0FFEE00 + C))
     # 3. other feature maps
-    for (nf, fs), weighted in (((29, 13), False), ((40, 24), True), ((24, 16), False), ((62, 21), False)):
+    # ... the last three with the default tail (a2 7 x 5, a3 4 x 3), so the clip-group kernels run off the default map: 28 x 20 without
+    # the pool fused into conv3 (stage 1 is 14 x 10), 30 x 22 without the compact conv2 gradient (stage 1 is 15 x 11, 165 pixels),
+    # 31 x 21 with stage 1 at 15 x 10 behind the per-thread layer 1 of an odd input map
+    for (nf, fs), weighted in (((29, 13), False), ((40, 24), True), ((24, 16), False), ((62, 21), False),
+                               ((28, 20), False), ((30, 22), True), ((31, 21), False)):
         name = "map%dx%d" % (nf, fs)
         rows.append(Row(name, nf, fs, 6, 21, weighted, FEAT_SEED[name], 3000 + nf, 4242 + nf))
     return rows
@@ -111,11 +115,12 @@ FEAT_SEED = {
     "b1": 301, "b3": 303, "b17": 317, "b65": 365, "mw1_b96": 396, "mw2_b468": 5768, "mw3_map62x21_b437": 8184,
     "c49": 549, "c100": 600,
     "map29x13": 2913, "map40x24": 4024, "map24x16": 2416, "map62x21": 6221,
+    "map28x20": 2820, "map30x22": 3022, "map31x21": 3121,
 }
 
 ROWS = _rows()
 ROW = {r.name: r for r in ROWS}
-CAPTURED_ROWS = ("b65", "c49", "map29x13")
+CAPTURED_ROWS = ("b65", "c49", "map29x13", "map28x20")
 
 
 def _cases():

@@ -23,9 +23,9 @@ def head_inputs(kind):
 
 
 # ---- float models -----------------------------------------------------------------------------------------------------
-def features(B, seed):
+def features(B, seed, n_features=30, feature_size=20):
     rng = np.random.default_rng(seed)
-    x = rng.standard_normal((B, 30, 20)) * 3.0
+    x = rng.standard_normal((B, n_features, feature_size)) * 3.0
     x[..., 0] -= 10.0   # MFCC-like: a large negative c0 column
     return x.astype(np.float32)
 
@@ -40,12 +40,12 @@ def penultimate(om, x):
     return h
 
 
-def float_model(kind, C, seed=0, spread=1.5):
+def float_model(kind, C, seed=0, spread=1.5, n_features=30, feature_size=20):
     """oracle weights as tests/test_model_gpu.py's build() perturbs them, BatchNorm moving statistics near those of a feature batch
     (so that inference and training see activations of the same scale), and a head centred on the batch (bias = -mean logit) and
     scaled to logits of standard deviation `spread` over the clips, so that many classes win somewhere; rounded to the device's
     float32"""
-    om = mo.Model(kind, C).init_weights(seed)
+    om = mo.Model(kind, C, n_features=n_features, feature_size=feature_size).init_weights(seed)
     rng = np.random.default_rng(seed + 1)
     ws = om.get_weights()
     for i, (li, n, t) in enumerate(om.weight_list()):
@@ -54,7 +54,7 @@ def float_model(kind, C, seed=0, spread=1.5):
         elif n in ("beta", "bias", "moving_mean"):
             ws[i] = ws[i] + 0.1 * rng.standard_normal(ws[i].shape)
     om.set_weights(ws)
-    h = features(256, seed + 2).astype(np.float64)
+    h = features(256, seed + 2, n_features, feature_size).astype(np.float64)
     h = h[..., None] if om.input_rank == 4 else h
     for l in om.layers[:-1]:
         if isinstance(l, mo.BatchNorm):
@@ -76,7 +76,7 @@ def centre_head(om, x):
 
 def device_model(om, kind=None, C=None):
     from kws_amd.model import DeviceModel, ModelSpec
-    dm = DeviceModel(ModelSpec(kind or om.model_type, C or om.num_classes, 30, 20))
+    dm = DeviceModel(ModelSpec(kind or om.model_type, C or om.num_classes, om.n_features, om.feature_size))
     dm.set_weights([w.astype(np.float32) for w in om.get_weights()])
     return dm
 

@@ -2,7 +2,7 @@
 other than 30 x 20) against the float64 oracle, each with evidence of the kernels it ran.
 
 csrc/kws_cnn_plan.h routes every stage of a call by matrix precision, deterministic mode, graph capture, geometry and class count; the
-rest of the suite meets the oracle almost only in the default combination.  tests/cnn_path_cases.py holds the cases (50: the scenarios
+rest of the suite meets the oracle almost only in the default combination.  tests/cnn_path_cases.py holds the cases (64: the scenarios
 crossed with the modes), the inputs, the shared oracle results and the kernel labels each case must and must not report;
 tests/test_cnn_paths_host.py proves on the oracle alone that every case lists few enough near ties for tests/tie_aware.py to enumerate.
 

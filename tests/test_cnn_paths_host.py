@@ -9,17 +9,17 @@ def test_case_ids_are_unique_and_the_table_is_what_the_modes_ask_for():
     ids = [c.id for c in cc.CASES]
     assert len(ids) == len(set(ids))
     assert len({r.name for r in cc.ROWS}) == len(cc.ROWS)
-    assert len(cc.CASES) == 50
+    assert len(cc.CASES) == 64
     by_mode = {m: [c.row.name for c in cc.CASES if c.mode == m] for m in cc.MODES}
     everything = [r.name for r in cc.ROWS]
     assert by_mode["fp32"] == by_mode["fp32+det"] == everything
     assert by_mode["det"] == [n for n in everything if not n.startswith("mw3")]
-    assert by_mode["default"] == ["c49", "c100", "map29x13", "map40x24", "map24x16", "map62x21"]
+    assert by_mode["default"] == ["c49", "c100", "map29x13", "map40x24", "map24x16", "map62x21", "map28x20", "map30x22", "map31x21"]
     assert by_mode["captured"] == by_mode["captured+fp32"] == list(cc.CAPTURED_ROWS)
     for r in cc.ROWS:
         assert r.dropout_seed != 0 and r.B <= cc.MAX_ORACLE_BATCH
-    # one weighted-loss variant per scenario
-    assert [r.name for r in cc.ROWS if r.weighted] == ["b17", "c100", "map40x24"]
+    # one weighted-loss variant per scenario, and one among the maps with the default tail
+    assert [r.name for r in cc.ROWS if r.weighted] == ["b17", "c100", "map40x24", "map30x22"]
 
 
 def test_restated_mw_rule_gives_the_intended_values():
@@ -78,6 +78,23 @@ def test_label_expectations_tell_the_paths_apart():
     assert "bf16" in lack and {"conv_wgrad<64,128>", "conv_dgrad<64,32>", "conv_gemm_fwd<32,64>"} <= set(have)
     have, lack = cc.expected_labels(cc.ROW["map29x13"], "default")
     assert not any("conv_group" in h for h in have) and "conv_group_fwd<32,64>" in lack
+    # the maps with the default tail off the default map: the clip-group kernels with each of the plan's other switches both ways
+    have, lack = cc.expected_labels(cc.ROW["map28x20"], "default")          # group, no fused pool, acc_bn2 without acc_fwd
+    assert {"conv_group_fwd<32,64>", "bn_act_pool_kernel.L2", "bn_finalize_train_kernel.L2", "conv_wgrad_clip_bf16<16,32>",
+            "l1_moments_kernel", "l1m_act_pool_kernel"} <= set(have)
+    assert {"bn_bwd_finalize_kernel.L2", "bn_bwd_reduce_pool_kernel.L2", "l1_conv2_fwd_bf16<30,20>", "weight_split_kernel"} <= set(lack)
+    have, lack = cc.expected_labels(cc.ROW["map30x22"], "default")          # group, no compact conv2 gradient, per-thread layer 1
+    assert {"conv_group_fwd<32,64>", "conv_wgrad_clip<16,32>", "bn_bwd_reduce_pool_kernel.L2", "bn_bwd_finalize_kernel.L2",
+            "l1_stats_kernel", "weight_split_kernel"} <= set(have)
+    assert {"conv_wgrad_clip_bf16<16,32>", "l1_moments_kernel", "bn_bwd_finalize_kernel.L3"} <= set(lack)
+    have, lack = cc.expected_labels(cc.ROW["map31x21"], "default")          # everything fused behind a per-thread layer 1
+    assert {"conv_group_fwd<32,64>", "l1_stats_kernel", "l1_act_pool_kernel", "weight_split_kernel", "conv_fwd_clip_bf16<16,32>",
+            "dense_head_fused_kernel"} <= set(have)
+    assert {"bn_act_pool_kernel.L2", "bn_act_pool_kernel.L4", "bn_finalize_train_kernel.L2", "bn_bwd_finalize_kernel.L2",
+            "l1_conv2_fwd_bf16<30,20>", "l1_moments_kernel"} <= set(lack)
+    for name, s1 in (("map28x20", (14, 10)), ("map30x22", (15, 11)), ("map31x21", (15, 10))):
+        d = cc.dims(cc.ROW[name].nf, cc.ROW[name].fs)
+        assert (d["H1"], d["W1"]) == s1 and (d["H2"], d["W2"], d["H3"], d["W3"]) == (7, 5, 4, 3)
     # check_labels reports both kinds of complaint
     rep = dict.fromkeys(cc.expected_labels(cc.ROW["b65"], "default")[0])
     assert cc.check_labels(rep, cc.ROW["b65"], "default") == []
