@@ -1116,7 +1116,9 @@ int kws_stream_postprocess(const kws_decoder *dec, const float *probs, int S, in
  * ------------------------------------------------------------------------ */
 
 /* feat (R * n_chunks, F, D): window i of recording r (at r * n_chunks + i) is the matrix of its chunk k0 + i (0-based), cut
- * from rows (R, max_frames, D); lengths: R device int32 sample counts.  Chunks at or past a recording's T give zeros. */
+ * from rows (R, max_frames, D); lengths: R device int32 sample counts.  Chunks at or past a recording's T give zeros.
+ * hop_samples <= window_samples is required (KWS_ERR_INVALID otherwise): only then do the chunk loop's frames start on
+ * multiples of the hop whatever the chunk size. */
 int kws_stream_gather_windows(const float *rows, int R, int max_frames, const int32_t *lengths, int chunk_size,
                               int window_samples, int hop_samples, int F, int D, int64_t k0, int n_chunks, float *feat,
                               void *stream);

@@ -165,6 +165,9 @@ __global__ __launch_bounds__(256) void push_rows_kernel(float *__restrict__ feat
 // (StreamBatch.push per chunk) has after its k-th chunk (1-based) n_k = min(k c, N) samples and -- its carry buffer always
 // starts on a frame boundary -- r_k = 0 if n_k < W else (n_k - W) / H + 1 rows, row j being vectorize_raw of samples
 // [j H, j H + W); the matrix the model sees is rows [r_k - F, r_k), zeros for negative indices (listen.py:92).
+// Precondition: H <= W.  With H > W a push can consume more samples than the carry holds; the loop then empties the carry
+// (listen.py:105) and its next frame starts with the next chunk, not on a multiple of H, so r_k depends on the chunking and
+// this closed form does not hold: kws_stream_gather_windows refuses such a geometry (as kws_amd.stream.scan_plan / scan do).
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ long scan_rows_after(long k, int chunk, long N, int W, int H)
 {
@@ -648,6 +651,9 @@ int kws_stream_gather_windows(const float *rows, int R, int max_frames, const in
     if (R < 0 || n_chunks < 0 || max_frames < 0 || k0 < 0) return fail(KWS_ERR_INVALID, "bad scan geometry R=%d n_chunks=%d max_frames=%d", R, n_chunks, max_frames);
     if (chunk_size < 1 || window_samples < 1 || hop_samples < 1 || F < 1 || D < 1)
         return fail(KWS_ERR_INVALID, "bad chunk_size=%d window=%d hop=%d F=%d D=%d", chunk_size, window_samples, hop_samples, F, D);
+    if (hop_samples > window_samples)
+        return fail(KWS_ERR_INVALID, "hop=%d > window=%d: the chunk loop's frames do not start on multiples of the hop, the scan's closed form "
+                                     "does not hold", hop_samples, window_samples);
     if (R == 0 || n_chunks == 0) return KWS_OK;
     if (!lengths || !feat || (!rows && max_frames > 0)) return fail(KWS_ERR_INVALID, "null argument");
     const long n_windows = (long)R * n_chunks;

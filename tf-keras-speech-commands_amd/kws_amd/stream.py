@@ -195,7 +195,7 @@ class StreamBatch(object):
             n_new = rows.shape[1]
             _l.check(self._L.kws_stream_push_rows(self.mfccs.data_ptr(), rows.data_ptr(), self.S, self.F, self.D, n_new, _stream()))
             used = n_new * self.hop_samples
-            keep = self.n_win - used
+            keep = max(self.n_win - used, 0)              # hop > window: the rows may consume more than is held; the carry empties (listen.py:105)
             if keep > 0:
                 self.win[:, :keep] = self.win[:, used:self.n_win].clone()
             self.n_win = keep
@@ -220,18 +220,29 @@ def scan_plan(n_samples, chunk_size, window_samples, hop_samples, n_features):
     in closed form.  Returns (T, n, r, first):
       T        number of chunks, ceil(N / chunk_size) (the last one may be short, as wave.readframes delivers it);
       n[k-1]   samples that have arrived after chunk k = 1..T: min(k * chunk_size, N);
-      r[k-1]   feature rows that exist after chunk k: the carry buffer always starts on a frame boundary, so
+      r[k-1]   feature rows that exist after chunk k: with hop <= window the carry buffer always starts on a frame boundary, so
                0 if n < window else (n - window) // hop + 1, row j being vectorize_raw of samples [j*hop, j*hop + window);
       first[k-1]  index of the first row of the matrix the model sees at chunk k, r - n_features: the matrix is rows
                [first, r), all-zero rows standing for the negative indices (listen.py:92).
+    Precondition: hop_samples <= window_samples.  With a larger hop a push can consume more samples than the carry buffer holds; the
+    loop then empties the buffer (listen.py:105) and its next frame starts with the next chunk, wherever that falls, so its rows
+    depend on the chunk size and no closed form over the recording gives them: ValueError.
     Pure Python, no device: the kernels behind `scan` compute the same numbers (csrc/kws_stream.hip)."""
     N, c, W, H, F = int(n_samples), int(chunk_size), int(window_samples), int(hop_samples), int(n_features)
     if N < 0 or c < 1 or W < 1 or H < 1 or F < 1:
         raise ValueError("scan_plan needs n_samples >= 0 and positive chunk_size / window / hop / n_features")
+    _check_hop(W, H)
     T = -(-N // c)
     n = [min(k * c, N) for k in range(1, T + 1)]
     r = [0 if v < W else (v - W) // H + 1 for v in n]
     return T, n, r, [v - F for v in r]
+
+
+def _check_hop(window_samples, hop_samples):
+    if hop_samples > window_samples:
+        raise ValueError("hop_samples=%d > window_samples=%d: the chunk loop's frames then start wherever a chunk does, not on multiples "
+                         "of the hop, and the scan's closed form does not hold; run the chunk loop (StreamBatch.push)"
+                         % (hop_samples, window_samples))
 
 
 class ScanResult(object):
@@ -297,6 +308,7 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
         raise ValueError("streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered")
     if class_names is not None:
         assert class_names[0] == 'background', '1st class should be background.'          # listen.py:66
+    _check_hop(pr.window_samples, pr.hop_samples)
     L = _l.get_lib()
     chunk_size, tile = int(chunk_size), int(tile)
     if chunk_size < 1 or tile < 1:
