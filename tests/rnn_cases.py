@@ -1,7 +1,7 @@
 """Case table of the recurrent-model shape tests (tests/test_rnn_shapes_gpu.py, tests/test_rnn_shapes_host.py).
 
-simple_gru and simple_lstm run gru_fwd_kernel / gru_bwd_kernel / lstm_fwd_kernel / lstm_bwd_kernel (csrc/kws_gru.h, csrc/kws_lstm.h),
-launched from csrc/kws_rnn.hip.  Which template runs, whether a launch has to opt in to more than 64 KiB of dynamic LDS, whether the
+simple_gru and simple_lstm run gru_fwd_kernel / gru_bwd_kernel / lstm_fwd_kernel / lstm_bwd_kernel (one template,
+csrc/kws_rnn_kernels.h, with the cells of csrc/kws_gru.h and csrc/kws_lstm.h), launched from csrc/kws_rnn.hip.  Which template runs, whether a launch has to opt in to more than 64 KiB of dynamic LDS, whether the
 geometry is refused and which head chain follows are all plain arithmetic on (T, F, C); that arithmetic is restated below, and the
 table holds one case per branch it can take, per edge of the sequence and batch loops, and per option of the train step.  Everything
 here is host-only (numpy and the float64 oracle): inputs, weights, references and the comparison that both test files apply.
@@ -17,7 +17,7 @@ from oracle import model_oracle as mo
 
 KINDS = ("simple_gru", "simple_lstm")
 
-# ---- the launch arithmetic of csrc/kws_gru.h and csrc/kws_rnn.hip, restated ---------------------------------------------
+# ---- the launch arithmetic of csrc/kws_rnn_kernels.h and csrc/kws_rnn.hip, restated ---------------------------------------------
 UNITS = 48                       # kGruU
 HS, GS, PS = 50, 210, 50         # kGruHS, kGruGS, kGruPS: LDS row strides of the state, gate-gradient and pre-activation tiles
 LDS_DEFAULT = 64 * 1024          # above this a launch calls hipFuncSetAttribute(MaxDynamicSharedMemorySize)

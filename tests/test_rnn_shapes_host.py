@@ -1,5 +1,5 @@
 """The case table of tests/test_rnn_shapes_gpu.py is worth running -- checked on the oracle alone, no device involved: the restated
-launch arithmetic gives the values read off csrc/kws_gru.h, the table reaches every template and branch for both kinds, the float64
+launch arithmetic gives the values read off csrc/kws_rnn_kernels.h, the table reaches every template and branch for both kinds, the float64
 oracle's gradients are finite and do not vanish, and the oracle restated in float32 lies at least rnn_cases.HOST_MARGIN times inside
 every tolerance the device is held to, the per-row one included (so the tolerances are not set by the code under test)."""
 import numpy as np

@@ -1,5 +1,6 @@
 // csrc/kws_rnn.hip -- the recurrent models behind the C ABI: 1 .. 4 stacked GRU(48, linear) or LSTM(48, tanh) -> Dense(C, softmax)
 // (classifier/models/rnn.py:10-43 and 46-79, classifier/model.py:20-29,37).
+#include "kws_gru.h"
 #include "kws_lstm.h"
 #include "kws_model_types.h"
 
@@ -113,7 +114,7 @@ int launch_rnn(const char *name, Kern kern, unsigned threads, size_t smem, int B
     return KWS_OK;
 }
 
-template <int KX, bool SEQ>
+template <class Cell, int KX, bool SEQ>
 int launch_fwd(const kws_model *m, const LayerIo &io, int B, const float *params, bool save, float rate, hipStream_t s, float *zero_buf,
                long zero_n)
 {
@@ -122,21 +123,14 @@ int launch_fwd(const kws_model *m, const LayerIo &io, int B, const float *params
     const uint32_t slo = (uint32_t)(io.seed & 0xFFFFFFFFu), shi = (uint32_t)(io.seed >> 32);
     if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
     const float *Wk = params + m->o_lk[io.l], *Uk = params + m->o_lu[io.l], *bias = params + m->o_lb[io.l];
-    if (m->kind == KWS_SIMPLE_LSTM) {
-        if (save)
-            return launch_rnn("lstm_fwd_kernel", &lstm_fwd_kernel<KX, true, SEQ>, kLstmFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out,
-                              io.saved, B, T, F, rate, slo, shi, zero_buf, zero_n, io.seq_out);
-        return launch_rnn("lstm_fwd_kernel", &lstm_fwd_kernel<KX, false, SEQ>, kLstmFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out,
-                          io.saved, B, T, F, rate, slo, shi, (float *)nullptr, 0L, io.seq_out);
-    }
     if (save)
-        return launch_rnn("gru_fwd_kernel", &gru_fwd_kernel<KX, true, SEQ>, kGruFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out, io.saved,
+        return launch_rnn(Cell::kFwdName, &rnn_fwd_kernel<Cell, KX, true, SEQ>, kGruFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out, io.saved,
                           B, T, F, rate, slo, shi, zero_buf, zero_n, io.seq_out);
-    return launch_rnn("gru_fwd_kernel", &gru_fwd_kernel<KX, false, SEQ>, kGruFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out, io.saved, B,
+    return launch_rnn(Cell::kFwdName, &rnn_fwd_kernel<Cell, KX, false, SEQ>, kGruFwdThreads, smem, B, s, io.in, Wk, Uk, bias, io.h_out, io.saved, B,
                       T, F, rate, slo, shi, (float *)nullptr, 0L, io.seq_out);
 }
 
-template <int KX, bool DSEQ, bool DX>
+template <class Cell, int KX, bool DSEQ, bool DX>
 int launch_bwd(const kws_model *m, const LayerIo &io, int B, const float *params, float *grads, float rate, hipStream_t s)
 {
     const int T = m->n_features, F = io.F;
@@ -145,47 +139,45 @@ int launch_bwd(const kws_model *m, const LayerIo &io, int B, const float *params
     if (smem > kRnnMaxSmem) return fail(KWS_ERR_UNSUPPORTED, "%s tile needs %zu B of LDS", rnn_name(m), smem);
     const float *Wk = params + m->o_lk[io.l], *Uk = params + m->o_lu[io.l];
     float *dW = grads + m->o_lk[io.l], *dU = grads + m->o_lu[io.l], *db = grads + m->o_lb[io.l];
-    if (m->kind == KWS_SIMPLE_LSTM)
-        return launch_rnn("lstm_bwd_kernel", &lstm_bwd_kernel<KX, DSEQ, DX>, DX ? kLstmBwdDxThreads : kLstmBwdThreads, smem, B, s, io.in, Uk,
-                          (const float *)io.saved, io.dh_last, dW, dU, db, B, T, F, rate, slo, shi, io.dseq_in, Wk, io.dx_out);
-    return launch_rnn("gru_bwd_kernel", &gru_bwd_kernel<KX, DSEQ, DX>, DX ? kGruBwdDxThreads : kGruBwdThreads, smem, B, s, io.in, Uk,
+    return launch_rnn(Cell::kBwdName, &rnn_bwd_kernel<Cell, KX, DSEQ, DX>, DX ? kGruBwdDxThreads : kGruBwdThreads, smem, B, s, io.in, Uk,
                       (const float *)io.saved, io.dh_last, dW, dU, db, B, T, F, rate, slo, shi, io.dseq_in, Wk, io.dx_out);
 }
 
-// Layer 0 takes the template of its width, as the one-layer models always did (their instantiations are SEQ = DSEQ = DX = false and
-// unchanged); the layers above are 48 wide and run the KX = 12 instantiations.
-int dispatch_fwd(const kws_model *m, const LayerIo &io, int B, const float *params, bool save, float rate, hipStream_t s,
-                 float *zero_buf = nullptr, long zero_n = 0)
+// Layer 0 takes the template of its width, as the one-layer models always did (their instantiations are SEQ = DSEQ = DX = false); the
+// layers above are 48 wide and run the KX = 12 instantiations, the only ones with DX.  launch(KxTag) starts the kernel of that shape.
+template <int KX_, bool UPPER_>
+struct KxTag {
+    static constexpr int KX = KX_;
+    static constexpr bool UPPER = UPPER_;
+};
+
+template <typename Launch>
+int dispatch_kx(const LayerIo &io, Launch launch)
 {
-    const bool seq = io.seq_out != nullptr;
-    if (io.l > 0)
-        return seq ? launch_fwd<12, true>(m, io, B, params, save, rate, s, zero_buf, zero_n)
-                   : launch_fwd<12, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+    if (io.l > 0) return launch(KxTag<12, true>());
     const int kx = (io.F + 3) / 4;
-    if (seq) {
-        if (kx <= 5) return launch_fwd<5, true>(m, io, B, params, save, rate, s, zero_buf, zero_n);
-        if (kx <= 10) return launch_fwd<10, true>(m, io, B, params, save, rate, s, zero_buf, zero_n);
-        return launch_fwd<16, true>(m, io, B, params, save, rate, s, zero_buf, zero_n);
-    }
-    if (kx <= 5) return launch_fwd<5, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
-    if (kx <= 10) return launch_fwd<10, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
-    return launch_fwd<16, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+    if (kx <= 5) return launch(KxTag<5, false>());
+    if (kx <= 10) return launch(KxTag<10, false>());
+    return launch(KxTag<16, false>());
 }
 
+template <class Cell>
+int dispatch_fwd(const kws_model *m, const LayerIo &io, int B, const float *params, bool save, float rate, hipStream_t s, float *zero_buf,
+                 long zero_n)
+{
+    return dispatch_kx(io, [&](auto k) {
+        return io.seq_out ? launch_fwd<Cell, k.KX, true>(m, io, B, params, save, rate, s, zero_buf, zero_n)
+                          : launch_fwd<Cell, k.KX, false>(m, io, B, params, save, rate, s, zero_buf, zero_n);
+    });
+}
+
+template <class Cell>
 int dispatch_bwd(const kws_model *m, const LayerIo &io, int B, const float *params, float *grads, float rate, hipStream_t s)
 {
-    const bool dseq = io.dseq_in != nullptr;
-    if (io.l > 0)
-        return dseq ? launch_bwd<12, true, true>(m, io, B, params, grads, rate, s) : launch_bwd<12, false, true>(m, io, B, params, grads, rate, s);
-    const int kx = (io.F + 3) / 4;
-    if (dseq) {
-        if (kx <= 5) return launch_bwd<5, true, false>(m, io, B, params, grads, rate, s);
-        if (kx <= 10) return launch_bwd<10, true, false>(m, io, B, params, grads, rate, s);
-        return launch_bwd<16, true, false>(m, io, B, params, grads, rate, s);
-    }
-    if (kx <= 5) return launch_bwd<5, false, false>(m, io, B, params, grads, rate, s);
-    if (kx <= 10) return launch_bwd<10, false, false>(m, io, B, params, grads, rate, s);
-    return launch_bwd<16, false, false>(m, io, B, params, grads, rate, s);
+    return dispatch_kx(io, [&](auto k) {
+        return io.dseq_in ? launch_bwd<Cell, k.KX, true, k.UPPER>(m, io, B, params, grads, rate, s)
+                          : launch_bwd<Cell, k.KX, false, k.UPPER>(m, io, B, params, grads, rate, s);
+    });
 }
 
 // forward of layers 0 .. N-1 in order; the first one clears zero_buf (the fused-head chain's gradient buffer) when given
@@ -193,7 +185,11 @@ int forward_layers(const kws_model *m, const float *feat, int B, const float *pa
                    hipStream_t s, float *zero_buf = nullptr, long zero_n = 0)
 {
     for (int l = 0; l < m->num_layers; ++l) {
-        const int rc = dispatch_fwd(m, layer_io(m, l, feat, w, seed), B, params, save, rate, s, l == 0 ? zero_buf : nullptr, l == 0 ? zero_n : 0);
+        const LayerIo io = layer_io(m, l, feat, w, seed);
+        float *zb = l == 0 ? zero_buf : nullptr;
+        const long zn = l == 0 ? zero_n : 0;
+        const int rc = m->kind == KWS_SIMPLE_LSTM ? dispatch_fwd<LstmCell>(m, io, B, params, save, rate, s, zb, zn)
+                                                  : dispatch_fwd<GruCell>(m, io, B, params, save, rate, s, zb, zn);
         if (rc) return rc;
     }
     return KWS_OK;
@@ -204,7 +200,9 @@ int backward_layers(const kws_model *m, const float *feat, int B, const float *p
                     hipStream_t s)
 {
     for (int l = m->num_layers - 1; l >= 0; --l) {
-        const int rc = dispatch_bwd(m, layer_io(m, l, feat, w, seed), B, params, grads, rate, s);
+        const LayerIo io = layer_io(m, l, feat, w, seed);
+        const int rc = m->kind == KWS_SIMPLE_LSTM ? dispatch_bwd<LstmCell>(m, io, B, params, grads, rate, s)
+                                                  : dispatch_bwd<GruCell>(m, io, B, params, grads, rate, s);
         if (rc) return rc;
     }
     return KWS_OK;
