@@ -38,13 +38,13 @@ def pad_before(n, k, s):
 
 
 def front_ok(nf, fs):
-    """lite_forward / lite_forward_f16 (csrc/kws_model.hip): every stage-1 pixel in a pool window, a haloed map of at most 768 floats"""
+    """lite_front_applies (csrc/kws_lite.h): every stage-1 pixel in a pool window, a haloed map of at most 768 floats"""
     d = dims(nf, fs)
     return nf % 2 == 0 and fs % 2 == 0 and (nf + 2) * (fs + 2) <= 64 * 12 and d["H2"] >= 1 and d["W2"] >= 1
 
 
 def f16_ok(nf, fs, classes=C):
-    """lite_forward_f16: kF16MaxN2 = 35 a2 pixels, kF16MaxP3 = 12 stage-3 pixels, kWdRow = 256 Dense inputs, kF16HeadCols = 48"""
+    """LiteCtx::forward_f16 (lite_front_applies and lite_f16_fits, csrc/kws_lite_f16.h): kF16MaxN2 = 35 a2 pixels, kF16MaxP3 = 12 stage-3 pixels, kWdRow = 256 Dense inputs, kF16HeadCols = 48"""
     d = dims(nf, fs)
     return (front_ok(nf, fs) and d["H2"] * d["W2"] <= 35 and d["H3"] * d["W3"] <= 12 and d["H4"] >= 1 and d["W4"] >= 1
             and classes <= 48 and d["flat"] <= 256)

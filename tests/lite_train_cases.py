@@ -1,6 +1,6 @@
 """Case table of the simple_cnn_lite train-step tests (tests/test_lite_train_gpu.py, tests/test_lite_train_host.py).
 
-The train step of simple_cnn_lite (lite_forward(training = true) and lite_backward, csrc/kws_model.hip) is the only user of
+The train step of simple_cnn_lite (LiteCtx::forward(training = true) and LiteCtx::backward, csrc/kws_model.hip) is the only user of
 dwconv_fwd / dgrad / wgrad_kernel, pw1_fwd / bwd_kernel<16>, partial_finalize_kernel and the 1x1 instantiations of conv_gemm,
 conv_wgrad and conv_dgrad.  Its grids are plain arithmetic on (B, H, W): the block count and rows per block of the channel reductions
 (stat_grid, capped at kStatStride = 1024 blocks), the 16-row tiles per wave of the pointwise data gradients (launch_dgrad's MW), the
@@ -113,14 +113,14 @@ def same_pad_before(n, k, s):
 
 
 def stage_rows(B, nf, fs):
-    """M of the four stages of lite_forward / lite_backward: B * (H0 W0, H1 W1, H3 W3, H3 W3)"""
+    """M of the four stages (CnnStep::pixels over cnn_stage's output maps): B * (H0 W0, H1 W1, H3 W3, H3 W3)"""
     d = dims(nf, fs)
     return (B * d["H0"] * d["W0"], B * d["H1"] * d["W1"], B * d["H3"] * d["W3"], B * d["H3"] * d["W3"])
 
 
 def step_stat_grids(B, nf, fs):
     """every (M, C) that a train step hands to stat_grid: per stage the BatchNorm statistics / bias sums over the stage's channels and
-    the depthwise weight gradient over the depthwise channels, then the Dense bias (lite_backward: stat_grid(B, 128))"""
+    the depthwise weight gradient over the depthwise channels, then the Dense bias (CnnStep::dense_bias_grad: stat_grid(B, 128))"""
     out = []
     for M, C, Cin in zip(stage_rows(B, nf, fs), CHANNELS, DW_CHANNELS):
         out += [(M, C), (M, Cin)]

@@ -1,6 +1,6 @@
 """The train step of simple_cnn_lite at its grid, tile and padding edges, against the float64 oracle (oracle/model_oracle.py).
 
-lite_forward(training = true) and lite_backward (csrc/kws_model.hip) are the only users of the depthwise kernels, of pw1_fwd / bwd_kernel,
+LiteCtx::forward(training = true) and LiteCtx::backward (csrc/kws_model.hip) are the only users of the depthwise kernels, of pw1_fwd / bwd_kernel,
 partial_finalize_kernel and of the 1x1 instantiations of conv_gemm, conv_wgrad and conv_dgrad; the rest of the suite compares them with
 the oracle at B = 40 and 64 on 30 x 20 and at B = 21 on 29 x 13 and 40 x 24.  tests/lite_train_cases.py holds one case per branch of the
 launch arithmetic that those shapes miss (the 1024-block cap of the channel reductions in stages 1 and 2, MW = 2, 3, 4 of

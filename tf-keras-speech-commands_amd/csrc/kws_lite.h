@@ -6,6 +6,7 @@
 #pragma once
 #include "kws_conv.h"
 #include "kws_layers.h"
+#include "kws_model_types.h"
 
 namespace kws {
 
@@ -163,6 +164,11 @@ __host__ __device__ inline int lite_front_floats(int H, int W)
     const int H1 = H / 2, W1 = W / 2, n2 = (H1 / 2) * (W1 / 2), p2 = 16 * ((n2 + 3) / 4);
     const int a = (H + 2) * (W + 2) + H * W, b = p2 * 17;          // xs + d1 share their space with d2 (dead by then)
     return ((H1 + 2) * (W1 + 2) * 16 + (a > b ? a : b) + 3) & ~3;
+}
+// host: the front kernel serves this model geometry (the requirements above, and a map that leaves a2 at least one pixel)
+inline bool lite_front_applies(const CnnDims &d)
+{
+    return d.H0 % 2 == 0 && d.W0 % 2 == 0 && (d.H0 + 2) * (d.W0 + 2) <= 64 * 12 && d.H2 >= 1 && d.W2 >= 1;
 }
 
 // a2h != nullptr: the pooled activation is written as fp16 there instead (fp16 inference, kws_lite_f16.h)

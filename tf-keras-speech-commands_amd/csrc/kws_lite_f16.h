@@ -18,6 +18,7 @@
 #include <hip/hip_fp16.h>
 
 #include "kws_layers.h"
+#include "kws_model_types.h"
 
 namespace kws {
 
@@ -32,6 +33,11 @@ constexpr int kW3Row = 48, kW4Row = 80, kW2Row = 144, kWdRow = 256;
 constexpr int kBlobW3 = 0, kBlobW4 = kBlobW3 + 64 * kW3Row, kBlobW2 = kBlobW4 + 128 * kW4Row,
               kBlobLds = kBlobW2 + kF16HeadCols * kW2Row,      // the part of the blob a block copies into LDS
               kBlobWd = kBlobLds, kBlobHalfs = kBlobWd + 128 * kWdRow;
+// host: maps and class count within these limits (the front kernel, kws_lite.h: lite_front_applies, has to serve the model too)
+inline bool lite_f16_fits(const CnnDims &d, int C)
+{
+    return d.H2 * d.W2 <= kF16MaxN2 && d.H3 * d.W3 <= kF16MaxP3 && d.H4 >= 1 && d.W4 >= 1 && C <= kF16HeadCols && d.flat <= kWdRow;
+}
 
 struct LiteF16Args {
     const float *dwk3, *pwb3, *sc3, *sh3;        // depthwise kernel [9][32], pointwise bias [64], BN scale / shift [64]

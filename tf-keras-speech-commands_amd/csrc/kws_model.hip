@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kws_common.h"
@@ -67,6 +68,17 @@ struct OverlapHook {
 constexpr int kCh[5] = {1, 16, 32, 64, 128};
 constexpr int kMaxStatBlocks = kStatStride;
 
+// Stage l = 0 .. 3 of either CNN: a 3x3 'same' convolution (a SeparableConv2D in simple_cnn_lite) from a (Hi x Wi x Cin) map to
+// (Ho x Wo x Cout), then BatchNorm -> ReLU6 and, where pooled, a 2x2 max-pool.  relu: simple_cnn_lite's pointwise output carries
+// activation='relu' (cnn.py:113,122)
+struct CnnStage { int Hi, Wi, Ho, Wo, stride, Cin, Cout; bool pooled, relu; };
+inline CnnStage cnn_stage(const CnnDims &d, int l)
+{
+    const int Hi[4] = {d.H0, d.H1, d.H2, d.H3}, Wi[4] = {d.W0, d.W1, d.W2, d.W3};
+    const int stride = l == 2 ? 2 : 1;
+    return CnnStage{Hi[l], Wi[l], same_out(Hi[l], stride), same_out(Wi[l], stride), stride, kCh[l], kCh[l + 1], l != 2, l >= 2};
+}
+
 // ---- workspace layout (simple_cnn) ---------------------------------------------------------------------------
 struct CnnWs {
     float *z[4], *a[4], *d1, *loss_i, *correct_i, *dlogits, *dd1, *da4, *gz[4], *da[3];
@@ -95,10 +107,14 @@ CnnWs carve_cnn(const kws_model *m, int B, bool training, unsigned char *base)
         return p;
     };
     const CnnDims &d = m->d;
-    const size_t zs[4] = {(size_t)d.H0 * d.W0 * 16, (size_t)d.H1 * d.W1 * 32, (size_t)d.H3 * d.W3 * 64, (size_t)d.H3 * d.W3 * 128};
-    const size_t as[4] = {(size_t)d.H1 * d.W1 * 16, (size_t)d.H2 * d.W2 * 32, (size_t)d.H3 * d.W3 * 64, (size_t)d.flat};
     const bool lite = m->kind == KWS_SIMPLE_CNN_LITE;
-    const size_t dws[4] = {(size_t)d.H0 * d.W0 * 1, (size_t)d.H1 * d.W1 * 16, (size_t)d.H3 * d.W3 * 32, (size_t)d.H3 * d.W3 * 64};
+    size_t zs[4], as[4], dws[4];        // floats per clip of a stage's convolution output, its activation and (lite) its depthwise output
+    for (int i = 0; i < 4; ++i) {
+        const CnnStage t = cnn_stage(d, i);
+        zs[i] = (size_t)t.Ho * t.Wo * t.Cout;
+        as[i] = t.pooled ? (size_t)(t.Ho / 2) * (t.Wo / 2) * t.Cout : zs[i];
+        dws[i] = (size_t)t.Ho * t.Wo * t.Cin;
+    }
     for (int i = 0; i < 4; ++i) { w.z[i] = take((i == 0 && !lite) ? 0 : zs[i] * B); w.a[i] = take(as[i] * B); }   // simple_cnn never materialises z1 (kws_layer1.h)
     for (int i = 0; i < 4; ++i) w.dwo[i] = take(lite ? dws[i] * B : 0);
     w.d1 = take((size_t)B * 128);
@@ -457,6 +473,19 @@ ConvGeom geom3x3(int B, int H, int W, int stride)
     g.pt = same_pad_before(H, 3, stride); g.pl = same_pad_before(W, 3, stride);
     return g;
 }
+ConvGeom geom1x1(int B, int H, int W)
+{
+    ConvGeom g;
+    g.B = B; g.H = H; g.W = W; g.Ho = H; g.Wo = W; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = 1; g.KW = 1;
+    return g;
+}
+// Dense(128, use_bias=True) + ReLU6 as a (H4 x W4) 'valid' convolution over the pooled map (Flatten is h,w,c)
+static ConvGeom dense_geom(const CnnDims &d, int B)
+{
+    ConvGeom g;
+    g.B = B; g.H = d.H4; g.W = d.W4; g.Ho = 1; g.Wo = 1; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = d.H4; g.KW = d.W4;
+    return g;
+}
 
 // Training forward pass in split precision: 48 extra blocks in the grid of the layer-1 activation kernel
 // (l1m_act_pool_moments_kernel<true>) split the conv3 / conv4 / dense weights into their bf16 planes and 16 clear the gradient
@@ -464,19 +493,42 @@ ConvGeom geom3x3(int B, int H, int W, int stride)
 // (6-8 us each) for 12 us of work that hides under the activation pass.
 constexpr int kPrepSplitBlocks = 16, kPrepZeroBlocks = 16, kPrepBlocks = 3 * kPrepSplitBlocks + kPrepZeroBlocks;
 
-// ---- one call of simple_cnn: what its stage functions share ---------------------------------------------------
-struct CnnCtx {
+// ---- one call of a CNN: what the step contexts of simple_cnn and simple_cnn_lite share -------------------------
+// The helpers are the launches that are the same for both models: BatchNorm's fp32 passes over z[l] / gz[l] and the fp32 Dense layer.
+struct CnnStep {
     const kws_model *m;
     const CnnDims &d;
     int B;
     const float *feat, *params;
     float *state, *grads;           // grads: training
     CnnWs &w;
+    hipStream_t s;                  // the caller's stream
+    uint64_t dropout_seed;
+
+    uint32_t slo() const { return (uint32_t)(dropout_seed & 0xFFFFFFFFu); }
+    uint32_t shi() const { return (uint32_t)(dropout_seed >> 32); }
+    float drop_rate() const { return dropout_seed != 0 ? 0.5f : 0.f; }      // Dropout(0.5) after Flatten, cnn.py:63
+    BnCoef coef(int l) const { return coef_of(w.coef[l], kCh[l + 1]); }
+    // pixels of layer l's convolution output over the batch (stage 3 has stride 2 and no pooling: stage 4 works on the same map)
+    long pixels(int l) const { const CnnStage t = cnn_stage(d, l); return (long)B * t.Ho * t.Wo; }
+
+    int bn_train_coefs(int l, int fused_stat_blocks = 0);
+    int bn_act(int l, float rate, float *zm = nullptr, unsigned char *ag = nullptr);
+    int bn_bwd_finalize(int l, int nblk);
+    template <bool RELU> int bn_bwd_apply(int l);
+    int colsum(const char *label, const float *x, long M, int C, float *dst);
+    int dense_fwd(), dense_bias_grad(), dense_wgrad(hipStream_t on, bool det), dense_dgrad();
+    // the head behind d1 in a launch of its own: an inference's outputs / a train step's loss and dlogits, then the caller's forward event
+    int head_infer(float *probs, int32_t *argmax) { return run_head(m, B, params, w.d1, w.loss_i, w.correct_i, nullptr, nullptr, probs, argmax, nullptr, 0.f, nullptr, 0, s); }
+    int head_train(const kws_train_args *a, float *stats);
+};
+
+// ---- one call of simple_cnn: what its stage functions share ---------------------------------------------------
+struct CnnCtx : CnnStep {
     ModelRes *R;                    // training; inference stays on ONE stream and needs none of the model's resources
-    hipStream_t s, s2;              // the caller's stream; the model's side stream (training)
+    hipStream_t s2;                 // the model's side stream (training)
     const CnnPlan &P;
     OverlapHook *hook;
-    uint64_t seed;
     const double *moments;          // second moments Q of the feature map from the caller (kws_train_args.feat_moments), or nullptr
     const kws_train_args *a;        // training: labels, loss options, events, communicator
     float *probs;                   // inference: where the fused tail leaves the head's outputs
@@ -485,12 +537,6 @@ struct CnnCtx {
     bool bound6;                    // the caller's overlap event rides on layer 4's activation kernel
     int fused_bn3_blocks;           // > 0: conv4's data gradient already did layer 3's BatchNorm-backward reduction
 
-    uint32_t slo() const { return (uint32_t)(seed & 0xFFFFFFFFu); }
-    uint32_t shi() const { return (uint32_t)(seed >> 32); }
-    float drop_rate() const { return seed != 0 ? 0.5f : 0.f; }      // Dropout(0.5) after Flatten, cnn.py:63
-    BnCoef coef(int l) const { return coef_of(w.coef[l], kCh[l + 1]); }
-    // pixels of layer l's convolution output over the batch (conv3 has stride 2 and no pooling: conv4 works on the same map)
-    long pixels(int l) const { return (long)B * (l == 0 ? d.H0 * d.W0 : l == 1 ? d.H1 * d.W1 : d.H3 * d.W3); }
     // the consumer's view of layer l's forward statistics / of its BatchNorm-backward sums
     BnAccFwd acc_in(int l, unsigned parity) const
     {
@@ -501,13 +547,10 @@ struct CnnCtx {
 
     int forward();      // P.fused_tail: the head's outputs are in probs / argmax when it returns (conv2's stage launched the one-kernel tail)
     int fwd_prepare(), fwd_layer1(), fwd_conv2(), fwd_conv3(), fwd_conv4(), fwd_dense();
-    int fwd_bn_finalize(int l, int C, int fused_stat_blocks);
-    int fwd_bn_act(int l, int H, int W, int C, bool pooled, float rate, float *zm = nullptr, unsigned char *ag = nullptr);
     int backward();
     int bwd_head_dense(), bwd_layer4(), bwd_layer3(), bwd_layer2(), bwd_layer1();
     void bwd_arm(int ev) { arm_stop_event(R->ev[ev], s); }
     int bwd_fork(int ev);
-    int bwd_bn_finalize(int l, int C, int nblk);
     int bwd_reduce_pool(int l, int H, int W, int C, float *da, float rate, int nblk, int rows);
 };
 
@@ -621,8 +664,7 @@ int CnnCtx::fwd_layer1()
     }
     if (P.training) {
         KWS_LAUNCH("l1_stats_kernel", l1_stats_kernel<16>, dim3(g.nb), dim3(256), g.smem1, s, feat, kern1, B, d.H0, d.W0, g.cpb, w.partial);
-        KWS_LAUNCH(prof_name("bn_finalize_train_kernel", 1), bn_finalize_train_kernel, dim3(16), dim3(64), 0, s, w.partial, g.nb, pixels(0), 16,
-                   params + m->o_g[0], params + m->o_b[0], state + m->o_mm[0], state + m->o_mv[0], k1);
+        KWS_TRY(bn_train_coefs(0, g.nb));
     }
     if (P.l1m) KWS_LAUNCH("l1m_act_pool_kernel", l1m_act_pool_kernel, dim3(g.nbm), dim3(256), g.smemm, s, feat, kern1, k1.scale, k1.shift, w.a[0], B,
                d.H0, d.W0, g.cpw);
@@ -631,11 +673,12 @@ int CnnCtx::fwd_layer1()
     return KWS_OK;
 }
 
-// Training without the accumulator form: BatchNorm coefficients of conv2 .. conv4 (l = 1 .. 3) from the batch statistics.
+// Training without the accumulator form: BatchNorm coefficients of layer l from the batch statistics of z[l].
 // fused_stat_blocks > 0: the conv kernel already wrote the partial sums of that many blocks
-int CnnCtx::fwd_bn_finalize(int l, int C, int fused_stat_blocks)
+int CnnStep::bn_train_coefs(int l, int fused_stat_blocks)
 {
     const long M = pixels(l);
+    const int C = kCh[l + 1];
     int nblk, rows;
     stat_grid(M, C, nblk, rows);
     if (fused_stat_blocks) nblk = fused_stat_blocks;
@@ -644,12 +687,14 @@ int CnnCtx::fwd_bn_finalize(int l, int C, int fused_stat_blocks)
                params + m->o_b[l], state + m->o_mm[l], state + m->o_mv[l], coef(l));
     return KWS_OK;
 }
-// BatchNorm affine -> ReLU6 (-> 2x2 max-pool, dropout) of conv2 .. conv4 from the coefficients; zm / ag (training): the routed element of
-// every pool window for the backward reduction (layer 2: compact g; layer 4: full-size g)
-int CnnCtx::fwd_bn_act(int l, int H, int W, int C, bool pooled, float rate, float *zm, unsigned char *ag)
+// BatchNorm affine -> ReLU6 (-> 2x2 max-pool, dropout) of layer l from the coefficients; zm / ag (simple_cnn's training): the routed element
+// of every pool window for the backward reduction (layer 2: compact g; layer 4: full-size g)
+int CnnStep::bn_act(int l, float rate, float *zm, unsigned char *ag)
 {
     const BnCoef k = coef(l);
-    if (pooled) {
+    const CnnStage t = cnn_stage(d, l);
+    const int H = t.Ho, W = t.Wo, C = t.Cout;
+    if (t.pooled) {
         const long total = (long)B * (H / 2) * (W / 2) * C;
         KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_kernel<true>, dim3(blocks_for(total, 256)), dim3(256), 0, s, w.z[l], k.scale, k.shift,
                    w.a[l], B, H, W, C, rate, slo(), shi(), zm, ag);
@@ -660,6 +705,49 @@ int CnnCtx::fwd_bn_act(int l, int H, int W, int C, bool pooled, float rate, floa
     }
     return KWS_OK;
 }
+// BatchNorm backward of layer l without the accumulator form: the coefficients k2 / k3 and dgamma / dbeta from nblk blocks' partial sums
+int CnnStep::bn_bwd_finalize(int l, int nblk)
+{
+    const int C = kCh[l + 1];
+    KWS_LAUNCH(prof_name("bn_bwd_finalize_kernel", l + 1), bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, pixels(l), C, params + m->o_g[l],
+               grads + m->o_g[l], grads + m->o_b[l], coef(l));
+    return KWS_OK;
+}
+// ... and dz[l] from g in place (gz[l]) in fp32.  RELU: the convolution in front carries activation='relu'
+template <bool RELU>
+int CnnStep::bn_bwd_apply(int l)
+{
+    const int C = kCh[l + 1];
+    const long total = pixels(l) * C;
+    KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", l + 1), bn_bwd_apply_kernel<RELU>, dim3(blocks_for(total, 256)), dim3(256), 0, s, w.z[l], w.gz[l], coef(l),
+               params + m->o_g[l], total, C);
+    return KWS_OK;
+}
+
+// dst[c] = sum over the M rows of x[.][c]: a bias gradient
+int CnnStep::colsum(const char *label, const float *x, long M, int C, float *dst)
+{
+    int nblk, rows;
+    stat_grid(M, C, nblk, rows);
+    KWS_LAUNCH(label, channel_stats_kernel, dim3(nblk), dim3(256), 0, s, x, M, C, rows, w.partial);
+    KWS_LAUNCH("colsum_finalize_kernel", colsum_finalize_kernel, dim3(C), dim3(256), 0, s, w.partial, nblk, C, dst);
+    return KWS_OK;
+}
+// Keras reduces the per-sample losses with a batch mean (train.py:75-77): d(mean)/d(logits) carries 1/B
+int CnnStep::head_train(const kws_train_args *a, float *stats)
+{
+    KWS_TRY(run_head(m, B, params, w.d1, w.loss_i, w.correct_i, a->labels, a->class_weights, a->probs, nullptr, w.dlogits, a->grad_scale / (float)B,
+                     stats, a->ignore_index, s));
+    if (a->forward_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->forward_event), s));
+    return KWS_OK;
+}
+
+// The Dense layer in fp32: forward with bias and ReLU6, bias gradient (column sums of dd1), weight gradient (on the caller's or the side
+// stream) and data gradient -> da4 (gradient w.r.t. the dropped, flattened map)
+int CnnStep::dense_fwd() { return launch_gemm<128, 128, MODE_FWD, EPI_BIAS_RELU6>(w.a[3], params + m->o_dk, params + m->o_db, w.d1, dense_geom(d, B), s); }
+int CnnStep::dense_bias_grad() { return colsum("channel_stats_kernel.dense", w.dd1, B, 128, grads + m->o_db); }
+int CnnStep::dense_wgrad(hipStream_t on, bool det) { return launch_wgrad<128, 128, 1>(w.a[3], w.dd1, grads + m->o_dk, dense_geom(d, B), on, det); }
+int CnnStep::dense_dgrad() { return launch_dgrad<128, 128, 1>(w.dd1, params + m->o_dk, w.da4, dense_geom(d, B), s); }
 
 // conv2: clip-resident kernel, batch statistics fused into the epilogue when training
 int CnnCtx::fwd_conv2()
@@ -688,9 +776,9 @@ int CnnCtx::fwd_conv2()
                    w.partial, kStatStride);
     if (hook) KWS_TRY(hook->fire(9, s));
     // acc_fwd: the next kernel of the chain derives the coefficients from the accumulator set
-    if (!P.acc_fwd) KWS_TRY(fwd_bn_finalize(1, 32, (int)nblk));
+    if (!P.acc_fwd) KWS_TRY(bn_train_coefs(1, (int)nblk));
     // fuse_pool2: conv3's group kernel forms a2 (and zmax2 / arg2) from z2 while it stages its tile
-    if (!P.fuse_pool2) KWS_TRY(fwd_bn_act(1, d.H1, d.W1, 32, true, 0.f, P.routed_g2 ? w.zmax2 : nullptr, P.routed_g2 ? w.arg2 : nullptr));
+    if (!P.fuse_pool2) KWS_TRY(bn_act(1, 0.f, P.routed_g2 ? w.zmax2 : nullptr, P.routed_g2 ? w.arg2 : nullptr));
     return KWS_OK;
 }
 
@@ -716,10 +804,10 @@ int CnnCtx::fwd_conv3()
         if (fused_stat_blocks < 0) return fused_stat_blocks;
     } else KWS_TRY(launch_gemm<32, 64, MODE_FWD, EPI_NONE>(in, kern, nullptr, w.z[2], g, s));
     if (hook) KWS_TRY(hook->fire(10, s));
-    if (P.training && !P.acc_fwd) KWS_TRY(fwd_bn_finalize(2, 64, fused_stat_blocks));
+    if (P.training && !P.acc_fwd) KWS_TRY(bn_train_coefs(2, fused_stat_blocks));
     // a3_on_load: a3 = relu6(BN3(z3)) is never written -- conv4 forms it from z3 while it stages its rows, and so does conv4's
     // weight gradient (conv3 has no pooling, so the activation is a per-element map)
-    if (!P.a3_on_load) KWS_TRY(fwd_bn_act(2, d.H3, d.W3, 64, false, 0.f));
+    if (!P.a3_on_load) KWS_TRY(bn_act(2, 0.f));
     return KWS_OK;
 }
 
@@ -740,7 +828,7 @@ int CnnCtx::fwd_conv4()
                                                                    P.a3_on_load ? coef(2).scale : nullptr);
         if (fused_stat_blocks < 0) return fused_stat_blocks;
     } else KWS_TRY(launch_gemm<64, 128, MODE_FWD, EPI_RELU>(in, kern, nullptr, w.z[3], g, s));
-    if (P.training && !P.acc_fwd) KWS_TRY(fwd_bn_finalize(3, 128, fused_stat_blocks));
+    if (P.training && !P.acc_fwd) KWS_TRY(bn_train_coefs(3, fused_stat_blocks));
     const float rate = P.training ? drop_rate() : 0.f;
     // behind the last convolution: from here to BN4's backward the main chain is small kernels (activation, dense, head),
     // the best place for the caller to start the next batch's featurizer (kws_train_args.overlap_event)
@@ -757,25 +845,17 @@ int CnnCtx::fwd_conv4()
         const long total = (long)B * (d.H3 / 2) * (d.W3 / 2) * 128;
         KWS_LAUNCH(prof_name("bn_act_pool_kernel", 4), bn_act_pool_acc_kernel, dim3(std::min<unsigned>(1024u, blocks_for(total, 256))), dim3(256), 0, s,
                    w.z[3], acc_in(3, fpar[3]), w.a[3], B, d.H3, d.W3, 128, rate, slo(), shi(), zm, ag);
-    } else KWS_TRY(fwd_bn_act(3, d.H3, d.W3, 128, true, rate, zm, ag));
+    } else KWS_TRY(bn_act(3, rate, zm, ag));
     if (arm6) bound6 = stop_event_bound(hook->ev);
     return KWS_OK;
 }
 
-// Dense(128, use_bias=True) + ReLU6 as a (H4 x W4) 'valid' convolution over the pooled map (Flatten is h,w,c)
-static ConvGeom dense_geom(const CnnDims &d, int B)
-{
-    ConvGeom g;
-    g.B = B; g.H = d.H4; g.W = d.W4; g.Ho = 1; g.Wo = 1; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = d.H4; g.KW = d.W4;
-    return g;
-}
 int CnnCtx::fwd_dense()
 {
-    const ConvGeom g = dense_geom(m->d, B);
     if (hook) KWS_TRY(hook->fire(6, s, bound6));
     if (P.dense_fused) ;                          // d1 is formed by dense_head_fused_kernel (bwd_head_dense)
-    else if (P.bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_FWD, EPI_BIAS_RELU6>("conv_bf16_fwd", w.a[3], w.wsp[2], params + m->o_db, w.d1, g, s));
-    else KWS_TRY(launch_gemm<128, 128, MODE_FWD, EPI_BIAS_RELU6>(w.a[3], params + m->o_dk, params + m->o_db, w.d1, g, s));
+    else if (P.bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_FWD, EPI_BIAS_RELU6>("conv_bf16_fwd", w.a[3], w.wsp[2], params + m->o_db, w.d1, dense_geom(d, B), s));
+    else KWS_TRY(dense_fwd());
     if (hook) KWS_TRY(hook->fire(7, s));
     return KWS_OK;
 }
@@ -811,13 +891,6 @@ int CnnCtx::bwd_fork(int ev)
     return KWS_OK;
 }
 
-// BatchNorm backward of layer l + 1 without the accumulator form: the coefficients k2 / k3 and dgamma / dbeta from nblk blocks' partial sums
-int CnnCtx::bwd_bn_finalize(int l, int C, int nblk)
-{
-    KWS_LAUNCH(prof_name("bn_bwd_finalize_kernel", l + 1), bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, pixels(l), C, params + m->o_g[l],
-               grads + m->o_g[l], grads + m->o_b[l], coef(l));
-    return KWS_OK;
-}
 // the reduction of a pooled layer (2 or 4) with a full-size g and no routing tables: gates by ReLU6, routes through the pool, stores g
 int CnnCtx::bwd_reduce_pool(int l, int H, int W, int C, float *da, float rate, int nblk, int rows)
 {
@@ -867,7 +940,6 @@ int CnnCtx::bwd_head_dense()
         if (a->forward_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->forward_event), s));
         if (hook) KWS_TRY(hook->fire(1, s));
     }
-    const ConvGeom g = dense_geom(d, B);
     const bool hook_ev_here = hook && hook->wants(2) && hook->ev;
     if (hook) KWS_TRY(hook->fire(2, s, fork0_bound && hook_ev_here));
     // its own fork: started later, together with conv4's weight gradient, the step was 2 % slower (same-box A/B)
@@ -879,16 +951,11 @@ int CnnCtx::bwd_head_dense()
     }
     // fused head: the sums of the per-sample losses / correct flags, in a fixed order, off the main chain
     if (P.fuse_head_fwd && stats) KWS_LAUNCH("loss_reduce_kernel", loss_reduce_kernel, dim3(1), dim3(256), 0, s2, w.loss_i, w.correct_i, B, stats);
-    KWS_TRY(launch_wgrad<128, 128, 1>(w.a[3], w.dd1, grads + m->o_dk, g, s2, P.det));
-    if (!P.fuse_head_fwd) {                 // no MFMA head kernel, or deterministic mode: the dense bias gradient takes its own two kernels
-        int nblk, rows;
-        stat_grid(B, 128, nblk, rows);
-        KWS_LAUNCH("channel_stats_kernel.dense", channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.dd1, (long)B, 128, rows, w.partial);
-        KWS_LAUNCH("colsum_finalize_kernel", colsum_finalize_kernel, dim3(128), dim3(256), 0, s, w.partial, nblk, 128, grads + m->o_db);
-    }
+    KWS_TRY(dense_wgrad(s2, P.det));
+    if (!P.fuse_head_fwd) KWS_TRY(dense_bias_grad());     // no MFMA head kernel, or deterministic mode: the dense bias gradient takes its own two kernels
     if (P.dense_fused) ;                        // da4 came out of dense_head_fused_kernel
-    else if (P.bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_DGRAD, EPI_NONE>("conv_bf16_dgrad", w.dd1, w.wsp[2], nullptr, w.da4, g, s));
-    else KWS_TRY(launch_dgrad<128, 128, 1>(w.dd1, params + m->o_dk, w.da4, g, s));
+    else if (P.bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_DGRAD, EPI_NONE>("conv_bf16_dgrad", w.dd1, w.wsp[2], nullptr, w.da4, dense_geom(d, B), s));
+    else KWS_TRY(dense_dgrad());
     if (hook) KWS_TRY(hook->fire(3, s));
     return KWS_OK;
 }
@@ -909,7 +976,7 @@ int CnnCtx::bwd_layer4()
         KWS_LAUNCH(prof_name("bn_bwd_reduce_pool_kernel", 4), bn_bwd_reduce_routed_full_kernel, dim3(nblk), dim3(256), 0, s, w.zmax4, w.arg4, w.da4, k,
                    w.gz[3], B, H, W, C, rows, w.partial, rate, slo(), shi());
     else KWS_TRY(bwd_reduce_pool(3, H, W, C, w.da4, rate, nblk, rows));
-    if (!P.acc_bn4) KWS_TRY(bwd_bn_finalize(3, C, nblk));
+    if (!P.acc_bn4) KWS_TRY(bn_bwd_finalize(3, nblk));
     bwd_arm(3);                          // the apply kernel below is the last one in front of fork(3)
     const Bf16PlanesOut dzp{{w.dzp[0], w.dzp[1], w.dzp[2]}};
     if (P.acc_bn4)
@@ -919,9 +986,7 @@ int CnnCtx::bwd_layer4()
         // split precision: dz4 leaves as bf16 h/m/l planes, which is what both of its consumers stage (no fp32 dz4)
         KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", 4), bn_bwd_apply_planes_kernel<true>, dim3(blocks_for(M * C / 4, 256)), dim3(256), 0, s,
                    w.z[3], w.gz[3], k, gamma, M * C / 4, C, dzp);
-    else
-        KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", 4), bn_bwd_apply_kernel<true>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[3], w.gz[3], k,
-                   gamma, M * C, C);
+    else KWS_TRY(bn_bwd_apply<true>(3));
     if (hook) KWS_TRY(hook->fire(4, s));
     KWS_TRY(bwd_fork(3));                // dz4 is final: wgrad may start on the side stream
     const float *in = w.a[2], *kern = params + m->o_k[3];
@@ -968,14 +1033,12 @@ int CnnCtx::bwd_layer3()
         KWS_LAUNCH(prof_name("bn_bwd_reduce_kernel", 3), bn_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, s, w.z[2], w.da[2], k, w.gz[2], B, H, W, C,
                    rows, w.partial, 0.f, slo(), shi());
     // acc_bn3 (implies the group data gradient of conv4, which put the sums into the accumulator set): the apply kernel derives the coefficients
-    if (!P.acc_bn3) KWS_TRY(bwd_bn_finalize(2, C, nblk));
+    if (!P.acc_bn3) KWS_TRY(bn_bwd_finalize(2, nblk));
     bwd_arm(2);                          // the apply kernel below is the last one in front of fork(2)
     if (P.acc_bn3)
         KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", 3), bn_bwd_apply_acc_kernel<false>, dim3(std::min<unsigned>(1024u, blocks_for(M * C / 4, 256))), dim3(256), 0, s,
                    w.z[2], w.gz[2], k, gamma, M * C / 4, C, acc_out(2));
-    else
-        KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", 3), bn_bwd_apply_kernel<false>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[2], w.gz[2], k,
-                   gamma, M * C, C);
+    else KWS_TRY(bn_bwd_apply<false>(2));
     KWS_TRY(bwd_fork(2));                // dz3 is final: wgrad may start on the side stream
     const float *in = w.a[1], *kern = params + m->o_k[2];
     float *dk = grads + m->o_k[2];
@@ -1013,7 +1076,7 @@ int CnnCtx::bwd_layer2()
     // acc_bn2: the consumers derive k2 / k3 themselves (fork(1) was armed in front of conv3's data gradient)
     if (!P.acc_bn2) {
         if (P.wgrad2_early) bwd_arm(1);  // conv2's early weight gradient forks right behind this finalize kernel
-        KWS_TRY(bwd_bn_finalize(1, C, nblk));
+        KWS_TRY(bn_bwd_finalize(1, nblk));
     }
     const float *in = w.a[0], *kern = params + m->o_k[1];
     float *dk = grads + m->o_k[1];
@@ -1100,7 +1163,7 @@ int CnnCtx::bwd_layer1()
     } else {
         KWS_LAUNCH("l1_bwd_reduce_kernel", l1_bwd_reduce_kernel<16>, dim3(g.nb), dim3(256), g.smem1, s, feat, kern1, w.da[0], k1, B, d.H0, d.W0,
                    g.cpb, w.partial);
-        KWS_TRY(bwd_bn_finalize(0, 16, g.nb));
+        KWS_TRY(bn_bwd_finalize(0, g.nb));
         KWS_LAUNCH("l1_bwd_wgrad_kernel", l1_bwd_wgrad_kernel<16>, dim3(P.det ? 1 : g.nb), dim3(256), g.smem1, s, feat, kern1, w.da[0], k1, params + m->o_g[0],
                    grads + m->o_k[0], B, d.H0, d.W0, P.det ? B : g.cpb);
     }
@@ -1132,44 +1195,66 @@ int CnnCtx::backward()
 
 
 // ---- simple_cnn_lite (cnn.py:77-141) --------------------------------------------------------------------------------
-ConvGeom geom1x1(int B, int H, int W)
+// Every stage is a SeparableConv2D: depthwise 3x3 (dwo[l], kws_lite.h), pointwise 1x1 + bias (z[l], the MFMA kernels of kws_conv.h at the
+// 1x1 geometry; stage 1 has one input channel and its own kernels), then the BatchNorm passes of CnnStep.  One stream, no side resources.
+struct LiteCtx : CnnStep {
+    bool det;                       // training: weight gradients reduced in a fixed order
+    int forward(bool training);     // ... up to d1; the head is the caller's
+    int forward_f16(float *probs, int32_t *argmax);
+    int backward(hipEvent_t bucket_event);
+    int fwd_stage(int l, bool training), bwd_stage(int l);
+};
+
+// hands stage l = 1 .. 3 to f as a compile-time index: the pointwise products are one template instantiation per (Cin, Cout)
+template <typename F>
+int with_lite_stage(int l, F &&f)
 {
-    ConvGeom g;
-    g.B = B; g.H = H; g.W = W; g.Ho = H; g.Wo = W; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = 1; g.KW = 1;
-    return g;
+    switch (l) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
+    }
 }
 
-// Storage / matrix-operand precision of simple_cnn_lite INFERENCE (kws_set_inference_precision): 0 = fp32, 1 = fp16
-
-// fp16 inference (kws_lite_f16.h): front kernel with fp16 output, then ONE kernel from a2 to the probabilities.
-// The fp16 weight blob lives at the head of the (otherwise unused in inference) double partial slab.
-static int lite_forward_f16(const kws_model *m, const float *feat, int B, const float *params, const float *state, CnnWs &w, float *probs,
-                            int32_t *argmax, hipStream_t s)
+// inference: stages 1 and 2 fused, one wave per clip, features -> a2 without touching HBM in between (kws_lite.h: lite_front_applies);
+// a2h: a2 leaves as fp16 there instead (kws_lite_f16.h)
+static int launch_lite_front(const kws_model *m, const float *feat, int B, const float *params, CnnWs &w, _Float16 *a2h, hipStream_t s)
 {
     const CnnDims &d = m->d;
-    const bool front_ok = d.H0 % 2 == 0 && d.W0 % 2 == 0 && (d.H0 + 2) * (d.W0 + 2) <= 64 * 12 && d.H2 >= 1 && d.W2 >= 1;
-    if (!front_ok || d.H2 * d.W2 > kF16MaxN2 || d.H3 * d.W3 > kF16MaxP3 || d.H4 < 1 || d.W4 < 1 || m->C > kF16HeadCols || d.flat > kWdRow)
-        return fail(KWS_ERR_UNSUPPORTED, "fp16 inference of simple_cnn_lite needs a feature map up to about 30 x 20 and at most %d classes "
-                                         "(got %d x %d, %d classes): use KWS_INFER_FP32", kF16HeadCols, d.H0, d.W0, m->C);
-    const bool prepared = m->prepared_for(params, state, w.base, B, matrix_prec(m), infer_prec(m));
-    _Float16 *blob = reinterpret_cast<_Float16 *>(w.partial);
-    if (!prepared) {
-        if (int rc = infer_coefs(m, params, state, w, s)) return rc;
-        KWS_LAUNCH("lite_f16_prepare_kernel", lite_f16_prepare_kernel, dim3(32), dim3(256), 0, s, params + m->o_pwk[2], params + m->o_pwk[3],
-                   params + m->o_dk, params + m->o_hk, m->C, d.flat, blob);
-    }
-    BnCoef k0 = coef_of(w.coef[0], 16), k1 = coef_of(w.coef[1], 32), k2 = coef_of(w.coef[2], 64), k3 = coef_of(w.coef[3], 128);
+    const BnCoef k0 = coef_of(w.coef[0], 16), k1 = coef_of(w.coef[1], 32);
     const LiteFrontArgs fa = {params + m->o_dwk[0], params + m->o_pwk[0], params + m->o_pwb[0], k0.scale, k0.shift,
                               params + m->o_dwk[1], params + m->o_pwk[1], params + m->o_pwb[1], k1.scale, k1.shift};
     const size_t sm = sizeof(float) * (size_t)lite_front_floats(d.H0, d.W0);
     const int waves = cu_count() * std::max(1, std::min(8, (int)(160 * 1024 / sm)));
     const int cpw = std::max(1, (B + waves - 1) / waves), nblk = (B + cpw - 1) / cpw;
-    _Float16 *a2h = reinterpret_cast<_Float16 *>(w.a[1]);
     KWS_LAUNCH("lite_front_infer_kernel", lite_front_infer_kernel, dim3(nblk), dim3(64), sm, s, feat, fa, w.a[1], B, d.H0, d.W0, cpw, a2h);
+    return KWS_OK;
+}
+// the fp16 weight blob (kws_lite_f16.h) lives at the head of the double partial slab, which the inference forward does not use otherwise
+static int prepare_lite_f16(const kws_model *m, const float *params, CnnWs &w, hipStream_t s)
+{
+    KWS_LAUNCH("lite_f16_prepare_kernel", lite_f16_prepare_kernel, dim3(32), dim3(256), 0, s, params + m->o_pwk[2], params + m->o_pwk[3],
+               params + m->o_dk, params + m->o_hk, m->C, m->d.flat, reinterpret_cast<_Float16 *>(w.partial));
+    return KWS_OK;
+}
+
+// fp16 inference (kws_lite_f16.h): front kernel with fp16 output, then ONE kernel from a2 to the probabilities
+int LiteCtx::forward_f16(float *probs, int32_t *argmax)
+{
+    if (!lite_front_applies(d) || !lite_f16_fits(d, m->C))
+        return fail(KWS_ERR_UNSUPPORTED, "fp16 inference of simple_cnn_lite needs a feature map up to about 30 x 20 and at most %d classes "
+                                         "(got %d x %d, %d classes): use KWS_INFER_FP32", kF16HeadCols, d.H0, d.W0, m->C);
+    if (!m->prepared_for(params, state, w.base, B, matrix_prec(m), infer_prec(m))) {
+        KWS_TRY(infer_coefs(m, params, state, w, s));
+        KWS_TRY(prepare_lite_f16(m, params, w, s));
+    }
+    _Float16 *a2h = reinterpret_cast<_Float16 *>(w.a[1]);
+    KWS_TRY(launch_lite_front(m, feat, B, params, w, a2h, s));
+    const BnCoef k2 = coef(2), k3 = coef(3);
     LiteF16Args a;
     a.dwk3 = params + m->o_dwk[2]; a.pwb3 = params + m->o_pwb[2]; a.sc3 = k2.scale; a.sh3 = k2.shift;
     a.dwk4 = params + m->o_dwk[3]; a.pwb4 = params + m->o_pwb[3]; a.sc4 = k3.scale; a.sh4 = k3.shift;
-    a.db = params + m->o_db; a.hb = params + m->o_hb; a.blob = blob;
+    a.db = params + m->o_db; a.hb = params + m->o_hb; a.blob = reinterpret_cast<_Float16 *>(w.partial);
     a.C = m->C; a.H2 = d.H2; a.W2 = d.W2; a.H3 = d.H3; a.W3 = d.W3;
     a.pt3 = same_pad_before(d.H2, 3, 2); a.pl3 = same_pad_before(d.W2, 3, 2); a.H4 = d.H4; a.W4 = d.W4;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(lite_back_f16_kernel), kF16LdsBytes)) return rc;
@@ -1179,140 +1264,96 @@ static int lite_forward_f16(const kws_model *m, const float *feat, int B, const 
     return KWS_OK;
 }
 
-int lite_forward(const kws_model *m, const float *feat, int B, const float *params, float *state, CnnWs &w, bool training,
-                 uint64_t seed, hipStream_t s)
+int LiteCtx::fwd_stage(int l, bool training)
 {
-    const CnnDims &d = m->d;
-    const int Hs[4] = {d.H0, d.H1, d.H2, d.H3}, Ws[4] = {d.W0, d.W1, d.W2, d.W3};
-    const int Hz[4] = {d.H0, d.H1, d.H3, d.H3}, Wz[4] = {d.W0, d.W1, d.W3, d.W3};
-    const int strd[4] = {1, 1, 2, 1};
-    const bool pool[4] = {true, true, false, true};
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
+    const CnnStage t = cnn_stage(d, l);
+    const long M = pixels(l);
+    const float *in = l == 0 ? feat : w.a[l - 1], *pwk = params + m->o_pwk[l], *pwb = params + m->o_pwb[l];
+    KWS_LAUNCH(prof_name("dwconv_fwd_kernel", l + 1), dwconv_fwd_kernel, dim3(blocks_for(M * t.Cin, 256)), dim3(256), 0, s, in,
+               params + m->o_dwk[l], w.dwo[l], geom3x3(B, t.Hi, t.Wi, t.stride), t.Cin);
+    if (l == 0) KWS_LAUNCH("pw1_fwd_kernel", pw1_fwd_kernel<16>, dim3(blocks_for(M * 16, 256)), dim3(256), 0, s, w.dwo[0], pwk, pwb, w.z[0], M);
+    else
+        KWS_TRY(with_lite_stage(l, [&](auto stage) {
+            constexpr int L = decltype(stage)::value;
+            return launch_gemm<kCh[L], kCh[L + 1], MODE_FWD, (L >= 2 ? EPI_BIAS_RELU : EPI_BIAS)>(w.dwo[l], pwk, pwb, w.z[l], geom1x1(B, t.Ho, t.Wo), s);
+        }));
+    if (training) KWS_TRY(bn_train_coefs(l));
+    return bn_act(l, l == 3 ? drop_rate() : 0.f);      // inference: no dropout seed
+}
+
+int LiteCtx::forward(bool training)
+{
     int l_begin = 0;
-    if (!training && !m->prepared_for(params, state, w.base, B, matrix_prec(m), infer_prec(m)))
-        if (int rc = infer_coefs(m, params, state, w, s)) return rc;
-    if (!training && d.H0 % 2 == 0 && d.W0 % 2 == 0 && (d.H0 + 2) * (d.W0 + 2) <= 64 * 12 && d.H2 >= 1 && d.W2 >= 1) {
-        // inference: stages 1 and 2 fused, one wave per clip, features -> a2 without touching HBM in between (kws_lite.h)
-        BnCoef k0 = coef_of(w.coef[0], 16), k1 = coef_of(w.coef[1], 32);
-        const LiteFrontArgs fa = {params + m->o_dwk[0], params + m->o_pwk[0], params + m->o_pwb[0], k0.scale, k0.shift,
-                                  params + m->o_dwk[1], params + m->o_pwk[1], params + m->o_pwb[1], k1.scale, k1.shift};
-        const size_t sm = sizeof(float) * (size_t)lite_front_floats(d.H0, d.W0);
-        const int waves = cu_count() * std::max(1, std::min(8, (int)(160 * 1024 / sm)));
-        const int cpw = std::max(1, (B + waves - 1) / waves), nblk = (B + cpw - 1) / cpw;
-        KWS_LAUNCH("lite_front_infer_kernel", lite_front_infer_kernel, dim3(nblk), dim3(64), sm, s, feat, fa, w.a[1], B, d.H0, d.W0, cpw);
-        l_begin = 2;
-    }
-    for (int l = l_begin; l < 4; ++l) {
-        const float *in = l == 0 ? feat : w.a[l - 1];
-        const int Cin = kCh[l], C = kCh[l + 1];
-        const long M = (long)B * Hz[l] * Wz[l];
-        const ConvGeom g = geom3x3(B, Hs[l], Ws[l], strd[l]);
-        KWS_LAUNCH(prof_name("dwconv_fwd_kernel", l + 1), dwconv_fwd_kernel, dim3(blocks_for(M * Cin, 256)), dim3(256), 0, s, in,
-                   params + m->o_dwk[l], w.dwo[l], g, Cin);
-        const float *pwk = params + m->o_pwk[l], *pwb = params + m->o_pwb[l];
-        const ConvGeom g1 = geom1x1(B, Hz[l], Wz[l]);
-        if (l == 0) KWS_LAUNCH("pw1_fwd_kernel", pw1_fwd_kernel<16>, dim3(blocks_for(M * 16, 256)), dim3(256), 0, s, w.dwo[0], pwk, pwb, w.z[0], M);
-        else if (l == 1) KWS_TRY(launch_gemm<16, 32, MODE_FWD, EPI_BIAS>(w.dwo[1], pwk, pwb, w.z[1], g1, s));
-        else if (l == 2) KWS_TRY(launch_gemm<32, 64, MODE_FWD, EPI_BIAS_RELU>(w.dwo[2], pwk, pwb, w.z[2], g1, s));      // activation='relu', cnn.py:113
-        else KWS_TRY(launch_gemm<64, 128, MODE_FWD, EPI_BIAS_RELU>(w.dwo[3], pwk, pwb, w.z[3], g1, s));                  // cnn.py:122
-        BnCoef k = coef_of(w.coef[l], C);
-        if (training) {
-            int nblk, rows;
-            stat_grid(M, C, nblk, rows);
-            KWS_LAUNCH(prof_name("channel_stats_kernel", l + 1), channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.z[l], M, C, rows, w.partial);
-            KWS_LAUNCH(prof_name("bn_finalize_train_kernel", l + 1), bn_finalize_train_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, M, C,
-                       params + m->o_g[l], params + m->o_b[l], state + m->o_mm[l], state + m->o_mv[l], k);
+    if (!training) {
+        if (!m->prepared_for(params, state, w.base, B, matrix_prec(m), infer_prec(m))) KWS_TRY(infer_coefs(m, params, state, w, s));
+        if (lite_front_applies(d)) {
+            KWS_TRY(launch_lite_front(m, feat, B, params, w, nullptr, s));
+            l_begin = 2;
         }
-        const float rate = (training && l == 3 && seed != 0) ? 0.5f : 0.f;
-        if (pool[l])
-            KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_kernel<true>, dim3(blocks_for((long)B * (Hz[l] / 2) * (Wz[l] / 2) * C, 256)),
-                       dim3(256), 0, s, w.z[l], k.scale, k.shift, w.a[l], B, Hz[l], Wz[l], C, rate, slo, shi);
-        else
-            KWS_LAUNCH(prof_name("bn_act_pool_kernel", l + 1), bn_act_pool_kernel<false>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[l],
-                       k.scale, k.shift, w.a[l], B, Hz[l], Wz[l], C, rate, slo, shi);
     }
-    ConvGeom g;
-    g.B = B; g.H = d.H4; g.W = d.W4; g.Ho = 1; g.Wo = 1; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = d.H4; g.KW = d.W4;
-    KWS_TRY(launch_gemm<128, 128, MODE_FWD, EPI_BIAS_RELU6>(w.a[3], params + m->o_dk, params + m->o_db, w.d1, g, s));
+    for (int l = l_begin; l < 4; ++l) KWS_TRY(fwd_stage(l, training));
+    KWS_TRY(dense_fwd());
     KWS_LAUNCH_CHECK("simple_cnn_lite forward");
     return KWS_OK;
 }
 
-int lite_backward(const kws_model *m, const float *feat, int B, const float *params, float *grads, CnnWs &w, uint64_t seed,
-                  hipEvent_t bucket_event, hipStream_t s)
+// stage l: BatchNorm backward (through dropout, the pool and ReLU6), the pointwise bias / weight / data gradients, the depthwise ones
+int LiteCtx::bwd_stage(int l)
 {
-    const CnnDims &d = m->d;
-    const int Hs[4] = {d.H0, d.H1, d.H2, d.H3}, Ws[4] = {d.W0, d.W1, d.W2, d.W3};
-    const int Hz[4] = {d.H0, d.H1, d.H3, d.H3}, Wz[4] = {d.W0, d.W1, d.W3, d.W3};
-    const int strd[4] = {1, 1, 2, 1};
-    const bool pool[4] = {true, true, false, true};
-    const uint32_t slo = (uint32_t)(seed & 0xFFFFFFFFu), shi = (uint32_t)(seed >> 32);
-    const bool det = m->deterministic != 0;
+    const CnnStage t = cnn_stage(d, l);
+    const int Cin = t.Cin, C = t.Cout;
+    const long M = pixels(l);
+    const float *da = l == 3 ? w.da4 : w.da[l];
+    const BnCoef k = coef(l);
+    int nblk, rows;
+    stat_grid(M, C, nblk, rows);
+    const float rate = l == 3 ? drop_rate() : 0.f;
+    if (t.pooled)
+        KWS_LAUNCH(prof_name("bn_bwd_reduce_kernel", l + 1), bn_bwd_reduce_kernel<true>, dim3(nblk), dim3(256), 0, s, w.z[l], da, k, w.gz[l], B,
+                   t.Ho, t.Wo, C, rows, w.partial, rate, slo(), shi());
+    else
+        KWS_LAUNCH(prof_name("bn_bwd_reduce_kernel", l + 1), bn_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, s, w.z[l], da, k, w.gz[l], B,
+                   t.Ho, t.Wo, C, rows, w.partial, rate, slo(), shi());
+    KWS_TRY(bn_bwd_finalize(l, nblk));
+    KWS_TRY(t.relu ? bn_bwd_apply<true>(l) : bn_bwd_apply<false>(l));
+    // pointwise 1x1 + bias
+    const float *pwk = params + m->o_pwk[l];
+    if (l == 0) {
+        KWS_LAUNCH("pw1_bwd_kernel", pw1_bwd_kernel<16>, dim3(nblk), dim3(256), 0, s, w.dwo[0], pwk, w.gz[0], w.ddw[0], M, rows, w.partial);
+        KWS_LAUNCH("partial_finalize_kernel", partial_finalize_kernel, dim3(16), dim3(256), 0, s, w.partial, nblk, 16, 0, grads + m->o_pwk[0]);
+        KWS_LAUNCH("partial_finalize_kernel", partial_finalize_kernel, dim3(16), dim3(256), 0, s, w.partial, nblk, 16, 1, grads + m->o_pwb[0]);
+    } else {
+        KWS_TRY(colsum(prof_name("channel_stats_kernel.bias", l + 1), w.gz[l], M, C, grads + m->o_pwb[l]));
+        KWS_TRY(with_lite_stage(l, [&](auto stage) {
+            constexpr int L = decltype(stage)::value;
+            const ConvGeom g1 = geom1x1(B, t.Ho, t.Wo);
+            KWS_TRY(launch_wgrad<kCh[L], kCh[L + 1], 1>(w.dwo[l], w.gz[l], grads + m->o_pwk[l], g1, s, det));
+            return launch_dgrad<kCh[L + 1], kCh[L], 1>(w.gz[l], pwk, w.ddw[l], g1, s);
+        }));
+    }
+    // depthwise 3x3
+    const float *in = l == 0 ? feat : w.a[l - 1];
+    const ConvGeom g = geom3x3(B, t.Hi, t.Wi, t.stride);
+    int nb2, rows2;
+    stat_grid(M, Cin, nb2, rows2);
+    KWS_LAUNCH(prof_name("dwconv_wgrad_kernel", l + 1), dwconv_wgrad_kernel, dim3(nb2), dim3(256), 0, s, in, w.ddw[l], g, Cin, rows2, w.partial);
+    KWS_LAUNCH("partial_finalize_kernel", partial_finalize_kernel, dim3(9 * Cin), dim3(256), 0, s, w.partial, nb2, 9 * Cin, 0, grads + m->o_dwk[l]);
+    if (l > 0)
+        KWS_LAUNCH(prof_name("dwconv_dgrad_kernel", l + 1), dwconv_dgrad_kernel, dim3(blocks_for((long)B * t.Hi * t.Wi * Cin, 256)), dim3(256), 0, s,
+                   w.ddw[l], params + m->o_dwk[l], w.da[l - 1], g, Cin);
+    return KWS_OK;
+}
+
+// bucket_event: recorded behind stage 4, when grads[o_k[3] ..] (the early bucket of kws_model_grad_split) are final
+int LiteCtx::backward(hipEvent_t bucket_event)
+{
     KWS_HIP_CHECK(hipMemsetAsync(grads, 0, sizeof(float) * (size_t)m->P, s));
     KWS_TRY(run_head_bwd(m, B, params, w.d1, w.dlogits, w.dd1, grads, true, s, nullptr, nullptr, nullptr, nullptr, det));
-    {
-        ConvGeom g;
-        g.B = B; g.H = d.H4; g.W = d.W4; g.Ho = 1; g.Wo = 1; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = d.H4; g.KW = d.W4;
-        int nblk, rows;
-        stat_grid(B, 128, nblk, rows);
-        KWS_LAUNCH("channel_stats_kernel.dense", channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.dd1, (long)B, 128, rows, w.partial);
-        KWS_LAUNCH("colsum_finalize_kernel", colsum_finalize_kernel, dim3(128), dim3(256), 0, s, w.partial, nblk, 128, grads + m->o_db);
-        KWS_TRY(launch_wgrad<128, 128, 1>(w.a[3], w.dd1, grads + m->o_dk, g, s, det));
-        KWS_TRY(launch_dgrad<128, 128, 1>(w.dd1, params + m->o_dk, w.da4, g, s));
-    }
+    KWS_TRY(dense_bias_grad());
+    KWS_TRY(dense_wgrad(s, det));
+    KWS_TRY(dense_dgrad());
     for (int l = 3; l >= 0; --l) {
-        const int Cin = kCh[l], C = kCh[l + 1];
-        const long M = (long)B * Hz[l] * Wz[l];
-        const float *da = l == 3 ? w.da4 : w.da[l];
-        BnCoef k = coef_of(w.coef[l], C);
-        int nblk, rows;
-        stat_grid(M, C, nblk, rows);
-        const float rate = (l == 3 && seed != 0) ? 0.5f : 0.f;
-        if (pool[l])
-            KWS_LAUNCH(prof_name("bn_bwd_reduce_kernel", l + 1), bn_bwd_reduce_kernel<true>, dim3(nblk), dim3(256), 0, s, w.z[l], da, k, w.gz[l], B,
-                       Hz[l], Wz[l], C, rows, w.partial, rate, slo, shi);
-        else
-            KWS_LAUNCH(prof_name("bn_bwd_reduce_kernel", l + 1), bn_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, s, w.z[l], da, k, w.gz[l], B,
-                       Hz[l], Wz[l], C, rows, w.partial, rate, slo, shi);
-        KWS_LAUNCH(prof_name("bn_bwd_finalize_kernel", l + 1), bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, w.partial, nblk, M, C,
-                   params + m->o_g[l], grads + m->o_g[l], grads + m->o_b[l], k);
-        if (l >= 2)      // sepconv3 and sepconv4 carry activation='relu' (cnn.py:113,122)
-            KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", l + 1), bn_bwd_apply_kernel<true>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[l], w.gz[l],
-                       k, params + m->o_g[l], M * C, C);
-        else
-            KWS_LAUNCH(prof_name("bn_bwd_apply_kernel", l + 1), bn_bwd_apply_kernel<false>, dim3(blocks_for(M * C, 256)), dim3(256), 0, s, w.z[l], w.gz[l],
-                       k, params + m->o_g[l], M * C, C);
-        // pointwise 1x1 + bias
-        const float *pwk = params + m->o_pwk[l];
-        const ConvGeom g1 = geom1x1(B, Hz[l], Wz[l]);
-        if (l == 0) {
-            KWS_LAUNCH("pw1_bwd_kernel", pw1_bwd_kernel<16>, dim3(nblk), dim3(256), 0, s, w.dwo[0], pwk, w.gz[0], w.ddw[0], M, rows, w.partial);
-            KWS_LAUNCH("partial_finalize_kernel", partial_finalize_kernel, dim3(16), dim3(256), 0, s, w.partial, nblk, 16, 0, grads + m->o_pwk[0]);
-            KWS_LAUNCH("partial_finalize_kernel", partial_finalize_kernel, dim3(16), dim3(256), 0, s, w.partial, nblk, 16, 1, grads + m->o_pwb[0]);
-        } else {
-            KWS_LAUNCH(prof_name("channel_stats_kernel.bias", l + 1), channel_stats_kernel, dim3(nblk), dim3(256), 0, s, w.gz[l], M, C, rows, w.partial);
-            KWS_LAUNCH("colsum_finalize_kernel", colsum_finalize_kernel, dim3(C), dim3(256), 0, s, w.partial, nblk, C, grads + m->o_pwb[l]);
-            if (l == 3) {
-                KWS_TRY(launch_wgrad<64, 128, 1>(w.dwo[3], w.gz[3], grads + m->o_pwk[3], g1, s, det));
-                KWS_TRY(launch_dgrad<128, 64, 1>(w.gz[3], pwk, w.ddw[3], g1, s));
-            } else if (l == 2) {
-                KWS_TRY(launch_wgrad<32, 64, 1>(w.dwo[2], w.gz[2], grads + m->o_pwk[2], g1, s, det));
-                KWS_TRY(launch_dgrad<64, 32, 1>(w.gz[2], pwk, w.ddw[2], g1, s));
-            } else {
-                KWS_TRY(launch_wgrad<16, 32, 1>(w.dwo[1], w.gz[1], grads + m->o_pwk[1], g1, s, det));
-                KWS_TRY(launch_dgrad<32, 16, 1>(w.gz[1], pwk, w.ddw[1], g1, s));
-            }
-        }
-        // depthwise 3x3
-        const float *in = l == 0 ? feat : w.a[l - 1];
-        const ConvGeom g = geom3x3(B, Hs[l], Ws[l], strd[l]);
-        int nb2, rows2;
-        stat_grid(M, Cin, nb2, rows2);
-        KWS_LAUNCH(prof_name("dwconv_wgrad_kernel", l + 1), dwconv_wgrad_kernel, dim3(nb2), dim3(256), 0, s, in, w.ddw[l], g, Cin, rows2, w.partial);
-        KWS_LAUNCH("partial_finalize_kernel", partial_finalize_kernel, dim3(9 * Cin), dim3(256), 0, s, w.partial, nb2, 9 * Cin, 0, grads + m->o_dwk[l]);
-        if (l > 0)
-            KWS_LAUNCH(prof_name("dwconv_dgrad_kernel", l + 1), dwconv_dgrad_kernel, dim3(blocks_for((long)B * Hs[l] * Ws[l] * Cin, 256)), dim3(256), 0, s,
-                       w.ddw[l], params + m->o_dwk[l], w.da[l - 1], g, Cin);
+        KWS_TRY(bwd_stage(l));
         if (l == 3 && bucket_event) KWS_HIP_CHECK(hipEventRecord(bucket_event, s));
     }
     KWS_LAUNCH_CHECK("simple_cnn_lite backward");
@@ -1326,6 +1367,75 @@ int check_ws(const kws_model *m, int B, bool training, void *ws, size_t ws_bytes
     w = carve_cnn(m, B, training, static_cast<unsigned char *>(ws));
     if (w.bytes > ws_bytes) return fail(KWS_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", w.bytes, ws_bytes);
     return KWS_OK;
+}
+
+// ---- one inference forward / one train step per family (kws_model_forward, kws_model_train_fwd_bwd) -----------------
+int lite_infer(const CnnStep &st, float *probs, int32_t *argmax)
+{
+    LiteCtx c{st, false};
+    if (infer_prec(c.m) == KWS_INFER_FP16) return c.forward_f16(probs, argmax);
+    KWS_TRY(c.forward(false));
+    return c.head_infer(probs, argmax);
+}
+
+int cnn_infer(const CnnStep &st, float *probs, int32_t *argmax)
+{
+    const kws_model *m = st.m;
+    // no path of the inference forward depends on the stream's capture state
+    const CnnPlan plan = plan_cnn(m, st.B, matrix_prec(m), false, false, true, m->prepared_for(st.params, st.state, st.w.base, st.B, matrix_prec(m), infer_prec(m)));
+    CnnCtx c{st, nullptr, nullptr, plan, nullptr, nullptr, nullptr, probs, argmax};
+    KWS_TRY(c.forward());
+    return plan.fused_tail ? KWS_OK : c.head_infer(probs, argmax);     // fused_tail: conv3 .. softmax ran as one kernel
+}
+
+// simple_cnn_lite has no side stream (and takes no ModelRes): one chain on the caller's stream, the caller's overlap event behind the
+// forward pass (point 1), and both gradient buckets reduced behind the backward pass
+int lite_train_step(const CnnStep &st, const kws_train_args *a)
+{
+    LiteCtx c{st, st.m->deterministic != 0};
+    OverlapHook hook{static_cast<hipEvent_t>(a->overlap_event), a->overlap_callback, a->overlap_user, 1};
+    KWS_TRY(c.forward(true));
+    KWS_TRY(hook.fire(1, c.s));
+    KWS_TRY(c.head_train(a, a->stats));
+    KWS_TRY(c.backward(static_cast<hipEvent_t>(a->bucket_event)));
+    if (!a->comm) return KWS_OK;
+    KWS_TRY(comm_allreduce_early(a->comm, c.grads + c.m->o_k[3], c.m->P - c.m->o_k[3], c.s));
+    return comm_allreduce_late(a->comm, c.grads, c.m->o_k[3], c.state, c.m->S, a->comm_state_weight, c.s);
+}
+
+int cnn_train_step(kws_model *m, const CnnStep &st, const kws_train_args *a)
+{
+    // point 0 = behind the last forward convolution; swept again with the persistent featurizer (same box, ms/step):
+    // 0: 0.722, behind the loss 0.753, behind the head's backward 0.721, behind the dense data gradient 0.734, behind BN4's
+    // backward 0.760, behind conv4's data gradient 0.727
+    // Behind BatchNorm-4's activation kernel, in front of the dense forward product.  Same-box sweeps with the round-2 kernels
+    // (ms per step at B = 4096, four different boxes): behind conv4's forward 0.679-0.697, HERE 0.681-0.691 (never worse than the former,
+    // usually 2-6 us better), behind the dense forward 0.714, behind the forward pass 0.729, behind the dense data gradient 0.704, behind
+    // BatchNorm-4's backward 0.721, behind conv4's data gradient 0.699.  Behind the head's backward kernel (point 2) was the best point on two
+    // boxes (0.686) and the worst on two others (0.709-0.722, whatever the hardware-queue count): the featurizer then starts together with
+    // the side stream's weight-gradient chain, and which of the two gets the chip first decides.  kws_model_set_overlap_point(m, 0 .. 7) re-runs the sweep.
+    // Round 3, after the finalize-free BatchNorm chain (fewer, shorter kernels behind conv4): behind conv3's forward (point 10) 0.548, behind
+    // conv4's forward 0.552, behind BN4's backward 0.556, point 6 0.561, behind layer 1 0.575, behind the loss 0.579 (two rounds, one box):
+    // the featurizer's persistent blocks (62 KB of LDS per CU) then run beside conv4's forward, the activation and the Dense + head kernel,
+    // which fit beside them, and are gone when conv4's data gradient needs 147 KB of every CU.
+    OverlapHook hook{static_cast<hipEvent_t>(a->overlap_event), a->overlap_callback, a->overlap_user, m->overlap_point >= 0 ? m->overlap_point : 10};
+    // ONE plan for both passes (kws_cnn_plan.h); the stream's capture state is queried here, once
+    ModelRes *R = m->dev_res();
+    if (!R) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
+    const CnnPlan plan = plan_cnn(m, st.B, matrix_prec(m), true, stream_is_capturing(st.s), false, false);
+    CnnCtx c{st, R, R->side, plan, &hook, a->feat_moments, a};
+    KWS_TRY(c.forward());
+    // fuse_head_fwd (non-deterministic mode): the head's forward pass rides in its backward kernel (kws_layers.h: head_bwd_mfma_kernel<.., FWD>):
+    // one launch and the dlogits round trip less on the main chain (same-box: -11 us upper bound measured by skipping the launch)
+    if (!plan.fuse_head_fwd) {
+        // head_bwd_fuses: the head's backward kernel also sums the per-sample losses (no separate loss_reduce launch)
+        KWS_TRY(c.head_train(a, plan.head_bwd_fuses ? nullptr : a->stats));
+        KWS_TRY(hook.fire(1, c.s));
+    }
+    KWS_TRY(c.backward());
+    // the early bucket was reduced on the side stream (joined again by now); the rest, and the BatchNormalization moving
+    // statistics, go behind the backward pass on the caller's stream
+    return a->comm ? comm_allreduce_late(a->comm, c.grads, m->o_k[3], c.state, m->S, a->comm_state_weight, c.s) : KWS_OK;
 }
 
 }  // namespace
@@ -1501,9 +1611,7 @@ int kws_model_prepare_inference(kws_model *m, int B, const float *params, const 
         const CnnPlan plan = plan_cnn(m, B, matrix_prec(m), false, false, true, false);
         KWS_TRY(plan.fused_tail ? split_weights_fused(m, params, w, s) : split_weights(m, params, w, s));
     }
-    if (m->kind == KWS_SIMPLE_CNN_LITE && infer_prec(m) == KWS_INFER_FP16)
-        KWS_LAUNCH("lite_f16_prepare_kernel", lite_f16_prepare_kernel, dim3(32), dim3(256), 0, s, params + m->o_pwk[2], params + m->o_pwk[3],
-                   params + m->o_dk, params + m->o_hk, m->C, m->d.flat, reinterpret_cast<_Float16 *>(w.partial));
+    if (m->kind == KWS_SIMPLE_CNN_LITE && infer_prec(m) == KWS_INFER_FP16) KWS_TRY(prepare_lite_f16(m, params, w, s));
     KWS_LAUNCH_CHECK("inference preparation");
     m->prep.params = params; m->prep.state = state; m->prep.ws = ws; m->prep.B = B;
     m->prep.matrix = matrix_prec(m); m->prep.infer = infer_prec(m);
@@ -1668,84 +1776,29 @@ int kws_model_forward(kws_model *m, const float *feat, int B, const float *param
     if (m->kind == KWS_SIMPLE_GRU || m->kind == KWS_SIMPLE_LSTM)
         return gru_forward(m, feat, B, params, ws, ws_bytes, probs, argmax, static_cast<hipStream_t>(stream));
     CnnWs w;
-    int rc = check_ws(m, B, false, ws, ws_bytes, w);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = check_ws(m, B, false, ws, ws_bytes, w)) return rc;
     // a forward that is not the prepared one re-derives the tables in this workspace: whatever was prepared in it is gone
     if (m->prep.ws == ws && !m->prepared_for(params, state, ws, B, matrix_prec(m), infer_prec(m))) m->prep = kws_model::Prepared{};
-    if (m->kind == KWS_SIMPLE_CNN_LITE && infer_prec(m) == KWS_INFER_FP16)
-        return lite_forward_f16(m, feat, B, params, state, w, probs, argmax, s);
-    if (m->kind == KWS_SIMPLE_CNN_LITE) rc = lite_forward(m, feat, B, params, const_cast<float *>(state), w, false, 0, s);
-    else {
-        // no path of the inference forward depends on the stream's capture state
-        const CnnPlan plan = plan_cnn(m, B, matrix_prec(m), false, false, true, m->prepared_for(params, state, ws, B, matrix_prec(m), infer_prec(m)));
-        CnnCtx c{m, m->d, B, feat, params, const_cast<float *>(state), nullptr, w, nullptr, s, nullptr, plan, nullptr, 0, nullptr, nullptr, probs, argmax};
-        rc = c.forward();
-        if (plan.fused_tail) return rc;     // conv3 .. softmax ran as one kernel
-    }
-    if (rc) return rc;
-    return run_head(m, B, params, w.d1, w.loss_i, w.correct_i, nullptr, nullptr, probs, argmax, nullptr, 0.f, nullptr, 0, s);
+    const CnnStep st{m, m->d, B, feat, params, const_cast<float *>(state), nullptr, w, static_cast<hipStream_t>(stream), 0};
+    return m->kind == KWS_SIMPLE_CNN_LITE ? lite_infer(st, probs, argmax) : cnn_infer(st, probs, argmax);
 }
 
 int kws_model_train_fwd_bwd(kws_model *m, const kws_train_args *a, void *stream)
 {
     if (!m || !a || !a->feat || !a->labels || !a->params || !a->state || !a->grads) return fail(KWS_ERR_INVALID, "null argument");
     if (a->B < 1) return fail(KWS_ERR_INVALID, "batch must be >= 1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (m->kind == KWS_SIMPLE_GRU || m->kind == KWS_SIMPLE_LSTM) {
-        if (int rc = gru_train_fwd_bwd(m, a, static_cast<hipStream_t>(stream))) return rc;
+        if (int rc = gru_train_fwd_bwd(m, a, s)) return rc;
         // recurrent models have no BatchNormalization and one bucket: the whole exchange behind the backward pass
-        if (a->comm) return comm_allreduce_late(a->comm, a->grads, m->P, nullptr, 0, 1.f, static_cast<hipStream_t>(stream));
+        if (a->comm) return comm_allreduce_late(a->comm, a->grads, m->P, nullptr, 0, 1.f, s);
         return KWS_OK;
     }
     CnnWs w;
-    int rc = check_ws(m, a->B, true, a->ws, a->ws_bytes, w);
-    if (rc) return rc;
+    if (int rc = check_ws(m, a->B, true, a->ws, a->ws_bytes, w)) return rc;
     m->prep = kws_model::Prepared{};       // a train step rewrites the BatchNorm coefficients (and is followed by a weight update)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool lite = m->kind == KWS_SIMPLE_CNN_LITE;
-    // point 0 = behind the last forward convolution (simple_cnn); swept again with the persistent featurizer (same box, ms/step):
-    // 0: 0.722, behind the loss 0.753, behind the head's backward 0.721, behind the dense data gradient 0.734, behind BN4's
-    // backward 0.760, behind conv4's data gradient 0.727
-    OverlapHook hook;
-    hook.ev = static_cast<hipEvent_t>(a->overlap_event); hook.cb = a->overlap_callback; hook.user = a->overlap_user;
-    // simple_cnn: behind BatchNorm-4's activation kernel, in front of the dense forward product.  Same-box sweeps with the round-2 kernels
-    // (ms per step at B = 4096, four different boxes): behind conv4's forward 0.679-0.697, HERE 0.681-0.691 (never worse than the former,
-    // usually 2-6 us better), behind the dense forward 0.714, behind the forward pass 0.729, behind the dense data gradient 0.704, behind
-    // BatchNorm-4's backward 0.721, behind conv4's data gradient 0.699.  Behind the head's backward kernel (point 2) was the best point on two
-    // boxes (0.686) and the worst on two others (0.709-0.722, whatever the hardware-queue count): the featurizer then starts together with
-    // the side stream's weight-gradient chain, and which of the two gets the chip first decides.  kws_model_set_overlap_point(m, 0 .. 7) re-runs the sweep.
-    // Round 3, after the finalize-free BatchNorm chain (fewer, shorter kernels behind conv4): behind conv3's forward (point 10) 0.548, behind
-    // conv4's forward 0.552, behind BN4's backward 0.556, point 6 0.561, behind layer 1 0.575, behind the loss 0.579 (two rounds, one box):
-    // the featurizer's persistent blocks (62 KB of LDS per CU) then run beside conv4's forward, the activation and the Dense + head kernel,
-    // which fit beside them, and are gone when conv4's data gradient needs 147 KB of every CU.
-    hook.at = lite ? 1 : (m->overlap_point >= 0 ? m->overlap_point : 10);     // kws_model_set_overlap_point re-runs the sweep
-    // simple_cnn: ONE plan for both passes (kws_cnn_plan.h); the stream's capture state is queried here, once
-    ModelRes *R = nullptr;
-    if (!lite && !(R = m->dev_res())) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
-    const CnnPlan plan = lite ? CnnPlan{} : plan_cnn(m, a->B, matrix_prec(m), true, stream_is_capturing(s), false, false);
-    CnnCtx c{m, m->d, a->B, a->feat, a->params, a->state, a->grads, w, R, s, R ? R->side : nullptr, plan, &hook, a->dropout_seed, a->feat_moments, a};
-    rc = lite ? lite_forward(m, a->feat, a->B, a->params, a->state, w, true, a->dropout_seed, s) : c.forward();
-    if (rc) return rc;
-    if (lite) KWS_TRY(hook.fire(1, s));
-    // Keras reduces the per-sample losses with a batch mean (train.py:75-77): d(mean)/d(logits) carries 1/B
-    // simple_cnn: the head's backward kernel also sums the per-sample losses (no separate loss_reduce launch)
-    const bool fuse_stats = !lite && plan.head_bwd_fuses;
-    // simple_cnn (non-deterministic mode): the head's forward pass rides in its backward kernel (kws_layers.h: head_bwd_mfma_kernel<.., FWD>):
-    // one launch and the dlogits round trip less on the main chain (same-box: -11 us upper bound measured by skipping the launch)
-    const bool fuse_head_fwd = !lite && plan.fuse_head_fwd;
-    if (!fuse_head_fwd) {
-        rc = run_head(m, a->B, a->params, w.d1, w.loss_i, w.correct_i, a->labels, a->class_weights, a->probs, nullptr, w.dlogits,
-                      a->grad_scale / (float)a->B, fuse_stats ? nullptr : a->stats, a->ignore_index, s);
-        if (rc) return rc;
-        if (a->forward_event) KWS_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(a->forward_event), s));
-        if (!lite) KWS_TRY(hook.fire(1, s));
-    }
-    rc = lite ? lite_backward(m, a->feat, a->B, a->params, a->grads, w, a->dropout_seed, static_cast<hipEvent_t>(a->bucket_event), s) : c.backward();
-    if (rc || !a->comm) return rc;
-    // simple_cnn reduced its early bucket on the side stream (joined again by now); the rest, and the BatchNormalization moving
-    // statistics, go behind the backward pass on the caller's stream.  simple_cnn_lite has no side stream: both buckets here.
-    if (lite) KWS_TRY(comm_allreduce_early(a->comm, a->grads + m->o_k[3], m->P - m->o_k[3], s));
-    return comm_allreduce_late(a->comm, a->grads, m->o_k[3], a->state, m->S, a->comm_state_weight, s);
+    const CnnStep st{m, m->d, a->B, a->feat, a->params, a->state, a->grads, w, s, a->dropout_seed};
+    return m->kind == KWS_SIMPLE_CNN_LITE ? lite_train_step(st, a) : cnn_train_step(m, st, a);
 }
 
 int kws_set_matrix_precision(int mode)
