@@ -60,8 +60,21 @@ def _sig(v):
     return 1.0 / (1.0 + np.exp(-np.asarray(v, np.float64)))
 
 
-def final_state(kind, arr, feat):
-    """the recurrence: feat (B, T, F) float32 -> h_T (B, 48) float32"""
+def gate_noise(seed, amplitude=1e-6):
+    """a gate_hook for final_state: every gate output moved by a draw uniform within +-amplitude, the absolute error include/kws.h
+    allows the device's sigmoidf_ / tanh_fast_ (one generator per hook: the draws follow the order of the calls)"""
+    rng = np.random.default_rng(seed)
+    return lambda name, t, a, y: y + rng.uniform(-amplitude, amplitude, y.shape)
+
+
+def final_state(kind, arr, feat, gate_hook=None, states=None):
+    """the recurrence: feat (B, T, F) float32 -> h_T (B, 48) float32.
+    gate_hook(name, t, a, y) -> y': called for every gate function of step t (GRU: "z", "r"; LSTM: "i", "f", "g", "o" and "tc", the tanh
+    of the new cell state) with its float32 pre-activation a and its float64 output y (B, 48); what it returns is used in y's place.
+    states: a list that receives h after every step.  With neither, the result is what it was without them, bit for bit."""
+    hook = gate_hook if gate_hook is not None else lambda name, t, a, y: y
+    sig = lambda name, t, a: hook(name, t, a, _sig(a))
+    tanh = lambda name, t, a: hook(name, t, a, np.tanh(a.astype(np.float64)))
     x = np.asarray(feat, np.float32)
     B, T, _ = x.shape
     bias = np.asarray(arr["bias"], np.float32)
@@ -75,16 +88,18 @@ def final_state(kind, arr, feat):
             H = _rescale(_matmul(ch, arr["recurrent_kernel"]), sh, arr["recurrent_scale"])
             if kind == "simple_gru":
                 mx, mh = X + bias[0], H + bias[1]
-                z = _sig(mx[:, :U] + mh[:, :U])
-                r = _sig(mx[:, U:2 * U] + mh[:, U:2 * U])
+                z = sig("z", t, mx[:, :U] + mh[:, :U])
+                r = sig("r", t, mx[:, U:2 * U] + mh[:, U:2 * U])
                 hh = mx[:, 2 * U:].astype(np.float64) + r * mh[:, 2 * U:].astype(np.float64)
                 h = (z * h + (1.0 - z) * hh).astype(np.float32)
             else:
                 a = (X + H) + bias
-                i, f = _sig(a[:, :U]), _sig(a[:, U:2 * U])
-                g, o = np.tanh(a[:, 2 * U:3 * U].astype(np.float64)), _sig(a[:, 3 * U:])
+                i, f = sig("i", t, a[:, :U]), sig("f", t, a[:, U:2 * U])
+                g, o = tanh("g", t, a[:, 2 * U:3 * U]), sig("o", t, a[:, 3 * U:])
                 c = (f * c + i * g).astype(np.float32)
-                h = (o * np.tanh(c.astype(np.float64))).astype(np.float32)
+                h = (o * tanh("tc", t, c)).astype(np.float32)
+            if states is not None:
+                states.append(h)
     return h
 
 
@@ -98,9 +113,9 @@ def head(arr, h):
     return logits.astype(np.float32), probs.astype(np.float32), logits.argmax(1).astype(np.int32)
 
 
-def forward(kind, arr, feat):
+def forward(kind, arr, feat, gate_hook=None):
     """arr: QuantizedRNN.arrays (or quantize()'s dict); feat (B, T, F) float32 -> (logits float32, probs float32, argmax int32)"""
-    return head(arr, final_state(kind, arr, feat))
+    return head(arr, final_state(kind, arr, feat, gate_hook))
 
 
 def float_forward(kind, weights, feat):
