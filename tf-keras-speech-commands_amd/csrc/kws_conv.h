@@ -736,13 +736,21 @@ __device__ __forceinline__ void load_vec(const float *__restrict__ p, float (&v)
 template <int CIN, int COUT, int GPB>
 __global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(const float *__restrict__ x, const float *__restrict__ dz,
                                                                  float *__restrict__ dw, const float *__restrict__ zeros,
-                                                                 ConvGeom g, int steps_per_wave)
+                                                                 ConvGeom g, int steps_per_wave, LossSumJob job)
 {
     constexpr int CB = CIN >= 64 ? 64 : CIN;
     constexpr int CBLK = CIN / CB;
     constexpr int MT = CB / 16, NT = COUT / 16;
     static_assert(CIN % CB == 0 && CB % 16 == 0 && COUT % 16 == 0, "channel counts must be multiples of 16");
     extern __shared__ __attribute__((aligned(16))) float red[];     // [4 waves][64 lanes][4] per tile round
+
+    // A launch that carries a loss-sum job (job.out: the Dense layer's, behind the fused head kernel) has one more column of blocks, which
+    // owns no pixels: its first block forms the step's loss / accuracy sums in the first 4 KB of `red` (kws_device.h: loss_sum_block --
+    // one block, fixed order, no atomics), so the sums need no launch of their own in front of this one on the side stream.
+    if (job.out && blockIdx.x == gridDim.x - 1) {
+        if (blockIdx.y == 0) loss_sum_block(job.loss_i, job.correct_i, job.B, job.out, reinterpret_cast<double *>(red));
+        return;
+    }
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
     const long M = (long)g.B * g.Ho * g.Wo;

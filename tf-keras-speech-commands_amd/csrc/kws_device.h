@@ -134,4 +134,25 @@ __device__ __forceinline__ void acc_clear(double *__restrict__ acc, int tid, int
     for (int i = tid; i < kAccDoubles; i += nthreads) acc[i] = 0.0;
 }
 
+// ---- loss / accuracy sums of a step ----------------------------------------------------------------------------
+// out[0] = sum(loss_i), out[1] = sum(correct_i) by ONE block of 256 threads; `sh` = 512 doubles of LDS.  The order of the sum is fixed
+// -- thread t adds elements t, t + 256, ... in double, then a halving tree over the 256 partials -- so the two floats depend on the
+// per-sample values alone, not on the run or on which kernel hosts the block (loss_reduce_kernel, or the spare block of the Dense
+// weight gradient's launch: kws_conv.h), and every mode reports the same stats.  Contains barriers: every thread of the block calls it.
+struct LossSumJob { const float *loss_i, *correct_i; float *out; int B; };
+__device__ __forceinline__ void loss_sum_block(const float *__restrict__ loss_i, const float *__restrict__ correct_i, int B,
+                                               float *__restrict__ out, double *sh)
+{
+    double s = 0.0, c = 0.0;
+    for (int i = threadIdx.x; i < B; i += 256) { s += (double)loss_i[i]; c += (double)correct_i[i]; }
+    sh[threadIdx.x] = s;
+    sh[256 + threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { sh[threadIdx.x] += sh[threadIdx.x + o]; sh[256 + threadIdx.x] += sh[256 + threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { out[0] = (float)sh[0]; out[1] = (float)sh[256]; }
+}
+
 }  // namespace kws

@@ -555,46 +555,149 @@ __device__ __forceinline__ void bn_bwd_k_prologue(const BnAccBwd &a, const BnCoe
     __syncthreads();
 }
 
+// The two grid-stride apply kernels below (accumulator form) share one unit of work: four consecutive channels of one pixel (a "unit", index i4).
+// bn_bwd_unit is that unit's arithmetic, the same expressions as bn_bwd_apply_kernel, on the operands of channels c0 .. c0 + 3.
+struct BnBwdCh { float mean[4], inv[4], gamma[4], k2[4], k3[4]; };
+__device__ __forceinline__ BnBwdCh bn_bwd_channels(const BnCoef &k, const float *__restrict__ gamma, const float *kk, int C, int c0)
+{
+    BnBwdCh o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        o.mean[j] = k.mean[c0 + j]; o.inv[j] = k.inv[c0 + j]; o.gamma[j] = gamma[c0 + j];
+        o.k2[j] = kk[c0 + j]; o.k3[j] = kk[C + c0 + j];
+    }
+    return o;
+}
+template <bool RELU_IN>
+__device__ __forceinline__ f32x4 bn_bwd_unit(const f32x4 zv, const f32x4 gv, const BnBwdCh &o)
+{
+    f32x4 d;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float xhat = (zv[j] - o.mean[j]) * o.inv[j];
+        float v = o.gamma[j] * o.inv[j] * (gv[j] - o.k2[j] - xhat * o.k3[j]);
+        if (RELU_IN) v = zv[j] > 0.f ? v : 0.f;
+        d[j] = v;
+    }
+    return d;
+}
+// WALK, the loop form of the routed kernel when the host finds (bn_bwd_walk_ok) that
+//   * 256 % (C / 4) == 0: the grid stride is then a multiple of C / 4, a thread keeps its four channels through all of its units and
+//     their operands are loaded once, in front of the loop;
+//   * every byte offset fits 31 bits, so the indices are 32-bit and nothing is divided in 64 bits.
+// A thread takes its units N at a time while it has N left (branch-free, every load of the N units stands before the first use and the
+// first store, so the thread waits for memory once per N units, not three times per unit) and the rest one by one; the loads of the first
+// N are issued in front of the prologue.  Alone at B = 4096 the layer-4 kernel went from 16.1 to 12.5 us (63 MB at 5.0 TB/s).
+// Without WALK the loop decodes every index by division and loads the channel operands per unit: any C % 4 == 0, any size.
+// The in-place kernel of layer 3 keeps the plain loop: the same form measured 12.6 (loads ahead of the prologue) and 13.0 us against
+// the plain loop's 12.3 us -- 38 MB in its 3 units per thread were already at the memory rate behind the prologue.
+constexpr int kBnRoutedUnits = 6;      // what a thread has at B = 4096 under the 1024-block cap (C = 128)
+inline bool bn_bwd_walk_ok(long total4, int C, unsigned blocks, int units)
+{
+    return C % 4 == 0 && 256 % (C / 4) == 0 && (total4 + (long)units * blocks * 256) * 16 < (1L << 31);
+}
+__device__ __forceinline__ f32x4 load_f32x4_at(const float *__restrict__ p, unsigned byte_off)
+{
+    return *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(p) + byte_off);
+}
+// where a thread of the routed kernel stands: clip b, pixel p of the clip's H x W map; a step of the grid stride advances it by (db, dp)
+struct BnWalk { unsigned b, p, db, dp, HW, W, Hp, Wp; };
+
+// units i4, i4 + stride, ..., N of them, all inside the tensor: what their loads bring (bn_routed_load) and the rest (bn_routed_finish)
+template <int N> struct BnRoutedRegs { f32x4 zv[N], g4[N]; unsigned a4[N], e[N]; };
+template <int N>
+__device__ __forceinline__ void bn_routed_load(const float *__restrict__ z, const float *__restrict__ gq, const unsigned char *__restrict__ arg,
+                                               unsigned C, unsigned c0, unsigned i4, unsigned stride, BnWalk &wk, BnRoutedRegs<N> &r)
+{
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const unsigned y = wk.p / wk.W, x = wk.p - y * wk.W;
+        // a pixel outside every pool window reads window 0 and compares with an element index that no byte of arg equals: no branch, and
+        // the loads of gq and arg wait for nothing
+        const bool win = (y >> 1) < wk.Hp && (x >> 1) < wk.Wp;
+        const unsigned q = win ? ((wk.b * wk.Hp + (y >> 1)) * wk.Wp + (x >> 1)) * C + c0 : c0;
+        r.e[u] = win ? (y & 1) * 2 + (x & 1) : 0x100u;
+        r.zv[u] = load_f32x4_at(z, (i4 + u * stride) * 16u);
+        r.g4[u] = load_f32x4_at(gq, q * 4u);
+        r.a4[u] = *reinterpret_cast<const unsigned *>(arg + q);
+        wk.p += wk.dp; wk.b += wk.db;
+        if (wk.p >= wk.HW) { wk.p -= wk.HW; ++wk.b; }
+    }
+}
+template <bool RELU_IN, int N>
+__device__ __forceinline__ void bn_routed_finish(const Bf16PlanesOut &out, const BnBwdCh &ch, unsigned i4, unsigned stride, const BnRoutedRegs<N> &r)
+{
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        f32x4 gv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = ((r.a4[u] >> (8 * j)) & 0xffu) == r.e[u] ? r.g4[u][j] : 0.f;
+        bf16x4 h, m, l;
+        split_bf16(bn_bwd_unit<RELU_IN>(r.zv[u], gv, ch), h, m, l);
+        const unsigned off = (i4 + u * stride) * 8u;
+        *reinterpret_cast<bf16x4 *>(reinterpret_cast<char *>(out.p[0]) + off) = h;
+        *reinterpret_cast<bf16x4 *>(reinterpret_cast<char *>(out.p[1]) + off) = m;
+        *reinterpret_cast<bf16x4 *>(reinterpret_cast<char *>(out.p[2]) + off) = l;
+    }
+}
+
 // Layer 4 (pooled, split precision) from the COMPACT gradient: gq (B, H/2, W/2, C) holds the dropped, gated gradient of every pool window
 // (dense_head_fused_kernel's epilogue), arg the element it belongs to; every other element of z has g = 0.  Same arithmetic as
 // bn_bwd_apply_planes_kernel on the expanded g, without the z-sized fp32 g tensor in between; grid-stride, 256 threads, C <= 128.
-template <bool RELU_IN>
+template <bool RELU_IN, bool WALK>
 __global__ __launch_bounds__(256) void bn_bwd_apply_routed_planes_kernel(const float *__restrict__ z, const float *__restrict__ gq,
                                                                           const unsigned char *__restrict__ arg, BnCoef k,
                                                                           const float *__restrict__ gamma, int B, int H, int W, int C,
                                                                           BnAccBwd a, Bf16PlanesOut out)
 {
     __shared__ float kk[256];
-    bn_bwd_k_prologue(a, k, C, kk);
     const int Hp = H / 2, Wp = W / 2, C4 = C / 4;
-    const long total4 = (long)B * H * W * C4;
-    for (long i4 = (long)blockIdx.x * 256 + threadIdx.x; i4 < total4; i4 += (long)gridDim.x * 256) {
-        const int c0 = (int)(i4 % C4) * 4;
-        const long pix = i4 / C4;
-        const int p = (int)(pix % ((long)H * W)), b = (int)(pix / ((long)H * W)), y = p / W, x = p - y * W, ph = y >> 1, pw = x >> 1;
-        const f32x4 zv = reinterpret_cast<const f32x4 *>(z)[i4];
-        f32x4 gv = {0.f, 0.f, 0.f, 0.f};
-        if (ph < Hp && pw < Wp) {
-            const long q = (((long)b * Hp + ph) * Wp + pw) * C + c0;
-            const f32x4 g4 = *reinterpret_cast<const f32x4 *>(gq + q);
-            const unsigned a4 = *reinterpret_cast<const unsigned *>(arg + q), e = (unsigned)((y & 1) * 2 + (x & 1));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) gv[j] = ((a4 >> (8 * j)) & 0xffu) == e ? g4[j] : 0.f;
+    if constexpr (WALK) {
+        constexpr int kU = kBnRoutedUnits;
+        const unsigned total4 = (unsigned)B * H * W * C4, stride = gridDim.x * 256u, HW = (unsigned)(H * W);
+        const unsigned c0 = threadIdx.x % (unsigned)C4 * 4u;           // blockIdx.x * 256 and the stride are multiples of C4
+        unsigned i4 = blockIdx.x * 256u + threadIdx.x;
+        const unsigned pix = i4 / C4, pstep = stride / C4;              // the only divisions of the index: once per thread
+        BnWalk wk{pix / HW, pix % HW, pstep / HW, pstep % HW, HW, (unsigned)W, (unsigned)Hp, (unsigned)Wp};
+        // the loads of the first kU units fly while the prologue sums the accumulator set: they depend on nothing it produces
+        const bool ahead = i4 + (kU - 1) * stride < total4;
+        BnRoutedRegs<kU> r0;
+        if (ahead) bn_routed_load<kU>(z, gq, arg, C, c0, i4, stride, wk, r0);
+        bn_bwd_k_prologue(a, k, C, kk);
+        const BnBwdCh ch = bn_bwd_channels(k, gamma, kk, C, (int)c0);
+        if (ahead) { bn_routed_finish<RELU_IN, kU>(out, ch, i4, stride, r0); i4 += kU * stride; }
+        for (; i4 + (kU - 1) * stride < total4; i4 += kU * stride) {
+            BnRoutedRegs<kU> r;
+            bn_routed_load<kU>(z, gq, arg, C, c0, i4, stride, wk, r);
+            bn_routed_finish<RELU_IN, kU>(out, ch, i4, stride, r);
         }
-        f32x4 d;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = c0 + j;
-            const float xhat = (zv[j] - k.mean[c]) * k.inv[c];
-            float v = gamma[c] * k.inv[c] * (gv[j] - kk[c] - xhat * kk[C + c]);
-            if (RELU_IN) v = zv[j] > 0.f ? v : 0.f;
-            d[j] = v;
+        for (; i4 < total4; i4 += stride) {
+            BnRoutedRegs<1> r;
+            bn_routed_load<1>(z, gq, arg, C, c0, i4, stride, wk, r);
+            bn_routed_finish<RELU_IN, 1>(out, ch, i4, stride, r);
         }
-        bf16x4 h, m, l;
-        split_bf16(d, h, m, l);
-        reinterpret_cast<bf16x4 *>(out.p[0])[i4] = h;
-        reinterpret_cast<bf16x4 *>(out.p[1])[i4] = m;
-        reinterpret_cast<bf16x4 *>(out.p[2])[i4] = l;
+    } else {
+        bn_bwd_k_prologue(a, k, C, kk);
+        const long total4 = (long)B * H * W * C4;
+        for (long i4 = (long)blockIdx.x * 256 + threadIdx.x; i4 < total4; i4 += (long)gridDim.x * 256) {
+            const int c0 = (int)(i4 % C4) * 4;
+            const long pix = i4 / C4;
+            const int p = (int)(pix % ((long)H * W)), b = (int)(pix / ((long)H * W)), y = p / W, x = p - y * W, ph = y >> 1, pw = x >> 1;
+            const f32x4 zv = reinterpret_cast<const f32x4 *>(z)[i4];
+            f32x4 gv = {0.f, 0.f, 0.f, 0.f};
+            if (ph < Hp && pw < Wp) {
+                const long q = (((long)b * Hp + ph) * Wp + pw) * C + c0;
+                const f32x4 g4 = *reinterpret_cast<const f32x4 *>(gq + q);
+                const unsigned a4 = *reinterpret_cast<const unsigned *>(arg + q), e = (unsigned)((y & 1) * 2 + (x & 1));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gv[j] = ((a4 >> (8 * j)) & 0xffu) == e ? g4[j] : 0.f;
+            }
+            bf16x4 h, m, l;
+            split_bf16(bn_bwd_unit<RELU_IN>(zv, gv, bn_bwd_channels(k, gamma, kk, C, c0)), h, m, l);
+            reinterpret_cast<bf16x4 *>(out.p[0])[i4] = h;
+            reinterpret_cast<bf16x4 *>(out.p[1])[i4] = m;
+            reinterpret_cast<bf16x4 *>(out.p[2])[i4] = l;
+        }
     }
 }
 
@@ -607,18 +710,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_acc_kernel(const float *__re
     bn_bwd_k_prologue(a, k, C, kk);
     const int C4 = C / 4;
     for (long i4 = (long)blockIdx.x * 256 + threadIdx.x; i4 < total4; i4 += (long)gridDim.x * 256) {
-        const int c0 = (int)(i4 % C4) * 4;
         const f32x4 zv = reinterpret_cast<const f32x4 *>(z)[i4], gv = reinterpret_cast<const f32x4 *>(gz)[i4];
-        f32x4 d;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = c0 + j;
-            const float xhat = (zv[j] - k.mean[c]) * k.inv[c];
-            float v = gamma[c] * k.inv[c] * (gv[j] - kk[c] - xhat * kk[C + c]);
-            if (RELU_IN) v = zv[j] > 0.f ? v : 0.f;
-            d[j] = v;
-        }
-        reinterpret_cast<f32x4 *>(gz)[i4] = d;
+        reinterpret_cast<f32x4 *>(gz)[i4] = bn_bwd_unit<RELU_IN>(zv, gv, bn_bwd_channels(k, gamma, kk, C, (int)(i4 % C4) * 4));
     }
 }
 
@@ -757,17 +850,8 @@ __global__ __launch_bounds__(256) void head_fwd_fast_kernel(const float *__restr
 __global__ __launch_bounds__(256) void loss_reduce_kernel(const float *__restrict__ loss_i, const float *__restrict__ correct_i,
                                                            int B, float *__restrict__ out)
 {
-    double s = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < B; i += 256) { s += (double)loss_i[i]; c += (double)correct_i[i]; }
-    __shared__ double sh[2][256];
-    sh[0][threadIdx.x] = s;
-    sh[1][threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[0] = (float)sh[0][0]; out[1] = (float)sh[1][0]; }
+    __shared__ double sh[2 * 256];
+    loss_sum_block(loss_i, correct_i, B, out, sh);       // kws_device.h: the fixed order
 }
 
 // head backward: dx[b][k] = sum_c dlogits[b][c] W2[k][c], gated by the ReLU6 of x (x = relu6 output: 0 < x < 6);

@@ -203,8 +203,10 @@ static int resident_blocks(K kernel, int threads, size_t smem)
 
 // dW += wgrad(x, dz).  The grid is sized so that all blocks are resident at once (ONE round): with more blocks than slots the
 // last round runs on a fraction of the chip (measured on conv4: 990 blocks on 768 slots left the CUs idle 43 % of the time).
+// `job`: the step's loss / accuracy sums ride in one more column of blocks (kws_conv.h), under the same label.
 template <int CIN, int COUT, int GPB>
-int launch_wgrad(const float *x, const float *dz, float *dw, const ConvGeom &g, hipStream_t s, bool deterministic = false)
+int launch_wgrad(const float *x, const float *dz, float *dw, const ConvGeom &g, hipStream_t s, bool deterministic = false,
+                 const LossSumJob *job = nullptr)
 {
     const float *zp = zero_page();
     if (!zp) return fail(KWS_ERR_NOMEM, "cannot allocate the zero page on this device");
@@ -221,8 +223,8 @@ int launch_wgrad(const float *x, const float *dz, float *dw, const ConvGeom &g, 
     const int spw = (int)((steps + 4 * gx_want - 1) / (4 * gx_want));
     const long gx = (steps + 4L * spw - 1) / (4L * spw);
     static const std::string name = "conv_wgrad<" + std::to_string(CIN) + "," + std::to_string(COUT) + ">";
-    KWS_LAUNCH(name.c_str(), (conv_wgrad_direct_kernel<CIN, COUT, GPB>), dim3((unsigned)gx, (unsigned)gy), dim3(256), smem,
-               s, x, dz, dw, zp, g, spw);
+    KWS_LAUNCH(name.c_str(), (conv_wgrad_direct_kernel<CIN, COUT, GPB>), dim3((unsigned)gx + (job ? 1u : 0u), (unsigned)gy), dim3(256), smem,
+               s, x, dz, dw, zp, g, spw, job ? *job : LossSumJob{});
     return KWS_OK;
 }
 
@@ -517,7 +519,7 @@ struct CnnStep {
     int bn_bwd_finalize(int l, int nblk);
     template <bool RELU> int bn_bwd_apply(int l);
     int colsum(const char *label, const float *x, long M, int C, float *dst);
-    int dense_fwd(), dense_bias_grad(), dense_wgrad(hipStream_t on, bool det), dense_dgrad();
+    int dense_fwd(), dense_bias_grad(), dense_wgrad(hipStream_t on, bool det, const LossSumJob *job = nullptr), dense_dgrad();
     // the head behind d1 in a launch of its own: an inference's outputs / a train step's loss and dlogits, then the caller's forward event
     int head_infer(float *probs, int32_t *argmax) { return run_head(m, B, params, w.d1, w.loss_i, w.correct_i, nullptr, nullptr, probs, argmax, nullptr, 0.f, nullptr, 0, s); }
     int head_train(const kws_train_args *a, float *stats);
@@ -746,7 +748,10 @@ int CnnStep::head_train(const kws_train_args *a, float *stats)
 // stream) and data gradient -> da4 (gradient w.r.t. the dropped, flattened map)
 int CnnStep::dense_fwd() { return launch_gemm<128, 128, MODE_FWD, EPI_BIAS_RELU6>(w.a[3], params + m->o_dk, params + m->o_db, w.d1, dense_geom(d, B), s); }
 int CnnStep::dense_bias_grad() { return colsum("channel_stats_kernel.dense", w.dd1, B, 128, grads + m->o_db); }
-int CnnStep::dense_wgrad(hipStream_t on, bool det) { return launch_wgrad<128, 128, 1>(w.a[3], w.dd1, grads + m->o_dk, dense_geom(d, B), on, det); }
+int CnnStep::dense_wgrad(hipStream_t on, bool det, const LossSumJob *job)
+{
+    return launch_wgrad<128, 128, 1>(w.a[3], w.dd1, grads + m->o_dk, dense_geom(d, B), on, det, job);
+}
 int CnnStep::dense_dgrad() { return launch_dgrad<128, 128, 1>(w.dd1, params + m->o_dk, w.da4, dense_geom(d, B), s); }
 
 // conv2: clip-resident kernel, batch statistics fused into the epilogue when training
@@ -949,9 +954,10 @@ int CnnCtx::bwd_head_dense()
         if (!fork0_bound) KWS_HIP_CHECK(hipEventRecord(R->ev[0], s));
         KWS_HIP_CHECK(hipStreamWaitEvent(s2, R->ev[0], 0));
     }
-    // fused head: the sums of the per-sample losses / correct flags, in a fixed order, off the main chain
-    if (P.fuse_head_fwd && stats) KWS_LAUNCH("loss_reduce_kernel", loss_reduce_kernel, dim3(1), dim3(256), 0, s2, w.loss_i, w.correct_i, B, stats);
-    KWS_TRY(dense_wgrad(s2, P.det));
+    // fused head: the sums of the per-sample losses / correct flags, in a fixed order, off the main chain -- as one more block of the Dense
+    // weight gradient's launch: a launch of their own held the whole side chain back by its 13-16 us, and nothing reads stats before the join
+    const LossSumJob sums{w.loss_i, w.correct_i, stats, B};
+    KWS_TRY(dense_wgrad(s2, P.det, P.fuse_head_fwd && stats ? &sums : nullptr));
     if (!P.fuse_head_fwd) KWS_TRY(dense_bias_grad());     // no MFMA head kernel, or deterministic mode: the dense bias gradient takes its own two kernels
     if (P.dense_fused) ;                        // da4 came out of dense_head_fused_kernel
     else if (P.bf16) KWS_TRY_NB(launch_bf16<128, 128, MODE_DGRAD, EPI_NONE>("conv_bf16_dgrad", w.dd1, w.wsp[2], nullptr, w.da4, dense_geom(d, B), s));
@@ -979,10 +985,15 @@ int CnnCtx::bwd_layer4()
     if (!P.acc_bn4) KWS_TRY(bn_bwd_finalize(3, nblk));
     bwd_arm(3);                          // the apply kernel below is the last one in front of fork(3)
     const Bf16PlanesOut dzp{{w.dzp[0], w.dzp[1], w.dzp[2]}};
-    if (P.acc_bn4)
-        KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", 4), bn_bwd_apply_routed_planes_kernel<true>, dim3(std::min<unsigned>(1024u, blocks_for(M * C / 4, 256))),
-                   dim3(256), 0, s, w.z[3], w.da4, w.arg4, k, gamma, B, H, W, C, acc_out(3), dzp);
-    else if (P.bf16)
+    if (P.acc_bn4) {
+        const unsigned nb = std::min<unsigned>(1024u, blocks_for(M * C / 4, 256));
+        if (bn_bwd_walk_ok(M * C / 4, C, nb, kBnRoutedUnits))
+            KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", 4), (bn_bwd_apply_routed_planes_kernel<true, true>), dim3(nb), dim3(256), 0, s, w.z[3], w.da4,
+                       w.arg4, k, gamma, B, H, W, C, acc_out(3), dzp);
+        else
+            KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", 4), (bn_bwd_apply_routed_planes_kernel<true, false>), dim3(nb), dim3(256), 0, s, w.z[3], w.da4,
+                       w.arg4, k, gamma, B, H, W, C, acc_out(3), dzp);
+    } else if (P.bf16)
         // split precision: dz4 leaves as bf16 h/m/l planes, which is what both of its consumers stage (no fp32 dz4)
         KWS_LAUNCH(prof_name("bn_bwd_apply_planes_kernel", 4), bn_bwd_apply_planes_kernel<true>, dim3(blocks_for(M * C / 4, 256)), dim3(256), 0, s,
                    w.z[3], w.gz[3], k, gamma, M * C / 4, C, dzp);
