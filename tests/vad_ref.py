@@ -1,5 +1,6 @@
 """float64 numpy restatement of the voice-activity arithmetic (include/kws.h, "Voice-activity detection"), written from its
-description: the yardstick of tests/test_vad_host.py and tests/test_vad_gpu.py.  One np.fft.rfft per window."""
+description: the yardstick of tests/test_vad_host.py, tests/test_vad_gpu.py and tests/test_vad_geometry_*.py.  One np.fft.rfft per
+window.  (`ratios_f32` is no yardstick: it shows what float32 products cost, beside the device's error.)"""
 import numpy as np
 
 
@@ -31,6 +32,28 @@ def ratios(x, rate, **kw):
         if full > 0.0:
             out[w] = 2.0 * E[lo:hi + 1].sum() / full
     return out
+
+
+def ratios_f32(x_int16, rate, **kw):
+    """the ratios as a float32 machine can form them, for comparison with the device's error (not a yardstick): a dense float32
+    product of the windows (samples x / 32768, exact in float32) with the cos / sin of the band bins, squares summed in float32; the
+    total from the Parseval form N sum x^2 - (sum x)^2 + (sum (-1)^n x_n)^2 in float64; the division in float64, rounded once"""
+    N, H, lo, hi, _ = geometry(rate, **kw)
+    x = np.asarray(x_int16, dtype=np.float64) / 32768.0
+    nw = n_windows(x.size, N, H)
+    if nw == 0:
+        return np.zeros(0, np.float32)
+    win = x[np.arange(nw)[:, None] * H + np.arange(N)[None, :]]                            # (nw, N), exact
+    ang = 2.0 * np.pi * ((np.arange(N)[:, None] * np.arange(lo, hi + 1)[None, :]) % N) / N
+    w32 = win.astype(np.float32)
+    re, im = w32 @ np.cos(ang).astype(np.float32), w32 @ np.sin(ang).astype(np.float32)
+    band = (re * re + im * im).sum(axis=1, dtype=np.float32).astype(np.float64)
+    alt = np.where(np.arange(N) % 2 == 0, 1.0, -1.0)
+    full = N * (win * win).sum(axis=1) - win.sum(axis=1) ** 2 + (win * alt).sum(axis=1) ** 2
+    out = np.zeros(nw)
+    ok = full > 0.0
+    out[ok] = 2.0 * band[ok] / full[ok]
+    return out.astype(np.float32)
 
 
 def smooth(raw, m=25):
