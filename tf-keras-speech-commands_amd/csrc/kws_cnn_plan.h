@@ -34,6 +34,7 @@ struct CnnPlan {
     bool acc_bn2, acc_bn3, acc_bn4;     // ... and in the BatchNorm backward of layers 2, 3, 4
     bool a3_on_load;         // conv4 and its weight gradient form a3 from z3 on the fly (kws_conv.h: ABN / XBN)
     bool pool4_fused;        // layer 4's activation rides in the fused Dense + head kernel of the backward pass (kws_dense_head.h: z4)
+    bool wgrad_pmajor;       // conv4's split-precision weight gradient in the position-major form, which skips the padding taps (kws_conv.h: WgradPm)
     bool wgrad2_bf16;        // conv2's weight gradient in split precision
     bool wgrad2_early;       // ... forming dz itself, forked BEFORE conv2's data gradient
     bool wgrad2_fast;        // ... as the wave-per-clip kernel of the default 15 x 10 map (kws_conv2_wgrad_fast.h)
@@ -78,6 +79,8 @@ inline CnnPlan plan_cnn(const kws_model *m, int B, int mprec, bool training, boo
     // split precision keeps a3 on load; the fp32 mode keeps the activation kernel (same-box A/B at B = 4096: 0.6714 -> 0.666 ms per step)
     p.a3_on_load = split_train;
     p.pool4_fused = p.acc_fwd && p.dense_fused;
+    // an output map of at most 16 pixels (the rule of ConvGeom.pmajor); deterministic mode keeps the pixel-major kernel and its single add per element
+    p.wgrad_pmajor = split_train && !p.det && d.H3 * d.W3 <= 16;
     p.wgrad2_bf16 = p.bf16 && P1 <= 160;
     // compact g and a clip that fits the kernels' register staging
     p.wgrad2_early = p.compact_g2 && p.wgrad2_bf16 && P1 * 8 <= 1280 && P1 * 4 <= 768;

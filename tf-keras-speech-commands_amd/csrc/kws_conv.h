@@ -529,14 +529,32 @@ __device__ __forceinline__ s16x4 lds_read_tr16(const unsigned char *p)
 // DPRE: dz arrives already split (planes `dpl`, NHWC like dzp, which is then unused): its staging is a 16-byte copy per plane.
 // XBN: `x` is the pre-activation tensor z of the BatchNormalization -> ReLU6 in front of the convolution, xbn = its scale[CIN] | shift[CIN];
 // the activation x = relu6(z * scale + shift) is formed while it is staged (see conv_bf16_kernel<..., ABN>).
-template <int CIN, int COUT, int TPB, bool DPRE = false, bool XBN = false>
+//
+// PM: the position-major form for output maps of at most 16 pixels (WgradPm, built by the host from the geometry).  The reduction index
+// is (output position, clip): a chunk is 32 CLIPS at one output position (rows one clip apart), so for a given tap a chunk is either
+// wholly inside the map or wholly in the 'same' padding, and the padding (tap, position) pairs are never loaded, staged or multiplied.
+// A tap walks its own list of positions at which it reads inside the map.  One tap per block only (conv4): conv3's kernel-row form
+// (TPB = 3, padding columns skipped under a wave-uniform mask) skipped 35 % of its products too but ran 0.030 -> 0.034 ms alone
+// (DESIGN.md section 5 log), so conv3 keeps the pixel-major form.  Block id -> (XCD, slot): XCD x takes the 32-clip chunks [x NC / 8, (x + 1) NC / 8) for every tap, so
+// the taps reading one clip range share an L2; the XCD's slots are dealt to the taps in proportion to their positions and a tap's
+// items (clip chunk major, kept position minor) are dealt to its ns slots in turn: slot k takes items k, k + ns, k + 2 ns, ...  Slots per
+// tap are proportional to items per tap, so at its j-th chunk every block of the XCD is at about the same clip chunk, whatever its
+// tap: the taps read a clip's rows at about the same time (with one contiguous range of items per block they read them a kernel apart).
+struct WgradPm {
+    unsigned long long pos[9];    // per tap: the output positions at which it reads inside the map, a nibble each
+    int npos[9];                  // ... and how many they are
+    int slot0[10];                // first slot of each tap within an XCD; slot0[taps] = slots per XCD (grid = 8 x that)
+};
+
+template <int CIN, int COUT, int TPB, bool DPRE = false, bool XBN = false, bool PM = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__restrict__ x, const float *__restrict__ dzp,
                                                                   float *__restrict__ dw, const float *__restrict__ zero_page,
                                                                   ConvGeom g, int chunks_per_block, int nranges,
                                                                   Bf16Planes dpl = Bf16Planes{{nullptr, nullptr, nullptr}},
-                                                                  const float *__restrict__ xbn = nullptr)
+                                                                  const float *__restrict__ xbn = nullptr, WgradPm pm = WgradPm{})
 {
-    constexpr int KC = 32;                                        // pixels per chunk
+    constexpr int KC = 32;                                        // pixels (PM: clips) per chunk
+    static_assert(!PM || TPB == 1, "the position-major form is built and measured for one tap per block");
     constexpr int XS = 4 * tr_row_words(CIN), DS = 4 * tr_row_words(COUT);   // row strides in bytes
     constexpr int MT = CIN / 16, NT = COUT / 16, NW = NT / 4;     // row tiles, column tiles, column tiles per wave
     constexpr int XU = KC * CIN / 4, DU = KC * COUT / 4;          // float4 units of a chunk
@@ -552,10 +570,37 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
     const long M = (long)g.B * HW;
     const int ngroups = g.KH * g.KW / TPB;                        // tap groups (TPB == KW: kernel rows)
     // block id -> (tap group, range): XCD = id % 8 holds every tap of its ranges
-    const int bid = blockIdx.x, tap0 = ((bid >> 3) % ngroups) * TPB, range = (bid / (8 * ngroups)) * 8 + (bid & 7);
-    const long nchunk_all = (M + KC - 1) / KC, chunk0 = (long)range * chunks_per_block;
-    const int nchunks = (range >= nranges || chunk0 >= nchunk_all) ? 0
-                        : (int)(chunk0 + chunks_per_block <= nchunk_all ? chunks_per_block : nchunk_all - chunk0);
+    const int bid = blockIdx.x;
+    int tap0, nchunks;
+    long chunk0 = 0;
+    // PM: the next item to load (clip chunk, index into the tap's position list) and the step to the one after, the tap's list, and
+    // whether the chunk in flight / the chunk in LDS was loaded at all (a bit per tap of the block; all wave-uniform)
+    int pm_cc = 0, pm_pi = 0, pm_np = 1, pm_dcc = 0, pm_dpi = 0;
+    unsigned long long pm_pos = 0ull;
+    unsigned ld_taps = 0u, st_taps = 0u;
+    if constexpr (PM) {
+        const int xcd = bid & 7, slot = bid >> 3;
+        int grp = 0;
+        while (grp + 1 < ngroups && slot >= pm.slot0[grp + 1]) ++grp;
+        tap0 = grp * TPB;
+        pm_np = pm.npos[grp]; pm_pos = pm.pos[grp];
+        const int nclip = (g.B + KC - 1) / KC, c0 = (int)((long)xcd * nclip / 8), c1 = (int)((long)(xcd + 1) * nclip / 8);
+        const int k = slot - pm.slot0[grp], ns = pm.slot0[grp + 1] - pm.slot0[grp];
+        const int items = (c1 - c0) * pm_np;
+        // slot k of the group's ns takes items k, k + ns, k + 2 ns, ...
+        nchunks = (k < ns && pm_np > 0 && items > k) ? (items - k + ns - 1) / ns : 0;
+        if (nchunks > 0) {
+            pm_cc = c0 + k / pm_np; pm_pi = k % pm_np;
+            pm_dcc = ns / pm_np; pm_dpi = ns % pm_np;
+        }
+    } else {
+        tap0 = ((bid >> 3) % ngroups) * TPB;
+        const int range = (bid / (8 * ngroups)) * 8 + (bid & 7);
+        const long nchunk_all = (M + KC - 1) / KC;
+        chunk0 = (long)range * chunks_per_block;
+        nchunks = (range >= nranges || chunk0 >= nchunk_all) ? 0
+                  : (int)(chunk0 + chunks_per_block <= nchunk_all ? chunks_per_block : nchunk_all - chunk0);
+    }
 
     f32x4 acc[TPB][MT][NW];
 #pragma unroll
@@ -584,7 +629,49 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
         xsc = *reinterpret_cast<const f32x4 *>(xbn + 4 * (tid % (CIN / 4)));
         xsh = *reinterpret_cast<const f32x4 *>(xbn + CIN + 4 * (tid % (CIN / 4)));
     }
+    auto load_chunk_pm = [&]() {
+        // one output position of 32 consecutive clips: unit rows are one clip apart; only the clips past B read the zero page
+        const int pos = (int)(pm_pos >> (4 * pm_pi)) & 15, oy = pos / g.Wo, ox = pos - oy * g.Wo;
+        const int b0 = pm_cc * KC;
+        ld_taps = (1u << TPB) - 1u;
+        xok = 0u;
+#pragma unroll
+        for (int t = 0; t < TPB; ++t) {
+            const int tap = tap0 + t, kh = tap / g.KW, kw = tap - kh * g.KW;
+            const int sy = oy * g.stride + kh - g.pt, sxx = ox * g.stride + kw - g.pl;
+            // the list names only positions inside the map; the (scalar) bounds test keeps a wrong list from reading outside the tensor
+            if (sy >= 0 && sy < g.H && sxx >= 0 && sxx < g.W) {
+#pragma unroll
+                for (int j = 0; j < NXU; ++j) {
+                    const int u = tid + 256 * j, b = b0 + u / (CIN / 4);
+                    const float *p = b < g.B ? x + (((long)b * g.H + sy) * g.W + sxx) * CIN + 4 * (u % (CIN / 4)) : zero_page;
+                    sx[t][j] = *reinterpret_cast<const f32x4 *>(p);
+                    if (XBN && b < g.B) xok |= 1u << (j * TPB + t);
+                }
+            } else {
+                ld_taps &= ~(1u << t);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NDU; ++j) {
+            const int u = tid + 256 * j;
+            if (DPRE) {
+                const int b = b0 + u / (COUT / 8);
+                const long m = (long)b * HW + pos;
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+                    sdp[p][j] = b < g.B ? *reinterpret_cast<const u32x4 *>(dpl.p[p] + m * COUT + 8 * (u % (COUT / 8))) : (u32x4){0u, 0u, 0u, 0u};
+            } else {
+                const int b = b0 + u / (COUT / 4);
+                const float *p = b < g.B ? dzp + ((long)b * HW + pos) * COUT + 4 * (u % (COUT / 4)) : zero_page;
+                sd[j] = *reinterpret_cast<const f32x4 *>(p);
+            }
+        }
+        pm_cc += pm_dcc; pm_pi += pm_dpi;
+        if (pm_pi >= pm_np) { pm_pi -= pm_np; ++pm_cc; }
+    };
     auto load_chunk = [&](int ch) {
+        if constexpr (PM) { load_chunk_pm(); return; }
         const long m0 = (chunk0 + ch) * KC;
         xok = 0u;
 #pragma unroll
@@ -631,6 +718,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
             const int u = tid + 256 * j, o = (u / (CIN / 4)) * XS + 8 * (u % (CIN / 4));
 #pragma unroll
             for (int t = 0; t < TPB; ++t) {
+                if (PM && !((st_taps >> t) & 1u)) continue;       // PM: nothing was loaded (see load_chunk_pm)
                 f32x4 xv = sx[t][j];
                 if constexpr (XBN) {
                     if (xok & (1u << (j * TPB + t))) {
@@ -668,6 +756,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
     if (nchunks > 0) load_chunk(0);
     for (int ch = 0; ch < nchunks; ++ch) {
         __syncthreads();
+        st_taps = ld_taps;
         store_chunk();
         __syncthreads();
         if (ch + 1 < nchunks) load_chunk(ch + 1);
@@ -677,7 +766,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
 #pragma unroll
             for (int p = 0; p < 3; ++p) b[nw][p] = frag(dfrag, DS, p, nw);
 #pragma unroll
-        for (int t = 0; t < TPB; ++t)
+        for (int t = 0; t < TPB; ++t) {
+            if (PM && !((st_taps >> t) & 1u)) continue;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 bf16x8 a[3];
@@ -686,6 +776,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
 #pragma unroll
                 for (int nw = 0; nw < NW; ++nw) acc[t][mt][nw] = mfma_bf16x6(a, b[nw], acc[t][mt][nw]);
             }
+        }
     }
     // gather each tap's (CIN x COUT) tile in LDS (reusing the staging space) and add it with contiguous atomics
     float *red = reinterpret_cast<float *>(wsm);                   // [CIN][COUT]
@@ -702,6 +793,58 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
         if (nchunks > 0)
             for (int i = tid; i < CIN * COUT; i += 256) atomicAdd(dw + (long)(tap0 + t) * CIN * COUT + i, red[i]);
     }
+}
+
+// The host side of the position-major form: the lists and the slot shares for one launch (tests/wgrad_pmajor_cases.py restates it).
+//   lists   tap (kh, kw) keeps the output positions p = oy Wo + ox at which it reads inside the map (0 <= oy stride + kh - pt < H and
+//           0 <= ox stride + kw - pl < W); its weight w is their number
+//   slots   S slots per XCD: enough for `min_chunks` chunks per block on average, at least one per tap that has positions and at most
+//           max_slots (one resident round); a tap starts from floor(S w / sum w) slots (at least 1), then slots go one by one to the
+//           tap with the most positions per slot (lowest index on ties) -- or, while there are too many, leave the tap with the
+//           fewest (highest index on ties) -- until they add up to S
+// false: a map of more than 16 pixels, more than nine taps, or fewer slots than taps
+inline bool wgrad_pm_plan(const ConvGeom &g, int max_slots, int min_chunks, WgradPm &pm)
+{
+    const int P = g.Ho * g.Wo, ntaps = g.KH * g.KW;
+    if (P < 1 || P > 16 || ntaps < 1 || ntaps > 9) return false;
+    long w[9], wsum = 0;
+    int live = 0;
+    for (int tap = 0; tap < ntaps; ++tap) {
+        const int kh = tap / g.KW, kw = tap % g.KW;
+        pm.pos[tap] = 0ull; pm.npos[tap] = 0;
+        for (int p = 0; p < P; ++p) {
+            const int sy = (p / g.Wo) * g.stride + kh - g.pt, sx = (p % g.Wo) * g.stride + kw - g.pl;
+            if (sy < 0 || sy >= g.H || sx < 0 || sx >= g.W) continue;
+            pm.pos[tap] |= (unsigned long long)p << (4 * pm.npos[tap]);
+            ++pm.npos[tap];
+        }
+        w[tap] = pm.npos[tap]; wsum += w[tap]; live += w[tap] > 0;
+    }
+    if (live < 1 || max_slots < live) return false;
+    const long nclip = ((long)g.B + 31) / 32, want = (wsum * nclip + 8L * min_chunks - 1) / (8L * min_chunks);
+    const int S = (int)(want < live ? live : want > max_slots ? max_slots : want);
+    int s[9], total = 0;
+    for (int tap = 0; tap < ntaps; ++tap) {
+        s[tap] = w[tap] ? (int)((long)S * w[tap] / wsum) : 0;
+        if (w[tap] && s[tap] < 1) s[tap] = 1;
+        total += s[tap];
+    }
+    for (; total < S; ++total) {
+        int best = -1;
+        for (int tap = 0; tap < ntaps; ++tap)
+            if (w[tap] && (best < 0 || w[tap] * s[best] > w[best] * s[tap])) best = tap;
+        ++s[best];
+    }
+    for (; total > S; --total) {
+        int best = -1;
+        for (int tap = 0; tap < ntaps; ++tap)
+            if (s[tap] > 1 && (best < 0 || w[tap] * s[best] <= w[best] * s[tap])) best = tap;
+        --s[best];
+    }
+    pm.slot0[0] = 0;
+    for (int tap = 0; tap < ntaps; ++tap) pm.slot0[tap + 1] = pm.slot0[tap] + s[tap];
+    for (int tap = ntaps + 1; tap < 10; ++tap) pm.slot0[tap] = pm.slot0[ntaps];
+    return true;
 }
 
 // N consecutive floats with the widest aligned load (N = 1, 2, 4, 8); p must be N*4-byte aligned (16 for N = 8)

@@ -231,9 +231,10 @@ int launch_wgrad(const float *x, const float *dz, float *dw, const ConvGeom &g, 
 // dW += wgrad(x, dz) in the split-precision form (conv_wgrad_bf16_kernel): grid = (tap groups) * (pixel ranges), one resident
 // round, the taps of a range on one XCD.  TPB = taps per block: 3 (one kernel row, dz split once for three products) pays
 // for conv3 (0.047 -> 0.042 ms); for conv4 its 238 registers and 74 KB of LDS cost more than they save (0.111 -> 0.122 ms).
+// pmajor (CnnPlan::wgrad_pmajor, TPB = 1): the position-major form, which never stages a tap's padding positions.
 template <int CIN, int COUT, int TPB, bool DPRE = false, bool XBN = false>
 int launch_wgrad_bf16(const float *x, const float *dz, float *dw, const ConvGeom &g, hipStream_t s, __bf16 *const *dz_planes = nullptr,
-                      bool deterministic = false, const float *xbn = nullptr)
+                      bool deterministic = false, const float *xbn = nullptr, bool pmajor = false)
 {
     if (TPB != 1 && g.KW != TPB) return fail(KWS_ERR_UNSUPPORTED, "split-precision weight gradient expects a kernel %d taps wide", TPB);
     const float *zp = zero_page();
@@ -251,6 +252,21 @@ int launch_wgrad_bf16(const float *x, const float *dz, float *dw, const ConvGeom
     if (deterministic) { nranges = 8; cpb = (int)nchunk; }   // range 0 takes every chunk: a single add per output element
     static const std::string name = "conv_wgrad_bf16<" + std::to_string(CIN) + "," + std::to_string(COUT) + ">";
     const Bf16Planes dpl{{DPRE ? dz_planes[0] : nullptr, DPRE ? dz_planes[1] : nullptr, DPRE ? dz_planes[2] : nullptr}};
+    if (pmajor && TPB != 1) return fail(KWS_ERR_UNSUPPORTED, "the position-major weight gradient takes one tap per block");
+    if constexpr (TPB == 1) {
+        if (pmajor) {
+            // the position-major form (kws_conv.h: WgradPm): one resident round of 8 XCDs x slots, under the same label
+            if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(conv_wgrad_bf16_kernel<CIN, COUT, 1, DPRE, XBN, true>), (int)smem)) return rc;
+            static const int occ_pm = resident_blocks(conv_wgrad_bf16_kernel<CIN, COUT, 1, DPRE, XBN, true>, 256, smem);
+            WgradPm pm{};
+            // a block's fixed part (tile gather and atomics) wants >= 4 chunks, as in the pixel-major form
+            if (!wgrad_pm_plan(g, cu_count() * occ_pm / 8, 4, pm))
+                return fail(KWS_ERR_UNSUPPORTED, "position-major weight gradient: a %d x %d map on %d block slots", g.Ho, g.Wo, cu_count() * occ_pm);
+            KWS_LAUNCH(name.c_str(), (conv_wgrad_bf16_kernel<CIN, COUT, 1, DPRE, XBN, true>), dim3(8u * (unsigned)pm.slot0[ngroups]), dim3(256), smem, s, x,
+                       dz, dw, zp, g, 0, 0, dpl, xbn, pm);
+            return KWS_OK;
+        }
+    }
     KWS_LAUNCH(name.c_str(), (conv_wgrad_bf16_kernel<CIN, COUT, TPB, DPRE, XBN>), dim3((unsigned)(nranges * ngroups)), dim3(256), smem, s, x, dz, dw,
                zp, g, cpb, (int)nranges, dpl, xbn);
     return KWS_OK;
@@ -1004,8 +1020,8 @@ int CnnCtx::bwd_layer4()
     float *dk = grads + m->o_k[3];
     const ConvGeom g = geom3x3(B, H, W, 1);
     if (P.bf16 && P.a3_on_load)
-        KWS_TRY((launch_wgrad_bf16<64, 128, 1, true, true>(w.z[2], nullptr, dk, g, s2, w.dzp, P.det, coef(2).scale)));
-    else if (P.bf16) KWS_TRY(launch_wgrad_bf16<64, 128, 1, true>(in, nullptr, dk, g, s2, w.dzp, P.det));
+        KWS_TRY((launch_wgrad_bf16<64, 128, 1, true, true>(w.z[2], nullptr, dk, g, s2, w.dzp, P.det, coef(2).scale, P.wgrad_pmajor)));
+    else if (P.bf16) KWS_TRY(launch_wgrad_bf16<64, 128, 1, true>(in, nullptr, dk, g, s2, w.dzp, P.det, nullptr, P.wgrad_pmajor));
     else KWS_TRY(launch_wgrad<64, 128, 1>(in, w.gz[3], dk, g, s2, P.det));
     // grads[o_k[3] ..] (conv4, bn4, dense, head = 82 % of the bytes) are final once the side stream gets here: it
     // runs the dense and conv4 weight gradients in order and joined the caller's stream at fork(3), i.e. after
