@@ -7,7 +7,7 @@ frames, 20 bands, 20 coefficients) almost everywhere.  The rows below are geomet
 this module restates those rules on the host (no device, no library call), so that tests/test_geometry_host.py can hold every row
 against the kernel and the job shape it claims, and the GPU tests can pick batch sizes from the device's compute-unit count.
 
-Restated from tf-keras-speech-commands_amd/csrc/kws_featurize.hip (the line of each rule is named at its restatement).  A tuned row
+Restated from tf-keras-speech-commands_amd/csrc/kws_featurize.hip and kws_featurize_tables.h (each rule is named at its restatement).  A tuned row
 also needs the chunk table of the mel bank to come out at 12, 16 or 20 positions per lane (v3_applies); that depends on n_fft, the band
 count, the sample rate and the bank alone, which the tuned rows share with the default geometry, where the tuned kernel is the one the
 whole suite and the benchmark run."""
@@ -18,11 +18,11 @@ import numpy as np
 from cnn_path_cases import MI355X_CUS, dims
 
 SAMPLE_RATE = 16000
-GEN1_WAVES = 5                      # kWaves, kws_featurize.hip:34
-GEN_WAVES = 4                       # kGenWaves, kws_featurize.hip:425
-MAX_LDS = 160 * 1024                # kMaxLdsBytes, kws_featurize.hip:515
+GEN1_WAVES = 5                      # kWaves, kws_featurize.hip
+GEN_WAVES = 4                       # kGenWaves, kws_featurize.hip
+MAX_LDS = 160 * 1024                # kMaxLdsBytes, kws_featurize.hip
 MAX_CLIPS = 4096                    # no test batch is larger
-LONG_TILE = 256                     # featurize_long_segments, kws_featurize.hip:1209
+LONG_TILE = 256                     # featurize_long_segments, kws_featurize.hip
 OTHER_CUS = 304                     # a second compute-unit count the table must hold at (tests/test_geometry_host.py)
 ATOL = 2e-4                         # tests/test_featurizer_gpu.py: clip features against the float64 oracle
 ATOL_ROWS = 3e-4                    # tests/test_scan_gpu.py, tests/test_stream_gpu.py: raw and long rows
@@ -48,7 +48,7 @@ LONG_ROWS = ("gen1-48", "rad2-48", "rad2-31")
 STREAM_ROWS = ("tuned-14", "gen1-9", "gen1-48", "rad2-48", "rad2-31")
 
 
-# ---- ListenerParams' derived sizes (classifier/params.py:40-65, derive() in kws_featurize.hip:539) -------------------------------
+# ---- ListenerParams' derived sizes (classifier/params.py:40-65, derive() in kws_featurize_tables.h) -------------------------------
 def window_samples(g):
     return int(SAMPLE_RATE * g.window_t + 0.5)
 
@@ -68,12 +68,12 @@ def n_features(g):
 
 
 def clip_frames(g):
-    """kws_featurizer_create, kws_featurize.hip:765: it refuses params whose frame count differs from n_features"""
+    """kws_featurizer_create, kws_featurize.hip (clip_frames, kws_featurize_tables.h): it refuses params whose frame count differs from n_features"""
     return (max_samples(g) - window_samples(g)) // hop_samples(g) + 1
 
 
 def raw_frames(g, n):
-    """kws_featurize_raw_frames, kws_featurize.hip:1181 (chop_array)"""
+    """kws_featurize_raw_frames, kws_featurize.hip (chop_array)"""
     return 0 if n < window_samples(g) else (n - window_samples(g)) // hop_samples(g) + 1
 
 
@@ -82,7 +82,7 @@ def feature_size(g):
 
 
 def mel_points(g):
-    """build_mel_bank, kws_featurize.hip:556: the FFT bins of the triangles' corners; the library refuses a grid that repeats a bin"""
+    """build_mel_bank, kws_featurize_tables.h: the FFT bins of the triangles' corners; the library refuses a grid that repeats a bin"""
     n_bins, n = g.n_fft // 2 + 1, g.n_filt + 2
     lo, hi = 1127.0 * np.log(1.0), 1127.0 * np.log(1.0 + SAMPLE_RATE / 700.0)
     step = (hi - lo) / (n - 1)
@@ -102,31 +102,31 @@ def oracle_kw(g):
 
 # ---- the dispatch rules of the clip featurizer, restated ---------------------------------------------------------------------------
 def window_eff(g):
-    """kws_featurizer_create, kws_featurize.hip:975: np.fft.rfft(frames, n) crops or zero-pads"""
+    """window_eff, build_feat_tables in kws_featurize_tables.h: np.fft.rfft(frames, n) crops or zero-pads"""
     return min(window_samples(g), g.n_fft)
 
 
 def tail_batch(g):
-    """kws_featurizer_create, kws_featurize.hip:980: frames whose band sums and DCT one wave evaluates together"""
+    """tail_batch, build_feat_tables in kws_featurize_tables.h: frames whose band sums and DCT one wave evaluates together"""
     n_filt_pad = (g.n_filt + 3) & ~3
     return max(1, min(4, 64 // max(n_filt_pad, g.n_mfcc)))
 
 
 def v3_applies(g, use_delta=None):
-    """v3_applies, kws_featurize.hip:653 (its chp3 condition: module docstring)"""
+    """v3_applies, kws_featurize.hip (its chp3 condition: module docstring)"""
     delta = g.use_delta if use_delta is None else use_delta
     return g.n_fft == 1024 and hop_samples(g) == 512 and window_eff(g) == 1024 and not delta and g.n_filt == 20 and g.n_mfcc == 20
 
 
 def kernel_of(g, use_delta=None):
-    """launch_featurize, kws_featurize.hip:1066"""
+    """launch_featurize, kws_featurize.hip"""
     if g.n_fft != 1024:
         return "generic"
     return "tuned" if v3_applies(g, use_delta) else "gen1"
 
 
 def feat_job_shape(n_frames, tb, use_delta):
-    """feat_job_shape, kws_featurize.hip:519 -> (fpw, jpc): frames per wave job, jobs per clip of the first-generation kernel"""
+    """feat_job_shape, kws_featurize.hip -> (fpw, jpc): frames per wave job, jobs per clip of the first-generation kernel"""
     fpw = (n_frames + GEN1_WAVES - 1) // GEN1_WAVES
     if not use_delta:
         fpw = max(fpw, min(n_frames, tb))
@@ -135,8 +135,8 @@ def feat_job_shape(n_frames, tb, use_delta):
 
 
 def gen1_grid(B, jpc, use_delta):
-    """launch_featurize, kws_featurize.hip:1083 -> (blocks, waves without a job).  With deltas a block is a clip and its waves
-    jpc..4 idle (featurize_fft1024_kernel, kws_featurize.hip:187); without, the last block's waves past B * jpc do."""
+    """the grid of launch_featurize, kws_featurize.hip -> (blocks, waves without a job).  With deltas a block is a clip and its waves
+    jpc..4 idle (the job index of featurize_fft1024_kernel, kws_featurize.hip); without, the last block's waves past B * jpc do."""
     if use_delta:
         return B, B * (GEN1_WAVES - jpc)
     grid = (B * jpc + GEN1_WAVES - 1) // GEN1_WAVES
@@ -144,13 +144,13 @@ def gen1_grid(B, jpc, use_delta):
 
 
 def v3_waves(cus, shared=False):
-    """launch_v3_any / launch_v3, kws_featurize.hip:735, 674: waves = bpc * cus * WAVES, two blocks of 8 waves per compute unit alone,
+    """launch_v3_any / launch_v3, kws_featurize.hip: waves = bpc * cus * WAVES, two blocks of 8 waves per compute unit alone,
     one of 12 (kV3Waves) beside a train step"""
     return (1 * 12 if shared else 2 * 8) * cus
 
 
 def v3_job_shape(n_frames, B, cus, shared=False, tb=3):
-    """the cost loop of launch_v3, kws_featurize.hip:690 -> (fpw, jpc, rounds)"""
+    """the cost loop of launch_v3, kws_featurize.hip -> (fpw, jpc, rounds)"""
     waves = v3_waves(cus, shared)
     best = None
     for fpw in range(min(n_frames, max(1, tb)), n_frames + 1):
@@ -163,7 +163,7 @@ def v3_job_shape(n_frames, B, cus, shared=False, tb=3):
 
 
 def long_tile(g, max_frames):
-    """featurize_long_segments, kws_featurize.hip:1209 -> (tile, segments per recording)"""
+    """featurize_long_segments, kws_featurize.hip -> (tile, segments per recording)"""
     tile = LONG_TILE
     if g.n_fft != 1024:
         fixed = GEN_WAVES * g.n_fft * 8 + GEN_WAVES * 256
@@ -173,7 +173,7 @@ def long_tile(g, max_frames):
 
 
 def long_uses_segments(g):
-    """kws_featurize_long, kws_featurize.hip:1265: the tuned kernel's own tiles, or segments through the clip kernels"""
+    """kws_featurize_long, kws_featurize.hip: the tuned kernel's own tiles, or segments through the clip kernels"""
     return not v3_applies(g, use_delta=False)
 
 

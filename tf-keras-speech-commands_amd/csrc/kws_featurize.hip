@@ -14,27 +14,19 @@
 //   HBM    : every sample is requested once per frame it belongs to (2x with hop = window/2);
 //            the second touch is an L1/L2 hit issued by the same block, so DRAM traffic stays at
 //            the algorithmic 4 B/sample in + 4 B/feature out.
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include <functional>
+#include <memory>
+#include <type_traits>
 
 #include "kws_common.h"
 #include "kws_device.h"
 #include "kws_augment.h"
-
-#ifndef KWS_FEAT_ABLATE
-#define KWS_FEAT_ABLATE 0
-#endif
+#include "kws_featurize_tables.h"   // the host side: geometry, bank, chunk tables, twiddles, DCT, table arena
 
 namespace kws {
 
 constexpr int kWaves = 5;                 // wavefronts per clip (30 default frames -> 6 frames each)
 constexpr int kThreads = kWaves * 64;
 constexpr int kFftTile = 8 * 72;          // float2 elements per wave (padded 8 x 64 tile)
-constexpr int kMaxChunks = 64;
 constexpr float kEps = 2.220446049250313e-16f;  // np.finfo(float).eps, common/bark_feature.py:77
 
 struct FeatDev {
@@ -251,12 +243,6 @@ __global__ __launch_bounds__(kThreads, 5) void featurize_fft1024_kernel(const Wa
             load_half<WavT, 4>(xh, src, (f + 1) * c.hop, pad, c.window_eff, vec_ok, lane);
         }
 
-#if (KWS_FEAT_ABLATE & 16)
-        { float acc = 0.f;
-          for (int j = 0; j < 8; ++j) acc += v[j].x + v[j].y;
-          if (f + 1 == f_end) dst[f * c.n_out + (lane % c.n_out)] = acc;
-          continue; }
-#endif
         // pass 1: DFT-8 over n1 (n = lane + 64 n1), twiddle W_512^(lane*k1)
         dft8(v);
 #pragma unroll
@@ -268,7 +254,6 @@ __global__ __launch_bounds__(kThreads, 5) void featurize_fft1024_kernel(const Wa
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = s_fft[72 * hi + lo + 8 * j];
 
-#if !(KWS_FEAT_ABLATE & 4)
         // pass 2: lane = (k1, l2); DFT-8 over l1, twiddle W_64^(l2*k2a)
         dft8(v);
 #pragma unroll
@@ -282,7 +267,6 @@ __global__ __launch_bounds__(kThreads, 5) void featurize_fft1024_kernel(const Wa
 
         // pass 3: lane = (k1, k2a); DFT-8 over l2 -> Z[k1 + 8 k2a + 64 k2b]
         dft8(v);
-#endif
         wave_sync();
 #pragma unroll
         for (int r = 0; r < 8; ++r) {       // natural order k = hi + 8 lo + 64 r, stored at k + (k >> 3) = hi + 9 lo + 72 r: the
@@ -292,9 +276,6 @@ __global__ __launch_bounds__(kThreads, 5) void featurize_fft1024_kernel(const Wa
 
         // real-FFT split: X[k] = E[k] + W_1024^k O[k], X[512-k] = conj(E[k] - W_1024^k O[k])
         float pk[4], pm[4], p256 = 0.f, energy = 0.f;
-#if (KWS_FEAT_ABLATE & 2)
-        for (int i = 0; i < 4; ++i) { pk[i] = v[i].x; pm[i] = v[i].y; energy += v[i + 4].x + v[i + 4].y; }
-#else
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = lane + 64 * i;
@@ -313,7 +294,6 @@ __global__ __launch_bounds__(kThreads, 5) void featurize_fft1024_kernel(const Wa
             p256 = (z.x * z.x + z.y * z.y) * c.inv_nfft;
             energy += p256;
         }
-#endif
         wave_sync();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -327,10 +307,6 @@ __global__ __launch_bounds__(kThreads, 5) void featurize_fft1024_kernel(const Wa
 
         // sparse band gather: lane = one chunk (<= chp bins) of one band's non-zero span.  Fixed trip count over
         // zero-padded weights so the LDS loads of a group issue back to back.
-#if (KWS_FEAT_ABLATE & 1)
-        if (f + 1 == f_end) dst[f * c.n_out + (lane % c.n_out)] = energy + s_pw[lane];
-        continue;
-#endif
         float part = 0.f;
         {
             const float *pp = s_pw + (chunk_pack & 0xFFFF);
@@ -348,12 +324,6 @@ __global__ __launch_bounds__(kThreads, 5) void featurize_fft1024_kernel(const Wa
         if (lane == 0) s_en[qi] = energy;
         ++qi;
         if (qi < tb && f + 1 < f_end) continue;
-#if (KWS_FEAT_ABLATE & 8)
-        wave_sync();
-        if (lane < qi * c.n_out) dst[(f + 1 - qi) * c.n_out + lane] = s_part[lane] + s_en[0];
-        qi = 0;
-        continue;
-#endif
 
         // ---- tail of the qi frames f-qi+1 .. f: band sums -> log -> DCT, all frames of the batch at once ----
         // lane roles are recomputed per batch (twice per wave) rather than held in registers across the FFTs;
@@ -510,7 +480,7 @@ __global__ __launch_bounds__(kGenWaves * 64) void featurize_generic_kernel(const
 namespace kws {
 
 // ---------------------------------------------------------------------------------------------
-// host side: parameter geometry and table construction (double precision, then rounded once)
+// host side: job shapes, LDS sizes and launches (the tables themselves: kws_featurize_tables.h)
 // ---------------------------------------------------------------------------------------------
 constexpr size_t kMaxLdsBytes = 160 * 1024;      // LDS per workgroup on gfx950
 
@@ -534,78 +504,6 @@ static size_t feat_smem_bytes(const FeatDev &d)
     return (size_t)kWaves * (kFftTile * 8 + 4 * (d.tail_batch * 64 + 64 + 4)) +
            4 * (size_t)(round4(d.n_filt_pad * d.n_out) + round4(d.nnz)) + 8 * (7 * 64 + 7 * 8) + 272 +
            (d.use_delta ? 4 * (size_t)round4(d.n_frames * d.n_out) : 0);
-}
-
-static int derive(const kws_params *p, kws_geometry *g)
-{
-    if (!p || !g) return fail(KWS_ERR_INVALID, "null params");
-    if (p->sample_rate <= 0 || p->window_t <= 0 || p->hop_t <= 0 || p->buffer_t <= 0)
-        return fail(KWS_ERR_INVALID, "sample_rate/window_t/hop_t/buffer_t must be positive");
-    // classifier/params.py:59-91
-    g->window_samples = (int)(p->sample_rate * p->window_t + 0.5);
-    g->hop_samples = (int)(p->sample_rate * p->hop_t + 0.5);
-    g->max_samples = (int)(p->buffer_t * p->sample_rate);
-    if (g->hop_samples <= 0 || g->window_samples <= 0) return fail(KWS_ERR_INVALID, "window/hop round to zero samples");
-    int samples = (int)(p->sample_rate * p->buffer_t + 0.5);
-    g->buffer_samples = g->hop_samples * (samples / g->hop_samples);
-    g->n_features = 1 + (int)std::floor((double)(g->buffer_samples - g->window_samples) / (double)g->hop_samples);
-    g->feature_size = p->use_delta ? 2 * p->n_mfcc : p->n_mfcc;
-    return KWS_OK;
-}
-
-static int build_mel_bank(int sample_rate, int n_fft, int n_filt, std::vector<double> &bank)
-{
-    // sonopy.filterbanks as restated by inference/tflite/mfcc.h:230-264; span 0..sample_rate
-    // (inference/tflite/speech_commands.h:304-307)
-    const int n_bins = n_fft / 2 + 1, n = n_filt + 2;
-    std::vector<int> pts(n);
-    const double lo = 1127.0 * std::log(1.0 + 0.0 / 700.0), hi = 1127.0 * std::log(1.0 + sample_rate / 700.0);
-    const double step = (hi - lo) / (double)(n - 1);
-    for (int i = 0; i < n; ++i) {
-        const double m = (i == n - 1) ? hi : lo + i * step;
-        pts[i] = (int)(700.0 * (std::exp(m / 1127.0) - 1.0) * n_bins / sample_rate);
-    }
-    for (int i = 1; i < n; ++i)
-        if (pts[i] <= pts[i - 1])
-            return fail(KWS_ERR_UNSUPPORTED, "mel grid has repeated FFT bins for n_fft=%d n_filt=%d (sonopy's "
-                                             "duplicate-point correction is not implemented)", n_fft, n_filt);
-    if (pts[n - 1] > n_bins) return fail(KWS_ERR_INVALID, "mel grid exceeds the spectrum");
-    bank.assign((size_t)n_filt * n_bins, 0.0);
-    for (int i = 0; i < n_filt; ++i) {
-        const int l = pts[i], m = pts[i + 1], r = pts[i + 2];
-        for (int j = l; j < m; ++j) bank[(size_t)i * n_bins + j] = (double)(j - l) / (double)(m - l);
-        for (int j = m; j < r; ++j) bank[(size_t)i * n_bins + j] = (double)(r - j) / (double)(r - m);
-    }
-    return KWS_OK;
-}
-
-static int build_bark_bank(int sample_rate, int n_fft, int n_filt, std::vector<double> &bank)
-{
-    // common/bark_feature.py:92-136 with scale="constant".  The bin<->Hz maps at :112/:134 are
-    // called with their DEFAULT nfft=512 and sample_rate=16000 whatever the caller passes; kept.
-    const int n_bins = n_fft / 2 + 1, n = n_filt + 4;
-    auto hz2bark = [](double f) { return 6.0 * std::asinh(f / 600.0); };
-    auto bark2hz = [](double v) { return 600.0 * std::sinh(v / 6.0); };
-    auto Fm = [](double fb, double fc) {
-        if (fc - 2.5 <= fb && fb <= fc - 0.5) return std::pow(10.0, 2.5 * (fb - fc + 0.5));
-        if (fc - 0.5 < fb && fb < fc + 0.5) return 1.0;
-        if (fc + 0.5 <= fb && fb <= fc + 1.3) return std::pow(10.0, -2.5 * (fb - fc - 0.5));
-        return 0.0;
-    };
-    const double lo = hz2bark(0.0), hi = hz2bark(sample_rate / 2.0), step = (hi - lo) / (double)(n - 1);
-    std::vector<double> pt(n);
-    std::vector<int> bins(n);
-    for (int i = 0; i < n; ++i) {
-        pt[i] = (i == n - 1) ? hi : lo + i * step;
-        bins[i] = (int)std::floor(513.0 * bark2hz(pt[i]) / 16000.0);
-    }
-    bank.assign((size_t)n_filt * n_bins, 0.0);
-    for (int i = 0; i < n_filt; ++i)
-        for (int j = bins[i]; j < bins[i + 4]; ++j) {
-            if (j < 0 || j >= n_bins) return fail(KWS_ERR_INVALID, "bark bank needs bin %d but n_fft=%d has %d", j, n_fft, n_bins);
-            bank[(size_t)i * n_bins + j] = std::fabs(Fm(hz2bark(j * 16000.0 / 513.0), pt[i + 2]));
-        }
-    return KWS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -697,24 +595,12 @@ static int launch_v3(const FeatDev &d, const WavT *wav, int B, int64_t stride, c
     const long jobs = (long)B * dd.jpc;
     if (jobs > 0x7fffffffL) return fail(KWS_ERR_UNSUPPORTED, "%ld featurizer jobs exceed the kernel's 32-bit job index", jobs);
     const unsigned grid = (unsigned)std::min<long>((long)bpc * cus, (jobs + WAVES - 1) / WAVES);
-    if constexpr (LONG)
-        KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, false, true>), dim3(grid), dim3(WAVES * 64), smem, s, wav,
-                   stride, valid_len, B, dd, feat);
-    else if constexpr (AUG)
-        KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, true>), dim3(grid), dim3(WAVES * 64), smem, s, wav, stride,
-                   valid_len, B, dd, feat, aug);
-    else
-        KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES>), dim3(grid), dim3(WAVES * 64), smem, s, wav, stride,
-                   valid_len, B, dd, feat);
+    KWS_LAUNCH(name, (featurize_fft1024_v3_kernel<WavT, CHP, kTunedBands, kTunedCoefs, WAVES, AUG, LONG>), dim3(grid), dim3(WAVES * 64), smem, s, wav, stride,
+               valid_len, B, dd, feat, aug);      // aug is {} (the kernel's default) unless AUG
     KWS_LAUNCH_CHECK("featurize_fft1024_v3_kernel");
     return KWS_OK;
 }
-#ifndef KWS_V3_ALONE_WAVES
-#define KWS_V3_ALONE_WAVES 8
-#endif
-#ifndef KWS_V3_ALONE_BLOCKS
-#define KWS_V3_ALONE_BLOCKS 2
-#endif
+constexpr int kV3AloneWaves = 8, kV3AloneBlocks = 2;
 template <typename WavT, int WAVES, bool AUG = false, bool LONG = false>
 static int launch_v3_chp(const FeatDev &d, const WavT *wav, int B, int64_t stride, const int32_t *valid_len, float *feat, hipStream_t s, const char *name, int bpc,
                          const AugDev &aug = {})
@@ -733,8 +619,112 @@ static int launch_v3_any(const FeatDev &d, const WavT *wav, int B, int64_t strid
                          const AugDev &aug = {})
 {
     if (d.blocks_per_cu == 1) return launch_v3_chp<WavT, kV3Waves, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, 1, aug);
-    return launch_v3_chp<WavT, KWS_V3_ALONE_WAVES, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, KWS_V3_ALONE_BLOCKS, aug);
+    return launch_v3_chp<WavT, kV3AloneWaves, AUG, LONG>(d, wav, B, stride, valid_len, feat, s, name, kV3AloneBlocks, aug);
 }
+
+// f(const float *) or f(const short *) for the samples at wav: the one place that reads wav_dtype.  Its return type and the lambdas'
+// are deduced, so they are instantiated where they are written and the kernels stay in the code object in source order.
+template <typename F> static auto with_wav(int wav_dtype, const void *wav, F &&f)
+{
+    if (wav_dtype == KWS_WAV_F32) return f(static_cast<const float *>(wav));
+    if (wav_dtype == KWS_WAV_I16) return f(static_cast<const short *>(wav));
+    return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
+}
+template <typename P> using wav_type = std::remove_cv_t<std::remove_pointer_t<P>>;
+// the launch's name in profiles: one per sample type
+template <typename WavT> static const char *wav_name(const char *name_f32, const char *name_i16) { return std::is_same<WavT, float>::value ? name_f32 : name_i16; }
+
+// the tables seen as "rows of n_frames frames from max_samples samples, no deltas": raw audio, long recordings and their segments
+static FeatDev rows_view(const kws_featurizer *f, int n_frames, int max_samples)
+{
+    FeatDev d = f->dev;
+    d.n_frames = n_frames; d.max_samples = max_samples; d.use_delta = 0; d.feature_size = d.n_out;
+    d.blocks_per_cu = f->blocks_per_cu; d.index = nullptr;
+    return d;
+}
+
+// the first-generation or the generic kernel on B clips: its dynamic LDS, the launch, its status
+template <typename WavT>
+static int launch_clips(const char *name, const char *what, void (*kernel)(const WavT *, int64_t, const int32_t *, int, FeatDev, float *), dim3 grid, dim3 block,
+                        size_t smem, hipStream_t s, const WavT *wav, int64_t stride, const int32_t *valid_len, int B, const FeatDev &d, float *feat)
+{
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), (int)smem)) return rc;
+    KWS_LAUNCH(name, kernel, grid, block, smem, s, wav, stride, valid_len, B, d, feat);
+    KWS_LAUNCH_CHECK(what);
+    return KWS_OK;
+}
+
+static int launch_generic(const FeatDev &d, const void *wav, int wav_dtype, int B, int64_t stride, const int32_t *valid_len, float *feat, void *stream)
+{
+    const size_t smem = generic_smem_bytes(d);
+    if (smem > kMaxLdsBytes) return fail(KWS_ERR_UNSUPPORTED, "n_fft=%d with %d frames needs %zu B of LDS (> 160 KiB)", d.n_fft, d.n_frames, smem);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return with_wav(wav_dtype, wav, [&](auto *w) {
+        using WavT = wav_type<decltype(w)>;
+        return launch_clips(wav_name<WavT>("featurize_generic_f32", "featurize_generic_i16"), "featurize_generic_kernel", featurize_generic_kernel<WavT>,
+                            dim3((unsigned)B), dim3(kGenWaves * 64), smem, s, w, stride, valid_len, B, d, feat);
+    });
+}
+
+static int launch_featurize(const FeatDev &d0, const void *wav, int wav_dtype, int B, int64_t stride, const int32_t *valid_len, float *feat, void *stream)
+{
+    if (d0.n_fft != 1024) return launch_generic(d0, wav, wav_dtype, B, stride, valid_len, feat, stream);
+    FeatDev d = d0;
+    feat_job_shape(d);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (v3_applies(d))
+        return with_wav(wav_dtype, wav, [&](auto *w) {
+            return launch_v3_any(d, w, B, stride, valid_len, feat, s, wav_name<wav_type<decltype(w)>>("featurize_fft1024_f32", "featurize_fft1024_i16"));
+        });
+    const size_t smem = feat_smem_bytes(d);
+    if (smem > kMaxLdsBytes) return fail(KWS_ERR_UNSUPPORTED, "%d frames need %zu B of LDS (> 160 KiB)", d.n_frames, smem);
+    const long jobs = (long)B * d.jpc;
+    const dim3 grid((unsigned)(d.use_delta ? B : (jobs + kWaves - 1) / kWaves));
+    return with_wav(wav_dtype, wav, [&](auto *w) {
+        using WavT = wav_type<decltype(w)>;
+        return launch_clips(wav_name<WavT>("featurize_fft1024_f32", "featurize_fft1024_i16"), "featurize_fft1024_kernel", featurize_fft1024_kernel<WavT>, grid,
+                            dim3(kThreads), smem, s, w, stride, valid_len, B, d, feat);
+    });
+}
+
+// kws_featurize_long off the tuned kernel's geometry (long_segments_kernel / long_rows_kernel above)
+template <typename WavT>
+static int featurize_long_segments(const kws_featurizer *f, const WavT *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths,
+                                   int max_frames, float *rows, hipStream_t s)
+{
+    const int window = f->geom.window_samples, hop = f->geom.hop_samples, D = f->dev.n_out;
+    // frames per segment: what the generic kernel can stage in LDS beside its FFT tiles, 256 at the most
+    int tile = 256;
+    if (f->dev.n_fft != 1024) {
+        const size_t fixed = (size_t)kGenWaves * f->dev.n_fft * 8 + kGenWaves * 256;
+        tile = (int)std::min<size_t>(256, (kMaxLdsBytes - fixed) / (4 * (size_t)D) - 4);
+    }
+    tile = std::max(1, std::min(tile, max_frames));
+    const int jpc = (max_frames + tile - 1) / tile;
+    const int64_t seg_len = (int64_t)(tile - 1) * hop + window, n_seg = (int64_t)R * jpc;
+    if (n_seg > 0x7fffffffL || seg_len > 0x7fffffffL) return fail(KWS_ERR_UNSUPPORTED, "%lld segments of %lld samples", (long long)n_seg, (long long)seg_len);
+    const size_t seg_bytes = (sizeof(WavT) * (size_t)n_seg * seg_len + 255) & ~(size_t)255;
+    unsigned char *tmp = nullptr;
+    KWS_HIP_CHECK(hipMallocAsync(reinterpret_cast<void **>(&tmp), seg_bytes + sizeof(float) * (size_t)n_seg * tile * D, s));
+    WavT *seg = reinterpret_cast<WavT *>(tmp);
+    float *seg_rows = reinterpret_cast<float *>(tmp + seg_bytes);
+    const int64_t n_in = n_seg * seg_len, n_out = (int64_t)R * max_frames * D;
+    const int cap = 64 * device_cus();
+    KWS_LAUNCH("long_segments_kernel", long_segments_kernel<WavT>, dim3((unsigned)std::min<int64_t>(cap, (n_in + 255) / 256)), dim3(256), 0, s, wav, stride,
+               lengths, jpc, (int64_t)tile * hop, (int)seg_len, n_in, seg);
+    KWS_LAUNCH_CHECK("long_segments_kernel");
+    int rc = launch_featurize(rows_view(f, tile, (int)seg_len), seg, wav_dtype, (int)n_seg, seg_len, nullptr, seg_rows, s);
+    if (rc == KWS_OK) {
+        KWS_LAUNCH("long_rows_kernel", long_rows_kernel, dim3((unsigned)std::min<int64_t>(cap, (n_out + 255) / 256)), dim3(256), 0, s, seg_rows, lengths,
+                   stride, window, hop, max_frames, (int64_t)jpc * tile, D, n_out, rows);
+        KWS_LAUNCH_CHECK("long_rows_kernel");
+    }
+    KWS_HIP_CHECK(hipFreeAsync(tmp, s));
+    return rc;
+}
+
+// a builder's status with its message (kws_featurize_tables.h) as this library reports errors
+static int table_status(int rc, const std::string &err) { return rc ? fail(rc, "%s", err.c_str()) : KWS_OK; }
 
 extern "C" {
 
@@ -746,15 +736,14 @@ void kws_params_default(kws_params *p)
     p->sample_rate = 16000; p->sample_depth = 2; p->n_fft = 1024; p->n_filt = 20; p->n_mfcc = 20; p->use_delta = 0;
 }
 
-int kws_params_derive(const kws_params *p, kws_geometry *g) { return derive(p, g); }
+int kws_params_derive(const kws_params *p, kws_geometry *g) { std::string err; return table_status(derive(p, g, err), err); }
 
 int kws_featurizer_create(const kws_params *p, int bank_kind, kws_featurizer **out)
 {
     if (!p || !out) return fail(KWS_ERR_INVALID, "null argument");
     *out = nullptr;
     kws_geometry g;
-    int rc = derive(p, &g);
-    if (rc) return rc;
+    if (int rc = kws_params_derive(p, &g)) return rc;
     if (bank_kind != KWS_BANK_MEL && bank_kind != KWS_BANK_BARK) return fail(KWS_ERR_INVALID, "unknown bank kind %d", bank_kind);
     if (p->n_filt < 1 || p->n_filt > 64) return fail(KWS_ERR_UNSUPPORTED, "n_filt must be in 1..64, got %d", p->n_filt);
     if (p->n_mfcc < 1 || p->n_mfcc > p->n_filt)
@@ -762,256 +751,55 @@ int kws_featurizer_create(const kws_params *p, int bank_kind, kws_featurizer **o
     if (p->n_fft < 64 || p->n_fft > 4096 || (p->n_fft & (p->n_fft - 1)))
         return fail(KWS_ERR_UNSUPPORTED, "n_fft must be a power of two in 64..4096 (got %d)", p->n_fft);
     if (g.max_samples < g.window_samples) return fail(KWS_ERR_INVALID, "buffer shorter than one window");
-    const int n_frames = (g.max_samples - g.window_samples) / g.hop_samples + 1;
-    if (n_frames != g.n_features)
-        return fail(KWS_ERR_INVALID, "params give %d frames but n_features=%d; the reference's model input would not match", n_frames, g.n_features);
+    if (clip_frames(g) != g.n_features)
+        return fail(KWS_ERR_INVALID, "params give %d frames but n_features=%d; the reference's model input would not match", clip_frames(g), g.n_features);
 
-    std::vector<double> bank;
-    rc = bank_kind == KWS_BANK_MEL ? build_mel_bank(p->sample_rate, p->n_fft, p->n_filt, bank)
-                                   : build_bark_bank(p->sample_rate, p->n_fft, p->n_filt, bank);
-    if (rc) return rc;
-    const int n_bins = p->n_fft / 2 + 1, n_filt = p->n_filt, n_out = p->n_mfcc;
-
-    // sparse tables: per band the span [first non-zero, last non-zero], cut into <= 64 lane chunks
-    std::vector<int> first(n_filt, 0), width(n_filt, 0);
-    for (int i = 0; i < n_filt; ++i) {
-        int a = -1, z = -1;
-        for (int j = 0; j < n_bins; ++j)
-            if (bank[(size_t)i * n_bins + j] != 0.0) { if (a < 0) a = j; z = j; }
-        if (a >= 0) { first[i] = a; width[i] = z - a + 1; }
-    }
-    // Chunk tables for the sparse band gather.  `align` = 1: a lane reads its bins one per LDS instruction (first-generation
-    // kernel); 2: chunks start on even positions so that two bins come per ds_read_b64 (kws_featurize_v3.h).
-    struct ChunkTables { int ch, chp, nlog; std::vector<int4> chunks; std::vector<float> w; std::vector<int> bcs; };
-    // `mirrored` (third-generation kernel): the chunks run over POSITIONS of the wave's two power planes (v3_pos_of_bin: bins 0..256 in
-    // place, bins 257..512 in descending order behind them), a band's span splits into at most two runs of consecutive positions, and the
-    // weights carry the factor 2^-12 the kernel leaves out of its power spectrum
-    auto build_chunks = [&](int align, bool mirrored = false) {
-        ChunkTables T;
-        const int npos = mirrored ? kV3OffM + 256 : n_bins;
-        std::vector<int> bin_of(npos, -1);
-        for (int k = 0; k < n_bins; ++k) bin_of[mirrored ? v3_pos_of_bin(k) : k] = k;
-        const double wscale = mirrored ? 1.0 / 4096.0 : 1.0;
-        struct Run { int band, lo, hi; };                        // positions [lo, hi)
-        std::vector<Run> runs;
-        for (int i = 0; i < n_filt; ++i) {
-            if (width[i] <= 0) continue;
-            if (!mirrored) { runs.push_back(Run{i, first[i], first[i] + width[i]}); continue; }
-            const int a = first[i], z = first[i] + width[i] - 1;
-            if (a <= 256) runs.push_back(Run{i, a, std::min(z, 256) + 1});
-            if (z >= 257) runs.push_back(Run{i, v3_pos_of_bin(z), v3_pos_of_bin(std::max(a, 257)) + 1});
-        }
-        int ch = align;
-        for (;; ch += align) {
-            int cnt = 0;
-            for (const Run &r : runs) cnt += ((r.hi - r.lo) + (r.lo % align) + ch - 1) / ch;
-            if (cnt <= kMaxChunks) break;
-        }
-        const int chp = (ch + 3) & ~3;
-        // logical chunks in band order: (band, first position, positions); chunk boundaries sit on multiples of `align`
-        struct Chunk { int band, a, len; };
-        std::vector<Chunk> logical;
-        std::vector<int> bcs(n_filt + 1, 0);
-        {
-            size_t ri = 0;
-            for (int i = 0; i < n_filt; ++i) {
-                bcs[i] = (int)logical.size();
-                for (; ri < runs.size() && runs[ri].band == i; ++ri) {
-                    const int s0 = runs[ri].lo - runs[ri].lo % align, end = runs[ri].hi;
-                    for (int lo = s0; lo < end; lo += ch) {
-                        const int a = std::max(lo, runs[ri].lo), z = std::min(lo + ch, end);
-                        if (z > a) logical.push_back(Chunk{i, a, z - a});
-                    }
-                }
-            }
-        }
-        bcs[n_filt] = (int)logical.size();
-        const int nlog = (int)logical.size();
-        // Lane placement.  Every lane reads p[start + t] for the same t, so the 32 lanes of a half-wave hit different LDS banks
-        // iff their starts (in units of `align` bins) differ mod 32.  A chunk of `len` bins may start anywhere (on a multiple
-        // of `align`) in [a + len - chp, a] (the extra bins get zero weights), so: bipartite matching of chunks to the 64
-        // (half, residue) slots, lane = 32 * half + residue.  (Chunk starts taken as they come collide ~3-way on average:
-        // 29 % of the first kernel's LDS cycles were conflicts.)
-        std::vector<int> start_of(nlog, 0), owner(64, -1);
-        {
-            std::vector<std::vector<std::pair<int, int>>> cand(nlog);          // (slot, start)
-            for (int c = 0; c < nlog; ++c)
-                for (int st = logical[c].a - logical[c].a % align; st >= std::max(0, logical[c].a + logical[c].len - chp); st -= align)
-                    for (int h = 0; h < 2; ++h) cand[c].push_back({32 * h + ((st / align) & 31), st});
-            std::vector<int> owner_start(64, 0);
-            std::function<bool(int, std::vector<char> &)> place = [&](int c, std::vector<char> &seen) -> bool {
-                for (auto &e : cand[c]) {
-                    if (seen[e.first]) continue;
-                    seen[e.first] = 1;
-                    if (owner[e.first] < 0 || place(owner[e.first], seen)) {
-                        owner[e.first] = c; owner_start[e.first] = e.second;
-                        return true;
-                    }
-                }
-                return false;
-            };
-            bool perfect = nlog <= 64;
-            for (int c = 0; c < nlog && perfect; ++c) {
-                std::vector<char> seen(64, 0);
-                perfect = place(c, seen);
-            }
-            if (perfect) {
-                for (int sl = 0; sl < 64; ++sl)
-                    if (owner[sl] >= 0) start_of[owner[sl]] = owner_start[sl];
-            } else {                                                           // keep the natural order (correct, just slower)
-                std::fill(owner.begin(), owner.end(), -1);
-                for (int c = 0; c < nlog && c < 64; ++c) { start_of[c] = logical[c].a - logical[c].a % align; owner[c] = c; }
-            }
-        }
-        // per-lane tables (always 64 lanes): {band, start, chunk id, 0} and chp weights; idle lanes take the unused chunk ids
-        T.chunks.assign(64, make_int4(0, 0, 0, 0));
-        T.w.assign((size_t)64 * chp, 0.f);
-        int spare = nlog;
-        for (int lane = 0; lane < 64; ++lane) {
-            const int c = owner[lane];
-            if (c < 0) { T.chunks[lane] = make_int4(0, 0, spare < 64 ? spare++ : 63, 0); continue; }
-            T.chunks[lane] = make_int4(logical[c].band, start_of[c], c, 0);
-            for (int t = 0; t < chp; ++t) {
-                const int pos = start_of[c] + t;
-                if (pos >= logical[c].a && pos < logical[c].a + logical[c].len && pos < npos && bin_of[pos] >= 0)
-                    T.w[(size_t)lane * chp + t] = (float)((double)(float)bank[(size_t)logical[c].band * n_bins + bin_of[pos]] * wscale);
-            }
-        }
-        T.ch = ch; T.chp = chp; T.nlog = nlog; T.bcs = bcs;
-        return T;
-    };
-    const ChunkTables T1 = build_chunks(1);
-    const bool v3_geom = p->n_fft == 1024;                                   // the position map is the 513-bin one
-    const ChunkTables T3 = build_chunks(2, v3_geom);
-    const int chp = T1.chp, nlog = T1.nlog, n_filt_pad = (n_filt + 3) & ~3;
-    const std::vector<int4> &chunks = T1.chunks;
-    const std::vector<float> &w = T1.w;
-    const std::vector<int> &bcs = T1.bcs;
-
-    std::vector<float2> tw1(7 * 64), tw2(7 * 8), tws(257);
-    for (int k = 1; k < 8; ++k)
-        for (int l = 0; l < 64; ++l) {
-            const double a = -2.0 * M_PI * (double)(l * k) / 512.0;
-            tw1[(k - 1) * 64 + l] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-    for (int k = 1; k < 8; ++k)
-        for (int l = 0; l < 8; ++l) {
-            const double a = -2.0 * M_PI * (double)(l * k) / 64.0;
-            tw2[(k - 1) * 8 + l] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-    for (int k = 0; k <= 256; ++k) {
-        const double a = -2.0 * M_PI * (double)k / 1024.0;
-        tws[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    std::vector<float2> tw1s(7 * 64), tws3(4 * 64);
-    for (int k = 1; k < 8; ++k)
-        for (int l = 0; l < 64; ++l) {
-            const double a = -2.0 * M_PI * (double)(v3_sigma(l) * k) / 512.0;
-            tw1s[(k - 1) * 64 + l] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-    for (int i = 0; i < 4; ++i)
-        for (int l = 0; l < 64; ++l) {
-            const double a = -2.0 * M_PI * (double)(l + 64 * i) / 1024.0;
-            tws3[i * 64 + l] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-    // generic-path tables (used when n_fft != 1024)
-    std::vector<float2> twg((size_t)p->n_fft / 2);
-    for (int k = 0; k < p->n_fft / 2; ++k) {
-        const double a = -2.0 * M_PI * (double)k / (double)p->n_fft;
-        twg[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    std::vector<float> bwf(bank.size());
-    for (size_t i = 0; i < bank.size(); ++i) bwf[i] = (float)bank[i];
-    std::vector<float> dct((size_t)n_filt_pad * n_out, 0.f);
-    for (int n = 0; n < n_filt; ++n)
-        for (int k = 0; k < n_out; ++k)  // scipy dct type II norm='ortho' (bark_feature.py:172, mfcc.h:55-67)
-            dct[(size_t)n * n_out + k] = (float)(std::cos(M_PI * (n + 0.5) * k / n_filt) * (k == 0 ? std::sqrt(1.0 / n_filt) : std::sqrt(2.0 / n_filt)));
-
+    FeatTables t;
+    std::string err;
+    if (int rc = build_feat_tables(*p, g, bank_kind, t, err)) return table_status(rc, err);
+    std::unique_ptr<kws_featurizer, decltype(&kws_featurizer_destroy)> f(new kws_featurizer(), kws_featurizer_destroy);
+    f->params = *p; f->geom = g; f->bank_kind = bank_kind; f->bank = t.bw;
+    FeatDev &d = f->dev;
+    // the device image: every table once, in the order the kernels have always found them
+    TableArena arena;
+    arena.add(t.tw1, &d.tw1);
+    arena.add(t.tw2, &d.tw2);
+    arena.add(t.tws, &d.tws);
+    arena.add(t.T1.chunks, &d.chunks, 1);
+    arena.add(t.T1.bcs, &d.bcs);
+    arena.add(t.T1.w, &d.w, 1);
+    arena.add(t.dct, &d.dct);
+    arena.add(t.twg, &d.twg);
+    arena.add(t.first, &d.bfirst);
+    arena.add(t.width, &d.bwidth);
+    arena.add(t.bw, &d.bw);
+    arena.add(t.T3.chunks, &d.chunks3);
+    arena.add(t.T3.bcs, &d.bcs3);
+    arena.add(t.T3.w, &d.w3);
+    arena.add(t.tw1s, &d.tw1s);
+    arena.add(t.tws3, &d.tws3);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
         return fail(KWS_ERR_HIP, "no HIP device: the featurizer has no CPU fallback");
     }
+    hipError_t e = hipMalloc(&f->dmem, arena.image.size());
+    if (e == hipSuccess) e = hipMemcpy(f->dmem, arena.image.data(), arena.image.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(KWS_ERR_HIP, "featurizer table upload failed: %s", hipGetErrorString(e));
+    arena.bind(f->dmem);
 
-    auto *f = new kws_featurizer();
-    f->params = *p; f->geom = g; f->bank_kind = bank_kind;
-    f->bank.resize(bank.size());
-    for (size_t i = 0; i < bank.size(); ++i) f->bank[i] = (float)bank[i];
-
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_tw1 = 0, o_tw2 = al(o_tw1 + tw1.size() * 8), o_tws = al(o_tw2 + tw2.size() * 8),
-                 o_ch = al(o_tws + tws.size() * 8), o_bcs = al(o_ch + std::max<size_t>(1, chunks.size()) * 16),
-                 o_w = al(o_bcs + bcs.size() * 4), o_dct = al(o_w + std::max<size_t>(1, w.size()) * 4),
-                 o_twg = al(o_dct + dct.size() * 4), o_bf = al(o_twg + twg.size() * 8), o_bwd = al(o_bf + first.size() * 4),
-                 o_bw = al(o_bwd + width.size() * 4), o_ch3 = al(o_bw + bwf.size() * 4),
-                 o_bcs3 = al(o_ch3 + 64 * 16), o_w3 = al(o_bcs3 + T3.bcs.size() * 4), o_tw1s = al(o_w3 + T3.w.size() * 4),
-                 o_tws3 = al(o_tw1s + tw1s.size() * 8), total = al(o_tws3 + tws3.size() * 8);
-    std::vector<unsigned char> host(total, 0);
-    std::memcpy(host.data() + o_tw1, tw1.data(), tw1.size() * 8);
-    std::memcpy(host.data() + o_tw2, tw2.data(), tw2.size() * 8);
-    std::memcpy(host.data() + o_tws, tws.data(), tws.size() * 8);
-    if (!chunks.empty()) std::memcpy(host.data() + o_ch, chunks.data(), chunks.size() * 16);
-    std::memcpy(host.data() + o_bcs, bcs.data(), bcs.size() * 4);
-    if (!w.empty()) std::memcpy(host.data() + o_w, w.data(), w.size() * 4);
-    std::memcpy(host.data() + o_dct, dct.data(), dct.size() * 4);
-    std::memcpy(host.data() + o_twg, twg.data(), twg.size() * 8);
-    std::memcpy(host.data() + o_bf, first.data(), first.size() * 4);
-    std::memcpy(host.data() + o_bwd, width.data(), width.size() * 4);
-    std::memcpy(host.data() + o_bw, bwf.data(), bwf.size() * 4);
-    std::memcpy(host.data() + o_ch3, T3.chunks.data(), 64 * 16);
-    std::memcpy(host.data() + o_bcs3, T3.bcs.data(), T3.bcs.size() * 4);
-    std::memcpy(host.data() + o_w3, T3.w.data(), T3.w.size() * 4);
-    std::memcpy(host.data() + o_tw1s, tw1s.data(), tw1s.size() * 8);
-    std::memcpy(host.data() + o_tws3, tws3.data(), tws3.size() * 8);
-    hipError_t e = hipMalloc(&f->dmem, total);
-    if (e == hipSuccess) e = hipMemcpy(f->dmem, host.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (f->dmem) (void)hipFree(f->dmem);
-        delete f;
-        return fail(KWS_ERR_HIP, "featurizer table upload failed: %s", hipGetErrorString(e));
-    }
-    auto *base = static_cast<unsigned char *>(f->dmem);
-    FeatDev &d = f->dev;
-    d.window_eff = std::min(g.window_samples, (int)p->n_fft);  // np.fft.rfft(frames, n): crop or zero-pad (bark_feature.py:87)
-    d.hop = g.hop_samples; d.max_samples = g.max_samples; d.n_frames = n_frames;
-    d.n_filt = n_filt; d.n_out = n_out; d.feature_size = g.feature_size; d.use_delta = p->use_delta ? 1 : 0;
-    d.nchunks = nlog; d.nnz = (int)w.size(); d.inv_nfft = 1.0f / (float)p->n_fft;
-    d.chp = chp; d.n_filt_pad = n_filt_pad;
-    d.tail_batch = std::max(1, std::min(4, 64 / std::max(n_filt_pad, n_out)));
-    d.tw1 = reinterpret_cast<const float2 *>(base + o_tw1);
-    d.tw2 = reinterpret_cast<const float2 *>(base + o_tw2);
-    d.tws = reinterpret_cast<const float2 *>(base + o_tws);
-    d.chunks = reinterpret_cast<const int4 *>(base + o_ch);
-    d.bcs = reinterpret_cast<const int *>(base + o_bcs);
-    d.w = reinterpret_cast<const float *>(base + o_w);
-    d.dct = reinterpret_cast<const float *>(base + o_dct);
-    d.n_fft = p->n_fft;
-    d.log2n = 0;
-    while ((1 << d.log2n) < p->n_fft) ++d.log2n;
-    d.twg = reinterpret_cast<const float2 *>(base + o_twg);
-    d.bfirst = reinterpret_cast<const int *>(base + o_bf);
-    d.bwidth = reinterpret_cast<const int *>(base + o_bwd);
-    d.bw = reinterpret_cast<const float *>(base + o_bw);
-    d.chp3 = (v3_geom && T3.nlog <= 64) ? T3.chp : 0;
-    d.chunks3 = reinterpret_cast<const int4 *>(base + o_ch3);
-    d.bcs3 = reinterpret_cast<const int *>(base + o_bcs3);
-    d.w3 = reinterpret_cast<const float *>(base + o_w3);
-    d.tw1s = reinterpret_cast<const float2 *>(base + o_tw1s);
-    d.tws3 = reinterpret_cast<const float2 *>(base + o_tws3);
+    d.window_eff = t.window_eff; d.hop = g.hop_samples; d.max_samples = g.max_samples; d.n_frames = t.n_frames;
+    d.n_filt = p->n_filt; d.n_out = p->n_mfcc; d.feature_size = g.feature_size; d.use_delta = p->use_delta ? 1 : 0;
+    d.nchunks = t.T1.nlog; d.nnz = (int)t.T1.w.size(); d.inv_nfft = 1.0f / (float)p->n_fft;
+    d.chp = t.T1.chp; d.n_filt_pad = t.n_filt_pad; d.tail_batch = t.tail_batch;
+    d.n_fft = p->n_fft; d.log2n = t.log2n;
+    d.chp3 = (p->n_fft == 1024 && t.T3.nlog <= 64) ? t.T3.chp : 0;
     // the LDS the launch will ask for (same job shape as launch_featurize / launch_generic, same 160 KiB limit)
-    if (d.n_fft == 1024) {
-        feat_job_shape(d);
-        f->smem_bytes = feat_smem_bytes(d);
-    } else {
-        f->smem_bytes = generic_smem_bytes(d);
-    }
-    if (f->smem_bytes > kMaxLdsBytes) {
-        const size_t need = f->smem_bytes;
-        (void)hipFree(f->dmem);
-        delete f;
-        return fail(KWS_ERR_UNSUPPORTED, "featurizer needs %zu B of LDS per block (> %d KiB)", need, (int)(kMaxLdsBytes / 1024));
-    }
-    *out = f;
+    if (d.n_fft == 1024) feat_job_shape(d);
+    f->smem_bytes = d.n_fft == 1024 ? feat_smem_bytes(d) : generic_smem_bytes(d);
+    if (f->smem_bytes > kMaxLdsBytes)
+        return fail(KWS_ERR_UNSUPPORTED, "featurizer needs %zu B of LDS per block (> %d KiB)", f->smem_bytes, (int)(kMaxLdsBytes / 1024));
+    *out = f.release();
     return KWS_OK;
 }
 
@@ -1034,69 +822,6 @@ int kws_featurizer_bank(const kws_featurizer *f, float *host_bank, size_t count)
     if (!f || !host_bank) return fail(KWS_ERR_INVALID, "null argument");
     if (count != f->bank.size()) return fail(KWS_ERR_INVALID, "bank has %zu floats, caller asked for %zu", f->bank.size(), count);
     std::memcpy(host_bank, f->bank.data(), count * sizeof(float));
-    return KWS_OK;
-}
-
-static int launch_generic(const FeatDev &d, const void *wav, int wav_dtype, int B, int64_t stride, const int32_t *valid_len,
-                          float *feat, void *stream)
-{
-    const size_t smem = generic_smem_bytes(d);
-    if (smem > kMaxLdsBytes) return fail(KWS_ERR_UNSUPPORTED, "n_fft=%d with %d frames needs %zu B of LDS (> 160 KiB)", d.n_fft, d.n_frames, smem);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)B), block(kGenWaves * 64);
-    if (wav_dtype == KWS_WAV_F32) {
-        if (smem > 64 * 1024)
-            KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&featurize_generic_kernel<float>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        KWS_LAUNCH("featurize_generic_f32", featurize_generic_kernel<float>, grid, block, smem, s, static_cast<const float *>(wav), stride,
-                   valid_len, B, d, feat);
-    } else if (wav_dtype == KWS_WAV_I16) {
-        if (smem > 64 * 1024)
-            KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&featurize_generic_kernel<short>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        KWS_LAUNCH("featurize_generic_i16", featurize_generic_kernel<short>, grid, block, smem, s, static_cast<const short *>(wav), stride,
-                   valid_len, B, d, feat);
-    } else {
-        return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
-    }
-    KWS_LAUNCH_CHECK("featurize_generic_kernel");
-    return KWS_OK;
-}
-
-static int launch_featurize(const FeatDev &d0, const void *wav, int wav_dtype, int B, int64_t stride,
-                            const int32_t *valid_len, float *feat, void *stream)
-{
-    if (d0.n_fft != 1024) return launch_generic(d0, wav, wav_dtype, B, stride, valid_len, feat, stream);
-    FeatDev d = d0;
-    feat_job_shape(d);
-    if (v3_applies(d)) {
-        if (wav_dtype == KWS_WAV_F32)
-            return launch_v3_any(d, static_cast<const float *>(wav), B, stride, valid_len, feat, static_cast<hipStream_t>(stream), "featurize_fft1024_f32");
-        if (wav_dtype == KWS_WAV_I16)
-            return launch_v3_any(d, static_cast<const short *>(wav), B, stride, valid_len, feat, static_cast<hipStream_t>(stream), "featurize_fft1024_i16");
-        return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
-    }
-    const size_t smem = feat_smem_bytes(d);
-    if (smem > kMaxLdsBytes) return fail(KWS_ERR_UNSUPPORTED, "%d frames need %zu B of LDS (> 160 KiB)", d.n_frames, smem);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long jobs = (long)B * d.jpc;
-    const dim3 grid((unsigned)(d.use_delta ? B : (jobs + kWaves - 1) / kWaves)), block(kThreads);
-    if (wav_dtype == KWS_WAV_F32) {
-        if (smem > 64 * 1024)
-            KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&featurize_fft1024_kernel<float>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        KWS_LAUNCH("featurize_fft1024_f32", featurize_fft1024_kernel<float>, grid, block, smem, s, static_cast<const float *>(wav), stride,
-                           valid_len, B, d, feat);
-    } else if (wav_dtype == KWS_WAV_I16) {
-        if (smem > 64 * 1024)
-            KWS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&featurize_fft1024_kernel<short>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        KWS_LAUNCH("featurize_fft1024_i16", featurize_fft1024_kernel<short>, grid, block, smem, s, static_cast<const short *>(wav), stride,
-                           valid_len, B, d, feat);
-    } else {
-        return fail(KWS_ERR_INVALID, "unknown wav dtype %d", wav_dtype);
-    }
-    KWS_LAUNCH_CHECK("featurize_fft1024_kernel");
     return KWS_OK;
 }
 
@@ -1129,9 +854,10 @@ int kws_featurize_gather_augmented(kws_featurizer *f, const void *wav, int wav_d
         feat_job_shape(d);
         if (v3_applies(d)) {       // the default geometry: the mix happens in the tuned kernel's sample loads
             const AugDev aug{plan, bank->samples, bank->d_start};
-            if (wav_dtype == KWS_WAV_F32)
-                return launch_v3_any<float, true>(d, static_cast<const float *>(wav), B, stride, nullptr, feat, s, "featurize_fft1024_aug_f32", aug);
-            return launch_v3_any<short, true>(d, static_cast<const short *>(wav), B, stride, nullptr, feat, s, "featurize_fft1024_aug_i16", aug);
+            return with_wav(wav_dtype, wav, [&](auto *w) {
+                using WavT = wav_type<decltype(w)>;
+                return launch_v3_any<WavT, true>(d, w, B, stride, nullptr, feat, s, wav_name<WavT>("featurize_fft1024_aug_f32", "featurize_fft1024_aug_i16"), aug);
+            });
         }
     }
     // other geometries: materialise the clips (stream-ordered scratch), then the plain featurizer on them with valid_len = L
@@ -1170,6 +896,7 @@ int kws_featurizer_occupancy(const kws_featurizer *f, int *blocks_per_cu, size_t
     const size_t smem = f->smem_bytes;
     if (lds_bytes) *lds_bytes = smem;
     int nb = 0;
+    // n_fft = 1024 reports the first-generation kernel even where the tuned one (launch_v3) runs: odd, but callers have always seen it
     if (tuned)
         KWS_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, featurize_fft1024_kernel<float>, kThreads, smem));
     else
@@ -1189,59 +916,10 @@ int kws_featurize_raw(kws_featurizer *f, const void *wav, int wav_dtype, int B, 
 {
     if (!f || !feat || (!wav && B > 0)) return fail(KWS_ERR_INVALID, "null argument");
     if (B < 0 || n_samples < 0 || stride < n_samples) return fail(KWS_ERR_INVALID, "bad batch / n_samples / stride");
-    FeatDev d = f->dev;
-    d.n_frames = kws_featurize_raw_frames(f, n_samples);
-    if (B == 0 || d.n_frames == 0) return KWS_OK;  // sonopy returns an empty matrix
-    d.max_samples = n_samples;
-    d.use_delta = 0;
-    d.feature_size = d.n_out;
-    d.blocks_per_cu = f->blocks_per_cu;
-    return launch_featurize(d, wav, wav_dtype, B, stride, nullptr, feat, stream);
+    const int n_frames = kws_featurize_raw_frames(f, n_samples);
+    if (B == 0 || n_frames == 0) return KWS_OK;  // sonopy returns an empty matrix
+    return launch_featurize(rows_view(f, n_frames, n_samples), wav, wav_dtype, B, stride, nullptr, feat, stream);
 }
-
-extern "C++" {
-template <typename WavT>
-static int featurize_long_segments(const kws_featurizer *f, const WavT *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths,
-                                   int max_frames, float *rows, hipStream_t s)
-{
-    const int window = f->geom.window_samples, hop = f->geom.hop_samples, D = f->dev.n_out;
-    // frames per segment: what the generic kernel can stage in LDS beside its FFT tiles, 256 at the most
-    int tile = 256;
-    if (f->dev.n_fft != 1024) {
-        const size_t fixed = (size_t)kGenWaves * f->dev.n_fft * 8 + kGenWaves * 256;
-        tile = (int)std::min<size_t>(256, (kMaxLdsBytes - fixed) / (4 * (size_t)D) - 4);
-    }
-    tile = std::max(1, std::min(tile, max_frames));
-    const int jpc = (max_frames + tile - 1) / tile;
-    const int64_t seg_len = (int64_t)(tile - 1) * hop + window, n_seg = (int64_t)R * jpc;
-    if (n_seg > 0x7fffffffL || seg_len > 0x7fffffffL) return fail(KWS_ERR_UNSUPPORTED, "%lld segments of %lld samples", (long long)n_seg, (long long)seg_len);
-    const size_t seg_bytes = (sizeof(WavT) * (size_t)n_seg * seg_len + 255) & ~(size_t)255;
-    unsigned char *tmp = nullptr;
-    KWS_HIP_CHECK(hipMallocAsync(reinterpret_cast<void **>(&tmp), seg_bytes + sizeof(float) * (size_t)n_seg * tile * D, s));
-    WavT *seg = reinterpret_cast<WavT *>(tmp);
-    float *seg_rows = reinterpret_cast<float *>(tmp + seg_bytes);
-    const int64_t n_in = n_seg * seg_len, n_out = (int64_t)R * max_frames * D;
-    const int cap = 64 * device_cus();
-    KWS_LAUNCH("long_segments_kernel", long_segments_kernel<WavT>, dim3((unsigned)std::min<int64_t>(cap, (n_in + 255) / 256)), dim3(256), 0, s, wav, stride,
-               lengths, jpc, (int64_t)tile * hop, (int)seg_len, n_in, seg);
-    KWS_LAUNCH_CHECK("long_segments_kernel");
-    FeatDev d = f->dev;
-    d.n_frames = tile;
-    d.max_samples = (int)seg_len;
-    d.use_delta = 0;
-    d.feature_size = d.n_out;
-    d.blocks_per_cu = f->blocks_per_cu;
-    d.index = nullptr;
-    int rc = launch_featurize(d, seg, wav_dtype, (int)n_seg, seg_len, nullptr, seg_rows, s);
-    if (rc == KWS_OK) {
-        KWS_LAUNCH("long_rows_kernel", long_rows_kernel, dim3((unsigned)std::min<int64_t>(cap, (n_out + 255) / 256)), dim3(256), 0, s, seg_rows, lengths,
-                   stride, window, hop, max_frames, (int64_t)jpc * tile, D, n_out, rows);
-        KWS_LAUNCH_CHECK("long_rows_kernel");
-    }
-    KWS_HIP_CHECK(hipFreeAsync(tmp, s));
-    return rc;
-}
-}  // extern "C++"
 
 int kws_featurize_long(kws_featurizer *f, const void *wav, int wav_dtype, int R, int64_t stride, const int32_t *lengths, int max_frames,
                        float *rows, void *stream)
@@ -1255,21 +933,14 @@ int kws_featurize_long(kws_featurizer *f, const void *wav, int wav_dtype, int R,
     if ((int64_t)max_frames * std::max(f->geom.hop_samples, f->dev.n_out) > 0x7fffffffL - f->geom.window_samples)
         return fail(KWS_ERR_INVALID, "max_frames=%d is more than an int32 sample count can hold", max_frames);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    FeatDev d = f->dev;
-    d.n_frames = max_frames;
-    d.use_delta = 0;
-    d.feature_size = d.n_out;
-    d.blocks_per_cu = f->blocks_per_cu;
-    d.index = nullptr;
+    FeatDev d = rows_view(f, max_frames, f->dev.max_samples);
     feat_job_shape(d);
-    if (d.n_fft == 1024 && v3_applies(d)) {      // the default geometry: tiles of frames are the tuned kernel's own jobs
-        if (wav_dtype == KWS_WAV_F32)
-            return launch_v3_any<float, false, true>(d, static_cast<const float *>(wav), R, stride, lengths, rows, s, "featurize_long_f32");
-        return launch_v3_any<short, false, true>(d, static_cast<const short *>(wav), R, stride, lengths, rows, s, "featurize_long_i16");
-    }
-    if (wav_dtype == KWS_WAV_F32)
-        return featurize_long_segments(f, static_cast<const float *>(wav), wav_dtype, R, stride, lengths, max_frames, rows, s);
-    return featurize_long_segments(f, static_cast<const short *>(wav), wav_dtype, R, stride, lengths, max_frames, rows, s);
+    if (d.n_fft == 1024 && v3_applies(d))      // the default geometry: tiles of frames are the tuned kernel's own jobs
+        return with_wav(wav_dtype, wav, [&](auto *w) {
+            using WavT = wav_type<decltype(w)>;
+            return launch_v3_any<WavT, false, true>(d, w, R, stride, lengths, rows, s, wav_name<WavT>("featurize_long_f32", "featurize_long_i16"));
+        });
+    return with_wav(wav_dtype, wav, [&](auto *w) { return featurize_long_segments(f, w, wav_dtype, R, stride, lengths, max_frames, rows, s); });
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 // Pass 1's lanes own the input points 8 (l & 7) + (l >> 3) + 64 a, i.e. a wave's sample loads are strided by 64 B between lanes inside
 // the same 512 B: as many cache lines per instruction, more tag look-ups (the address path is far from its limit here).
 #pragma once
+#include "kws_featurize_tables.h"   // kV3OffM, v3_sigma, v3_pos_of_bin: the host tables follow them
 
 // Every multiply-add of this file is written out (fmaf) and the compiler's own contraction is off: the kernel has two instantiations per
 // input type (twiddles from LDS / from registers) that must give the same bits (tests/test_featurizer_gpu.py), and left to itself the
@@ -143,12 +144,7 @@ __device__ __forceinline__ void dft8x(float2 (&v)[8])
 constexpr int kV3Waves = 12;
 constexpr int kV3Comp = 520;                 // floats per component (8 planes of 64 + padding)
 constexpr int kV3Tile = 2 * kV3Comp;         // floats per wave: re planes, im planes
-constexpr int kV3OffM = 320;                 // the mirrored half of the power spectrum: position kV3OffM + p holds bin 512 - p, p = 0..255
 __host__ __device__ constexpr int v3_plane(int A) { return 64 * A + 4 * ((A + 2) >> 2); }
-// pass-1 lane l owns the input points sigma(l) + 64 a
-__host__ __device__ inline int v3_sigma(int l) { return 8 * (l & 7) + (l >> 3); }
-// position of bin k in the wave's power planes
-__host__ __device__ inline int v3_pos_of_bin(int k) { return k <= 256 ? k : kV3OffM + 512 - k; }
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void lds_wait4(f32x4v (&a)[4])
