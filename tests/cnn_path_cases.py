@@ -26,7 +26,7 @@ Case = collections.namedtuple("Case", "id row mode")
 
 # ---- the library's selection rules, restated ----------------------------------------------------------------------------
 def dims(nf, fs):
-    """CnnDims of kws_model_create: two 'valid' 2x2 pools, conv3 with stride 2 and 'same' padding, one more pool"""
+    """cnn_dims (csrc/kws_cnn_shape.h), the CnnDims of kws_model_create: two 'valid' 2x2 pools, conv3 with stride 2 and 'same' padding, one more pool"""
     H1, W1 = nf // 2, fs // 2
     H2, W2 = H1 // 2, W1 // 2
     H3, W3 = (H2 + 1) // 2, (W2 + 1) // 2
@@ -35,7 +35,7 @@ def dims(nf, fs):
 
 
 def parity_class_rows(B, H, W, stride):
-    """rows (input pixels times clips) of every stride-parity class of launch_dgrad (kws_model.hip), in its order"""
+    """rows (input pixels times clips) of every stride-parity class of dgrad_plan (csrc/kws_cnn_shape.h, called by launch_dgrad), in its order"""
     rows = []
     for cy in range(min(stride, 2)):
         for cx in range(min(stride, 2)):
@@ -46,7 +46,7 @@ def parity_class_rows(B, H, W, stride):
 
 
 def dgrad_mw(rows, simds):
-    """launch_dgrad's template parameter MW (16-row tiles per wave): the waves of all classes are dealt over the SIMDs, every SIMD's
+    """launch_dgrad's template parameter MW (16-row tiles per wave, dgrad_plan in csrc/kws_cnn_shape.h): the waves of all classes are dealt over the SIMDs, every SIMD's
     matrix pipe runs ceil(waves / simds) * MW tile-times, the smallest product wins and a tie goes to the larger MW"""
     best, best_cost = 4, -1
     for mw in (4, 3, 2, 1):
@@ -76,7 +76,8 @@ def dgrad_mws(B, nf, fs, cus=MI355X_CUS):
 # those batches do, so MW = 4 has no case here.  MW_ROWS maps each covered value to (frames, coefficients, batch); MW_BEYOND records
 # where MW = 4 starts; the host test checks every figure against the restated rule.
 # The label of the launch ("conv_dgrad<64,32>") is the same for every MW, so the profile cannot show which instantiation ran: these
-# cases rest on the restated rule and on the device reporting MI355X_CUS compute units, which the GPU test checks before it runs them.
+# cases rest on the restated rule and on the device reporting MI355X_CUS compute units, which the GPU test checks before it runs them;
+# tests/test_cnn_shape_host.py holds the library's own rule (dgrad_plan, csrc/kws_cnn_shape.h) to the restatement on the host.
 MW_ROWS = {1: (30, 20, 96), 2: (30, 20, 468), 3: (62, 21, 437)}
 MW_BEYOND = {4: {(62, 21): 656, (30, 20): 1405}}
 MAX_ORACLE_BATCH = 512
@@ -212,34 +213,59 @@ def reference(row):
 
 
 # ---- path evidence ----------------------------------------------------------------------------------------------------
-def expected_labels(row, mode):
-    """(labels that the train step's profile must hold, substrings that no label may hold) for an eager step of `row` in `mode`,
-    read off plan_cnn and the stage functions of csrc/kws_model.hip.  While profiling, the per-layer kernels report as "<name>.L<n>"."""
-    assert not mode.startswith("captured"), "profiling is not enabled inside a capture"
+def plan_flags(row, mode, capturing=False, training=True, wants_head=False, prepared=False):
+    """plan_cnn (csrc/kws_cnn_plan.h) restated: every flag of the CnnPlan of a simple_cnn call on `row`'s map, class count and batch in
+    `mode`, as a dict.  capturing: the caller's stream is being captured into a graph (the "captured" modes imply it).  The last three
+    arguments are plan_cnn's own: a train step by default, else an inference that takes the head's outputs from the forward or not, after
+    kws_model_prepare_inference or not.  tests/test_cnn_shape_host.py holds the dict to the C++ on the host."""
     d = dims(row.nf, row.fs)
     bf16 = "fp32" not in mode
     det = "det" in mode
+    capturing = capturing or mode.startswith("captured")
+    split_train = bf16 and training
     default_map = (row.nf, row.fs) == DEFAULT_MAP
     P1 = d["H1"] * d["W1"]
-    # plan_cnn
     default_tail = (d["H2"], d["W2"], d["H3"], d["W3"]) == (7, 5, 4, 3)
-    group = bf16 and default_tail and (row.B + 15) // 16 <= 1024      # blocks_for(B, kFuClips) <= kStatStride
-    head_bwd_fuses = row.C <= 48
+    fused_tail = not training and wants_head and bf16 and default_tail and (d["H4"], d["W4"]) == (2, 1) and row.C <= 48
+    group = split_train and default_tail and (row.B + 15) // 16 <= 1024      # blocks_for(B, kFuClips) <= kStatStride
+    head_bwd_fuses = row.C <= 48                                              # head_K = 128 passes the rule's other two terms
     fuse_head_fwd = head_bwd_fuses and not det
-    dense_fused = bf16 and fuse_head_fwd and d["flat"] % 128 == 0 and d["flat"] <= 1024
+    dense_fused = split_train and fuse_head_fwd and d["flat"] % 128 == 0 and d["flat"] <= 1024
     l1m = row.nf % 2 == 0 and row.fs % 2 == 0 and (row.nf + 2) * (row.fs + 2) <= 64 * 12 and P1 <= 4 * 40
+    prep_in_stats = split_train and l1m
     compact_g2 = bf16 and P1 * 8 <= 1280 and (d["H1"] // 2) * (d["W1"] // 2) * 32 <= 4 * d["H3"] * d["W3"] * 64
-    fuse_pool2 = group and compact_g2 and (d["H1"], d["W1"]) == (15, 10)
-    acc_ok = not det
+    routed_g2 = compact_g2
+    fuse_pool2 = group and routed_g2 and (d["H1"], d["W1"]) == (15, 10)
+    acc_ok = not det and not capturing
     acc_fwd = fuse_pool2 and acc_ok
-    l1_conv2 = bf16 and l1m and acc_fwd and default_map
+    l1_conv2 = prep_in_stats and acc_fwd and default_map
+    a3_on_load = split_train
     pool4_fused = acc_fwd and dense_fused
+    wgrad_pmajor = split_train and not det and d["H3"] * d["W3"] <= 16
     wgrad2_bf16 = bf16 and P1 <= 160
-    wgrad2_early = compact_g2 and wgrad2_bf16 and P1 * 4 <= 768
-    acc_bn2 = group and acc_ok and compact_g2 and wgrad2_early
+    wgrad2_early = compact_g2 and wgrad2_bf16 and P1 * 8 <= 1280 and P1 * 4 <= 768
+    acc_bn2 = group and acc_ok and routed_g2 and wgrad2_early
     acc_bn3 = group and acc_ok
-    acc_bn4 = dense_fused and acc_ok
+    acc_bn4 = dense_fused and acc_ok and d["flat"] == d["H4"] * d["W4"] * 128
     l1_fin_in_kernel = acc_ok and default_map
+    wgrad2_fast = wgrad2_early and acc_bn2 and (d["H1"], d["W1"]) == (15, 10)
+    return dict(training=training, bf16=bf16, det=det, prepared=not training and prepared, fused_tail=fused_tail, group=group,
+                dense_fused=dense_fused, l1m=l1m, l1_default_map=default_map, prep_in_stats=prep_in_stats, l1_conv2=l1_conv2,
+                compact_g2=compact_g2, routed_g2=routed_g2, fuse_pool2=fuse_pool2, acc_fwd=acc_fwd, acc_bn2=acc_bn2, acc_bn3=acc_bn3,
+                acc_bn4=acc_bn4, a3_on_load=a3_on_load, pool4_fused=pool4_fused, wgrad_pmajor=wgrad_pmajor, wgrad2_bf16=wgrad2_bf16,
+                wgrad2_early=wgrad2_early, wgrad2_fast=wgrad2_fast, l1_fin_in_kernel=l1_fin_in_kernel, head_bwd_fuses=head_bwd_fuses,
+                fuse_head_fwd=fuse_head_fwd)
+
+
+def expected_labels(row, mode):
+    """(labels that the train step's profile must hold, substrings that no label may hold) for an eager step of `row` in `mode`,
+    read off plan_cnn (plan_flags above) and the stage functions of csrc/kws_model.hip.  While profiling, the per-layer kernels report
+    as "<name>.L<n>"."""
+    assert not mode.startswith("captured"), "profiling is not enabled inside a capture"
+    f = plan_flags(row, mode)
+    bf16, det, group, l1m, l1_conv2, l1_fin_in_kernel = f["bf16"], f["det"], f["group"], f["l1m"], f["l1_conv2"], f["l1_fin_in_kernel"]
+    acc_fwd, fuse_pool2, pool4_fused, dense_fused, fuse_head_fwd = f["acc_fwd"], f["fuse_pool2"], f["pool4_fused"], f["dense_fused"], f["fuse_head_fwd"]
+    acc_bn2, acc_bn3, acc_bn4, wgrad2_bf16 = f["acc_bn2"], f["acc_bn3"], f["acc_bn4"], f["wgrad2_bf16"]
 
     have, lack = [], []
 

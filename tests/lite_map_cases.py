@@ -32,7 +32,7 @@ MUTATION_FACTOR = 100
 
 # ---- the library's admission rules, restated ----------------------------------------------------------------------------
 def pad_before(n, k, s):
-    """same_pad_before (csrc/kws_layers.h): TF 'SAME' puts the odd padding pixel at the end"""
+    """same_pad_before (csrc/kws_cnn_shape.h): TF 'SAME' puts the odd padding pixel at the end"""
     out = -(-n // s)
     return max((out - 1) * s + k - n, 0) // 2
 

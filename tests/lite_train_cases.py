@@ -77,9 +77,9 @@ TIE_MARGIN = 5e-7                  # no hard decision of the oracle's pass close
 PAD_MUTATION, CAP_MUTATION = 100, 10          # what a wrong padding side / a dropped last block must move, in tolerances
 
 
-# ---- the launch arithmetic of csrc/kws_model.hip, restated -------------------------------------------------------------------
+# ---- the launch arithmetic of csrc/kws_cnn_shape.h, restated -----------------------------------------------------------------
 def stat_grid(M, C):
-    """stat_grid (csrc/kws_model.hip): (blocks, rows per block) of an (M x C) channel reduction, at most STAT_STRIDE blocks"""
+    """stat_grid (csrc/kws_cnn_shape.h): (blocks, rows per block) of an (M x C) channel reduction, at most STAT_STRIDE blocks"""
     R = 256 // C
     want = (M + R * 8 - 1) // (R * 8)
     nblk = min(STAT_STRIDE, max(1, want))
@@ -94,7 +94,7 @@ def stat_capped(M, C):
 
 
 def dgrad_mw(rows, cus):
-    """the loop of launch_dgrad (csrc/kws_model.hip) for one parity class: from mw = 4 down to 1, the strictly smaller
+    """the loop of dgrad_plan (csrc/kws_cnn_shape.h) for one parity class: from mw = 4 down to 1, the strictly smaller
     ceil(waves / (4 cus)) * mw is kept"""
     simds = 4 * cus
     best, best_cost = 4, -1
@@ -107,7 +107,7 @@ def dgrad_mw(rows, cus):
 
 
 def same_pad_before(n, k, s):
-    """same_pad_before (csrc/kws_model.hip): TF 'SAME' puts the odd padding pixel at the end"""
+    """same_pad_before (csrc/kws_cnn_shape.h): TF 'SAME' puts the odd padding pixel at the end"""
     out = -(-n // s)
     return max((out - 1) * s + k - n, 0) // 2
 

@@ -1,5 +1,6 @@
 """The position-major weight gradient's valid-position lists and block partition (tests/wgrad_pmajor_cases.py, which restates
-csrc/kws_conv.h: wgrad_pm_plan and the kernel's block decoding), proven on the restatement alone; tests/test_wgrad_pmajor_gpu.py holds
+csrc/kws_cnn_shape.h: wgrad_pm_plan and the block decoding of the kernel in csrc/kws_conv.h), proven on the restatement alone;
+tests/test_cnn_shape_host.py holds the C++ plan to it on the host, tests/test_wgrad_pmajor_gpu.py holds
 the C++ to the same rule through its results.
 
 Five feature maps (cases.MAPS) and B in 1..70 and 680..1400:

@@ -1,4 +1,4 @@
-"""The launch arithmetic of the position-major split-precision weight gradient (csrc/kws_conv.h: WgradPm, wgrad_pm_plan and the block
+"""The launch arithmetic of the position-major split-precision weight gradient (csrc/kws_cnn_shape.h: WgradPm, wgrad_pm_plan; csrc/kws_conv.h: the block
 decoding at the top of conv_wgrad_bf16_kernel<..., PM = true>), restated in Python, and the feature maps the tests use.
 
 conv4 (3 x 3, stride 1, 'same') maps the H3 x W3 map conv3 (3 x 3, stride 2, 'same') produces onto itself.  When that map has at most 16

@@ -4,16 +4,10 @@
 // backward pass, kws_model_forward / kws_model_prepare_inference build the inference plan; the stage functions in kws_model.hip only read it.
 // A flag that follows from another is derived from it, so the two passes cannot disagree about what the forward left for the backward
 // (fragment-major weight planes, zmax2 / arg2, the accumulator sets, layer 4's activation).  The builder makes no HIP call: the caller
-// queries the stream's capture state once and passes it in.
+// queries the stream's capture state once and passes it in.  The shape constants of the kernels it chooses between live in
+// kws_cnn_shape.h, the only header this one includes: tests/host/cnn_shape_main.cpp builds plan_cnn with a plain C++ compiler.
 #pragma once
-#include "kws_model_types.h"
-#include "kws_layers.h"
-#include "kws_layer1.h"
-#include "kws_infer_fused.h"
-#include "kws_conv_group.h"
-#include "kws_dense_head.h"
-#include "kws_conv.h"
-#include "kws_conv2_wgrad_fast.h"
+#include "kws_cnn_shape.h"
 
 namespace kws {
 
@@ -43,25 +37,28 @@ struct CnnPlan {
     bool fuse_head_fwd;      // the head's forward pass rides in its backward kernel
 };
 
+// what plan_cnn reads of a model (kws_model.hip: cnn_desc)
+struct CnnDesc { int kind, C, head_K, deterministic; CnnDims d; };
+
 // mprec: the model's matrix precision (1 = split bf16); capturing: the caller's stream is being captured into a hipGraph;
 // wants_head_outputs: an inference caller that takes probs / argmax from the forward itself; prepared: kws_model::prepared_for(...)
-inline CnnPlan plan_cnn(const kws_model *m, int B, int mprec, bool training, bool capturing, bool wants_head_outputs, bool prepared)
+inline CnnPlan plan_cnn(const CnnDesc &m, int B, int mprec, bool training, bool capturing, bool wants_head_outputs, bool prepared)
 {
-    const CnnDims &d = m->d;
+    const CnnDims &d = m.d;
     CnnPlan p{};
     p.training = training;
     p.bf16 = mprec == 1;
-    p.det = m->deterministic != 0;
+    p.det = m.deterministic != 0;
     p.prepared = !training && prepared;
     const bool split_train = p.bf16 && training;
     // the geometry the one-kernel inference tail and the clip-group kernels are built for
-    const bool default_tail = m->kind == KWS_SIMPLE_CNN && d.H2 == kFuH2 && d.W2 == kFuW2 && d.H3 == kFuH3 && d.W3 == kFuW3;
-    p.fused_tail = !training && wants_head_outputs && p.bf16 && default_tail && d.H4 == kFuH4 && d.W4 == kFuW4 && m->C <= kFuHeadCols;
+    const bool default_tail = m.kind == KWS_SIMPLE_CNN && d.H2 == kFuH2 && d.W2 == kFuW2 && d.H3 == kFuH3 && d.W3 == kFuW3;
+    p.fused_tail = !training && wants_head_outputs && p.bf16 && default_tail && d.H4 == kFuH4 && d.W4 == kFuW4 && m.C <= kFuHeadCols;
     // the group kernels leave their BatchNorm sums per block: at most kStatStride blocks
     p.group = split_train && default_tail && (long)blocks_for(B, kFuClips) <= kStatStride;
-    p.head_bwd_fuses = head_bwd_fuses(m);
+    p.head_bwd_fuses = head_bwd_fuses(m.head_K, m.C);
     p.fuse_head_fwd = p.head_bwd_fuses && !p.det;
-    p.dense_fused = split_train && m->kind == KWS_SIMPLE_CNN && p.fuse_head_fwd && m->head_K == kDhK && d.flat % (16 * kDhWaves) == 0 && d.flat <= 1024;
+    p.dense_fused = split_train && m.kind == KWS_SIMPLE_CNN && p.fuse_head_fwd && m.head_K == kDhK && d.flat % (16 * kDhWaves) == 0 && d.flat <= 1024;
     // every pixel in a pool window, a haloed map of at most 768 floats and at most 40 tiles
     p.l1m = d.H0 % 2 == 0 && d.W0 % 2 == 0 && (d.H0 + 2) * (d.W0 + 2) <= 64 * kL1Stage && (d.H0 / 2) * (d.W0 / 2) <= 4 * kL1MaxTiles;
     p.l1_default_map = d.H0 == 30 && d.W0 == 20;

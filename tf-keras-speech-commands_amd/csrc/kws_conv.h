@@ -15,17 +15,10 @@
 // LDS strides of the FWD kernel keep every half-wave ds_read_b32 of a fragment bank-conflict free
 // (row stride == 2 mod 32 words for A[row][k], == 16 mod 32 for [k][col] tiles).
 #pragma once
+#include "kws_cnn_shape.h"   // ConvGeom, DgradClasses, WgradPm and the host rules that build them
 #include "kws_device.h"
 
 namespace kws {
-
-struct ConvGeom {
-    int B, H, W, Ho, Wo;   // input and output spatial sizes (NHWC)
-    int stride, pt, pl;    // TF 'SAME': pad_top / pad_left (the extra pad, if any, is bottom/right)
-    int KH, KW;
-    // conv_bf16_kernel only: rows in pixel-major order (row q = pixel q / B of clip q % B instead of clip-major), see there
-    int pmajor = 0;
-};
 
 enum { EPI_NONE = 0, EPI_RELU = 1, EPI_BIAS_RELU6 = 2, EPI_BIAS = 3, EPI_BIAS_RELU = 4,
        EPI_BN_RELU6 = 5,     // inference: relu6(v * scale[n] + shift[n]), scale passed as `bias`, shift as `shift`
@@ -540,11 +533,7 @@ __device__ __forceinline__ s16x4 lds_read_tr16(const unsigned char *p)
 // items (clip chunk major, kept position minor) are dealt to its ns slots in turn: slot k takes items k, k + ns, k + 2 ns, ...  Slots per
 // tap are proportional to items per tap, so at its j-th chunk every block of the XCD is at about the same clip chunk, whatever its
 // tap: the taps read a clip's rows at about the same time (with one contiguous range of items per block they read them a kernel apart).
-struct WgradPm {
-    unsigned long long pos[9];    // per tap: the output positions at which it reads inside the map, a nibble each
-    int npos[9];                  // ... and how many they are
-    int slot0[10];                // first slot of each tap within an XCD; slot0[taps] = slots per XCD (grid = 8 x that)
-};
+// (WgradPm itself and wgrad_pm_plan, which builds it: kws_cnn_shape.h)
 
 template <int CIN, int COUT, int TPB, bool DPRE = false, bool XBN = false, bool PM = false>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__restrict__ x, const float *__restrict__ dzp,
@@ -795,58 +784,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const float *__
     }
 }
 
-// The host side of the position-major form: the lists and the slot shares for one launch (tests/wgrad_pmajor_cases.py restates it).
-//   lists   tap (kh, kw) keeps the output positions p = oy Wo + ox at which it reads inside the map (0 <= oy stride + kh - pt < H and
-//           0 <= ox stride + kw - pl < W); its weight w is their number
-//   slots   S slots per XCD: enough for `min_chunks` chunks per block on average, at least one per tap that has positions and at most
-//           max_slots (one resident round); a tap starts from floor(S w / sum w) slots (at least 1), then slots go one by one to the
-//           tap with the most positions per slot (lowest index on ties) -- or, while there are too many, leave the tap with the
-//           fewest (highest index on ties) -- until they add up to S
-// false: a map of more than 16 pixels, more than nine taps, or fewer slots than taps
-inline bool wgrad_pm_plan(const ConvGeom &g, int max_slots, int min_chunks, WgradPm &pm)
-{
-    const int P = g.Ho * g.Wo, ntaps = g.KH * g.KW;
-    if (P < 1 || P > 16 || ntaps < 1 || ntaps > 9) return false;
-    long w[9], wsum = 0;
-    int live = 0;
-    for (int tap = 0; tap < ntaps; ++tap) {
-        const int kh = tap / g.KW, kw = tap % g.KW;
-        pm.pos[tap] = 0ull; pm.npos[tap] = 0;
-        for (int p = 0; p < P; ++p) {
-            const int sy = (p / g.Wo) * g.stride + kh - g.pt, sx = (p % g.Wo) * g.stride + kw - g.pl;
-            if (sy < 0 || sy >= g.H || sx < 0 || sx >= g.W) continue;
-            pm.pos[tap] |= (unsigned long long)p << (4 * pm.npos[tap]);
-            ++pm.npos[tap];
-        }
-        w[tap] = pm.npos[tap]; wsum += w[tap]; live += w[tap] > 0;
-    }
-    if (live < 1 || max_slots < live) return false;
-    const long nclip = ((long)g.B + 31) / 32, want = (wsum * nclip + 8L * min_chunks - 1) / (8L * min_chunks);
-    const int S = (int)(want < live ? live : want > max_slots ? max_slots : want);
-    int s[9], total = 0;
-    for (int tap = 0; tap < ntaps; ++tap) {
-        s[tap] = w[tap] ? (int)((long)S * w[tap] / wsum) : 0;
-        if (w[tap] && s[tap] < 1) s[tap] = 1;
-        total += s[tap];
-    }
-    for (; total < S; ++total) {
-        int best = -1;
-        for (int tap = 0; tap < ntaps; ++tap)
-            if (w[tap] && (best < 0 || w[tap] * s[best] > w[best] * s[tap])) best = tap;
-        ++s[best];
-    }
-    for (; total > S; --total) {
-        int best = -1;
-        for (int tap = 0; tap < ntaps; ++tap)
-            if (s[tap] > 1 && (best < 0 || w[tap] * s[best] <= w[best] * s[tap])) best = tap;
-        --s[best];
-    }
-    pm.slot0[0] = 0;
-    for (int tap = 0; tap < ntaps; ++tap) pm.slot0[tap + 1] = pm.slot0[tap] + s[tap];
-    for (int tap = ntaps + 1; tap < 10; ++tap) pm.slot0[tap] = pm.slot0[ntaps];
-    return true;
-}
-
 // N consecutive floats with the widest aligned load (N = 1, 2, 4, 8); p must be N*4-byte aligned (16 for N = 8)
 template <int N>
 __device__ __forceinline__ void load_vec(const float *__restrict__ p, float (&v)[N])
@@ -1004,8 +941,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(const float *__r
 // by every wave), dz rows are 64-byte segments.  Strided convolutions are launched once per parity class
 // (cy, cx): rows of a class share the set of contributing taps, so no zero tap is ever multiplied.
 // ---------------------------------------------------------------------------------------------------------------
-struct DgradClass { int cy, cx, ny, nx; };   // rows of the class: ih = stride*a + cy (a < ny), iw = stride*b + cx (b < nx)
-struct DgradClasses { DgradClass c[4]; };     // one launch covers every class: blockIdx.y selects it (blocks past a class's rows exit)
+// (DgradClass / DgradClasses and dgrad_plan, which builds them: kws_cnn_shape.h)
 
 template <int CR, int CO, int MW, int STRIDE>
 __global__ __launch_bounds__(256) void conv_dgrad_direct_kernel(const float *__restrict__ dz, const float *__restrict__ wgt,

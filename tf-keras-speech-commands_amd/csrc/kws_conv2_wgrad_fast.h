@@ -22,10 +22,9 @@
 // enter an accumulator differs.  Chosen by plan_cnn (wgrad2_fast); every other geometry, deterministic mode and graph capture keep the
 // block kernel.
 #pragma once
+#include "kws_cnn_shape.h"   // kW2fH x kW2fW, the map the kernel is instantiated for: plan_cnn reads it
 
 namespace kws {
-
-constexpr int kW2fH = 15, kW2fW = 10;                              // the map the kernel is instantiated for (kws_model.hip)
 
 template <int H, int W>
 struct Conv2WgradFast {

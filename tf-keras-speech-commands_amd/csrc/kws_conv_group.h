@@ -10,6 +10,7 @@
 //   conv4: z3 -> a3 = relu6(BN3(z3)) formed and split ONCE per element while it is staged (a3 is never written to memory) -> z4 =
 //          relu(conv4(a3)) (B, 4, 3, 128) (Conv2D(activation='relu'), cnn.py:55); A = three bf16 planes, one ds_read_b128 each
 #pragma once
+#include "kws_cnn_shape.h"   // kGrH1 x kGrW1, conv2's map under the fused pool: plan_cnn reads it
 
 namespace kws {
 
@@ -44,7 +45,6 @@ __device__ __forceinline__ void group_stats(float s, float ss, int ch, int grp, 
 // bn_fwd_coef_prologue) instead of sc2 / sh2; acc != nullptr: this kernel's own sums go to an accumulator set instead of `partial`.
 struct GroupConv3Args { const float *a2; const __bf16 *f3[3]; float *z3; double *partial; int stride, B;
                         const float *z2, *sc2, *sh2; float *a2w, *zmax2; unsigned char *arg2; BnAccFwd in; double *acc; };
-constexpr int kGrH1 = 2 * kFuH2 + 1, kGrW1 = 2 * kFuW2;                         // conv2's map: 15 x 10 (the last row falls out of the 'valid' pooling)
 
 __global__ __launch_bounds__(kGrThreads, 1) void conv3_group_fwd_kernel(GroupConv3Args g)
 {

@@ -9,10 +9,11 @@
 // forward planes, ofrag = 1 for the data gradient's), three-way bf16 split products with fp32 accumulation like the kernels it replaces.
 // The Dense weight gradient stays a kernel of its own on the side stream (it reduces over the whole batch): dd1 is still written.
 #pragma once
+#include "kws_cnn_shape.h"   // kDhK (Dense units) and kDhWaves: plan_cnn reads them
 
 namespace kws {
 
-constexpr int kDhK = 128, kDhCP = 48, kDhCS = 50;          // Dense units; padded classes; LDS row stride of the class tiles
+constexpr int kDhCP = 48, kDhCS = 50;                      // padded classes; LDS row stride of the class tiles
 constexpr int kDhKS = kDhK + 8;                            // row stride of the 16 x 128 fp32 tiles: 544 B = 16 B x (2 mod 4)
 
 struct DenseHeadArgs {
@@ -40,10 +41,7 @@ struct DenseHeadArgs {
     int H3 = 0, W3 = 0;
 };
 
-// kDhWaves waves per block of 16 samples: every phase below is a chain of dependent LDS / L2 round trips with little work per wave, and
-// the kernel shares its CU with the next batch's featurizer (twelve vector-ALU-bound waves) -- eight waves halve the serial work of a
-// wave in the Dense product, the data gradient and the dW2 tiles against four (four waves: 0.037 ms alone, 0.115 under the featurizer).
-constexpr int kDhWaves = 8, kDhThreads = 64 * kDhWaves;
+constexpr int kDhThreads = 64 * kDhWaves;                  // kDhWaves waves per block of 16 samples (kws_cnn_shape.h says why eight)
 __global__ __launch_bounds__(kDhThreads) void dense_head_fused_kernel(DenseHeadArgs g)
 {
     constexpr int NW = kDhWaves, NT = kDhThreads;

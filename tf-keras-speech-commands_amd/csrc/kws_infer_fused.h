@@ -20,16 +20,13 @@
 //     block; with eight waves and every fragment read once the dependent read -> product chains of two waves per SIMD were the limit
 //     (0.045 against 0.041 ms).
 #pragma once
+#include "kws_cnn_shape.h"   // kFuClips, the maps kFuH2 x kFuW2 .. kFuH4 x kFuW4 and kFuHeadCols: plan_cnn reads them
 
 namespace kws {
 
-constexpr int kFuClips = 16;                      // clips per block = MFMA rows
-constexpr int kFuH2 = 7, kFuW2 = 5, kFuC2 = 32;   // a2: input of conv3
-constexpr int kFuH3 = 4, kFuW3 = 3, kFuC3 = 64;   // conv3 output (stride 2, 'same': pad 1 before on both axes)
-constexpr int kFuC4 = 128, kFuH4 = 2, kFuW4 = 1;  // conv4 output 4 x 3 x 128, pooled 2 x 1 x 128
+constexpr int kFuC2 = 32, kFuC3 = 64, kFuC4 = 128;              // channels of a2 (conv3's input), of conv3's and of conv4's output
 constexpr int kFuFlat = kFuH4 * kFuW4 * kFuC4;    // 256
 constexpr int kFuD = 128;                         // Dense units
-constexpr int kFuHeadCols = 48;                   // classes padded to three column tiles
 constexpr int kFuRS4 = kFuFlat + 8, kFuRSD = kFuD + 8;         // row strides in floats of the small fp32 tiles: 16 B x (2 mod 4)
 constexpr int kFuA2 = kFuH2 * kFuW2 * kFuClips * kFuC2;         // floats: a2 [pixel][clip][32], swizzled units, 71 680 B
 constexpr int kFuA3P = kFuH3 * kFuW3 * kFuClips * kFuC3;        // bf16 per plane of a3 [position][clip][64], swizzled units

@@ -13,6 +13,7 @@
 // (l1m_act_pool_kernel for inference, L1Mma / l1f_forward_clips shared with the training kernel) and, for training, the second-moment
 // form of kws_layer1_moments.h (statistics and gradients in closed form, ONE backward pass: kws_layer1_fast.h for the default map).
 #pragma once
+#include "kws_cnn_shape.h"   // kL1MaxTiles, kL1Stage: plan_cnn reads them
 #include "kws_layers.h"
 
 namespace kws {
@@ -247,9 +248,8 @@ __global__ __launch_bounds__(256) void l1_bwd_wgrad_kernel(const float *__restri
 // and clip, each a full HBM round trip): a wave now owns whole clips, keeps its zero-haloed map in a private LDS tile (no
 // block barriers), issues ALL of the clip's da1 loads up front and fetches the next clip's map while it computes.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int kL1MaxTiles = 40;      // tiles (4 pool windows each) per clip
+// kL1MaxTiles (tiles per clip) and kL1Stage (staged elements per lane): kws_cnn_shape.h
 constexpr int kL1Group = 10;         // da1 values fetched together, one group ahead of the tiles that use them
-constexpr int kL1Stage = 12;         // staged elements per lane: (H+2)(W+2) <= 64 * 12
 
 struct L1Mma {
     float wb[3];      // B fragments of the conv1 kernel: W[tap = 4j + lq][c = li], zero for tap >= 9

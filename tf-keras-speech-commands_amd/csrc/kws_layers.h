@@ -4,6 +4,7 @@
 // Reference semantics: classifier/models/cnn.py:27-66, classifier/loss.py:21-77, common/model_utils.py:47 and the
 // Keras layer defaults listed in SURVEY.md section 7.
 #pragma once
+#include "kws_cnn_shape.h"   // kStatStride
 #include "kws_device.h"
 
 namespace kws {
@@ -11,7 +12,7 @@ namespace kws {
 constexpr float kBnEps = 1e-3f;        // BatchNormalization(epsilon=1e-3)
 constexpr double kBnMomentum = 0.99;   // BatchNormalization(momentum=0.99)
 constexpr float kCeEps = 1e-7f;        // keras.backend.epsilon()
-constexpr int kStatStride = 1024;      // max blocks of a channel reduction; partial[(which*C + c)*kStatStride + blk]
+// kStatStride (max blocks of a channel reduction; partial[(which*C + c)*kStatStride + blk]): kws_cnn_shape.h
 
 // sum of partial[(which*C + c)*kStatStride + 0..nblk) by one 256-thread block, result in every thread
 __device__ __forceinline__ double block_sum_partials(const double *__restrict__ partial, int which, int C, int c, int nblk,

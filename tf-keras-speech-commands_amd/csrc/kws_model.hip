@@ -29,13 +29,6 @@ using namespace kws;
 
 namespace {
 
-inline int same_out(int n, int s) { return (n + s - 1) / s; }
-inline int same_pad_before(int n, int k, int s)
-{
-    const int out = same_out(n, s), total = std::max((out - 1) * s + k - n, 0);
-    return total / 2;   // TF 'SAME': the extra element goes to the end
-}
-
 // where in the step the caller's overlap event is recorded (and its callback runs): see kws_train_args.overlap_event
 struct OverlapHook {
     hipEvent_t ev = nullptr;
@@ -65,19 +58,8 @@ struct OverlapHook {
         if (int rc__ = (__VA_ARGS__)) return rc__; \
     } while (0)
 
-constexpr int kCh[5] = {1, 16, 32, 64, 128};
-constexpr int kMaxStatBlocks = kStatStride;
-
-// Stage l = 0 .. 3 of either CNN: a 3x3 'same' convolution (a SeparableConv2D in simple_cnn_lite) from a (Hi x Wi x Cin) map to
-// (Ho x Wo x Cout), then BatchNorm -> ReLU6 and, where pooled, a 2x2 max-pool.  relu: simple_cnn_lite's pointwise output carries
-// activation='relu' (cnn.py:113,122)
-struct CnnStage { int Hi, Wi, Ho, Wo, stride, Cin, Cout; bool pooled, relu; };
-inline CnnStage cnn_stage(const CnnDims &d, int l)
-{
-    const int Hi[4] = {d.H0, d.H1, d.H2, d.H3}, Wi[4] = {d.W0, d.W1, d.W2, d.W3};
-    const int stride = l == 2 ? 2 : 1;
-    return CnnStage{Hi[l], Wi[l], same_out(Hi[l], stride), same_out(Wi[l], stride), stride, kCh[l], kCh[l + 1], l != 2, l >= 2};
-}
+// what plan_cnn reads of the model (kws_cnn_plan.h)
+inline CnnDesc cnn_desc(const kws_model *m) { return CnnDesc{m->kind, m->C, m->head_K, m->deterministic, m->d}; }
 
 // ---- workspace layout (simple_cnn) ---------------------------------------------------------------------------
 struct CnnWs {
@@ -171,16 +153,6 @@ static int infer_coefs(const kws_model *m, const float *params, const float *sta
     return KWS_OK;
 }
 
-// rows-per-block and grid for the (M x C) channel reductions
-inline void stat_grid(long M, int C, int &nblk, int &rows)
-{
-    const int R = 256 / C;
-    long want = (M + (long)R * 8 - 1) / ((long)R * 8);
-    nblk = (int)std::min<long>(kMaxStatBlocks, std::max<long>(1, want));
-    rows = (int)((M + nblk - 1) / nblk);
-    nblk = (int)((M + rows - 1) / rows);
-}
-
 template <int CR, int CO, int MODE, int EPI>
 int launch_gemm(const float *src, const float *w, const float *bias, float *dst, const ConvGeom &g, hipStream_t s)
 {
@@ -201,8 +173,7 @@ static int resident_blocks(K kernel, int threads, size_t smem)
     return nb;
 }
 
-// dW += wgrad(x, dz).  The grid is sized so that all blocks are resident at once (ONE round): with more blocks than slots the
-// last round runs on a fraction of the chip (measured on conv4: 990 blocks on 768 slots left the CUs idle 43 % of the time).
+// dW += wgrad(x, dz) on a grid of one resident round (kws_cnn_shape.h: wgrad_round).
 // `job`: the step's loss / accuracy sums ride in one more column of blocks (kws_conv.h), under the same label.
 template <int CIN, int COUT, int GPB>
 int launch_wgrad(const float *x, const float *dz, float *dw, const ConvGeom &g, hipStream_t s, bool deterministic = false,
@@ -216,21 +187,16 @@ int launch_wgrad(const float *x, const float *dz, float *dw, const ConvGeom &g, 
     const int ngroups = g.KH * g.KW * (CIN / CB), gy = (ngroups + GPB - 1) / GPB;
     const long steps = (M + 3) / 4;                                   // 4-pixel MFMA k-steps
     static const int occ = resident_blocks(conv_wgrad_direct_kernel<CIN, COUT, GPB>, 256, smem);
-    // deterministic: ONE block along the pixel axis, so every output element receives a single add onto the cleared buffer
-    const long slots = deterministic ? 1 : std::max<long>(1, (long)cu_count() * occ / gy); // blocks along x that fit at once
-    // >= 8 steps per wave so the end-of-block tile reduction amortises
-    const long gx_want = std::max<long>(1, std::min<long>(slots, (steps + 4 * 8 - 1) / (4 * 8)));
-    const int spw = (int)((steps + 4 * gx_want - 1) / (4 * gx_want));
-    const long gx = (steps + 4L * spw - 1) / (4L * spw);
+    const WgradRound r = wgrad_round(steps, gy, (long)cu_count() * occ, deterministic);
     static const std::string name = "conv_wgrad<" + std::to_string(CIN) + "," + std::to_string(COUT) + ">";
-    KWS_LAUNCH(name.c_str(), (conv_wgrad_direct_kernel<CIN, COUT, GPB>), dim3((unsigned)gx + (job ? 1u : 0u), (unsigned)gy), dim3(256), smem,
-               s, x, dz, dw, zp, g, spw, job ? *job : LossSumJob{});
+    KWS_LAUNCH(name.c_str(), (conv_wgrad_direct_kernel<CIN, COUT, GPB>), dim3((unsigned)r.gx + (job ? 1u : 0u), (unsigned)gy), dim3(256), smem,
+               s, x, dz, dw, zp, g, r.spw, job ? *job : LossSumJob{});
     return KWS_OK;
 }
 
 // dW += wgrad(x, dz) in the split-precision form (conv_wgrad_bf16_kernel): grid = (tap groups) * (pixel ranges), one resident
-// round, the taps of a range on one XCD.  TPB = taps per block: 3 (one kernel row, dz split once for three products) pays
-// for conv3 (0.047 -> 0.042 ms); for conv4 its 238 registers and 74 KB of LDS cost more than they save (0.111 -> 0.122 ms).
+// round, the taps of a range on one XCD (kws_cnn_shape.h: wgrad_bf16_round).  TPB = taps per block: 3 (one kernel row, dz split once for
+// three products) pays for conv3 (0.047 -> 0.042 ms); for conv4 its 238 registers and 74 KB of LDS cost more than they save (0.111 -> 0.122 ms).
 // pmajor (CnnPlan::wgrad_pmajor, TPB = 1): the position-major form, which never stages a tap's padding positions.
 template <int CIN, int COUT, int TPB, bool DPRE = false, bool XBN = false>
 int launch_wgrad_bf16(const float *x, const float *dz, float *dw, const ConvGeom &g, hipStream_t s, __bf16 *const *dz_planes = nullptr,
@@ -245,17 +211,13 @@ int launch_wgrad_bf16(const float *x, const float *dz, float *dw, const ConvGeom
     static const int occ = resident_blocks(conv_wgrad_bf16_kernel<CIN, COUT, TPB, DPRE, XBN>, 256, smem);
     const long M = (long)g.B * g.Ho * g.Wo, nchunk = (M + 31) / 32;
     const int ngroups = g.KH * g.KW / TPB;
-    // ranges: a multiple of 8 (one per XCD), at most one resident round, at least 4 chunks per block
-    long nranges = std::max<long>(8, ((long)cu_count() * occ / ngroups) / 8 * 8);
-    nranges = std::min<long>(nranges, std::max<long>(8, (nchunk / 4 + 7) / 8 * 8));
-    int cpb = (int)((nchunk + nranges - 1) / nranges);
-    if (deterministic) { nranges = 8; cpb = (int)nchunk; }   // range 0 takes every chunk: a single add per output element
+    const WgradBf16Round r = wgrad_bf16_round(nchunk, ngroups, (long)cu_count() * occ, deterministic);
     static const std::string name = "conv_wgrad_bf16<" + std::to_string(CIN) + "," + std::to_string(COUT) + ">";
     const Bf16Planes dpl{{DPRE ? dz_planes[0] : nullptr, DPRE ? dz_planes[1] : nullptr, DPRE ? dz_planes[2] : nullptr}};
     if (pmajor && TPB != 1) return fail(KWS_ERR_UNSUPPORTED, "the position-major weight gradient takes one tap per block");
     if constexpr (TPB == 1) {
         if (pmajor) {
-            // the position-major form (kws_conv.h: WgradPm): one resident round of 8 XCDs x slots, under the same label
+            // the position-major form (kws_cnn_shape.h: WgradPm): one resident round of 8 XCDs x slots, under the same label
             if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(conv_wgrad_bf16_kernel<CIN, COUT, 1, DPRE, XBN, true>), (int)smem)) return rc;
             static const int occ_pm = resident_blocks(conv_wgrad_bf16_kernel<CIN, COUT, 1, DPRE, XBN, true>, 256, smem);
             WgradPm pm{};
@@ -267,14 +229,13 @@ int launch_wgrad_bf16(const float *x, const float *dz, float *dw, const ConvGeom
             return KWS_OK;
         }
     }
-    KWS_LAUNCH(name.c_str(), (conv_wgrad_bf16_kernel<CIN, COUT, TPB, DPRE, XBN>), dim3((unsigned)(nranges * ngroups)), dim3(256), smem, s, x, dz, dw,
-               zp, g, cpb, (int)nranges, dpl, xbn);
+    KWS_LAUNCH(name.c_str(), (conv_wgrad_bf16_kernel<CIN, COUT, TPB, DPRE, XBN>), dim3((unsigned)(r.nranges * ngroups)), dim3(256), smem, s, x, dz, dw,
+               zp, g, r.cpb, (int)r.nranges, dpl, xbn);
     return KWS_OK;
 }
 
-// dx <- dgrad(dz): ONE launch over every stride-parity class of the input pixels (blockIdx.y = class).  MW (16-row tiles
-// per wave) is picked so that the waves divide evenly over the SIMDs: every SIMD's matrix pipe then runs
-// ceil(waves / SIMDs) * MW tile-times, and the smallest such product wins (ties: the larger MW reuses weights more).
+// dx <- dgrad(dz): ONE launch over every stride-parity class of the input pixels (blockIdx.y = class), MW 16-row tiles per wave
+// (kws_cnn_shape.h: dgrad_plan).
 template <int CR, int CO, int MW, int STRIDE>
 int launch_dgrad_mw(const float *dz, const float *w, float *dx, const ConvGeom &g, const DgradClasses &cls, int ncls, long max_rows,
                      hipStream_t s)
@@ -290,35 +251,18 @@ int launch_dgrad_mw(const float *dz, const float *w, float *dx, const ConvGeom &
 template <int CR, int CO, int STRIDE>
 int launch_dgrad(const float *dz, const float *w, float *dx, const ConvGeom &g, hipStream_t s)
 {
-    if (g.KH > 8 * g.stride || g.KW > 8 * g.stride)
+    DgradPlan p;
+    switch (dgrad_plan(g, 4L * cu_count(), p)) {
+    case DGRAD_KERNEL_TOO_LARGE:
         return fail(KWS_ERR_UNSUPPORTED, "kernel %dx%d too large for the dgrad tap masks (at most %d taps per axis)", g.KH, g.KW, 8 * g.stride);
-    DgradClasses cls;
-    int ncls = 0;
-    long rows[4] = {0, 0, 0, 0}, max_rows = 0;
-    for (int cy = 0; cy < g.stride && cy < 2; ++cy)
-        for (int cx = 0; cx < g.stride && cx < 2; ++cx) {
-            DgradClass c{cy, cx, (g.H - cy + g.stride - 1) / g.stride, (g.W - cx + g.stride - 1) / g.stride};
-            if (c.ny <= 0 || c.nx <= 0) continue;
-            rows[ncls] = (long)g.B * c.ny * c.nx;
-            max_rows = std::max(max_rows, rows[ncls]);
-            cls.c[ncls++] = c;
-        }
-    for (int i = ncls; i < 4; ++i) cls.c[i] = DgradClass{0, 0, 0, 0};
-    if (g.stride > 2) return fail(KWS_ERR_UNSUPPORTED, "dgrad is built for strides 1 and 2");
-    const long simds = 4L * cu_count();
-    int best = 4;
-    long best_cost = -1;
-    for (int mw = 4; mw >= 1; --mw) {
-        long waves = 0;
-        for (int i = 0; i < ncls; ++i) waves += ((rows[i] + 15) / 16 + mw - 1) / mw;
-        const long cost = ((waves + simds - 1) / simds) * mw;
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = mw; }
+    case DGRAD_STRIDE: return fail(KWS_ERR_UNSUPPORTED, "dgrad is built for strides 1 and 2");
+    default: break;
     }
-    switch (best) {
-    case 1: return launch_dgrad_mw<CR, CO, 1, STRIDE>(dz, w, dx, g, cls, ncls, max_rows, s);
-    case 2: return launch_dgrad_mw<CR, CO, 2, STRIDE>(dz, w, dx, g, cls, ncls, max_rows, s);
-    case 3: return launch_dgrad_mw<CR, CO, 3, STRIDE>(dz, w, dx, g, cls, ncls, max_rows, s);
-    default: return launch_dgrad_mw<CR, CO, 4, STRIDE>(dz, w, dx, g, cls, ncls, max_rows, s);
+    switch (p.mw) {
+    case 1: return launch_dgrad_mw<CR, CO, 1, STRIDE>(dz, w, dx, g, p.cls, p.ncls, p.max_rows, s);
+    case 2: return launch_dgrad_mw<CR, CO, 2, STRIDE>(dz, w, dx, g, p.cls, p.ncls, p.max_rows, s);
+    case 3: return launch_dgrad_mw<CR, CO, 3, STRIDE>(dz, w, dx, g, p.cls, p.ncls, p.max_rows, s);
+    default: return launch_dgrad_mw<CR, CO, 4, STRIDE>(dz, w, dx, g, p.cls, p.ncls, p.max_rows, s);
     }
 }
 
@@ -339,17 +283,11 @@ int launch_bf16(const char *what, const float *src, __bf16 *const planes[6], con
     ConvGeom g = g_in;
     const long M = MODE == MODE_FWD ? (long)g.B * g.Ho * g.Wo : (long)g.B * g.H * g.W;
     if (M >= (1L << 31)) return fail(KWS_ERR_UNSUPPORTED, "%s: %ld rows exceed the kernel's 32-bit row index", what, M);
-    {
-        // small maps with 'same' padding: pixel-major rows let a block skip the taps that are padding for its position (kws_conv.h)
-        const int P = MODE == MODE_FWD ? g.Ho * g.Wo : g.H * g.W;
-        g.pmajor = (g.KH == 3 && g.KW == 3 && P > 1 && P <= 16) ? 1 : 0;
-    }
+    g.pmajor = conv_bf16_pmajor(g, MODE == MODE_FWD);
     static const std::string name = std::string(what) + "<" + std::to_string(CR) + "," + std::to_string(CO) + ">";
     const int o = MODE == MODE_FWD ? 3 : 0;      // forward reads the transposed planes, the data gradient the original order
     const Bf16Planes wp{{planes[o], planes[o + 1], planes[o + 2]}};
-    // rows per block = 32 * RT: 96 for conv4's forward (8 column tiles: the larger tile halves the LDS reads per MFMA), 64
-    // elsewhere (3 resident blocks per CU overlap their staging and MFMA phases better; measured per kernel at B = 4096)
-    constexpr int RT = (MODE == MODE_FWD && CO == 128 && CR == 64) ? 3 : 2;
+    constexpr int RT = conv_bf16_rt(MODE == MODE_FWD, CR, CO);       // rows per block = 32 * RT
     const unsigned nblk = blocks_for(M, 32 * RT);
     if (abn) {
         // src is the pre-activation tensor of the BatchNormalization -> ReLU6 in front of this layer (conv4's training forward)
@@ -483,28 +421,6 @@ static int launch_fused_tail(const kws_model *m, int B, const float *params, Cnn
     return KWS_OK;
 }
 
-ConvGeom geom3x3(int B, int H, int W, int stride)
-{
-    ConvGeom g;
-    g.B = B; g.H = H; g.W = W; g.stride = stride; g.KH = 3; g.KW = 3;
-    g.Ho = same_out(H, stride); g.Wo = same_out(W, stride);
-    g.pt = same_pad_before(H, 3, stride); g.pl = same_pad_before(W, 3, stride);
-    return g;
-}
-ConvGeom geom1x1(int B, int H, int W)
-{
-    ConvGeom g;
-    g.B = B; g.H = H; g.W = W; g.Ho = H; g.Wo = W; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = 1; g.KW = 1;
-    return g;
-}
-// Dense(128, use_bias=True) + ReLU6 as a (H4 x W4) 'valid' convolution over the pooled map (Flatten is h,w,c)
-static ConvGeom dense_geom(const CnnDims &d, int B)
-{
-    ConvGeom g;
-    g.B = B; g.H = d.H4; g.W = d.W4; g.Ho = 1; g.Wo = 1; g.stride = 1; g.pt = 0; g.pl = 0; g.KH = d.H4; g.KW = d.W4;
-    return g;
-}
-
 // Training forward pass in split precision: 48 extra blocks in the grid of the layer-1 activation kernel
 // (l1m_act_pool_moments_kernel<true>) split the conv3 / conv4 / dense weights into their bf16 planes and 16 clear the gradient
 // buffer.  Both jobs used to run on the side stream behind an event and were joined before conv3: two events on the main chain
@@ -573,17 +489,13 @@ struct CnnCtx : CnnStep {
 };
 
 // launch geometry of the layer-1 kernels, forward and backward (conv1 is recomputed from the feature map wherever z1 is needed, kws_layer1.h)
-struct L1Geom {
-    int cpb, nb;        // clips per block and blocks of the block-per-clip forms
-    int cpw, nbm;       // clips per wave and blocks of the MFMA, wave-per-clip forms
+struct L1Geom : L1Grid {        // clips per block / wave and the grids (kws_cnn_shape.h), then the LDS bytes of the two families of kernels
     size_t smem1, smemm;
 };
 static L1Geom l1_geom(const CnnDims &d, int B, const CnnPlan &P)
 {
-    L1Geom g;
-    g.cpb = std::max(1, (B + kMaxStatBlocks - 1) / kMaxStatBlocks); g.nb = (B + g.cpb - 1) / g.cpb;
+    L1Geom g{l1_grid(B), 0, 0};
     g.smem1 = sizeof(float) * (size_t)(d.H0 + 2) * (d.W0 + 2);
-    g.cpw = std::max(1, (B + 4 * kMaxStatBlocks - 1) / (4 * kMaxStatBlocks)); g.nbm = (B + 4 * g.cpw - 1) / (4 * g.cpw);
     // per-wave LDS tiles; the compile-time form of the default map reads two rows past the haloed map (kws_layer1.h: L1Runs)
     g.smemm = sizeof(float) * 4 * (P.l1_default_map ? (size_t)L1Runs<30, 20>::TILE : (size_t)((((d.H0 + 2) * (d.W0 + 2)) + 3) & ~3));
     return g;
@@ -595,8 +507,7 @@ struct Conv2Clip {
     size_t sm, smb;         // forward, fp32 / split precision
     size_t smw, smwb;       // weight gradient, fp32 / split precision
     size_t smd, smdb;       // data gradient, fp32 / split precision
-    // persistent grids: at most max_blocks (the LDS-limited residency), with an equal share of clips each
-    unsigned even_grid(int max_blocks) const { const int cpb = (B + max_blocks - 1) / max_blocks; return (unsigned)((B + cpb - 1) / cpb); }
+    unsigned even_grid(int max_blocks) const { return kws::even_grid(B, max_blocks); }      // persistent grids
 };
 static Conv2Clip conv2_clip(const CnnDims &d, int B)
 {
@@ -1252,9 +1163,8 @@ static int launch_lite_front(const kws_model *m, const float *feat, int B, const
     const LiteFrontArgs fa = {params + m->o_dwk[0], params + m->o_pwk[0], params + m->o_pwb[0], k0.scale, k0.shift,
                               params + m->o_dwk[1], params + m->o_pwk[1], params + m->o_pwb[1], k1.scale, k1.shift};
     const size_t sm = sizeof(float) * (size_t)lite_front_floats(d.H0, d.W0);
-    const int waves = cu_count() * std::max(1, std::min(8, (int)(160 * 1024 / sm)));
-    const int cpw = std::max(1, (B + waves - 1) / waves), nblk = (B + cpw - 1) / cpw;
-    KWS_LAUNCH("lite_front_infer_kernel", lite_front_infer_kernel, dim3(nblk), dim3(64), sm, s, feat, fa, w.a[1], B, d.H0, d.W0, cpw, a2h);
+    const LiteFrontGrid g = lite_front_grid(B, cu_count(), sm);
+    KWS_LAUNCH("lite_front_infer_kernel", lite_front_infer_kernel, dim3(g.nblk), dim3(64), sm, s, feat, fa, w.a[1], B, d.H0, d.W0, g.cpw, a2h);
     return KWS_OK;
 }
 // the fp16 weight blob (kws_lite_f16.h) lives at the head of the double partial slab, which the inference forward does not use otherwise
@@ -1409,7 +1319,7 @@ int cnn_infer(const CnnStep &st, float *probs, int32_t *argmax)
 {
     const kws_model *m = st.m;
     // no path of the inference forward depends on the stream's capture state
-    const CnnPlan plan = plan_cnn(m, st.B, matrix_prec(m), false, false, true, m->prepared_for(st.params, st.state, st.w.base, st.B, matrix_prec(m), infer_prec(m)));
+    const CnnPlan plan = plan_cnn(cnn_desc(m), st.B, matrix_prec(m), false, false, true, m->prepared_for(st.params, st.state, st.w.base, st.B, matrix_prec(m), infer_prec(m)));
     CnnCtx c{st, nullptr, nullptr, plan, nullptr, nullptr, nullptr, probs, argmax};
     KWS_TRY(c.forward());
     return plan.fused_tail ? KWS_OK : c.head_infer(probs, argmax);     // fused_tail: conv3 .. softmax ran as one kernel
@@ -1449,7 +1359,7 @@ int cnn_train_step(kws_model *m, const CnnStep &st, const kws_train_args *a)
     // ONE plan for both passes (kws_cnn_plan.h); the stream's capture state is queried here, once
     ModelRes *R = m->dev_res();
     if (!R) return fail(KWS_ERR_HIP, "cannot create the model's side stream / events on this device");
-    const CnnPlan plan = plan_cnn(m, st.B, matrix_prec(m), true, stream_is_capturing(st.s), false, false);
+    const CnnPlan plan = plan_cnn(cnn_desc(m), st.B, matrix_prec(m), true, stream_is_capturing(st.s), false, false);
     CnnCtx c{st, R, R->side, plan, &hook, a->feat_moments, a};
     KWS_TRY(c.forward());
     // fuse_head_fwd (non-deterministic mode): the head's forward pass rides in its backward kernel (kws_layers.h: head_bwd_mfma_kernel<.., FWD>):
@@ -1494,7 +1404,7 @@ int run_loss_reduce(const float *loss_i, const float *correct_i, int B, float *s
     return KWS_OK;
 }
 
-bool head_bwd_fuses(const kws_model *m) { return m->head_K % 16 == 0 && m->head_K <= 128 && m->C <= 48; }
+bool head_bwd_fuses(const kws_model *m) { return head_bwd_fuses(m->head_K, m->C); }
 
 int run_head_bwd(const kws_model *m, int B, const float *params, const float *x, const float *dlogits, float *dx,
                  float *grads, bool relu6_gate, hipStream_t s, float *dx_colsum, const float *loss_i, const float *correct_i,
@@ -1606,12 +1516,12 @@ int kws_feature_moments(const float *feat, int B, int n_features, int feature_si
         return fail(KWS_ERR_UNSUPPORTED, "feature moments cover even maps up to (H+2)(W+2) <= %d (got %d x %d)", 64 * kL1Stage, H, W);
     if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(KWS_ERR_INVALID, "workspace must be 256-byte aligned");
     if (ws_bytes < (size_t)kws_feature_moments_workspace_bytes(B)) return fail(KWS_ERR_WORKSPACE, "workspace too small for the moment partial sums");
-    const int cpw = std::max(1, (B + 4 * kMaxStatBlocks - 1) / (4 * kMaxStatBlocks)), nbm = (B + 4 * cpw - 1) / (4 * cpw);
+    const L1Grid g = l1_grid(B);
     const size_t smemm = sizeof(float) * 4 * (size_t)((((H + 2) * (W + 2)) + 3) & ~3);
     hipStream_t s = static_cast<hipStream_t>(stream);
     double *partial = static_cast<double *>(ws);
-    KWS_LAUNCH("l1_moments_kernel", l1_moments_kernel, dim3(nbm), dim3(256), smemm, s, feat, B, H, W, cpw, partial);
-    KWS_LAUNCH("l1_moments_finalize_kernel", l1_moments_finalize_kernel, dim3(kMomCount), dim3(64), 0, s, partial, nbm, moments);
+    KWS_LAUNCH("l1_moments_kernel", l1_moments_kernel, dim3(g.nbm), dim3(256), smemm, s, feat, B, H, W, g.cpw, partial);
+    KWS_LAUNCH("l1_moments_finalize_kernel", l1_moments_finalize_kernel, dim3(kMomCount), dim3(64), 0, s, partial, g.nbm, moments);
     KWS_LAUNCH_CHECK("feature moments");
     return KWS_OK;
 }
@@ -1635,7 +1545,7 @@ int kws_model_prepare_inference(kws_model *m, int B, const float *params, const 
     KWS_TRY(infer_coefs(m, params, state, w, s));
     if (m->kind == KWS_SIMPLE_CNN && matrix_prec(m) == 1) {
         // the planes the prepared forward will read: the plan of an inference call that takes the head's outputs (kws_model_forward)
-        const CnnPlan plan = plan_cnn(m, B, matrix_prec(m), false, false, true, false);
+        const CnnPlan plan = plan_cnn(cnn_desc(m), B, matrix_prec(m), false, false, true, false);
         KWS_TRY(plan.fused_tail ? split_weights_fused(m, params, w, s) : split_weights(m, params, w, s));
     }
     if (m->kind == KWS_SIMPLE_CNN_LITE && infer_prec(m) == KWS_INFER_FP16) KWS_TRY(prepare_lite_f16(m, params, w, s));
@@ -1732,13 +1642,7 @@ int kws_model_create_stacked(int kind, int num_classes, int n_features, int feat
         *out = m;
         return KWS_OK;
     }
-    CnnDims &d = m->d;
-    d.H0 = n_features; d.W0 = feature_size;
-    d.H1 = d.H0 / 2; d.W1 = d.W0 / 2;                 // MaxPooling2D(): 2x2, stride 2, 'valid'
-    d.H2 = d.H1 / 2; d.W2 = d.W1 / 2;
-    d.H3 = same_out(d.H2, 2); d.W3 = same_out(d.W2, 2);
-    d.H4 = d.H3 / 2; d.W4 = d.W3 / 2;
-    d.flat = d.H4 * d.W4 * 128;
+    const CnnDims &d = m->d = cnn_dims(n_features, feature_size);
     if (d.H4 < 1 || d.W4 < 1) {
         delete m;
         return fail(KWS_ERR_INVALID, "input %dx%d is too small for simple_cnn", n_features, feature_size);

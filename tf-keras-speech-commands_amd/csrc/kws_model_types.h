@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "kws_cnn_shape.h"   // CnnDims, al4, al256, blocks_for
 #include "kws_common.h"
 #include "kws_device.h"
 
@@ -31,13 +32,7 @@ struct ModelRes {
     bool acc_dirty = false;             // an enqueue failed half-way: clear everything before the next pass
 };
 
-struct CnnDims { int H0, W0, H1, W1, H2, W2, H3, W3, H4, W4, flat; };
-
 constexpr int kRnnMaxLayers = 4;          // kws_model_create_stacked: num_layers 1 .. 4
-
-inline int64_t al4(int64_t x) { return (x + 3) & ~(int64_t)3; }
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline unsigned blocks_for(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // bump allocator over the caller's workspace (base may be NULL to only measure)
 struct WsCarver {
@@ -105,7 +100,8 @@ int run_head(const kws_model *m, int B, const float *params, const float *x, flo
              const int32_t *labels, const float *class_w, float *probs, int32_t *argmax, float *dlogits, float grad_scale,
              float *stats, int ignore_index, hipStream_t s);
 // dx_colsum / stats: optional extras the MFMA form of the kernel produces on the way (bias gradient of the layer in front of
-// the head; {sum loss, sum correct} from loss_i / correct_i).  head_bwd_fuses(m) tells whether that form applies.
+// the head; {sum loss, sum correct} from loss_i / correct_i).  head_bwd_fuses(m) tells whether that form applies (the rule on
+// (head_K, C): kws_cnn_shape.h).
 bool head_bwd_fuses(const kws_model *m);
 int run_head_bwd(const kws_model *m, int B, const float *params, const float *x, const float *dlogits, float *dx,
                  float *grads, bool relu6_gate, hipStream_t s, float *dx_colsum = nullptr, const float *loss_i = nullptr,
