@@ -1122,11 +1122,18 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
         *reinterpret_cast<float4 *>(m + i) = mv;
         *reinterpret_cast<float4 *>(v + i) = vv;
     } else {
+        // The last n % 4 floats.  Left to the compiler, this loop's multiply-adds were contracted another way than the float4 branch's
+        // (m differed in its last bit from the second step on): the same element got other bits at n = 5 than at n = 8, and
+        // kws_optimizer_step's default options, which reproduce the float4 branch, did not reproduce the tail.  So the branch's
+        // fused multiply-adds are spelled out here, as in csrc/kws_optim.hip: update_one.
+#pragma clang fp contract(off)
         for (long j = i; j < n; ++j) {
             const float ge = g[j] * grad_scale;
-            m[j] = b1 * m[j] + (1.f - b1) * ge;
-            v[j] = b2 * v[j] + (1.f - b2) * ge * ge;
-            p[j] -= lr_t * m[j] / (sqrtf(v[j]) + eps);
+            const float me = fmaf(b1, m[j], (1.f - b1) * ge);
+            const float ve = fmaf((1.f - b2) * ge, ge, b2 * v[j]);
+            m[j] = me;
+            v[j] = ve;
+            p[j] = p[j] - lr_t * me / (sqrtf(ve) + eps);
         }
     }
 }
