@@ -225,7 +225,8 @@ typedef struct kws_rir_bank kws_rir_bank;
 
 /* K RIRs concatenated on the HOST: taps[sum(rir_len)] float32, rir_len[K] >= 1 each, finite.  Taps at index >= max_samples can never
  * reach an output sample and are clipped away (Lh = min(rir_len, max_samples)).  Every clipped RIR is transformed once (fp64 on the
- * host) into the spectrum the kernel multiplies by.  max_samples in [1, 16384] (KWS_ERR_UNSUPPORTED above: one 32768-point transform). */
+ * host) into the spectrum the kernel multiplies by; the clipped taps are kept on the device as well, for the clips of at most 64
+ * samples, which are convolved directly in fp64.  max_samples in [1, 16384] (KWS_ERR_UNSUPPORTED above: one 32768-point transform). */
 int kws_rir_bank_create(const float *taps, const int32_t *rir_len, int K, int max_samples, kws_rir_bank **out);
 void kws_rir_bank_destroy(kws_rir_bank *bank);
 /* host: number of RIRs, the bank's max_samples and the real transform size (32768) */

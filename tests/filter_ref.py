@@ -1,4 +1,5 @@
-"""float64 numpy restatements for the filter augmentation tests (tests/test_filter_host.py, tests/test_filter_gpu.py): the draws of
+"""float64 numpy restatements for the filter augmentation tests (tests/test_filter_host.py, tests/test_filter_gpu.py and the edge suite of
+tests/wave_edge_cases.py): the draws of
 kws_filter_apply and scipy.signal.filtfilt's defaults on second-order sections, batched over clips."""
 import numpy as np
 
@@ -80,3 +81,9 @@ def filtfilt_batch(sos_list, clips, padlens):
 
 def filtfilt(sos, v, padlen):
     return filtfilt_batch([sos], [v], [padlen])[0]
+
+
+def keep_energy(v, y):
+    """kws_filter_apply's rescale of a filtered clip y to the energy of its input v, float64"""
+    v = np.asarray(v, np.float64)
+    return y * np.sqrt(np.sum(v * v) / (np.sum(y * y) + len(v) * np.finfo(np.float32).eps))

@@ -27,5 +27,6 @@ struct kws_rir_bank {
     int32_t *d_len = nullptr;  // [K] device copy
     float2 *spec = nullptr;    // [K][kSpecStride]: H_k[0..M] / (4 M), fp64-computed, rounded to fp32 (the 1 / (4 M) folds every
                                // normalisation of the real-FFT packing and the inverse transform into the spectrum; a power of two)
+    float *taps = nullptr;     // [K][max_samples]: the clipped taps, zeros after Lh (clips of a few samples are convolved directly)
     float2 *tw = nullptr;      // [N] exp(-2 pi i n / N), fp64-computed, rounded to fp32
 };

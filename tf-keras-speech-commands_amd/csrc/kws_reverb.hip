@@ -9,6 +9,12 @@
 // imaginary parts through one 68 KiB plane (padded every 16 floats against bank conflicts), so two blocks' worth of LDS is never held:
 // what the co-running train step needs stays free.  Sums are fp32 per thread and fp64 across the block in a fixed order (no atomics),
 // so two calls give the same bits.
+//
+// A clip of at most kDirect samples does not go through the transform.  Its output samples are few products, so |y| comes close to
+// ||v|| ||h|| (for one sample they are equal), and the last bit that the float32 sums of the inverse transform lose is then as large
+// as the error the tests allow (1e-7 ||v|| ||h||, less than one float32 ulp of such a y).  That clip is convolved with the bank's taps
+// directly in fp64, rescaled in fp64 and rounded once.  Past a wave's worth of samples |y| / (||v|| ||h||) of a noise-like clip is
+// below 3 / sqrt(64) and the transform's ulp no longer shows.
 #include <cfloat>
 #include <cmath>
 #include <complex>
@@ -23,6 +29,7 @@ namespace kws {
 namespace rv {
 
 constexpr int kThreads = 1024;
+constexpr int kDirect = 64;                             // clips up to this many samples are convolved directly
 constexpr int kPlane = M + M / 16;                      // floats of the padded exchange plane
 constexpr int kLdsBytes = kPlane * (int)sizeof(float);  // 69632
 enum { kRevApply = 0, kRevRir = 1, kRevFields = 2 };    // draw fields: aug_hash(seed_r, step, 2 p + f)
@@ -174,10 +181,42 @@ __device__ __forceinline__ double block_sum(double v, double *red)
     return s;
 }
 
+// The wet clip of lv <= kDirect samples: y[t] = sum_j v[j] h[t - j] in fp64 with the taps h[0, lh), the rescale in fp64, one rounding
+// to float32.  Every thread of the block calls it; dst[0, out_stride) is written whole.
+template <typename WavT>
+__device__ __forceinline__ void direct_clip(const WavT *__restrict__ v, int lv, const float *__restrict__ h, int lh, int len_out,
+                                            int rescale, float *__restrict__ dst, int64_t out_stride, double *red)
+{
+    const int tid = threadIdx.x;
+    auto y_at = [&](int t) -> double {
+        double acc = 0.0;
+        const int j0 = t - (lh - 1) > 0 ? t - (lh - 1) : 0, j1 = t < lv - 1 ? t : lv - 1;
+        for (int j = j0; j <= j1; ++j) acc = fma((double)aug_to_f32(v[j]), (double)h[t - j], acc);
+        return acc;
+    };
+    double scale = 1.0;
+    if (rescale) {
+        double ev = 0.0, ey = 0.0;
+        for (int j = 0; j < lv; ++j) {
+            const double x = (double)aug_to_f32(v[j]);
+            ev = fma(x, x, ev);
+        }
+        if (tid < lv && tid < len_out) {
+            const double y = y_at(tid);
+            ey = y * y;
+        }
+        const double Ey = block_sum(ey, red);
+        scale = sqrt(ev / (Ey + (double)lv * (double)FLT_EPSILON));
+    }
+    for (int t = tid; t < len_out; t += kThreads) dst[t] = (float)(y_at(t) * scale);
+    for (int64_t t = (int64_t)len_out + tid; t < out_stride; t += kThreads) dst[t] = 0.f;
+}
+
 template <typename WavT>
 __global__ __launch_bounds__(1024) void reverb_apply_kernel(const WavT *__restrict__ wav, int64_t stride, const int32_t *__restrict__ index,
                                                             const int32_t *__restrict__ valid_len, kws_reverb_params p, int K,
-                                                            const int32_t *__restrict__ rir_len, const float2 *__restrict__ spec,
+                                                            const int32_t *__restrict__ rir_len, const float *__restrict__ taps,
+                                                            int tap_stride, const float2 *__restrict__ spec,
                                                             const float2 *__restrict__ tw, int64_t position_base, uint32_t step,
                                                             int explicit_rir, float *__restrict__ out, int64_t out_stride,
                                                             int32_t *__restrict__ lengths, int32_t *__restrict__ rir_used)
@@ -201,6 +240,10 @@ __global__ __launch_bounds__(1024) void reverb_apply_kernel(const WavT *__restri
     }
     if (k < 0 || lv == 0) {                                 // dry (or empty): a copy
         dry_copy<kThreads>(dst, v, lv, out_stride);
+        return;
+    }
+    if (lv <= kDirect) {                                    // a few samples: directly, in fp64
+        direct_clip(v, lv, taps + (int64_t)k * tap_stride, rir_len[k], len_out, p.rescale, dst, out_stride, red[0]);
         return;
     }
     for (int64_t t = (int64_t)ms + tid; t < out_stride; t += kThreads) dst[t] = 0.f;
@@ -330,6 +373,7 @@ int kws_rir_bank_create(const float *taps, const int32_t *rir_len, int K, int ma
     rb->max_samples = max_samples;
     rb->len.resize(K);
     std::vector<float2> spec((size_t)K * kSpecStride, make_float2(0.f, 0.f));
+    std::vector<float> kept((size_t)K * max_samples, 0.f);
     std::vector<std::complex<double>> x(N);
     const double norm = 1.0 / (4.0 * M);
     int64_t off = 0;
@@ -338,6 +382,7 @@ int kws_rir_bank_create(const float *taps, const int32_t *rir_len, int K, int ma
         rb->len[k] = lh;
         std::fill(x.begin(), x.end(), std::complex<double>(0.0, 0.0));
         for (int j = 0; j < lh; ++j) x[j] = (double)taps[off + j];
+        for (int j = 0; j < lh; ++j) kept[(size_t)k * max_samples + j] = taps[off + j];
         host_fft(x);
         for (int i = 0; i <= M; ++i) spec[(size_t)k * kSpecStride + i] = make_float2((float)(x[i].real() * norm), (float)(x[i].imag() * norm));
         off += rir_len[k];
@@ -349,12 +394,14 @@ int kws_rir_bank_create(const float *taps, const int32_t *rir_len, int K, int ma
         return rc;
     };
     if (hipMalloc(&rb->spec, sizeof(float2) * spec.size()) != hipSuccess || hipMalloc(&rb->tw, sizeof(float2) * N) != hipSuccess ||
+        hipMalloc(&rb->taps, sizeof(float) * kept.size()) != hipSuccess ||
         hipMalloc(&rb->d_len, sizeof(int32_t) * K) != hipSuccess) {
         (void)hipGetLastError();
         return cleanup(fail(KWS_ERR_HIP, "RIR bank: device allocation for %d spectra failed", K));
     }
     if (hipMemcpy(rb->spec, spec.data(), sizeof(float2) * spec.size(), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(rb->tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(rb->taps, kept.data(), sizeof(float) * kept.size(), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(rb->d_len, rb->len.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         return cleanup(fail(KWS_ERR_HIP, "RIR bank: upload failed"));
@@ -368,6 +415,7 @@ void kws_rir_bank_destroy(kws_rir_bank *rb)
     if (!rb) return;
     if (rb->spec) (void)hipFree(rb->spec);
     if (rb->tw) (void)hipFree(rb->tw);
+    if (rb->taps) (void)hipFree(rb->taps);
     if (rb->d_len) (void)hipFree(rb->d_len);
     delete rb;
 }
@@ -401,7 +449,7 @@ int kws_reverb_apply(const kws_rir_bank *rb, const kws_reverb_params *p, const v
         using WavT = decltype(t);
         if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(reverb_apply_kernel<WavT>), kLdsBytes)) return rc;
         KWS_LAUNCH(name, reverb_apply_kernel<WavT>, grid, block, kLdsBytes, s, static_cast<const WavT *>(wav), stride, index, valid_len, *p,
-                   rb->K, rb->d_len, rb->spec, rb->tw, position_base, (uint32_t)step, explicit_rir ? 1 : 0, out, out_stride, lengths, rir_used);
+                   rb->K, rb->d_len, rb->taps, rb->max_samples, rb->spec, rb->tw, position_base, (uint32_t)step, explicit_rir ? 1 : 0, out, out_stride, lengths, rir_used);
         KWS_LAUNCH_CHECK("reverb_apply_kernel");
         return KWS_OK;
     });
