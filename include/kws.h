@@ -189,14 +189,17 @@ typedef struct kws_aug_clip {
  * clip's global position position_base + b (a data-parallel shard plans with position_base = its first position): apply = u <
  * noised_rate, k, s, o uniform in [0, seg_len[k] - L], d uniform in [-max_shift, max_shift].  explicit_plan (HOST, B records, or NULL):
  * take apply / segment / offset / shift / snr_db from the caller instead (an offset past seg_len[k] - L is clamped to it); L, gain and
- * voice_length are computed either way.  plan: B device records. */
+ * voice_length are computed either way.  plan: B device records.
+ * KWS_ERR_INVALID: an SNR outside [-200, 200] dB, in params->snr_db or in an explicit record (the message names the list entry or the
+ * clip).  At +-200 dB and |v| <= 1 the gain is at most 2.9e13, finite in float32 with 25 orders of magnitude to spare, and nothing real
+ * needs more; from -702 dB on a full-scale voice over silent noise gives g = inf and a mix of inf and NaN. */
 int kws_augment_plan(const kws_noise_bank *bank, const kws_augment_params *params, const void *wav, int wav_dtype, const int32_t *index,
                      int B, int64_t stride, const int32_t *valid_len, int64_t position_base, int64_t step, kws_aug_clip *plan,
                      const kws_aug_clip *explicit_plan, void *stream);
 
 /* Materialise the planned clips m' (what the model trains on): out (B x out_stride float32, out_stride >= max_samples) holds m'[0:L]
- * head-aligned, zeros after; lengths (device int32 B, may be NULL) = L.  featurize(out, valid_len = lengths) equals
- * kws_featurize_gather_augmented bit for bit. */
+ * head-aligned, zeros after, out to out_stride as every wave stage fills its rows; lengths (device int32 B, may be NULL) = L.
+ * featurize(out, valid_len = lengths) equals kws_featurize_gather_augmented bit for bit. */
 int kws_augment_apply(const kws_noise_bank *bank, const kws_aug_clip *plan, const void *wav, int wav_dtype, const int32_t *index, int B,
                       int64_t stride, int max_samples, float *out, int64_t out_stride, int32_t *lengths, void *stream);
 

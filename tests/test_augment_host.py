@@ -147,3 +147,43 @@ def test_invalid_plan_arguments_are_reported_host_side():
     x = (ctypes.c_float * 4)()
     rc = L.kws_noise_bank_create(ctypes.cast(x, ctypes.c_void_p), 0, ctypes.cast(seg, ctypes.c_void_p), 0, ctypes.byref(ctypes.c_void_p()))
     assert rc == l.ERR_INVALID and b"at least one segment" in L.kws_last_error()
+
+
+def test_snr_outside_200_db_is_refused_host_side():
+    """An SNR outside [-200, 200] dB is KWS_ERR_INVALID in kws_augment_params and in explicit records alike, and a ValueError in
+    WaveAugment: beyond it the float32 gain can overflow (tests/test_speed_mix_edges_host.py).  The checks need no bank, so a NULL one
+    shows which values pass: they get as far as "null noise bank"."""
+    import ctypes
+    from kws_amd import lib as l
+    from kws_amd.augment import CLIP_DTYPE, WaveAugment
+    noise = [np.zeros(100, np.float32) + 0.1]
+    assert WaveAugment(noise, snr=[-200, 200]).snr == [-200.0, 200.0]
+    for bad, entry in (([-200.5], 0), ([0, 201], 1), ([5, 10, 1e30], 2), ([-700], 0), ([float("inf")], 0), ([float("nan")], 0)):
+        with pytest.raises(ValueError, match="SNR %d " % entry):
+            WaveAugment(noise, snr=bad)
+    L = l.get_lib()
+    wav = np.zeros((2, 8), np.float32)
+    plan = np.zeros(2, CLIP_DTYPE)
+
+    def call(snrs, explicit=None):
+        p = l.KwsAugmentParams()
+        p.noised_rate, p.n_snr, p.max_samples = 0.5, len(snrs), 8
+        for i, s in enumerate(snrs):
+            p.snr_db[i] = s
+        rc = L.kws_augment_plan(None, ctypes.byref(p), wav.ctypes.data, l.WAV_F32, None, 2, 8, None, 0, 0, plan.ctypes.data,
+                                None if explicit is None else explicit.ctypes.data, None)
+        return rc, L.kws_last_error().decode()
+
+    for ok in ([-200.0, 200.0], [0.0], [199.99]):
+        rc, msg = call(ok)
+        assert rc == l.ERR_INVALID and msg == "null noise bank", (ok, msg)
+    for bad, entry in (([-200.5], 0), ([0.0, 201.0], 1), ([5.0, 10.0, 1e30], 2), ([-700.0], 0), ([float("inf")], 0), ([float("nan")], 0)):
+        rc, msg = call(bad)
+        assert rc == l.ERR_INVALID and msg.startswith("SNR %d " % entry) and "[-200, 200]" in msg, (bad, msg)
+    for s, accepted in ((-200.0, True), (200.0, True), (-200.5, False), (201.0, False), (-700.0, False), (3e38, False),
+                        (float("nan"), False)):
+        ex = np.zeros(2, CLIP_DTYPE)
+        ex["snr_db"][1] = s
+        rc, msg = call([0.0], ex)
+        assert rc == l.ERR_INVALID
+        assert msg == "null noise bank" if accepted else (msg.startswith("clip 1: SNR") and "[-200, 200]" in msg), (s, msg)

@@ -72,8 +72,9 @@ __global__ __launch_bounds__(256) void augment_apply_kernel(const WavT *__restri
     const WavT *v = wav + (int64_t)row * stride;
     const float *n = bank + (r.apply ? seg_start[r.segment] + r.offset : 0);
     float *dst = out + (int64_t)b * out_stride;
-    for (int t = (int)threadIdx.x; t < max_samples; t += (int)blockDim.x)
-        dst[t] = aug_sample(v, n, r.length, r.shift, r.gain, r.apply != 0, t);
+    // to out_stride, as every sibling stage: aug_sample is 0 from r.length (<= max_samples) on
+    for (int64_t t = (int64_t)threadIdx.x; t < out_stride; t += (int64_t)blockDim.x)
+        dst[t] = t < max_samples ? aug_sample(v, n, r.length, r.shift, r.gain, r.apply != 0, (int)t) : 0.f;
     if (lengths && threadIdx.x == 0) lengths[b] = r.length;
 }
 
@@ -158,13 +159,19 @@ int kws_noise_bank_info(const kws_noise_bank *nb, int *K, int64_t *total, int32_
     return KWS_OK;
 }
 
+// The SNRs the plan accepts (include/kws.h): at +-200 dB and |v| <= 1 the gain sqrt(p_v / 10^(s/10) / FLT_EPSILON) is at most 2.9e13,
+// finite in float32 with 25 orders of magnitude to spare; from -702 dB on it is inf.  NaN fails both comparisons.
+constexpr float kMaxSnrDb = 200.f;
+static bool snr_ok(float s) { return s >= -kMaxSnrDb && s <= kMaxSnrDb; }
+
 static int check_params(const kws_augment_params *p)
 {
     if (!p) return fail(KWS_ERR_INVALID, "null augment params");
     if (!(p->noised_rate >= 0.f && p->noised_rate <= 1.f)) return fail(KWS_ERR_INVALID, "noised_rate %g is outside [0, 1]", (double)p->noised_rate);
     if (p->n_snr < 1 || p->n_snr > KWS_AUG_MAX_SNR) return fail(KWS_ERR_INVALID, "the SNR list needs 1..%d entries, got %d", KWS_AUG_MAX_SNR, p->n_snr);
     for (int i = 0; i < p->n_snr; ++i)
-        if (!std::isfinite(p->snr_db[i])) return fail(KWS_ERR_INVALID, "SNR %d is not finite", i);
+        if (!snr_ok(p->snr_db[i]))
+            return fail(KWS_ERR_INVALID, "SNR %d (%g dB) is outside [%g, %g]", i, (double)p->snr_db[i], -(double)kMaxSnrDb, (double)kMaxSnrDb);
     if (p->max_shift < 0) return fail(KWS_ERR_INVALID, "max_shift %d is negative", p->max_shift);
     if (p->max_shift > (1 << 24)) return fail(KWS_ERR_INVALID, "max_shift %d is too large", p->max_shift);
     return KWS_OK;
@@ -174,18 +181,25 @@ int kws_augment_plan(const kws_noise_bank *bank, const kws_augment_params *param
                      int B, int64_t stride, const int32_t *valid_len, int64_t position_base, int64_t step, kws_aug_clip *plan,
                      const kws_aug_clip *explicit_plan, void *stream)
 {
-    if (!bank || !plan || (!wav && B > 0)) return fail(KWS_ERR_INVALID, "null argument");
-    if (bank->K < 1) return fail(KWS_ERR_INVALID, "empty noise bank");
+    // what needs no bank comes first, so that a caller's values are judged the same with and without a device
+    if (!plan || (!wav && B > 0)) return fail(KWS_ERR_INVALID, "null argument");
     if (int rc = check_params(params)) return rc;
     if (int rc = check_clip_batch(params->max_samples, INT_MAX, B, stride, false, valid_len, position_base, nullptr, wav_dtype)) return rc;
+    if (explicit_plan)
+        for (int b = 0; b < B; ++b) {
+            const kws_aug_clip &r = explicit_plan[b];
+            if (!snr_ok(r.snr_db))
+                return fail(KWS_ERR_INVALID, "clip %d: SNR %g dB is outside [%g, %g]", b, (double)r.snr_db, -(double)kMaxSnrDb, (double)kMaxSnrDb);
+            if (r.shift < -(1 << 24) || r.shift > (1 << 24)) return fail(KWS_ERR_INVALID, "clip %d: shift %d is too large", b, r.shift);
+        }
+    if (!bank) return fail(KWS_ERR_INVALID, "null noise bank");
+    if (bank->K < 1) return fail(KWS_ERR_INVALID, "empty noise bank");
     if (explicit_plan)
         for (int b = 0; b < B; ++b) {
             const kws_aug_clip &r = explicit_plan[b];
             if (r.segment < 0 || r.segment >= bank->K) return fail(KWS_ERR_INVALID, "clip %d: segment %d is outside [0, %d)", b, r.segment, bank->K);
             if (r.offset < 0 || r.offset >= bank->len[r.segment])
                 return fail(KWS_ERR_INVALID, "clip %d: offset %d is outside segment %d (%d samples)", b, r.offset, r.segment, bank->len[r.segment]);
-            if (!std::isfinite(r.snr_db)) return fail(KWS_ERR_INVALID, "clip %d: SNR is not finite", b);
-            if (r.shift < -(1 << 24) || r.shift > (1 << 24)) return fail(KWS_ERR_INVALID, "clip %d: shift %d is too large", b, r.shift);
         }
     if (B == 0) return KWS_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);

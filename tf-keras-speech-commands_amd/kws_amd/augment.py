@@ -629,8 +629,9 @@ class WaveAugment(object):
         snr = parse_snr(snr)
         if not 1 <= len(snr) <= _l.AUG_MAX_SNR:
             raise ValueError("the SNR list needs 1..%d values, got %d" % (_l.AUG_MAX_SNR, len(snr)))
-        if not all(math.isfinite(s) for s in snr):
-            raise ValueError("SNR values must be finite: %r" % (snr,))
+        for i, s in enumerate(snr):                         # kws_augment_plan's range: beyond it the float32 gain can overflow
+            if not -_l.AUG_MAX_SNR_DB <= s <= _l.AUG_MAX_SNR_DB:
+                raise ValueError("SNR %d (%r dB) is outside [-%g, %g]" % (i, s, _l.AUG_MAX_SNR_DB, _l.AUG_MAX_SNR_DB))
         if not float(time_shift_ms) >= 0:
             raise ValueError("time_shift_ms must be >= 0, got %r" % time_shift_ms)
         self.noise = None if noise is None else noise if isinstance(noise, NoiseBank) else NoiseBank(noise)

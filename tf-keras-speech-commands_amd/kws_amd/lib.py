@@ -63,6 +63,7 @@ class KwsOptimizerArgs(ctypes.Structure):
 
 
 AUG_MAX_SNR = 16
+AUG_MAX_SNR_DB = 200.0    # kws_augment_plan refuses SNRs outside [-200, 200] dB (include/kws.h)
 
 
 class KwsAugmentParams(ctypes.Structure):
