@@ -358,10 +358,13 @@ __global__ __launch_bounds__(kThreads) void pitch_synth_kernel(const WavT *__res
                     else if (q == 2) y = make_float2(-y.x, -y.y);
                     else if (q == 3) y = make_float2(y.y, -y.x);
                     b1[g * KB + k] = y;
-                    const float kq = (float)(k & 3);                         // the quarter turns of (pi / 2) k that are no whole turn
-                    float d = d1[i].ang - d0[i].ang;
-                    d = __fmaf_rn(-kq, -4.37113883e-8f, __fmaf_rn(-kq, 1.57079637050628662f, d));
-                    phi[i] = wrap_pi(phi[i] + wrap_pi(d));
+                    // The measured advance minus the quarter turns of (pi / 2) k that are no whole turn, wrapped into [-pi, pi], in
+                    // fp64 and rounded once.  In fp32 the difference of the angles minus kq fl(pi / 2) lands on a grid of 2^-22 or
+                    // 2^-21, which swallows a low part of pi / 2 (4.4e-8): every bin with k mod 4 != 0 then ran 4.4e-8 kq rad a frame
+                    // fast, the same way in every frame: 3e-5 rad after a second at N = 256, and a steady tone shows it.
+                    double dd = (double)d1[i].ang - (double)d0[i].ang - (double)(k & 3) * 1.5707963267948966;
+                    dd -= 6.283185307179586 * rint(dd * 0.15915494309189535);
+                    phi[i] = wrap_pi(phi[i] + (float)dd);
                 }
                 pm0 = m0;
             }
