@@ -1107,6 +1107,60 @@ int kws_stream_postprocess(const kws_decoder *dec, const float *probs, int S, in
                            double *score, int32_t *fired, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Ragged streaming: the same per-chunk loop for streams that do NOT advance in lockstep.  A server has S slots, each an
+ * independent Listener of the reference with, per slot,
+ *   window_audio  the carry, win[slot][0 : carry) int16; with H <= W at most W - 1 samples after a push, so cap = W + chunk_size
+ *                 samples per slot suffice (W = window_samples, H = hop_samples);
+ *   mfccs         the (F, D) feature window, initially zero;
+ *   state         {activation, record_index}, initially {0, -1};
+ *   sensitivity, trigger_level   its own operating point.
+ * One push delivers A chunks for A DISTINCT slots, in any order, 1 <= len <= chunk_size samples each, 0 <= A <= S.  For every
+ * entry it does what listen.py:96-109 and :350-375 do for one chunk:
+ *   L = carry + len;  n_new = 0 if L < W else (L - W) / H + 1;
+ *   new rows = vectorize_raw of the samples [j H, j H + W) of carry + chunk, j < n_new;
+ *   mfccs = concatenate(mfccs[n:], new[-n:]) with n = min(n_new, F);
+ *   the carry keeps the max(L - n_new H, 0) samples from n_new H on (H > W: the carry empties, as in the lockstep form);
+ *   the slot's window is predicted on, ALSO when n_new == 0 (the reference predicts on every chunk); argmax, max, decode
+ *   unless background, then TriggerDetector.update with the slot's own sensitivity and trigger level.  The refractory
+ *   period uses the server's nominal chunk_size, as the lockstep form does.
+ * Slots a push does not name are not touched in any buffer.
+ *
+ * The push is described by one host-built table of A entries of KWS_RAGGED_FIELDS int32 each, copied to the device with the
+ * push: the slot, the carry length BEFORE the push (the host mirrors it with the three lines above, which is also how it knows
+ * max_frames = max n_new without reading anything back), the chunk's length, n_new, and a flag that restarts the slot (empty
+ * carry, zero window, state {0, -1}) before the chunk is taken.  The sequence of a push, all on one stream:
+ *   kws_stream_ragged_append -> kws_featurize_long(act, act_len) when max_frames > 0 -> kws_stream_ragged_push_rows ->
+ *   the forward pass on feat (A, F, D) -> kws_stream_ragged_postprocess.
+ * Each entry point checks its arguments on the host before any launch (KWS_ERR_INVALID), does nothing for A == 0, is
+ * stream-ordered and uses neither synchronisation nor atomics.  The kernels clamp what they read from the table to the
+ * buffers, so a wrong table gives wrong results and no access outside them; entries naming one slot twice race.
+ * ------------------------------------------------------------------------ */
+enum { KWS_RAGGED_SLOT = 0, KWS_RAGGED_CARRY = 1, KWS_RAGGED_LEN = 2, KWS_RAGGED_NEW = 3, KWS_RAGGED_RESET = 4, KWS_RAGGED_FIELDS = 8 };
+
+/* Entry a: act[a][0 : L) = win[slot][0 : carry) ++ chunks[a][0 : len), act_len[a] = L (the input of kws_featurize_long), and
+ * win[slot][0 : keep) = the samples of that row from n_new H on, in the same kernel.  win (S, win_stride), act (A, act_stride):
+ * rows of at least cap samples, a multiple of 8 samples long, the arrays starting on 16 bytes; chunks (A, chunk_stride), any
+ * stride and alignment (rows that start on 16 bytes and are a multiple of 8 long are read 16 bytes at a time).
+ * cap >= window_samples + chunk_size, at most 32768 (KWS_ERR_UNSUPPORTED beyond). */
+int kws_stream_ragged_append(int16_t *win, int64_t win_stride, int S, int cap, const int16_t *chunks, int64_t chunk_stride,
+                             const int32_t *table, int A, int chunk_size, int window_samples, int hop_samples, int16_t *act,
+                             int64_t act_stride, int32_t *act_len, void *stream);
+
+/* Entry a: mfccs[slot] (of mfccs (S, F, D)) slides by n = min(n_new, F) with rows[a][n_new - n : n_new) of rows
+ * (A, max_frames, D), what kws_featurize_long wrote for act; the updated window is also written to feat[a] of feat (A, F, D).
+ * n_new == 0 only copies; the restart flag takes the old window as zeros.  rows may be NULL when max_frames == 0. */
+int kws_stream_ragged_push_rows(float *mfccs, int S, int F, int D, const float *rows, int max_frames, const int32_t *table, int A,
+                                float *feat, void *stream);
+
+/* Entry a: kws_stream_postprocess of probs[a] (probs (A, C)) with sensitivity[slot], trigger_level[slot] (device arrays of S)
+ * on state[slot] (state (S, 2); the restart flag sets {0, -1} first).  The results go to index / score / fired [a] (A) and to
+ * slot_index / slot_score / slot_fired [slot] (S). */
+int kws_stream_ragged_postprocess(const kws_decoder *dec, const float *probs, int A, int C, const int32_t *table, int S,
+                                  int background_index, const double *sensitivity, const int32_t *trigger_level, int chunk_size,
+                                  int32_t *state, int32_t *slot_index, double *slot_score, int32_t *slot_fired, int32_t *index,
+                                  double *score, int32_t *fired, void *stream);
+
+/* ------------------------------------------------------------------------
  * Offline scan: the loop above over whole recordings that already lie in memory, parallel over time.  It returns per
  * chunk what the chunk loop returns.  With W = window_samples, H = hop_samples, c = chunk_size and N samples:
  *   chunks  T = ceil(N / c); after chunk k (1-based) n_k = min(k c, N) samples have arrived (wave.readframes delivers a short

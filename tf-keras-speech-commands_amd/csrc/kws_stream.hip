@@ -15,6 +15,10 @@
 //   Listener.on_activation    listen.py:291-308   -> kws_stream_collect (the walk once more at one operating point, every activation
 //                                                    recorded with its chunk, class and kind -- hit, duplicate, false alarm)
 //   (nothing in the reference)                    -> kws_stream_peaks (the near misses: the best well-separated non-background chunks)
+// and the same per-chunk loop for streams that do NOT advance together (kws_amd.stream.StreamServer):
+//   update_vectors (samples)  listen.py:96-105    -> kws_stream_ragged_append (carry + chunk -> compact row, carry shifted in the same kernel)
+//   update_vectors (rows)     listen.py:107-109   -> kws_stream_ragged_push_rows (each slot slides by its own row count)
+//   the prediction loop       listen.py:361-375   -> kws_stream_ragged_postprocess (per-slot sensitivity, trigger level and state)
 // Everything here is a few bytes per stream and one thread per stream: the kernels are latency-sized, the point of doing
 // them on the device is that probabilities, scores and detector state never leave HBM between the forward pass of one
 // chunk and the next (the whole step can sit in one hipGraph).  Arithmetic is float64 wherever the reference computes
@@ -471,6 +475,149 @@ __global__ __launch_bounds__(64) void peaks_kernel(const int32_t *__restrict__ i
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Ragged streaming (kws_amd.stream.StreamServer): S slots, of which the A named in a push's table advance, each by a chunk of
+// its own length.  An entry of the table is KWS_RAGGED_FIELDS int32: slot, the carry length the host mirrors, the chunk's
+// length, the rows the push gives the slot, and a flag that restarts the slot first.  Every kernel clamps what it reads from
+// the table to its buffers, so a wrong table gives wrong numbers and never an access outside them.
+// ---------------------------------------------------------------------------------------------------------------------
+using short8 = __attribute__((ext_vector_type(8))) short;
+constexpr int kRaggedStep = 256 * 8;                                            // samples a block moves per pass, 16 bytes per thread
+
+// block = one entry.  Carry and chunk are staged once in LDS (carry + chunk <= cap samples); after the barrier the LDS copy is the
+// only source, so the compact row act[a] and the slot's post-push carry are written from it in the same kernel: the carry's shift
+// cannot overlap its own reads and needs no second pass.  Rows of win / act (and of chunks when chunks_wide) start on 16 bytes
+// and are a multiple of 8 samples long: that side moves 16 bytes per thread, the side whose offset is arbitrary (the chunk's
+// place behind the carry, the carry's place inside the row) moves sample by sample through LDS.
+__global__ __launch_bounds__(256) void ragged_append_kernel(short *__restrict__ win, long win_stride, int S, int cap,
+                                                             const short *__restrict__ chunks, long chunk_stride, int chunks_wide,
+                                                             const int32_t *__restrict__ table, int chunk_size, int W, int H,
+                                                             short *__restrict__ act, long act_stride, int32_t *__restrict__ act_len)
+{
+    extern __shared__ __attribute__((aligned(16))) short ragged_lds[];         // cap samples, rounded up to 8
+    const int a = blockIdx.x, t = threadIdx.x;
+    const int32_t *e = table + (long)a * KWS_RAGGED_FIELDS;
+    const int slot = e[KWS_RAGGED_SLOT];
+    if (slot < 0 || slot >= S) {                                                // block-uniform
+        if (t == 0) act_len[a] = 0;
+        return;
+    }
+    int carry = e[KWS_RAGGED_RESET] ? 0 : e[KWS_RAGGED_CARRY];
+    carry = carry < 0 ? 0 : (carry < cap ? carry : cap);
+    int room = cap - carry;
+    room = room < chunk_size ? room : chunk_size;
+    room = (long)room < chunk_stride ? room : (int)chunk_stride;
+    int len = e[KWS_RAGGED_LEN];
+    len = len < 0 ? 0 : (len < room ? len : room);
+    const int L = carry + len;
+    short *w = win + (long)slot * win_stride;
+    const short *c = chunks + (long)a * chunk_stride;
+    for (int i = t * 8; i < carry; i += kRaggedStep) {
+        const short8 v = *reinterpret_cast<const short8 *>(w + i);
+        if (i + 8 <= carry) {
+            *reinterpret_cast<short8 *>(ragged_lds + i) = v;
+        } else {                                                                // the chunk's first samples share this vector
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (i + j < carry) ragged_lds[i + j] = v[j];
+        }
+    }
+    if (chunks_wide) {
+        for (int i = t * 8; i < len; i += kRaggedStep) {
+            const short8 v = *reinterpret_cast<const short8 *>(c + i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (i + j < len) ragged_lds[carry + i + j] = v[j];
+        }
+    } else {
+        for (int i = t; i < len; i += 256) ragged_lds[carry + i] = c[i];
+    }
+    __syncthreads();
+    short *o = act + (long)a * act_stride;
+    for (int i = t * 8; i < L; i += kRaggedStep) {
+        short8 v = *reinterpret_cast<const short8 *>(ragged_lds + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (i + j >= L) v[j] = 0;
+        *reinterpret_cast<short8 *>(o + i) = v;
+    }
+    if (t == 0) act_len[a] = L;
+    const int n_new = L < W ? 0 : (L - W) / H + 1;                              // listen.py:103-105
+    const long used = (long)n_new * H;
+    const int keep = used < L ? (int)(L - used) : 0;                            // hop > window: the rows may consume more than is held
+    for (int i = t * 8; i < keep; i += kRaggedStep) {
+        short8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = i + j < keep ? ragged_lds[used + i + j] : (short)0;
+        *reinterpret_cast<short8 *>(w + i) = v;
+    }
+}
+
+// block = one entry: push_rows_kernel for the entry's slot with the entry's own row count, the updated window written a second
+// time, compact, to feat[a] for the forward pass.  Every element is read before the pass's barrier, as there.
+__global__ __launch_bounds__(256) void ragged_push_rows_kernel(float *__restrict__ mfccs, int S, int F, int D, const float *__restrict__ rows,
+                                                                int max_frames, const int32_t *__restrict__ table, float *__restrict__ feat)
+{
+    const int a = blockIdx.x;
+    const int32_t *e = table + (long)a * KWS_RAGGED_FIELDS;
+    const int slot = e[KWS_RAGGED_SLOT];
+    if (slot < 0 || slot >= S) return;
+    int n_new = e[KWS_RAGGED_NEW];
+    n_new = n_new < 0 ? 0 : (n_new < max_frames ? n_new : max_frames);
+    const int n_keep = n_new < F ? n_new : F;
+    const bool reset = e[KWS_RAGGED_RESET] != 0;
+    const bool store = reset || n_keep > 0;                                     // no new row: the window is only copied
+    float *f = mfccs + (long)slot * F * D;
+    float *o = feat + (long)a * F * D;
+    const float *r = rows + ((long)a * max_frames + (n_new - n_keep)) * D;      // the last n_keep new rows
+    const int total = F * D, shift = n_keep * D;
+    constexpr int kPer = 8;                                                     // F*D <= 2048 per pass
+    for (int base = 0; base < total; base += 256 * kPer) {
+        float v[kPer];
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const int i = base + threadIdx.x + 256 * j;
+            v[j] = 0.f;
+            if (i < total) v[j] = i + shift < total ? (reset ? 0.f : f[i + shift]) : r[i + shift - total];
+        }
+        __syncthreads();     // the reads of this pass precede its writes; later passes only read further right
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const int i = base + threadIdx.x + 256 * j;
+            if (i < total) {
+                if (store) f[i] = v[j];
+                o[i] = v[j];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// one thread per entry: postprocess_kernel with the slot's own operating point and state; results go to the entry's place in the
+// compact arrays and to the slot's place in the per-slot ones
+__global__ __launch_bounds__(256) void ragged_postprocess_kernel(const float *__restrict__ probs, int A, int C, const int32_t *__restrict__ table,
+                                                                  int S, int background, DecDev d, const double *__restrict__ sensitivity,
+                                                                  const int32_t *__restrict__ level, int refractory, int32_t *__restrict__ state,
+                                                                  int32_t *__restrict__ slot_index, double *__restrict__ slot_score,
+                                                                  int32_t *__restrict__ slot_fired, int32_t *__restrict__ index,
+                                                                  double *__restrict__ score, int32_t *__restrict__ fired)
+{
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= A) return;
+    const int32_t *e = table + (long)a * KWS_RAGGED_FIELDS;
+    const int slot = e[KWS_RAGGED_SLOT];
+    if (slot < 0 || slot >= S) { index[a] = -1; score[a] = 0.0; fired[a] = 0; return; }
+    int32_t st[2] = {0, -1};
+    if (!e[KWS_RAGGED_RESET]) { st[0] = state[2 * (long)slot]; st[1] = state[2 * (long)slot + 1]; }
+    double sc;
+    const int arg = argmax_decode(probs + (long)a * C, C, background, d, sc);
+    const int f = trigger_one(arg, sc, background, sensitivity[slot], level[slot], refractory, st);
+    state[2 * (long)slot] = st[0];
+    state[2 * (long)slot + 1] = st[1];
+    index[a] = arg; score[a] = sc; fired[a] = f;
+    slot_index[slot] = arg; slot_score[slot] = sc; slot_fired[slot] = f;
+}
+
 static DecDev dec_dev(const kws_decoder *d)
 {
     DecDev v;
@@ -642,6 +789,64 @@ int kws_stream_postprocess(const kws_decoder *dec, const float *probs, int S, in
                probs, S, C, background_index, dec_dev(dec), sensitivity, trigger_level, refractory_of(chunk_size), state, index, score,
                fired);
     KWS_LAUNCH_CHECK("postprocess_kernel");
+    return KWS_OK;
+}
+
+static bool on_16_bytes(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int kws_stream_ragged_append(int16_t *win, int64_t win_stride, int S, int cap, const int16_t *chunks, int64_t chunk_stride,
+                             const int32_t *table, int A, int chunk_size, int window_samples, int hop_samples, int16_t *act,
+                             int64_t act_stride, int32_t *act_len, void *stream)
+{
+    if (A < 0 || S < 0 || A > S) return fail(KWS_ERR_INVALID, "bad ragged push: A=%d entries for S=%d slots", A, S);
+    if (chunk_size < 1 || window_samples < 1 || hop_samples < 1)
+        return fail(KWS_ERR_INVALID, "bad chunk_size=%d window=%d hop=%d", chunk_size, window_samples, hop_samples);
+    if ((int64_t)cap < (int64_t)window_samples + chunk_size)
+        return fail(KWS_ERR_INVALID, "cap=%d is less than window + chunk_size = %d + %d: a slot's carry and one chunk would not fit", cap,
+                    window_samples, chunk_size);
+    if (cap > 32768) return fail(KWS_ERR_UNSUPPORTED, "cap=%d samples: carry and chunk are staged in 64 KiB of LDS (at most 32768)", cap);
+    if (win_stride < cap || act_stride < cap || (win_stride & 7) || (act_stride & 7) || chunk_stride < 1)
+        return fail(KWS_ERR_INVALID, "bad strides win=%lld act=%lld chunks=%lld: win / act rows hold cap=%d samples and are a multiple of 8 long",
+                    (long long)win_stride, (long long)act_stride, (long long)chunk_stride, cap);
+    if (A == 0) return KWS_OK;
+    if (!win || !chunks || !table || !act || !act_len) return fail(KWS_ERR_INVALID, "null argument");
+    if (!on_16_bytes(win) || !on_16_bytes(act)) return fail(KWS_ERR_INVALID, "win and act must start on 16 bytes");
+    const int wide = on_16_bytes(chunks) && (chunk_stride & 7) == 0;
+    const size_t smem = sizeof(int16_t) * (size_t)((cap + 7) & ~7);
+    KWS_LAUNCH("ragged_append_kernel", ragged_append_kernel, dim3((unsigned)A), dim3(256), smem, static_cast<hipStream_t>(stream),
+               reinterpret_cast<short *>(win), (long)win_stride, S, cap, reinterpret_cast<const short *>(chunks), (long)chunk_stride, wide, table,
+               chunk_size, window_samples, hop_samples, reinterpret_cast<short *>(act), (long)act_stride, act_len);
+    KWS_LAUNCH_CHECK("ragged_append_kernel");
+    return KWS_OK;
+}
+
+int kws_stream_ragged_push_rows(float *mfccs, int S, int F, int D, const float *rows, int max_frames, const int32_t *table, int A,
+                                float *feat, void *stream)
+{
+    if (A < 0 || S < 0 || A > S) return fail(KWS_ERR_INVALID, "bad ragged push: A=%d entries for S=%d slots", A, S);
+    if (F < 1 || D < 1 || max_frames < 0) return fail(KWS_ERR_INVALID, "bad stream geometry F=%d D=%d max_frames=%d", F, D, max_frames);
+    if (A == 0) return KWS_OK;
+    if (!mfccs || !table || !feat || (!rows && max_frames > 0)) return fail(KWS_ERR_INVALID, "null argument");
+    KWS_LAUNCH("ragged_push_rows_kernel", ragged_push_rows_kernel, dim3((unsigned)A), dim3(256), 0, static_cast<hipStream_t>(stream), mfccs, S, F,
+               D, rows, max_frames, table, feat);
+    KWS_LAUNCH_CHECK("ragged_push_rows_kernel");
+    return KWS_OK;
+}
+
+int kws_stream_ragged_postprocess(const kws_decoder *dec, const float *probs, int A, int C, const int32_t *table, int S, int background_index,
+                                  const double *sensitivity, const int32_t *trigger_level, int chunk_size, int32_t *state,
+                                  int32_t *slot_index, double *slot_score, int32_t *slot_fired, int32_t *index, double *score, int32_t *fired,
+                                  void *stream)
+{
+    if (A < 0 || S < 0 || A > S) return fail(KWS_ERR_INVALID, "bad ragged push: A=%d entries for S=%d slots", A, S);
+    if (C < 1 || chunk_size < 1) return fail(KWS_ERR_INVALID, "bad C=%d chunk_size=%d", C, chunk_size);
+    if (A == 0) return KWS_OK;
+    if (!probs || !table || !sensitivity || !trigger_level || !state || !slot_index || !slot_score || !slot_fired || !index || !score || !fired)
+        return fail(KWS_ERR_INVALID, "null argument");
+    KWS_LAUNCH("ragged_postprocess_kernel", ragged_postprocess_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0,
+               static_cast<hipStream_t>(stream), probs, A, C, table, S, background_index, dec_dev(dec), sensitivity, trigger_level,
+               refractory_of(chunk_size), state, slot_index, slot_score, slot_fired, index, score, fired);
+    KWS_LAUNCH_CHECK("ragged_postprocess_kernel");
     return KWS_OK;
 }
 

@@ -198,6 +198,7 @@ WAV_F32, WAV_I16 = 0, 1
 RAW_F64, RAW_F32 = 0, 1
 VAD_ALIGN = {"left": 0, "center": 1}                                                    # include/kws.h KWS_VAD_ALIGN_*
 DET_UNLABELLED, DET_HIT, DET_DUPLICATE, DET_FALSE_ALARM = 0, 1, 2, 3                     # include/kws.h KWS_DET_*
+RAGGED_SLOT, RAGGED_CARRY, RAGGED_LEN, RAGGED_NEW, RAGGED_RESET, RAGGED_FIELDS = 0, 1, 2, 3, 4, 8   # include/kws.h KWS_RAGGED_*
 
 _lib = None
 
@@ -281,6 +282,9 @@ def get_lib():
     L.kws_stream_push_rows.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.kws_trigger_update.argtypes = [vp, vp, i32, i32, f64, i32, i32, vp, vp, vp]
     L.kws_stream_postprocess.argtypes = [vp, vp, i32, i32, i32, f64, i32, i32, vp, vp, vp, vp, vp]
+    L.kws_stream_ragged_append.argtypes = [vp, i64, i32, i32, vp, i64, vp, i32, i32, i32, i32, vp, i64, vp, vp]
+    L.kws_stream_ragged_push_rows.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, fp, vp]
+    L.kws_stream_ragged_postprocess.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.kws_stream_gather_windows.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, i64, i32, fp, vp]
     L.kws_stream_scan_postprocess.argtypes = [vp, vp, i32, i32, i32, vp, i64, i32, f64, i32, i32, vp, vp, vp, vp, i64, vp]
     L.kws_stream_sweep.argtypes = [vp, vp, i32, i64, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]

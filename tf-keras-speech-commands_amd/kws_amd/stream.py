@@ -7,6 +7,8 @@ update) for S audio streams at once, and `scan`, the same loop over whole record
 parallel over time, and `sweep`, which walks the detector over a scan's decoded scores at a whole grid of operating points
 and counts hits, false alarms and misses against labelled events, and `collect` / `peaks`, which turn a scan's activations and
 near misses into `Detections`: the clips (`Detections.clips`, `.save`) the next training run needs as `background` examples.
+`StreamServer` is `StreamBatch` for streams that do not advance together: slots that open and close, a push that names the slots
+with audio, chunks of differing lengths, an operating point per slot (`RaggedPlan` is its host-only bookkeeping).
 All arithmetic runs in the HIP library; there is no host fallback.
 """
 import ctypes
@@ -213,6 +215,283 @@ class StreamBatch(object):
                                                 self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),
                                                 self.fired.data_ptr(), _stream()))
         return self.index, self.score, self.fired
+
+
+_NO_DELTAS = "streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered"
+
+
+class RaggedStep(object):
+    """One push as `RaggedPlan.push` worked it out, entry a for slots[a]: table, the (A, RAGGED_FIELDS) int32 array the kernels
+    read (include/kws.h); n_new, rows the push gives the slot; carry, its carry length after the push; first, the position in
+    the slot's stream (samples since it was opened) of the first sample of the first new row -- row j covers
+    [first + j * hop, first + j * hop + window); max_frames = max(n_new), 0 for an empty push."""
+
+    def __init__(self, table, n_new, carry, first, hop_samples):
+        self.table, self.n_new, self.carry, self.first, self.hop_samples = table, n_new, carry, first, hop_samples
+        self.A = int(table.shape[0])
+        self.max_frames = int(n_new.max()) if self.A else 0
+
+    def frame_starts(self, a):
+        return [int(self.first[a]) + j * self.hop_samples for j in range(int(self.n_new[a]))]
+
+
+class RaggedPlan(object):
+    """The host's half of `StreamServer`: which slots are open, each slot's carry length (a mirror of what the device holds,
+    kept with the arithmetic of listen.py:96-105, so nothing is ever read back), its operating point, the restart a freshly
+    opened slot still owes, and the checks of a push's arguments.  numpy only, no device."""
+
+    def __init__(self, n_slots, chunk_size, window_samples, hop_samples, sensitivity=0.5, trigger_level=3):
+        self.S, self.chunk_size = int(n_slots), int(chunk_size)
+        self.window_samples, self.hop_samples = int(window_samples), int(hop_samples)
+        if self.S < 0 or self.chunk_size < 1 or self.window_samples < 1 or self.hop_samples < 1:
+            raise ValueError("RaggedPlan needs n_slots >= 0 and positive chunk_size / window / hop")
+        self.cap = self.window_samples + self.chunk_size
+        self.default_sensitivity, self.default_trigger_level = float(sensitivity), int(trigger_level)
+        self.carry = np.zeros(self.S, np.int64)
+        self.position = np.zeros(self.S, np.int64)             # samples of the slot's stream in front of its carry
+        self.is_open = np.zeros(self.S, bool)
+        self.reset = np.zeros(self.S, bool)
+        self.sensitivity = np.full(self.S, self.default_sensitivity, np.float64)
+        self.trigger_level = np.full(self.S, self.default_trigger_level, np.int32)
+
+    def open(self, sensitivity=None, trigger_level=None):
+        """-> the lowest free slot, marked for a restart that rides in its next push"""
+        free = np.flatnonzero(~self.is_open)
+        if free.size == 0:
+            raise RuntimeError("the server is full: all %d slots are open" % self.S)
+        slot = int(free[0])
+        self.is_open[slot], self.reset[slot] = True, True
+        self.carry[slot] = self.position[slot] = 0
+        self.sensitivity[slot] = self.default_sensitivity if sensitivity is None else float(sensitivity)
+        self.trigger_level[slot] = self.default_trigger_level if trigger_level is None else int(trigger_level)
+        return slot
+
+    def _open_slot(self, slot):
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)):
+            raise ValueError("a slot is an integer, got %r" % (slot,))
+        if not 0 <= slot < self.S:
+            raise ValueError("slot %d is out of range 0..%d" % (slot, self.S - 1))
+        if not self.is_open[slot]:
+            raise ValueError("slot %d is closed" % slot)
+        return int(slot)
+
+    def close(self, slot):
+        self.is_open[self._open_slot(slot)] = False
+
+    def check(self, slots, lengths):
+        """-> (slots, lengths) as int64 arrays, or ValueError naming the fault; changes nothing"""
+        s = np.asarray(slots).reshape(-1) if len(slots) else np.zeros(0, np.int64)
+        n = np.asarray(lengths).reshape(-1) if len(lengths) else np.zeros(0, np.int64)
+        if s.dtype.kind not in "iu" or n.dtype.kind not in "iu":
+            raise ValueError("slots and lengths must be integers")
+        s, n = s.astype(np.int64), n.astype(np.int64)
+        if s.size != n.size:
+            raise ValueError("%d slots for %d chunks" % (s.size, n.size))
+        bad = np.flatnonzero((s < 0) | (s >= self.S))
+        if bad.size:
+            raise ValueError("slot %d is out of range 0..%d" % (s[bad[0]], self.S - 1))
+        bad = np.flatnonzero(~self.is_open[s])
+        if bad.size:
+            raise ValueError("slot %d is closed" % s[bad[0]])
+        if s.size > 1:
+            o = np.sort(s)
+            dup = np.flatnonzero(o[1:] == o[:-1])
+            if dup.size:
+                raise ValueError("slot %d is named twice in one push (duplicate slot)" % o[dup[0]])
+        bad = np.flatnonzero(n < 1)
+        if bad.size:
+            raise ValueError("the chunk for slot %d is empty" % s[bad[0]])
+        bad = np.flatnonzero(n > self.chunk_size)
+        if bad.size:
+            raise ValueError("chunk of %d samples for slot %d exceeds chunk_size=%d" % (n[bad[0]], s[bad[0]], self.chunk_size))
+        return s, n
+
+    def chunks(self, slots, chunks, lengths=None):
+        """A push's audio in the forms `StreamServer.push` takes -> (rows, lengths): rows is a list of 1-D int16 arrays, an
+        (A, n) int16 array or an (A, n) int16 tensor; lengths the int64 sample counts, not yet checked against chunk_size."""
+        A = len(slots)
+        if hasattr(chunks, "is_cuda") or (isinstance(chunks, np.ndarray) and chunks.ndim == 2):
+            if str(chunks.dtype).split(".")[-1] != "int16":
+                raise ValueError("chunks must be int16 PCM (the 1/32768 scaling of buffer_to_audio happens on the device), got %s" % chunks.dtype)
+            if len(chunks.shape) != 2 or chunks.shape[0] != A:
+                raise ValueError("expected an (A, n) array of A = %d chunks, got shape %s" % (A, tuple(chunks.shape)))
+            n = int(chunks.shape[1])
+            if lengths is None:
+                lens = np.full(A, n, np.int64)
+            else:
+                if hasattr(lengths, "is_cuda") and lengths.is_cuda:
+                    raise ValueError("lengths must be host values: the carry bookkeeping reads nothing back from the device")
+                lens = np.asarray(lengths).reshape(-1)
+                if lens.dtype.kind not in "iu" or lens.size != A:
+                    raise ValueError("lengths must give one integer sample count per chunk")
+                lens = lens.astype(np.int64)
+                if lens.size and lens.max() > n:
+                    raise ValueError("a length of %d exceeds the %d samples per row of chunks" % (lens.max(), n))
+            return chunks, lens
+        if lengths is not None:
+            raise ValueError("lengths goes with a padded (A, n) array; a list of chunks carries its own")
+        if len(chunks) != A:
+            raise ValueError("%d slots for %d chunks" % (A, len(chunks)))
+        rows = []
+        for c in chunks:
+            if isinstance(c, (bytes, bytearray, memoryview)):
+                c = np.frombuffer(c, dtype='<i2')                              # buffer_to_audio's view, data_utils.py:19-21
+            else:
+                c = np.asarray(c)
+                if c.dtype != np.int16:
+                    raise ValueError("chunks must be int16 PCM (the 1/32768 scaling of buffer_to_audio happens on the device), got %s" % c.dtype)
+                if c.ndim != 1:
+                    raise ValueError("a chunk is a 1-D array of samples")
+            rows.append(c)
+        return rows, np.array([c.size for c in rows], np.int64)
+
+    def push(self, slots, lengths):
+        """Checks the push, advances the mirror and -> its `RaggedStep`."""
+        s, n = self.check(slots, lengths)
+        W, H = self.window_samples, self.hop_samples
+        reset = self.reset[s]
+        carry = np.where(reset, 0, self.carry[s])
+        first = np.where(reset, 0, self.position[s])
+        L = carry + n
+        n_new = np.where(L < W, 0, (L - W) // H + 1)                           # listen.py:103-105
+        used = n_new * H
+        keep = np.maximum(L - used, 0)                                         # hop > window: the carry empties
+        table = np.zeros((s.size, _l.RAGGED_FIELDS), np.int32)
+        table[:, _l.RAGGED_SLOT], table[:, _l.RAGGED_CARRY], table[:, _l.RAGGED_LEN] = s, carry, n
+        table[:, _l.RAGGED_NEW], table[:, _l.RAGGED_RESET] = n_new, reset
+        self.carry[s], self.position[s], self.reset[s] = keep, first + np.minimum(used, L), False
+        return RaggedStep(table, n_new, keep, first, H)
+
+
+class StreamServer(object):
+    """S independent audio streams ("slots") that need NOT advance together, through update_vectors -> model -> decode -> trigger
+    (listen.py:96-114, 350-375): a push names the slots that have a chunk, each chunk of its own length 1..chunk_size, and
+    only those slots move; every slot has its own sensitivity and trigger level, and slots open and close while others run.
+    The contract is the ragged-streaming block of include/kws.h.  `StreamBatch` is the lockstep form.
+
+    open(sensitivity=None, trigger_level=None) -> slot (the lowest free one; its carry, window and detector restart with its
+    next push); close(slot); push(slots, chunks, lengths=None) -> (index, score, fired), CUDA tensors of length A = len(slots)
+    in the order given (views of buffers the next push overwrites).  Per slot: mfccs (S, F, D), state (S, 2), index, score,
+    fired (S), sensitivity, trigger_level (S), win (S, >= cap) with each slot's carry in front; probs: the last compact (A, C).
+    A push enqueues one table copy, the chunk copy, kws_stream_ragged_append, kws_featurize_long (unless no slot completes a
+    row), kws_stream_ragged_push_rows, the forward pass and kws_stream_ragged_postprocess on the current stream; it reads
+    nothing back and does not wait for the device."""
+
+    def __init__(self, pr, device_model, n_slots, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
+                 decoder=None, featurizer=None, background_index=0, quantized=None):
+        if pr.use_delta:
+            raise ValueError(_NO_DELTAS)
+        torch = _torch()
+        self._L = _l.get_lib()
+        self.pr, self.model, self.quantized = pr, device_model, quantized
+        self.plan = RaggedPlan(n_slots, chunk_size, pr.window_samples, pr.hop_samples, sensitivity, trigger_level)
+        self.S, self.chunk_size, self.cap = self.plan.S, self.plan.chunk_size, self.plan.cap
+        self.background_index = int(background_index)
+        if class_names is not None:
+            assert class_names[0] == 'background', '1st class should be background.'      # listen.py:66
+        self.class_names = class_names
+        self.featurizer = featurizer if featurizer is not None else Featurizer(pr)
+        self.decoder = decoder if decoder is not None else ThresholdDecoder(pr.threshold_config, pr.threshold_center)
+        self.window_samples, self.hop_samples = pr.window_samples, pr.hop_samples
+        self.F, self.D = pr.n_features, pr.n_mfcc
+        S, dev = self.S, device_model.device
+        self._stride = (self.cap + 7) & ~7                                                # rows start on 16 bytes
+        self._max_frames = self.chunk_size // self.hop_samples + 1                        # rows a full buffer of cap samples gives
+        self.win = torch.zeros((S, self._stride), dtype=torch.int16, device=dev)
+        self.mfccs = torch.zeros((S, self.F, self.D), dtype=torch.float32, device=dev)
+        self.state = torch.zeros((S, 2), dtype=torch.int32, device=dev)
+        self.state[:, 1] = -1
+        self.index = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.score = torch.zeros(S, dtype=torch.float64, device=dev)
+        self.fired = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.sensitivity = torch.full((S,), float(sensitivity), dtype=torch.float64, device=dev)
+        self.trigger_level = torch.full((S,), int(trigger_level), dtype=torch.int32, device=dev)
+        self.probs = None
+        # per-push work buffers, sized for a push that names every slot
+        self._table = torch.zeros((S, _l.RAGGED_FIELDS), dtype=torch.int32, device=dev)
+        self._chunks = torch.zeros((S, self._stride), dtype=torch.int16, device=dev)
+        self._act = torch.zeros((S, self._stride), dtype=torch.int16, device=dev)
+        self._act_len = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._rows = torch.zeros(S * self._max_frames * self.D, dtype=torch.float32, device=dev)
+        self._feat = torch.zeros((S, self.F, self.D), dtype=torch.float32, device=dev)
+        self._index = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._score = torch.zeros(S, dtype=torch.float64, device=dev)
+        self._fired = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.launches, self.featurizer_launches = 0, 0                                    # stages enqueued so far (a forward counts as one)
+
+    def open(self, sensitivity=None, trigger_level=None):
+        slot = self.plan.open(sensitivity, trigger_level)
+        self.sensitivity[slot] = float(self.plan.sensitivity[slot])                       # stream-ordered fills, nothing waits
+        self.trigger_level[slot] = int(self.plan.trigger_level[slot])
+        return slot
+
+    def close(self, slot):
+        self.plan.close(slot)
+
+    def _stage_chunks(self, torch, rows, lens):
+        """-> (device pointer, row stride in samples) of the push's audio"""
+        A = len(lens)
+        if hasattr(rows, "is_cuda"):
+            if rows.is_cuda:
+                t = rows.contiguous()                                                     # read in place, stream-ordered
+                return t.data_ptr(), int(t.shape[1])
+            rows = rows.numpy()
+        width = (int(lens.max()) + 7) & ~7
+        pinned = torch.empty((A, width), dtype=torch.int16, pin_memory=True)
+        host = pinned.numpy()
+        if isinstance(rows, np.ndarray):
+            n = min(width, rows.shape[1])
+            host[:, :n] = rows[:, :n]
+        else:
+            for a, c in enumerate(rows):
+                host[a, :c.size] = c
+        d = self._chunks.view(-1)[:A * width].view(A, width)
+        d.copy_(pinned, non_blocking=True)
+        return d.data_ptr(), width
+
+    def push(self, slots, chunks, lengths=None):
+        """One chunk for each of the A distinct open `slots` (any order).  chunks: a list of A `bytes` objects or 1-D int16
+        arrays of their own lengths, or an (A, n) int16 array / CUDA tensor with optional host `lengths`.  ValueError for a
+        duplicate, closed or out-of-range slot, an empty chunk, one longer than chunk_size, or audio that is not int16."""
+        slots = list(slots) if not isinstance(slots, np.ndarray) else slots
+        rows, lens = self.plan.chunks(slots, chunks, lengths)
+        self.plan.check(slots, lens)                                                      # before torch is touched
+        torch = _torch()
+        A = len(lens)
+        if A == 0:
+            self.probs = torch.empty((0, self.quantized.num_classes if self.quantized is not None else self.model.spec.num_classes),
+                                     dtype=torch.float32, device=self.win.device)
+            return self._index[:0], self._score[:0], self._fired[:0]
+        step = self.plan.push(slots, lens)
+        pinned = torch.empty((A, _l.RAGGED_FIELDS), dtype=torch.int32, pin_memory=True)
+        pinned.numpy()[:] = step.table
+        table = self._table[:A]
+        table.copy_(pinned, non_blocking=True)
+        src, src_stride = self._stage_chunks(torch, rows, lens)
+        L, st, mf = self._L, _stream(), step.max_frames
+        _l.check(L.kws_stream_ragged_append(self.win.data_ptr(), self._stride, self.S, self.cap, src, src_stride, table.data_ptr(), A,
+                                            self.chunk_size, self.window_samples, self.hop_samples, self._act.data_ptr(), self._stride,
+                                            self._act_len.data_ptr(), st))
+        if mf > 0:
+            if mf > self._max_frames:
+                raise RuntimeError("a push of %d rows per slot exceeds the %d the buffers hold" % (mf, self._max_frames))
+            _l.check(L.kws_featurize_long(self.featurizer._h, self._act.data_ptr(), _l.WAV_I16, A, self._stride, self._act_len.data_ptr(), mf,
+                                          self._rows.data_ptr(), st))
+        feat = self._feat[:A]
+        _l.check(L.kws_stream_ragged_push_rows(self.mfccs.data_ptr(), self.S, self.F, self.D, self._rows.data_ptr(), mf, table.data_ptr(), A,
+                                               feat.data_ptr(), st))
+        if self.quantized is not None:
+            self.probs, _ = self.quantized.forward(feat)
+        else:
+            self.probs, _ = self.model.forward(feat, want_probs=True, want_argmax=False)
+        _l.check(L.kws_stream_ragged_postprocess(self.decoder.handle, self.probs.data_ptr(), A, self.probs.shape[1], table.data_ptr(), self.S,
+                                                 self.background_index, self.sensitivity.data_ptr(), self.trigger_level.data_ptr(),
+                                                 self.chunk_size, self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),
+                                                 self.fired.data_ptr(), self._index.data_ptr(), self._score.data_ptr(),
+                                                 self._fired.data_ptr(), st))
+        self.launches += 4 + (mf > 0)
+        self.featurizer_launches += mf > 0
+        return self._index[:A], self._score[:A], self._fired[:A]
 
 
 def scan_plan(n_samples, chunk_size, window_samples, hop_samples, n_features):
