@@ -980,6 +980,33 @@ int kws_adam_step(float *params, const float *grads, float *m, float *v, int64_t
 /* Evaluation (eval.py:201-256): counts[label * C + pred] += 1 for every sample of the batch (int32, caller zeroes it). */
 int kws_confusion_counts(const int32_t *labels, const int32_t *pred, int B, int C, int32_t *counts, void *stream);
 
+/* Score statistics of a batch, from which the host derives per-class ROC / DET curves, top-k accuracy and calibration
+ * (kws_amd/metrics.py): one read of probs (B, C) and labels (B), integer counts only.  Every output
+ * ACCUMULATES (the caller zeroes it once and calls per batch), so the result is the same bit for bit whatever the grid, the order of
+ * the atomics or the split into batches.  A sample whose label is outside [0, C) is skipped in all three outputs (callers map an
+ * ignored label to -1).
+ *
+ *   bin of a score p (fp32):  !(p > 0) -> 0 (zero, negatives, NaN);  p >= 1 -> bins - 1;  else min(bins - 1, (int)(p * (float)bins))
+ *   hist[c][1][bin]   samples whose label is c, by their score for c (targets)
+ *   hist[c][0][bin]   samples whose label is another valid class, by their score for c (non-targets)
+ *   rank_counts[r]    samples whose true class y has rank r = #{c : p_c > p_y} + #{c < y : p_c == p_y}: the heads' arg-max takes the
+ *                     first maximum (the lowest index wins a tie), so rank_counts[0] is the trace of kws_confusion_counts over the
+ *                     forward's own arg-max.  A sample with a NaN score anywhere counts at rank C - 1.
+ *   calib[0][bin]     samples by the bin of their largest score (the largest bin of the row: a NaN score counts as bin 0)
+ *   calib[1][bin]     the correct ones among them (rank 0)
+ * rank_counts (C) and calib (2, bins) may be NULL.  B == 0 is a no-op; C >= 1, bins >= 2, else KWS_ERR_INVALID.
+ *
+ * Two counting paths.  While the 2 * C * bins counters of hist fit KWS_SCORE_LDS_BUDGET bytes as int32, every block counts into a
+ * copy in LDS (with calib and rank_counts behind it) and adds its non-zero counters to the int64 arrays once at its end; otherwise
+ * the counts go to global memory with 64-bit atomics (a lane merges a run of counts for one counter into one add).  The budget is 96 KiB: the default evaluation (12 classes, 1024 bins) fits it
+ * exactly, and with the calibration counters behind it (at most half as much again for C >= 2) a block stays inside the 160 KiB
+ * of a compute unit.  One block of 16 waves per compute unit holds it: tiling the classes over blocks instead would make every
+ * block read every row.  kws_score_hist_uses_lds (host only, no device needed) tells which path a shape takes. */
+#define KWS_SCORE_LDS_BUDGET 98304
+int kws_score_hist_uses_lds(int C, int bins);
+int kws_score_hist(const float *probs, const int32_t *labels, int B, int C, int bins, int64_t *hist, int64_t *rank_counts,
+                   int64_t *calib, void *stream);
+
 /* keras SGD(momentum=0) and RMSprop(rho=0.9, momentum=0, epsilon=1e-7, centered=False), model_utils.py:48-51:
  *   sgd:     p -= lr * g
  *   rmsprop: a = rho a + (1-rho) g^2;  p -= lr * g / (sqrt(a) + eps)            with g = grad_scale * grads */

@@ -522,6 +522,24 @@ class KWSModel(object):
     def test_on_batch(self, x, y):
         return self.evaluate(x, y, batch_size=len(x))
 
+    def evaluate_scores(self, x, y, batch_size=4096, bins=1024, quantized=None):
+        """-> kws_amd.metrics.ScoreStats of (x, y) in inference mode: per-class target / non-target score histograms, the rank of the
+        true class and the calibration counts, accumulated on the device with one kernel per batch and no synchronisation (ROC / DET
+        curves, EER, top-k and ECE come from its methods).  x: features or raw audio, as predict takes.  quantized: the
+        QuantizedKWSModel that quantize returned (or its `quantized` member) to score the int8 forward instead of the float one."""
+        from kws_amd.metrics import ScoreStats
+        dm = self._device()
+        q = getattr(quantized, 'quantized', quantized)
+        xd, is_audio = self._to_device_inputs(x)
+        yd = self._labels(y, xd.shape[0])
+        stats = ScoreStats(self.num_classes, bins, device=xd.device)
+        batch_size = int(batch_size or 4096)
+        for i in range(0, xd.shape[0], batch_size):
+            f = self._features_of(xd[i:i + batch_size], is_audio).contiguous()
+            probs = dm.forward(f, True, False)[0] if q is None else q.forward(f)[0]
+            stats.update(probs, yd[i:i + batch_size])
+        return stats
+
     def quantize(self, x_calib=None, method=None, batch_size=None):
         """int8 post-training quantization of a simple_cnn or simple_cnn_lite (what the reference's users do with the MNN quantizer or
         custom_tflite_convert.py --post_training_quantize before deploying): calibrates the quantized tensors (six for simple_cnn,

@@ -3,7 +3,9 @@
 
 The reference predicts one sample at a time through five foreign runtimes and builds the confusion matrix with sklearn
 (eval.py:201-256).  Here the whole set is scored in GPU batches and the confusion counts are accumulated on the device
-(kws_confusion_counts); the printed summary is the reference's: accuracy, then the matrix."""
+(kws_confusion_counts); the printed summary is the reference's: accuracy, then the matrix.  --curves adds what the reference has no
+counterpart for: per-class AUC, equal-error rate and miss rate at a false-accept rate, top-k accuracy and the calibration error, from score
+statistics counted on the device (kws_score_hist, kws_amd.metrics)."""
 import argparse
 import os
 import sys
@@ -71,6 +73,42 @@ def evaluate_int8(model, x, y, class_names, x_calib, calib_samples=1000, method=
     return qmodel, (float(np.trace(cm)) / total if total else 0.0), (float(agree.item()) / total if total else 0.0), cm
 
 
+def print_score_table(stats, class_names, max_far=0.01, top_k=3, title=None, baseline=None):
+    """The per-keyword operating points of a kws_amd.metrics.ScoreStats: one row per class, then top-1..k accuracy and the ECE.
+    baseline: the ScoreStats of another model on the same clips (the float model, for an int8 table): two more columns hold this model's
+    EER and miss rate minus the baseline's."""
+    targets, non_targets = stats.totals()
+    auc = stats.auc()
+    eer, eer_t = stats.eer()
+    far_t, far_miss = stats.at_far(max_far)
+    w = max(8, max(len(c) for c in class_names) + 1)
+    if title:
+        print(title)
+    extra = ['', ''] + [''] * len(class_names)
+    if baseline is not None:
+        d_eer, d_miss = eer - baseline.eer()[0], far_miss - baseline.at_far(max_far)[1]
+        extra = ['%10s%12s' % ('EER-fp32', 'miss-fp32')] + ['%+10.4f%+12.4f' % (d_eer[i], d_miss[i]) for i in range(len(class_names))]
+    print('%*s%9s%12s%9s%9s%9s%12s%12s' % (w, 'class', 'targets', 'non-targets', 'AUC', 'EER', 'EER thr', 'miss@%g' % max_far,
+                                            'thr@%g' % max_far) + extra[0])
+    for i, c in enumerate(class_names):
+        print('%*s%9d%12d%9.4f%9.4f%9.4f%12.4f%12.4f' % (w, c[:w - 1], targets[i], non_targets[i], auc[i], eer[i], eer_t[i], far_miss[i],
+                                                          far_t[i]) + extra[1 + i])
+    print('  '.join('top-%d accuracy %.4f' % (k, stats.top_k(k)) for k in range(1, max(1, min(top_k, len(class_names))) + 1)))
+    print('ECE %.4f (%d confidence bins)' % (stats.ece()[0], stats.bins))
+
+
+def write_curves_csv(path, stats, class_names, tag=None):
+    """class,threshold,tpr,fpr for every class and threshold j / bins (tag: a prefix of the class column, for a second model)"""
+    cv = stats.curves()
+    with open(path, 'w' if tag is None else 'a') as f:
+        if tag is None:
+            f.write('class,threshold,tpr,fpr\n')
+        for i, c in enumerate(class_names):
+            name = c if tag is None else '%s:%s' % (tag, c)
+            for t, tp, fp in zip(cv['thresholds'], cv['tpr'][i], cv['fpr'][i]):
+                f.write('%s,%.10g,%.10g,%.10g\n' % (name, t, tp, fp))
+
+
 def print_confusion_matrix(cm, class_names):
     w = max(8, max(len(c) for c in class_names) + 1)
     print(' ' * w + ''.join('%*s' % (w, c[:w - 1]) for c in class_names))
@@ -97,10 +135,21 @@ def parse_args(argv=None):
                              "tensor ('relu6'), or the ranges of least KL divergence of a second, histogram pass ('kl', the reference's MNN "
                              "recipe); simple_gru / simple_lstm: 'dynamic' (dynamic-range int8, no calibration: their only method)")
     parser.add_argument('--save_quantized', type=str, default=None, help='write the int8 model to this .npz')
+    parser.add_argument('--curves', default=False, action='store_true',
+                        help='also print per-class AUC, equal-error rate and the miss rate at --max_far, top-k accuracy and the expected '
+                             'calibration error (with --int8: for the quantized model as well)')
+    parser.add_argument('--bins', type=int, default=1024, help='score bins of --curves (thresholds j / bins), default=%(default)s')
+    parser.add_argument('--max_far', type=float, default=0.01, help='false-accept rate of the operating point --curves reports, default=%(default)s')
+    parser.add_argument('--top_k', type=int, default=3, help='--curves prints top-1 .. top-k accuracy, default=%(default)s')
+    parser.add_argument('--curves_csv', type=str, default=None, help='with --curves: write class,threshold,tpr,fpr to this file')
     args = parser.parse_args(argv)
     rnn = args.model_type in RNN_TYPES
     if args.rnn_layers != 1 and not rnn:
         parser.error('--rnn_layers %d does not apply to %s: only simple_gru / simple_lstm stack layers' % (args.rnn_layers, args.model_type))
+    if args.bins < 2 or args.top_k < 1 or not 0.0 <= args.max_far <= 1.0:
+        parser.error('--bins must be >= 2, --top_k >= 1 and --max_far within [0, 1]')
+    if args.curves_csv and not args.curves:
+        parser.error('--curves_csv needs --curves')
     if args.int8 and args.quant_method is not None and (args.quant_method == 'dynamic') != rnn:
         parser.error("--quant_method %s does not apply to %s: simple_gru / simple_lstm take 'dynamic' only, the CNNs max, relu6 or kl"
                      % (args.quant_method, args.model_type))
@@ -119,6 +168,11 @@ def main(argv=None):
     acc, cm = evaluate_accuracy(model, x, y, class_names, args.batch_size)
     print('%d correct out of %d samples, accuracy %.4f' % (int(np.trace(cm)), int(cm.sum()), acc))
     print_confusion_matrix(cm, class_names)
+    if args.curves:
+        stats = model.evaluate_scores(x, y, args.batch_size, args.bins)
+        print_score_table(stats, class_names, args.max_far, args.top_k)
+        if args.curves_csv:
+            write_curves_csv(args.curves_csv, stats, class_names)
     if args.int8 and rnn:
         # dynamic-range int8: no calibration, so --calib_path / --calib_samples are not read
         qmodel, acc8, agree, cm8 = evaluate_int8(model, x, y, class_names, None, method='dynamic', batch_size=args.batch_size)
@@ -132,6 +186,11 @@ def main(argv=None):
     if args.int8:
         print('fp32 / int8 argmax agreement %.4f' % agree)
         print_confusion_matrix(cm8, class_names)
+        if args.curves:
+            stats8 = model.evaluate_scores(x, y, args.batch_size, args.bins, quantized=qmodel)
+            print_score_table(stats8, class_names, args.max_far, args.top_k, title='int8:', baseline=stats)
+            if args.curves_csv:
+                write_curves_csv(args.curves_csv, stats8, class_names, tag='int8')
         if args.save_quantized:
             qmodel.save(args.save_quantized)
             print('Saved int8 model {}.'.format(args.save_quantized))
