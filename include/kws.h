@@ -1404,6 +1404,65 @@ int kws_synth_render(const kws_noise_bank *bank, const void *wav, int wav_dtype,
                      const kws_synth_event *events, int max_events, const int32_t *lengths, int R, int64_t max_len, int fade,
                      void *out, int out_dtype, int64_t out_stride, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Transfer to a new keyword set: the activations in front of the last Dense layer ("embeddings") of a frozen backbone, and a
+ * trainer for Dense(E -> C, softmax) heads on them (csrc/kws_transfer.hip).
+ * ---------------------------------------------------------------------- */
+/* Host only: E = 128 for simple_cnn / simple_cnn_lite (dense, after ReLU6), 48 for simple_gru / simple_lstm (the last layer's final
+ * state), whatever num_layers is.  0 for a NULL model. */
+int kws_model_embed_size(const kws_model *m);
+/* emb (B, E) float32: what score_predict reads in inference mode (BatchNormalization moving statistics, no dropout).  Workspace of
+ * kws_model_workspace_bytes(m, B, 0).  Always runs the unfused layer chain at the model's matrix precision: simple_cnn's one-kernel
+ * tail and simple_cnn_lite's fp16 forward never materialise the activation, so the inference precision (KWS_INFER_FP16) is ignored.
+ * Rewrites the weight-derived tables of `ws`: a state prepared there by kws_model_prepare_inference is dropped. */
+int kws_model_embed(kws_model *m, const float *feat, int B, const float *params, const float *state, void *ws, size_t ws_bytes,
+                    float *emb, void *stream);
+
+/* One head to train.  Offsets are in elements of the shared arrays handed to kws_head_fit. */
+typedef struct kws_head_job {
+    int64_t order_offset;        /* first entry of this job's slice of `order`                                            */
+    int64_t weight_offset;       /* first float of this job's kernel (E, C) row-major, followed by its bias (C): Keras Dense
+                                    layout; the same offset addresses the job's optimizer slots                            */
+    int64_t class_weight_offset; /* first of C floats in `class_weights`, or < 0: the plain (clipped) loss                 */
+    int64_t t0;                  /* steps already taken (>= 0): step s of the launch is Adam's t = t0 + s, s = 1 ..        */
+    int32_t n_order;             /* entries of the slice; steps = ceil(n_order / batch); 0: the job is left untouched      */
+    int32_t batch;               /* rows per step; the last step takes the rest and averages over its own size             */
+    int32_t num_classes;         /* 2 .. kws_head_fit_max_classes(E)                                                       */
+    int32_t ignore_index;        /* <= 0: off                                                                              */
+    int32_t optimizer;           /* KWS_OPT_ADAM or KWS_OPT_SGD                                                            */
+    float lr, beta1, beta2, eps; /* Adam: keras defaults are 0.9, 0.999, 1e-7                                              */
+    float momentum;              /* SGD, in [0, 1], no nesterov (the rule above kws_optimizer_step)                        */
+    int32_t reserved[2];         /* 0: the struct is 80 bytes */
+} kws_head_job;
+
+/* Host only: the most classes a head on E-wide embeddings may have (0 for an E kws_head_fit does not take).  The kernel keeps a
+ * job's weights, optimizer slots and gradient sums in registers, 32 elements of the kernel matrix per thread and slot, next to at
+ * most 160 KiB of LDS tiles per block; the smaller of the two bounds is reported: 64 at E = 128. */
+int kws_head_fit_max_classes(int E);
+
+/* Trains J independent heads in ONE launch, one 256-thread block per job, every step of a job inside the block.
+ * emb (N, E) float32 and labels (N) int32 are shared; order holds int32 row numbers into them.  Step s of job j takes the next `batch`
+ * entries of its slice: logits = X W + b, softmax, the loss and dlogits of the train heads (plain: p_y clipped to [1e-7, 1 - 1e-7],
+ * gradient gated by the clip; weighted: unclipped; ignored samples give zero loss and a zero row; the mean runs over every row of
+ * the step), dW = X^T dlogits, db = column sums, then the update: KWS_OPT_ADAM by the formula of kws_adam_step with t = t0 + s,
+ * KWS_OPT_SGD by the rule above kws_optimizer_step (momentum 0: p -= lr g).  All arithmetic is float32, every sum runs in a fixed
+ * order, jobs never interact: the same inputs give the same bits on every run and for every J.
+ *   weights        in: initial value, out: trained                        (addressed by weight_offset, (E + 1) C floats per job)
+ *   slot_m, slot_v in/out optimizer slots in the layout of `weights`: Adam's m and v; SGD with momentum: slot_m is the momentum
+ *                  buffer.  Either may be NULL: the slot then starts at zero and is not stored.
+ *   stats          (J, 2) floats: the sum of the per-sample losses and the number of top-1 hits over all steps of the launch.  A job
+ *                  with n_order == 0 writes nothing at all, its stats included.
+ *   jobs           host array; jobs_dev: device scratch of J * sizeof(kws_head_job) bytes, 8-byte aligned, that the call fills on
+ *                  `stream`.
+ * Checked on the host before any HIP call: KWS_ERR_INVALID for J < 1, N < 1, E not a multiple of 4 in 4 .. 128, a NULL buffer,
+ * batch < 1, num_classes < 2, n_order < 0, negative offsets or t0, a momentum outside [0, 1], a class_weight_offset >= 0 without
+ * class_weights; KWS_ERR_UNSUPPORTED for another optimizer and for num_classes > kws_head_fit_max_classes(E) (the message names the
+ * limit).  The device arrays `order` and `labels` are trusted, as kws_featurize_gather's index: entries of order in [0, N), labels in
+ * [0, num_classes). */
+int kws_head_fit(const float *emb, const int32_t *labels, int64_t N, int E, const int32_t *order, const float *class_weights,
+                 const kws_head_job *jobs, void *jobs_dev, int J, float *weights, float *slot_m, float *slot_v, float *stats,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1714,6 +1714,34 @@ int kws_model_forward(kws_model *m, const float *feat, int B, const float *param
     return m->kind == KWS_SIMPLE_CNN_LITE ? lite_infer(st, probs, argmax) : cnn_infer(st, probs, argmax);
 }
 
+int kws_model_embed_size(const kws_model *m) { return m ? m->head_K : 0; }
+
+// The layer chain up to the activation score_predict reads.  simple_cnn's one-kernel tail and simple_cnn_lite's fp16 forward never write
+// it, so the call plans the unfused tail (a caller that does not take the head's outputs) at the matrix precision and derives the
+// weight planes and BatchNorm coefficients anew: whatever was prepared in this workspace may be in the other layout and is dropped.
+int kws_model_embed(kws_model *m, const float *feat, int B, const float *params, const float *state, void *ws, size_t ws_bytes,
+                    float *emb, void *stream)
+{
+    if (!m || !feat || !params || !state || !emb) return fail(KWS_ERR_INVALID, "null argument");
+    if (B < 1) return fail(KWS_ERR_INVALID, "batch must be >= 1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m->kind == KWS_SIMPLE_GRU || m->kind == KWS_SIMPLE_LSTM) return gru_embed(m, feat, B, params, ws, ws_bytes, emb, s);
+    CnnWs w;
+    if (int rc = check_ws(m, B, false, ws, ws_bytes, w)) return rc;
+    if (m->prep.ws == ws) m->prep = kws_model::Prepared{};
+    const CnnStep st{m, m->d, B, feat, params, const_cast<float *>(state), nullptr, w, s, 0};
+    if (m->kind == KWS_SIMPLE_CNN_LITE) {
+        LiteCtx c{st, false};
+        KWS_TRY(c.forward(false));
+    } else {
+        const CnnPlan plan = plan_cnn(cnn_desc(m), B, matrix_prec(m), false, false, false, false);
+        CnnCtx c{st, nullptr, nullptr, plan, nullptr, nullptr, nullptr, nullptr, nullptr};
+        KWS_TRY(c.forward());
+    }
+    KWS_HIP_CHECK(hipMemcpyAsync(emb, w.d1, sizeof(float) * (size_t)B * 128, hipMemcpyDeviceToDevice, s));
+    return KWS_OK;
+}
+
 int kws_model_train_fwd_bwd(kws_model *m, const kws_train_args *a, void *stream)
 {
     if (!m || !a || !a->feat || !a->labels || !a->params || !a->state || !a->grads) return fail(KWS_ERR_INVALID, "null argument");

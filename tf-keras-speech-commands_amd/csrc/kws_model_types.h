@@ -114,6 +114,7 @@ int run_loss_reduce(const float *loss_i, const float *correct_i, int B, float *s
 size_t gru_workspace_bytes(const kws_model *m, int B, bool training);
 int gru_forward(kws_model *m, const float *feat, int B, const float *params, void *ws, size_t ws_bytes, float *probs,
                 int32_t *argmax, hipStream_t s);
+int gru_embed(kws_model *m, const float *feat, int B, const float *params, void *ws, size_t ws_bytes, float *emb, hipStream_t s);
 int gru_train_fwd_bwd(kws_model *m, const kws_train_args *a, hipStream_t s);
 
 }  // namespace kws

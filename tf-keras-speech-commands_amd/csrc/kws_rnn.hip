@@ -225,6 +225,20 @@ int gru_forward(kws_model *m, const float *feat, int B, const float *params, voi
     return run_head(m, B, params, w.h_last, w.loss_i, w.correct_i, nullptr, nullptr, probs, argmax, nullptr, 0.f, nullptr, 0, s);
 }
 
+// the inference forward without the head: the last layer's final state (B, 48), copied out of the workspace on the same stream
+int gru_embed(kws_model *m, const float *feat, int B, const float *params, void *ws, size_t ws_bytes, float *emb, hipStream_t s)
+{
+    GruWs w;
+    int rc = check(m, B, false, ws, ws_bytes, w);
+    if (rc) return rc;
+    rc = check_tiles(m, false);
+    if (rc) return rc;
+    rc = forward_layers(m, feat, B, params, w, false, 0.f, 0, s);
+    if (rc) return rc;
+    KWS_HIP_CHECK(hipMemcpyAsync(emb, w.h_last, sizeof(float) * (size_t)B * kGruU, hipMemcpyDeviceToDevice, s));
+    return KWS_OK;
+}
+
 int gru_train_fwd_bwd(kws_model *m, const kws_train_args *a, hipStream_t s)
 {
     GruWs w;

@@ -62,6 +62,14 @@ class KwsOptimizerArgs(ctypes.Structure):
                 ("avg_mode", ctypes.c_int32), ("avg_alpha", ctypes.c_float)]
 
 
+class KwsHeadJob(ctypes.Structure):
+    """kws_head_job: one head of a kws_head_fit launch (include/kws.h); 80 bytes"""
+    _fields_ = [("order_offset", ctypes.c_int64), ("weight_offset", ctypes.c_int64), ("class_weight_offset", ctypes.c_int64),
+                ("t0", ctypes.c_int64), ("n_order", ctypes.c_int32), ("batch", ctypes.c_int32), ("num_classes", ctypes.c_int32),
+                ("ignore_index", ctypes.c_int32), ("optimizer", ctypes.c_int32), ("lr", ctypes.c_float), ("beta1", ctypes.c_float),
+                ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("momentum", ctypes.c_float), ("reserved", ctypes.c_int32 * 2)]
+
+
 AUG_MAX_SNR = 16
 AUG_MAX_SNR_DB = 200.0    # kws_augment_plan refuses SNRs outside [-200, 200] dB (include/kws.h)
 
@@ -371,6 +379,10 @@ def get_lib():
     L.kws_vad_gather_clips.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     L.kws_synth_plan.argtypes = [vp, ctypes.POINTER(KwsSynthParams), vp, i32, i32, i64, vp, vp, i32, vp, i32, i32, i64, vp, vp, vp]
     L.kws_synth_render.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, vp, i32, i64, i32, vp, i32, i64, vp]
+    L.kws_model_embed_size.argtypes = [vp]
+    L.kws_model_embed.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp]
+    L.kws_head_fit_max_classes.argtypes = [i32]
+    L.kws_head_fit.argtypes = [vp, vp, i64, i32, vp, vp, ctypes.POINTER(KwsHeadJob), vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

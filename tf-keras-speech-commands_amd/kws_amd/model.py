@@ -255,6 +255,22 @@ class DeviceModel(object):
                                            am.data_ptr() if want_argmax else 0, torch.cuda.current_stream().cuda_stream))
         return probs, am
 
+    @property
+    def embed_size(self):
+        """width of the activation in front of score_predict (kws_model_embed_size): 128 for the CNNs, 48 for the recurrent models"""
+        return int(self._L.kws_model_embed_size(self.spec.handle))
+
+    def embed(self, feat, workspace=None):
+        """kws_model_embed: the (B, embed_size) float32 activations score_predict reads in inference mode.  Drops whatever
+        prepare_inference left in the workspace it runs in."""
+        torch = _torch()
+        B = self._check_feat(feat)
+        ws, nbytes = self._workspace(B, False, workspace)
+        emb = torch.empty((B, self.embed_size), dtype=torch.float32, device=self.device)
+        _l.check(self._L.kws_model_embed(self.spec.handle, feat.data_ptr(), B, self.params.data_ptr(), self.state.data_ptr(), ws, nbytes,
+                                         emb.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        return emb
+
     def train_fwd_bwd(self, feat, labels, class_weights=None, dropout_seed=0, grad_scale=1.0, want_probs=False,
                       ignore_index=0, bucket_event=None, forward_event=None, overlap_event=None, overlap_callback=None,
                       feat_moments=None, comm=None, comm_state_weight=1.0, stats_out=None):

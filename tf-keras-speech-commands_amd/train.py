@@ -22,7 +22,9 @@ step behind the featurizer or the cached features: they work with and without --
 The optimizer takes the Keras options the reference's command line leaves at their defaults: --clipnorm, --global_clipnorm and
 --clipvalue (any optimizer), --momentum (sgd, rmsprop), --nesterov (sgd), --centered (rmsprop) and --amsgrad (adam).
 --average_type wraps the optimizer as the reference's get_averaged_optimizer does: ema and swa keep an average of the weights on the
-GPU, which is what gets validated, checkpointed and written as trained_final; lookahead changes the trained weights themselves."""
+GPU, which is what gets validated, checkpointed and written as trained_final; lookahead changes the trained weights themselves.
+--freeze_backbone (with --weights_path, also a checkpoint of another class count) keeps every layer but the softmax layer fixed and
+trains that layer alone on embeddings computed once, one kernel launch per epoch (kws_amd.transfer; adam or sgd only)."""
 import argparse
 import os
 import sys
@@ -77,6 +79,7 @@ def main(argv=None):
     perturb = perturb_options(args)
     mask = mask_options(args)
     opt_options = optimizer_options(args)
+    freeze_check(args)
 
     # callbacks for training process
     logging = JsonlLogger(os.path.join(log_dir, 'train_log.jsonl'))
@@ -159,7 +162,17 @@ def main(argv=None):
         losses = SparseCategoricalCrossEntropy()
 
     # get train model
-    model = get_model(args.model_type, num_classes, weights_path=args.weights_path, num_layers=args.rnn_layers)
+    if args.freeze_backbone:
+        # the checkpoint may hold another class count: every tensor of matching name and shape is loaded, the head keeps its initial value
+        model = get_model(args.model_type, num_classes, num_layers=args.rnn_layers)
+        model.load_weights(args.weights_path, by_name=True, skip_mismatch=True)
+        # a checkpoint of the same class count also brought its head: training continues from it; otherwise the head starts afresh
+        path = args.weights_path if os.path.exists(args.weights_path) else args.weights_path + '.npz'
+        with np.load(path, allow_pickle=False) as z:
+            head_loaded = 'score_predict/kernel' in z.files and z['score_predict/kernel'].shape == model.get_weights()[-2].shape
+        print('Load backbone weights {} ({}).'.format(args.weights_path, 'with its head' if head_loaded else 'new head'))
+    else:
+        model = get_model(args.model_type, num_classes, weights_path=args.weights_path, num_layers=args.rnn_layers)
     model.compile(optimizer=optimizer, loss=losses, metrics=['accuracy'])
     model.summary()
 
@@ -174,8 +187,14 @@ def main(argv=None):
         fit_kw['validate_averaged'] = True
     if feature_mask is not None:
         fit_kw['feature_mask'] = feature_mask
-    history = model.fit(x_train, y_train, batch_size=args.batch_size, epochs=args.epochs, validation_data=(x_val, y_val),
-                        validation_freq=1, callbacks=callbacks, shuffle=True, verbose=1, **fit_kw)
+    if args.freeze_backbone:
+        # only score_predict trains: embeddings once (or once per epoch under augmentation), one head-fit launch per epoch
+        from kws_amd.transfer import fit_frozen
+        history = fit_frozen(model, x_train, y_train, batch_size=args.batch_size, epochs=args.epochs, validation_data=(x_val, y_val),
+                             callbacks=callbacks, verbose=1, init='model' if head_loaded else None, **fit_kw)
+    else:
+        history = model.fit(x_train, y_train, batch_size=args.batch_size, epochs=args.epochs, validation_data=(x_val, y_val),
+                            validation_freq=1, callbacks=callbacks, shuffle=True, verbose=1, **fit_kw)
 
     # Finally store model
     if averaged:
@@ -201,6 +220,25 @@ def optimizer_options(args):
             raise SystemExit('--%s is an option of %s, not of --optimizer %s' % (name, ' / '.join(kinds), args.optimizer))
         kw[name] = value
     return kw
+
+
+def freeze_check(args):
+    """--freeze_backbone trains score_predict alone (kws_amd.transfer): what its head trainer does not cover is refused here"""
+    if not args.freeze_backbone:
+        return
+    if not args.weights_path:
+        raise SystemExit('--freeze_backbone needs --weights_path: the backbone to freeze')
+    if args.optimizer == 'rmsprop':
+        raise SystemExit('--freeze_backbone trains the head with adam or sgd, not --optimizer rmsprop')
+    for flag in ('clipnorm', 'global_clipnorm', 'clipvalue'):
+        if getattr(args, flag) is not None:
+            raise SystemExit('--freeze_backbone does not clip gradients: drop --%s' % flag)
+    if args.nesterov or args.amsgrad:
+        raise SystemExit('--freeze_backbone trains the head with plain adam or sgd momentum: drop --nesterov / --amsgrad')
+    if args.average_type is not None:
+        raise SystemExit('--freeze_backbone does not average weights: drop --average_type')
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('--freeze_backbone runs on one GPU: it is not data parallel (WORLD_SIZE > 1)')
 
 
 def parse_range(flag, text, lo, hi):
@@ -282,6 +320,11 @@ def parse_args(argv=None):
     parser.add_argument('--weights_path', type=str, required=False, default=None,
                         help="Pretrained model/weights file for fine tune (the file holds no optimizer state: with --average_type the "
                              "average starts from the loaded weights)")
+
+    parser.add_argument('--freeze_backbone', action='store_true',
+                        help="transfer to the classes of --classes_path: load every matching tensor of --weights_path (a checkpoint of another "
+                             "class count works), keep all of it fixed and train only the softmax layer, on embeddings computed once "
+                             "(once per epoch under augmentation). adam or sgd (--momentum) only; no clipping, averaging or data parallelism")
 
     # Data options
     parser.add_argument('--train_data_path', type=str, required=True,
