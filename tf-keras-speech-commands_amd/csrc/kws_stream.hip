@@ -19,6 +19,9 @@
 //   update_vectors (samples)  listen.py:96-105    -> kws_stream_ragged_append (carry + chunk -> compact row, carry shifted in the same kernel)
 //   update_vectors (rows)     listen.py:107-109   -> kws_stream_ragged_push_rows (each slot slides by its own row count)
 //   the prediction loop       listen.py:361-375   -> kws_stream_ragged_postprocess (per-slot sensitivity, trigger level and state)
+// Shared device code: the kernels that step the detector through a recording are one walk, walk_chunks, plus their own few lines
+// (scan_trigger, sweep; collect keeps the loop written out, for speed); the ones that hold chunks against labelled events (sweep,
+// collect, peaks) use one EventMatcher; the lockstep and the ragged sliding window are one pass, slide_window.
 // Everything here is a few bytes per stream and one thread per stream: the kernels are latency-sized, the point of doing
 // them on the device is that probabilities, scores and detector state never leave HBM between the forward pass of one
 // chunk and the next (the whole step can sit in one hipGraph).  Arithmetic is float64 wherever the reference computes
@@ -137,14 +140,13 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float *__restric
     fired[s] = trigger_one(arg, sc, background, sensitivity, level, refractory, state + 2 * (long)s);
 }
 
-// block = one stream: every element is read into a register before the barrier, so the in-place shift has no hazards
-__global__ __launch_bounds__(256) void push_rows_kernel(float *__restrict__ feat, const float *__restrict__ rows, int F, int D,
-                                                         int n_rows, int n_keep)
+// The sliding-window pass of one block of 256 threads: the window f of `total` floats moves left by `shift` and r[0 .. shift) comes
+// in behind it (`reset`: zeros stand for the old window).  Every element of a pass (2048) is read into a register before the barrier,
+// so the in-place shift has no hazards.  `store` writes the window back to f; kCompact writes it a second time, to o.
+template <bool kCompact>
+__device__ __forceinline__ void slide_window(float *__restrict__ f, const float *__restrict__ r, int total, int shift, bool reset, bool store,
+                                             float *__restrict__ o)
 {
-    const int s = blockIdx.x;
-    float *f = feat + (long)s * F * D;
-    const float *r = rows + (long)s * n_rows * D + (long)(n_rows - n_keep) * D;     // the last n_keep new rows
-    const int total = F * D, shift = n_keep * D;
     constexpr int kPer = 8;                                                          // F*D <= 2048 per pass
     for (int base = 0; base < total; base += 256 * kPer) {
         float v[kPer];
@@ -152,16 +154,28 @@ __global__ __launch_bounds__(256) void push_rows_kernel(float *__restrict__ feat
         for (int j = 0; j < kPer; ++j) {
             const int i = base + threadIdx.x + 256 * j;
             v[j] = 0.f;
-            if (i < total) v[j] = i + shift < total ? f[i + shift] : r[i + shift - total];
+            if (i < total) v[j] = i + shift < total ? (reset ? 0.f : f[i + shift]) : r[i + shift - total];
         }
         __syncthreads();     // the reads of this pass precede its writes; later passes only read further right
 #pragma unroll
         for (int j = 0; j < kPer; ++j) {
             const int i = base + threadIdx.x + 256 * j;
-            if (i < total) f[i] = v[j];
+            if (i < total) {
+                if (store) f[i] = v[j];
+                if (kCompact) o[i] = v[j];
+            }
         }
         __syncthreads();
     }
+}
+
+// block = one stream
+__global__ __launch_bounds__(256) void push_rows_kernel(float *__restrict__ feat, const float *__restrict__ rows, int F, int D,
+                                                         int n_rows, int n_keep)
+{
+    const int s = blockIdx.x;
+    const float *r = rows + (long)s * n_rows * D + (long)(n_rows - n_keep) * D;     // the last n_keep new rows
+    slide_window<false>(feat + (long)s * F * D, r, F * D, n_keep * D, false, true, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -217,35 +231,6 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(const float *__restric
     score[r * out_stride + i] = sc;
 }
 
-// block = one wave = one recording: 64 chunks' predictions are loaded at once (one per lane), then walked in order by
-// trigger_one with the state in registers; lane i ends up with the fired flag of chunk base + i
-__global__ __launch_bounds__(64) void scan_trigger_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, int n_chunks,
-                                                          const int32_t *__restrict__ rec_chunks, long k0, int background, double sensitivity,
-                                                          int level, int refractory, long out_stride, int32_t *__restrict__ state,
-                                                          int32_t *__restrict__ fired)
-{
-    const int r = blockIdx.x, lane = threadIdx.x;
-    long live = (long)rec_chunks[r] - k0;                                       // chunks of this tile the recording still has
-    live = live < 0 ? 0 : (live < n_chunks ? live : n_chunks);
-    int32_t st[2] = {state[2 * (long)r], state[2 * (long)r + 1]};
-    for (int base = 0; base < n_chunks; base += 64) {
-        const int i = base + lane;
-        int idx = -1;
-        double sc = 0.0;
-        if (i < live) { idx = index[r * out_stride + i]; sc = score[r * out_stride + i]; }
-        const int n = (int)(live - base < 64 ? (live - base < 0 ? 0 : live - base) : 64);
-        int mine = 0;
-        for (int j = 0; j < n; ++j) {                                             // wave-uniform: every lane carries the same state
-            const int ij = __shfl(idx, j);
-            const double sj = __shfl(sc, j);
-            const int f = trigger_one(ij, sj, background, sensitivity, level, refractory, st);
-            if (j == lane) mine = f;
-        }
-        if (i < n_chunks) fired[r * out_stride + i] = mine;
-    }
-    if (lane == 0) { state[2 * (long)r] = st[0]; state[2 * (long)r + 1] = st[1]; }
-}
-
 // wave-uniform broadcast of lane j's value (j is the same in every lane): v_readlane into scalar registers, no LDS round trip
 __device__ __forceinline__ int lane_value(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
 __device__ __forceinline__ double lane_value(double v, int j)
@@ -253,11 +238,92 @@ __device__ __forceinline__ double lane_value(double v, int j)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
 }
 
+// a chunk count read from device memory, clamped to 0 .. limit: no walk leaves its row, whatever rec_chunks holds
+__device__ __forceinline__ long clamp_chunks(long T, long limit) { return T < 0 ? 0 : (T < limit ? T : limit); }
+
+// The walk over one row of T chunks, by one wave; a kernel that steps the detector through a recording is this plus its own few
+// lines (collect_kernel says why it is not).  64 chunks' (index, score) are loaded at once, one per lane, and step(k, index_k, score_k) runs once per chunk in chunk
+// order with wave-uniform arguments (lane_value); after each group of up to 64 chunks, group(base) runs with the group's first chunk.
+template <typename Step, typename Group>
+__device__ __forceinline__ void walk_chunks(const int32_t *__restrict__ row_index, const double *__restrict__ row_score, long T, Step step,
+                                            Group group)
+{
+    const int lane = threadIdx.x;
+    for (long base = 0; base < T; base += 64) {
+        const long i = base + lane;
+        int idx = -1;
+        double sc = 0.0;
+        if (i < T) { idx = row_index[i]; sc = row_score[i]; }
+        const int n = (int)(T - base < 64 ? T - base : 64);
+        for (int j = 0; j < n; ++j) step((int)base + j, lane_value(idx, j), lane_value(sc, j));
+        group(base);
+    }
+}
+
+// block = one wave = one recording: the walk with the state in registers, the same in every lane; lane i keeps the fired flag of
+// chunk base + i, so each group's flags leave in one coalesced store.  Chunks of the tile past the recording's end get 0.
+__global__ __launch_bounds__(64) void scan_trigger_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, int n_chunks,
+                                                          const int32_t *__restrict__ rec_chunks, long k0, int background, double sensitivity,
+                                                          int level, int refractory, long out_stride, int32_t *__restrict__ state,
+                                                          int32_t *__restrict__ fired)
+{
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const long live = clamp_chunks((long)rec_chunks[r] - k0, n_chunks);         // chunks of this tile the recording still has
+    int32_t st[2] = {state[2 * (long)r], state[2 * (long)r + 1]};
+    int32_t *row_fired = fired + r * out_stride;
+    int mine = 0;
+    walk_chunks(index + r * out_stride, score + r * out_stride, live,
+                [&](int k, int idx, double sc) {
+                    const int f = trigger_one(idx, sc, background, sensitivity, level, refractory, st);
+                    if ((k & 63) == lane) mine = f;
+                },
+                [&](long base) {
+                    if (base + lane < n_chunks) row_fired[base + lane] = mine;
+                    mine = 0;
+                });
+    for (long i = ((live + 63) & ~63L) + lane; i < n_chunks; i += 64) row_fired[i] = 0;
+    if (lane == 0) { state[2 * (long)r] = st[0]; state[2 * (long)r + 1] = st[1]; }
+}
+
+// The labelled events of one recording against the chunks of a walk that only moves forward.  The events are sorted and their chunk
+// ranges lo .. hi disjoint (kws_amd.stream.events_to_chunks), so one cursor serves: e, the first event that does not end before the
+// chunk last asked about.  Without labels (ev_off == nullptr) there are no events; the kernels say what a fire is then.
+struct EventMatcher {
+    const int32_t *cls, *lo, *hi;
+    int begin, end, e;
+    bool labelled, found;                                                       // found: event e already detected
+
+    __device__ __forceinline__ EventMatcher(const int32_t *ev_off, const int32_t *ev_class, const int32_t *ev_lo, const int32_t *ev_hi, int r)
+        : cls(ev_class), lo(ev_lo), hi(ev_hi), labelled(ev_off != nullptr), found(false)
+    {
+        begin = e = labelled ? ev_off[r] : 0;
+        end = labelled ? ev_off[r + 1] : 0;
+    }
+    __device__ __forceinline__ void advance(int k)
+    {
+        while (e < end && hi[e] < k) { e += 1; found = false; }
+    }
+    // after advance(k): chunk k lies in event e's range
+    __device__ __forceinline__ bool inside(int k) const { return e < end && lo[e] <= k; }
+    // A fire of class c at chunk k: the first one inside an event of its class is the hit, later ones are duplicates, and a fire
+    // outside every range, or of the wrong class inside one, is a false alarm.  `event` is the event's position among the
+    // recording's (-1 for a false alarm); the cursor stays on it.
+    __device__ __forceinline__ int classify(int k, int c, int &event)
+    {
+        advance(k);
+        event = -1;
+        if (!inside(k) || cls[e] != c) return KWS_DET_FALSE_ALARM;
+        event = e - begin;
+        if (found) return KWS_DET_DUPLICATE;
+        found = true;
+        return KWS_DET_HIT;
+    }
+};
+
 // Operating-point sweep.  block = one wave = (recording r, 64 operating points): lane l owns point p = 64 blockIdx.y + l and carries
-// ITS detector state, event cursor and counters in registers; the recording's (index, score) are loaded 64 chunks at a time, one per
-// lane, and handed to every lane's walk by lane_value.  A lane with p >= P walks like the others (the loads and broadcasts need the
-// whole wave) with a level no activation count exceeds, and stores nothing.  counts (R, P, 5) = {fires, hits, false alarms,
-// duplicates, sum over hits of (fire chunk - event's first chunk)}; every cell has one writer.
+// ITS detector state, event matcher and counters in registers, all fed by the one walk.  A lane with p >= P walks like the others
+// (the loads and broadcasts need the whole wave) with a level no activation count exceeds, and stores nothing.  counts (R, P, 5) =
+// {fires, hits, false alarms, duplicates, sum over hits of (fire chunk - event's first chunk)}; every cell has one writer.
 __global__ __launch_bounds__(64) void sweep_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, long stride,
                                                    const int32_t *__restrict__ rec_chunks, int background, int refractory,
                                                    const double *__restrict__ sensitivity, const int32_t *__restrict__ trigger_level, int P,
@@ -270,49 +336,35 @@ __global__ __launch_bounds__(64) void sweep_kernel(const int32_t *__restrict__ i
     const bool owner = p < P;
     const double sens = owner ? sensitivity[p] : 0.0;
     const int level = owner ? trigger_level[p] : 0x7fffffff;
-    long T = rec_chunks[r];
-    T = T < 0 ? 0 : (T < stride ? T : stride);                                  // never past the row, whatever rec_chunks holds
-    const bool labelled = ev_off != nullptr;
-    int e = labelled ? ev_off[r] : 0;                                           // cursor: the first event that does not end before the last fire
-    const int e_end = labelled ? ev_off[r + 1] : 0;
-    bool found = false;                                                         // event e already detected by this point
+    EventMatcher events(ev_off, ev_class, ev_lo, ev_hi, r);
     int32_t st[2] = {0, -1};
     int fires = 0, hits = 0, false_alarms = 0, duplicates = 0, latency = 0;
-    for (long base = 0; base < T; base += 64) {
-        const long i = base + lane;
-        int idx = -1;
-        double sc = 0.0;
-        if (i < T) { idx = index[r * stride + i]; sc = score[r * stride + i]; }
-        const int n = (int)(T - base < 64 ? T - base : 64);
-        for (int j = 0; j < n; ++j) {
-            const int ij = lane_value(idx, j);
-            const double sj = lane_value(sc, j);
-            if (!trigger_one(ij, sj, background, sens, level, refractory, st)) continue;
-            fires += 1;
-            if (!labelled) continue;
-            const int k = (int)base + j;
-            while (e < e_end && ev_hi[e] < k) { e += 1; found = false; }
-            if (e < e_end && ev_lo[e] <= k && ev_class[e] == ij) {
-                if (found) {
-                    duplicates += 1;
-                } else {
-                    found = true;
-                    hits += 1;
-                    latency += k - ev_lo[e];
-                }
-            } else {
-                false_alarms += 1;                                              // outside every window, or the wrong class inside one
-            }
+    walk_chunks(index + r * stride, score + r * stride, clamp_chunks(rec_chunks[r], stride), [&](int k, int idx, double sc) {
+        if (!trigger_one(idx, sc, background, sens, level, refractory, st)) return;
+        fires += 1;
+        if (!events.labelled) return;
+        int event;
+        const int kind = events.classify(k, idx, event);
+        if (kind == KWS_DET_HIT) {
+            hits += 1;
+            latency += k - ev_lo[events.e];                                     // the cursor is on the event that was hit
+        } else if (kind == KWS_DET_DUPLICATE) {
+            duplicates += 1;
+        } else {
+            false_alarms += 1;
         }
-    }
+    }, [](long) {});
     if (!owner) return;
     int32_t *out = counts + ((long)r * P + p) * 5;
     out[0] = fires; out[1] = hits; out[2] = false_alarms; out[3] = duplicates; out[4] = latency;
 }
 
-// Activations of one operating point.  block = one wave = one recording: the walk of sweep_kernel with ONE state, so state, event
-// cursor and write position are wave-uniform (scalar registers); lane 0 stores each record, and the whole wave fills the unused
-// slots afterwards.  det (R, max_det, 4) = {chunk, class, kind, event}; the first max_det activations are kept, all are counted.
+// Activations of one operating point.  block = one wave = one recording: the walk with ONE state, so state, event matcher and write
+// position are wave-uniform (scalar registers); lane 0 stores each record, and the whole wave fills the unused slots afterwards.
+// det (R, max_det, 4) = {chunk, class, kind, event}; the first max_det activations are kept, all are counted.
+// The walk is written out here, the one kernel that does not call walk_chunks: with everything in scalar registers the compiler
+// turned the call's step into a per-chunk path with four more register copies, and the kernel measured 3 % slower
+// (profiles/stream_walk_speed.txt).  A change to walk_chunks belongs here too.
 __global__ __launch_bounds__(64) void collect_kernel(const int32_t *__restrict__ index, const double *__restrict__ score, long stride,
                                                      const int32_t *__restrict__ rec_chunks, int background, int refractory, double sensitivity,
                                                      int level, const int32_t *__restrict__ ev_off, const int32_t *__restrict__ ev_class,
@@ -320,18 +372,13 @@ __global__ __launch_bounds__(64) void collect_kernel(const int32_t *__restrict__
                                                      int32_t *__restrict__ n_det, int32_t *__restrict__ det, double *__restrict__ det_score)
 {
     const int r = blockIdx.x, lane = threadIdx.x;
-    long T = rec_chunks[r];
-    T = T < 0 ? 0 : (T < stride ? T : stride);                                  // never past the row, whatever rec_chunks holds
-    const bool labelled = ev_off != nullptr;
-    const int e_begin = labelled ? ev_off[r] : 0;
-    const int e_end = labelled ? ev_off[r + 1] : 0;
-    int e = e_begin;                                                            // cursor: the first event that does not end before the last fire
-    bool found = false;                                                         // event e already detected
+    EventMatcher events(ev_off, ev_class, ev_lo, ev_hi, r);
     int32_t st[2] = {0, -1};
     int n = 0;
     int32_t *out = det + (long)r * max_det * 4;
     double *out_score = det_score + (long)r * max_det;
-    for (long base = 0; base < T; base += 64) {
+    const long T = clamp_chunks(rec_chunks[r], stride);
+    for (long base = 0; base < T; base += 64) {                                 // walk_chunks, written out (see above)
         const long i = base + lane;
         int idx = -1;
         double sc = 0.0;
@@ -343,16 +390,7 @@ __global__ __launch_bounds__(64) void collect_kernel(const int32_t *__restrict__
             if (!trigger_one(ij, sj, background, sensitivity, level, refractory, st)) continue;
             const int k = (int)base + j;
             int kind = KWS_DET_UNLABELLED, event = -1;
-            if (labelled) {
-                while (e < e_end && ev_hi[e] < k) { e += 1; found = false; }
-                if (e < e_end && ev_lo[e] <= k && ev_class[e] == ij) {
-                    kind = found ? KWS_DET_DUPLICATE : KWS_DET_HIT;
-                    found = true;
-                    event = e - e_begin;
-                } else {
-                    kind = KWS_DET_FALSE_ALARM;                                 // outside every window, or the wrong class inside one
-                }
-            }
+            if (events.labelled) kind = events.classify(k, ij, event);
             if (n < max_det && lane == 0) {
                 out[4 * n] = k; out[4 * n + 1] = ij; out[4 * n + 2] = kind; out[4 * n + 3] = event;
                 out_score[n] = sj;
@@ -425,11 +463,8 @@ __global__ __launch_bounds__(64) void peaks_kernel(const int32_t *__restrict__ i
                                                    int32_t *__restrict__ peaks, double *__restrict__ peak_score)
 {
     const int r = blockIdx.x, lane = threadIdx.x;
-    long T = rec_chunks[r];
-    T = T < 0 ? 0 : (T < stride ? T : stride);
-    const bool labelled = ev_off != nullptr;
-    const int e_begin = labelled ? ev_off[r] : 0;
-    const int e_end = labelled ? ev_off[r + 1] : 0;
+    const long T = clamp_chunks(rec_chunks[r], stride);
+    const EventMatcher events(ev_off, nullptr, ev_lo, ev_hi, r);
     const int32_t *row_index = index + r * stride;
     const double *row_score = score + r * stride;
     int32_t *out = peaks + (long)r * K * 2;
@@ -440,7 +475,7 @@ __global__ __launch_bounds__(64) void peaks_kernel(const int32_t *__restrict__ i
         Peak best;
         best.score = -INFINITY;
         best.chunk = kNoPeak;
-        int e = e_begin;                                                        // this lane's event cursor: its chunks ascend
+        EventMatcher mine_events = events;                                      // this lane's cursor, from the start: its chunks ascend
         for (long base = 0; base < T; base += 64) {
             const long k = base + lane;
             double sc = 0.0;
@@ -448,9 +483,9 @@ __global__ __launch_bounds__(64) void peaks_kernel(const int32_t *__restrict__ i
             if (k < T) {
                 sc = row_score[k];
                 cand = row_index[k] != background && sc > min_score && sc > best.score;
-                if (cand && labelled) {                                         // inside an event's window, whatever its class: not a negative
-                    while (e < e_end && ev_hi[e] < k) e += 1;
-                    if (e < e_end && ev_lo[e] <= k) cand = false;
+                if (cand) {                                                     // inside an event's window, whatever its class: not a negative
+                    mine_events.advance((int)k);
+                    if (mine_events.inside((int)k)) cand = false;
                 }
             }
             if (__builtin_amdgcn_ballot_w64(cand) == 0) continue;
@@ -553,8 +588,8 @@ __global__ __launch_bounds__(256) void ragged_append_kernel(short *__restrict__ 
     }
 }
 
-// block = one entry: push_rows_kernel for the entry's slot with the entry's own row count, the updated window written a second
-// time, compact, to feat[a] for the forward pass.  Every element is read before the pass's barrier, as there.
+// block = one entry: push_rows_kernel's pass for the entry's slot with the entry's own row count, the updated window written a second
+// time, compact, to feat[a] for the forward pass.
 __global__ __launch_bounds__(256) void ragged_push_rows_kernel(float *__restrict__ mfccs, int S, int F, int D, const float *__restrict__ rows,
                                                                 int max_frames, const int32_t *__restrict__ table, float *__restrict__ feat)
 {
@@ -567,30 +602,8 @@ __global__ __launch_bounds__(256) void ragged_push_rows_kernel(float *__restrict
     const int n_keep = n_new < F ? n_new : F;
     const bool reset = e[KWS_RAGGED_RESET] != 0;
     const bool store = reset || n_keep > 0;                                     // no new row: the window is only copied
-    float *f = mfccs + (long)slot * F * D;
-    float *o = feat + (long)a * F * D;
     const float *r = rows + ((long)a * max_frames + (n_new - n_keep)) * D;      // the last n_keep new rows
-    const int total = F * D, shift = n_keep * D;
-    constexpr int kPer = 8;                                                     // F*D <= 2048 per pass
-    for (int base = 0; base < total; base += 256 * kPer) {
-        float v[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            const int i = base + threadIdx.x + 256 * j;
-            v[j] = 0.f;
-            if (i < total) v[j] = i + shift < total ? (reset ? 0.f : f[i + shift]) : r[i + shift - total];
-        }
-        __syncthreads();     // the reads of this pass precede its writes; later passes only read further right
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            const int i = base + threadIdx.x + 256 * j;
-            if (i < total) {
-                if (store) f[i] = v[j];
-                o[i] = v[j];
-            }
-        }
-        __syncthreads();
-    }
+    slide_window<true>(mfccs + (long)slot * F * D, r, F * D, n_keep * D, reset, store, feat + (long)a * F * D);
 }
 
 // one thread per entry: postprocess_kernel with the slot's own operating point and state; results go to the entry's place in the
@@ -636,6 +649,23 @@ static int refractory_of(int chunk_size)
     int q = a / chunk_size;
     if ((a % chunk_size != 0) && ((a < 0) != (chunk_size < 0))) --q;
     return q;
+}
+
+// Argument checks that several entry points share: KWS_OK, or the failure as fail() recorded it.
+static int check_ragged_push(int A, int S)
+{
+    return A < 0 || S < 0 || A > S ? fail(KWS_ERR_INVALID, "bad ragged push: A=%d entries for S=%d slots", A, S) : KWS_OK;
+}
+
+static int check_chunk_numbers(int64_t stride)
+{
+    return stride >= 0x7fffffffLL ? fail(KWS_ERR_UNSUPPORTED, "rows of %lld chunks: a chunk number must fit 31 bits", (long long)stride) : KWS_OK;
+}
+
+// `rest`: the event arrays the kernel reads besides ev_off are all there; `names` says which they are
+static int check_events(const int32_t *ev_off, bool rest, const char *names)
+{
+    return ev_off && !rest ? fail(KWS_ERR_INVALID, "null argument: ev_off without %s", names) : KWS_OK;
 }
 
 }  // namespace kws
@@ -798,7 +828,7 @@ int kws_stream_ragged_append(int16_t *win, int64_t win_stride, int S, int cap, c
                              const int32_t *table, int A, int chunk_size, int window_samples, int hop_samples, int16_t *act,
                              int64_t act_stride, int32_t *act_len, void *stream)
 {
-    if (A < 0 || S < 0 || A > S) return fail(KWS_ERR_INVALID, "bad ragged push: A=%d entries for S=%d slots", A, S);
+    if (int rc = check_ragged_push(A, S)) return rc;
     if (chunk_size < 1 || window_samples < 1 || hop_samples < 1)
         return fail(KWS_ERR_INVALID, "bad chunk_size=%d window=%d hop=%d", chunk_size, window_samples, hop_samples);
     if ((int64_t)cap < (int64_t)window_samples + chunk_size)
@@ -823,7 +853,7 @@ int kws_stream_ragged_append(int16_t *win, int64_t win_stride, int S, int cap, c
 int kws_stream_ragged_push_rows(float *mfccs, int S, int F, int D, const float *rows, int max_frames, const int32_t *table, int A,
                                 float *feat, void *stream)
 {
-    if (A < 0 || S < 0 || A > S) return fail(KWS_ERR_INVALID, "bad ragged push: A=%d entries for S=%d slots", A, S);
+    if (int rc = check_ragged_push(A, S)) return rc;
     if (F < 1 || D < 1 || max_frames < 0) return fail(KWS_ERR_INVALID, "bad stream geometry F=%d D=%d max_frames=%d", F, D, max_frames);
     if (A == 0) return KWS_OK;
     if (!mfccs || !table || !feat || (!rows && max_frames > 0)) return fail(KWS_ERR_INVALID, "null argument");
@@ -838,7 +868,7 @@ int kws_stream_ragged_postprocess(const kws_decoder *dec, const float *probs, in
                                   int32_t *slot_index, double *slot_score, int32_t *slot_fired, int32_t *index, double *score, int32_t *fired,
                                   void *stream)
 {
-    if (A < 0 || S < 0 || A > S) return fail(KWS_ERR_INVALID, "bad ragged push: A=%d entries for S=%d slots", A, S);
+    if (int rc = check_ragged_push(A, S)) return rc;
     if (C < 1 || chunk_size < 1) return fail(KWS_ERR_INVALID, "bad C=%d chunk_size=%d", C, chunk_size);
     if (A == 0) return KWS_OK;
     if (!probs || !table || !sensitivity || !trigger_level || !state || !slot_index || !slot_score || !slot_fired || !index || !score || !fired)
@@ -911,11 +941,11 @@ int kws_stream_collect(const int32_t *index, const double *score, int R, int64_t
 {
     if (R < 0 || stride < 0 || chunk_size < 1 || max_det < 0)
         return fail(KWS_ERR_INVALID, "bad R=%d stride=%lld chunk_size=%d max_det=%d", R, (long long)stride, chunk_size, max_det);
-    if (stride >= 0x7fffffffLL) return fail(KWS_ERR_UNSUPPORTED, "rows of %lld chunks: a chunk number must fit 31 bits", (long long)stride);
+    if (int rc = check_chunk_numbers(stride)) return rc;
     if (R == 0) return KWS_OK;
     if (!rec_chunks || !n_det || ((!index || !score) && stride > 0) || ((!det || !det_score) && max_det > 0))
         return fail(KWS_ERR_INVALID, "null argument");
-    if (ev_off && (!ev_class || !ev_lo || !ev_hi)) return fail(KWS_ERR_INVALID, "null argument: ev_off without ev_class / ev_lo / ev_hi");
+    if (int rc = check_events(ev_off, ev_class && ev_lo && ev_hi, "ev_class / ev_lo / ev_hi")) return rc;
     KWS_LAUNCH("collect_kernel", collect_kernel, dim3((unsigned)R), dim3(64), 0, static_cast<hipStream_t>(stream), index, score, (long)stride,
                rec_chunks, background_index, refractory_of(chunk_size), sensitivity, trigger_level, ev_off, ev_class, ev_lo, ev_hi, max_det,
                n_det, det, det_score);
@@ -930,10 +960,10 @@ int kws_stream_peaks(const int32_t *index, const double *score, int R, int64_t s
     if (K < 1 || K > 64) return fail(KWS_ERR_INVALID, "K=%d peaks per recording is outside 1..64", K);
     if (min_gap < 1) return fail(KWS_ERR_INVALID, "min_gap=%d must be at least 1", min_gap);
     if (R < 0 || stride < 0) return fail(KWS_ERR_INVALID, "bad R=%d stride=%lld", R, (long long)stride);
-    if (stride >= 0x7fffffffLL) return fail(KWS_ERR_UNSUPPORTED, "rows of %lld chunks: a chunk number must fit 31 bits", (long long)stride);
+    if (int rc = check_chunk_numbers(stride)) return rc;
     if (R == 0) return KWS_OK;
     if (!rec_chunks || !n_peaks || !peaks || !peak_score || ((!index || !score) && stride > 0)) return fail(KWS_ERR_INVALID, "null argument");
-    if (ev_off && (!ev_lo || !ev_hi)) return fail(KWS_ERR_INVALID, "null argument: ev_off without ev_lo / ev_hi");
+    if (int rc = check_events(ev_off, ev_lo && ev_hi, "ev_lo / ev_hi")) return rc;
     KWS_LAUNCH("peaks_kernel", peaks_kernel, dim3((unsigned)R), dim3(64), 0, static_cast<hipStream_t>(stream), index, score, (long)stride,
                rec_chunks, background_index, min_score, min_gap, ev_off, ev_lo, ev_hi, K, n_peaks, peaks, peak_score);
     KWS_LAUNCH_CHECK("peaks_kernel");

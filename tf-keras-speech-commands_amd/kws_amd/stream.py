@@ -128,7 +128,73 @@ class TriggerDetector(object):
         return bool(self._fired.item())
 
 
-class StreamBatch(object):
+# listen.py:111-112 re-applies add_deltas to the whole matrix on every chunk, which doubles its width and makes the next
+# np.concatenate raise; streaming with deltas never worked in the reference
+_NO_DELTAS = "streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered"
+_NOT_INT16 = "chunks must be int16 PCM (the 1/32768 scaling of buffer_to_audio happens on the device), got %s"
+
+
+def _pcm(chunk):
+    """One chunk of audio as PyAudio / wave.readframes deliver it (bytes, bytearray, memoryview), or an array -> int16 ndarray"""
+    if isinstance(chunk, (bytes, bytearray, memoryview)):
+        return np.frombuffer(chunk, dtype='<i2')                                          # buffer_to_audio's view, data_utils.py:19-21
+    a = np.asarray(chunk)
+    if a.dtype != np.int16:
+        raise ValueError(_NOT_INT16 % a.dtype)
+    return a
+
+
+def _defaults(pr, featurizer, decoder):
+    """-> (featurizer, decoder), the one given or the one `pr` describes"""
+    return (featurizer if featurizer is not None else Featurizer(pr),
+            decoder if decoder is not None else ThresholdDecoder(pr.threshold_config, pr.threshold_center))
+
+
+def _num_classes(device_model, quantized):
+    return quantized.num_classes if quantized is not None else device_model.spec.num_classes
+
+
+def _forward(device_model, quantized, feat):
+    """(N, F, D) features -> (N, C) float32 probabilities, from `quantized`'s int8 forward when there is one, else the model's"""
+    if quantized is not None:
+        return quantized.forward(feat)[0]
+    return device_model.forward(feat, want_probs=True, want_argmax=False)[0]
+
+
+class _Streams(object):
+    """What `StreamBatch` and `StreamServer` share: the refusal of deltas, the model, featurizer and decoder, the geometry, and per
+    stream the feature window (mfccs), the detector state and the last (index, score, fired)."""
+
+    def __init__(self, pr, device_model, quantized):
+        if pr.use_delta:
+            raise ValueError(_NO_DELTAS)
+        _torch()
+        self._L = _l.get_lib()
+        self.pr, self.model, self.quantized = pr, device_model, quantized
+
+    def _allocate(self, n_streams, chunk_size, class_names, decoder, featurizer, background_index):
+        torch = _torch()
+        pr = self.pr
+        self.S, self.chunk_size = n_streams, chunk_size
+        self.background_index = int(background_index)
+        if class_names is not None:
+            assert class_names[0] == 'background', '1st class should be background.'      # listen.py:66
+        self.class_names = class_names
+        self.featurizer, self.decoder = _defaults(pr, featurizer, decoder)
+        self.window_samples, self.hop_samples = pr.window_samples, pr.hop_samples
+        self.F, self.D = pr.n_features, pr.n_mfcc
+        self.cap = self.window_samples + self.chunk_size                                  # a carry and one chunk
+        S, dev = self.S, self.model.device
+        self.mfccs = torch.zeros((S, self.F, self.D), dtype=torch.float32, device=dev)
+        self.state = torch.zeros((S, 2), dtype=torch.int32, device=dev)
+        self.state[:, 1] = -1
+        self.index = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.score = torch.zeros(S, dtype=torch.float64, device=dev)
+        self.fired = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.probs = None
+
+
+class StreamBatch(_Streams):
     """S lock-stepped audio streams through update_vectors -> model -> decode -> trigger (listen.py:96-114, 350-375).
 
     push(chunks) takes one chunk of int16 PCM per stream -- (S, n) int16 array / CUDA tensor, or a list of S `bytes`
@@ -139,34 +205,12 @@ class StreamBatch(object):
 
     def __init__(self, pr, device_model, n_streams, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
                  decoder=None, featurizer=None, background_index=0, quantized=None):
-        torch = _torch()
-        if pr.use_delta:
-            # listen.py:111-112 re-applies add_deltas to the whole matrix on every chunk, which doubles its width and
-            # makes the next np.concatenate raise; streaming with deltas never worked in the reference
-            raise ValueError("streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered")
-        self._L = _l.get_lib()
-        self.pr, self.model, self.quantized = pr, device_model, quantized
-        self.S, self.chunk_size = int(n_streams), int(chunk_size)
+        torch = _torch()                                                                  # a missing device is named first, as `scan` does
+        _Streams.__init__(self, pr, device_model, quantized)
         self.sensitivity, self.trigger_level = float(sensitivity), int(trigger_level)
-        self.background_index = int(background_index)
-        if class_names is not None:
-            assert class_names[0] == 'background', '1st class should be background.'      # listen.py:66
-        self.class_names = class_names
-        self.featurizer = featurizer if featurizer is not None else Featurizer(pr)
-        self.decoder = decoder if decoder is not None else ThresholdDecoder(pr.threshold_config, pr.threshold_center)
-        self.window_samples, self.hop_samples = pr.window_samples, pr.hop_samples
-        self.F, self.D = pr.n_features, pr.n_mfcc
-        dev = device_model.device
-        self.cap = self.window_samples + self.chunk_size
-        self.win = torch.zeros((self.S, self.cap), dtype=torch.int16, device=dev)         # carried + new samples
+        self._allocate(int(n_streams), int(chunk_size), class_names, decoder, featurizer, background_index)
+        self.win = torch.zeros((self.S, self.cap), dtype=torch.int16, device=device_model.device)     # carried + new samples
         self.n_win = 0
-        self.mfccs = torch.zeros((self.S, self.F, self.D), dtype=torch.float32, device=dev)
-        self.state = torch.zeros((self.S, 2), dtype=torch.int32, device=dev)
-        self.state[:, 1] = -1
-        self.index = torch.zeros(self.S, dtype=torch.int32, device=dev)
-        self.score = torch.zeros(self.S, dtype=torch.float64, device=dev)
-        self.fired = torch.zeros(self.S, dtype=torch.int32, device=dev)
-        self.probs = None
 
     def _chunk_tensor(self, chunks):
         torch = _torch()
@@ -174,11 +218,9 @@ class StreamBatch(object):
             t = chunks
         else:
             if isinstance(chunks, (list, tuple)) and chunks and isinstance(chunks[0], (bytes, bytearray, memoryview)):
-                a = np.stack([np.frombuffer(c, dtype='<i2') for c in chunks])             # buffer_to_audio's view, data_utils.py:19-21
+                a = np.stack([_pcm(c) for c in chunks])
             else:
-                a = np.asarray(chunks)
-            if a.dtype != np.int16:
-                raise ValueError("chunks must be int16 PCM (the 1/32768 scaling of buffer_to_audio happens on the device)")
+                a = _pcm(chunks)
             t = torch.from_numpy(np.ascontiguousarray(a))
         if t.dim() != 2 or t.shape[0] != self.S or t.dtype != torch.int16:
             raise ValueError("expected %d int16 chunks of equal length" % self.S)
@@ -205,19 +247,12 @@ class StreamBatch(object):
 
     def push(self, chunks):
         """One step of the loop listen.py:350-375 for every stream."""
-        feats = self.update_vectors(chunks)
-        if self.quantized is not None:
-            self.probs, _ = self.quantized.forward(feats)
-        else:
-            self.probs, _ = self.model.forward(feats, want_probs=True, want_argmax=False)
+        self.probs = _forward(self.model, self.quantized, self.update_vectors(chunks))
         _l.check(self._L.kws_stream_postprocess(self.decoder.handle, self.probs.data_ptr(), self.S, self.probs.shape[1],
                                                 self.background_index, self.sensitivity, self.trigger_level, self.chunk_size,
                                                 self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),
                                                 self.fired.data_ptr(), _stream()))
         return self.index, self.score, self.fired
-
-
-_NO_DELTAS = "streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered"
 
 
 class RaggedStep(object):
@@ -311,8 +346,8 @@ class RaggedPlan(object):
         (A, n) int16 array or an (A, n) int16 tensor; lengths the int64 sample counts, not yet checked against chunk_size."""
         A = len(slots)
         if hasattr(chunks, "is_cuda") or (isinstance(chunks, np.ndarray) and chunks.ndim == 2):
-            if str(chunks.dtype).split(".")[-1] != "int16":
-                raise ValueError("chunks must be int16 PCM (the 1/32768 scaling of buffer_to_audio happens on the device), got %s" % chunks.dtype)
+            if str(chunks.dtype).split(".")[-1] != "int16":                    # numpy's or torch's, without importing torch
+                raise ValueError(_NOT_INT16 % chunks.dtype)
             if len(chunks.shape) != 2 or chunks.shape[0] != A:
                 raise ValueError("expected an (A, n) array of A = %d chunks, got shape %s" % (A, tuple(chunks.shape)))
             n = int(chunks.shape[1])
@@ -334,14 +369,9 @@ class RaggedPlan(object):
             raise ValueError("%d slots for %d chunks" % (A, len(chunks)))
         rows = []
         for c in chunks:
-            if isinstance(c, (bytes, bytearray, memoryview)):
-                c = np.frombuffer(c, dtype='<i2')                              # buffer_to_audio's view, data_utils.py:19-21
-            else:
-                c = np.asarray(c)
-                if c.dtype != np.int16:
-                    raise ValueError("chunks must be int16 PCM (the 1/32768 scaling of buffer_to_audio happens on the device), got %s" % c.dtype)
-                if c.ndim != 1:
-                    raise ValueError("a chunk is a 1-D array of samples")
+            c = _pcm(c)
+            if c.ndim != 1:
+                raise ValueError("a chunk is a 1-D array of samples")
             rows.append(c)
         return rows, np.array([c.size for c in rows], np.int64)
 
@@ -363,7 +393,7 @@ class RaggedPlan(object):
         return RaggedStep(table, n_new, keep, first, H)
 
 
-class StreamServer(object):
+class StreamServer(_Streams):
     """S independent audio streams ("slots") that need NOT advance together, through update_vectors -> model -> decode -> trigger
     (listen.py:96-114, 350-375): a push names the slots that have a chunk, each chunk of its own length 1..chunk_size, and
     only those slots move; every slot has its own sensitivity and trigger level, and slots open and close while others run.
@@ -379,34 +409,16 @@ class StreamServer(object):
 
     def __init__(self, pr, device_model, n_slots, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
                  decoder=None, featurizer=None, background_index=0, quantized=None):
-        if pr.use_delta:
-            raise ValueError(_NO_DELTAS)
+        _Streams.__init__(self, pr, device_model, quantized)
         torch = _torch()
-        self._L = _l.get_lib()
-        self.pr, self.model, self.quantized = pr, device_model, quantized
         self.plan = RaggedPlan(n_slots, chunk_size, pr.window_samples, pr.hop_samples, sensitivity, trigger_level)
-        self.S, self.chunk_size, self.cap = self.plan.S, self.plan.chunk_size, self.plan.cap
-        self.background_index = int(background_index)
-        if class_names is not None:
-            assert class_names[0] == 'background', '1st class should be background.'      # listen.py:66
-        self.class_names = class_names
-        self.featurizer = featurizer if featurizer is not None else Featurizer(pr)
-        self.decoder = decoder if decoder is not None else ThresholdDecoder(pr.threshold_config, pr.threshold_center)
-        self.window_samples, self.hop_samples = pr.window_samples, pr.hop_samples
-        self.F, self.D = pr.n_features, pr.n_mfcc
+        self._allocate(self.plan.S, self.plan.chunk_size, class_names, decoder, featurizer, background_index)
         S, dev = self.S, device_model.device
         self._stride = (self.cap + 7) & ~7                                                # rows start on 16 bytes
         self._max_frames = self.chunk_size // self.hop_samples + 1                        # rows a full buffer of cap samples gives
         self.win = torch.zeros((S, self._stride), dtype=torch.int16, device=dev)
-        self.mfccs = torch.zeros((S, self.F, self.D), dtype=torch.float32, device=dev)
-        self.state = torch.zeros((S, 2), dtype=torch.int32, device=dev)
-        self.state[:, 1] = -1
-        self.index = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.score = torch.zeros(S, dtype=torch.float64, device=dev)
-        self.fired = torch.zeros(S, dtype=torch.int32, device=dev)
         self.sensitivity = torch.full((S,), float(sensitivity), dtype=torch.float64, device=dev)
         self.trigger_level = torch.full((S,), int(trigger_level), dtype=torch.int32, device=dev)
-        self.probs = None
         # per-push work buffers, sized for a push that names every slot
         self._table = torch.zeros((S, _l.RAGGED_FIELDS), dtype=torch.int32, device=dev)
         self._chunks = torch.zeros((S, self._stride), dtype=torch.int16, device=dev)
@@ -459,8 +471,7 @@ class StreamServer(object):
         torch = _torch()
         A = len(lens)
         if A == 0:
-            self.probs = torch.empty((0, self.quantized.num_classes if self.quantized is not None else self.model.spec.num_classes),
-                                     dtype=torch.float32, device=self.win.device)
+            self.probs = torch.empty((0, _num_classes(self.model, self.quantized)), dtype=torch.float32, device=self.win.device)
             return self._index[:0], self._score[:0], self._fired[:0]
         step = self.plan.push(slots, lens)
         pinned = torch.empty((A, _l.RAGGED_FIELDS), dtype=torch.int32, pin_memory=True)
@@ -480,10 +491,7 @@ class StreamServer(object):
         feat = self._feat[:A]
         _l.check(L.kws_stream_ragged_push_rows(self.mfccs.data_ptr(), self.S, self.F, self.D, self._rows.data_ptr(), mf, table.data_ptr(), A,
                                                feat.data_ptr(), st))
-        if self.quantized is not None:
-            self.probs, _ = self.quantized.forward(feat)
-        else:
-            self.probs, _ = self.model.forward(feat, want_probs=True, want_argmax=False)
+        self.probs = _forward(self.model, self.quantized, feat)
         _l.check(L.kws_stream_ragged_postprocess(self.decoder.handle, self.probs.data_ptr(), A, self.probs.shape[1], table.data_ptr(), self.S,
                                                  self.background_index, self.sensitivity.data_ptr(), self.trigger_level.data_ptr(),
                                                  self.chunk_size, self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),
@@ -584,7 +592,7 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     result keeps the packed int16 tensor and the lengths built here (`ScanResult.wav`, `.lengths`)."""
     torch = _torch()
     if pr.use_delta:
-        raise ValueError("streaming with use_delta=True is not usable in the reference (listen.py:111-112) and is not offered")
+        raise ValueError(_NO_DELTAS)
     if class_names is not None:
         assert class_names[0] == 'background', '1st class should be background.'          # listen.py:66
     _check_hop(pr.window_samples, pr.hop_samples)
@@ -593,14 +601,13 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     if chunk_size < 1 or tile < 1:
         raise ValueError("chunk_size and tile must be positive")
     dev = device_model.device
-    featurizer = featurizer if featurizer is not None else Featurizer(pr)
-    decoder = decoder if decoder is not None else ThresholdDecoder(pr.threshold_config, pr.threshold_center)
+    featurizer, decoder = _defaults(pr, featurizer, decoder)
     W, H, F, D = pr.window_samples, pr.hop_samples, pr.n_features, pr.n_mfcc
     wav, lens = _pack_recordings(torch, recordings, lengths, dev)
     R = len(lens)
     n_chunks = [-(-n // chunk_size) for n in lens]
     T_max = max(n_chunks + [0])
-    C = quantized.num_classes if quantized is not None else device_model.spec.num_classes
+    C = _num_classes(device_model, quantized)
     index = torch.empty((R, T_max), dtype=torch.int32, device=dev)
     score = torch.empty((R, T_max), dtype=torch.float64, device=dev)
     fired = torch.empty((R, T_max), dtype=torch.int32, device=dev)
@@ -635,10 +642,7 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
         fv = feat[:R * n]
         timed("gather", lambda: _l.check(L.kws_stream_gather_windows(rows.data_ptr(), R, max_frames, d_len.data_ptr(), chunk_size, W, H, F, D,
                                                                        k0, n, fv.data_ptr(), st)))
-        if quantized is not None:
-            probs = timed("forward", lambda: quantized.forward(fv)[0])
-        else:
-            probs = timed("forward", lambda: device_model.forward(fv, want_probs=True, want_argmax=False)[0])
+        probs = timed("forward", lambda: _forward(device_model, quantized, fv))
         off = k0 * 4
         timed("scan", lambda: _l.check(L.kws_stream_scan_postprocess(decoder.handle, probs.data_ptr(), R, n, C, d_chunks.data_ptr(), k0,
                                                                        int(background_index), float(sensitivity), int(trigger_level), chunk_size,
@@ -747,71 +751,63 @@ def sweep(result, sensitivities, trigger_levels, chunk_size, events=None, length
     stays inside the model's buffer for that long after it ends); None counts fires only.  The decoder is the scan's.
     Returns a `SweepResult`; nothing is synchronised."""
     torch = _torch()
-    if isinstance(result, ScanResult):
-        index, score, n_chunks = result.index, result.score, result.n_chunks
-    else:
-        index, score, n_chunks = result
-    n_chunks = [int(v) for v in n_chunks]
     chunk_size = int(chunk_size)
-    if chunk_size < 1:
-        raise ValueError("chunk_size must be positive")
-    if not (index.is_cuda and score.is_cuda and index.dtype == torch.int32 and score.dtype == torch.float64 and index.dim() == 2
-            and index.shape == score.shape):
-        raise ValueError("index / score must be (R, stride) int32 / float64 CUDA tensors of one shape")
-    R, stride = int(index.shape[0]), int(index.shape[1])
-    if len(n_chunks) != R or any(v < 0 or v > stride for v in n_chunks):
-        raise ValueError("n_chunks must give one chunk count in 0..%d per recording" % stride)
+    scanned = _Scanned(result, chunk_size, events, lengths, tolerance_samples, background_index, pr)
     sens = [float(v) for v in sensitivities]
     levels = [int(v) for v in trigger_levels]
     S, L = len(sens), len(levels)
-    P = S * L
-    dev = index.device
-    index, score = index.contiguous(), score.contiguous()
-    n_events = [0] * R
-    ev = [0, 0, 0, 0]                                              # ev_off, ev_class, ev_lo, ev_hi: NULL without labels
-    if events is not None:
-        rows = _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr)
-        n_events = [len(v) for v in rows]
-        keep = _event_tensors(torch, rows, dev)
-        ev = [t.data_ptr() for t in keep]
+    R, P, dev = scanned.R, S * L, scanned.index.device
     counts = torch.zeros((R, P, 5), dtype=torch.int32, device=dev)
     if R > 0 and P > 0:
-        d_chunks = torch.tensor(n_chunks, dtype=torch.int32).to(dev)
         d_sens = torch.tensor(np.repeat(sens, L), dtype=torch.float64).to(dev)
         d_level = torch.tensor(np.tile(levels, S), dtype=torch.int32).to(dev)
-        _l.check(_l.get_lib().kws_stream_sweep(index.data_ptr(), score.data_ptr(), R, stride, d_chunks.data_ptr(), int(background_index),
-                                               chunk_size, d_sens.data_ptr(), d_level.data_ptr(), P, ev[0], ev[1], ev[2], ev[3],
-                                               counts.data_ptr(), _stream()))
+        ev = scanned.ev
+        _l.check(_l.get_lib().kws_stream_sweep(scanned.index.data_ptr(), scanned.score.data_ptr(), R, scanned.stride,
+                                               scanned.d_chunks.data_ptr(), int(background_index), chunk_size, d_sens.data_ptr(),
+                                               d_level.data_ptr(), P, ev[0], ev[1], ev[2], ev[3], counts.data_ptr(), _stream()))
     f = counts.permute(2, 0, 1).contiguous().view(5, R, S, L)
+    n_events = [0] * R if scanned.rows is None else [len(v) for v in scanned.rows]
     return SweepResult(f[0], f[1], f[2], f[3], f[4], n_events, sens, levels)
 
 
-def _scan_arrays(result, chunk_size):
-    """The checks `collect` and `peaks` share with `sweep`, before any device use -> (index, score, n_chunks, audio)"""
-    import torch
-    audio = None
-    if isinstance(result, ScanResult):
-        index, score, n_chunks = result.index, result.score, result.n_chunks
-        if result.wav is not None:
-            audio = (result.wav, result.lengths)
-    else:
-        index, score, n_chunks = result
-    if int(chunk_size) < 1:
-        raise ValueError("chunk_size must be positive")
-    if not (isinstance(index, torch.Tensor) and isinstance(score, torch.Tensor) and index.dtype == torch.int32
-            and score.dtype == torch.float64 and index.dim() == 2 and index.shape == score.shape):
-        raise ValueError("index / score must be (R, stride) int32 / float64 CUDA tensors of one shape")
-    n_chunks = [int(v) for v in n_chunks]
-    R, stride = int(index.shape[0]), int(index.shape[1])
-    if len(n_chunks) != R or any(v < 0 or v > stride for v in n_chunks):
-        raise ValueError("n_chunks must give one chunk count in 0..%d per recording" % stride)
-    return index, score, n_chunks, audio
+class _Scanned(object):
+    """The opening steps of `sweep`, `collect` and `peaks`: a scan's arrays and the labelled events, checked and on the device.
+    Every check runs on host data alone, the CUDA check last; only then is anything enqueued.
 
+    index, score: the scan's (R, stride) tensors, contiguous; n_chunks: host list, d_chunks: its int32 device copy; rows: per
+    recording the events as [(class, lo, hi), ...] in chunk units, None without labels; ev: the device pointers ev_off, ev_class,
+    ev_lo, ev_hi (a CSR over the recordings; this object keeps their tensors alive), four NULLs without labels; audio: the (packed
+    int16 tensor, lengths) a scan made with keep_audio kept, else None."""
 
-def _on_device(index, score):
-    """the last of the checks: every other one has passed on host data alone"""
-    if not (index.is_cuda and score.is_cuda):
-        raise ValueError("index / score must be (R, stride) int32 / float64 CUDA tensors of one shape")
+    def __init__(self, result, chunk_size, events, lengths, tolerance_samples, background_index, pr):
+        import torch
+        self.audio = None
+        if isinstance(result, ScanResult):
+            index, score, n_chunks = result.index, result.score, result.n_chunks
+            if result.wav is not None:
+                self.audio = (result.wav, result.lengths)
+        else:
+            index, score, n_chunks = result
+        if chunk_size < 1:
+            raise ValueError("chunk_size must be positive")
+        unfit = "index / score must be (R, stride) int32 / float64 CUDA tensors of one shape"
+        if not (isinstance(index, torch.Tensor) and isinstance(score, torch.Tensor) and index.dtype == torch.int32
+                and score.dtype == torch.float64 and index.dim() == 2 and index.shape == score.shape):
+            raise ValueError(unfit)
+        self.n_chunks = [int(v) for v in n_chunks]
+        self.R, self.stride = int(index.shape[0]), int(index.shape[1])
+        if len(self.n_chunks) != self.R or any(v < 0 or v > self.stride for v in self.n_chunks):
+            raise ValueError("n_chunks must give one chunk count in 0..%d per recording" % self.stride)
+        self.rows = None
+        if events is not None:
+            self.rows = _event_rows(events, self.n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr)
+        if not (index.is_cuda and score.is_cuda):                  # the last of the checks: every other one has passed on host data
+            raise ValueError(unfit)
+        dev = index.device
+        self.index, self.score = index.contiguous(), score.contiguous()
+        self.d_chunks = torch.tensor(self.n_chunks, dtype=torch.int32).to(dev)
+        self._keep = [] if self.rows is None else _event_tensors(torch, self.rows, dev)
+        self.ev = [t.data_ptr() for t in self._keep] or [0, 0, 0, 0]
 
 
 def _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr):
@@ -965,25 +961,18 @@ def collect(result, chunk_size, sensitivity=0.5, trigger_level=3, events=None, l
     max_det: slots per recording; the default is the largest count, found by a counting launch (max_det = 0) whose result
     is read back -- the one host synchronisation here.  Returns `Detections` in (recording, chunk) order."""
     chunk_size = int(chunk_size)
-    index, score, n_chunks, audio = _scan_arrays(result, chunk_size)
     if max_det is not None and int(max_det) < 0:
         raise ValueError("max_det must be >= 0")
-    rows = None if events is None else _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr)
-    _on_device(index, score)
+    scanned = _Scanned(result, chunk_size, events, lengths, tolerance_samples, background_index, pr)
     torch = _torch()
     L = _l.get_lib()
-    R, stride = int(index.shape[0]), int(index.shape[1])
-    dev = index.device
-    index, score = index.contiguous(), score.contiguous()
-    keep = None if rows is None else _event_tensors(torch, rows, dev)
-    ev = [0, 0, 0, 0] if keep is None else [t.data_ptr() for t in keep]
-    d_chunks = torch.tensor(n_chunks, dtype=torch.int32).to(dev)
+    R, dev, ev = scanned.R, scanned.index.device, scanned.ev
     n_det = torch.zeros(R, dtype=torch.int32, device=dev)
 
     def launch(cap, det, det_score):
-        _l.check(L.kws_stream_collect(index.data_ptr(), score.data_ptr(), R, stride, d_chunks.data_ptr(), int(background_index), chunk_size,
-                                      float(sensitivity), int(trigger_level), ev[0], ev[1], ev[2], ev[3], cap, n_det.data_ptr(), det,
-                                      det_score, _stream()))
+        _l.check(L.kws_stream_collect(scanned.index.data_ptr(), scanned.score.data_ptr(), R, scanned.stride, scanned.d_chunks.data_ptr(),
+                                      int(background_index), chunk_size, float(sensitivity), int(trigger_level), ev[0], ev[1], ev[2], ev[3],
+                                      cap, n_det.data_ptr(), det, det_score, _stream()))
 
     n = None
     if max_det is None:
@@ -1000,7 +989,7 @@ def collect(result, chunk_size, sensitivity=0.5, trigger_level=3, events=None, l
         n = n_det.cpu().tolist()
     f, rec, sc = _flatten(torch, torch.clamp(n_det, max=cap), det, det_score)
     return Detections(n, rec, f[:, 0].contiguous(), f[:, 1].contiguous(), f[:, 2].contiguous(), f[:, 3].contiguous(), sc, chunk_size,
-                      n_stored=[min(v, cap) for v in n], audio=audio)
+                      n_stored=[min(v, cap) for v in n], audio=scanned.audio)
 
 
 def _check_peaks(k, min_gap):
@@ -1019,28 +1008,21 @@ def peaks(result, chunk_size, k=8, min_score=0.0, min_gap=None, events=None, len
     `Detections` in (recording, pick) order with kind DET_UNLABELLED and event -1; n is read back (one synchronisation)."""
     chunk_size = int(chunk_size)
     _check_peaks(k, min_gap)
-    index, score, n_chunks, audio = _scan_arrays(result, chunk_size)
+    scanned = _Scanned(result, chunk_size, events, lengths, tolerance_samples, background_index, pr)
     if min_gap is None:
         if pr is None:
             from classifier.params import pr
         min_gap = max(1, -(-int(pr.buffer_samples) // chunk_size))
-    rows = None if events is None else _event_rows(events, n_chunks, chunk_size, lengths, tolerance_samples, background_index, pr)
-    _on_device(index, score)
     torch = _torch()
     k, min_gap = int(k), int(min_gap)
-    R, stride = int(index.shape[0]), int(index.shape[1])
-    dev = index.device
-    index, score = index.contiguous(), score.contiguous()
-    keep = None if rows is None else _event_tensors(torch, rows, dev)
-    ev = [0, 0, 0, 0] if keep is None else [t.data_ptr() for t in keep]
-    d_chunks = torch.tensor(n_chunks, dtype=torch.int32).to(dev)
+    R, dev, ev = scanned.R, scanned.index.device, scanned.ev
     n_peaks = torch.zeros(R, dtype=torch.int32, device=dev)
     found = torch.empty((R, k, 2), dtype=torch.int32, device=dev)
     found_score = torch.empty((R, k), dtype=torch.float64, device=dev)
-    _l.check(_l.get_lib().kws_stream_peaks(index.data_ptr(), score.data_ptr(), R, stride, d_chunks.data_ptr(), int(background_index),
-                                           float(min_score), min_gap, ev[0], ev[2], ev[3], k, n_peaks.data_ptr(), found.data_ptr(),
-                                           found_score.data_ptr(), _stream()))
+    _l.check(_l.get_lib().kws_stream_peaks(scanned.index.data_ptr(), scanned.score.data_ptr(), R, scanned.stride, scanned.d_chunks.data_ptr(),
+                                           int(background_index), float(min_score), min_gap, ev[0], ev[2], ev[3], k, n_peaks.data_ptr(),
+                                           found.data_ptr(), found_score.data_ptr(), _stream()))
     n = n_peaks.cpu().tolist()
     f, rec, sc = _flatten(torch, n_peaks, found, found_score)
     chunk = f[:, 0].contiguous()
-    return Detections(n, rec, chunk, f[:, 1].contiguous(), torch.zeros_like(chunk), torch.full_like(chunk, -1), sc, chunk_size, audio=audio)
+    return Detections(n, rec, chunk, f[:, 1].contiguous(), torch.zeros_like(chunk), torch.full_like(chunk, -1), sc, chunk_size, audio=scanned.audio)
