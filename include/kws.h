@@ -1188,6 +1188,74 @@ int kws_stream_ragged_postprocess(const kws_decoder *dec, const float *probs, in
                                   double *score, int32_t *fired, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Sample-rate conversion in front of the detector: a stream or a recording at f_in Hz becomes one at f_out Hz, streaming (state per
+ * stream, any chunking gives the same samples bit for bit) or in one shot.  The reference has no counterpart on the device
+ * (common/data_utils.py load_wav converts one file on the host); this comment is the definition, tests/rate_ref.py restates it.
+ *
+ * Rates f_in, f_out are positive integers; g = gcd(f_in, f_out), p = f_in / g, q = f_out / g, s = min(1, q / p).  Supported pairs
+ * have 1/4 <= p / q <= 4 and a bank of at most KWS_RATE_MAX_BANK_BYTES (q * 2K float32); KWS_ERR_UNSUPPORTED outside either limit.
+ * Z (zero crossings, 4..32), beta and rolloff have the meaning of kws_resampler_create.
+ *   kernel   h(x) = rolloff sinc(rolloff x) kaiser_beta(x / Z) for 0 <= x < Z, 0 from Z on.
+ *   taps     per wing K = Z if p <= q else ceil(Z p / q) = (Z p + q - 1) / q  (tap K would have weight 0 at every phase).
+ *   bank     W, q rows of 2K float32, computed in float64 from the formula and rounded once (no interpolated table):
+ *              W[m][k]     = s h(s (m / q + k))        the left wing,
+ *              W[m][K + k] = s h(s (1 - m / q + k))    the right wing,   k < K,
+ *            the distances formed from the integers m + k q and q - m + k q.
+ *   output n (n = 0, 1, ... since the stream began): n0 = (n p) div q, m = (n p) mod q in 64-bit integers; acc = 0;
+ *              acc = fmaf(W[m][k],     v[n0 - k],     acc)   k = 0 .. K-1, then
+ *              acc = fmaf(W[m][K + k], v[n0 + 1 + k], acc)   k = 0 .. K-1,   float32, in this order;  y[n] = acc.
+ *            v[j] = int16 sample j of the stream / 32768, 0 for j < 0 (the silence in front of the stream).  The int16 sample handed
+ *            on is clamp(rintf(y[n] * 32768), -32768, 32767), rounding half to even.
+ *   streaming  output n is emitted by the push that delivers input sample n0 + K, its rightmost tap: after N input samples in all,
+ *            M(N) = 0 if N <= K else ceil((N - K) q / p) outputs have been emitted; a push of len samples emits
+ *            M(N + len) - M(N) <= ceil(len q / p), so a chunk of at most floor(chunk_size p / q) input samples emits at most
+ *            chunk_size.  The latency is K input samples.  Between pushes a stream keeps its last 2K - 1 input samples and N.
+ *   flush / one shot  a finished stream of N samples gives ceil(N q / p) outputs in all, the taps at j >= N taken as 0; the outputs
+ *            n < M(N) are bit-identical to the streaming ones.
+ *   p == q   K = 0: the samples pass through bit for bit, without latency.
+ * ------------------------------------------------------------------------ */
+typedef struct kws_rate_bank kws_rate_bank;
+enum { KWS_RATE_MAX_BANKS = 16, KWS_RATE_MAX_BANK_BYTES = 1 << 20 };
+
+/* The bank, a HOST object (no device is needed to create or query it; the device copy is made by the first kws_rate_convert on each
+ * device).  KWS_ERR_INVALID: a rate < 1, Z outside [4, 32], beta outside [0, 20], rolloff outside (0, 1]; KWS_ERR_UNSUPPORTED: see above. */
+int kws_rate_bank_create(int f_in, int f_out, int zero_crossings, double beta, double rolloff, kws_rate_bank **out);
+void kws_rate_bank_destroy(kws_rate_bank *bank);
+/* host: p, q and K (each may be NULL) */
+int kws_rate_bank_info(const kws_rate_bank *bank, int *p, int *q, int *taps);
+/* host: W as (q, 2K) float32, row-major (n >= q * 2K); the device holds the same values tap-major, (2K, q) */
+int kws_rate_bank_weights(const kws_rate_bank *bank, float *out, size_t n);
+/* host: emitted = M(N), total = ceil(N q / p) (each may be NULL); 0 <= N <= 2^44 */
+int kws_rate_counts(const kws_rate_bank *bank, int64_t N, int64_t *emitted, int64_t *total);
+
+/* One launch is described by a host-built table of A entries of KWS_RATE_FIELDS int32 each (device memory, copied with the call's
+ * audio).  Entry a: BANK, index into banks; IN_ROW and IN_LEN, its new input samples in[IN_ROW][0 : IN_LEN) (IN_LEN may be 0); N_LO /
+ * N_HI, the low and high words of N, the stream's sample count before this chunk; OUT_ROW, the row of out_i16 / out_f32 it writes, -1 for an
+ * entry that emits nothing and only feeds its history;
+ * FIRST_LO / FIRST_HI, the index n of its first output, and COUNT, how many it writes from column 0 on -- the host computes both with M:
+ * FIRST = M(N), COUNT = M(N + IN_LEN) - M(N), or ceil((N + IN_LEN) q / p) - M(N) for an entry that flushes; HIST_IN, the row of hist
+ * that holds the stream's last 2K - 1 input samples (zeros in front of a shorter stream), -1 for none (zeros); HIST_OUT, the row that
+ * receives them after this chunk (a chunk shorter than 2K - 1 shifts the old ones), -1 for none -- a DIFFERENT row from HIST_IN, since
+ * the blocks of an entry read one while one of them writes the other; FLAGS, KWS_RATE_RESTART takes the history as zeros,
+ * KWS_RATE_FINAL marks the stream's last entry: its COUNT includes the flush and no history is written.  Taps past the chunk's end are
+ * taken as 0 in every entry. */
+enum { KWS_RATE_BANK = 0, KWS_RATE_IN_ROW = 1, KWS_RATE_IN_LEN = 2, KWS_RATE_N_LO = 3, KWS_RATE_N_HI = 4, KWS_RATE_OUT_ROW = 5,
+       KWS_RATE_FIRST_LO = 6, KWS_RATE_FIRST_HI = 7, KWS_RATE_COUNT = 8, KWS_RATE_HIST_IN = 9, KWS_RATE_HIST_OUT = 10,
+       KWS_RATE_FLAGS = 11, KWS_RATE_FIELDS = 12 };
+enum { KWS_RATE_RESTART = 1, KWS_RATE_FINAL = 2 };
+
+/* Convert A entries in one stream-ordered launch: no atomics, no synchronisation, nothing read back (the first use of a bank on a device
+ * uploads it, once).  in (in_rows, in_stride) int16; hist (hist_rows, hist_stride) int16 with hist_stride >= 2K - 1 of every bank, NULL
+ * with hist_rows == 0 when no entry has history; out_i16 and out_f32 (out_rows, out_stride), either may be NULL: row OUT_ROW receives
+ * COUNT samples and zeros from there to out_width <= out_stride (at most 65535 * 512 columns, KWS_ERR_UNSUPPORTED beyond).  Entries
+ * must name distinct OUT_ROWs and distinct HIST_OUT rows.  Arguments are checked on the host before any launch (KWS_ERR_INVALID); the
+ * kernel clamps what it reads from the table to the buffers, so a wrong table gives wrong samples and no access outside them.  Fixed
+ * order of every sum: two calls give the same bits. */
+int kws_rate_convert(const kws_rate_bank *const *banks, int n_banks, const int16_t *in, int64_t in_stride, int in_rows,
+                     const int32_t *table, int A, int16_t *hist, int64_t hist_stride, int hist_rows, int16_t *out_i16, float *out_f32,
+                     int64_t out_stride, int out_rows, int out_width, void *stream);
+
+/* ------------------------------------------------------------------------
  * Offline scan: the loop above over whole recordings that already lie in memory, parallel over time.  It returns per
  * chunk what the chunk loop returns.  With W = window_samples, H = hop_samples, c = chunk_size and N samples:
  *   chunks  T = ceil(N / c); after chunk k (1-based) n_k = min(k c, N) samples have arrived (wave.readframes delivers a short

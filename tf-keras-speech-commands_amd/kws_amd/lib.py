@@ -207,6 +207,11 @@ RAW_F64, RAW_F32 = 0, 1
 VAD_ALIGN = {"left": 0, "center": 1}                                                    # include/kws.h KWS_VAD_ALIGN_*
 DET_UNLABELLED, DET_HIT, DET_DUPLICATE, DET_FALSE_ALARM = 0, 1, 2, 3                     # include/kws.h KWS_DET_*
 RAGGED_SLOT, RAGGED_CARRY, RAGGED_LEN, RAGGED_NEW, RAGGED_RESET, RAGGED_FIELDS = 0, 1, 2, 3, 4, 8   # include/kws.h KWS_RAGGED_*
+# include/kws.h KWS_RATE_*
+(RATE_BANK, RATE_IN_ROW, RATE_IN_LEN, RATE_N_LO, RATE_N_HI, RATE_OUT_ROW, RATE_FIRST_LO, RATE_FIRST_HI, RATE_COUNT, RATE_HIST_IN,
+ RATE_HIST_OUT, RATE_FLAGS, RATE_FIELDS) = range(13)
+RATE_RESTART, RATE_FINAL = 1, 2
+RATE_MAX_BANKS = 16
 
 _lib = None
 
@@ -295,6 +300,13 @@ def get_lib():
     L.kws_stream_ragged_append.argtypes = [vp, i64, i32, i32, vp, i64, vp, i32, i32, i32, i32, vp, i64, vp, vp]
     L.kws_stream_ragged_push_rows.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, fp, vp]
     L.kws_stream_ragged_postprocess.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.kws_rate_bank_create.argtypes = [i32, i32, i32, ctypes.c_double, ctypes.c_double, ctypes.POINTER(vp)]
+    L.kws_rate_bank_destroy.argtypes = [vp]
+    L.kws_rate_bank_destroy.restype = None
+    L.kws_rate_bank_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.kws_rate_bank_weights.argtypes = [vp, vp, ctypes.c_size_t]
+    L.kws_rate_counts.argtypes = [vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.kws_rate_convert.argtypes = [ctypes.POINTER(vp), i32, vp, i64, i32, vp, i32, vp, i64, i32, vp, fp, i64, i32, i32, vp]
     L.kws_stream_gather_windows.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, i32, i64, i32, fp, vp]
     L.kws_stream_scan_postprocess.argtypes = [vp, vp, i32, i32, i32, vp, i64, i32, f64, i32, i32, vp, vp, vp, vp, i64, vp]
     L.kws_stream_sweep.argtypes = [vp, vp, i32, i64, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]

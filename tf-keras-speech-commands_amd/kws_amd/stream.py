@@ -259,10 +259,14 @@ class RaggedStep(object):
     """One push as `RaggedPlan.push` worked it out, entry a for slots[a]: table, the (A, RAGGED_FIELDS) int32 array the kernels
     read (include/kws.h); n_new, rows the push gives the slot; carry, its carry length after the push; first, the position in
     the slot's stream (samples since it was opened) of the first sample of the first new row -- row j covers
-    [first + j * hop, first + j * hop + window); max_frames = max(n_new), 0 for an empty push."""
+    [first + j * hop, first + j * hop + window); max_frames = max(n_new), 0 for an empty push.
+    A push that names a slot with a sample rate of its own also has rate, the (pushed entries, RATE_FIELDS) int32 table of
+    kws_rate_convert (None otherwise); emitted, per pushed entry the samples it gives the detector; and entries, the positions in the
+    push of the entries that emit at least one: the ragged table, n_new, carry and first describe those alone, in converted samples."""
 
-    def __init__(self, table, n_new, carry, first, hop_samples):
+    def __init__(self, table, n_new, carry, first, hop_samples, rate=None, emitted=None, entries=None):
         self.table, self.n_new, self.carry, self.first, self.hop_samples = table, n_new, carry, first, hop_samples
+        self.rate, self.emitted, self.entries = rate, emitted, entries
         self.A = int(table.shape[0])
         self.max_frames = int(n_new.max()) if self.A else 0
 
@@ -273,9 +277,22 @@ class RaggedStep(object):
 class RaggedPlan(object):
     """The host's half of `StreamServer`: which slots are open, each slot's carry length (a mirror of what the device holds,
     kept with the arithmetic of listen.py:96-105, so nothing is ever read back), its operating point, the restart a freshly
-    opened slot still owes, and the checks of a push's arguments.  numpy only, no device."""
+    opened slot still owes, and the checks of a push's arguments.  numpy only, no device.
 
-    def __init__(self, n_slots, chunk_size, window_samples, hop_samples, sensitivity=0.5, trigger_level=3):
+    With `sample_rate` (the detector's) a slot may be opened at a rate of its own: the plan then keeps its `RateBank` (`bank[slot]`, None
+    for a slot at the detector's rate; `banks` lists the distinct ones, `banks[0]` the pass-through), the samples it has received
+    (`received[slot]`, the N of include/kws.h's rate-conversion block; `sent[slot]` = M(N), what it has emitted), its longest push (`max_chunk[slot]`) and which of its two
+    history rows is current (`parity[slot]`); chunk lengths of such a slot are in ITS samples, carry and position in converted ones."""
+
+    def __init__(self, n_slots, chunk_size, window_samples, hop_samples, sensitivity=0.5, trigger_level=3, sample_rate=None):
+        self.sample_rate = None if sample_rate is None else int(sample_rate)
+        self.banks, self.bank, self.bank_index = [], [None] * int(n_slots), np.zeros(int(n_slots), np.int64)
+        self.received = np.zeros(int(n_slots), np.int64)
+        self.sent = np.zeros(int(n_slots), np.int64)           # M(received): samples the slot's converter has emitted
+        self._pqk = np.tile(np.array([[1], [1], [0]], np.int64), (1, int(n_slots)))    # the bank's p, q, K per slot; 1, 1, 0 passes through
+        self.parity = np.zeros(int(n_slots), np.int64)
+        self.rate_reset = np.zeros(int(n_slots), bool)
+        self.max_chunk = np.full(int(n_slots), int(chunk_size), np.int64)
         self.S, self.chunk_size = int(n_slots), int(chunk_size)
         self.window_samples, self.hop_samples = int(window_samples), int(hop_samples)
         if self.S < 0 or self.chunk_size < 1 or self.window_samples < 1 or self.hop_samples < 1:
@@ -289,12 +306,33 @@ class RaggedPlan(object):
         self.sensitivity = np.full(self.S, self.default_sensitivity, np.float64)
         self.trigger_level = np.full(self.S, self.default_trigger_level, np.int32)
 
-    def open(self, sensitivity=None, trigger_level=None):
-        """-> the lowest free slot, marked for a restart that rides in its next push"""
+    def _bank(self, sample_rate):
+        """-> (bank, its index in `banks`) of a slot at sample_rate, (None, 0) at the detector's own rate"""
+        if sample_rate is None or (self.sample_rate is not None and int(sample_rate) == self.sample_rate):
+            return None, 0
+        if self.sample_rate is None:
+            raise ValueError("a slot with a sample_rate of its own needs a plan made with the detector's sample_rate")
+        from .rate import bank_for
+        bank = bank_for(sample_rate, self.sample_rate)                         # ValueError for a pair the library refuses
+        if not self.banks:
+            self.banks.append(bank_for(self.sample_rate, self.sample_rate))
+        if bank not in self.banks:
+            if len(self.banks) == _l.RATE_MAX_BANKS:
+                raise ValueError("a server converts from at most %d distinct sample rates" % (_l.RATE_MAX_BANKS - 1))
+            self.banks.append(bank)
+        return bank, self.banks.index(bank)
+
+    def open(self, sensitivity=None, trigger_level=None, sample_rate=None):
+        """-> the lowest free slot, marked for a restart that rides in its next push.  sample_rate: the rate its audio arrives at,
+        None for the detector's."""
+        bank, which = self._bank(sample_rate)
         free = np.flatnonzero(~self.is_open)
         if free.size == 0:
             raise RuntimeError("the server is full: all %d slots are open" % self.S)
         slot = int(free[0])
+        self.bank[slot], self.bank_index[slot], self.received[slot], self.rate_reset[slot] = bank, which, 0, bank is not None
+        self.sent[slot], self._pqk[:, slot] = 0, (1, 1, 0) if bank is None else (bank.p, bank.q, bank.taps)
+        self.max_chunk[slot] = self.chunk_size if bank is None else bank.max_chunk(self.chunk_size)
         self.is_open[slot], self.reset[slot] = True, True
         self.carry[slot] = self.position[slot] = 0
         self.sensitivity[slot] = self.default_sensitivity if sensitivity is None else float(sensitivity)
@@ -336,9 +374,13 @@ class RaggedPlan(object):
         bad = np.flatnonzero(n < 1)
         if bad.size:
             raise ValueError("the chunk for slot %d is empty" % s[bad[0]])
-        bad = np.flatnonzero(n > self.chunk_size)
+        bad = np.flatnonzero(n > (self.max_chunk[s] if self.banks else self.chunk_size))    # no gather while every slot is native
         if bad.size:
-            raise ValueError("chunk of %d samples for slot %d exceeds chunk_size=%d" % (n[bad[0]], s[bad[0]], self.chunk_size))
+            b = bad[0]
+            if self.bank[s[b]] is None:
+                raise ValueError("chunk of %d samples for slot %d exceeds chunk_size=%d" % (n[b], s[b], self.chunk_size))
+            raise ValueError("chunk of %d samples for slot %d exceeds its max_chunk=%d: at %d Hz a longer one could give the detector more "
+                             "than chunk_size=%d samples" % (n[b], s[b], self.max_chunk[s[b]], self.bank[s[b]].f_in, self.chunk_size))
         return s, n
 
     def chunks(self, slots, chunks, lengths=None):
@@ -378,6 +420,35 @@ class RaggedPlan(object):
     def push(self, slots, lengths):
         """Checks the push, advances the mirror and -> its `RaggedStep`."""
         s, n = self.check(slots, lengths)
+        which = self.bank_index[s] if self.banks else None
+        if which is None or not which.any():
+            return self._advance(s, n)
+        # some slot arrives at a rate of its own: every entry goes through kws_rate_convert (banks[0] passes the others through), which
+        # packs the rows of those that emit a sample; only they reach the detector
+        from .rate import rate_table
+        conv = which > 0
+        fresh = conv & self.rate_reset[s]
+        going = conv & ~fresh
+        before, first_out = np.where(going, self.received[s], 0), np.where(going, self.sent[s], 0)
+        p, q, k = self._pqk[0][s], self._pqk[1][s], self._pqk[2][s]
+        after = before + n
+        sent = np.where(after <= k, 0, -((-(after - k) * q) // p))               # M(N + len); the pass-through's is len
+        emitted = sent - first_out
+        kept = np.flatnonzero(emitted > 0)
+        out_row = np.full(s.size, -1, np.int64)
+        out_row[kept] = np.arange(kept.size)
+        row = 2 * s + self.parity[s]
+        rate = rate_table(which, np.arange(s.size), n, before, out_row, first_out, emitted, np.where(conv, row, -1),
+                          np.where(conv, row ^ 1, -1), np.where(fresh, _l.RATE_RESTART, 0))
+        c = s[conv]
+        self.received[c], self.sent[c], self.rate_reset[c] = after[conv], sent[conv], False
+        self.parity[c] ^= 1
+        step = self._advance(s[kept], emitted[kept])
+        step.rate, step.emitted, step.entries = rate, emitted, kept
+        return step
+
+    def _advance(self, s, n):
+        """The carry arithmetic of listen.py:96-105 for chunks of n samples at the detector's rate in the slots s"""
         W, H = self.window_samples, self.hop_samples
         reset = self.reset[s]
         carry = np.where(reset, 0, self.carry[s])
@@ -405,13 +476,24 @@ class StreamServer(_Streams):
     fired (S), sensitivity, trigger_level (S), win (S, >= cap) with each slot's carry in front; probs: the last compact (A, C).
     A push enqueues one table copy, the chunk copy, kws_stream_ragged_append, kws_featurize_long (unless no slot completes a
     row), kws_stream_ragged_push_rows, the forward pass and kws_stream_ragged_postprocess on the current stream; it reads
-    nothing back and does not wait for the device."""
+    nothing back and does not wait for the device.
+
+    open(..., sample_rate=f) takes the slot's audio at f Hz instead of pr.sample_rate (kws_amd.rate.RateBank says which pairs are
+    supported); its chunks may then hold up to plan.max_chunk[slot] = floor(chunk_size f / pr.sample_rate) samples.  A push that names
+    such a slot enqueues kws_rate_convert in front of the append -- one more launch, and the push's audio goes to a buffer of its own
+    first -- which converts with the state the slot keeps between pushes (the converter block of include/kws.h: the same samples
+    however the stream is cut) and hands the rest of the push the converted chunks.  An entry whose chunk yields no converted sample
+    (the first K input samples of a stream, a tiny chunk at 48 kHz) gets no prediction: its place in the returned tensors holds the
+    slot's previous index and score with fired = 0, and probs has a row only for the entries that took part.  A push that names
+    only slots at pr.sample_rate runs the sequence above unchanged."""
 
     def __init__(self, pr, device_model, n_slots, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
                  decoder=None, featurizer=None, background_index=0, quantized=None):
         _Streams.__init__(self, pr, device_model, quantized)
         torch = _torch()
-        self.plan = RaggedPlan(n_slots, chunk_size, pr.window_samples, pr.hop_samples, sensitivity, trigger_level)
+        self.plan = RaggedPlan(n_slots, chunk_size, pr.window_samples, pr.hop_samples, sensitivity, trigger_level,
+                               sample_rate=pr.sample_rate)
+        self._hist = self._raw = self._rate_table = None                                  # made when a slot opens at a rate of its own
         self._allocate(self.plan.S, self.plan.chunk_size, class_names, decoder, featurizer, background_index)
         S, dev = self.S, device_model.device
         self._stride = (self.cap + 7) & ~7                                                # rows start on 16 bytes
@@ -431,8 +513,14 @@ class StreamServer(_Streams):
         self._fired = torch.zeros(S, dtype=torch.int32, device=dev)
         self.launches, self.featurizer_launches = 0, 0                                    # stages enqueued so far (a forward counts as one)
 
-    def open(self, sensitivity=None, trigger_level=None):
-        slot = self.plan.open(sensitivity, trigger_level)
+    def open(self, sensitivity=None, trigger_level=None, sample_rate=None):
+        slot = self.plan.open(sensitivity, trigger_level, sample_rate)
+        if self.plan.bank[slot] is not None and self._hist is None:
+            torch, dev = _torch(), self.win.device
+            # two history rows per slot (one read, one written, by turns); 2K - 1 <= 8 Z - 1 samples for every supported pair at Z = 16
+            self._hist = torch.zeros((2 * self.S, 128), dtype=torch.int16, device=dev)
+            self._rate_table = torch.zeros((self.S, _l.RATE_FIELDS), dtype=torch.int32, device=dev)
+            self._gather = torch.zeros((2, self.S), dtype=torch.int64, device=dev)
         self.sensitivity[slot] = float(self.plan.sensitivity[slot])                       # stream-ordered fills, nothing waits
         self.trigger_level[slot] = int(self.plan.trigger_level[slot])
         return slot
@@ -440,15 +528,18 @@ class StreamServer(_Streams):
     def close(self, slot):
         self.plan.close(slot)
 
-    def _stage_chunks(self, torch, rows, lens):
-        """-> (device pointer, row stride in samples) of the push's audio"""
+    def _stage_chunks(self, torch, rows, lens, raw=False):
+        """-> (device pointer, row stride in samples) of the push's audio; raw: (the (A, stride) device tensor) of audio that is still
+        to be converted, in a buffer of its own that grows with the longest push"""
         A = len(lens)
         if hasattr(rows, "is_cuda"):
             if rows.is_cuda:
                 t = rows.contiguous()                                                     # read in place, stream-ordered
-                return t.data_ptr(), int(t.shape[1])
+                return t if raw else (t.data_ptr(), int(t.shape[1]))
             rows = rows.numpy()
         width = (int(lens.max()) + 7) & ~7
+        if raw and (self._raw is None or self._raw.numel() < A * width):
+            self._raw = torch.empty(A * width, dtype=torch.int16, device=self.win.device)
         pinned = torch.empty((A, width), dtype=torch.int16, pin_memory=True)
         host = pinned.numpy()
         if isinstance(rows, np.ndarray):
@@ -457,9 +548,9 @@ class StreamServer(_Streams):
         else:
             for a, c in enumerate(rows):
                 host[a, :c.size] = c
-        d = self._chunks.view(-1)[:A * width].view(A, width)
+        d = (self._raw if raw else self._chunks.view(-1))[:A * width].view(A, width)
         d.copy_(pinned, non_blocking=True)
-        return d.data_ptr(), width
+        return d if raw else (d.data_ptr(), width)
 
     def push(self, slots, chunks, lengths=None):
         """One chunk for each of the A distinct open `slots` (any order).  chunks: a list of A `bytes` objects or 1-D int16
@@ -474,11 +565,45 @@ class StreamServer(_Streams):
             self.probs = torch.empty((0, _num_classes(self.model, self.quantized)), dtype=torch.float32, device=self.win.device)
             return self._index[:0], self._score[:0], self._fired[:0]
         step = self.plan.push(slots, lens)
+        if step.rate is not None:
+            return self._push_converted(torch, step, slots, rows, lens)
+        self._detect(torch, step, lambda: self._stage_chunks(torch, rows, lens))
+        return self._index[:A], self._score[:A], self._fired[:A]
+
+    def _push_converted(self, torch, step, slots, rows, lens):
+        """A push that names a slot at a rate of its own: kws_rate_convert turns every entry's audio into the detector's (the slots
+        already at its rate pass through bit for bit) and packs the rows of those that emit a sample into the buffer
+        kws_stream_ragged_append reads; the rest of the push runs on them alone."""
+        from .rate import launch
+        A, kept = len(lens), step.entries
+        pinned = torch.empty((A, _l.RATE_FIELDS), dtype=torch.int32, pin_memory=True)
+        pinned.numpy()[:] = step.rate
+        self._rate_table[:A].copy_(pinned, non_blocking=True)
+        raw = self._stage_chunks(torch, rows, lens, raw=True)
+        launch(self.plan.banks, raw, self._rate_table, A, out_i16=self._chunks, out_width=int(step.emitted.max()), hist=self._hist)
+        self.launches += 1
+        if kept.size:
+            self._detect(torch, step, lambda: (self._chunks.data_ptr(), self._stride))
+        else:
+            self.probs = torch.empty((0, _num_classes(self.model, self.quantized)), dtype=torch.float32, device=self.win.device)
+        if kept.size == A:
+            return self._index[:A], self._score[:A], self._fired[:A]
+        # an entry that emitted nothing was not predicted on: its place holds the slot's previous index and score, fired = 0
+        pinned = torch.empty((2, A), dtype=torch.int64, pin_memory=True)
+        pinned.numpy()[0], pinned.numpy()[1] = np.asarray(slots, np.int64), step.emitted > 0
+        g = self._gather.view(-1)[:2 * A].view(2, A)
+        g.copy_(pinned, non_blocking=True)
+        return (self.index.index_select(0, g[0]), self.score.index_select(0, g[0]),
+                (self.fired.index_select(0, g[0]) * g[1]).to(torch.int32))
+
+    def _detect(self, torch, step, stage):
+        """The push from its ragged table on, for the step's A entries; stage() -> (device pointer, row stride) of their audio"""
+        A = step.A
         pinned = torch.empty((A, _l.RAGGED_FIELDS), dtype=torch.int32, pin_memory=True)
         pinned.numpy()[:] = step.table
         table = self._table[:A]
         table.copy_(pinned, non_blocking=True)
-        src, src_stride = self._stage_chunks(torch, rows, lens)
+        src, src_stride = stage()
         L, st, mf = self._L, _stream(), step.max_frames
         _l.check(L.kws_stream_ragged_append(self.win.data_ptr(), self._stride, self.S, self.cap, src, src_stride, table.data_ptr(), A,
                                             self.chunk_size, self.window_samples, self.hop_samples, self._act.data_ptr(), self._stride,
@@ -499,7 +624,6 @@ class StreamServer(_Streams):
                                                  self._fired.data_ptr(), st))
         self.launches += 4 + (mf > 0)
         self.featurizer_launches += mf > 0
-        return self._index[:A], self._score[:A], self._fired[:A]
 
 
 def scan_plan(n_samples, chunk_size, window_samples, hop_samples, n_features):
@@ -579,7 +703,7 @@ def _pack_recordings(torch, recordings, lengths, device):
 
 def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
          decoder=None, featurizer=None, background_index=0, quantized=None, tile=4096, return_probs=False, timings=None,
-         keep_audio=False):
+         keep_audio=False, sample_rates=None):
     """The chunk loop of `StreamBatch` over R whole recordings at once: for every chunk of every recording the (index,
     score, fired) that `push` would have returned for it, and the final detector state, as a `ScanResult`.
 
@@ -589,7 +713,9 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     kws_stream_scan_postprocess, which carries the detector state from tile to tile.  Everything is enqueued on the
     current stream; the host does not wait for the device.  `timings`: an optional dict that receives lists of
     (start, end) CUDA event pairs per stage ("rows", "gather", "forward", "scan") for tools/scanbench.py.  keep_audio: the
-    result keeps the packed int16 tensor and the lengths built here (`ScanResult.wav`, `.lengths`)."""
+    result keeps the packed int16 tensor and the lengths built here (`ScanResult.wav`, `.lengths`).  sample_rates: the rate of the
+    recordings in Hz, one for all or one each; those not at pr.sample_rate are first converted to it by one kws_amd.rate.convert
+    call, and chunks, lengths, events and times are then in converted samples (None: all are at pr.sample_rate)."""
     torch = _torch()
     if pr.use_delta:
         raise ValueError(_NO_DELTAS)
@@ -603,6 +729,9 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     dev = device_model.device
     featurizer, decoder = _defaults(pr, featurizer, decoder)
     W, H, F, D = pr.window_samples, pr.hop_samples, pr.n_features, pr.n_mfcc
+    if sample_rates is not None and np.any(np.asarray(sample_rates) != pr.sample_rate):
+        from .rate import convert
+        recordings, lengths = convert(recordings, sample_rates, pr.sample_rate, lengths=lengths, device=dev)
     wav, lens = _pack_recordings(torch, recordings, lengths, dev)
     R = len(lens)
     n_chunks = [-(-n // chunk_size) for n in lens]

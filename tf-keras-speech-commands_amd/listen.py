@@ -54,6 +54,7 @@ default_config = {                                     # listen.py:31-40
     "input_wav": None,
     "scan": False,
     "scan_tile": 4096,
+    "resample": False,
 }
 
 
@@ -213,9 +214,29 @@ class Listener(object):
     def run_microphone(self):
         raise RuntimeError("PyAudio is not available in this image; feed chunks with Listener.step() or use run_wav()")
 
+    def _run_converted(self, rate, quiet):
+        """run_wav of a file at another rate (resample=True): the file is converted at once (kws_amd.rate.convert), then walked
+        chunk by chunk like any other; chunks and the saved buffer are in converted samples."""
+        from kws_amd.rate import convert
+        out, lens = convert([self._read_wav(self.input_wav, with_rate=True)[0]], rate, self.pr.sample_rate)
+        pcm = out[0, :lens[0]].cpu().numpy()
+        results = []
+        for k in range(0, pcm.size, self.chunk_size):
+            index, score, fired = self.step(pcm[k:k + self.chunk_size].tobytes())
+            if not quiet:
+                self.on_prediction(index, score)
+            if fired:
+                self.on_activation(index, play_activate=False)
+            results.append((index, score, fired))
+        return results
+
     def run_wav(self, quiet=False):
         wf = wave.open(self.input_wav, 'rb')
         assert wf.getnchannels() == 1, 'input wav channels mismatch'
+        if self.resample and wf.getframerate() != self.pr.sample_rate:
+            rate = wf.getframerate()
+            wf.close()
+            return self._run_converted(rate, quiet)
         assert wf.getframerate() == self.pr.sample_rate, 'input wav sample rate mismatch'
         assert wf.getsampwidth() == self.pr.sample_depth, 'input wav sample depth mismatch'
         assert wf.getnframes() > 0, 'no valid data in input wav'
@@ -232,22 +253,29 @@ class Listener(object):
         wf.close()
         return results
 
-    def _read_wav(self, path):
+    def _read_wav(self, path, with_rate=False):
+        """-> the file's int16 samples; with_rate: (samples, its sample rate), which resample=True lets differ from pr.sample_rate"""
         wf = wave.open(path, 'rb')
         assert wf.getnchannels() == 1, 'input wav channels mismatch'
-        assert wf.getframerate() == self.pr.sample_rate, 'input wav sample rate mismatch'
+        rate = wf.getframerate()
+        assert (with_rate and self.resample) or rate == self.pr.sample_rate, 'input wav sample rate mismatch'
         assert wf.getsampwidth() == self.pr.sample_depth, 'input wav sample depth mismatch'
         pcm = np.frombuffer(wf.readframes(wf.getnframes()), dtype='<i2')
         wf.close()
-        return pcm
+        return (pcm, rate) if with_rate else pcm
 
     def _scan_files(self, files, keep_audio=False):
-        """-> (ScanResult of the files, their sample counts): read, packed and scanned at once"""
-        pcm = [self._read_wav(p) for p in files]
+        """-> (ScanResult of the files, their sample counts): read, packed and scanned at once.  With resample=True files at other
+        rates are converted on the device first; the counts, like everything the scan returns, are then in converted samples."""
+        read = [self._read_wav(p, with_rate=True) for p in files]
+        pcm, rates = [a for a, _ in read], [r for _, r in read]
         res = scan(self.pr, self.model._device(), pcm, chunk_size=self.chunk_size, class_names=self.class_names,
                    sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
-                   quantized=self.quantized, tile=self.scan_tile, keep_audio=keep_audio)
-        return res, [int(a.size) for a in pcm]
+                   quantized=self.quantized, tile=self.scan_tile, keep_audio=keep_audio, sample_rates=rates)
+        if all(r == self.pr.sample_rate for r in rates):
+            return res, [int(a.size) for a in pcm]
+        from kws_amd.rate import bank_for
+        return res, [bank_for(r, self.pr.sample_rate).total(a.size) for a, r in zip(pcm, rates)]
 
     def scan_wav(self, paths=None, quiet=True):
         """run_wav for whole files at once (kws_amd.stream.scan): `paths` is one wav or a list of them (default: input_wav).
@@ -449,6 +477,9 @@ def parse_args(argv=None):
     parser.add_argument('--scan', action='store_true',
                         help='offline scan: the whole recording(s) at once instead of chunk by chunk; prints every activation with its time')
     parser.add_argument('--scan_tile', type=int, default=default_config['scan_tile'], help='windows per forward launch of --scan')
+    parser.add_argument('--resample', action='store_true',
+                        help='accept mono 16-bit wavs at other sample rates (a quarter to four times the model\'s): they are converted on the '
+                             'device first, and chunks, times and labels then count converted samples')
     parser.add_argument('--sweep', action='store_true',
                         help='scan the recording(s) once and evaluate the detector at every (sensitivity, trigger level) of a grid')
     parser.add_argument('--labels_path', type=str, default=None,
