@@ -1531,6 +1531,61 @@ int kws_head_fit(const float *emb, const int32_t *labels, int64_t N, int E, cons
                  const kws_head_job *jobs, void *jobs_dev, int J, float *weights, float *slot_m, float *slot_v, float *stats,
                  void *stream);
 
+/* ------------------------------------------------------------------------
+ * Nearest neighbours over embeddings: which rows of an (N, E) matrix look alike (csrc/kws_knn.hip).  The
+ * reference's hygiene tools (tools/audio_process/wav_check.py, silent_check.py, speech_duration_check.py) look at one file at a time;
+ * this looks at pairs: duplicates across a train / validation split, clips whose neighbours carry another label, k-NN as a classifier.
+ *
+ * Scores.  E is a multiple of 4 in 4 .. 128 (as kws_head_fit), k is in 1 .. KWS_KNN_MAX_K, N in 1 .. 2^31 - 1.
+ *   KWS_KNN_DOT  score = q.r                          best = largest
+ *   KWS_KNN_L2   score = max(0, (q.q + r.r) - 2 q.r)   best = smallest
+ * Cosine similarity is KWS_KNN_DOT on rows that went through kws_rows_normalize; it is not a third metric.  Every dot product (q.r,
+ * q.q and r.r alike) is ONE float32 chain acc = fma(a_c, b_c, acc) over the columns c in ascending order, starting from 0 -- what
+ * v_mfma_f32_32x32x2_f32 computes -- so a score depends on its two rows only, not on the tile, slice or launch that computed it.
+ * KWS_KNN_L2 caveat: the expansion loses the distance of near-identical rows to cancellation (two rows that differ in the last bits
+ * come out at 0 or at a few ulp of q.q, in any order); a search for duplicates uses cosine.
+ * Order.  Candidates are ordered by the pair (score, reference index): the better score first, at equal score the lower index; the k
+ * output entries of a query are sorted in that order.  The order is total, so the result is the same bits for every `slices` and
+ * every block schedule; there are no atomics.  Where fewer than k candidates exist the tail is idx = -1 with score = -inf (DOT) /
+ * +inf (L2).  A NaN score ranks last among the candidates and is REPORTED as the worst score (-inf / +inf) with its index; other
+ * non-finite inputs are compared as IEEE compares them.  A NaN never touches another query's row.
+ * ---------------------------------------------------------------------- */
+#define KWS_KNN_MAX_K 64
+enum { KWS_KNN_DOT = 0, KWS_KNN_L2 = 1 };
+
+/* out[i] = x[i] / ||x[i]|| (a zero row stays zero); norms: NULL or (N), the norms.  out may be x.  The sum of squares is taken in
+ * double, so the norm is the correctly rounded one and a unit row is the float32 nearest to the exact quotient.  x and out 16-byte
+ * aligned.  N == 0 does nothing.  KWS_ERR_INVALID: E, N < 0, a NULL or misaligned x / out. */
+int kws_rows_normalize(const float *x, int64_t N, int E, float *out, float *norms, void *stream);
+
+/* Host only.  Bytes of the workspace kws_knn needs with the same arguments: 0 for one slice, else `slices` x Q x k (index, score)
+ * pairs rounded up to 256 bytes.  slices == 0 asks for the library's choice, which depends on Q and N only.  A negative kws_status
+ * for arguments kws_knn refuses. */
+int64_t kws_knn_workspace_bytes(int64_t Q, int64_t N, int E, int k, int slices);
+
+/* For every query row, its k best reference rows.  queries (Q, E), refs (N, E), 16-byte aligned; idx (Q, k) int32, score (Q, k) float32.
+ * exclude: NULL or (Q) int32, the reference row query i must skip (-1: none); a search of a set in itself passes i.
+ * slices: 0 = the library chooses (a small Q gets enough blocks to fill the chip, a large Q gets 1); 1 .. 1024 = the N reference rows
+ * are cut into that many runs of 32-row tiles, handled by different blocks, and merged by the total order above.  Slices past the last
+ * tile are empty, which is allowed.  The Q x N scores never reach memory.
+ * Checked on the host before any device work: KWS_ERR_INVALID for E, k, N, Q < 0, the metric, slices outside 0 .. 1024, a NULL or
+ * misaligned queries / refs, a NULL idx / score; KWS_ERR_WORKSPACE for more than one slice with ws NULL or ws_bytes below
+ * kws_knn_workspace_bytes.  Q == 0 does nothing and returns KWS_OK. */
+int kws_knn(const float *queries, int64_t Q, const float *refs, int64_t N, int E, int metric, int k, const int32_t *exclude, int slices,
+            int32_t *idx, float *score, void *ws, size_t ws_bytes, void *stream);
+
+/* Votes of the neighbours kws_knn found.  labels (N) int32: the labels of the reference rows; C classes, 2 .. 1024.
+ * An entry with idx = -1, or whose label lies outside [0, C), casts no vote.  weighted == 0: every vote counts 1.  weighted != 0: a vote
+ * counts its score, a negative (or NaN) score counts 0 -- meaningful for KWS_KNN_DOT scores only; this function cannot see the metric,
+ * kws_amd.neighbors refuses the combination with L2.
+ *   pred (Q)     the class with the most votes, a tie goes to the lower class; -1 for a query whose votes sum to 0
+ *   support (Q)  pred's share of the votes (0 without a vote)
+ *   own          NULL or (Q): the share of own_labels[i] (own_labels NULL <=> own NULL)
+ * KWS_ERR_INVALID: k, C, Q < 0, N outside 1 .. 2^31 - 1, a NULL idx / labels / pred / support, weighted without score, own without
+ * own_labels or the reverse.  Q == 0 does nothing. */
+int kws_knn_vote(const int32_t *idx, const float *score, int64_t Q, int k, const int32_t *labels, int64_t N, int C, int weighted,
+                 const int32_t *own_labels, int32_t *pred, float *support, float *own, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
