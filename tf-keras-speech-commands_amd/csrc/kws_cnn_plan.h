@@ -35,6 +35,7 @@ struct CnnPlan {
     bool l1_fin_in_kernel;   // layer 1's backward kernel evaluates the closed forms in its last block (no finalize launch)
     bool head_bwd_fuses;     // the MFMA head kernel also leaves the dense bias gradient and the loss / accuracy sums
     bool fuse_head_fwd;      // the head's forward pass rides in its backward kernel
+    bool dgrad2_fast;        // conv2's split-precision data gradient as the compile-time kernel of the default 15 x 10 map (kws_conv2_dgrad_fast.h)
 };
 
 // what plan_cnn reads of a model (kws_model.hip: cnn_desc)
@@ -90,6 +91,8 @@ inline CnnPlan plan_cnn(const CnnDesc &m, int B, int mprec, bool training, bool 
     p.l1_fin_in_kernel = acc_ok && p.l1_default_map;
     // the compile-time map, coefficients from the accumulator set (so neither deterministic mode nor a captured step)
     p.wgrad2_fast = p.wgrad2_early && p.acc_bn2 && d.H1 == kW2fH && d.W1 == kW2fW;
+    // the data gradient beside it: same map, same conditions (it takes the place of conv_dgrad_clip_bf16_kernel<true, true, false>)
+    p.dgrad2_fast = p.wgrad2_fast;
     return p;
 }
 

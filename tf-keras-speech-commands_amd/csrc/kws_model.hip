@@ -18,6 +18,7 @@
 #include "kws_layer1_fast.h"
 #include "kws_l1_conv2.h"
 #include "kws_conv2_wgrad_fast.h"
+#include "kws_conv2_dgrad_fast.h"
 #include "kws_lite.h"
 #include "kws_lite_f16.h"
 #include "kws_infer_fused.h"
@@ -1049,7 +1050,11 @@ int CnnCtx::bwd_layer2()
     }
     if (P.bf16) {
         const dim3 grid(cc.even_grid(cu_count() * 2));
-        if (P.wgrad2_early)
+        if (P.dgrad2_fast) {
+            // the default map: compile-time geometry, window-major staging (kws_conv2_dgrad_fast.h); same label, stream and grid rule
+            using G = Conv2DgradFast<kW2fH, kW2fW>;
+            KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv2_dgrad_fast_kernel<kW2fH, kW2fW>), grid, dim3(256), G::BYTES, s, kern, w.da[0], B, bn);
+        } else if (P.wgrad2_early)
             KWS_LAUNCH("conv_dgrad_clip_bf16<32,16>", (conv_dgrad_clip_bf16_kernel<true, true, false>), grid, dim3(256), cc.smdb, s,
                        w.gz[1], kern, w.da[0], B, H1, W1, bn);
         else if (P.compact_g2)
