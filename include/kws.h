@@ -1586,6 +1586,65 @@ int kws_knn(const float *queries, int64_t Q, const float *refs, int64_t N, int E
 int kws_knn_vote(const int32_t *idx, const float *score, int64_t Q, int k, const int32_t *labels, int64_t N, int C, int weighted,
                  const int32_t *own_labels, int32_t *pred, float *support, float *own, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Query-by-example keyword search: where in a recording does something occur that sounds like these few examples?  No model, no
+ * labels and no one-second framing: subsequence dynamic time warping of templates (the MFCC rows of the examples) against the rows
+ * kws_featurize_long gives whole recordings (csrc/kws_dtw.hip).
+ *
+ * A template q has L rows, 1 <= L <= KWS_DTW_MAX_ROWS; a recording x has n rows; all rows are D wide, D a multiple of 4 in 4 .. 64
+ * (pad with zero columns, which change neither metric).  Local cost of template row i against frame j:
+ *   KWS_DTW_DOT  d(i, j) = 1 - q_i . x_j        (cosine distance on rows that went through kws_rows_normalize; nothing is normalised here)
+ *   KWS_DTW_L2   d(i, j) = sum_k (q_ik - x_jk)^2
+ * Both are ONE float32 chain acc = fma(., ., acc) over the columns in ascending order, starting from 0.  The recurrence is slope
+ * constrained and every path weighs L in total:
+ *   C(0, j) = d(0, j)                  S(0, j) = j                (a match may begin at any frame)
+ *   C(i, j) = min( C(i-1, j-1) +   d(i, j),       candidate 1
+ *                  C(i-1, j-2) +   d(i, j),       candidate 2
+ *                  C(i-2, j-1) + 2 d(i, j) )      candidate 3     (a candidate with a negative index does not exist)
+ *   S(i, j) = S of the winning candidate; a tie goes to the lower candidate number
+ *   cost[j] = C(L-1, j) / L            start[j] = S(L-1, j)
+ * in float32 throughout.  A cell without a finite candidate is +inf with start -1 (the first ceil((L-1)/2) frames of a recording);
+ * frames j >= n are +inf / -1; cost and start are written for every j < max_frames.  A match that ends at frame j spans
+ * ceil((L+1)/2) .. 2L - 1 frames, so every path to (L-1, j) lies in the columns >= j - 2 (L-1): a recording is cut into tiles of
+ * frames that each recompute a halo of 2 (L-1) frames, and the result is the SAME BITS for every tile size.  No atomics.
+ * ---------------------------------------------------------------------- */
+#define KWS_DTW_MAX_ROWS 64
+#define KWS_DTW_MAX_HITS 64
+enum { KWS_DTW_DOT = 0, KWS_DTW_L2 = 1 };
+
+/* Host only.  Bytes of the workspace kws_dtw needs with the same arguments, or a negative kws_status for arguments kws_dtw refuses.
+ * The DP lives in registers and a tile recomputes its halo instead of taking it from its neighbour, so this is 0 today; callers
+ * still ask, so that a later kernel may need one. */
+int64_t kws_dtw_workspace_bytes(int R, int Q, int max_frames, int D, int tile_frames);
+
+/* Every template against every recording.  All pointers but `ws` are device memory.
+ *   templates (Q, Lmax, D), 16-byte aligned; tmpl_len (Q) int32, the rows of each (clamped to 0 .. Lmax; 0 rows match nothing)
+ *   rows (R, max_frames, D), 16-byte aligned, as kws_featurize_long writes them; n_frames (R) int32 (clamped to 0 .. max_frames)
+ *   cost (R, Q, max_frames) float32, start (R, Q, max_frames) int32
+ *   tile_frames: 0 = the library cuts the frames so that the chip is filled (from R, Q and max_frames alone: the lengths live on the
+ *   device); 32 .. 2^20 = that many frames per job.  Any value gives the same bits.
+ * One launch, no host synchronisation, nothing read back.  Checked on the host before any device work: KWS_ERR_INVALID for D, R < 0,
+ * Q < 0, max_frames outside 1 .. 2^30, Lmax outside 1 .. KWS_DTW_MAX_ROWS, the metric, tile_frames, a NULL or misaligned pointer;
+ * KWS_ERR_WORKSPACE for a workspace below kws_dtw_workspace_bytes; KWS_ERR_UNSUPPORTED for more jobs than one launch takes.
+ * R == 0 or Q == 0 does nothing and returns KWS_OK. */
+int kws_dtw(const float *templates, const int32_t *tmpl_len, int Q, int Lmax, const float *rows, const int32_t *n_frames, int R, int max_frames,
+            int D, int metric, int tile_frames, float *cost, int32_t *start, void *ws, size_t ws_bytes, void *stream);
+
+/* The detections in what kws_dtw wrote.  Template q belongs to keyword group[q]; group is (Q) int32 on the DEVICE, group_host is NULL or
+ * the same Q values on the host, which are then checked: non-decreasing from 0 without gaps, the last one G - 1.  (The kernel itself
+ * takes a keyword's templates wherever they stand.)  Q is at most 1024 here.
+ * For each (recording, keyword) the curve is the minimum over the keyword's templates of cost[r, q, :], a tie going to the lower q.
+ * Greedy selection, up to K <= KWS_DTW_MAX_HITS times: the unsuppressed frame with the lowest curve value, which must be finite and
+ * <= threshold, a tie going to the lower frame; it is emitted as (end frame, start of that template at that frame, cost, template),
+ * and every frame f with |f - end| < min_gap is suppressed (min_gap >= 1).
+ *   count (R, G) int32; end, hit_start, hit_template (R, G, K) int32, hit_cost (R, G, K) float32, in the order of selection; unused
+ *   slots hold -1 / +inf.
+ * KWS_ERR_INVALID: R < 0, Q outside 1 .. 1024, max_frames < 1, G outside 1 .. Q, K, min_gap < 1, a NaN threshold, a NULL pointer, a
+ * group_host that is not sorted as above.  R == 0 does nothing. */
+int kws_dtw_peaks(const float *cost, const int32_t *start, int R, int Q, int max_frames, const int32_t *group, const int32_t *group_host, int G,
+                  float threshold, int min_gap, int K, int32_t *count, int32_t *end, int32_t *hit_start, float *hit_cost, int32_t *hit_template,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,8 @@ RATE_RESTART, RATE_FINAL = 1, 2
 RATE_MAX_BANKS = 16
 KNN_MAX_K = 64
 KNN_METRICS = {"dot": 0, "l2": 1}                                                       # include/kws.h KWS_KNN_*
+DTW_MAX_ROWS, DTW_MAX_HITS, DTW_MAX_Q = 64, 64, 1024
+DTW_METRICS = {"dot": 0, "l2": 1}                                                       # include/kws.h KWS_DTW_*
 
 _lib = None
 
@@ -402,6 +404,10 @@ def get_lib():
     L.kws_knn_workspace_bytes.restype = i64
     L.kws_knn.argtypes = [vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, ctypes.c_size_t, vp]
     L.kws_knn_vote.argtypes = [vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, vp]
+    L.kws_dtw_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    L.kws_dtw_workspace_bytes.restype = i64
+    L.kws_dtw.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, ctypes.c_size_t, vp]
+    L.kws_dtw_peaks.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
