@@ -181,7 +181,9 @@ class ReLU6(Layer):
 
 class MaxPool2(Layer):
     """MaxPooling2D(): 2x2 window, stride 2, 'valid' (odd sizes floor).  The gradient goes to the FIRST maximum in
-    row-major window order (ties happen after ReLU6 saturates at 0 or 6)."""
+    row-major window order.  Ties happen after ReLU6 saturates at 0 or 6, where the gate makes the routed gradient zero, and between
+    equal unsaturated values as well (the identical frames of a clip that is left-padded with digital silence), where the choice
+    shows in the gradients upstream: the first-maximum rule is what tests/test_pool_ties_host.py and tests/test_pool_ties_gpu.py pin."""
 
     def forward(self, x, training):
         B, H, W, C = x.shape

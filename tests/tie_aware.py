@@ -27,7 +27,9 @@ class TieAwareOracle(object):
     """One training forward + backward of `om` on (x, y) with the near-tie decisions recorded."""
 
     def __init__(self, om, x, y, class_weights=None, dropout_seed=None, eps=3e-6, max_candidates=6, ignore_index=None,
-                 grad_scale=1.0):
+                 grad_scale=1.0, exact_ties=True):
+        """exact_ties = False leaves out the ReLU6 / ReLU decisions whose margin is exactly 0 (tests/pool_tie_cases.py: both sides
+        compute that value exactly there, so nothing is ambiguous about them)"""
         self.om = om
         rec, patched = {}, []
         for li, l in enumerate(om.layers):
@@ -46,6 +48,7 @@ class TieAwareOracle(object):
             for l in patched:
                 del l.forward
         self.base = [g.copy() for g in om.grad_list()]
+        self.inputs = rec                             # layer index -> input of every ReLU6 and MaxPool2 of the pass
         _, self.dlogits = mo.loss_and_grad(self.probs, y, class_weights, ignore_index, grad_scale)
         cands = []                                    # (relative margin, layer index, kind, index, payload)
         for li, l in enumerate(om.layers):
@@ -65,6 +68,8 @@ class TieAwareOracle(object):
                 order = np.argsort(-win, axis=0, kind="stable")
                 top = np.take_along_axis(win, order[:2], 0)
                 gap = (top[0] - top[1]) / (xin.std() + 1e-30)
+                # gap > 0: an exact tie is no candidate for a flip.  Both sides see it, and "the first maximum wins" decides it:
+                # tests/test_pool_ties_host.py and tests/test_pool_ties_gpu.py pin that rule, on data built to tie
                 for i in np.argwhere((gap > 0) & (gap < eps)):
                     cands.append((float(gap[tuple(i)]), li, "pool", tuple(i), int(order[1][tuple(i)])))
             elif isinstance(l, mo.Conv2D) and l.relu:
@@ -73,6 +78,8 @@ class TieAwareOracle(object):
                 d = np.abs(pre) / (pre.std() + 1e-30)
                 for i in np.argwhere(d < eps):
                     cands.append((float(d[tuple(i)]), li, "relu", tuple(i), None))
+        if not exact_ties:
+            cands = [c for c in cands if c[0] > 0]
         cands.sort(key=lambda c: c[0])
         self.candidates = cands[:max_candidates]
         self.n_near_ties = len(cands)
