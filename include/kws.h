@@ -1532,6 +1532,48 @@ int kws_head_fit(const float *emb, const int32_t *labels, int64_t N, int E, cons
                  void *stream);
 
 /* ------------------------------------------------------------------------
+ * A bank of heads on one backbone: the serving half of the transfer block (csrc/kws_heads.hip).  The backbone
+ * runs once over all rows (kws_model_embed); kws_heads_apply then gives every row the Dense(E -> C_h, softmax) head that row names,
+ * out of H heads resident on the device: a keyword set per stream, or every fold's head on its own held-out rows, in one launch.
+ *
+ * Bank layout.  Head h is C_h = head_classes[h] classes wide, 2 <= C_h <= Cmax <= KWS_HEADS_MAX_CLASSES; its kernel matrix (E, C_h),
+ * row-major, followed by its bias (C_h), lies at weights + head_offset[h]: kws_head_fit's layout, so a fitted head is copied in as it
+ * is.  weights holds weights_count floats; head_offset (H) int64 and head_classes (H) int32 are DEVICE arrays, so a head is replaced
+ * or emptied (head_classes[h] = 0) by stream-ordered copies between two launches.  E is a multiple of 4 in 4 .. 128, as for
+ * kws_head_fit.  KWS_HEADS_MAX_CLASSES is the largest value kws_head_fit_max_classes(E) takes over those E (256, for E <= 32; it is
+ * 64 at E = 128), so every head kws_head_fit can train can be banked.
+ *
+ * Rows.  Row r of the R output rows reads emb[rows[r]] (rows NULL: emb[r], and then R <= N), has the key key[r * key_stride], and its
+ * head is the key itself (head_of_key NULL) or head_of_key[key] with key in [0, K).  A streaming push passes key = table +
+ * KWS_RAGGED_SLOT, key_stride = KWS_RAGGED_FIELDS, head_of_key = the server's per-slot head array, K = S: no gather, no read-back.
+ *
+ * Arithmetic, all float32.  logit[c] is ONE chain: acc = b_c; acc = fma(x_e, W[e][c], acc) for e = 0, 1, .. E - 1.  m = max_c logit[c];
+ * p_c = exp(logit[c] - m) / sum, the sum taken over c = 0, 1, .. C_h - 1 in that order, exp the precise expf and the division IEEE.
+ * pred is the arg-max of the logits, an exact tie going to the lower class.  Columns C_h .. Cmax - 1 of logits and probs are written
+ * as 0 (a padded zero cannot win an arg-max over probabilities: the largest of them is at least 1 / C_h).
+ * Independence.  A row's outputs depend on its embedding row and its head alone: not on R, on its position, on the rows that share
+ * its tile or on the other heads.  No atomics; the same bits on every run.  A tile whose rows all name one head reads that head from
+ * LDS instead of from memory; the chains are the same, so are the bits.
+ *
+ * Trust and clamping, as in the ragged-streaming entry points: key (R entries at key_stride) and rows (R) are read as given; whatever
+ * they lead to is checked.  A row is written as zeros with pred = -1, and nothing is read outside emb, head_of_key, head_offset,
+ * head_classes or weights, when rows[r] is outside [0, N), its key is outside [0, K), its head id is outside [0, H), head_classes[h]
+ * is outside 2 .. Cmax, or head_offset[h] is negative or head_offset[h] + (E + 1) C_h runs past weights_count.
+ *
+ * logits, probs: NULL or (R, Cmax) float32; pred: NULL or (R) int32.  One launch, stream-ordered, no synchronisation.
+ * Checked on the host before any HIP call (KWS_ERR_INVALID): E not a multiple of 4 in 4 .. 128, N < 0, R < 0, H < 1, Cmax outside
+ * 2 .. KWS_HEADS_MAX_CLASSES, key_stride < 1, weights_count < 0, a NULL emb / key / weights / head_offset / head_classes, an emb that
+ * is not 16-byte aligned, head_of_key with K < 1, all three outputs NULL, rows == NULL with R > N.  R == 0 does nothing and returns
+ * KWS_OK.
+ * ---------------------------------------------------------------------- */
+#define KWS_HEADS_MAX_CLASSES 256
+#define KWS_HEADS_TILE_ROWS 16         /* consecutive rows one block handles; no result depends on it (the tests cut their runs around it) */
+int kws_heads_apply(const float *emb, int64_t N, int E, const int32_t *rows, const int32_t *key, int64_t key_stride,
+                    const int32_t *head_of_key, int64_t K, int64_t R, const float *weights, int64_t weights_count,
+                    const int64_t *head_offset, const int32_t *head_classes, int H, int Cmax, float *logits, float *probs,
+                    int32_t *pred, void *stream);
+
+/* ------------------------------------------------------------------------
  * Nearest neighbours over embeddings: which rows of an (N, E) matrix look alike (csrc/kws_knn.hip).  The
  * reference's hygiene tools (tools/audio_process/wav_check.py, silent_check.py, speech_duration_check.py) look at one file at a time;
  * this looks at pairs: duplicates across a train / validation split, clips whose neighbours carry another label, k-NN as a classifier.

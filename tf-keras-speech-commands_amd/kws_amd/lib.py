@@ -212,6 +212,7 @@ RAGGED_SLOT, RAGGED_CARRY, RAGGED_LEN, RAGGED_NEW, RAGGED_RESET, RAGGED_FIELDS =
  RATE_HIST_OUT, RATE_FLAGS, RATE_FIELDS) = range(13)
 RATE_RESTART, RATE_FINAL = 1, 2
 RATE_MAX_BANKS = 16
+HEADS_MAX_CLASSES, HEADS_TILE_ROWS = 256, 16                                            # include/kws.h KWS_HEADS_*
 KNN_MAX_K = 64
 KNN_METRICS = {"dot": 0, "l2": 1}                                                       # include/kws.h KWS_KNN_*
 DTW_MAX_ROWS, DTW_MAX_HITS, DTW_MAX_Q = 64, 64, 1024
@@ -399,6 +400,7 @@ def get_lib():
     L.kws_model_embed.argtypes = [vp, vp, i32, vp, vp, vp, ctypes.c_size_t, vp, vp]
     L.kws_head_fit_max_classes.argtypes = [i32]
     L.kws_head_fit.argtypes = [vp, vp, i64, i32, vp, vp, ctypes.POINTER(KwsHeadJob), vp, i32, vp, vp, vp, vp, vp]
+    L.kws_heads_apply.argtypes = [vp, i64, i32, vp, vp, i64, vp, i64, i64, vp, i64, vp, vp, i32, i32, vp, vp, vp, vp]
     L.kws_rows_normalize.argtypes = [vp, i64, i32, vp, vp, vp]
     L.kws_knn_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
     L.kws_knn_workspace_bytes.restype = i64

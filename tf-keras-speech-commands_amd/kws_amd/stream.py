@@ -150,27 +150,66 @@ def _defaults(pr, featurizer, decoder):
             decoder if decoder is not None else ThresholdDecoder(pr.threshold_config, pr.threshold_center))
 
 
-def _num_classes(device_model, quantized):
+def _num_classes(device_model, quantized, heads=None):
+    if heads is not None:
+        return heads.max_classes
     return quantized.num_classes if quantized is not None else device_model.spec.num_classes
 
 
-def _forward(device_model, quantized, feat):
-    """(N, F, D) features -> (N, C) float32 probabilities, from `quantized`'s int8 forward when there is one, else the model's"""
+def _forward(device_model, quantized, feat, heads=None, key=None):
+    """(N, F, D) features -> (N, C) float32 probabilities, from `quantized`'s int8 forward when there is one, else the model's.
+    With `heads` (a kws_amd.transfer.HeadBank): the backbone once over all rows (kws_model_embed), then kws_heads_apply gives every
+    row the head its key names -- key = (int32 tensor, stride, head_of_key or None) -- and C is the bank's max_classes, the columns
+    past a head's own classes zero."""
+    if heads is not None:
+        k, stride, head_of_key = key
+        emb = device_model.embed(feat)
+        return heads.launch(emb, emb.shape[0], k, key_stride=stride, head_of_key=head_of_key, want=("probs",))[0]
     if quantized is not None:
         return quantized.forward(feat)[0]
     return device_model.forward(feat, want_probs=True, want_argmax=False)[0]
+
+
+def _check_heads(device_model, quantized, heads):
+    """the refusals of a head bank, on the host: not with an int8 forward, and only on the backbone whose embeddings it reads"""
+    if heads is None:
+        return
+    if quantized is not None:
+        raise ValueError("heads and quantized do not go together: the int8 forwards end in their own head")
+    if heads.embed_size != device_model.embed_size:
+        raise ValueError("the bank's heads read %d-wide embeddings, %s produces %d-wide ones"
+                         % (heads.embed_size, device_model.spec.model_type, device_model.embed_size))
+
+
+def _head_ids(heads, ids, n, what):
+    """`n` head ids of a bank (None: all 0) as an int32 host array, or ValueError"""
+    if heads is None:
+        if ids is not None:
+            raise ValueError("%s needs heads=HeadBank" % what)
+        return None
+    a = np.zeros(n, np.int64) if ids is None else np.asarray(ids).reshape(-1)
+    if a.dtype.kind not in "iu" or a.size != n:
+        raise ValueError("%s must give one integer head id for each of the %d" % (what, n))
+    if a.size and (a.min() < 0 or a.max() >= heads.capacity):
+        raise ValueError("%s: head ids must lie in 0..%d" % (what, heads.capacity - 1))
+    return a.astype(np.int32)
 
 
 class _Streams(object):
     """What `StreamBatch` and `StreamServer` share: the refusal of deltas, the model, featurizer and decoder, the geometry, and per
     stream the feature window (mfccs), the detector state and the last (index, score, fired)."""
 
-    def __init__(self, pr, device_model, quantized):
+    def __init__(self, pr, device_model, quantized, heads=None):
         if pr.use_delta:
             raise ValueError(_NO_DELTAS)
+        _check_heads(device_model, quantized, heads)
         _torch()
         self._L = _l.get_lib()
-        self.pr, self.model, self.quantized = pr, device_model, quantized
+        self.pr, self.model, self.quantized, self.heads = pr, device_model, quantized, heads
+
+    def head_class_names(self, head):
+        """the class names of an activation in a stream that listens with `head` of the bank (class_names without a bank)"""
+        return self.class_names if self.heads is None else self.heads.class_names[int(head)]
 
     def _allocate(self, n_streams, chunk_size, class_names, decoder, featurizer, background_index):
         torch = _torch()
@@ -200,14 +239,17 @@ class StreamBatch(_Streams):
     push(chunks) takes one chunk of int16 PCM per stream -- (S, n) int16 array / CUDA tensor, or a list of S `bytes`
     objects as PyAudio / wave.readframes deliver them -- and returns (index, score, fired) as CUDA tensors of length S.
     With `quantized` (a kws_amd.quant.QuantizedCNN / QuantizedCNNLite) the probabilities come from its int8 forward instead of
-    device_model's.
+    device_model's.  With `heads` (a kws_amd.transfer.HeadBank) stream s listens with head stream_heads[s] of the bank (default 0)
+    on device_model's backbone; probs is then (S, heads.max_classes).
     """
 
     def __init__(self, pr, device_model, n_streams, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
-                 decoder=None, featurizer=None, background_index=0, quantized=None):
+                 decoder=None, featurizer=None, background_index=0, quantized=None, heads=None, stream_heads=None):
         torch = _torch()                                                                  # a missing device is named first, as `scan` does
-        _Streams.__init__(self, pr, device_model, quantized)
+        _Streams.__init__(self, pr, device_model, quantized, heads)
         self.sensitivity, self.trigger_level = float(sensitivity), int(trigger_level)
+        ids = _head_ids(heads, stream_heads, int(n_streams), "stream_heads")
+        self.stream_head = None if ids is None else torch.from_numpy(ids).to(device_model.device)
         self._allocate(int(n_streams), int(chunk_size), class_names, decoder, featurizer, background_index)
         self.win = torch.zeros((self.S, self.cap), dtype=torch.int16, device=device_model.device)     # carried + new samples
         self.n_win = 0
@@ -247,7 +289,7 @@ class StreamBatch(_Streams):
 
     def push(self, chunks):
         """One step of the loop listen.py:350-375 for every stream."""
-        self.probs = _forward(self.model, self.quantized, self.update_vectors(chunks))
+        self.probs = _forward(self.model, self.quantized, self.update_vectors(chunks), self.heads, (self.stream_head, 1, None))
         _l.check(self._L.kws_stream_postprocess(self.decoder.handle, self.probs.data_ptr(), self.S, self.probs.shape[1],
                                                 self.background_index, self.sensitivity, self.trigger_level, self.chunk_size,
                                                 self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),
@@ -485,11 +527,17 @@ class StreamServer(_Streams):
     however the stream is cut) and hands the rest of the push the converted chunks.  An entry whose chunk yields no converted sample
     (the first K input samples of a stream, a tiny chunk at 48 kHz) gets no prediction: its place in the returned tensors holds the
     slot's previous index and score with fired = 0, and probs has a row only for the entries that took part.  A push that names
-    only slots at pr.sample_rate runs the sequence above unchanged."""
+    only slots at pr.sample_rate runs the sequence above unchanged.
+
+    heads=bank (a kws_amd.transfer.HeadBank) gives every slot a keyword set of its own on the one backbone: open(..., head=h) names
+    the bank's head the slot listens with (slot_head (S) int32 on the device, a stream-ordered fill like sensitivity), and the
+    forward pass of a push becomes kws_model_embed over the A windows followed by kws_heads_apply, which finds each row's head through
+    the push's own table (key = the table's slot column, head_of_key = slot_head): one more launch, still nothing read back.  probs is
+    then (A, bank.max_classes), the columns past a head's own classes zero; bank.set replaces a head between two pushes."""
 
     def __init__(self, pr, device_model, n_slots, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
-                 decoder=None, featurizer=None, background_index=0, quantized=None):
-        _Streams.__init__(self, pr, device_model, quantized)
+                 decoder=None, featurizer=None, background_index=0, quantized=None, heads=None):
+        _Streams.__init__(self, pr, device_model, quantized, heads)
         torch = _torch()
         self.plan = RaggedPlan(n_slots, chunk_size, pr.window_samples, pr.hop_samples, sensitivity, trigger_level,
                                sample_rate=pr.sample_rate)
@@ -511,10 +559,14 @@ class StreamServer(_Streams):
         self._index = torch.zeros(S, dtype=torch.int32, device=dev)
         self._score = torch.zeros(S, dtype=torch.float64, device=dev)
         self._fired = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.slot_head = torch.zeros(S, dtype=torch.int32, device=dev)                    # the bank's head each slot listens with
         self.launches, self.featurizer_launches = 0, 0                                    # stages enqueued so far (a forward counts as one)
 
-    def open(self, sensitivity=None, trigger_level=None, sample_rate=None):
+    def open(self, sensitivity=None, trigger_level=None, sample_rate=None, head=0):
+        head = int(_head_ids(self.heads, [head], 1, "head")[0]) if self.heads is not None or head != 0 else 0
         slot = self.plan.open(sensitivity, trigger_level, sample_rate)
+        if self.heads is not None:
+            self.slot_head[slot] = head                                                   # a stream-ordered fill, as the two below
         if self.plan.bank[slot] is not None and self._hist is None:
             torch, dev = _torch(), self.win.device
             # two history rows per slot (one read, one written, by turns); 2K - 1 <= 8 Z - 1 samples for every supported pair at Z = 16
@@ -562,7 +614,7 @@ class StreamServer(_Streams):
         torch = _torch()
         A = len(lens)
         if A == 0:
-            self.probs = torch.empty((0, _num_classes(self.model, self.quantized)), dtype=torch.float32, device=self.win.device)
+            self.probs = torch.empty((0, _num_classes(self.model, self.quantized, self.heads)), dtype=torch.float32, device=self.win.device)
             return self._index[:0], self._score[:0], self._fired[:0]
         step = self.plan.push(slots, lens)
         if step.rate is not None:
@@ -585,7 +637,7 @@ class StreamServer(_Streams):
         if kept.size:
             self._detect(torch, step, lambda: (self._chunks.data_ptr(), self._stride))
         else:
-            self.probs = torch.empty((0, _num_classes(self.model, self.quantized)), dtype=torch.float32, device=self.win.device)
+            self.probs = torch.empty((0, _num_classes(self.model, self.quantized, self.heads)), dtype=torch.float32, device=self.win.device)
         if kept.size == A:
             return self._index[:A], self._score[:A], self._fired[:A]
         # an entry that emitted nothing was not predicted on: its place holds the slot's previous index and score, fired = 0
@@ -616,13 +668,15 @@ class StreamServer(_Streams):
         feat = self._feat[:A]
         _l.check(L.kws_stream_ragged_push_rows(self.mfccs.data_ptr(), self.S, self.F, self.D, self._rows.data_ptr(), mf, table.data_ptr(), A,
                                                feat.data_ptr(), st))
-        self.probs = _forward(self.model, self.quantized, feat)
+        # with a bank, a row's head is slot_head[its slot], found through the push's own table
+        key = None if self.heads is None else (table.view(-1)[_l.RAGGED_SLOT:], _l.RAGGED_FIELDS, self.slot_head)
+        self.probs = _forward(self.model, self.quantized, feat, self.heads, key)
         _l.check(L.kws_stream_ragged_postprocess(self.decoder.handle, self.probs.data_ptr(), A, self.probs.shape[1], table.data_ptr(), self.S,
                                                  self.background_index, self.sensitivity.data_ptr(), self.trigger_level.data_ptr(),
                                                  self.chunk_size, self.state.data_ptr(), self.index.data_ptr(), self.score.data_ptr(),
                                                  self.fired.data_ptr(), self._index.data_ptr(), self._score.data_ptr(),
                                                  self._fired.data_ptr(), st))
-        self.launches += 4 + (mf > 0)
+        self.launches += 4 + (mf > 0) + (self.heads is not None)
         self.featurizer_launches += mf > 0
 
 
@@ -703,7 +757,7 @@ def _pack_recordings(torch, recordings, lengths, device):
 
 def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_names=None, sensitivity=0.5, trigger_level=3,
          decoder=None, featurizer=None, background_index=0, quantized=None, tile=4096, return_probs=False, timings=None,
-         keep_audio=False, sample_rates=None):
+         keep_audio=False, sample_rates=None, heads=None, recording_heads=None):
     """The chunk loop of `StreamBatch` over R whole recordings at once: for every chunk of every recording the (index,
     score, fired) that `push` would have returned for it, and the final detector state, as a `ScanResult`.
 
@@ -715,10 +769,13 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     (start, end) CUDA event pairs per stage ("rows", "gather", "forward", "scan") for tools/scanbench.py.  keep_audio: the
     result keeps the packed int16 tensor and the lengths built here (`ScanResult.wav`, `.lengths`).  sample_rates: the rate of the
     recordings in Hz, one for all or one each; those not at pr.sample_rate are first converted to it by one kws_amd.rate.convert
-    call, and chunks, lengths, events and times are then in converted samples (None: all are at pr.sample_rate)."""
+    call, and chunks, lengths, events and times are then in converted samples (None: all are at pr.sample_rate).  heads (a
+    kws_amd.transfer.HeadBank) with recording_heads, one head id per recording (default 0): every window of recording r goes through
+    device_model's backbone and then through that head (kws_heads_apply); probs are (R, T_max, heads.max_classes)."""
     torch = _torch()
     if pr.use_delta:
         raise ValueError(_NO_DELTAS)
+    _check_heads(device_model, quantized, heads)
     if class_names is not None:
         assert class_names[0] == 'background', '1st class should be background.'          # listen.py:66
     _check_hop(pr.window_samples, pr.hop_samples)
@@ -736,7 +793,8 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     R = len(lens)
     n_chunks = [-(-n // chunk_size) for n in lens]
     T_max = max(n_chunks + [0])
-    C = _num_classes(device_model, quantized)
+    C = _num_classes(device_model, quantized, heads)
+    rec_heads = _head_ids(heads, recording_heads, R, "recording_heads")
     index = torch.empty((R, T_max), dtype=torch.int32, device=dev)
     score = torch.empty((R, T_max), dtype=torch.float64, device=dev)
     fired = torch.empty((R, T_max), dtype=torch.int32, device=dev)
@@ -765,13 +823,16 @@ def scan(pr, device_model, recordings, lengths=None, chunk_size=1024, class_name
     timed("rows", lambda: _l.check(L.kws_featurize_long(featurizer._h, wav.data_ptr(), _l.WAV_I16, R, wav.shape[1], d_len.data_ptr(),
                                                           max_frames, rows.data_ptr(), st)))
     per = max(1, tile // R)                                   # chunks of every recording per tile
+    d_heads = None if heads is None else torch.from_numpy(rec_heads).to(dev, non_blocking=True)
     feat = torch.empty((R * min(per, T_max), F, D), dtype=torch.float32, device=dev)
     for k0 in range(0, T_max, per):
         n = min(per, T_max - k0)
         fv = feat[:R * n]
         timed("gather", lambda: _l.check(L.kws_stream_gather_windows(rows.data_ptr(), R, max_frames, d_len.data_ptr(), chunk_size, W, H, F, D,
                                                                        k0, n, fv.data_ptr(), st)))
-        probs = timed("forward", lambda: _forward(device_model, quantized, fv))
+        # window (r, k) of the tile is row r * n + k: its head is its recording's
+        key = None if heads is None else (torch.repeat_interleave(d_heads, n, output_size=R * n), 1, None)
+        probs = timed("forward", lambda: _forward(device_model, quantized, fv, heads, key))
         off = k0 * 4
         timed("scan", lambda: _l.check(L.kws_stream_scan_postprocess(decoder.handle, probs.data_ptr(), R, n, C, d_chunks.data_ptr(), k0,
                                                                        int(background_index), float(sensitivity), int(trigger_level), chunk_size,

@@ -4,7 +4,9 @@
     head = fit_head(emb, y, num_classes, epochs=10, lr=1e-3)
     new_model = with_head(model, head)             # a KWSModel of the new class count: predict / evaluate / quantize / save / streams
 
-`fit_heads` trains many independent heads in ONE launch (one block each), `cross_validate` is built on it.  torch is device memory and
+`fit_heads` trains many independent heads in ONE launch (one block each), `cross_validate` is built on it.  `HeadBank` keeps many
+fitted heads on the device and applies to every row the head that row names (kws_heads_apply): `score_heads` scores every head on its
+own rows in one launch, and kws_amd.stream serves a keyword set per stream from a bank.  torch is device memory and
 the stream only; the head's arithmetic is the kernel's.  Everything is validated on the host before any device work (ValueError): the
 kernel trusts the `order` and `labels` it is given."""
 import ctypes
@@ -434,3 +436,254 @@ def fit_frozen(model, x, y, batch_size=32, epochs=1, validation_data=None, callb
         cb.on_train_end()
     model.head_fit = head
     return model.history
+
+
+# ---- a bank of heads on one backbone (include/kws.h: kws_heads_apply) ------------------------------------------
+def plan_bank(classes, E):
+    """Where the heads of a bank lie.  classes: the class count (or the room, for a slot that may take any head up to it) of every
+    head.  -> (offsets, count): int64 offsets in floats into the weights array, each a multiple of 4 -- head h takes (E + 1) * classes[h]
+    floats, kernel (E, C) row-major then bias (C), kws_head_fit's layout -- and the length of that array.  Host only."""
+    E = int(E)
+    if E < 4 or E > 128 or E % 4:
+        raise ValueError("E = %d: the embedding width must be a multiple of 4 in 4..128" % E)
+    classes = np.asarray(classes, np.int64).reshape(-1)
+    if classes.size and (classes.min() < 2 or classes.max() > _l.HEADS_MAX_CLASSES):
+        raise ValueError("a banked head has 2..%d classes" % _l.HEADS_MAX_CLASSES)
+    room = ((E + 1) * classes + 3) // 4 * 4
+    offsets = np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.int64) if classes.size else np.zeros((0,), np.int64)
+    return offsets, int(room.sum())
+
+
+def _head_arrays(head, E):
+    """a HeadFit or (kernel, bias) -> (C, flat weights: a device tensor for a HeadFit, else a float32 ndarray)"""
+    if isinstance(head, HeadFit):
+        if head.embed_size != E:
+            raise ValueError("the head reads %d-wide embeddings, the bank holds %d-wide ones" % (head.embed_size, E))
+        return head.num_classes, head.weights
+    k, b = np.asarray(head[0], np.float32), np.asarray(head[1], np.float32)
+    if k.ndim != 2 or k.shape[0] != E or b.shape != (k.shape[1],):
+        raise ValueError("a head is (kernel (%d, C), bias (C,)), got %s and %s" % (E, k.shape, b.shape))
+    return int(k.shape[1]), np.concatenate([k.reshape(-1), b])
+
+
+class HeadBank(object):
+    """`capacity` slots for Dense(embed_size -> C, softmax) heads of up to max_classes classes, resident on the device, that
+    kws_heads_apply applies row by row: a keyword set per stream (kws_amd.stream: StreamServer / StreamBatch / scan take `heads=bank`)
+    or per fold (score_heads).  weights, head_offset, head_classes: the device tensors of include/kws.h, every slot with room for
+    max_classes classes (plan_bank), so any head that fits the bank fits any slot; classes (host mirror, 0: empty) and class_names per slot.
+    set / remove are stream-ordered copies and fills: a head is replaced between two pushes of a running server without stopping it.
+    device: None is the current HIP device; 'cpu' keeps the arrays in host memory for bookkeeping alone (save / load / planning) --
+    nothing is ever applied there, launch refuses embeddings that are not on the GPU."""
+
+    def __init__(self, embed_size, capacity, max_classes, device=None):
+        self.embed_size, self.capacity, self.max_classes = int(embed_size), int(capacity), int(max_classes)
+        if self.capacity < 1:
+            raise ValueError("a bank has at least one slot")
+        if not 2 <= self.max_classes <= _l.HEADS_MAX_CLASSES:
+            raise ValueError("max_classes = %d is outside 2..%d" % (self.max_classes, _l.HEADS_MAX_CLASSES))
+        self.offsets, self.count = plan_bank([self.max_classes] * self.capacity, self.embed_size)
+        self.classes = np.zeros((self.capacity,), np.int32)
+        self.class_names = [None] * self.capacity
+        self.names = [None] * self.capacity                      # an optional name per head (listen.py --head_map refers to it)
+        import torch
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.weights = torch.zeros((self.count,), dtype=torch.float32, device=self.device)
+        self.head_offset = torch.from_numpy(self.offsets).to(self.device)
+        self.head_classes = torch.zeros((self.capacity,), dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return int((self.classes > 0).sum())
+
+    def _slot(self, h):
+        if isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, np.integer)) or not 0 <= h < self.capacity:
+            raise ValueError("head id %r is outside 0..%d" % (h, self.capacity - 1))
+        return int(h)
+
+    def set(self, h, head, class_names=None, name=None):
+        """copies `head` (a HeadFit or (kernel, bias)) into slot h, replacing what was there; class_names: its C names, class 0 the
+        background as the servers require; name: the head's own (a user, a keyword set).  Enqueued on the current stream."""
+        import torch
+        h = self._slot(h)
+        C, flat = _head_arrays(head, self.embed_size)
+        if C < 2 or C > self.max_classes:
+            raise ValueError("a head of %d classes in a bank of 2..%d" % (C, self.max_classes))
+        if class_names is not None:
+            class_names = list(class_names)
+            if len(class_names) != C:
+                raise ValueError("%d class names for %d classes" % (len(class_names), C))
+            if class_names[0] != 'background':
+                raise ValueError("1st class should be background.")
+        lo, n = int(self.offsets[h]), (self.embed_size + 1) * C
+        with _on(self.device):
+            if isinstance(flat, np.ndarray):
+                staged = torch.empty((n,), dtype=torch.float32, pin_memory=self.device.type == "cuda")
+                staged.numpy()[:] = flat
+                self.weights[lo:lo + n].copy_(staged, non_blocking=True)
+            else:
+                self.weights[lo:lo + n].copy_(flat)
+            self.head_classes[h:h + 1].fill_(C)
+        self.classes[h], self.class_names[h], self.names[h] = C, class_names, None if name is None else str(name)
+        return h
+
+    def add(self, head, class_names=None, name=None):
+        """-> the id of the lowest empty slot, now holding `head`"""
+        free = np.flatnonzero(self.classes == 0)
+        if free.size == 0:
+            raise RuntimeError("the bank is full: all %d slots hold a head" % self.capacity)
+        return self.set(int(free[0]), head, class_names, name)
+
+    def remove(self, h):
+        """empties slot h (classes = 0): rows that name it come out as zeros with pred = -1"""
+        import torch
+        h = self._slot(h)
+        with _on(self.device):
+            self.head_classes[h:h + 1].fill_(0)
+        self.classes[h], self.class_names[h], self.names[h] = 0, None, None
+
+    def launch(self, emb, R, key, key_stride=1, head_of_key=None, rows=None, want=("probs",)):
+        """kws_heads_apply on the current stream.  emb (N, E) float32 CUDA; key: int32 CUDA tensor read at key[r * key_stride];
+        head_of_key, rows: int32 CUDA tensors or None.  -> the tensors named in `want`, of 'logits' (R, Cmax), 'probs' (R, Cmax),
+        'pred' (R), in that order.  No synchronisation, nothing read back."""
+        import torch
+        N, E = _check_emb_bank(emb, self)
+        unknown = set(want) - {"logits", "probs", "pred"}
+        if unknown or not want:
+            raise ValueError("want names some of 'logits', 'probs', 'pred', got %r" % (want,))
+        R = int(R)
+        out = {k: torch.empty((R,) if k == "pred" else (R, self.max_classes), dtype=torch.int32 if k == "pred" else torch.float32,
+                              device=emb.device) for k in want}
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        with torch.cuda.device(emb.device):
+            _l.check(_l.get_lib().kws_heads_apply(emb.data_ptr(), N, E, rows.data_ptr() if rows is not None else None, key.data_ptr(),
+                                                  int(key_stride), head_of_key.data_ptr() if head_of_key is not None else None,
+                                                  int(head_of_key.numel()) if head_of_key is not None else 0, R, self.weights.data_ptr(),
+                                                  self.count, self.head_offset.data_ptr(), self.head_classes.data_ptr(), self.capacity,
+                                                  self.max_classes, ptr("logits"), ptr("probs"), ptr("pred"),
+                                                  torch.cuda.current_stream().cuda_stream))
+        return tuple(out[k] for k in want)
+
+    def apply(self, emb, head, rows=None, want=("probs",)):
+        """Row r of the result is head[r] applied to emb[rows[r]] (rows None: emb[r]).  head: (R) head ids, rows: (R) row numbers -- int
+        arrays or tensors; an id or row outside the bank / emb, or an empty slot, gives a zero row with pred -1.  -> tuple of `want`."""
+        head = _index_tensor(head, emb.device)
+        if rows is not None:
+            rows = _index_tensor(rows, emb.device)
+            if rows.numel() != head.numel():
+                raise ValueError("%d rows for %d head ids" % (rows.numel(), head.numel()))
+        elif head.numel() > emb.shape[0]:
+            raise ValueError("%d head ids for %d embeddings" % (head.numel(), emb.shape[0]))
+        return self.launch(emb, head.numel(), head, rows=rows, want=want)
+
+    def save(self, path):
+        """the occupied slots' heads and names to a .npz (numpy only on the way back in)"""
+        w = self.weights.cpu().numpy()
+        data = dict(embed_size=self.embed_size, capacity=self.capacity, max_classes=self.max_classes, classes=self.classes)
+        for h in np.flatnonzero(self.classes > 0):
+            lo, C = int(self.offsets[h]), int(self.classes[h])
+            data["head_%d" % h] = w[lo:lo + (self.embed_size + 1) * C]
+            if self.class_names[h] is not None:
+                data["names_%d" % h] = np.asarray(self.class_names[h], dtype=str)
+            if self.names[h] is not None:
+                data["name_%d" % h] = np.asarray(self.names[h], dtype=str)
+        with open(path, "wb") as f:
+            np.savez(f, **data)
+
+    @classmethod
+    def load(cls, path, device=None):
+        with np.load(path, allow_pickle=False) as z:
+            bank = cls(int(z["embed_size"]), int(z["capacity"]), int(z["max_classes"]), device)
+            E = bank.embed_size
+            for h in np.flatnonzero(z["classes"] > 0):
+                C, flat = int(z["classes"][h]), z["head_%d" % h]
+                names = [str(n) for n in z["names_%d" % h]] if "names_%d" % h in z.files else None
+                bank.set(int(h), (flat[:E * C].reshape(E, C), flat[E * C:]), names, str(z["name_%d" % h]) if "name_%d" % h in z.files else None)
+        return bank
+
+    @classmethod
+    def from_fits(cls, heads, names=None, device=None):
+        """a bank of exactly these heads (HeadFit or (kernel, bias)), head i in slot i; names: per head its class names, or None"""
+        heads = list(heads)
+        if not heads:
+            raise ValueError("no heads")
+        if names is not None and len(names) != len(heads):
+            raise ValueError("%d name lists for %d heads" % (len(names), len(heads)))
+        E = heads[0].embed_size if isinstance(heads[0], HeadFit) else int(np.asarray(heads[0][0]).shape[0])
+        Cs = [h.num_classes if isinstance(h, HeadFit) else int(np.asarray(h[0]).shape[1]) for h in heads]
+        if device is None and isinstance(heads[0], HeadFit):
+            device = heads[0].weights.device
+        bank = cls(E, len(heads), max(Cs), device)
+        for i, h in enumerate(heads):
+            bank.set(i, h, None if names is None else names[i])
+        return bank
+
+
+def _on(device):
+    """the device's context: torch.cuda.device for a GPU, nothing for the host"""
+    import contextlib
+    import torch
+    return torch.cuda.device(device) if device.type == "cuda" else contextlib.nullcontext()
+
+
+def _check_emb_bank(emb, bank):
+    N, E = int(emb.shape[0]) if emb.dim() == 2 else -1, int(emb.shape[-1])
+    import torch
+    if emb.dim() != 2 or emb.dtype != torch.float32 or not emb.is_contiguous() or not emb.is_cuda:
+        raise ValueError("emb must be a contiguous float32 CUDA tensor of shape (N, E)")
+    if E != bank.embed_size:
+        raise ValueError("emb is %d wide, the bank's heads read %d-wide embeddings" % (E, bank.embed_size))
+    return N, E
+
+
+def _index_tensor(a, device):
+    import torch
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu":
+            raise ValueError("head ids and row numbers must be integers")
+        a = torch.from_numpy(np.ascontiguousarray(a.reshape(-1).astype(np.int32)))
+    return a.reshape(-1).to(torch.int32).to(device).contiguous()
+
+
+def score_heads(emb, y, bank_or_heads, rows_per_head):
+    """Every head on its own rows in ONE kws_heads_apply launch: head i (of a HeadBank, or of a list of HeadFit / (kernel, bias) that is
+    banked here) is scored on emb[rows_per_head[i]] against y.  -> (accuracy, loss), two lists of floats: the share of rows whose
+    arg-max (pred, an exact tie to the lower class) is the label, counted in integers, and the mean of -log p_y over the rows, p the
+    kernel's float32 probabilities, summed in float64 by torch.  A head without rows gives NaN twice.  Labels are checked on the host
+    (ValueError outside the head's classes)."""
+    import torch
+    bank = bank_or_heads if isinstance(bank_or_heads, HeadBank) else HeadBank.from_fits(bank_or_heads, device=emb.device)
+    N, E = _check_emb_bank(emb, bank)
+    yh = _host_labels(y, N)
+    if len(rows_per_head) > bank.capacity:
+        raise ValueError("%d row sets for a bank of %d heads" % (len(rows_per_head), bank.capacity))
+    rows = [_check_order(r, N) for r in rows_per_head]
+    for h, r in enumerate(rows):
+        if r.size:
+            if bank.classes[h] == 0:
+                raise ValueError("head %d is empty" % h)
+            _check_labels(yh, int(bank.classes[h]), 0, r)
+    sizes = np.array([r.size for r in rows], np.int64)
+    R = int(sizes.sum())
+    nan = float("nan")
+    if R == 0:
+        return [nan] * len(rows), [nan] * len(rows)
+    dev = emb.device
+    rows_d = torch.from_numpy(np.concatenate(rows)).to(dev)
+    key = torch.repeat_interleave(torch.arange(len(rows), dtype=torch.int32, device=dev), torch.from_numpy(sizes).to(dev), output_size=R)
+    yt = torch.from_numpy(yh[np.concatenate(rows)]).to(dev)
+    probs, pred = bank.launch(emb, R, key, rows=rows_d, want=("probs", "pred"))
+    hit = torch.cumsum((pred.long() == yt).long(), 0)
+    nll = torch.cumsum(-torch.log(probs.gather(1, yt.reshape(-1, 1)).reshape(-1).double()), 0)
+    ends = torch.from_numpy(np.cumsum(sizes) - 1).to(dev).clamp_(min=0)
+    hit_h, nll_h = hit.index_select(0, ends).cpu().numpy(), nll.index_select(0, ends).cpu().numpy()       # the one synchronisation
+    acc, loss = [], []
+    prev_hit, prev_nll = 0, 0.0
+    for h, n in enumerate(sizes):
+        if n == 0:
+            acc.append(nan)
+            loss.append(nan)
+            continue
+        acc.append(float(int(hit_h[h]) - prev_hit) / float(n))
+        loss.append(float(nll_h[h] - prev_nll) / float(n))
+        prev_hit, prev_nll = int(hit_h[h]), float(nll_h[h])
+    return acc, loss

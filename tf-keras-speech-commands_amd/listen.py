@@ -10,7 +10,8 @@ recordings once and evaluates the detector at a whole grid of (sensitivity, trig
 for whole files at once in --scan / --sweep through `Listener.collect_wav` (kws_amd.stream.collect / peaks), which with labels
 tells false alarms from hits and can add the near misses that never fired (--mine_peaks).  `Listener.sweep_synth` (CLI: --sweep
 --synth_from DATASET_DIR) needs no labelled recordings: it synthesizes them on the device from a dataset's one-second clips and a
-folder of background noise (kws_amd.synth) and sweeps those.
+folder of background noise (kws_amd.synth) and sweeps those.  `--head_bank BANK.npz` (with --scan / --sweep) gives every recording a
+keyword set of its own on the one backbone: a kws_amd.transfer.HeadBank, and `--head_map FILE` naming each recording's head.
 
 Differences from listen.py: checkpoints are the `.npz` files classifier.model writes (no h5/pb/tflite/onnx/mnn
 back ends); there is no PyAudio in this image, so `run_microphone` raises and `run_wav` does not play the audio while it
@@ -55,6 +56,8 @@ default_config = {                                     # listen.py:31-40
     "scan": False,
     "scan_tile": 4096,
     "resample": False,
+    "head_bank": None,
+    "head_map": None,
 }
 
 
@@ -83,10 +86,36 @@ def parse_trigger_levels(text):
     return vals
 
 
+def parse_head_map(path, bank):
+    """The file of --head_map: text, one recording per line, `wav_name head_name`; '#' starts a comment.  head_name is a name the bank
+    holds (HeadBank.names) or a head id.  -> {wav_name: head id}; a wav it does not mention listens with head 0."""
+    out = {}
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            fields = line.split('#', 1)[0].split()
+            if not fields:
+                continue
+            if len(fields) != 2:
+                raise ValueError("%s:%d: expected `wav_name head_name`" % (path, no))
+            name, head = fields
+            if head in bank.names:
+                h = bank.names.index(head)
+            elif head.isdigit() and int(head) < bank.capacity:
+                h = int(head)
+            else:
+                raise ValueError("%s:%d: the bank has no head %r" % (path, no, head))
+            if bank.classes[h] == 0:
+                raise ValueError("%s:%d: head %r is empty" % (path, no, head))
+            out[os.path.basename(name)] = h
+    return out
+
+
 def parse_labels(path, class_names, sample_rate):
     """The labels file of --sweep: text, one event per line, `wav_name class_name start_seconds end_seconds`; '#' starts a
-    comment.  -> {wav_name: [(class_index, start_sample, end_sample), ...]}; a wav it does not mention has no events."""
+    comment.  -> {wav_name: [(class_index, start_sample, end_sample), ...]}; a wav it does not mention has no events.
+    class_names: the list, or a function of the wav's name that gives its list (a head per recording)."""
     out = {}
+    names_of = class_names if callable(class_names) else (lambda wav_name: class_names)
     with open(path) as f:
         for no, line in enumerate(f, 1):
             fields = line.split('#', 1)[0].split()
@@ -95,6 +124,7 @@ def parse_labels(path, class_names, sample_rate):
             if len(fields) != 4:
                 raise ValueError("%s:%d: expected `wav_name class_name start_seconds end_seconds`" % (path, no))
             name, cls, start, end = fields
+            class_names = names_of(os.path.basename(name))
             if cls not in class_names:
                 raise ValueError("%s:%d: unknown class name %r" % (path, no, cls))
             a, b = int(round(float(start) * sample_rate)), int(round(float(end) * sample_rate))
@@ -139,6 +169,15 @@ class Listener(object):
         self.model = kwargs.get("model") or get_model(self.model_type, len(self.class_names), weights_path=self.model_path or None,
                                                       num_layers=self.rnn_layers)
         self.threshold_decoder = ThresholdDecoder(self.pr.threshold_config, self.pr.threshold_center)
+        # --head_bank: a keyword set per recording for scan_wav / sweep_wav / collect_wav; run_wav keeps the model's own head
+        self.heads, self.head_of = None, {}
+        if getattr(self, "head_bank", None):
+            from kws_amd.transfer import HeadBank
+            if self.quantized is not None:
+                raise ValueError("--head_bank does not go with --quantized_path: the int8 forwards end in their own head")
+            self.heads = HeadBank.load(self.head_bank)
+            if getattr(self, "head_map", None):
+                self.head_of = parse_head_map(self.head_map, self.heads)
         self._sb = self.batch(1)
         self.detector = self._sb                       # detector state lives in the stream batch (device)
         self.activations = []
@@ -147,6 +186,12 @@ class Listener(object):
         self._pcm_ring = np.zeros(self.pr.buffer_samples, dtype=np.int16)
         self.session_id, self.record_num = '%09d' % randint(0, 999999999), 0
         self.saved_paths = []
+
+    def names_for(self, wav_path):
+        """the class names of a recording: its head's in the bank (where the bank keeps names), else the listener's"""
+        if self.heads is None:
+            return self.class_names
+        return self.heads.class_names[self.head_of.get(os.path.basename(wav_path), 0)] or self.class_names
 
     def batch(self, n_streams):
         """A StreamBatch of n lock-stepped streams sharing this listener's model, decoder and settings."""
@@ -269,9 +314,11 @@ class Listener(object):
         rates are converted on the device first; the counts, like everything the scan returns, are then in converted samples."""
         read = [self._read_wav(p, with_rate=True) for p in files]
         pcm, rates = [a for a, _ in read], [r for _, r in read]
+        rec_heads = None if self.heads is None else [self.head_of.get(os.path.basename(p), 0) for p in files]
         res = scan(self.pr, self.model._device(), pcm, chunk_size=self.chunk_size, class_names=self.class_names,
                    sensitivity=self.sensitivity, trigger_level=self.trigger_level, decoder=self.threshold_decoder,
-                   quantized=self.quantized, tile=self.scan_tile, keep_audio=keep_audio, sample_rates=rates)
+                   quantized=self.quantized, tile=self.scan_tile, keep_audio=keep_audio, sample_rates=rates, heads=self.heads,
+                   recording_heads=rec_heads)
         if all(r == self.pr.sample_rate for r in rates):
             return res, [int(a.size) for a in pcm]
         from kws_amd.rate import bank_for
@@ -290,7 +337,9 @@ class Listener(object):
         res, lens = self.last_scan = self._scan_files(files, keep_audio=bool(self.save_dir))
         index, score, fired = res.index.cpu().numpy(), res.score.cpu().numpy(), res.fired.cpu().numpy()
         out, self.scan_times = [], []
+        own_names = self.class_names
         for r, n in enumerate(res.n_chunks):
+            self.class_names = self.names_for(files[r])            # what on_prediction / on_activation print: the recording's head's
             rows = [(int(index[r, k]), float(score[r, k]), bool(fired[r, k])) for k in range(n)]
             times = []
             for k, (i, sc, f) in enumerate(rows):
@@ -301,6 +350,7 @@ class Listener(object):
                     self.on_activation(i, play_activate=False, save=False)
             out.append(rows)
             self.scan_times.append(times)
+        self.class_names = own_names
         return out[0] if single else out
 
     def sweep_wav(self, paths, labels, sensitivities, trigger_levels, tolerance_s=None):
@@ -311,7 +361,7 @@ class Listener(object):
         Returns the SweepResult, its `seconds` set to the files' durations; `self.sweep_scan` keeps the scan."""
         files = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
         if isinstance(labels, (str, bytes, os.PathLike)):
-            labels = parse_labels(labels, self.class_names, self.pr.sample_rate)
+            labels = parse_labels(labels, self.names_for, self.pr.sample_rate)
         res, lens = self._scan_files(files, keep_audio=bool(self.save_dir))
         events = None if labels is None else [labels.get(os.path.basename(p), []) for p in files]
         tol = None if tolerance_s is None else int(round(tolerance_s * self.pr.sample_rate))
@@ -450,7 +500,7 @@ class Listener(object):
                 hits = [i for i, _, f in rows if f]
                 print('%s: %d chunks, %d activations' % (path, len(rows), len(hits)))
                 for t, i in zip(times, hits):
-                    print('  %9.3f s  %s' % (t, self.class_names[i]))
+                    print('  %9.3f s  %s' % (t, self.names_for(path)[i]))
             if self.save_dir:
                 self.collect_wav(files, getattr(self, 'labels_path', None), scan=self.last_scan, **self._collect_options())
                 print('saved %d clips under %s' % (len(self.collected_paths), self.save_dir))
@@ -480,6 +530,12 @@ def parse_args(argv=None):
     parser.add_argument('--resample', action='store_true',
                         help='accept mono 16-bit wavs at other sample rates (a quarter to four times the model\'s): they are converted on the '
                              'device first, and chunks, times and labels then count converted samples')
+    parser.add_argument('--head_bank', type=str, default=None,
+                        help='--scan / --sweep: a kws_amd.transfer.HeadBank (.npz, HeadBank.save); every recording is scored by the '
+                             'backbone of --model_path and its own head of the bank')
+    parser.add_argument('--head_map', type=str, default=None,
+                        help='--head_bank: text file, one line per recording: wav_name head_name (a name of the bank or a head id; '
+                             'recordings it does not mention use head 0)')
     parser.add_argument('--sweep', action='store_true',
                         help='scan the recording(s) once and evaluate the detector at every (sensitivity, trigger level) of a grid')
     parser.add_argument('--labels_path', type=str, default=None,
@@ -520,6 +576,12 @@ def parse_args(argv=None):
         parser.error('one of --input_wav and --synth_from is required')
     if args.synth_from and not args.sweep:
         parser.error('--synth_from goes with --sweep')
+    if args.head_bank and not (args.scan or args.sweep):
+        parser.error('--head_bank goes with --scan or --sweep')
+    if args.head_bank and (args.quantized_path or args.synth_from):
+        parser.error('--head_bank goes with neither --quantized_path nor --synth_from')
+    if args.head_map and not args.head_bank:
+        parser.error('--head_map goes with --head_bank')
     if args.synth_from:
         try:
             parse_gap(args.synth_gap_s)
